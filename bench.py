@@ -11,6 +11,12 @@ cotangent on (vertices, existence_probabilities, edge_probs) [+ the RCCL
 gradient all-reduce when N > 1].  Inputs and parameters are resident in HBM
 before the timed region; no optimizer step, no Hungarian loss.
 Rank 0 prints ONE JSON line.
+
+    python bench.py --gpus 1 --steps K --warmup W --dump-outputs bench_outputs/<tag>
+
+also writes what the last timed step computed (rank 0), as float32 <dir>/<name>.npy: the model outputs
+(out.<key>.npy) and every parameter gradient (grad.<parameter name>.npy; tensors above DUMP_SAMPLE
+elements as a fixed, seeded sample of DUMP_SAMPLE flat elements, in ascending index order).
 """
 import argparse
 import json
@@ -37,6 +43,7 @@ BF16_MFMA_PEAK_TFLOPS = 2500.0      # dense bf16 MFMA (never the 2:1-sparsity fi
 HBM_PEAK_GBS = 8000.0               # HBM3E spec (6.3 TB/s measured on a float4 copy, same guide)
 PROFILE_TAG = "r03"                 # rocprofv3 summaries of this round's build under profiles/
 SEED = 1234
+DUMP_SAMPLE = 1 << 16               # --dump-outputs: largest gradient written whole; larger ones are sampled to this size
 
 
 def algorithmic_flops_per_cloud(N, V, hidden=(512, 1024, 2048, 1024), out=512, din=8):
@@ -138,6 +145,27 @@ class OpTimer:
             o = g["ops"].setdefault(name, [0, 0.0, 0.0])
             o[0] += 1; o[1] += ms; o[2] += by
         return out
+
+
+def dump_outputs(path, out, model):
+    """The last timed step's results as float32 .npy files: outputs whole, gradients whole or sampled (module docstring).
+    The sample indices depend only on the tensor's name and size, so two builds write the same elements."""
+    import zlib
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    arrays = {f"out.{k}": v for k, v in out.items() if torch.is_tensor(v) and v.is_floating_point()}
+    arrays.update({f"grad.{n}": p.grad for n, p in model.named_parameters() if p.grad is not None})
+    total = 0
+    for name, t in arrays.items():
+        a = t.detach().float().cpu().numpy().ravel() if name.startswith("grad.") else t.detach().float().cpu().numpy()
+        if name.startswith("grad.") and a.size > DUMP_SAMPLE:
+            rng = np.random.default_rng([SEED, zlib.crc32(name.encode())])
+            a = a[np.sort(rng.choice(a.size, DUMP_SAMPLE, replace=False))]
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
+        total += a.nbytes
+    if total > 64 << 20:
+        raise SystemExit(f"--dump-outputs wrote {total / 2 ** 20:.1f} MB, over the 64 MB budget")
+    return len(arrays), total
 
 
 def host_cores():
@@ -260,7 +288,11 @@ def main():
     ap.add_argument("--dropout", type=float, default=0.1)
     ap.add_argument("--precision", choices=["fp32", "bf16x3"], default=None,
                     help="arithmetic of the large GEMMs (default: wf3d.config / WF3D_PRECISION = bf16x3)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs and parameter gradients as float32 DIR/<name>.npy (rank 0)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     from wf3d import config
     from wf3d import dist as wd
@@ -293,6 +325,7 @@ def main():
         torch.autograd.backward([out[k] for k in keys], cots)
         if reducer is not None:
             reducer.finish()
+        return out
 
     def fence():
         if world > 1:
@@ -314,8 +347,10 @@ def main():
     for i in range(args.steps):
         timer.active = (i % 4 == 0) and not args.no_op_timers
         timer.steps_sampled += int(timer.active)
-        step()
+        out = step()
         marks[i + 1].record()
+        if i + 1 < args.steps:
+            out = None                        # only the last step's outputs outlive their step
     timer.active = False
     fence()
     dt = time.perf_counter() - t0
@@ -364,6 +399,9 @@ def main():
                             "ops": {k: {"launches_per_step": v[0] / ns, "ms_per_step": v[1] / ns,
                                         "GB/s": v[2] / (v[1] * 1e-3) / 1e9} for k, v in r["ops"].items()}}
         roof["hbm"] = hbm
+        if args.dump_outputs:
+            n_arrays, n_bytes = dump_outputs(args.dump_outputs, out, model)     # its gradients are still on the parameters
+        out = None
         res = {
             "metric": "point-clouds/sec fwd+bwd",
             "value": B * world * args.steps / dt,
@@ -385,6 +423,8 @@ def main():
                        if split else "fp32 MFMA everywhere"},
             "roofline": roof,
         }
+        if args.dump_outputs:
+            res["dump_outputs"] = {"dir": args.dump_outputs, "arrays": n_arrays, "bytes": n_bytes}
         if world > 1:
             ex = sorted(reducer.exposed_ms())
             res["rccl_ranks"] = torch.distributed.get_world_size()

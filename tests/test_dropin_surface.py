@@ -2,9 +2,6 @@
 signatures, state_dict keys/shapes, lazy parameter, edge index order, and that
 nothing computes on the CPU (no fallback)."""
 import inspect
-import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -12,6 +9,7 @@ import torch
 
 import helpers as H
 from helpers import oracle
+from refsummary import digest
 
 
 def test_signatures_and_state_dict_match_reference_table():
@@ -56,41 +54,19 @@ def test_no_cpu_fallback():
         m(torch.zeros(1, 16, 8), torch.tensor([2]))
 
 
-REF = os.environ.get("WF3D_REFERENCE", "/root/reference")
-INIT_SCRIPT = r"""
-import sys, importlib.util, types
-sys.dont_write_bytecode = True
-import torch
-def load_pkg(root, alias):
-    # import <root>/models/*.py under a private package name so both trees coexist
-    pkg = types.ModuleType(alias); pkg.__path__ = [root + "/models"]; sys.modules[alias] = pkg
-    mods = {}
-    for n in ("EdgePredictor", "PointNetEncoder", "VertexPredictor", "PointCloudToWireframe"):
-        src = open(f"{root}/models/{n}.py").read().replace("from models.", f"from {alias}.")
-        m = types.ModuleType(f"{alias}.{n}"); sys.modules[f"{alias}.{n}"] = m
-        exec(compile(src, f"{root}/models/{n}.py", "exec"), m.__dict__)
-        mods[n] = m
-    return mods["PointCloudToWireframe"].PointCloudToWireframe
-sys.path.insert(0, %(pkg)r)
-Ref = load_pkg(%(ref)r, "refmodels")
-Ours = load_pkg(%(pkg)r, "ourmodels")
-torch.manual_seed(1234); a = Ref(8, 12)
-torch.manual_seed(1234); b = Ours(8, 12)
-sa, sb = a.state_dict(), b.state_dict()
-assert list(sa) == list(sb), "state_dict key order differs"
-for k in sa:
-    assert torch.equal(sa[k], sb[k]), k
-assert [n for n, _ in a.named_parameters()] == [n for n, _ in b.named_parameters()]
-print("INIT_IDENTICAL")
-"""
-
-
-@pytest.mark.skipif(not os.path.isdir(os.path.join(REF, "models")), reason="reference not present")
 def test_same_seed_gives_reference_initialisation():
-    r = subprocess.run([sys.executable, "-c", INIT_SCRIPT % {"ref": REF, "pkg": H.PKG}],
-                       capture_output=True, text=True, timeout=600,
-                       env={**os.environ, "PYTHONDONTWRITEBYTECODE": "1"})
-    assert "INIT_IDENTICAL" in r.stdout, r.stdout[-2000:] + r.stderr[-3000:]
+    """Under the same seed the drop-in PointCloudToWireframe(8, 12) draws the reference's parameters bit for bit, in the
+    reference's state_dict and parameter order (tests/golden/refcheck_init.npz, recorded from the reference)."""
+    from models.PointCloudToWireframe import PointCloudToWireframe
+    gold = H.load_golden("refcheck_init")
+    with torch.random.fork_rng(devices=[]):
+        torch.manual_seed(1234)
+        m = PointCloudToWireframe(8, 12)
+    sd = m.state_dict()
+    assert list(sd) == list(gold["state_dict.keys"]), "state_dict key order differs"
+    for k, want in zip(sd, gold["state_dict.digests"]):
+        assert digest(sd[k]) == want, k
+    assert [n for n, _ in m.named_parameters()] == list(gold["params.names"])
 
 
 def test_edge_index_lists_are_read_only_and_equal_to_plain_lists():

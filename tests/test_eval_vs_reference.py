@@ -1,77 +1,49 @@
-"""Direct check of the drop-in eval.ap_calculator against the reference's own file on random and degenerate batches;
-runs only where /root/reference exists (the build container).  On the GPU box the committed fixture (tests/golden/eval.npz)
-stands in."""
+"""The drop-in eval.ap_calculator against the reference's own file on random and degenerate batches, against results
+recorded from the reference (tests/golden/refcheck_eval.npz, tests/golden/make_golden_refcheck.py)."""
+import contextlib
+import copy
+import importlib.util
+import io
 import os
-import subprocess
-import sys
 
-import pytest
-
-REF = os.environ.get("WF3D_REFERENCE", "/root/reference")
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
-
-SCRIPT = r"""
-import sys, importlib.util, io, contextlib, copy
-sys.dont_write_bytecode = True
 import numpy as np
+
+import helpers as H
+import refcases
+
 
 def load(name, path):
     spec = importlib.util.spec_from_file_location(name, path)
-    m = importlib.util.module_from_spec(spec); spec.loader.exec_module(m); return m
+    m = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(m)
+    return m
 
-ref = load("ref_ap", %(ref)r + "/eval/ap_calculator.py")
-mine = load("my_ap", %(root)r + "/wireframe-3d-prediction_amd/eval/ap_calculator.py")
-KEYS = ("tp_corners", "tp_fp_corners", "tp_fn_corners", "distance", "tp_edges", "wed", "tp_fp_edges", "tp_fn_edges")
 
-def z_first(v, e):
-    if len(e) == 0:
-        return np.empty((0, 2, 3), dtype=np.float32)
-    ev = np.stack((v[e[:, 0]], v[e[:, 1]]), axis=1)
-    return ev[np.arange(len(ev))[:, None], np.flip(np.argsort(ev[:, :, -1]), axis=1)].astype(np.float32)
-
-def sample(rng, nv_p, ne_p, nv_g, ne_g, noise):
-    gv = rng.normal(0, 2, (nv_g, 3)).astype(np.float32)
-    pairs = np.array([(i, j) for i in range(nv_g) for j in range(i + 1, nv_g)], dtype=np.int64).reshape(-1, 2)
-    ge = pairs[rng.permutation(len(pairs))[:ne_g]] if len(pairs) else pairs
-    pv = (np.resize(gv, (nv_p, 3)) + rng.normal(0, noise, (nv_p, 3))).astype(np.float32)
-    pp = np.array([(i, j) for i in range(nv_p) for j in range(i + 1, nv_p)], dtype=np.int64).reshape(-1, 2)
-    pe = pp[rng.permutation(len(pp))[:ne_p]] if len(pp) else pp
-    return {"predicted_vertices": [pv], "predicted_edges": [pe], "pred_edges_vertices": [z_first(pv, pe)],
-            "wf_vertices": [gv], "wf_edges": [ge], "wf_edges_vertices": [z_first(gv, ge)]}
-
-rng = np.random.RandomState(3)
-cases = [(6, 5, 6, 5, 0.01), (6, 0, 6, 5, 0.01), (9, 12, 5, 4, 0.3), (3, 3, 8, 10, 0.05), (12, 30, 12, 20, 0.02), (2, 1, 2, 1, 0.0),
-         (7, 7, 7, 7, 2.0), (5, 10, 5, 1, 0.01)]
-computed = 0
-for thr in (0.1, 1.0):
-    a, b = ref.APCalculator(distance_thresh=thr), mine.APCalculator(distance_thresh=thr)
-    for c in cases:
-        batch = sample(rng, *c)
-        errs = []
-        for calc in (a, b):
+def test_ap_calculator_equals_the_reference_on_random_and_degenerate_batches():
+    gold = H.load_golden("refcheck_eval")
+    mine = load("my_ap", os.path.join(H.PKG, "eval", "ap_calculator.py"))
+    rng = np.random.RandomState(3)
+    computed = 0
+    for t, thr in enumerate(refcases.EVAL_THRESHOLDS):
+        calc = mine.APCalculator(distance_thresh=thr)
+        for c, case in enumerate(refcases.EVAL_CASES):
+            batch = refcases.eval_sample(rng, *case)
+            assert refcases.eval_batch_digest(batch) == gold[f"t{t}.c{c}.batch"], (thr, case)
             try:
                 with contextlib.redirect_stdout(io.StringIO()):
-                    calc.compute_metrics(copy.deepcopy(batch))          # both overwrite matched predicted edges in place
-                errs.append(None)
-            except Exception as e:                                      # no edge within the radius: numpy refuses min() of nothing, in both
-                errs.append(type(e).__name__)
-        assert errs[0] == errs[1], (thr, c, errs)
-        computed += errs[0] is None
-        for k in KEYS:
-            assert np.isclose(float(a.ap_dict[k]), float(b.ap_dict[k]), rtol=1e-9, atol=1e-9), (thr, c, k, a.ap_dict[k], b.ap_dict[k])
-    with contextlib.redirect_stdout(io.StringIO()):
-        a.output_accuracy(); b.output_accuracy()
-    for k in ("average_corner_offset", "average_wed", "corners_precision", "corners_recall", "corners_f1", "edges_precision", "edges_recall", "edges_f1"):
-        assert np.isclose(float(a.ap_dict[k]), float(b.ap_dict[k]), rtol=1e-9, atol=1e-12), (thr, k)
-p, t = rng.normal(0, 3, (40, 2, 3)), rng.normal(0, 3, (9, 2, 3))
-assert np.allclose(ref.hausdorff_distance_line(p, t), mine.hausdorff_distance_line(p, t), rtol=1e-12, atol=1e-12)
-assert computed >= 8, computed            # most cases go all the way through
-print("AP_CALCULATOR_MATCHES_REFERENCE", computed)
-"""
-
-
-@pytest.mark.skipif(not os.path.isfile(os.path.join(REF, "eval", "ap_calculator.py")), reason="reference not present")
-def test_ap_calculator_equals_the_reference_on_random_and_degenerate_batches():
-    out = subprocess.run([sys.executable, "-c", SCRIPT % {"ref": REF, "root": ROOT}], capture_output=True, text=True, timeout=600)
-    assert out.returncode == 0 and "AP_CALCULATOR_MATCHES_REFERENCE" in out.stdout, out.stderr[-3000:] + out.stdout[-1000:]
+                    calc.compute_metrics(copy.deepcopy(batch))          # it overwrites matched predicted edges in place
+                err = ""
+            except Exception as e:                                      # no edge within the radius: numpy refuses min() of nothing
+                err = type(e).__name__
+            assert err == str(gold[f"t{t}.c{c}.error"]), (thr, case, err)
+            computed += err == ""
+            for k, want in zip(refcases.EVAL_KEYS, gold[f"t{t}.c{c}.ap"]):
+                assert np.isclose(want, float(calc.ap_dict[k]), rtol=1e-9, atol=1e-9), (thr, case, k, want, calc.ap_dict[k])
+        with contextlib.redirect_stdout(io.StringIO()):
+            calc.output_accuracy()
+        for k, want in zip(refcases.EVAL_ACCURACY_KEYS, gold[f"t{t}.accuracy"]):
+            assert np.isclose(want, float(calc.ap_dict[k]), rtol=1e-9, atol=1e-12), (thr, k)
+    p, t = rng.normal(0, 3, (40, 2, 3)), rng.normal(0, 3, (9, 2, 3))
+    assert [refcases.digest(p), refcases.digest(t)] == list(gold["hausdorff.inputs"])
+    assert np.allclose(gold["hausdorff"], mine.hausdorff_distance_line(p, t), rtol=1e-12, atol=1e-12)
+    assert computed >= 8, computed            # most cases go all the way through
