@@ -126,6 +126,15 @@ int wf3d_gemm_split_tn_ok(int Mo, int No, int K, int lda, int ldb);
 size_t wf3d_gemm_split_tn_ws_bytes(int Mo, int No, int K);
 int wf3d_gemm_split_tn(const void* A_sx8, const void* B_sx8, float* C, int Mo, int No, int K, int lda, int ldb,
                        int ldc, int accumulate, void* ws, size_t ws_bytes, void* stream);
+/* bf16 arithmetic (opt-in precision mode "bf16"): the same two products, one bf16 MFMA per product on the
+ * hi planes of the sx8 operands (hi = bf16 round-to-nearest of v; the lo planes are not read), fp32 accumulation.
+ * Same signatures, argument checks, error codes, accepted shapes / layouts and kernel selection as
+ * wf3d_gemm_split / wf3d_gemm_split_tn; the workspace is sized by wf3d_gemm_split_ws_bytes /
+ * wf3d_gemm_split_tn_ws_bytes. */
+int wf3d_gemm_bf16(const void* A_sx8, const void* B_sx8, float* C, const float* bias, int M, int N, int K,
+                   int lda, int ldb, int ldc, int accumulate, void* ws, size_t ws_bytes, void* stream);
+int wf3d_gemm_bf16_tn(const void* A_sx8, const void* B_sx8, float* C, int Mo, int No, int K, int lda, int ldb,
+                      int ldc, int accumulate, void* ws, size_t ws_bytes, void* stream);
 /* out_sx8[r, c] = split(in[r*row_stride + c*col_stride])  (col_stride 1: convert;
  * row_stride 1: transpose-convert, used for W^T) */
 int wf3d_split_rows(const float* in, long row_stride, long col_stride, int R, int C, void* out_sx8, void* stream);

@@ -216,7 +216,7 @@ __device__ __forceinline__ void static_steps(F&& f) {
     }
 }
 
-template <int WAVES_M, int WAVES_N, int TM, int TN, bool A_KC, bool B_KC, int ACT, bool PRO, bool FAST, bool SPLIT, bool X3, int R>
+template <int WAVES_M, int WAVES_N, int TM, int TN, bool A_KC, bool B_KC, int ACT, bool PRO, bool FAST, bool SPLIT, bool X3, int R, int NP>
 __device__ __forceinline__ void gemm_body(const GemmParams& p, float* smem, int m0, int n0, int kt0, int kt1) {
     constexpr int BM = WAVES_M * TM * 32, BN = WAVES_N * TN * 32;
     constexpr int A_SZ = (A_KC || X3) ? BM * LDK : BK * BM;
@@ -349,6 +349,7 @@ __device__ __forceinline__ void gemm_body(const GemmParams& p, float* smem, int 
         if (SPLIT || X3) {
             // bf16x3 split precision: each 32-B group of a staged row holds [8 x hi | 8 x lo] bf16 of 8
             // consecutive k; a*b ~= ah*bh + ah*bl + al*bh (fp32 accumulate), v_mfma_f32_32x32x16_bf16.
+            // NP = 1 (bf16 mode, SPLIT only): a*b ~= ah*bh, the lo halves are not read.
 #pragma unroll
             for (int s2 = 0; s2 < BK / 16; ++s2) {
                 f32x4 ah[TM], al[TM], bh[TN], bl[TN];
@@ -362,7 +363,7 @@ __device__ __forceinline__ void gemm_body(const GemmParams& p, float* smem, int 
                     } else {
                         const float* pr = As + ((wm * TM + i) * 32 + l31) * LDK + (2 * s2 + h) * 8;
                         ah[i] = *reinterpret_cast<const f32x4*>(pr);
-                        al[i] = *reinterpret_cast<const f32x4*>(pr + 4);
+                        if (NP == 3) al[i] = *reinterpret_cast<const f32x4*>(pr + 4);
                     }
                 }
 #pragma unroll
@@ -375,15 +376,17 @@ __device__ __forceinline__ void gemm_body(const GemmParams& p, float* smem, int 
                     } else {
                         const float* pr = Bs + ((wn * TN + j) * 32 + l31) * LDK + (2 * s2 + h) * 8;
                         bh[j] = *reinterpret_cast<const f32x4*>(pr);
-                        bl[j] = *reinterpret_cast<const f32x4*>(pr + 4);
+                        if (NP == 3) bl[j] = *reinterpret_cast<const f32x4*>(pr + 4);
                     }
                 }
 #pragma unroll
                 for (int i = 0; i < TM; ++i)
 #pragma unroll
                     for (int j = 0; j < TN; ++j) {
-                        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, al[i]), __builtin_bit_cast(bf16x8, bh[j]), acc[i][j], 0, 0, 0);
-                        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, ah[i]), __builtin_bit_cast(bf16x8, bl[j]), acc[i][j], 0, 0, 0);
+                        if (NP == 3) {
+                            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, al[i]), __builtin_bit_cast(bf16x8, bh[j]), acc[i][j], 0, 0, 0);
+                            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, ah[i]), __builtin_bit_cast(bf16x8, bl[j]), acc[i][j], 0, 0, 0);
+                        }
                         acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, ah[i]), __builtin_bit_cast(bf16x8, bh[j]), acc[i][j], 0, 0, 0);
                     }
             }
@@ -484,8 +487,9 @@ __device__ __forceinline__ void gemm_body(const GemmParams& p, float* smem, int 
     }
 }
 
-template <int WAVES_M, int WAVES_N, int TM, int TN, bool A_KC, bool B_KC, int ACT, bool PRO, bool SPLIT = false, bool X3 = false>
+template <int WAVES_M, int WAVES_N, int TM, int TN, bool A_KC, bool B_KC, int ACT, bool PRO, bool SPLIT = false, bool X3 = false, int NP = 3>
 __global__ __launch_bounds__(256, 2) void gemm_kernel(const GemmParams p) {
+    static_assert(NP == 3 || (NP == 1 && SPLIT && !X3), "one-product form: sx8 operands only");
     constexpr int BM = WAVES_M * TM * 32, BN = WAVES_N * TN * 32;
     constexpr int A_SZ = (A_KC || X3) ? BM * LDK : BK * BM;
     constexpr int B_SZ = (B_KC || X3) ? BN * LDK : BK * BN;
@@ -510,8 +514,8 @@ __global__ __launch_bounds__(256, 2) void gemm_kernel(const GemmParams p) {
     // FAST: every staged tile of this workgroup lies fully inside A and B and is
     // 16-B loadable -> branch-free staging (block-uniform choice)
     const bool fast = p.vecA && p.vecB && p.vecP && (m0 + BM <= p.M) && (n0 + BN <= p.N) && (kt1 * BK <= p.K);
-    if (fast) gemm_body<WAVES_M, WAVES_N, TM, TN, A_KC, B_KC, ACT, PRO, true, SPLIT, X3, R>(p, smem, m0, n0, kt0, kt1);
-    else      gemm_body<WAVES_M, WAVES_N, TM, TN, A_KC, B_KC, ACT, PRO, false, SPLIT, X3, R>(p, smem, m0, n0, kt0, kt1);
+    if (fast) gemm_body<WAVES_M, WAVES_N, TM, TN, A_KC, B_KC, ACT, PRO, true, SPLIT, X3, R, NP>(p, smem, m0, n0, kt0, kt1);
+    else      gemm_body<WAVES_M, WAVES_N, TM, TN, A_KC, B_KC, ACT, PRO, false, SPLIT, X3, R, NP>(p, smem, m0, n0, kt0, kt1);
 }
 
 // split-K combine: deterministic slab sum + epilogue terms
@@ -737,20 +741,23 @@ extern "C" size_t wf3d_gemm_split_ws_bytes(int M, int N, int K) {
     return a > b ? a : b;
 }
 
-extern "C" int wf3d_gemm_split(const void* A_sx8, const void* B_sx8, float* C, const float* bias, int M, int N, int K,
-                               int lda, int ldb, int ldc, int accumulate, void* ws, size_t ws_bytes, void* stream) {
-    WF3D_CHECK(M >= 0 && N >= 0 && K > 0, WF3D_ERR_ARG, "wf3d_gemm_split: bad dims");
+namespace {
+// products: 3 = bf16x3 (wf3d_gemm_split), 1 = plain bf16 on the hi planes (wf3d_gemm_bf16).  Same checks, same kernel
+// choice, same workspace either way.
+int gemm_split_impl(const char* fn, int products, const void* A_sx8, const void* B_sx8, float* C, const float* bias, int M,
+                    int N, int K, int lda, int ldb, int ldc, int accumulate, void* ws, size_t ws_bytes, void* stream) {
+    WF3D_CHECK(M >= 0 && N >= 0 && K > 0, WF3D_ERR_ARG, "%s: bad dims", fn);
     if (M == 0 || N == 0) return WF3D_OK;
-    WF3D_CHECK(A_sx8 && B_sx8 && C, WF3D_ERR_ARG, "wf3d_gemm_split: null operand");
+    WF3D_CHECK(A_sx8 && B_sx8 && C, WF3D_ERR_ARG, "%s: null operand", fn);
     WF3D_CHECK(K % 8 == 0 && lda % 8 == 0 && ldb % 8 == 0, WF3D_ERR_UNSUPPORTED,
-               "wf3d_gemm_split: K, lda, ldb must be multiples of 8 (sx8 groups)");
-    WF3D_CHECK(lda >= K && ldb >= K && ldc >= N, WF3D_ERR_ARG, "wf3d_gemm_split: leading dimension too small");
-    WF3D_CHECK(((uintptr_t)A_sx8 % 16 == 0) && ((uintptr_t)B_sx8 % 16 == 0), WF3D_ERR_ARG, "wf3d_gemm_split: operands must be 16-byte aligned");
+               "%s: K, lda, ldb must be multiples of 8 (sx8 groups)", fn);
+    WF3D_CHECK(lda >= K && ldb >= K && ldc >= N, WF3D_ERR_ARG, "%s: leading dimension too small", fn);
+    WF3D_CHECK(((uintptr_t)A_sx8 % 16 == 0) && ((uintptr_t)B_sx8 % 16 == 0), WF3D_ERR_ARG, "%s: operands must be 16-byte aligned", fn);
     {
         // LDS-DMA staged kernel for every shape it supports (WF3D_SPLIT_DMA=0 forces the register-staged one)
         static const int use_dma = [] { const char* e = getenv("WF3D_SPLIT_DMA"); return e ? atoi(e) : 1; }();
         if (use_dma && wf3d_gemm_split_dma_ok(M, N, K, lda, ldb))
-            return wf3d_gemm_split_dma(A_sx8, B_sx8, C, bias, M, N, K, lda, ldb, ldc, accumulate, ws, ws_bytes, stream);
+            return wf3d_gemm_split_dma(A_sx8, B_sx8, C, bias, M, N, K, lda, ldb, ldc, accumulate, ws, ws_bytes, stream, products);
     }
     GemmParams p{};
     p.A = (const float*)A_sx8; p.B = (const float*)B_sx8; p.C = C; p.bias = bias;
@@ -765,7 +772,8 @@ extern "C" int wf3d_gemm_split(const void* A_sx8, const void* B_sx8, float* C, c
     p.slab = sp.ksplit > 1 ? (float*)ws : nullptr;
     hipStream_t st = (hipStream_t)stream;
     dim3 grid(p.nbm * p.nbn, 1, p.ksplit);
-    hipLaunchKernelGGL((gemm_kernel<2, 2, 2, 2, true, true, 0, false, true>), grid, dim3(256), 0, st, p);
+    if (products == 1) hipLaunchKernelGGL((gemm_kernel<2, 2, 2, 2, true, true, 0, false, true, false, 1>), grid, dim3(256), 0, st, p);
+    else               hipLaunchKernelGGL((gemm_kernel<2, 2, 2, 2, true, true, 0, false, true>), grid, dim3(256), 0, st, p);
     WF3D_LAUNCH_CHECK();
     if (p.ksplit > 1) {
         const size_t total = (size_t)M * N;
@@ -775,4 +783,16 @@ extern "C" int wf3d_gemm_split(const void* A_sx8, const void* B_sx8, float* C, c
         WF3D_LAUNCH_CHECK();
     }
     return WF3D_OK;
+}
+}  // namespace
+
+extern "C" int wf3d_gemm_split(const void* A_sx8, const void* B_sx8, float* C, const float* bias, int M, int N, int K,
+                               int lda, int ldb, int ldc, int accumulate, void* ws, size_t ws_bytes, void* stream) {
+    return gemm_split_impl("wf3d_gemm_split", 3, A_sx8, B_sx8, C, bias, M, N, K, lda, ldb, ldc, accumulate, ws, ws_bytes, stream);
+}
+
+// bf16 mode: one bf16 MFMA per product on the hi planes of the sx8 operands; workspace: wf3d_gemm_split_ws_bytes
+extern "C" int wf3d_gemm_bf16(const void* A_sx8, const void* B_sx8, float* C, const float* bias, int M, int N, int K,
+                              int lda, int ldb, int ldc, int accumulate, void* ws, size_t ws_bytes, void* stream) {
+    return gemm_split_impl("wf3d_gemm_bf16", 1, A_sx8, B_sx8, C, bias, M, N, K, lda, ldb, ldc, accumulate, ws, ws_bytes, stream);
 }

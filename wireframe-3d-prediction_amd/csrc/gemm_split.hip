@@ -10,7 +10,10 @@
 // §5.4 rule 21): the 16 lanes of every ds_read_b128 group then hit 16 distinct slots.
 // One 16-B chunk is exactly one MFMA fragment (8 consecutive k of one bf16 plane).
 //
-// Every product costs three bf16 MFMAs, acc += al*bh + ah*bl + ah*bh (fp32 accumulate).  Kernels in this file:
+// Every product costs three bf16 MFMAs, acc += al*bh + ah*bl + ah*bh (fp32 accumulate).  Every kernel also exists with
+// a compile-time product count NP = 1 (wf3d_gemm_bf16 / wf3d_gemm_bf16_tn): acc += ah*bh only, a plain bf16 GEMM on the
+// round-to-nearest hi planes of the same sx8 operands — the lo fragments are neither read from LDS nor held in registers,
+// the DMA pieces are re-spread over the shorter MFMA sequence.  Kernels in this file:
 //   gemm_split_x16p_kernel / gemm_split_x16_kernel<false>   forward + dgrad: 256x256x32 tile, v_mfma_f32_16x16x32_bf16,
 //                                                            3 A + 2 B LDS stages (persistent / plain launch)
 //   gemm_split_x16_kernel<true>                              wgrad on reduction-major operands (ds_read_b64_tr_b16)
@@ -75,6 +78,7 @@ constexpr int T3_A = 256 * SBK, T3_B = 128 * SBK, T3_STAGE = T3_A + T3_B;
 
 struct Frag { f32x4 ah[2], al[2], bh[2], bl[2]; };
 
+template <int NP>
 __device__ __forceinline__ void load_frag(Frag& f, const float* As, const float* Bs, int wm, int wn, int l31, int h,
                                           int fsw, int s2) {
     const int phi = ((2 * (2 * s2 + h)) ^ fsw) * 4, plo = phi ^ 4;
@@ -82,27 +86,29 @@ __device__ __forceinline__ void load_frag(Frag& f, const float* As, const float*
     for (int i = 0; i < 2; ++i) {
         const float* pr = As + ((wm * 2 + i) * 32 + l31) * SBK;
         f.ah[i] = *reinterpret_cast<const f32x4*>(pr + phi);
-        f.al[i] = *reinterpret_cast<const f32x4*>(pr + plo);
+        if (NP == 3) f.al[i] = *reinterpret_cast<const f32x4*>(pr + plo);
     }
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
         const float* pr = Bs + ((wn * 2 + j) * 32 + l31) * SBK;
         f.bh[j] = *reinterpret_cast<const f32x4*>(pr + phi);
-        f.bl[j] = *reinterpret_cast<const f32x4*>(pr + plo);
+        if (NP == 3) f.bl[j] = *reinterpret_cast<const f32x4*>(pr + plo);
     }
 }
 
-// 12 MFMAs of one k16 step; DMA pieces P0, P0+1, P0+2 of the slice two ahead are issued one
-// at a time after the 3rd, 6th and 9th MFMA (pieces 0..3 = A rows, 4..5 = B rows).
-template <int P0>
+// 12 MFMAs of one k16 step (NP = 3; 4 with NP = 1); DMA pieces P0, P0+1, P0+2 of the slice two ahead are issued
+// one at a time after the 3rd, 6th and 9th MFMA (NP = 1: after the 1st, 2nd and 3rd) (pieces 0..3 = A rows, 4..5 = B rows).
+template <int P0, int NP>
 __device__ __forceinline__ void mma12(f32x16 (&acc)[2][2], const Frag& f, bool ahead, const float* const (&asrc)[4],
                                       const float* const (&bsrc)[2], int kn, float* dA, float* dB) {
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
-            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, f.al[i]), __builtin_bit_cast(bf16x8, f.bh[j]), acc[i][j], 0, 0, 0);
-            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, f.ah[i]), __builtin_bit_cast(bf16x8, f.bl[j]), acc[i][j], 0, 0, 0);
+            if (NP == 3) {
+                acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, f.al[i]), __builtin_bit_cast(bf16x8, f.bh[j]), acc[i][j], 0, 0, 0);
+                acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, f.ah[i]), __builtin_bit_cast(bf16x8, f.bl[j]), acc[i][j], 0, 0, 0);
+            }
             acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, f.ah[i]), __builtin_bit_cast(bf16x8, f.bh[j]), acc[i][j], 0, 0, 0);
             if (i * 2 + j < 3) {
                 constexpr int dummy = 0; (void)dummy;
@@ -119,6 +125,7 @@ __device__ __forceinline__ void mma12(f32x16 (&acc)[2][2], const Frag& f, bool a
 }
 
 
+template <int NP>
 __global__ __launch_bounds__(512, 2) void gemm_split_dma3_kernel(const SplitParams p) {
     __shared__ __attribute__((aligned(16))) float smem[3 * T3_STAGE];      // 147,456 B
     const int tid = threadIdx.x, lane = tid & 63;
@@ -189,10 +196,10 @@ __global__ __launch_bounds__(512, 2) void gemm_split_dma3_kernel(const SplitPara
         const int kn = (kt + 2) * SBK;
         const float* As = smem + stage * T3_STAGE;
         const float* Bs = As + T3_A;
-        load_frag(X, As, Bs, wm, wn, l31, h, fsw, 0);
-        mma12<0>(acc, X, ahead, asrc, bsrc, kn, dA, dB);
-        load_frag(Y, As, Bs, wm, wn, l31, h, fsw, 1);
-        mma12<3>(acc, Y, ahead, asrc, bsrc, kn, dA, dB);
+        load_frag<NP>(X, As, Bs, wm, wn, l31, h, fsw, 0);
+        mma12<0, NP>(acc, X, ahead, asrc, bsrc, kn, dA, dB);
+        load_frag<NP>(Y, As, Bs, wm, wn, l31, h, fsw, 1);
+        mma12<3, NP>(acc, Y, ahead, asrc, bsrc, kn, dA, dB);
         // retire slice kt+1 (all but the 6 youngest DMA pieces), make sure this wave's LDS reads
         // of slice kt are done (lgkmcnt) before anyone may overwrite the stage, then publish.
         if (ahead) asm volatile("s_waitcnt vmcnt(6) lgkmcnt(0)" ::: "memory");
@@ -249,15 +256,17 @@ __device__ __forceinline__ f32x4 tr_frag(const char* base, int off, int row_byte
     return __builtin_bit_cast(f32x4, __builtin_shufflevector(a, b, 0, 1, 2, 3, 4, 5, 6, 7));
 }
 
-template <int P0>
+template <int P0, int NP>
 __device__ __forceinline__ void mma12_tn(f32x16 (&acc)[2][2], const Frag& f, bool ahead, const float* const (&asrc)[4],
                                          const float* const (&bsrc)[2], size_t ka, size_t kb, float* dA, float* dB) {
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
-            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, f.al[i]), __builtin_bit_cast(bf16x8, f.bh[j]), acc[i][j], 0, 0, 0);
-            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, f.ah[i]), __builtin_bit_cast(bf16x8, f.bl[j]), acc[i][j], 0, 0, 0);
+            if (NP == 3) {
+                acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, f.al[i]), __builtin_bit_cast(bf16x8, f.bh[j]), acc[i][j], 0, 0, 0);
+                acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, f.ah[i]), __builtin_bit_cast(bf16x8, f.bl[j]), acc[i][j], 0, 0, 0);
+            }
             acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, f.ah[i]), __builtin_bit_cast(bf16x8, f.bh[j]), acc[i][j], 0, 0, 0);
             if (i * 2 + j < 3) {
                 const int piece = P0 + i * 2 + j;
@@ -272,6 +281,7 @@ __device__ __forceinline__ void mma12_tn(f32x16 (&acc)[2][2], const Frag& f, boo
     }
 }
 
+template <int NP>
 __global__ __launch_bounds__(512, 2) void gemm_split_tn_kernel(const SplitParams p) {
     __shared__ __attribute__((aligned(16))) float smem[3 * T3_STAGE];      // A slice 32x256, B slice 32x128 floats
     const int tid = threadIdx.x, lane = tid & 63;
@@ -323,12 +333,12 @@ __global__ __launch_bounds__(512, 2) void gemm_split_tn_kernel(const SplitParams
 #pragma unroll
         for (int i = 0; i < 2; ++i) {
             f.ah[i] = tr_frag(As, aoff[i] + s2 * 16 * 1024, 1024);
-            f.al[i] = tr_frag(As, (aoff[i] ^ 16) + s2 * 16 * 1024, 1024);
+            if (NP == 3) f.al[i] = tr_frag(As, (aoff[i] ^ 16) + s2 * 16 * 1024, 1024);
         }
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
             f.bh[j] = tr_frag(Bs, boff[j] + s2 * 16 * 512, 512);
-            f.bl[j] = tr_frag(Bs, (boff[j] ^ 16) + s2 * 16 * 512, 512);
+            if (NP == 3) f.bl[j] = tr_frag(Bs, (boff[j] ^ 16) + s2 * 16 * 512, 512);
         }
     };
     auto issue = [&](int kt, int stage) {
@@ -369,9 +379,9 @@ __global__ __launch_bounds__(512, 2) void gemm_split_tn_kernel(const SplitParams
         const char* As = reinterpret_cast<const char*>(smem + stage * T3_STAGE);
         const char* Bs = As + T3_A * 4;
         load_frag_tn(X, As, Bs, 0);
-        mma12_tn<0>(acc, X, ahead, asrc, bsrc, ka, kb, dA, dB);
+        mma12_tn<0, NP>(acc, X, ahead, asrc, bsrc, ka, kb, dA, dB);
         load_frag_tn(Y, As, Bs, 1);
-        mma12_tn<3>(acc, Y, ahead, asrc, bsrc, ka, kb, dA, dB);
+        mma12_tn<3, NP>(acc, Y, ahead, asrc, bsrc, ka, kb, dA, dB);
         if (ahead) asm volatile("s_waitcnt vmcnt(6) lgkmcnt(0)" ::: "memory");
         else       asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
         __builtin_amdgcn_s_barrier();
@@ -436,7 +446,7 @@ __device__ __forceinline__ f32x4 tr_frag16(const char* base, int off) {
 //              the LDS image is [32 k-rows][256 cols] per operand and the fragments come out of
 //              ds_read_b64_tr_b16: the 16 lanes of k-group g read the 4 x 16 block of k-rows 8g..8g+3
 //              (then 8g+4..8g+7) and each receives its column's 4 k-values — exactly the 16x16x32 operand.
-template <bool TN>
+template <bool TN, int NP>
 __global__ __launch_bounds__(512, 2) void gemm_split_x16_kernel(const SplitParams p) {
     // All 160 KB of LDS: THREE stages for A (the operand streamed from HBM: its slice t+2 is in flight while t
     // is multiplied) and two for B (weights / the other streamed operand: slice t+1).  Measured with in-kernel
@@ -536,12 +546,14 @@ __global__ __launch_bounds__(512, 2) void gemm_split_x16_kernel(const SplitParam
     // slice t+1 sit in front of row-tile 7 of slice t, and slice t+1's first fragments (B-hi into the second register
     // set, A row-tile 0 into pair 0, B-lo behind row-tile 7's B-lo group) are fetched under its twelve MFMAs.
     f32x4 bhA[4], bhB[4], bl[4], pah[2], pal[2];
-    pal[0] = rdA(smem, 0, true);
+    if (NP == 3) pal[0] = rdA(smem, 0, true);
 #pragma unroll
     for (int j = 0; j < 4; ++j) bhA[j] = rdB(smemB, j, false);
     pah[0] = rdA(smem, 0, false);
+    if (NP == 3) {
 #pragma unroll
-    for (int j = 0; j < 4; ++j) bl[j] = rdB(smemB, j, true);
+        for (int j = 0; j < 4; ++j) bl[j] = rdB(smemB, j, true);
+    }
     __builtin_amdgcn_sched_barrier(0);
 
     int stage = 0, astage = 0;                              // B ring of 2, A ring of 3
@@ -557,18 +569,21 @@ __global__ __launch_bounds__(512, 2) void gemm_split_x16_kernel(const SplitParam
 #pragma unroll
         for (int i = 0; i < 7; ++i) {
             pah[(i + 1) & 1] = rdA(As, i + 1, false);
-            pal[(i + 1) & 1] = rdA(As, i + 1, true);
+            if (NP == 3) pal[(i + 1) & 1] = rdA(As, i + 1, true);
             __builtin_amdgcn_sched_barrier(0);
             if (i < 4) {          // B(kt+1) first, A(kt+2) last: the wait below skips exactly the 4 youngest
                 if (i < 2) { dma16_asm(bsrc[2 * i] + kb, dB + (2 * i) * 8 * SBK);         dma16_asm(bsrc[2 * i + 1] + kb, dB + (2 * i + 1) * 8 * SBK); }
                 else       { dma16_asm(asrc[2 * i - 4] + ka, dA + (2 * i - 4) * 8 * SBK); dma16_asm(asrc[2 * i - 3] + ka, dA + (2 * i - 3) * 8 * SBK); }
             }
             __builtin_amdgcn_sched_barrier(0);
-            const bf16x8 vah = __builtin_bit_cast(bf16x8, pah[i & 1]), val = __builtin_bit_cast(bf16x8, pal[i & 1]);
+            const bf16x8 vah = __builtin_bit_cast(bf16x8, pah[i & 1]);
+            if (NP == 3) {
+                const bf16x8 val = __builtin_bit_cast(bf16x8, pal[i & 1]);
 #pragma unroll
-            for (int j = 0; j < 4; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, bhc[j]), val, acc[i][j], 0, 0, 0);
+                for (int j = 0; j < 4; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, bhc[j]), val, acc[i][j], 0, 0, 0);
 #pragma unroll
-            for (int j = 0; j < 4; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, bl[j]), vah, acc[i][j], 0, 0, 0);
+                for (int j = 0; j < 4; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, bl[j]), vah, acc[i][j], 0, 0, 0);
+            }
 #pragma unroll
             for (int j = 0; j < 4; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, bhc[j]), vah, acc[i][j], 0, 0, 0);
             __builtin_amdgcn_sched_barrier(0);
@@ -578,21 +593,24 @@ __global__ __launch_bounds__(512, 2) void gemm_split_x16_kernel(const SplitParam
         __builtin_amdgcn_s_barrier();
         asm volatile("" ::: "memory");
         __builtin_amdgcn_sched_barrier(0);
-        pal[0] = rdA(Asn, 0, true);
+        if (NP == 3) pal[0] = rdA(Asn, 0, true);
 #pragma unroll
         for (int j = 0; j < 4; ++j) bhn[j] = rdB(Bsn, j, false);
         pah[0] = rdA(Asn, 0, false);
         __builtin_amdgcn_sched_barrier(0);
         {   // row-tile 7 (pair 1): B-lo group first, which frees the B-lo registers for the next slice's
-            const bf16x8 vah = __builtin_bit_cast(bf16x8, pah[1]), val = __builtin_bit_cast(bf16x8, pal[1]);
+            const bf16x8 vah = __builtin_bit_cast(bf16x8, pah[1]);
+            if (NP == 3) {
+                const bf16x8 val = __builtin_bit_cast(bf16x8, pal[1]);
 #pragma unroll
-            for (int j = 0; j < 4; ++j) acc[7][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, bl[j]), vah, acc[7][j], 0, 0, 0);
-            __builtin_amdgcn_sched_barrier(0);
+                for (int j = 0; j < 4; ++j) acc[7][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, bl[j]), vah, acc[7][j], 0, 0, 0);
+                __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-            for (int j = 0; j < 4; ++j) bl[j] = rdB(Bsn, j, true);
-            __builtin_amdgcn_sched_barrier(0);
+                for (int j = 0; j < 4; ++j) bl[j] = rdB(Bsn, j, true);
+                __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-            for (int j = 0; j < 4; ++j) acc[7][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, bhc[j]), val, acc[7][j], 0, 0, 0);
+                for (int j = 0; j < 4; ++j) acc[7][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, bhc[j]), val, acc[7][j], 0, 0, 0);
+            }
 #pragma unroll
             for (int j = 0; j < 4; ++j) acc[7][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, bhc[j]), vah, acc[7][j], 0, 0, 0);
             __builtin_amdgcn_sched_barrier(0);
@@ -698,7 +716,7 @@ __device__ __forceinline__ void dma16_sbase(const float* sbase, unsigned voff_by
 // A row-tile 0 into the rolling pair) are fetched while row-tile 7's twelve MFMAs run.  Row-tile 7 runs its B-lo group
 // first, which frees the B-lo registers for slice s+1's B-lo reads behind it.  One barrier per slice, as before.
 //   bhc / bhn: B-hi fragments of this / the next slice (two named sets, the caller alternates them).
-template <bool BIAS>
+template <bool BIAS, int NP>
 __device__ __forceinline__ void x16p_slice(f32x4 (&acc)[8][4], f32x4 (&bhc)[4], f32x4 (&bhn)[4], f32x4 (&bl)[4], f32x4 (&pah)[2],
                                            f32x4 (&pal)[2], const float* As, const float* Bs, const float* Asn, const float* Bsn,
                                            int a_row, int b_row, int c_hi, int c_lo, const float* Ap, const float* Bp,
@@ -709,18 +727,21 @@ __device__ __forceinline__ void x16p_slice(f32x4 (&acc)[8][4], f32x4 (&bhc)[4], 
 #pragma unroll
     for (int i = 0; i < 7; ++i) {
         pah[(i + 1) & 1] = *reinterpret_cast<const f32x4*>(As + a_row + (i + 1) * 16 * SBK + c_hi);
-        pal[(i + 1) & 1] = *reinterpret_cast<const f32x4*>(As + a_row + (i + 1) * 16 * SBK + c_lo);
+        if (NP == 3) pal[(i + 1) & 1] = *reinterpret_cast<const f32x4*>(As + a_row + (i + 1) * 16 * SBK + c_lo);
         __builtin_amdgcn_sched_barrier(0);
         if (i < 4) {      // B(s+1) first, A(s+2) last: the wait below skips exactly the 4 youngest pieces
             if (i < 2) { dma16_sbase(Bp, boff[2 * i], dB + (2 * i) * 8 * SBK);     dma16_sbase(Bp, boff[2 * i + 1], dB + (2 * i + 1) * 8 * SBK); }
             else       { dma16_sbase(Ap, aoff[2 * i - 4], dA + (2 * i - 4) * 8 * SBK); dma16_sbase(Ap, aoff[2 * i - 3], dA + (2 * i - 3) * 8 * SBK); }
         }
         __builtin_amdgcn_sched_barrier(0);
-        const bf16x8 vah = __builtin_bit_cast(bf16x8, pah[i & 1]), val = __builtin_bit_cast(bf16x8, pal[i & 1]);
+        const bf16x8 vah = __builtin_bit_cast(bf16x8, pah[i & 1]);
+        if (NP == 3) {
+            const bf16x8 val = __builtin_bit_cast(bf16x8, pal[i & 1]);
 #pragma unroll
-        for (int j = 0; j < 4; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, bhc[j]), val, acc[i][j], 0, 0, 0);
+            for (int j = 0; j < 4; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, bhc[j]), val, acc[i][j], 0, 0, 0);
 #pragma unroll
-        for (int j = 0; j < 4; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, bl[j]), vah, acc[i][j], 0, 0, 0);
+            for (int j = 0; j < 4; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, bl[j]), vah, acc[i][j], 0, 0, 0);
+        }
 #pragma unroll
         for (int j = 0; j < 4; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, bhc[j]), vah, acc[i][j], 0, 0, 0);
         __builtin_amdgcn_sched_barrier(0);
@@ -733,28 +754,31 @@ __device__ __forceinline__ void x16p_slice(f32x4 (&acc)[8][4], f32x4 (&bhc)[4], 
     asm volatile("" ::: "memory");
     __builtin_amdgcn_sched_barrier(0);
     // first fragments of slice s+1, in the order its MFMAs will ask for them
-    pal[0] = *reinterpret_cast<const f32x4*>(Asn + a_row + c_lo);
+    if (NP == 3) pal[0] = *reinterpret_cast<const f32x4*>(Asn + a_row + c_lo);
 #pragma unroll
     for (int j = 0; j < 4; ++j) bhn[j] = *reinterpret_cast<const f32x4*>(Bsn + b_row + j * 16 * SBK + c_hi);
     pah[0] = *reinterpret_cast<const f32x4*>(Asn + a_row + c_hi);
     __builtin_amdgcn_sched_barrier(0);
     {   // row-tile 7 (pair 1): B-lo group first
-        const bf16x8 vah = __builtin_bit_cast(bf16x8, pah[1]), val = __builtin_bit_cast(bf16x8, pal[1]);
+        const bf16x8 vah = __builtin_bit_cast(bf16x8, pah[1]);
+        if (NP == 3) {
+            const bf16x8 val = __builtin_bit_cast(bf16x8, pal[1]);
 #pragma unroll
-        for (int j = 0; j < 4; ++j) acc[7][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, bl[j]), vah, acc[7][j], 0, 0, 0);
-        __builtin_amdgcn_sched_barrier(0);
+            for (int j = 0; j < 4; ++j) acc[7][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, bl[j]), vah, acc[7][j], 0, 0, 0);
+            __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-        for (int j = 0; j < 4; ++j) bl[j] = *reinterpret_cast<const f32x4*>(Bsn + b_row + j * 16 * SBK + c_lo);
-        __builtin_amdgcn_sched_barrier(0);
+            for (int j = 0; j < 4; ++j) bl[j] = *reinterpret_cast<const f32x4*>(Bsn + b_row + j * 16 * SBK + c_lo);
+            __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-        for (int j = 0; j < 4; ++j) acc[7][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, bhc[j]), val, acc[7][j], 0, 0, 0);
+            for (int j = 0; j < 4; ++j) acc[7][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, bhc[j]), val, acc[7][j], 0, 0, 0);
+        }
 #pragma unroll
         for (int j = 0; j < 4; ++j) acc[7][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, bhc[j]), vah, acc[7][j], 0, 0, 0);
         __builtin_amdgcn_sched_barrier(0);
     }
 }
 
-template <bool BIAS>
+template <bool BIAS, int NP>
 __global__ __launch_bounds__(512, 2) void gemm_split_x16p_kernel(const SplitParams p) {
     __shared__ __attribute__((aligned(16))) float smem[5 * T4_A];          // 163,840 B: A x 3 stages, B x 2
     const int tid = threadIdx.x, lane = tid & 63;
@@ -835,12 +859,14 @@ __global__ __launch_bounds__(512, 2) void gemm_split_x16p_kernel(const SplitPara
     asm volatile("" ::: "memory");
     // fragments of the very first slice
     f32x4 bhA[4], bhB[4], bl[4], pah[2], pal[2];
-    pal[0] = *reinterpret_cast<const f32x4*>(smem + a_row + c_lo);
+    if (NP == 3) pal[0] = *reinterpret_cast<const f32x4*>(smem + a_row + c_lo);
 #pragma unroll
     for (int j = 0; j < 4; ++j) bhA[j] = *reinterpret_cast<const f32x4*>(smemB + b_row + j * 16 * SBK + c_hi);
     pah[0] = *reinterpret_cast<const f32x4*>(smem + a_row + c_hi);
+    if (NP == 3) {
 #pragma unroll
-    for (int j = 0; j < 4; ++j) bl[j] = *reinterpret_cast<const f32x4*>(smemB + b_row + j * 16 * SBK + c_lo);
+        for (int j = 0; j < 4; ++j) bl[j] = *reinterpret_cast<const f32x4*>(smemB + b_row + j * 16 * SBK + c_lo);
+    }
     __builtin_amdgcn_sched_barrier(0);
 
     // ONE loop over the slices of all tiles this workgroup draws, two slices per trip (the two B-hi register sets)
@@ -919,8 +945,8 @@ __global__ __launch_bounds__(512, 2) void gemm_split_x16p_kernel(const SplitPara
 #pragma unroll
                 for (int j = 0; j < 4; ++j) init[j] = gload16_asm(bsrc + j * 16);
             }
-            if (half == 0) x16p_slice<BIAS>(acc, bhA, bhB, bl, pah, pal, As, Bs, Asn, Bsn, a_row, b_row, c_hi, c_lo, Ap, Bp, aoff, boff, dA, dB, init);
-            else           x16p_slice<BIAS>(acc, bhB, bhA, bl, pah, pal, As, Bs, Asn, Bsn, a_row, b_row, c_hi, c_lo, Ap, Bp, aoff, boff, dA, dB, init);
+            if (half == 0) x16p_slice<BIAS, NP>(acc, bhA, bhB, bl, pah, pal, As, Bs, Asn, Bsn, a_row, b_row, c_hi, c_lo, Ap, Bp, aoff, boff, dA, dB, init);
+            else           x16p_slice<BIAS, NP>(acc, bhB, bhA, bl, pah, pal, As, Bs, Asn, Bsn, a_row, b_row, c_hi, c_lo, Ap, Bp, aoff, boff, dA, dB, init);
             stage ^= 1;
             astage = astage1;
             ++kt;
@@ -1068,9 +1094,27 @@ extern "C" size_t wf3d_gemm_split_dma_ws_bytes(int M, int N, int K) {
     return ks > 1 ? (size_t)ks * M * N * sizeof(float) : CTL_BYTES;
 }
 
+namespace {
+template <int NP>
+void launch_split_dma(const SplitParams& p, int variant, bool persist, int cus, hipStream_t st) {
+    if (variant == 6) {
+        if (persist) {
+            if (p.bias) hipLaunchKernelGGL((gemm_split_x16p_kernel<true, NP>), dim3(cus, 1, 1), dim3(512), 0, st, p);
+            else        hipLaunchKernelGGL((gemm_split_x16p_kernel<false, NP>), dim3(cus, 1, 1), dim3(512), 0, st, p);
+        } else
+            hipLaunchKernelGGL((gemm_split_x16_kernel<false, NP>), dim3(p.nbm * p.nbn, 1, p.ksplit), dim3(512), 0, st, p);
+    } else {
+        hipLaunchKernelGGL((gemm_split_dma3_kernel<NP>), dim3(p.nbm * p.nbn, 1, p.ksplit), dim3(512), 0, st, p);
+    }
+}
+}  // namespace
+
+// products: 3 = bf16x3 (wf3d_gemm_split), 1 = plain bf16 on the hi planes (wf3d_gemm_bf16); the kernel choice,
+// tiling and split-K plan do not depend on it.
 extern "C" int wf3d_gemm_split_dma(const void* A_sx8, const void* B_sx8, float* C, const float* bias, int M, int N,
                                    int K, int lda, int ldb, int ldc, int accumulate, void* ws, size_t ws_bytes,
-                                   void* stream) {
+                                   void* stream, int products) {
+    WF3D_CHECK(products == 1 || products == 3, WF3D_ERR_ARG, "wf3d_gemm_split_dma: products must be 1 or 3 (got %d)", products);
     WF3D_CHECK(wf3d_gemm_split_dma_ok(M, N, K, lda, ldb), WF3D_ERR_UNSUPPORTED, "wf3d_gemm_split_dma: shape not supported");
     WF3D_CHECK(A_sx8 && B_sx8 && C, WF3D_ERR_ARG, "wf3d_gemm_split_dma: null operand");
     WF3D_CHECK(lda >= K && ldb >= K && ldc >= N, WF3D_ERR_ARG, "wf3d_gemm_split_dma: leading dimension too small");
@@ -1085,23 +1129,23 @@ extern "C" int wf3d_gemm_split_dma(const void* A_sx8, const void* B_sx8, float* 
     if (need && (ws == nullptr || ws_bytes < need)) { p.ksplit = 1; p.kt_per_split = K / SBK; }
     p.slab = p.ksplit > 1 ? (float*)ws : nullptr;
     hipStream_t st = (hipStream_t)stream;
+    bool persist = false;
+    int cus = 0;
     if (variant == 6) {
         static const int persist_on = [] { const char* e = getenv("WF3D_SPLIT_PERSIST"); return e ? atoi(e) : 1; }();
-        int cus = cu_count();
+        cus = cu_count();
         { const int lim = g_gemm_cus.load(std::memory_order_relaxed); if (lim >= 8 && lim < cus) cus = lim / 8 * 8; }
         // persistent form: full tiles, one pass over K, plain (non-accumulating) 16-B stores
-        if (persist_on && p.ksplit == 1 && !accumulate && M % 256 == 0 && N % 256 == 0 && K / SBK >= 8 && K % (2 * SBK) == 0 &&
+        persist = persist_on && p.ksplit == 1 && !accumulate && M % 256 == 0 && N % 256 == 0 && K / SBK >= 8 && K % (2 * SBK) == 0 &&
             ws != nullptr && ws_bytes >= CTL_BYTES && (uintptr_t)ws % 64 == 0 && cus <= 384 && cus >= 8 && cus % 8 == 0 &&
-            p.nbm * p.nbn >= 2 * cus && ldc % 4 == 0 && (long)lda * 1024 < (1L << 32) && (long)ldb * 1024 < (1L << 32) && (long)ldc * 1024 < (1L << 32) && ((uintptr_t)C % 16 == 0) && (!bias || (uintptr_t)bias % 16 == 0)) {
+            p.nbm * p.nbn >= 2 * cus && ldc % 4 == 0 && (long)lda * 1024 < (1L << 32) && (long)ldb * 1024 < (1L << 32) && (long)ldc * 1024 < (1L << 32) && ((uintptr_t)C % 16 == 0) && (!bias || (uintptr_t)bias % 16 == 0);
+        if (persist) {
             p.ctl = (unsigned*)ws;
             if (hipMemsetAsync(ws, 0, 512, st) != hipSuccess) { wf3d_set_error("wf3d_gemm_split_dma: hipMemsetAsync failed"); return WF3D_ERR_LAUNCH; }
-            if (bias) hipLaunchKernelGGL(gemm_split_x16p_kernel<true>, dim3(cus, 1, 1), dim3(512), 0, st, p);
-            else      hipLaunchKernelGGL(gemm_split_x16p_kernel<false>, dim3(cus, 1, 1), dim3(512), 0, st, p);
-        } else
-            hipLaunchKernelGGL(gemm_split_x16_kernel<false>, dim3(p.nbm * p.nbn, 1, p.ksplit), dim3(512), 0, st, p);
-    } else {
-        hipLaunchKernelGGL(gemm_split_dma3_kernel, dim3(p.nbm * p.nbn, 1, p.ksplit), dim3(512), 0, st, p);
+        }
     }
+    if (products == 1) launch_split_dma<1>(p, variant, persist, cus, st);
+    else               launch_split_dma<3>(p, variant, persist, cus, st);
     WF3D_LAUNCH_CHECK();
     if (p.ksplit > 1) {
         launch_split_reduce(p, st);
@@ -1181,13 +1225,21 @@ extern "C" size_t wf3d_gemm_split_tn_ws_bytes(int Mo, int No, int K) {
     return ks > 1 ? (size_t)ks * Mo * No * sizeof(float) : 0;
 }
 
-extern "C" int wf3d_gemm_split_tn(const void* A_sx8, const void* B_sx8, float* C, int Mo, int No, int K, int lda,
-                                  int ldb, int ldc, int accumulate, void* ws, size_t ws_bytes, void* stream) {
+namespace {
+template <int NP>
+void launch_split_tn(const SplitParams& p, bool big, hipStream_t st) {
+    if (big && p.zmap) hipLaunchKernelGGL((gemm_split_x16_kernel<true, NP>), dim3(p.nbm * p.nbn * p.ksplit, 1, 1), dim3(512), 0, st, p);
+    else if (big)      hipLaunchKernelGGL((gemm_split_x16_kernel<true, NP>), dim3(p.nbm * p.nbn, 1, p.ksplit), dim3(512), 0, st, p);
+    else               hipLaunchKernelGGL((gemm_split_tn_kernel<NP>), dim3(p.nbm * p.nbn, 1, p.ksplit), dim3(512), 0, st, p);
+}
+
+int gemm_split_tn_impl(const char* fn, int products, const void* A_sx8, const void* B_sx8, float* C, int Mo, int No, int K,
+                       int lda, int ldb, int ldc, int accumulate, void* ws, size_t ws_bytes, void* stream) {
     WF3D_CHECK(wf3d_gemm_split_tn_ok(Mo, No, K, lda, ldb), WF3D_ERR_UNSUPPORTED,
-               "wf3d_gemm_split_tn: needs Mo %% 256 == 0, No %% 128 == 0, K %% 32 == 0 (Mo=%d No=%d K=%d)", Mo, No, K);
-    WF3D_CHECK(A_sx8 && B_sx8 && C, WF3D_ERR_ARG, "wf3d_gemm_split_tn: null operand");
-    WF3D_CHECK(lda >= Mo && ldb >= No && ldc >= No, WF3D_ERR_ARG, "wf3d_gemm_split_tn: leading dimension too small");
-    WF3D_CHECK(((uintptr_t)A_sx8 % 16 == 0) && ((uintptr_t)B_sx8 % 16 == 0), WF3D_ERR_ARG, "wf3d_gemm_split_tn: misaligned operand");
+               "%s: needs Mo %% 256 == 0, No %% 128 == 0, K %% 32 == 0 (Mo=%d No=%d K=%d)", fn, Mo, No, K);
+    WF3D_CHECK(A_sx8 && B_sx8 && C, WF3D_ERR_ARG, "%s: null operand", fn);
+    WF3D_CHECK(lda >= Mo && ldb >= No && ldc >= No, WF3D_ERR_ARG, "%s: leading dimension too small", fn);
+    WF3D_CHECK(((uintptr_t)A_sx8 % 16 == 0) && ((uintptr_t)B_sx8 % 16 == 0), WF3D_ERR_ARG, "%s: misaligned operand", fn);
     SplitParams p{};
     p.A = (const float*)A_sx8; p.B = (const float*)B_sx8; p.C = C; p.bias = nullptr;
     p.M = Mo; p.N = No; p.K = K; p.lda = lda; p.ldb = ldb; p.ldc = ldc; p.accumulate = accumulate;
@@ -1199,15 +1251,25 @@ extern "C" int wf3d_gemm_split_tn(const void* A_sx8, const void* B_sx8, float* C
     p.slab = p.ksplit > 1 ? (float*)ws : nullptr;
     hipStream_t st = (hipStream_t)stream;
     static const int zmap_off = [] { const char* e = getenv("WF3D_TN_ZMAP"); return e && atoi(e) == 0; }();
-    if (big && !zmap_off && p.ksplit >= 8 && p.ksplit % 8 == 0) {
-        p.zmap = 1;
-        hipLaunchKernelGGL(gemm_split_x16_kernel<true>, dim3(p.nbm * p.nbn * p.ksplit, 1, 1), dim3(512), 0, st, p);
-    } else if (big) hipLaunchKernelGGL(gemm_split_x16_kernel<true>, dim3(p.nbm * p.nbn, 1, p.ksplit), dim3(512), 0, st, p);
-    else     hipLaunchKernelGGL(gemm_split_tn_kernel, dim3(p.nbm * p.nbn, 1, p.ksplit), dim3(512), 0, st, p);
+    if (big && !zmap_off && p.ksplit >= 8 && p.ksplit % 8 == 0) p.zmap = 1;
+    if (products == 1) launch_split_tn<1>(p, big, st);
+    else               launch_split_tn<3>(p, big, st);
     WF3D_LAUNCH_CHECK();
     if (p.ksplit > 1) {
         launch_split_reduce(p, st);
         WF3D_LAUNCH_CHECK();
     }
     return WF3D_OK;
+}
+}  // namespace
+
+extern "C" int wf3d_gemm_split_tn(const void* A_sx8, const void* B_sx8, float* C, int Mo, int No, int K, int lda,
+                                  int ldb, int ldc, int accumulate, void* ws, size_t ws_bytes, void* stream) {
+    return gemm_split_tn_impl("wf3d_gemm_split_tn", 3, A_sx8, B_sx8, C, Mo, No, K, lda, ldb, ldc, accumulate, ws, ws_bytes, stream);
+}
+
+// bf16 mode: the same launch on the hi planes only (one MFMA per product); workspace: wf3d_gemm_split_tn_ws_bytes
+extern "C" int wf3d_gemm_bf16_tn(const void* A_sx8, const void* B_sx8, float* C, int Mo, int No, int K, int lda,
+                                 int ldb, int ldc, int accumulate, void* ws, size_t ws_bytes, void* stream) {
+    return gemm_split_tn_impl("wf3d_gemm_bf16_tn", 1, A_sx8, B_sx8, C, Mo, No, K, lda, ldb, ldc, accumulate, ws, ws_bytes, stream);
 }

@@ -39,7 +39,7 @@ extern "C" WF3D_INTERNAL int wf3d_gemm_split_dma_ok(int M, int N, int K, int lda
 extern "C" WF3D_INTERNAL size_t wf3d_gemm_split_dma_ws_bytes(int M, int N, int K);
 extern "C" WF3D_INTERNAL int wf3d_gemm_split_dma(const void* A_sx8, const void* B_sx8, float* C, const float* bias, int M, int N,
                                    int K, int lda, int ldb, int ldc, int accumulate, void* ws, size_t ws_bytes,
-                                   void* stream);
+                                   void* stream, int products);
 
 // internal: MFMA attention for head_dim 64 (attn_mfma.hip)
 extern "C" WF3D_INTERNAL int wf3d_attn_fwd_mfma(const float* qkv, const int32_t* voff, int S, int vmax, int E, int heads, float drop_p,

@@ -39,7 +39,7 @@ class PointNetEncoder(nn.Module):
             nn.Linear(4 * d, 2 * d), nn.LayerNorm(2 * d), nn.ReLU(inplace=True),
             nn.Linear(2 * d, d))
         self._n_hidden = len(hidden_dims)
-        self.precision = None          # None -> wf3d.config.precision() ("bf16x3" | "fp32")
+        self.precision = None          # None -> wf3d.config.precision() ("bf16x3" | "bf16" | "fp32")
 
     def _mlp_params(self):
         ps = []

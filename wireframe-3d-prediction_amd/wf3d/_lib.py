@@ -95,6 +95,10 @@ SIGNATURES = {
     "wf3d_gemm_split_tn_ws_bytes": (c_size_t, [c_int, c_int, c_int]),
     "wf3d_gemm_split_tn": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
                                    c_void_p, c_size_t, c_void_p]),
+    "wf3d_gemm_bf16": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int,
+                               c_int, c_void_p, c_size_t, c_void_p]),
+    "wf3d_gemm_bf16_tn": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
+                                  c_void_p, c_size_t, c_void_p]),
     "wf3d_split_rows": (c_int, [c_void_p, ctypes.c_long, ctypes.c_long, c_int, c_int, c_void_p, c_void_p]),
     "wf3d_split_rows_multi": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
     "wf3d_split_transpose": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int,

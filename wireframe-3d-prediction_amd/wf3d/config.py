@@ -6,14 +6,19 @@ precision
              bf16 MFMAs per product, fp32 accumulation: results agree with the fp32 path to
              ~1e-5 (inside the 1e-4 parity gate) at ~3x the fp32-MFMA throughput.
     "fp32":  every GEMM on the exact-fp32 MFMA (v_mfma_f32_32x32x2_f32).
+    "bf16":  opt-in.  Exactly the GEMMs "bf16x3" runs split, on the same sx8 operands, with ONE bf16 MFMA per
+             product (hi*hi: bf16 round-to-nearest operands, fp32 accumulation; wf3d_gemm_bf16 / _tn).
+             Everything else stays as in "bf16x3".  Narrower than fp32: its error is measured and gated
+             (tests/test_precision_bf16_gpu.py).
 Environment override: WF3D_PRECISION.
 """
 import os
 
 SPLIT_MIN_ROWS = 1024
+PRECISIONS = ("fp32", "bf16x3", "bf16")
 _precision = os.environ.get("WF3D_PRECISION", "bf16x3")
-if _precision not in ("fp32", "bf16x3"):
-    raise RuntimeError(f"WF3D_PRECISION={_precision!r}: expected 'fp32' or 'bf16x3'")
+if _precision not in PRECISIONS:
+    raise RuntimeError(f"WF3D_PRECISION={_precision!r}: expected 'fp32', 'bf16x3' or 'bf16'")
 
 
 def precision():
@@ -22,8 +27,8 @@ def precision():
 
 def set_precision(p):
     global _precision
-    if p not in ("fp32", "bf16x3"):
-        raise ValueError("precision must be 'fp32' or 'bf16x3'")
+    if p not in PRECISIONS:
+        raise ValueError("precision must be 'fp32', 'bf16x3' or 'bf16'")
     _precision = p
 
 

@@ -103,16 +103,21 @@ def _split_ok(rows, k, split):
     return split and rows >= config.SPLIT_MIN_ROWS and k % 8 == 0 and k >= 32
 
 
+# Modes that run the large Linears on sx8 operands, and the bf16 MFMAs per product each one issues: "bf16" runs exactly
+# the GEMMs "bf16x3" runs split, one product (hi*hi) instead of three.
+_SPLIT_PRODUCTS = {"bf16x3": 3, "bf16": 1}
+
+
 def _tn_either(a_s, b_s):
     """The wgrad kernel tiles dW[Mo, No] with Mo % 256 == 0; when only the transposed problem fits
     (e.g. dW[128, 256]) it computes dW^T = h^T·dz and the small result is transposed."""
     return ops.gemm_split_tn_ok(a_s, b_s) or ops.gemm_split_tn_ok(b_s, a_s)
 
 
-def _wgrad_tn(dz_s, h_s):
+def _wgrad_tn(dz_s, h_s, products=3):
     if ops.gemm_split_tn_ok(dz_s, h_s):
-        return ops.gemm_split_tn(dz_s, h_s)
-    return ops.gemm_split_tn(h_s, dz_s).t().contiguous()
+        return ops.gemm_split_tn(dz_s, h_s, products=products)
+    return ops.gemm_split_tn(h_s, dz_s, products=products).t().contiguous()
 
 
 class EncoderFn(torch.autograd.Function):
@@ -129,7 +134,8 @@ class EncoderFn(torch.autograd.Function):
     layer's relu(LN(z)) as an sx8 split operand produced by wf3d_ln_prep (which also
     yields the LN statistics), through wf3d_gemm_split; backward uses split GEMMs for
     dgrad (W^T in sx8) and wgrad (transposed sx8 operands).  Only z and (mu, rstd) are
-    kept for backward in either mode."""
+    kept for backward in either mode.  precision "bf16": the same GEMMs on the same operands with
+    one bf16 MFMA per product (hi planes only); backward uses the forward's mode (ctx.products)."""
 
     @staticmethod
     def forward(ctx, x, n_hidden, precision, *params):
@@ -141,7 +147,8 @@ class EncoderFn(torch.autograd.Function):
         x2 = x.reshape(M, Din)
         if not x2.is_contiguous():
             x2 = x2.contiguous()
-        split = precision == "bf16x3"
+        split = precision in _SPLIT_PRODUCTS
+        npr = _SPLIT_PRODUCTS.get(precision, 3)
         valid = ops.point_valid(x2)
         # both sx8 orientations (W for the forward GEMM, W^T for its dgrad) of every split layer's weight, one launch
         widx = [i for i in range(1, n_hidden + 1)
@@ -157,7 +164,7 @@ class EncoderFn(torch.autograd.Function):
                 # first Linear + LayerNorm + ReLU + split in one pass (K = input_dim <= 8: a pure write of z and h)
                 z, mu, rs, a_s = ops.first_layer_fwd(x2, W, b, params[2], params[3], ACT_RELU)
             elif a_s is not None:
-                z = ops.gemm_split(a_s, wsplit[i][0] if i in wsplit else ops.split_rows(W), bias=b)
+                z = ops.gemm_split(a_s, wsplit[i][0] if i in wsplit else ops.split_rows(W), bias=b, products=npr)
                 a_s = None
             else:
                 z = ops.gemm(a, W, NT, bias=b, pro=pro)
@@ -180,7 +187,7 @@ class EncoderFn(torch.autograd.Function):
         del a_s
         C = pf.shape[1]
         po = ops.pool4_fwd(pf.view(B, N, C), valid, packed=True)          # [max | avg] (PointNetEncoder.py:115), [mean | max]
-        ctx.n_hidden, ctx.dims, ctx.split = n_hidden, (B, N, C), split
+        ctx.n_hidden, ctx.dims, ctx.split, ctx.products = n_hidden, (B, N, C), split, npr
         _keep_params(ctx, params)
         ctx.saved = (x2, valid, zs, stats, hs, po.arg_m, po.arg_u, po.cnt)
         ctx.nvalid = po.nvalid
@@ -192,7 +199,7 @@ class EncoderFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dpooled, dpf, dupooled):
-        nh, (B, N, C), split = ctx.n_hidden, ctx.dims, ctx.split
+        nh, (B, N, C), split, npr = ctx.n_hidden, ctx.dims, ctx.split, ctx.products
         M = B * N
         params = _params(ctx)
         x2, valid, zs, stats, hs, arg_m, arg_u, cnt = _saved(ctx)
@@ -251,17 +258,19 @@ class EncoderFn(torch.autograd.Function):
             h_prev_s = hs[i - 1] if i > 0 else None
             if i > 0 and dz_s is not None and h_prev_s is not None and ops.gemm_split_tn_ok(dz_s, h_prev_s):
                 # wgrad dW = dz^T · h_prev straight from the reduction-major sx8 operands (transposing LDS reads)
-                grads[4 * i] = ops.gemm_split_tn(dz_s, h_prev_s)
+                grads[4 * i] = ops.gemm_split_tn(dz_s, h_prev_s, products=npr)
                 if not config.RETAIN_SAVED:
                     hs[i - 1] = None
             elif i > 0 and dz_s is not None and _split_ok(M, K, split) and M % 8 == 0:
                 # same through materialised transposes (shapes the TN kernel does not tile)
-                grads[4 * i] = ops.gemm_split(ops.split_transpose(dz_s, in_sx8=True), ops.split_transpose(a_prev, pro_prev))
+                grads[4 * i] = ops.gemm_split(ops.split_transpose(dz_s, in_sx8=True), ops.split_transpose(a_prev, pro_prev),
+                                              products=npr)
             else:
                 grads[4 * i] = ops.gemm(dz, a_prev, TN, pro=pro_prev)
             if i > 0:
                 if dz_s is not None:
-                    dh = ops.gemm_split(dz_s, ctx.wT[i] if i in ctx.wT else ops.split_rows(W, transpose=True))     # dgrad: dz · W
+                    dh = ops.gemm_split(dz_s, ctx.wT[i] if i in ctx.wT else ops.split_rows(W, transpose=True),     # dgrad: dz · W
+                                        products=npr)
                 else:
                     dh = ops.gemm(dz, W, NN)
             elif ctx.want_dx:
@@ -497,7 +506,8 @@ class EdgeFn(torch.autograd.Function):
         # the two wide edge-MLP layers (E rows: 52 % of the FLOPs at V=256) on the split path
         # (H / 4, the third layer's width, is the reduction width of its dgrad and the row length of its transposed weight:
         # it has to be made of whole 8-column groups too — EdgePredictor(hidden_dim=208) used to fail in split_weights)
-        split = _split_ok(meta.Re, H, precision == "bf16x3") and _split_ok(meta.Re, H // 2, True) and (H // 4) % 8 == 0
+        npr = _SPLIT_PRODUCTS.get(precision, 3)
+        split = _split_ok(meta.Re, H, precision in _SPLIT_PRODUCTS) and _split_ok(meta.Re, H // 2, True) and (H // 4) % 8 == 0
         if split:
             # the pair kernel holds each edge row in registers: it also emits gelu(LN(pre)) as the next GEMM's operand.
             # `pre` itself (2 KB per edge row) is stored only when something in backward reads it: with the wgrad of the
@@ -514,10 +524,10 @@ class EdgeFn(torch.autograd.Function):
         if split:
             (M4s, M4t), (M8s, M8t) = ops.split_weights([M4w, M8w])
             ctx.wT = (M4t, M8t)
-            z2 = ops.gemm_split(h1, M4s, bias=M4b)
+            z2 = ops.gemm_split(h1, M4s, bias=M4b, products=npr)
             mu2, rs2, h2 = ops.ln_prep(z2, M5g, M5b, ACT_GELU, drop_p=p2_, seed=sd[3])
             s2 = (mu2, rs2)
-            z3 = ops.gemm_split(h2, M8s, bias=M8b)
+            z3 = ops.gemm_split(h2, M8s, bias=M8b, products=npr)
         else:
             h1 = h2 = None
             z2 = ops.gemm(pre, M4w, NT, bias=M4b, pro=Pro(ACT_GELU, mu0, rs0, M1g, M1b, p1_, sd[2]), x3=x3); s2 = ops.row_stats(z2)
@@ -529,7 +539,7 @@ class EdgeFn(torch.autograd.Function):
         probs = ops.edge_prob_fwd(logit, meta)
         _keep_params(ctx, params)
         ctx.cfg = (B, V, H, heads, (pf_, pa_, p1_, p2_), sd, meta)
-        ctx.split, ctx.x3 = split, x3
+        ctx.split, ctx.x3, ctx.products = split, x3, npr
         ctx.saved = (cv, za, sa, zb, sb, f, qkv, cx, lse, Fm, pre, mu0, rs0, delta, z2, s2, z3, h1, h2, Pa, Pb)
         ctx.save_for_backward(probs)
         return probs
@@ -543,7 +553,7 @@ class EdgeFn(torch.autograd.Function):
         cv, za, sa, zb, sb, f, qkv, cx, lse, Fm, pre, mu0, rs0, delta, z2, s2, z3, h1, h2, Pa, Pb = _saved(ctx)
         (probs,) = ctx.saved_tensors
         G = [None] * len(params)
-        x3 = ctx.x3
+        x3, npr = ctx.x3, ctx.products
         # weight / bias gradients run beside the dgrad chain while the launches are small enough to share the chip
         # (cfg2, 64.5 k edge rows: +0.7 % on the step; cfg5, 1.04 M rows: -1.3 %, every kernel fills it alone)
         lv = _Leaves(dprobs.device, enable=meta.Re <= (1 << 18))
@@ -572,22 +582,22 @@ class EdgeFn(torch.autograd.Function):
                 dz3, _, _, G[21] = ops.ln_act_bwd(dh3, z3, None, None, None, None, ACT_GELU, inplace=True,
                                                   dz_split=dz3_s, want_dz=not (tsplit or tn3))
             if tn3:
-                G[20] = lv.run(lambda: _wgrad_tn(dz3_s, h2), dz3_s, h2)
+                G[20] = lv.run(lambda: _wgrad_tn(dz3_s, h2, npr), dz3_s, h2)
             else:
-                G[20] = lv.run(lambda: (ops.gemm_split(ops.split_transpose(dz3_s, in_sx8=True), ops.split_transpose(z2, p2)) if tsplit
+                G[20] = lv.run(lambda: (ops.gemm_split(ops.split_transpose(dz3_s, in_sx8=True), ops.split_transpose(z2, p2), products=npr) if tsplit
                                         else ops.gemm(dz3, z2, TN, pro=p2, x3=x3)), dz3_s, dz3, z2)
-            dh2 = ops.gemm_split(dz3_s, ctx.wT[1])
+            dh2 = ops.gemm_split(dz3_s, ctx.wT[1], products=npr)
             del dz3, dz3_s
             dz2_s = torch.empty_like(dh2)
             tn2 = _tn_either(dh2, h1)
             dz2, G[18], G[19], G[17] = ops.ln_act_bwd(dh2, z2, s2[0], s2[1], M5g, M5b, ACT_GELU, p2_, sd[3],
                                                       inplace=True, dz_split=dz2_s, want_dz=not (tsplit or tn2))
             if tn2:
-                G[16] = lv.run(lambda: _wgrad_tn(dz2_s, h1), dz2_s, h1)
+                G[16] = lv.run(lambda: _wgrad_tn(dz2_s, h1, npr), dz2_s, h1)
             else:
-                G[16] = lv.run(lambda: (ops.gemm_split(ops.split_transpose(dz2_s, in_sx8=True), ops.split_transpose(pre, p1)) if tsplit
+                G[16] = lv.run(lambda: (ops.gemm_split(ops.split_transpose(dz2_s, in_sx8=True), ops.split_transpose(pre, p1), products=npr) if tsplit
                                         else ops.gemm(dz2, pre, TN, pro=p1, x3=x3)), dz2_s, dz2, pre)
-            dh1 = ops.gemm_split(dz2_s, ctx.wT[0])
+            dh1 = ops.gemm_split(dz2_s, ctx.wT[0], products=npr)
             del dz2, dz2_s
         else:
             if fused_tail:

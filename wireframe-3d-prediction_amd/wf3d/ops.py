@@ -631,8 +631,16 @@ def ln_act_bwd_first(dh, z, x, mu, rs, gamma, beta, act):
     return trio[0], trio[1], trio[2], dW
 
 
-def gemm_split(a_s, b_s, bias=None, out=None, accumulate=False):
-    """C[M,N] = A·B^T (+bias) with A = sx8[M,K], B = sx8[N,K] (bf16x3: hi*hi + hi*lo + lo*hi, fp32 accumulate)."""
+def _products(products):
+    if products not in (1, 3):
+        raise ValueError(f"wf3d: products must be 1 (bf16) or 3 (bf16x3), got {products!r}")
+    return products
+
+
+def gemm_split(a_s, b_s, bias=None, out=None, accumulate=False, products=3):
+    """C[M,N] = A·B^T (+bias) with A = sx8[M,K], B = sx8[N,K] (products=3, bf16x3: hi*hi + hi*lo + lo*hi; products=1,
+    bf16: hi*hi only, wf3d_gemm_bf16; fp32 accumulate)."""
+    _products(products)
     _need_cuda(a_s, b_s, bias, out)
     a_s, b_s = _rows2d(a_s), _rows2d(b_s)
     M, K = a_s.shape
@@ -645,9 +653,10 @@ def gemm_split(a_s, b_s, bias=None, out=None, accumulate=False):
         out = torch.empty(M, N, dtype=torch.float32, device=a_s.device)
     lib = _lib.load()
     ws = scratch(lib.wf3d_gemm_split_ws_bytes(M, N, K), a_s.device)
-    check(lib.wf3d_gemm_split(_p(a_s), _p(b_s), _p(out), _p(bias), M, N, K, a_s.stride(0), b_s.stride(0),
-                              out.stride(0), 1 if accumulate else 0, _p(ws), ws.numel() if ws is not None else 0,
-                              _stream()), "gemm_split")
+    fn = lib.wf3d_gemm_split if products == 3 else lib.wf3d_gemm_bf16
+    check(fn(_p(a_s), _p(b_s), _p(out), _p(bias), M, N, K, a_s.stride(0), b_s.stride(0),
+             out.stride(0), 1 if accumulate else 0, _p(ws), ws.numel() if ws is not None else 0,
+             _stream()), "gemm_split" if products == 3 else "gemm_bf16")
     return out
 
 
@@ -677,8 +686,9 @@ def gemm_split_tn_shape_ok(K, Mo, No, lda, ldb):
     return bool(_lib.load().wf3d_gemm_split_tn_ok(Mo, No, K, lda, ldb))
 
 
-def gemm_split_tn(a_s, b_s, out=None, accumulate=False):
-    """C[Mo,No] = A^T·B with A = sx8[K,Mo], B = sx8[K,No] (wgrad on operands as stored)."""
+def gemm_split_tn(a_s, b_s, out=None, accumulate=False, products=3):
+    """C[Mo,No] = A^T·B with A = sx8[K,Mo], B = sx8[K,No] (wgrad on operands as stored); products as in gemm_split."""
+    _products(products)
     _need_cuda(a_s, b_s, out)
     a_s, b_s = _rows2d(a_s), _rows2d(b_s)
     K, Mo = a_s.shape
@@ -691,9 +701,10 @@ def gemm_split_tn(a_s, b_s, out=None, accumulate=False):
         out = torch.empty(Mo, No, dtype=torch.float32, device=a_s.device)
     lib = _lib.load()
     ws = scratch(lib.wf3d_gemm_split_tn_ws_bytes(Mo, No, K), a_s.device)
-    check(lib.wf3d_gemm_split_tn(_p(a_s), _p(b_s), _p(out), Mo, No, K, a_s.stride(0), b_s.stride(0), out.stride(0),
-                                 1 if accumulate else 0, _p(ws), ws.numel() if ws is not None else 0, _stream()),
-          "gemm_split_tn")
+    fn = lib.wf3d_gemm_split_tn if products == 3 else lib.wf3d_gemm_bf16_tn
+    check(fn(_p(a_s), _p(b_s), _p(out), Mo, No, K, a_s.stride(0), b_s.stride(0), out.stride(0),
+             1 if accumulate else 0, _p(ws), ws.numel() if ws is not None else 0, _stream()),
+          "gemm_split_tn" if products == 3 else "gemm_bf16_tn")
     return out
 
 
