@@ -16,9 +16,25 @@ against the imported reference whenever /root/reference is present.
 All parameters are addressed by the reference's state_dict names, e.g.
 ``encoder.mlp.4.weight`` (reference layouts: models/PointNetEncoder.py:35-65,
 models/VertexPredictor.py:27-61, models/EdgePredictor.py:31-68).
-Dropout is taken as p = 0 everywhere (the reference's p = 0.1 dropouts use the
-global torch RNG and are not reproducible by any other implementation;
-SURVEY.md §9 Q3).
+Dropout: with no `drop=` argument every dropout is the identity (p = 0, or eval
+mode).  The edge functions and model_forward also take `drop=`, explicit
+pre-scaled multiplicative masks (0 where an element is dropped, 1/(1-p) where it
+is kept) for the edge head's four train-mode dropout sites, applied exactly where
+the reference applies them:
+
+    "vertex_proj.5"  after vertex_proj's second LayerNorm        [Bs, V, H]
+    "attention"      on MHA's softmax weights, need_weights path  [Bs, heads, V, V]
+                     (torch.nn.functional.multi_head_attention_forward)
+    "edge_mlp.3"     after the GELU of edge_mlp.2                 [Bs*E, H]
+    "edge_mlp.7"     after the GELU of edge_mlp.6                 [Bs*E, H/2]
+
+A missing key is no dropout at that site.  The masks come either from the
+reference itself (torch's own draws, recorded by
+tests/golden/make_golden_dropout.py; tests/test_dropout_oracle.py pins this
+oracle to the reference's train-mode outputs and gradients under them) or from
+oracle/dropout.py, which recomputes bit for bit the counter-based masks the HIP
+kernels draw, so that a train-mode run of the kernels is compared with this
+oracle under the very same masks (tests/test_dropout_gpu.py).
 """
 import math
 
@@ -146,17 +162,26 @@ def edge_index_pairs(v):
     return [[i, j] for i in range(v) for j in range(i + 1, v)]
 
 
-def edge_vertex_embed(P, c, prefix="edge_predictor."):
+def _drop(drop, site, x):
+    """x times the pre-scaled mask of `site` (identity when there is none)."""
+    if drop is None or drop.get(site) is None:
+        return x
+    m = drop[site]
+    m = torch.as_tensor(m).to(dtype=x.dtype, device=x.device)
+    return x * m.reshape(x.shape)
+
+
+def edge_vertex_embed(P, c, prefix="edge_predictor.", drop=None):
     vp = prefix + "vertex_proj."
     h = F.gelu(_ln(P, vp + "1", _lin(P, vp + "0", c)))            # erf GELU
-    return _ln(P, vp + "4", _lin(P, vp + "3", h))                 # Dropout(.1) -> identity
+    return _drop(drop, "vertex_proj.5", _ln(P, vp + "4", _lin(P, vp + "3", h)))     # Dropout(.1)
 
 
-def edge_self_attention(P, f, num_heads, prefix="edge_predictor."):
+def edge_self_attention(P, f, num_heads, prefix="edge_predictor.", drop=None):
     """nn.MultiheadAttention(batch_first) self-attention, need_weights path
     (torch nn/functional.py multi_head_attention_forward): packed in_proj,
     q scaled by 1/sqrt(head_dim) BEFORE the product, softmax over keys,
-    heads concatenated, out_proj."""
+    dropout on the softmax weights, heads concatenated, out_proj."""
     ap = prefix + "attention."
     Bs, V, E = f.shape
     hd = E // num_heads
@@ -168,25 +193,26 @@ def edge_self_attention(P, f, num_heads, prefix="edge_predictor."):
 
     q = heads(q) * math.sqrt(1.0 / hd)
     s = q @ heads(k).transpose(-1, -2)
-    p = torch.softmax(s, dim=-1)
+    p = _drop(drop, "attention", torch.softmax(s, dim=-1))
     ctx = (p @ heads(v)).transpose(1, 2).reshape(Bs, V, E)
     return F.linear(ctx, P[ap + "out_proj.weight"], P[ap + "out_proj.bias"])
 
 
-def edge_pair_mlp(P, z, prefix="edge_predictor."):
+def edge_pair_mlp(P, z, prefix="edge_predictor.", drop=None):
     ep = prefix + "edge_mlp."
-    h = F.gelu(_ln(P, ep + "1", _lin(P, ep + "0", z)))
-    h = F.gelu(_ln(P, ep + "5", _lin(P, ep + "4", h)))
+    h = _drop(drop, "edge_mlp.3", F.gelu(_ln(P, ep + "1", _lin(P, ep + "0", z))))
+    h = _drop(drop, "edge_mlp.7", F.gelu(_ln(P, ep + "5", _lin(P, ep + "4", h))))
     h = F.gelu(_lin(P, ep + "8", h))
     return _lin(P, ep + "10", h)
 
 
-def edge_forward(P, verts, num_heads=8, prefix="edge_predictor."):
+def edge_forward(P, verts, num_heads=8, prefix="edge_predictor.", drop=None):
     """verts [Bs, V, 3] -> (probs [Bs, E], list of [i, j]).  V <= 1 raises
-    IndexError like the reference (EdgePredictor.py:118)."""
+    IndexError like the reference (EdgePredictor.py:118).
+    drop: {site: pre-scaled mask} of this call (module docstring), or None."""
     Bs, V, _ = verts.shape
-    f = edge_vertex_embed(P, verts, prefix)
-    f = f + edge_self_attention(P, f, num_heads, prefix)
+    f = edge_vertex_embed(P, verts, prefix, drop)
+    f = f + edge_self_attention(P, f, num_heads, prefix, drop)
     pairs = edge_index_pairs(V)
     if not pairs:
         raise IndexError("too many indices for tensor of dimension 1")
@@ -195,16 +221,18 @@ def edge_forward(P, verts, num_heads=8, prefix="edge_predictor."):
     ci, cj = verts[:, i, :], verts[:, j, :]
     dist = torch.linalg.vector_norm(ci - cj, dim=-1, keepdim=True)
     z = torch.cat([f[:, i, :], f[:, j, :], ci, cj, dist], dim=-1)   # 512|512|3|3|1
-    logits = edge_pair_mlp(P, z.reshape(-1, z.shape[-1]), prefix)
+    logits = edge_pair_mlp(P, z.reshape(-1, z.shape[-1]), prefix, drop)
     return torch.sigmoid(logits).reshape(Bs, -1), pairs
 
 
 # --------------------------------------------------------------------------
 # PointCloudToWireframe.forward  (reference models/PointCloudToWireframe.py:43-121)
 # --------------------------------------------------------------------------
-def model_forward(P, x, target_vertex_counts, max_vertices, training=True, num_heads=8, frozen=None):
+def model_forward(P, x, target_vertex_counts, max_vertices, training=True, num_heads=8, frozen=None, drop=None):
     """frozen: optional {"relu": {LayerNorm name: bool mask}, "argmax": {"enc_masked"|"vert_unmasked": [B,C]}}
-    — the piecewise-constant decisions of another run, see _relu_ln."""
+    — the piecewise-constant decisions of another run, see _relu_ln.
+    drop: optional list, per sample, of the edge head's {site: pre-scaled mask} for that sample's one-sample
+    edge_forward call (module docstring); None (or a None entry) is no dropout."""
     g, pf = encoder_forward(P, x, frozen=frozen)
     vo = vertex_forward(P, g, pf, max_vertices, frozen=frozen)
     verts = vo["vertices"]
@@ -215,7 +243,7 @@ def model_forward(P, x, target_vertex_counts, max_vertices, training=True, num_h
         counts = [int(c) for c in vo["actual_vertex_counts"].tolist()]
     probs, indices = [], []
     for s in range(B):
-        p, idx = edge_forward(P, verts[s:s + 1, :counts[s], :], num_heads)
+        p, idx = edge_forward(P, verts[s:s + 1, :counts[s], :], num_heads, drop=None if drop is None else drop[s])
         probs.append(p[0])
         indices.append(idx)
     max_e = max((len(p) for p in probs), default=0)

@@ -60,6 +60,13 @@ def grad_summary_of(name, g):
     return g.norm().item(), (g * probe).sum().item(), g[:64].float().numpy()
 
 
+def unpack_sx8(t):
+    """sx8 tensor [R, C] (fp32 container) -> (hi, lo) float32 [R, C]."""
+    R, C = t.shape
+    b = t.contiguous().view(torch.bfloat16).reshape(R, C // 8, 2, 8)
+    return b[:, :, 0, :].reshape(R, C).float(), b[:, :, 1, :].reshape(R, C).float()
+
+
 def rel_err(a, b):
     """max|a-b| / max(|b|, tiny): error relative to the tensor's scale."""
     a = np.asarray(a, dtype=np.float64)

@@ -51,7 +51,9 @@ TOL_X3 = 2e-4
 TOL_X3_FORCED = 4e-4
 
 
-def _run(precision, B, N, V, counts, din=8, min_rows=1, kernel_masks=False, draws=32):
+def _run(precision, B, N, V, counts, din=8, min_rows=1, kernel_masks=False, draws=32, drop_p=0.0):
+    """drop_p > 0: train-mode dropout at the edge head's four sites; the oracle replays the masks of the seed the forward
+    drew (oracle/dropout.py; tests/test_dropout_gpu.py)."""
     from wf3d import config
     from models.PointCloudToWireframe import PointCloudToWireframe
     old = (config.precision(), config.SPLIT_MIN_ROWS)
@@ -60,16 +62,24 @@ def _run(precision, B, N, V, counts, din=8, min_rows=1, kernel_masks=False, draw
         config.SPLIT_MIN_ROWS = min_rows
     try:
         torch.manual_seed(20)
-        model = PointCloudToWireframe(din, V).to(dev()).set_dropout(0.0)
+        model = PointCloudToWireframe(din, V).to(dev()).set_dropout(drop_p)
         model.train()
         # give LayerNorm affines and biases non-trivial values (default init is gamma=1, beta=0)
         with torch.no_grad():
             for n, p in model.named_parameters():
                 if p.dim() == 1:
                     p.add_(0.05 * torch.randn(p.shape, generator=torch.Generator().manual_seed(len(n))).to(dev()))
+        if drop_p:
+            # a first forward creates the lazily built point_pool_proj, whose initialisation draws from torch's RNG: the
+            # drop seed of every later forward is then the first draw after torch.manual_seed
+            with torch.no_grad():
+                x, cnt, _, _ = _case(100, B, N, V, counts, din)
+                model(x.to(dev()), cnt.to(dev()))
         for seed in range(100, 100 + draws):
             x, cnt, gen, _ = _case(seed, B, N, V, counts, din)
             model.zero_grad(set_to_none=True)
+            if drop_p:
+                torch.manual_seed(seed)
             out = model(x.to(dev()), cnt.to(dev()))
             frozen, n_border = H.capture_decisions(out, model, kernel_masks=kernel_masks)
             if n_border == 0:
@@ -80,7 +90,15 @@ def _run(precision, B, N, V, counts, din=8, min_rows=1, kernel_masks=False, draw
         sum((out[k] * cot[k].to(dev())).sum() for k in cot).backward()
         got = {n: p.grad.detach().cpu().numpy() for n, p in model.named_parameters() if p.grad is not None}
         P = oracle.params_from_module(model, dtype=torch.float64)
-        ref = oracle.model_forward(P, x.double(), cnt, V, training=True, frozen=frozen)
+        drop = None
+        if drop_p:
+            from oracle import dropout as D
+            with torch.random.fork_rng(devices=[]):
+                torch.manual_seed(seed)
+                dseed = int(torch.empty((), dtype=torch.int64).random_().item())    # EdgePredictor.forward_ragged's draw
+            drop = D.edge_head_masks(dseed, [min(int(c), V) for c in cnt], (drop_p,) * 4,
+                                     model.edge_predictor.vertex_proj[4].weight.shape[0], model.edge_predictor._heads)
+        ref = oracle.model_forward(P, x.double(), cnt, V, training=True, frozen=frozen, drop=drop)
         sum((ref[k] * cot[k].double()).sum() for k in cot).backward()
         assert out["edge_indices"] == ref["edge_indices"]
         fwd = H.out_errs(out, ref)

@@ -10,6 +10,7 @@ import torch
 pytestmark = pytest.mark.gpu
 
 import helpers as H  # noqa: E402,F401  (sets sys.path)
+from helpers import unpack_sx8  # noqa: E402
 
 TOL_GEMM = 1e-4
 TOL_ELT = 2e-5
@@ -276,13 +277,6 @@ def test_bad_arguments_raise(ops):
 # ---------------------------------------------------------------------------
 # bf16x3 split-precision path (sx8 operands)
 # ---------------------------------------------------------------------------
-def unpack_sx8(t):
-    """sx8 tensor [R, C] (fp32 container) -> (hi, lo) float32 [R, C]."""
-    R, C = t.shape
-    b = t.contiguous().view(torch.bfloat16).reshape(R, C // 8, 2, 8)
-    return b[:, :, 0, :].reshape(R, C).float(), b[:, :, 1, :].reshape(R, C).float()
-
-
 def ref_split(x):
     hi = x.to(torch.bfloat16).float()
     lo = (x - hi).to(torch.bfloat16).float()

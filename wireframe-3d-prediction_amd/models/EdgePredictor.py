@@ -55,7 +55,13 @@ class EdgePredictor(nn.Module):
     def _dropout_ps(self):
         if not self.training:
             return (0.0, 0.0, 0.0, 0.0)
-        return (self.vertex_proj[5].p, self.attention.dropout, self.edge_mlp[3].p, self.edge_mlp[7].p)
+        ps = (self.vertex_proj[5].p, self.attention.dropout, self.edge_mlp[3].p, self.edge_mlp[7].p)
+        for name, p in zip(("vertex_proj.5", "attention", "edge_mlp.3", "edge_mlp.7"), ps):
+            if not 0.0 <= float(p) < 1.0:
+                # torch would zero the whole site at p = 1; the dropout kernels take p in [0, 1)
+                raise ValueError(f"EdgePredictor: dropout p = {p} at {name} is not supported by the HIP edge head in train mode "
+                                 "(needs 0 <= p < 1)")
+        return ps
 
     def forward_ragged(self, vertices, counts):
         """vertices [B, Vmax, 3]; sample s uses its first counts[s] vertices.
