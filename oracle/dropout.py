@@ -97,15 +97,18 @@ def edge_rows(eoff_s, v, width, seed, p):
     return scaled(seed, r, np.arange(width)[None, :], p)
 
 
-def edge_head_masks(seed, counts, ps, hidden, heads):
+def edge_head_masks(seed, counts, ps, hidden, heads, s0=0, s1=None):
     """Per sample, {site: pre-scaled mask} of one EdgeFn forward with drop seed `seed` and site probabilities `ps`
     (SITES order), in the shapes oracle.reference_cpu.edge_forward(drop=...) takes for a one-sample batch:
     vertex_proj.5 [1, v, hidden], attention [1, heads, v, v], edge_mlp.3 [E, hidden], edge_mlp.7 [E, hidden // 2].
-    A site with p = 0 is left out (no mask)."""
+    A site with p = 0 is left out (no mask).  `counts` are the whole batch's; [s0, s1) selects the samples returned
+    (default all), their rows placed by the batch-global offsets, so that a large batch's masks can be built a few
+    samples at a time."""
     sd = site_seeds(seed)
     voff, eoff = offsets(counts)
     out = []
-    for s, v in enumerate(counts):
+    for s in range(s0, len(counts) if s1 is None else s1):
+        v = counts[s]
         m = {}
         if ps[0] > 0:
             m[SITES[0]] = vertex_rows(voff[s], v, hidden, sd[0], ps[0])[None]

@@ -60,14 +60,14 @@ def _relu_ln(P, name, u, frozen=None):
     result is a smooth function of the arithmetic: relu(v) -> v * mask."""
     v = _ln(P, name, u)
     if frozen is not None and name in frozen.get("relu", {}):
-        return v * frozen["relu"][name].to(v.dtype)
+        return v * frozen["relu"][name].to(device=v.device, dtype=v.dtype)
     return torch.relu(v)
 
 
 def _max_over_points(pf, frozen, key, fill_dead=False):
     """max over dim 1 of pf [B,N,C]; decision-frozen mode gathers the recorded arg-max rows
     frozen["argmax"][key] ([B,C] int64, -1 = no valid row -> 0) instead of re-deciding them."""
-    idx = frozen["argmax"][key]
+    idx = frozen["argmax"][key].to(pf.device)
     got = torch.gather(pf, 1, idx.clamp(min=0).unsqueeze(1)).squeeze(1)
     return torch.where(idx >= 0, got, torch.zeros_like(got))
 
@@ -268,9 +268,9 @@ def params_from_numpy(arrs, requires_grad=True, dtype=torch.float32):
             for k, v in arrs.items()}
 
 
-def params_from_module(module, requires_grad=True, dtype=torch.float32):
-    """Detached CPU copies of a module's state_dict, keyed identically."""
-    return {k: v.detach().to("cpu", dtype).clone().requires_grad_(requires_grad)
+def params_from_module(module, requires_grad=True, dtype=torch.float32, device="cpu"):
+    """Detached copies of a module's state_dict on `device` (default: the CPU), keyed identically."""
+    return {k: v.detach().to(device, dtype).clone().requires_grad_(requires_grad)
             for k, v in module.state_dict().items()}
 
 
