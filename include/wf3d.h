@@ -49,13 +49,18 @@ int wf3d_version(void);
 const char* wf3d_last_error(void);
 
 /* Process-wide run-time switches (everything else is per call).
- *   "tn_rounds" (1..8, default 1 or $WF3D_TN_ROUNDS): workgroups per CU that the large weight-gradient launches of
+ *   "tn_rounds" (1..8, default 1): workgroups per CU that the large weight-gradient launches of
  *       wf3d_gemm_split_tn are cut into.  1 is fastest on an idle chip; with a collective's kernels holding CUs beside
  *       the backward pass (data parallel) a launch of one workgroup per CU waits a whole extra
  *       round for its last workgroup (+67 %), 2 / 4 rounds lose 15 % / 0 % there and cost 2.5 % / 4 % otherwise.
  *   "gemm_cus" (0 = one workgroup per CU, the default; or 8..1024, rounded down to a multiple of 8): workgroups the
  *       persistent kernel of wf3d_gemm_split is launched with.  Its tiles are claimed, so fewer workgroups only leave
  *       CUs to whatever else the caller runs beside it (224 of 256 CUs: +9 % time; scripts/bench_overlap.py).
+ *   "split_kernel" (0, 1, 3 or 6; for tests and diagnostics): 0 = automatic kernel choice, the default; 1 = the
+ *       register-staged kernel for every wf3d_gemm_split / wf3d_gemm_bf16 call; 3 = 256x128 tiles for every split call
+ *       (the three-stage LDS-DMA kernel forward / dgrad, the 256x128 kernel for wf3d_gemm_split_tn); 6 = the 256x256
+ *       forward / dgrad kernel on every shape (wgrad keeps its automatic choice).  The workspace queries follow it, so
+ *       a workspace sized under one value may be too small under another (the launch then does not split K).
  * Returns WF3D_OK, or WF3D_ERR_ARG for an unknown name or a value out of range. */
 int wf3d_set_option(const char* name, int value);
 
@@ -115,7 +120,8 @@ int wf3d_gemm(const wf3d_gemm_t* desc, void* stream);
  * 8 consecutive columns holding [8 x bf16 high | 8 x bf16 low], v ~= hi + lo.
  * ------------------------------------------------------------------------ */
 /* C[M,N] (+)= A·B^T + bias, A = sx8[M,K], B = sx8[N,K] (nn.Linear forward with
- * B = W; its dgrad with A = dY, B = W^T in sx8) */
+ * B = W; its dgrad with A = dY, B = W^T in sx8).  The workspace is written by every call that is given one (split-K
+ * slabs, or the persistent kernel's tile-claim counters), so launches that may run concurrently must not share it. */
 size_t wf3d_gemm_split_ws_bytes(int M, int N, int K);
 int wf3d_gemm_split(const void* A_sx8, const void* B_sx8, float* C, const float* bias, int M, int N, int K,
                     int lda, int ldb, int ldc, int accumulate, void* ws, size_t ws_bytes, void* stream);

@@ -1,13 +1,14 @@
 #!/usr/bin/env python3
 """The edge MLP's four split GEMMs (forward 512->256->128, dgrad back) at cfg2's 64,512 and cfg5's 1,044,480 edge rows:
-time per launch under the default kernel choice; run with WF3D_SPLIT_DMA=3 / 6 to force the 256x128 / 256x256 kernel."""
+time per launch under the default kernel choice; run with SPLIT_KERNEL=3 / 6 to force the 256x128 / 256x256 kernel
+(wf3d_set_option("split_kernel", v), include/wf3d.h)."""
 import os
 import sys
 
 import torch
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "wireframe-3d-prediction_amd"))
-from wf3d import ops  # noqa: E402
+from wf3d import _lib, ops  # noqa: E402
 
 
 def timed(fn, reps=20):
@@ -46,6 +47,7 @@ def wgrads():
 
 
 if __name__ == "__main__":
+    _lib.check(_lib.load().wf3d_set_option(b"split_kernel", int(os.environ.get("SPLIT_KERNEL", 0))), "split_kernel")
     if len(sys.argv) > 1 and sys.argv[1] == "wgrad":
         wgrads()
     else:

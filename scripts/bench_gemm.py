@@ -1,5 +1,6 @@
 """Micro-benchmark of wf3d_gemm at the encoder's shapes (cfg2: M = 32*4096 rows).
-Interleaved rounds in one process, random data, median per shape (TFLOP/s)."""
+Interleaved rounds in one process, random data, median per shape (TFLOP/s).  SPLIT_KERNEL=v forces a split-GEMM kernel
+(wf3d_set_option("split_kernel", v), include/wf3d.h)."""
 import os
 import statistics
 import sys
@@ -7,8 +8,9 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "wireframe-3d-prediction_amd"))
 import torch  # noqa: E402
-from wf3d import ops  # noqa: E402
+from wf3d import _lib, ops  # noqa: E402
 
+_lib.check(_lib.load().wf3d_set_option(b"split_kernel", int(os.environ.get("SPLIT_KERNEL", 0))), "split_kernel")
 dev = torch.device("cuda:0")
 M = int(os.environ.get("M", 131072))
 layers = [(512, 1024), (1024, 2048), (2048, 1024), (1024, 512)]   # (K_in, N_out)

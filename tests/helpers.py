@@ -1,4 +1,5 @@
 """Shared helpers for the test-suite (rebuild fixture inputs from detgen)."""
+import contextlib
 import os
 import sys
 
@@ -134,3 +135,14 @@ def check_grad_summaries(gold, named_grads, tol, skip=()):
         if max(e_norm, e_dot) > tol or e_head > 20 * tol:
             bad.append((name, e_norm, e_dot, e_head))
     return bad
+
+
+@contextlib.contextmanager
+def lib_option(name, value, default=0):
+    """wf3d_set_option(name, value) for the body of a `with`, then `default` again (process-wide switches)."""
+    from wf3d import _lib
+    _lib.check(_lib.load().wf3d_set_option(name.encode(), value), f"wf3d_set_option {name}")
+    try:
+        yield
+    finally:
+        _lib.check(_lib.load().wf3d_set_option(name.encode(), default), f"wf3d_set_option {name}")

@@ -40,6 +40,14 @@ def test_library_exports_nothing_but_the_header():
     assert exported == set(declared_symbols()), sorted(exported ^ set(declared_symbols()))
 
 
+def test_library_reads_no_environment():
+    """kernel choice is never left to a variable no caller sees: libwf3d.so does not import getenv."""
+    import subprocess
+    from wf3d import _lib
+    out = subprocess.run(["nm", "-D", "--undefined-only", _lib.LIB_PATH], capture_output=True, text=True, check=True).stdout
+    assert not {ln.split()[-1].split("@")[0] for ln in out.splitlines() if ln.strip()} & {"getenv", "secure_getenv"}
+
+
 def test_set_option_validates():
     from wf3d import _lib
     lib = _lib.load()
@@ -48,8 +56,53 @@ def test_set_option_validates():
     assert lib.wf3d_set_option(b"tn_rounds", 9) == -1 and b"1..8" in lib.wf3d_last_error()
     assert lib.wf3d_set_option(b"gemm_cus", 224) == 0 and lib.wf3d_set_option(b"gemm_cus", 0) == 0
     assert lib.wf3d_set_option(b"gemm_cus", 3) == -1 and b"gemm_cus" in lib.wf3d_last_error()
+    for v in (3, 6, 1, 0):
+        assert lib.wf3d_set_option(b"split_kernel", v) == 0
+    for v in (-1, 2, 4, 7):
+        assert lib.wf3d_set_option(b"split_kernel", v) == -1 and b"split_kernel" in lib.wf3d_last_error()
     assert lib.wf3d_set_option(b"no_such_switch", 1) == -1 and b"unknown option" in lib.wf3d_last_error()
     assert lib.wf3d_set_option(None, 1) == -1
+
+
+# Workspace bytes of the split-K GEMM families as recorded before their planners were merged, for every shape bench.py launches
+# at cfg1/2/4/5 and shapes on each side of each threshold.  "M,N,K[,layout]:k[/k2]" = k * M * N * 4 bytes (k K ranges; k2 under
+# tn_rounds 2 where it differs); "c" = the persistent split kernel's 2048-byte control block.
+WS_TABLE = {
+    "G": """32,3,256,1:2 32,256,3,0:0 32,256,512,1:4 32,256,4096,0:32 32,512,256,0:2 32,512,512,0:4 32,512,512,1:4
+        32,512,1536,1:12 32,1536,512,0:4 128,256,496,2:4 256,3,32,2:0 256,3,512,2:4 256,3,2048,2:16 256,3,8192,2:64
+        256,512,496,2:4 496,128,256,0:2 496,256,128,1:0 496,256,512,0:4 496,512,256,1:2 512,3,32,2:0 512,3,256,1:2
+        512,3,512,2:4 512,3,2048,2:16 512,3,8192,2:64 512,8,131072,2:128 512,128,4096,0:32 512,256,3,0:0 512,256,32,2:0
+        512,256,512,1:4 512,256,512,2:4 512,256,2048,2:16 512,256,8192,2:16 512,512,32,2:0 512,512,256,0:2
+        512,512,512,0:4 512,512,512,1:4 512,512,512,2:4 512,512,1536,1:12 512,512,2048,2:8 512,512,8192,2:8
+        512,1536,512,0:3 1024,128,224,0:0 1024,128,256,0:2 1024,128,4096,0:32 1536,512,32,2:0 1536,512,512,2:3
+        1536,512,2048,2:3 1536,512,8192,2:11 2048,3,256,1:2 2048,128,4096,0:32 2048,256,3,0:0 2048,256,512,1:4
+        2048,512,256,0:0 2048,512,512,0:0 2048,512,512,1:0 2048,512,1536,1:0 2048,512,8192,2:8 2048,1536,512,0:0
+        8192,3,256,1:2 8192,256,3,0:0 8192,256,512,1:0 8192,512,256,0:0 8192,512,512,0:0 8192,512,512,1:0
+        8192,512,1536,1:0 8192,1536,512,0:0 24448,128,4096,0:3 24576,128,4096,0:3 32640,128,4096,0:3 32768,128,4096,0:0""",
+    "S": """1000,200,40:c 1000,200,224:c 1000,200,256:2 1024,128,4096:32 1024,512,1024:8 1024,1024,512:4
+        1024,1024,2048:16 1024,2048,1024:8 2048,128,4096:32 4096,128,4096:32 4096,512,4104:8 16128,128,256:2
+        16128,256,128:c 16128,256,512:4 16128,512,256:c 48896,128,4096:3 49152,128,4096:c 64512,128,256:c
+        64512,256,128:c 64512,256,512:c 64512,512,256:c 65280,128,4096:c 65536,128,4096:c 65536,384,512:c
+        131072,512,1024:c 131072,1024,512:c 131072,1024,2048:c 131072,2048,1024:c 1044480,128,256:c 1044480,256,128:c
+        1044480,256,512:c 1044480,512,256:c""",
+    "T": """256,128,16128:56 256,128,64512:224 256,128,1044480:255 256,512,16128:56 256,512,64512:126
+        256,512,1044480:128 256,1024,65536:64 256,2048,65536:32 256,4096,65536:16/32 256,48896,65536:2/3
+        256,49152,65536:2/3 256,65280,65536:2/3 256,65536,65536:0 512,384,8192:64 512,1024,1024:8 512,1024,131072:32
+        1024,128,65536:128 1024,256,224:0 1024,256,256:0 1024,512,1024:8 1024,512,131072:32 1024,2048,1024:8
+        1024,2048,131072:8/16 2048,128,65536:64 2048,1024,1024:8 2048,1024,131072:8/16 4096,128,65536:32/64
+        48896,128,65536:3/6 49152,128,65536:3/6 65280,128,65536:3/5 65536,128,65536:0""",
+}
+
+
+def test_workspace_sizes_pin_every_split_k_plan():
+    from wf3d import _lib
+    lib = _lib.load()
+    fns = {"G": lib.wf3d_gemm_ws_bytes, "S": lib.wf3d_gemm_split_ws_bytes, "T": lib.wf3d_gemm_split_tn_ws_bytes}
+    for r in (1, 2):
+        with H.lib_option("tn_rounds", r, default=1):
+            for fam, e in ((f, e) for f, entries in WS_TABLE.items() for e in entries.split()):
+                a, k = [int(x) for x in e.split(":")[0].split(",")], e.split(":")[1].split("/")[r - 1 if "/" in e else 0]
+                assert fns[fam](*a) == (2048 if k == "c" else int(k) * a[0] * a[1] * 4), (fam, e, r)
 
 
 def test_argument_errors_reported_without_gpu():

@@ -8,16 +8,12 @@ products matter) and once on small-integer data (every fp32 sum exact: a slice d
 bit-exactly).  Reference lines replaced: models/PointNetEncoder.py:94 (the per-point Linear chain), its autograd
 backward, and models/EdgePredictor.py:137 (edge MLP) at max_vertices = 256.
 """
-import os
-import subprocess
-import sys
-
 import pytest
 import torch
 
 pytestmark = pytest.mark.gpu
 
-import helpers as H  # noqa: E402,F401  (sets sys.path)
+import helpers as H  # noqa: E402  (sets sys.path)
 
 TOL_SPLIT = 3e-5          # bf16x3 keeps ~16 significant bits per product; the gate on the path is 1e-4
 M_ENC = 131072            # cfg2: 32 clouds x 4096 points
@@ -145,36 +141,21 @@ def test_edge_mlp_gemms_at_cfg5_row_count(ops, K, N):
     assert r < TOL_SPLIT, f"edge wgrad {N}x{K}: {r:.2e}"
 
 
-CHILD = r"""
-import sys, torch
-sys.path.insert(0, sys.argv[1])
-from wf3d import ops
-dev = torch.device("cuda:0")
-g = torch.Generator(device=dev).manual_seed(21)
-M, K, N = 131072, 512, 1024
-A = torch.randn(M, K, generator=g, device=dev); W = torch.randn(N, K, generator=g, device=dev) * 0.05; b = torch.randn(N, generator=g, device=dev)
-got = ops.gemm_split(ops.split_rows(A), ops.split_rows(W), bias=b)
-err = 0.0; top = 0.0
-for r in range(0, M, 16384):
-    want = A[r:r + 16384].double() @ W.double().T + b.double()
-    err = max(err, float((got[r:r + 16384].double() - want).abs().max())); top = max(top, float(want.abs().max()))
-print("REL", err / top)
-"""
-
-
-def test_persistent_kernel_with_reserved_cus_in_child_process():
-    """WF3D_RESERVED_CUS=8 (read once per process): the persistent grid is 248 workgroups, every tile still computed once."""
-    env = dict(os.environ, WF3D_RESERVED_CUS="8")
-    out = subprocess.run([sys.executable, "-c", CHILD, H.PKG], env=env, capture_output=True, text=True, timeout=600)
-    assert out.returncode == 0, out.stderr[-2000:]
-    rel = float([ln for ln in out.stdout.splitlines() if ln.startswith("REL")][-1].split()[1])
-    assert rel < TOL_SPLIT
+def test_persistent_kernel_on_248_workgroups(ops):
+    """gemm_cus = 248 (the grid of 8 reserved CUs): the persistent grid is 248 workgroups, every tile computed once."""
+    g = torch.Generator(device=dev()).manual_seed(21)
+    M, K, N = 131072, 512, 1024
+    A, W = torch.randn(M, K, generator=g, device=dev()), torch.randn(N, K, generator=g, device=dev()) * 0.05
+    b = torch.randn(N, generator=g, device=dev())
+    with H.lib_option("gemm_cus", 248):
+        got = ops.gemm_split(ops.split_rows(A), ops.split_rows(W), bias=b)
+    assert worst_nt(got, A, W, b)[0] < TOL_SPLIT
 
 
 @pytest.mark.parametrize("cus", [8, 200])
 def test_persistent_kernel_on_fewer_workgroups(cus):
     """wf3d_set_option("gemm_cus", n): the claimed tiles are all computed, once each, whatever the grid."""
-    from wf3d import _lib, ops
+    from wf3d import ops
     dev = torch.device("cuda:0")
     g = torch.Generator(device=dev).manual_seed(22)
     M, K, N = 131072, 512, 1024
@@ -182,12 +163,8 @@ def test_persistent_kernel_on_fewer_workgroups(cus):
     W = torch.randn(N, K, generator=g, device=dev) * 0.05
     As, Ws = ops.split_rows(A), ops.split_rows(W)
     want = ops.gemm_split(As, Ws)
-    lib = _lib.load()
-    assert lib.wf3d_set_option(b"gemm_cus", cus) == 0
-    try:
+    with H.lib_option("gemm_cus", cus):
         got = ops.gemm_split(As, Ws)
-    finally:
-        lib.wf3d_set_option(b"gemm_cus", 0)
     assert torch.equal(got, want)
 
 

@@ -4,17 +4,13 @@
    operands themselves (view as bf16, first 8 of every 16).  What is left is fp32 accumulation only, so the bound is
    5e-6 of max |C64| — bf16x3's output misses it by ~2^-9, so the test tells the two arithmetics apart.  Every kernel
    the entry points can select is reached: the persistent and plain 256x256 kernels, the XCD-mapped split-K wgrad,
-   dma3, the 256x128 TN kernel, the register-staged fallback (K % 32 != 0) and, in child processes, the forced
-   variants (WF3D_SPLIT_DMA is read once per process).
+   dma3, the 256x128 TN kernel, the register-staged fallback (K % 32 != 0) and the variants forced with
+   wf3d_set_option("split_kernel", v).
 2. - 6. the model in "bf16" mode: golden forward, decision-frozen gradients at the production kernel selection, the
    three-step training trajectory, no state leaking between modes, graph capture.
 
 Bounds TOL_BF16_* were set once, at 2x the first measurement on an MI355X (values beside them and in DESIGN.md §2).
 """
-import os
-import subprocess
-import sys
-
 import numpy as np
 import pytest
 import torch
@@ -214,36 +210,15 @@ def test_bf16_exact_on_integer_data(ops, K, N):
     assert err == 0.0
 
 
-CHILD = r"""
-import sys, torch
-sys.path.insert(0, sys.argv[1])
-from wf3d import ops
-dev = torch.device("cuda:0")
-def rnd(*s, seed):
-    g = torch.Generator(device=dev).manual_seed(seed)
-    return torch.randn(*s, generator=g, device=dev)
-def hi(s):
-    R, C = s.shape
-    return s.contiguous().view(torch.bfloat16).view(R, -1, 16)[:, :, :8].reshape(R, C).double()
-worst = 0.0
-for (M, N, K) in [(4096, 512, 256), (65536, 1024, 512), (1000, 384, 128)]:
-    As, Ws, b = ops.split_rows(rnd(M, K, seed=1)), ops.split_rows(rnd(N, K, seed=2) * 0.1), rnd(N, seed=3)
-    got = ops.gemm_split(As, Ws, bias=b, products=1).double()
-    want = hi(As) @ hi(Ws).T + b.double()
-    worst = max(worst, float((got - want).abs().max() / want.abs().max()))
-print("REL", worst)
-"""
-
-
-@pytest.mark.parametrize("forced", ["3", "6", "0"])
-def test_bf16_forced_variants_in_child_process(forced):
-    """WF3D_SPLIT_DMA=3 / 6 / 0 (read once per process): every problem through dma3, the 256x256 kernels, or the
-    register-staged one."""
-    env = dict(os.environ, WF3D_SPLIT_DMA=forced)
-    r = subprocess.run([sys.executable, "-c", CHILD, H.PKG], env=env, capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, r.stderr[-2000:]
-    rel = float(r.stdout.split("REL")[-1])
-    assert rel < TOL_ORACLE, (forced, rel)
+@pytest.mark.parametrize("kernel", [3, 6, 1])
+def test_bf16_forced_variants(ops, kernel):
+    """split_kernel = 3 / 6 / 1: every problem through dma3, the 256x256 kernels, or the register-staged one."""
+    worst = 0.0
+    with H.lib_option("split_kernel", kernel):
+        for (M, N, K) in [(4096, 512, 256), (65536, 1024, 512), (1000, 384, 128)]:
+            As, Ws, b = ops.split_rows(rnd(M, K, seed=1)), ops.split_rows(rnd(N, K, seed=2, scale=0.1)), rnd(N, seed=3)
+            worst = max(worst, err_nt(ops.gemm_split(As, Ws, bias=b, products=1), As, Ws, b)[0])
+    assert worst < TOL_ORACLE, (kernel, worst)
 
 
 # ---------------------------------------------------------------------------------------------------------------------

@@ -11,19 +11,14 @@
 //
 // Vertex rows are COMPACT: sample s owns rows voff[s] .. voff[s+1]-1 of every
 // [Rv, *] matrix, so ragged batches cost nothing and no key mask is needed.
-#include <stdlib.h>
-
 #include "wf3d_common.h"
 
 namespace {
 
 constexpr int ATT_WAVES = 4;
 
-// head_dim 64 runs on the matrix cores (attn_mfma.hip); WF3D_ATTN_MFMA=0 forces the VALU kernels below
-bool use_mfma(int E, int heads) {
-    static const int on = [] { const char* e = getenv("WF3D_ATTN_MFMA"); return e ? atoi(e) : 1; }();
-    return on && E / heads == 64;
-}
+// head_dim 64 runs on the matrix cores (attn_mfma.hip), every other one on the VALU kernels below
+bool use_mfma(int E, int heads) { return E / heads == 64; }
 
 struct AttnParams {
     const float* qkv;      // [Rv, 3E]

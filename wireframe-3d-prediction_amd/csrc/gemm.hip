@@ -26,8 +26,6 @@
 // The LayerNorm-apply + ReLU/GELU (+dropout) of the *previous* layer is fused
 // into the staging pass of the activation operand, so normalised activations
 // are never written to HBM: only pre-LN z and per-row (mu, rstd) exist.
-#include <stdlib.h>
-
 #include <type_traits>
 
 #include "wf3d_common.h"
@@ -518,8 +516,8 @@ __global__ __launch_bounds__(256, 2) void gemm_kernel(const GemmParams p) {
     else      gemm_body<WAVES_M, WAVES_N, TM, TN, A_KC, B_KC, ACT, PRO, false, SPLIT, X3, R, NP>(p, smem, m0, n0, kt0, kt1);
 }
 
-// split-K combine: deterministic slab sum + epilogue terms
-__global__ __launch_bounds__(256) void gemm_splitk_reduce(const GemmParams p) {
+// split-K combine (wf3d_splitk_combine): deterministic slab sum + epilogue terms
+__global__ __launch_bounds__(256) void splitk_combine_kernel(const SplitKCombine p) {
     const size_t total = (size_t)p.M * p.N;
     for (size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (size_t)gridDim.x * 256) {
         const int row = (int)(idx / p.N), col = (int)(idx % p.N);
@@ -534,10 +532,11 @@ __global__ __launch_bounds__(256) void gemm_splitk_reduce(const GemmParams p) {
     }
 }
 
-// The same combine for many slabs (few output tiles, up to 256 K ranges): a wave owns 16 consecutive outputs, lane =
-// (slab lane 0..15, float4 0..3) walks slabs sl, sl + 16, ... with four loads in flight, the 16 partial sums meet in
-// a fixed shuffle tree (deterministic).
-__global__ __launch_bounds__(256) void gemm_splitk_reduce_wide(const GemmParams p) {
+// The same combine for many slabs (the few-tile wgrads split K up to 256 ways): a serial walk over the slabs is one
+// dependent 4-byte load per slab per thread (126 slabs of 128 KB took 55 us).  Here a wave owns 16 consecutive
+// outputs; lane = (slab lane 0..15, float4 0..3) walks slabs sl, sl + 16, ... four loads in flight, and the 16
+// partial sums meet in a fixed shuffle tree — the result does not depend on timing.
+__global__ __launch_bounds__(256) void splitk_combine_wide_kernel(const SplitKCombine p) {
     const size_t total = (size_t)p.M * p.N;
     const int lane = threadIdx.x & 63, sl = lane >> 2, q = lane & 3;
     const size_t idx = ((size_t)blockIdx.x * 4 + (threadIdx.x >> 6)) * 16 + q * 4;
@@ -573,25 +572,6 @@ __global__ __launch_bounds__(256) void gemm_splitk_reduce_wide(const GemmParams 
     }
 }
 
-struct SplitPlan { int ksplit, kt_per; };
-
-SplitPlan plan_split(int M, int N, int K, int bm, int bn) {
-    const long tiles = (long)wf3d_cdiv(M, bm) * wf3d_cdiv(N, bn);
-    const int ktotal = wf3d_cdiv(K, BK);
-    SplitPlan s{1, ktotal};
-    if (tiles >= 256 || ktotal < 8) return s;
-    int want = (int)((512 + tiles - 1) / tiles);
-    int ks = want < ktotal / 4 ? want : ktotal / 4;
-    // Few tiles and a very long reduction (first-layer wgrad: 512 x 8 outputs over K = B*N rows) stream
-    // their operands from HBM: they need >= 2 workgroups per CU in flight, slabs stay tiny.
-    const int cap = tiles <= 8 ? 256 : 64;
-    if (ks > cap) ks = cap;
-    if (ks < 2) return s;
-    s.kt_per = wf3d_cdiv(ktotal, ks);
-    s.ksplit = wf3d_cdiv(ktotal, s.kt_per);      // no empty split
-    return s;
-}
-
 inline bool small_m(int M) { return M <= 64; }
 // A few thousand rows (the edge head's per-vertex Linears, M = sum of vertex counts): 128 x 128 tiles give fewer than
 // one workgroup per CU and then need split-K slabs plus a reduce launch; 64 x 64 tiles (one MFMA tile per wave) fill
@@ -599,8 +579,7 @@ inline bool small_m(int M) { return M <= 64; }
 // reduction is short enough that the halved operand reuse does not matter.
 inline bool mid_tile(int M, int N, int K) {
     const long t128 = (long)wf3d_cdiv(M, 128) * wf3d_cdiv(N, 128), t64 = (long)wf3d_cdiv(M, 64) * wf3d_cdiv(N, 64);
-    static const int lim = [] { const char* e = getenv("WF3D_MID_T128"); return e ? atoi(e) : 256; }();
-    return M > 64 && t128 < lim && t64 >= 128 && K <= 2048;
+    return M > 64 && t128 < 256 && t64 >= 128 && K <= 2048;
 }
 
 template <int WM, int WN, int TM, int TN, bool AKC, bool BKC, int ACT, bool PRO, bool X3 = false>
@@ -627,11 +606,10 @@ void launch_tn(const GemmParams& p, int kind, bool x3, hipStream_t st) {
 // wgrad of a per-vertex Linear (a [512, 512]-class output over a few thousand rows): 128 x 128 tiles leave 16 of them,
 // each cut into 16 K ranges of 4 slices; 64 x 64 tiles give 64, cut 8 ways: 22 -> 16 us at [512, 512] x 2048 rows,
 // 38 -> 29 us at [1536, 512] (scripts/bench_gemm_mid.py wgrad).  Long reductions over the larger outputs keep the
-// big tile (77 vs 81 us at [1536, 512] x 8192).  WF3D_TN_MID=0 switches it off.
+// big tile (77 vs 81 us at [1536, 512] x 8192).
 inline bool tn_mid(int M, int N, int K) {
-    static const int on = [] { const char* e = getenv("WF3D_TN_MID"); return e ? atoi(e) : 1; }();
     const long t128 = (long)wf3d_cdiv(M, 128) * wf3d_cdiv(N, 128);
-    return on && M > 64 && N > 64 && t128 < 64 && (K <= 4096 || t128 <= 16);
+    return M > 64 && N > 64 && t128 < 64 && (K <= 4096 || t128 <= 16);
 }
 
 }  // namespace
@@ -640,8 +618,8 @@ extern "C" size_t wf3d_gemm_ws_bytes(int M, int N, int K, int layout) {
     if (M <= 0 || N <= 0 || K <= 0) return 0;
     const bool small = layout != WF3D_TN && small_m(M);
     const bool mid = layout != WF3D_TN ? (!small && mid_tile(M, N, K)) : tn_mid(M, N, K);
-    SplitPlan s = plan_split(M, N, K, small ? 32 : (mid ? 64 : 128), mid ? 64 : 128);
-    return s.ksplit > 1 ? (size_t)s.ksplit * M * N * sizeof(float) : 0;
+    const int bm = small ? 32 : (mid ? 64 : 128), bn = mid ? 64 : 128;
+    return wf3d_splitk_slab_bytes(wf3d_splitk_plan(WF3D_SPLITK_GEMM, (long)wf3d_cdiv(M, bm) * wf3d_cdiv(N, bn), wf3d_cdiv(K, BK)), M, N);
 }
 
 extern "C" int wf3d_gemm(const wf3d_gemm_t* d, void* stream) {
@@ -689,9 +667,8 @@ extern "C" int wf3d_gemm(const wf3d_gemm_t* d, void* stream) {
     const int bm = small ? 32 : (mid ? 64 : 128), bn = mid ? 64 : 128;
     p.nbm = wf3d_cdiv(d->M, bm);
     p.nbn = wf3d_cdiv(d->N, bn);
-    SplitPlan s = plan_split(d->M, d->N, d->K, bm, bn);
-    const size_t need = s.ksplit > 1 ? (size_t)s.ksplit * d->M * d->N * sizeof(float) : 0;
-    if (need && (d->ws == nullptr || d->ws_bytes < need)) { s.ksplit = 1; s.kt_per = wf3d_cdiv(d->K, BK); }
+    const int ktotal = wf3d_cdiv(d->K, BK);
+    const SplitK s = wf3d_splitk_fit(wf3d_splitk_plan(WF3D_SPLITK_GEMM, (long)p.nbm * p.nbn, ktotal), ktotal, d->M, d->N, d->ws, d->ws_bytes);
     p.ksplit = s.ksplit; p.kt_per_split = s.kt_per;
     p.slab = s.ksplit > 1 ? (float*)d->ws : nullptr;
 
@@ -713,86 +690,40 @@ extern "C" int wf3d_gemm(const wf3d_gemm_t* d, void* stream) {
         else                              launch_tn<WF3D_ACT_NONE, true>(p, kind, x3, st);
     }
     WF3D_LAUNCH_CHECK();
-    if (p.ksplit > 1) {
-        const size_t total = (size_t)p.M * p.N;
-        if (p.ksplit > 16 && p.N % 4 == 0 && ((uintptr_t)p.slab % 16 == 0)) {
-            hipLaunchKernelGGL(gemm_splitk_reduce_wide, dim3((unsigned)((total + 63) / 64)), dim3(256), 0, st, p);
-        } else {
-            int blocks = (int)((total + 255) / 256);
-            if (blocks > 2048) blocks = 2048;
-            hipLaunchKernelGGL(gemm_splitk_reduce, dim3(blocks), dim3(256), 0, st, p);
-        }
-        WF3D_LAUNCH_CHECK();
+    if (p.ksplit == 1) return WF3D_OK;
+    return wf3d_splitk_combine({p.slab, p.C, p.bias, p.addend, p.lr_u, p.lr_v, p.M, p.N, p.ldc, p.ld_addend, p.lr_k, p.ld_lr_u,
+                                p.ld_lr_v, p.ksplit, p.accumulate}, false, st);
+}
+
+int wf3d_splitk_combine(const SplitKCombine& c, bool narrow_only, hipStream_t st) {
+    const size_t total = (size_t)c.M * c.N;
+    if (!narrow_only && c.ksplit > 16 && c.N % 4 == 0 && ((uintptr_t)c.slab % 16 == 0)) {
+        hipLaunchKernelGGL(splitk_combine_wide_kernel, dim3((unsigned)((total + 63) / 64)), dim3(256), 0, st, c);
+    } else {
+        int blocks = (int)((total + 255) / 256);
+        if (blocks > 2048) blocks = 2048;
+        hipLaunchKernelGGL(splitk_combine_kernel, dim3(blocks), dim3(256), 0, st, c);
     }
+    WF3D_LAUNCH_CHECK();
     return WF3D_OK;
 }
 
-// ---------------------------------------------------------------------------
-// bf16x3 split-precision GEMM (NT form): C[M,N] = A·B^T (+bias) with A, B in the
-// "sx8" split format produced by wf3d_split_rows / wf3d_ln_prep: logical [R, K]
-// fp32 values stored as [R][K/8][2][8] bf16 = 8 high parts then 8 low parts per
-// 8 consecutive k (same bytes and row pitch as the fp32 tensor).
-// ---------------------------------------------------------------------------
-extern "C" size_t wf3d_gemm_split_ws_bytes(int M, int N, int K) {
-    if (M <= 0 || N <= 0 || K <= 0) return 0;
-    SplitPlan s = plan_split(M, N, K, 128, 128);
-    const size_t a = s.ksplit > 1 ? (size_t)s.ksplit * M * N * sizeof(float) : 0;
-    const size_t b = wf3d_gemm_split_dma_ws_bytes(M, N, K);
-    return a > b ? a : b;
-}
-
-namespace {
-// products: 3 = bf16x3 (wf3d_gemm_split), 1 = plain bf16 on the hi planes (wf3d_gemm_bf16).  Same checks, same kernel
-// choice, same workspace either way.
-int gemm_split_impl(const char* fn, int products, const void* A_sx8, const void* B_sx8, float* C, const float* bias, int M,
-                    int N, int K, int lda, int ldb, int ldc, int accumulate, void* ws, size_t ws_bytes, void* stream) {
-    WF3D_CHECK(M >= 0 && N >= 0 && K > 0, WF3D_ERR_ARG, "%s: bad dims", fn);
-    if (M == 0 || N == 0) return WF3D_OK;
-    WF3D_CHECK(A_sx8 && B_sx8 && C, WF3D_ERR_ARG, "%s: null operand", fn);
-    WF3D_CHECK(K % 8 == 0 && lda % 8 == 0 && ldb % 8 == 0, WF3D_ERR_UNSUPPORTED,
-               "%s: K, lda, ldb must be multiples of 8 (sx8 groups)", fn);
-    WF3D_CHECK(lda >= K && ldb >= K && ldc >= N, WF3D_ERR_ARG, "%s: leading dimension too small", fn);
-    WF3D_CHECK(((uintptr_t)A_sx8 % 16 == 0) && ((uintptr_t)B_sx8 % 16 == 0), WF3D_ERR_ARG, "%s: operands must be 16-byte aligned", fn);
-    {
-        // LDS-DMA staged kernel for every shape it supports (WF3D_SPLIT_DMA=0 forces the register-staged one)
-        static const int use_dma = [] { const char* e = getenv("WF3D_SPLIT_DMA"); return e ? atoi(e) : 1; }();
-        if (use_dma && wf3d_gemm_split_dma_ok(M, N, K, lda, ldb))
-            return wf3d_gemm_split_dma(A_sx8, B_sx8, C, bias, M, N, K, lda, ldb, ldc, accumulate, ws, ws_bytes, stream, products);
-    }
+// The register-staged bf16x3 / bf16 split GEMM on sx8 operands (wf3d_gemm_split / wf3d_gemm_bf16 take it for K % 32 != 0;
+// gemm_split.hip chooses and plans).  products: 3 = bf16x3, 1 = plain bf16 on the hi planes.
+int wf3d_gemm_split_regs(int products, const void* A_sx8, const void* B_sx8, float* C, const float* bias, int M, int N, int K,
+                         int lda, int ldb, int ldc, int accumulate, SplitK s, float* slab, hipStream_t st) {
     GemmParams p{};
     p.A = (const float*)A_sx8; p.B = (const float*)B_sx8; p.C = C; p.bias = bias;
     p.M = M; p.N = N; p.K = K; p.lda = lda; p.ldb = ldb; p.ldc = ldc;
     p.accumulate = accumulate;
     p.vecA = p.vecB = p.vecP = 1;
     p.nbm = wf3d_cdiv(M, 128); p.nbn = wf3d_cdiv(N, 128);
-    SplitPlan sp = plan_split(M, N, K, 128, 128);
-    const size_t need = sp.ksplit > 1 ? (size_t)sp.ksplit * M * N * sizeof(float) : 0;
-    if (need && (ws == nullptr || ws_bytes < need)) { sp.ksplit = 1; sp.kt_per = wf3d_cdiv(K, BK); }
-    p.ksplit = sp.ksplit; p.kt_per_split = sp.kt_per;
-    p.slab = sp.ksplit > 1 ? (float*)ws : nullptr;
-    hipStream_t st = (hipStream_t)stream;
+    p.ksplit = s.ksplit; p.kt_per_split = s.kt_per;
+    p.slab = s.ksplit > 1 ? slab : nullptr;
     dim3 grid(p.nbm * p.nbn, 1, p.ksplit);
     if (products == 1) hipLaunchKernelGGL((gemm_kernel<2, 2, 2, 2, true, true, 0, false, true, false, 1>), grid, dim3(256), 0, st, p);
     else               hipLaunchKernelGGL((gemm_kernel<2, 2, 2, 2, true, true, 0, false, true>), grid, dim3(256), 0, st, p);
     WF3D_LAUNCH_CHECK();
-    if (p.ksplit > 1) {
-        const size_t total = (size_t)M * N;
-        int blocks = (int)((total + 255) / 256);
-        if (blocks > 2048) blocks = 2048;
-        hipLaunchKernelGGL(gemm_splitk_reduce, dim3(blocks), dim3(256), 0, st, p);
-        WF3D_LAUNCH_CHECK();
-    }
-    return WF3D_OK;
-}
-}  // namespace
-
-extern "C" int wf3d_gemm_split(const void* A_sx8, const void* B_sx8, float* C, const float* bias, int M, int N, int K,
-                               int lda, int ldb, int ldc, int accumulate, void* ws, size_t ws_bytes, void* stream) {
-    return gemm_split_impl("wf3d_gemm_split", 3, A_sx8, B_sx8, C, bias, M, N, K, lda, ldb, ldc, accumulate, ws, ws_bytes, stream);
-}
-
-// bf16 mode: one bf16 MFMA per product on the hi planes of the sx8 operands; workspace: wf3d_gemm_split_ws_bytes
-extern "C" int wf3d_gemm_bf16(const void* A_sx8, const void* B_sx8, float* C, const float* bias, int M, int N, int K,
-                              int lda, int ldb, int ldc, int accumulate, void* ws, size_t ws_bytes, void* stream) {
-    return gemm_split_impl("wf3d_gemm_bf16", 1, A_sx8, B_sx8, C, bias, M, N, K, lda, ldb, ldc, accumulate, ws, ws_bytes, stream);
+    if (p.ksplit == 1) return WF3D_OK;
+    return wf3d_splitk_combine({p.slab, C, bias, nullptr, nullptr, nullptr, M, N, ldc, 0, 0, 0, 0, p.ksplit, accumulate}, true, st);
 }

@@ -19,8 +19,6 @@
 //   gemm_split_x16_kernel<true>                              wgrad on reduction-major operands (ds_read_b64_tr_b16)
 //   gemm_split_dma3_kernel / gemm_split_tn_kernel            256x128 tile, 32x32x16 MFMA: problems with < 512 tiles /
 //                                                            wgrad outputs that are not multiples of 256
-//   split_reduce_kernel                                      split-K slab fold
-#include <stdlib.h>
 #include <string.h>
 
 #include <atomic>
@@ -955,146 +953,68 @@ __global__ __launch_bounds__(512, 2) void gemm_split_x16p_kernel(const SplitPara
     asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");          // no LDS-DMA may outlive the workgroup
 }
 
-__global__ __launch_bounds__(256) void split_reduce_kernel(const SplitParams p) {
-    const size_t total = (size_t)p.M * p.N;
-    for (size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (size_t)gridDim.x * 256) {
-        const int row = (int)(idx / p.N), col = (int)(idx % p.N);
-        float v = 0.f;
-        for (int z = 0; z < p.ksplit; ++z) v += p.slab[(size_t)z * total + idx];
-        if (p.bias) v += p.bias[col];
-        float* c = p.C + (size_t)row * p.ldc + col;
-        if (p.accumulate) v += *c;
-        *c = v;
-    }
-}
-
-// The same fold for many slabs (the few-tile wgrads split K up to 256 ways): a serial walk over the slabs is one
-// dependent 4-byte load per slab per thread (126 slabs of 128 KB took 55 us).  Here a wave owns 16 consecutive
-// outputs; lane = (slab lane 0..15, float4 0..3) walks slabs sl, sl + 16, ... four loads in flight, and the 16
-// partial sums meet in a fixed shuffle tree — the result does not depend on timing.
-__global__ __launch_bounds__(256) void split_reduce_wide_kernel(const SplitParams p) {
-    const size_t total = (size_t)p.M * p.N;
-    const int lane = threadIdx.x & 63, sl = lane >> 2, q = lane & 3;
-    const size_t idx = ((size_t)blockIdx.x * 4 + (threadIdx.x >> 6)) * 16 + q * 4;
-    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-    const bool live = idx < total;
-    if (live) {
-        const float* base = p.slab + idx;
-        for (int z = sl; z < p.ksplit; z += 64) {
-            const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
-            const f32x4 v0 = *reinterpret_cast<const f32x4*>(base + (size_t)z * total);
-            const f32x4 v1 = z + 16 < p.ksplit ? *reinterpret_cast<const f32x4*>(base + (size_t)(z + 16) * total) : zero;
-            const f32x4 v2 = z + 32 < p.ksplit ? *reinterpret_cast<const f32x4*>(base + (size_t)(z + 32) * total) : zero;
-            const f32x4 v3 = z + 48 < p.ksplit ? *reinterpret_cast<const f32x4*>(base + (size_t)(z + 48) * total) : zero;
-            acc += v0; acc += v1; acc += v2; acc += v3;
-        }
-    }
-#pragma unroll
-    for (int o = 4; o < 64; o <<= 1)
-#pragma unroll
-        for (int e = 0; e < 4; ++e) acc[e] += __shfl_xor(acc[e], o, 64);
-    if (live && sl == 0) {
-        const int row = (int)(idx / p.N), col = (int)(idx % p.N);          // N % 4 == 0: the float4 stays inside its row
-        float* c = p.C + (size_t)row * p.ldc + col;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            float v = acc[e];
-            if (p.bias) v += p.bias[col + e];
-            if (p.accumulate) v += c[e];
-            c[e] = v;
-        }
-    }
-}
-
-void launch_split_reduce(const SplitParams& p, hipStream_t st) {
-    const size_t total = (size_t)p.M * p.N;
-    if (p.ksplit > 16 && p.N % 4 == 0 && ((uintptr_t)p.slab % 16 == 0)) {
-        hipLaunchKernelGGL(split_reduce_wide_kernel, dim3((unsigned)((total + 63) / 64)), dim3(256), 0, st, p);
-        return;
-    }
-    int blocks = (int)((total + 255) / 256);
-    if (blocks > 2048) blocks = 2048;
-    hipLaunchKernelGGL(split_reduce_kernel, dim3(blocks), dim3(256), 0, st, p);
-}
-
-// Kernel choice.  WF3D_SPLIT_DMA forces one: 2 = 128x128 2-stage, 3 = 256x128 3-stage,
-// 4 = 256x256 2-stage (32x32x16 MFMA), 5 = 256x256 4-stage k16 register-pipelined, 6 = 256x256
-// 2-stage on 16x16x32 MFMA, 7 = 128x128 two-workgroups-per-CU on 16x16x32 (measured 20 % slower than 6).  Default (unset): 6 when the output has >= 512 such tiles (the tall
-// forward / dgrad GEMMs), else 3 (few tiles, long split-K reductions).  Measured on the encoder
-// shapes, same process: 6 is 11-14 % faster than 4; 5 equals 4 with its DMA issued early (+5 %).
 int cu_count() {
-    // per device (a process may drive several); WF3D_RESERVED_CUS=r: the persistent kernel launches on r CUs fewer
-    // (rounded to whole XCD-octets).  Since its tiles are claimed, not dealt, a CU held by another stream's kernel no
-    // longer costs a round — the switch remains for experiments.
-    static std::atomic<int> cache[16];
-    static const int reserved = [] { const char* e = getenv("WF3D_RESERVED_CUS"); return e ? atoi(e) : 0; }();
+    static std::atomic<int> cache[16];           // per device (a process may drive several)
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess) return 0;
     const bool cached = dev >= 0 && dev < 16;
     int v = cached ? cache[dev].load(std::memory_order_relaxed) : 0;
     if (v == 0) {
         if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) return 0;
-        if (reserved > 0 && v - reserved >= 8) v = (v - reserved) / 8 * 8;
         if (cached) cache[dev].store(v, std::memory_order_relaxed);
     }
     return v;
 }
 
-// 6 = 256x256 tile on v_mfma_f32_16x16x32_bf16 (gemm_split_x16_kernel / its persistent form): >= 192 tiles (3/4 of the CUs) and N a
-//     multiple of 256 (a 128-wide output wastes half of every tile: 380 vs 420 us at 1,044,480 x 128 x 256);
-// 3 = 256x128 tile, three LDS stages, 32x32x16 MFMA (gemm_split_dma3_kernel): the smaller ones.
-// K is split only below 192 tiles: at 252 tiles (the edge MLP at cfg2) two K ranges + slabs + a combine launch cost more than
-// the idle quarter-wave they fill (scripts/bench_edge_gemms.py: 62 -> 48, 52 -> 26, 36 -> 25, 86 -> 61 us for its four GEMMs).
-// WF3D_SPLIT_DMA=3|6 forces one of them (tests/test_variants_gpu.py); the other round-1 variants live in
-// scripts/ablation/gemm_split_variants.hip.txt.
-int split_variant(int M, int N) {
-    static const int forced = [] { const char* e = getenv("WF3D_SPLIT_DMA"); return e ? atoi(e) : 0; }();
-    if (forced == 3 || forced == 6) return forced;
-    static const int min_tiles = [] { const char* e = getenv("WF3D_X16_MIN_TILES"); return e ? atoi(e) : 192; }();
-    return (long)wf3d_cdiv(M, 256) * wf3d_cdiv(N, 256) >= min_tiles && N % 256 == 0 ? 6 : 3;
+// Run-time switches (process-wide), wf3d_set_option:
+std::atomic<int> g_tn_rounds{1};       // "tn_rounds": workgroups per CU the 16+-tile wgrad launches are cut into (1..8)
+std::atomic<int> g_gemm_cus{0};        // "gemm_cus": workgroups of the persistent kernel (0 = one per CU)
+std::atomic<int> g_split_kernel{0};    // "split_kernel": 0 = automatic, 1 = register-staged, 3 = 256x128, 6 = 256x256
+constexpr size_t CTL_BYTES = 2048;     // persistent kernel: 8 claim counters 64 B apart (512 B, zeroed per launch) + 256+ mailbox words
+
+// Forward / dgrad kernel: 6 = 256x256 tile on v_mfma_f32_16x16x32_bf16 (gemm_split_x16_kernel / its persistent form)
+// when there are >= 192 such tiles (3/4 of the CUs) and N is a multiple of 256 (a 128-wide output wastes half of every
+// tile: 380 vs 420 us at 1,044,480 x 128 x 256); else 3 = 256x128 tile, three LDS stages, 32x32x16 MFMA
+// (gemm_split_dma3_kernel).  Measured on the encoder shapes, same process: the 256x256 kernel on 16x16x32 is 11-14 %
+// faster than on 32x32x16.  The other round-1 variants live in scripts/ablation/gemm_split_variants.hip.txt.
+int split_variant(int M, int N, int kernel) {
+    if (kernel == 3 || kernel == 6) return kernel;
+    return (long)wf3d_cdiv(M, 256) * wf3d_cdiv(N, 256) >= 192 && N % 256 == 0 ? 6 : 3;
+}
+SplitK plan_dma(int M, int N, int K, int variant) {
+    return wf3d_splitk_plan(WF3D_SPLITK_SPLIT, (long)wf3d_cdiv(M, 256) * wf3d_cdiv(N, variant == 6 ? 256 : 128), K / SBK);
+}
+SplitK plan_regs(int M, int N, int K) {
+    return wf3d_splitk_plan(WF3D_SPLITK_GEMM, (long)wf3d_cdiv(M, 128) * wf3d_cdiv(N, 128), wf3d_cdiv(K, SBK));
 }
 
-void plan(int M, int N, int K, int& ksplit, int& kt_per) {
-    const int v = split_variant(M, N);
-    const int bm = 256, bn = v == 6 ? 256 : 128;
-    const long tiles = (long)wf3d_cdiv(M, bm) * wf3d_cdiv(N, bn);
-    const int ktotal = K / SBK;
-    ksplit = 1; kt_per = ktotal;
-    static const int nosplit = [] { const char* e = getenv("WF3D_SPLIT_NOSPLIT_TILES"); return e ? atoi(e) : 192; }();
-    if (tiles >= nosplit || ktotal < 8) return;
-    int want = (int)((512 + tiles - 1) / tiles);
-    int ks = want < ktotal / 4 ? want : ktotal / 4;
-    if (ks > 64) ks = 64;
-    if (ks < 2) return;
-    kt_per = wf3d_cdiv(ktotal, ks);
-    ksplit = wf3d_cdiv(ktotal, kt_per);
+// The persistent form of the 256x256 kernel claims full tiles from counters in the workspace and makes one pass over K
+// (>= 8 slices, an even count) with plain, non-accumulating 16-B stores; it needs >= 2 tiles per workgroup and row
+// offsets of 1024 rows that fit 32 bits.
+bool persistent_ok(const SplitParams& p, int cus, const void* ws, size_t ws_bytes) {
+    return p.ksplit == 1 && !p.accumulate && p.M % 256 == 0 && p.N % 256 == 0 && p.K / SBK >= 8 && p.K % (2 * SBK) == 0 &&
+        ws != nullptr && ws_bytes >= CTL_BYTES && (uintptr_t)ws % 64 == 0 && cus <= 384 && cus >= 8 && cus % 8 == 0 &&
+        p.nbm * p.nbn >= 2 * cus && p.ldc % 4 == 0 && (long)p.lda * 1024 < (1L << 32) && (long)p.ldb * 1024 < (1L << 32) &&
+        (long)p.ldc * 1024 < (1L << 32) && ((uintptr_t)p.C % 16 == 0) && (!p.bias || (uintptr_t)p.bias % 16 == 0);
 }
 
-}  // namespace
-
-// Returns 1 when the DMA kernel can take the problem (K a multiple of the 32-wide slice,
-// 16-B aligned rows); the register-staged kernel in gemm.hip handles everything else.
-extern "C" int wf3d_gemm_split_dma_ok(int M, int N, int K, int lda, int ldb) {
-    return M > 0 && N > 0 && K >= SBK && K % SBK == 0 && lda % 4 == 0 && ldb % 4 == 0;
+// Wgrad kernel: 256x256 tiles on the 16x16x32 MFMA when the output allows (split_kernel 3 takes the 256x128 one).
+bool tn16(int Mo, int No) {
+    return g_split_kernel.load(std::memory_order_relaxed) != 3 && Mo % 256 == 0 && No % 256 == 0;
+}
+SplitK plan_tn(int Mo, int No, int K) {
+    const bool big = tn16(Mo, No);
+    const long tiles = (long)wf3d_cdiv(Mo, 256) * wf3d_cdiv(No, big ? 256 : 128);
+    // tn_rounds = f deals f workgroups per CU (K ranges f times shorter, f times the slabs): a CU held by another
+    // stream's kernel then costs the launch 1/f of its time instead of all of it, at the price of the extra slab traffic.
+    // Measured (scripts/bench_contention.py, scripts/ab_gemm.sh): the 32-tile wgrads (2048 x 1024) pay +2.5 % / +4 % for
+    // f = 2 / 4 on an idle chip and lose 15 % / 0 % instead of 67 % beside a kernel that holds CUs; the 8-tile ones
+    // (already 32 ranges of 2 MB slabs) pay +9 % / +28 %, so f applies from 16 tiles up.  wf3d.dist turns it on (2) when
+    // gradients are reduced beside the backward pass.
+    const int rounds = tiles >= 16 ? g_tn_rounds.load(std::memory_order_relaxed) : 1;
+    return wf3d_splitk_plan(big ? WF3D_SPLITK_TN16 : WF3D_SPLITK_TN, tiles, K / SBK, rounds);
 }
 
-#if WF3D_STAMP
-extern "C" int wf3d_debug_stamps(unsigned long long* dst, size_t n) {
-    return (int)hipMemcpyFromSymbol(dst, HIP_SYMBOL(g_stamps), n * sizeof(unsigned long long), 0, hipMemcpyDeviceToHost);
-}
-#endif
-
-static std::atomic<int> g_gemm_cus{0};           // wf3d_set_option("gemm_cus", n): workgroups of the persistent kernel (0 = one per CU)
-constexpr size_t CTL_BYTES = 2048;        // persistent kernel: 8 claim counters 64 B apart (512 B, zeroed per launch) + 256+ mailbox words
-
-extern "C" size_t wf3d_gemm_split_dma_ws_bytes(int M, int N, int K) {
-    if (M <= 0 || N <= 0 || K <= 0) return 0;
-    int ks, per;
-    plan(M, N, K, ks, per);
-    return ks > 1 ? (size_t)ks * M * N * sizeof(float) : CTL_BYTES;
-}
-
-namespace {
 template <int NP>
 void launch_split_dma(const SplitParams& p, int variant, bool persist, int cus, hipStream_t st) {
     if (variant == 6) {
@@ -1107,130 +1027,62 @@ void launch_split_dma(const SplitParams& p, int variant, bool persist, int cus, 
         hipLaunchKernelGGL((gemm_split_dma3_kernel<NP>), dim3(p.nbm * p.nbn, 1, p.ksplit), dim3(512), 0, st, p);
     }
 }
-}  // namespace
 
-// products: 3 = bf16x3 (wf3d_gemm_split), 1 = plain bf16 on the hi planes (wf3d_gemm_bf16); the kernel choice,
-// tiling and split-K plan do not depend on it.
-extern "C" int wf3d_gemm_split_dma(const void* A_sx8, const void* B_sx8, float* C, const float* bias, int M, int N,
-                                   int K, int lda, int ldb, int ldc, int accumulate, void* ws, size_t ws_bytes,
-                                   void* stream, int products) {
-    WF3D_CHECK(products == 1 || products == 3, WF3D_ERR_ARG, "wf3d_gemm_split_dma: products must be 1 or 3 (got %d)", products);
-    WF3D_CHECK(wf3d_gemm_split_dma_ok(M, N, K, lda, ldb), WF3D_ERR_UNSUPPORTED, "wf3d_gemm_split_dma: shape not supported");
-    WF3D_CHECK(A_sx8 && B_sx8 && C, WF3D_ERR_ARG, "wf3d_gemm_split_dma: null operand");
-    WF3D_CHECK(lda >= K && ldb >= K && ldc >= N, WF3D_ERR_ARG, "wf3d_gemm_split_dma: leading dimension too small");
-    WF3D_CHECK(((uintptr_t)A_sx8 % 16 == 0) && ((uintptr_t)B_sx8 % 16 == 0), WF3D_ERR_ARG, "wf3d_gemm_split_dma: misaligned operand");
-    SplitParams p{};
-    p.A = (const float*)A_sx8; p.B = (const float*)B_sx8; p.C = C; p.bias = bias;
-    p.M = M; p.N = N; p.K = K; p.lda = lda; p.ldb = ldb; p.ldc = ldc; p.accumulate = accumulate;
-    const int variant = split_variant(M, N);
-    p.nbm = wf3d_cdiv(M, 256); p.nbn = wf3d_cdiv(N, variant == 6 ? 256 : 128);
-    plan(M, N, K, p.ksplit, p.kt_per_split);
-    const size_t need = p.ksplit > 1 ? (size_t)p.ksplit * M * N * sizeof(float) : 0;
-    if (need && (ws == nullptr || ws_bytes < need)) { p.ksplit = 1; p.kt_per_split = K / SBK; }
-    p.slab = p.ksplit > 1 ? (float*)ws : nullptr;
-    hipStream_t st = (hipStream_t)stream;
-    bool persist = false;
-    int cus = 0;
-    if (variant == 6) {
-        static const int persist_on = [] { const char* e = getenv("WF3D_SPLIT_PERSIST"); return e ? atoi(e) : 1; }();
-        cus = cu_count();
-        { const int lim = g_gemm_cus.load(std::memory_order_relaxed); if (lim >= 8 && lim < cus) cus = lim / 8 * 8; }
-        // persistent form: full tiles, one pass over K, plain (non-accumulating) 16-B stores
-        persist = persist_on && p.ksplit == 1 && !accumulate && M % 256 == 0 && N % 256 == 0 && K / SBK >= 8 && K % (2 * SBK) == 0 &&
-            ws != nullptr && ws_bytes >= CTL_BYTES && (uintptr_t)ws % 64 == 0 && cus <= 384 && cus >= 8 && cus % 8 == 0 &&
-            p.nbm * p.nbn >= 2 * cus && ldc % 4 == 0 && (long)lda * 1024 < (1L << 32) && (long)ldb * 1024 < (1L << 32) && (long)ldc * 1024 < (1L << 32) && ((uintptr_t)C % 16 == 0) && (!bias || (uintptr_t)bias % 16 == 0);
-        if (persist) {
-            p.ctl = (unsigned*)ws;
-            if (hipMemsetAsync(ws, 0, 512, st) != hipSuccess) { wf3d_set_error("wf3d_gemm_split_dma: hipMemsetAsync failed"); return WF3D_ERR_LAUNCH; }
-        }
-    }
-    if (products == 1) launch_split_dma<1>(p, variant, persist, cus, st);
-    else               launch_split_dma<3>(p, variant, persist, cus, st);
-    WF3D_LAUNCH_CHECK();
-    if (p.ksplit > 1) {
-        launch_split_reduce(p, st);
-        WF3D_LAUNCH_CHECK();
-    }
-    return WF3D_OK;
-}
-
-// C[Mo,No] (+)= A^T·B, A = sx8[K,Mo], B = sx8[K,No]  (Linear wgrad: A = dY, B = X, both as stored)
-extern "C" int wf3d_gemm_split_tn_ok(int Mo, int No, int K, int lda, int ldb) {
-    return Mo > 0 && No > 0 && K >= SBK && Mo % 256 == 0 && No % 128 == 0 && K % SBK == 0 && lda % 4 == 0 && ldb % 4 == 0;
-}
-
-namespace {
-std::atomic<int> g_tn_rounds{[] { const char* e = getenv("WF3D_TN_ROUNDS"); const int v = e ? atoi(e) : 1; return v < 1 ? 1 : v > 8 ? 8 : v; }()};
-}  // namespace
-
-// Run-time switches (process-wide).  "tn_rounds" = workgroups per CU the 16+-tile wgrad launches are cut into (1..8).
-extern "C" int wf3d_set_option(const char* name, int value) {
-    WF3D_CHECK(name != nullptr, WF3D_ERR_ARG, "wf3d_set_option: null name");
-    if (strcmp(name, "tn_rounds") == 0) {
-        WF3D_CHECK(value >= 1 && value <= 8, WF3D_ERR_ARG, "wf3d_set_option: tn_rounds must be 1..8 (got %d)", value);
-        g_tn_rounds.store(value, std::memory_order_relaxed);
-        return WF3D_OK;
-    }
-    if (strcmp(name, "gemm_cus") == 0) {
-        WF3D_CHECK(value == 0 || (value >= 8 && value <= 1024), WF3D_ERR_ARG, "wf3d_set_option: gemm_cus must be 0 (all) or 8..1024 (got %d)", value);
-        g_gemm_cus.store(value, std::memory_order_relaxed);
-        return WF3D_OK;
-    }
-    wf3d_set_error("wf3d_set_option: unknown option '%s'", name);
-    return WF3D_ERR_ARG;
-}
-
-namespace {
-// Wgrad kernel choice: 256x256 tiles on the 16x16x32 MFMA when the output allows (WF3D_TN16=0 forces
-// the 256x128 32x32x16 kernel).
-bool tn16(int Mo, int No) {
-    static const int off = [] { const char* e = getenv("WF3D_TN16"); return e && atoi(e) == 0; }();
-    return !off && Mo % 256 == 0 && No % 256 == 0;
-}
-void plan_tn(int Mo, int No, int K, int& ksplit, int& kt_per) {
-    const bool big = tn16(Mo, No);
-    const long tiles = (long)(Mo / 256) * (No / (big ? 256 : 128));
-    const int ktotal = K / SBK;
-    ksplit = 1; kt_per = ktotal;
-    if (tiles >= 256 || ktotal < 8) return;
-    // one workgroup per CU either way; the big tile runs one full wave of 256 workgroups.  WF3D_TN_ROUNDS=f deals f
-    // workgroups per CU (K ranges f times shorter, f times the slabs): a CU held by another stream's kernel then costs
-    // the launch 1/f of its time instead of all of it, at the price of the extra slab traffic.
-    // Measured (scripts/bench_contention.py, scripts/ab_gemm.sh): the 32-tile wgrads (2048 x 1024) pay +2.5 % / +4 % for
-    // f = 2 / 4 on an idle chip and lose 15 % / 0 % instead of 67 % beside a kernel that holds CUs; the 8-tile ones
-    // (already 32 ranges of 2 MB slabs) pay +9 % / +28 %, so f applies from 16 tiles up.  wf3d_set_option("tn_rounds", f);
-    // wf3d.dist turns it on (2) when gradients are reduced beside the backward pass.
-    const int rounds = tiles >= 16 ? g_tn_rounds.load(std::memory_order_relaxed) : 1;
-    int want = (int)(((big ? 256 : 512) * rounds + tiles - 1) / tiles);
-    // One or two output tiles (the edge MLP's 128 x 256 and 256 x 512 weights over ~10^5 - 10^6 edge rows) are a streaming
-    // reduction over K: they get a K range per CU (up to 256 slabs) as long as a range keeps >= 8 slices; more tiles
-    // keep the 64-range cap that bounds the slab traffic (with 64 ranges the 128 x 256 wgrad of cfg5 ran on 64 CUs
-    // at 2.0 TB/s, the 256 x 512 one on half the chip).
-    const bool few = tiles <= 4;
-    int ks = want < ktotal / (few ? 8 : 4) ? want : ktotal / (few ? 8 : 4);
-    static const int few_cap = [] { const char* e = getenv("WF3D_TN_FEW_CAP"); return e ? atoi(e) : 256; }();
-    const int cap = few ? few_cap : 64 * rounds;
-    if (ks > cap) ks = cap;
-    if (few && ks >= 8) ks &= ~7;                 // multiples of 8: the XCD-mapped launch order applies
-    if (ks < 2) return;
-    kt_per = wf3d_cdiv(ktotal, ks);
-    ksplit = wf3d_cdiv(ktotal, kt_per);
-}
-}  // namespace
-
-extern "C" size_t wf3d_gemm_split_tn_ws_bytes(int Mo, int No, int K) {
-    if (Mo <= 0 || No <= 0 || K <= 0) return 0;
-    int ks, per;
-    plan_tn(Mo, No, K, ks, per);
-    return ks > 1 ? (size_t)ks * Mo * No * sizeof(float) : 0;
-}
-
-namespace {
 template <int NP>
 void launch_split_tn(const SplitParams& p, bool big, hipStream_t st) {
     if (big && p.zmap) hipLaunchKernelGGL((gemm_split_x16_kernel<true, NP>), dim3(p.nbm * p.nbn * p.ksplit, 1, 1), dim3(512), 0, st, p);
     else if (big)      hipLaunchKernelGGL((gemm_split_x16_kernel<true, NP>), dim3(p.nbm * p.nbn, 1, p.ksplit), dim3(512), 0, st, p);
     else               hipLaunchKernelGGL((gemm_split_tn_kernel<NP>), dim3(p.nbm * p.nbn, 1, p.ksplit), dim3(512), 0, st, p);
+}
+
+int combine(const SplitParams& p, hipStream_t st) {
+    if (p.ksplit == 1) return WF3D_OK;
+    return wf3d_splitk_combine({p.slab, p.C, p.bias, nullptr, nullptr, nullptr, p.M, p.N, p.ldc, 0, 0, 0, 0, p.ksplit, p.accumulate},
+                               false, st);
+}
+
+// products: 3 = bf16x3 (wf3d_gemm_split), 1 = plain bf16 on the hi planes (wf3d_gemm_bf16).  Same checks, same kernel
+// choice, same split-K plan and workspace either way.
+int gemm_split_impl(const char* fn, int products, const void* A_sx8, const void* B_sx8, float* C, const float* bias, int M,
+                    int N, int K, int lda, int ldb, int ldc, int accumulate, void* ws, size_t ws_bytes, void* stream) {
+    WF3D_CHECK(M >= 0 && N >= 0 && K > 0, WF3D_ERR_ARG, "%s: bad dims", fn);
+    if (M == 0 || N == 0) return WF3D_OK;
+    WF3D_CHECK(A_sx8 && B_sx8 && C, WF3D_ERR_ARG, "%s: null operand", fn);
+    WF3D_CHECK(K % 8 == 0 && lda % 8 == 0 && ldb % 8 == 0, WF3D_ERR_UNSUPPORTED,
+               "%s: K, lda, ldb must be multiples of 8 (sx8 groups)", fn);
+    WF3D_CHECK(lda >= K && ldb >= K && ldc >= N, WF3D_ERR_ARG, "%s: leading dimension too small", fn);
+    WF3D_CHECK(((uintptr_t)A_sx8 % 16 == 0) && ((uintptr_t)B_sx8 % 16 == 0), WF3D_ERR_ARG, "%s: operands must be 16-byte aligned", fn);
+    hipStream_t st = (hipStream_t)stream;
+    const int kernel = g_split_kernel.load(std::memory_order_relaxed);
+    // the LDS-DMA kernels take every K that is a multiple of their 32-wide slice, the register-staged one the rest
+    if (kernel == 1 || K % SBK != 0) {
+        const int ktotal = wf3d_cdiv(K, SBK);
+        const SplitK s = wf3d_splitk_fit(plan_regs(M, N, K), ktotal, M, N, ws, ws_bytes);
+        return wf3d_gemm_split_regs(products, A_sx8, B_sx8, C, bias, M, N, K, lda, ldb, ldc, accumulate, s, (float*)ws, st);
+    }
+    SplitParams p{};
+    p.A = (const float*)A_sx8; p.B = (const float*)B_sx8; p.C = C; p.bias = bias;
+    p.M = M; p.N = N; p.K = K; p.lda = lda; p.ldb = ldb; p.ldc = ldc; p.accumulate = accumulate;
+    const int variant = split_variant(M, N, kernel);
+    p.nbm = wf3d_cdiv(M, 256); p.nbn = wf3d_cdiv(N, variant == 6 ? 256 : 128);
+    const SplitK s = wf3d_splitk_fit(plan_dma(M, N, K, variant), K / SBK, M, N, ws, ws_bytes);
+    p.ksplit = s.ksplit; p.kt_per_split = s.kt_per;
+    p.slab = p.ksplit > 1 ? (float*)ws : nullptr;
+    bool persist = false;
+    int cus = 0;
+    if (variant == 6) {
+        cus = cu_count();
+        { const int lim = g_gemm_cus.load(std::memory_order_relaxed); if (lim >= 8 && lim < cus) cus = lim / 8 * 8; }
+        persist = persistent_ok(p, cus, ws, ws_bytes);
+        if (persist) {
+            p.ctl = (unsigned*)ws;
+            if (hipMemsetAsync(ws, 0, 512, st) != hipSuccess) { wf3d_set_error("%s: hipMemsetAsync failed", fn); return WF3D_ERR_LAUNCH; }
+        }
+    }
+    if (products == 1) launch_split_dma<1>(p, variant, persist, cus, st);
+    else               launch_split_dma<3>(p, variant, persist, cus, st);
+    WF3D_LAUNCH_CHECK();
+    return combine(p, st);
 }
 
 int gemm_split_tn_impl(const char* fn, int products, const void* A_sx8, const void* B_sx8, float* C, int Mo, int No, int K,
@@ -1245,23 +1097,77 @@ int gemm_split_tn_impl(const char* fn, int products, const void* A_sx8, const vo
     p.M = Mo; p.N = No; p.K = K; p.lda = lda; p.ldb = ldb; p.ldc = ldc; p.accumulate = accumulate;
     const bool big = tn16(Mo, No);
     p.nbm = Mo / 256; p.nbn = No / (big ? 256 : 128);
-    plan_tn(Mo, No, K, p.ksplit, p.kt_per_split);
-    const size_t need = p.ksplit > 1 ? (size_t)p.ksplit * Mo * No * sizeof(float) : 0;
-    if (need && (ws == nullptr || ws_bytes < need)) { p.ksplit = 1; p.kt_per_split = K / SBK; }
+    const SplitK s = wf3d_splitk_fit(plan_tn(Mo, No, K), K / SBK, Mo, No, ws, ws_bytes);
+    p.ksplit = s.ksplit; p.kt_per_split = s.kt_per;
     p.slab = p.ksplit > 1 ? (float*)ws : nullptr;
+    p.zmap = big && p.ksplit >= 8 && p.ksplit % 8 == 0;
     hipStream_t st = (hipStream_t)stream;
-    static const int zmap_off = [] { const char* e = getenv("WF3D_TN_ZMAP"); return e && atoi(e) == 0; }();
-    if (big && !zmap_off && p.ksplit >= 8 && p.ksplit % 8 == 0) p.zmap = 1;
     if (products == 1) launch_split_tn<1>(p, big, st);
     else               launch_split_tn<3>(p, big, st);
     WF3D_LAUNCH_CHECK();
-    if (p.ksplit > 1) {
-        launch_split_reduce(p, st);
-        WF3D_LAUNCH_CHECK();
-    }
-    return WF3D_OK;
+    return combine(p, st);
 }
+
 }  // namespace
+
+#if WF3D_STAMP
+extern "C" int wf3d_debug_stamps(unsigned long long* dst, size_t n) {
+    return (int)hipMemcpyFromSymbol(dst, HIP_SYMBOL(g_stamps), n * sizeof(unsigned long long), 0, hipMemcpyDeviceToHost);
+}
+#endif
+
+extern "C" int wf3d_set_option(const char* name, int value) {
+    WF3D_CHECK(name != nullptr, WF3D_ERR_ARG, "wf3d_set_option: null name");
+    if (strcmp(name, "tn_rounds") == 0) {
+        WF3D_CHECK(value >= 1 && value <= 8, WF3D_ERR_ARG, "wf3d_set_option: tn_rounds must be 1..8 (got %d)", value);
+        g_tn_rounds.store(value, std::memory_order_relaxed);
+        return WF3D_OK;
+    }
+    if (strcmp(name, "gemm_cus") == 0) {
+        WF3D_CHECK(value == 0 || (value >= 8 && value <= 1024), WF3D_ERR_ARG, "wf3d_set_option: gemm_cus must be 0 (all) or 8..1024 (got %d)", value);
+        g_gemm_cus.store(value, std::memory_order_relaxed);
+        return WF3D_OK;
+    }
+    if (strcmp(name, "split_kernel") == 0) {
+        WF3D_CHECK(value == 0 || value == 1 || value == 3 || value == 6, WF3D_ERR_ARG,
+                   "wf3d_set_option: split_kernel must be 0, 1, 3 or 6 (got %d)", value);
+        g_split_kernel.store(value, std::memory_order_relaxed);
+        return WF3D_OK;
+    }
+    wf3d_set_error("wf3d_set_option: unknown option '%s'", name);
+    return WF3D_ERR_ARG;
+}
+
+// Either kernel family may take a call (the register-staged one for K % 32 != 0 or under split_kernel 1): room for
+// both plans, and at least the persistent kernel's control block when the LDS-DMA kernels do not split K.
+extern "C" size_t wf3d_gemm_split_ws_bytes(int M, int N, int K) {
+    if (M <= 0 || N <= 0 || K <= 0) return 0;
+    const size_t regs = wf3d_splitk_slab_bytes(plan_regs(M, N, K), M, N);
+    const SplitK s = plan_dma(M, N, K, split_variant(M, N, g_split_kernel.load(std::memory_order_relaxed)));
+    const size_t dma = s.ksplit > 1 ? wf3d_splitk_slab_bytes(s, M, N) : CTL_BYTES;
+    return regs > dma ? regs : dma;
+}
+
+extern "C" int wf3d_gemm_split(const void* A_sx8, const void* B_sx8, float* C, const float* bias, int M, int N, int K,
+                               int lda, int ldb, int ldc, int accumulate, void* ws, size_t ws_bytes, void* stream) {
+    return gemm_split_impl("wf3d_gemm_split", 3, A_sx8, B_sx8, C, bias, M, N, K, lda, ldb, ldc, accumulate, ws, ws_bytes, stream);
+}
+
+// bf16 mode: one bf16 MFMA per product on the hi planes of the sx8 operands; workspace: wf3d_gemm_split_ws_bytes
+extern "C" int wf3d_gemm_bf16(const void* A_sx8, const void* B_sx8, float* C, const float* bias, int M, int N, int K,
+                              int lda, int ldb, int ldc, int accumulate, void* ws, size_t ws_bytes, void* stream) {
+    return gemm_split_impl("wf3d_gemm_bf16", 1, A_sx8, B_sx8, C, bias, M, N, K, lda, ldb, ldc, accumulate, ws, ws_bytes, stream);
+}
+
+// C[Mo,No] (+)= A^T·B, A = sx8[K,Mo], B = sx8[K,No]  (Linear wgrad: A = dY, B = X, both as stored)
+extern "C" int wf3d_gemm_split_tn_ok(int Mo, int No, int K, int lda, int ldb) {
+    return Mo > 0 && No > 0 && K >= SBK && Mo % 256 == 0 && No % 128 == 0 && K % SBK == 0 && lda % 4 == 0 && ldb % 4 == 0;
+}
+
+extern "C" size_t wf3d_gemm_split_tn_ws_bytes(int Mo, int No, int K) {
+    if (Mo <= 0 || No <= 0 || K <= 0) return 0;
+    return wf3d_splitk_slab_bytes(plan_tn(Mo, No, K), Mo, No);
+}
 
 extern "C" int wf3d_gemm_split_tn(const void* A_sx8, const void* B_sx8, float* C, int Mo, int No, int K, int lda,
                                   int ldb, int ldc, int accumulate, void* ws, size_t ws_bytes, void* stream) {

@@ -6,8 +6,6 @@
 // hi = bf16_rne(v), lo = bf16_rne(v - hi)  (|v - hi - lo| <= 2^-17 |v|).  A staged
 // row slice then delivers each lane's v_mfma_f32_32x32x16_bf16 fragment (8
 // consecutive k) as one 16-byte chunk, with no conversion inside the GEMM.
-#include <stdlib.h>
-
 #include "wf3d_common.h"
 
 namespace {
@@ -442,11 +440,10 @@ extern "C" int wf3d_ln_prep(const float* z, int R, int D, const float* gamma, co
                ((uintptr_t)beta % 16 == 0), WF3D_ERR_ARG, "wf3d_ln_prep: pointers must be 16-byte aligned");
     const int ns = wf3d_cdiv(D, 512);
     hipStream_t st = (hipStream_t)stream;
-    // persistent grid: a few workgroups per CU (WF3D_LNPREP_WGS overrides, for sweeps)
-    static const int lp_wgs = [] { const char* e = getenv("WF3D_LNPREP_WGS"); return e ? atoi(e) : 4096; }();
+    // persistent grid: a few workgroups per CU
     const int rpb = D <= 256 ? 8 : 4;
     int blocks = wf3d_cdiv(R, rpb);
-    if (blocks > lp_wgs) blocks = lp_wgs;
+    if (blocks > 4096) blocks = 4096;
 #define WF3D_LP(NS_)                                                                                              \
     if (D == NS_ * 512)                                                                                           \
         hipLaunchKernelGGL((ln_prep_kernel<NS_, 64, true>), dim3(blocks), dim3(256), 0, st, z, R, D, gamma, beta, act, eps, \
@@ -477,9 +474,8 @@ extern "C" int wf3d_first_layer_fwd(const float* x, int R, int K, int ldx, const
     // each wave keeps its slice of W in registers for all its rows; 4096 workgroups measured best of 512..32768 with the
     // vector prologue (118 / 124 / 112 / 106 / 129 us at 512 / 1024 / 2048 / 4096 / 8192; 512 was best while the prologue
     // was 72 single loads)
-    static const int fl_blocks = [] { const char* e = getenv("WF3D_FL_BLOCKS"); return e ? atoi(e) : 4096; }();
     int blocks = wf3d_cdiv(R, 4);
-    blocks = blocks > fl_blocks ? fl_blocks : (blocks < 1 ? 1 : blocks);
+    blocks = blocks > 4096 ? 4096 : (blocks < 1 ? 1 : blocks);
     hipStream_t st = (hipStream_t)stream;
     const bool fast = K == 8 && ldx % 4 == 0 && ((uintptr_t)x % 16 == 0) && act == WF3D_ACT_RELU && D % 512 == 0 && ldw % 4 == 0 &&
                       ((uintptr_t)W % 16 == 0) && (!bias || (uintptr_t)bias % 16 == 0);

@@ -34,12 +34,79 @@ WF3D_INTERNAL void wf3d_set_error(const char* fmt, ...);
         }                                                                     \
     } while (0)
 
-// internal (not part of include/wf3d.h): LDS-DMA variant of the split GEMM, gemm_split.hip
-extern "C" WF3D_INTERNAL int wf3d_gemm_split_dma_ok(int M, int N, int K, int lda, int ldb);
-extern "C" WF3D_INTERNAL size_t wf3d_gemm_split_dma_ws_bytes(int M, int N, int K);
-extern "C" WF3D_INTERNAL int wf3d_gemm_split_dma(const void* A_sx8, const void* B_sx8, float* C, const float* bias, int M, int N,
-                                   int K, int lda, int ldb, int ldc, int accumulate, void* ws, size_t ws_bytes,
-                                   void* stream, int products);
+static inline int wf3d_cdiv(long a, long b) { return (int)((a + b - 1) / b); }
+
+// ---- split-K (host) --------------------------------------------------------
+// A GEMM whose output has too few tiles to fill the chip cuts its reduction into `ksplit` ranges of `kt_per` K slices;
+// each range writes a slab of M x N partial sums into the caller's workspace and wf3d_splitk_combine folds them.  One
+// planner; each kernel family's constants are one row.
+struct SplitKRule {
+    int nosplit_tiles;   // K is not split from this many output tiles up
+    int target;          // workgroups (tiles x K ranges) to aim for
+    int cap;             // K ranges at most
+    int few_tiles;       // up to this many tiles the launch is a streaming reduction over K:
+    int few_slices;      //   K slices per range at least (otherwise 4)
+    int few_cap;         //   K ranges at most
+    bool few_mult8;      //   range count rounded down to a multiple of 8 (the XCD-mapped launch order applies)
+};
+// fp32 wf3d_gemm and the register-staged split kernel.  Few tiles and a very long reduction (first-layer wgrad:
+// 512 x 8 outputs over K = B*N rows) stream their operands from HBM: they need >= 2 workgroups per CU in flight.
+constexpr SplitKRule WF3D_SPLITK_GEMM = {256, 512, 64, 8, 4, 256, false};
+// LDS-DMA split forward / dgrad: K is split only below 192 tiles.  At 252 tiles (the edge MLP at cfg2) two K ranges +
+// slabs + a combine launch cost more than the idle quarter-wave they fill (scripts/bench_edge_gemms.py: 62 -> 48,
+// 52 -> 26, 36 -> 25, 86 -> 61 us for its four GEMMs).
+constexpr SplitKRule WF3D_SPLITK_SPLIT = {192, 512, 64, 0, 4, 64, false};
+// Split wgrad, 256x128 and 256x256 tiles (one full wave of 256 workgroups either way).  One to four output tiles (the
+// edge MLP's 128 x 256 and 256 x 512 weights over ~10^5 - 10^6 edge rows) get a K range per CU (up to 256 slabs) as
+// long as a range keeps >= 8 slices; more tiles keep the 64-range cap that bounds the slab traffic (with 64 ranges the
+// 128 x 256 wgrad of cfg5 ran on 64 CUs at 2.0 TB/s, the 256 x 512 one on half the chip).
+constexpr SplitKRule WF3D_SPLITK_TN = {256, 512, 64, 4, 8, 256, true};
+constexpr SplitKRule WF3D_SPLITK_TN16 = {256, 256, 64, 4, 8, 256, true};
+
+struct SplitK { int ksplit, kt_per; };
+
+// `rounds` multiplies the target and the cap (the wgrad "tn_rounds" option)
+static inline SplitK wf3d_splitk_plan(const SplitKRule& r, long tiles, int ktotal, int rounds = 1) {
+    SplitK s{1, ktotal};
+    if (tiles >= r.nosplit_tiles || ktotal < 8) return s;
+    const bool few = tiles <= r.few_tiles;
+    const int want = (int)(((long)r.target * rounds + tiles - 1) / tiles);
+    const int most = ktotal / (few ? r.few_slices : 4);
+    int ks = want < most ? want : most;
+    const int cap = few ? r.few_cap : r.cap * rounds;
+    if (ks > cap) ks = cap;
+    if (few && r.few_mult8 && ks >= 8) ks &= ~7;
+    if (ks < 2) return s;
+    s.kt_per = wf3d_cdiv(ktotal, ks);
+    s.ksplit = wf3d_cdiv(ktotal, s.kt_per);      // no empty range
+    return s;
+}
+
+static inline size_t wf3d_splitk_slab_bytes(SplitK s, int M, int N) {
+    return s.ksplit > 1 ? (size_t)s.ksplit * M * N * sizeof(float) : 0;
+}
+
+// At launch: a split whose slabs do not fit the caller's workspace runs as one K range.
+static inline SplitK wf3d_splitk_fit(SplitK s, int ktotal, int M, int N, const void* ws, size_t ws_bytes) {
+    const size_t need = wf3d_splitk_slab_bytes(s, M, N);
+    return need && (ws == nullptr || ws_bytes < need) ? SplitK{1, ktotal} : s;
+}
+
+// C = sum of the `ksplit` slabs (+ bias[n]) (+ lr_u[m, :lr_k] . lr_v[n, :lr_k]) (+ addend[m, n]) (+ C if accumulate).
+// The fold order is fixed (deterministic): slab after slab, or, for more than 16 slabs with N % 4 == 0 and a 16-B
+// aligned workspace, 16 strided partial sums per output met in a shuffle tree.  narrow_only keeps slab after slab.
+struct SplitKCombine {
+    const float* slab; float* C; const float* bias; const float* addend; const float* lr_u; const float* lr_v;
+    int M, N, ldc, ld_addend, lr_k, ld_lr_u, ld_lr_v, ksplit, accumulate;
+};
+WF3D_INTERNAL int wf3d_splitk_combine(const SplitKCombine& c, bool narrow_only, hipStream_t st);
+
+// The register-staged split GEMM (gemm.hip, gemm_kernel<..., SPLIT>: 128 x 128 tiles, K in 32-wide slices, any K % 8
+// == 0).  Its caller, gemm_split.hip, plans `s` with WF3D_SPLITK_GEMM; the slabs (s.ksplit > 1) are folded slab after
+// slab.
+WF3D_INTERNAL int wf3d_gemm_split_regs(int products, const void* A_sx8, const void* B_sx8, float* C, const float* bias,
+                                       int M, int N, int K, int lda, int ldb, int ldc, int accumulate, SplitK s,
+                                       float* slab, hipStream_t st);
 
 // internal: MFMA attention for head_dim 64 (attn_mfma.hip)
 extern "C" WF3D_INTERNAL int wf3d_attn_fwd_mfma(const float* qkv, const int32_t* voff, int S, int vmax, int E, int heads, float drop_p,
@@ -47,8 +114,6 @@ extern "C" WF3D_INTERNAL int wf3d_attn_fwd_mfma(const float* qkv, const int32_t*
 extern "C" WF3D_INTERNAL int wf3d_attn_bwd_mfma(const float* qkv, const float* dctx, const float* ctx, const float* lse,
                                   const int32_t* voff, int S, int vmax, int E, int heads, float drop_p,
                                   uint32_t drop_seed, float* dqkv, void* stream);
-
-static inline int wf3d_cdiv(long a, long b) { return (int)((a + b - 1) / b); }
 
 // ---- device helpers --------------------------------------------------------
 #ifdef __HIPCC__

@@ -213,7 +213,22 @@ def load():
     if lib.wf3d_version() < 102:
         raise RuntimeError("wf3d: libwf3d.so is stale; rebuild it")
     _lib = lib
+    try:
+        set_tn_rounds(1)
+    except Exception:
+        _lib = None
+        raise
     return lib
+
+
+def set_tn_rounds(default):
+    """wf3d_set_option("tn_rounds", n): workgroups per CU of the large weight-gradient launches (include/wf3d.h).
+    n = $WF3D_TN_ROUNDS when set, else `default`: 1 from load(), 2 from wf3d.dist.GradReducer across ranks."""
+    v = os.environ.get("WF3D_TN_ROUNDS")
+    n = int(v) if v else default
+    if not 1 <= n <= 8:
+        raise ValueError(f"wf3d: WF3D_TN_ROUNDS must be 1..8 (got {v!r})")
+    check(load().wf3d_set_option(b"tn_rounds", n), "wf3d_set_option(tn_rounds)")
 
 
 def check(code, what):

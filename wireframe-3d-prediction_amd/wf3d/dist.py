@@ -116,7 +116,7 @@ class GradReducer:
             # the reduces run beside the backward pass: cut the large wgrad launches into two rounds of workgroups so a
             # CU the collective's kernels hold costs them 15 % instead of 67 % (include/wf3d.h, wf3d_set_option)
             from . import _lib
-            _lib.load().wf3d_set_option(b"tn_rounds", int(os.environ.get("WF3D_TN_ROUNDS", "2")))
+            _lib.set_tn_rounds(2)
 
     def _build(self):
         for h in self._hooks:

@@ -6,7 +6,6 @@ per-16-column (mean, M2) partials of it; the launch that consumes act(LN(z)) mer
 alternates two launches per stage: `bwd` (weight/bias gradient + dgrad partial slabs, for up to 4 Linears that are
 ready together) and `reduce` (slab sum + the elementwise half of the next LayerNorm backward)."""
 import ctypes
-import os
 
 import torch
 
@@ -108,10 +107,7 @@ def _pick_nc(N, K):
     """dgrad chunk height (weight rows per workgroup).  A chunk of nc rows costs one slab of M*K*4 bytes (written, read
     back by reduce) and nc/2 x 4 fp32 MFMAs of 64 cycles per wave.  Measured GPU-side over the nine head layers of cfg2
     (rocprofv3, bwd + reduce per step): nc = 32: 305 us, 64: 270 us, 128: 289 us, the earlier mixed rule (128 for the big
-    and the narrow layers) 292 us — so 64 everywhere (WF3D_SKINNY_NC forces another value)."""
-    force = os.environ.get("WF3D_SKINNY_NC")
-    if force:
-        return min(int(force), max(2, N + (N & 1)))
+    and the narrow layers) 292 us — so 64 everywhere."""
     if N < 64:
         return max(2, N + (N & 1))
     return 64
