@@ -361,15 +361,14 @@ def _set_site_ps(ep, ps):
     return ep
 
 
-def edge_head_case(counts, precision, min_rows, hidden=512, heads=8, keep_pre=False, ps=SITE_PS, tseed=77):
+def edge_head_case(counts, precision, min_rows, hidden=512, heads=8, ps=SITE_PS, tseed=77):
     """Train-mode forward_ragged + backward against the oracle under the replayed masks.  Returns (errors, tol)."""
     from wf3d import config
     from models.EdgePredictor import EdgePredictor
-    old = (config.precision(), config.SPLIT_MIN_ROWS, config.KEEP_PRE)
+    old = (config.precision(), config.SPLIT_MIN_ROWS)
     config.set_precision(precision)
     if min_rows is not None:
         config.SPLIT_MIN_ROWS = min_rows
-    config.KEEP_PRE = keep_pre
     try:
         torch.manual_seed(5)
         ep = _set_site_ps(EdgePredictor(3, hidden, heads), ps).to(dev()).train()
@@ -409,7 +408,7 @@ def edge_head_case(counts, precision, min_rows, hidden=512, heads=8, keep_pre=Fa
         return errs
     finally:
         config.set_precision(old[0])
-        config.SPLIT_MIN_ROWS, config.KEEP_PRE = old[1], old[2]
+        config.SPLIT_MIN_ROWS = old[1]
 
 
 def _report(tag, errs, tol):
@@ -433,16 +432,16 @@ def test_edge_head_train_mode_fp32_unsplit_path(spy):
     _report("fp32 unsplit", errs, 1e-4)
 
 
-@pytest.mark.parametrize("counts,keep_pre,route", [
+@pytest.mark.parametrize("counts,wide,route", [
     ([9, 2, 5, 12], False, "gemm"),             # 113 edge rows (odd): split forward, wgrads on the fp32-operand TN GEMM
     ([16, 9, 8], False, "transpose"),           # 184 rows: whole 8-row groups, not 32: wgrads through split_transpose
     ([12, 12, 8], False, "tn"),                 # 160 rows: transposing-read TN kernel, pre not stored (rebuilt)
-    ([12, 12, 8], True, "tn"),                  # same with config.KEEP_PRE
+    ([12, 12, 8], True, "tn"),                  # same at hidden 2048: pre stored (edge_pair_ln_bwd takes H <= 1024)
 ])
-def test_edge_head_train_mode_split_paths(spy, counts, keep_pre, route):
+def test_edge_head_train_mode_split_paths(spy, counts, wide, route):
     """bf16x3 forced onto the split path (SPLIT_MIN_ROWS = 1) at edge-row counts that select each wgrad route; bound as
     the p = 0 forced cases (tests/test_model_gpu.py::test_edge_head_other_hidden_sizes_vs_oracle: 3e-4)."""
-    errs = edge_head_case(counts, "bf16x3", 1, keep_pre=keep_pre)
+    errs = edge_head_case(counts, "bf16x3", 1, hidden=2048 if wide else 512)
     b = branches(spy)
     assert b["pair_ln"] == [P1] and b["prep_drop"] == [P2] and b["rowdot_bwd"] == 1
     if route == "gemm":
@@ -451,7 +450,7 @@ def test_edge_head_train_mode_split_paths(spy, counts, keep_pre, route):
         assert b["tn"] == 0 and sorted(b["st_drop"]) == [P1, P2] and b["gemm_tn_drop"] == []
     else:
         assert b["tn"] == 2 and b["st_drop"] == [] and b["gemm_tn_drop"] == []
-    want_keep = keep_pre or route != "tn"
+    want_keep = wide or route != "tn"
     assert b["keep_pre"] == [want_keep]
     assert (b["wsum"], b["pair_ln_bwd"]) == ((1, 0) if want_keep else (0, 1))
     _report(f"bf16x3 forced, {route}, keep_pre={want_keep}", errs, 3e-4)

@@ -135,7 +135,7 @@ def test_edge_mlp_gemms_at_cfg5_row_count(ops, K, N):
     want = ref_tn(G, A)                                                   # dW [N, K]
     if ops.gemm_split_tn_ok(Gs, As):
         got = ops.gemm_split_tn(Gs, As)
-    else:                                                                 # the transposed problem, as functional._wgrad_tn does
+    else:                                                                 # the transposed problem, as functional._wgrad does ("tn_t")
         got = ops.gemm_split_tn(As, Gs).t()
     r = float((got.double() - want).abs().max() / want.abs().max())
     assert r < TOL_SPLIT, f"edge wgrad {N}x{K}: {r:.2e}"

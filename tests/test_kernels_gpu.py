@@ -439,14 +439,16 @@ def test_first_layer_fused_forward_and_backward(ops, R, K, D):
 
 
 def test_wgrad_through_the_transposed_problem(ops):
-    """dW[128, 256] = dz^T·h does not tile (Mo % 256 != 0) but its transpose does: functional._wgrad_tn computes
-    h^T·dz and transposes the small result (third edge-MLP layer, EdgePredictor.py:64)."""
+    """dW[128, 256] = dz^T·h does not tile (Mo % 256 != 0) but its transpose does: the "tn_t" route of
+    functional._wgrad computes h^T·dz and transposes the small result (third edge-MLP layer at hidden 512,
+    EdgePredictor.py:64)."""
     from wf3d import functional as F
     K, Mo, No = 4096, 128, 256
     dz, h = rnd(K, Mo, seed=1), rnd(K, No, seed=2)
     dz_s, h_s = ops.split_rows(dz), ops.split_rows(h)
-    assert not ops.gemm_split_tn_ok(dz_s, h_s) and ops.gemm_split_tn_ok(h_s, dz_s) and F._tn_either(dz_s, h_s)
-    got = F._wgrad_tn(dz_s, h_s)
+    r = F._edge_routes(K, 512, "bf16x3", False)[1]
+    assert not ops.gemm_split_tn_ok(dz_s, h_s) and ops.gemm_split_tn_ok(h_s, dz_s) and r.wgrad == "tn_t"
+    got = F._wgrad(r, None, dz_s, None, None, h_s, 3)
     assert got.shape == (Mo, No) and got.is_contiguous()
     assert rel(got, dz.double().cpu().T @ h.double().cpu()) < TOL_SPLIT
 

@@ -145,7 +145,7 @@ def test_bf16_edge_mlp_gemms_at_cfg5_row_count(ops, K, N):
     if ops.gemm_split_tn_ok(Gs, As):
         got = ops.gemm_split_tn(Gs, As, products=1)
         r, _ = err_tn(got, Gs, As)
-    else:                                                                 # the transposed problem, as functional._wgrad_tn does
+    else:                                                                 # the transposed problem, as functional._wgrad does ("tn_t")
         got = ops.gemm_split_tn(As, Gs, products=1)
         r, _ = err_tn(got, As, Gs)
     assert r < TOL_ORACLE, f"edge wgrad {N}x{K}: {r:.2e}"

@@ -11,7 +11,12 @@ Data layout in HBM (fp32): per Linear only its PRE-LayerNorm output z and the
 per-row (mu, rstd) are stored; LN-apply + ReLU/GELU (+dropout) are re-applied in
 the staging pass of whichever GEMM consumes them (forward GEMM, wgrad GEMM), so
 normalised activations never exist in memory.
+
+Which kernels a Linear of the encoder's per-point MLP or of the edge MLP's two wide layers runs on, forward and
+backward, is its Route: decided once in the stage's forward (_encoder_routes, _edge_routes) and only read by backward.
 """
+from collections import namedtuple
+
 import torch
 
 from . import config, ops
@@ -47,13 +52,11 @@ def _params(ctx):
     return ctx.params
 
 
-def _lin_bwd(dz, a, W, pro_a, need_da=True, x3=False):
+def _lin_bwd(dz, a, W, pro_a):
     """Linear backward pieces for z = pro(a)·W^T + b given dz:
     dW = dz^T·pro(a) (TN, prologue re-applied to the stored pre-activation),
     d pro(a) = dz·W (NN)."""
-    dW = ops.gemm(dz, a, TN, pro=pro_a, x3=x3)
-    da = ops.gemm(dz, W, NN, x3=x3) if need_da else None
-    return dW, da
+    return ops.gemm(dz, a, TN, pro=pro_a), ops.gemm(dz, W, NN)
 
 
 _side_streams = {}
@@ -64,10 +67,10 @@ class _Leaves:
     `run(fn, *reads)` makes the side stream wait for everything issued so far on the current one, then calls fn
     under it; `reads` are the tensors fn consumes (their memory must not be recycled by the current stream's
     allocator pool before the side stream is done with them).  `join(*outs)` orders the current stream after the
-    side stream and hands the outputs over.  With config.SIDE_STREAM off, run() just calls fn."""
+    side stream and hands the outputs over.  Not enabled, run() just calls fn."""
 
     def __init__(self, device, enable=True):
-        self.on = enable and config.SIDE_STREAM and device.type == "cuda"
+        self.on = enable and device.type == "cuda"
         if self.on:
             self.main = torch.cuda.current_stream(device)
             self.side = _side_streams.get(device.index)
@@ -95,7 +98,7 @@ class _Leaves:
 
 
 # ===========================================================================
-# Encoder
+# Routes of the large Linears
 # ===========================================================================
 def _split_ok(rows, k, split):
     """A Linear runs as a bf16x3 split GEMM when the mode asks for it, the layer is big
@@ -107,19 +110,84 @@ def _split_ok(rows, k, split):
 # the GEMMs "bf16x3" runs split, one product (hi*hi) instead of three.
 _SPLIT_PRODUCTS = {"bf16x3": 3, "bf16": 1}
 
-
-def _tn_either(a_s, b_s):
-    """The wgrad kernel tiles dW[Mo, No] with Mo % 256 == 0; when only the transposed problem fits
-    (e.g. dW[128, 256]) it computes dW^T = h^T·dz and the small result is transposed."""
-    return ops.gemm_split_tn_ok(a_s, b_s) or ops.gemm_split_tn_ok(b_s, a_s)
+_TN = ("tn", "tn_t")        # the wgrad forms that read the forward's sx8 input operand instead of the fp32 one
 
 
-def _wgrad_tn(dz_s, h_s, products=3):
-    if ops.gemm_split_tn_ok(dz_s, h_s):
+# The kernels of one Linear z = h·W^T + b, forward and backward:
+# fwd    "split": gemm_split on sx8 operands; "fp32": gemm; "first": the encoder's fused first layer (first_layer_fwd)
+# wgrad  dW = dz^T·h.  "tn": the transposing-read TN kernel on both sx8 operands as stored; "tn_t": the same on the
+#        transposed problem dW^T = h^T·dz, the small result transposed back (the kernel tiles dW[Mo, No] with
+#        Mo % 256 == 0, e.g. not dW[128, 256]); "transposes": gemm_split on materialised split_transposes (shapes the TN
+#        kernel does not tile, whole 8-row groups); "fp32": gemm TN re-applying h's prologue to the stored z; "first":
+#        ln_act_bwd_first (LN/ReLU backward, bias and weight gradient of the encoder's first layer in one pass)
+# dgrad  dh = dz·W.  "split": gemm_split with W^T in sx8; "fp32": gemm NN; None: no input gradient
+# x3     the fp32 GEMMs' operands split in their staging pass (config.EDGE_X3)
+Route = namedtuple("Route", "fwd wgrad dgrad x3", defaults=(False,))
+
+
+def _dz32(r):
+    """Backward forms dz in fp32 (with both of its consumers on sx8 operands only the sx8 dz is written)."""
+    return "fp32" in (r.wgrad, r.dgrad)
+
+
+def _encoder_routes(x2, Ws, split, want_dx):
+    """Routes of the per-point MLP's Linears Ws = [W_0, ..., W_out] over the rows of x2.  Linear i >= 1 runs forward
+    split when its input width takes the split path (the LayerNorm pass before it then writes its operand in sx8), its
+    dgrad when its output width does, and its wgrad on sx8 operands when both do.  Linear 0 (in_features <= 8) is one
+    fused pass with its LayerNorm, forward and — unless the cloud requires grad: dx = dz·W needs dz — backward."""
+    M = x2.shape[0]
+    ok = lambda d: _split_ok(M, d, split)  # noqa: E731
+    first = len(Ws) > 1 and ok(Ws[0].shape[0]) and ops.first_layer_ok(x2, Ws[0])
+    dx = "fp32" if want_dx else None
+    routes = [Route("first", "fp32" if want_dx else "first", dx) if first else Route("fp32", "fp32", dx)]
+    for W in Ws[1:]:
+        n, k = W.shape
+        wgrad = "fp32"
+        if ok(n) and ok(k):
+            wgrad = "tn" if ops.gemm_split_tn_shape_ok(M, n, k, n, k) else "transposes" if M % 8 == 0 else "fp32"
+        routes.append(Route("split" if ok(k) else "fp32", wgrad, "split" if ok(n) else "fp32"))
+    return routes
+
+
+def _edge_routes(Re, H, precision, x3):
+    """Routes of the edge MLP's two wide Linears, edge_mlp.4 (H -> H/2) and edge_mlp.8 (H/2 -> H/4), over Re edge rows
+    (52 % of the FLOPs at V=256): both split or both fp32.  H / 4, the second one's width, is the reduction width of its
+    dgrad and the row length of its transposed weight: it has to be made of whole 8-column groups too
+    (EdgePredictor(hidden_dim=208) used to fail in split_weights)."""
+    if not (_split_ok(Re, H, precision in _SPLIT_PRODUCTS) and _split_ok(Re, H // 2, True) and (H // 4) % 8 == 0):
+        return Route("fp32", "fp32", "fp32", x3), Route("fp32", "fp32", "fp32", x3)
+
+    def wgrad(n, k):
+        if ops.gemm_split_tn_shape_ok(Re, n, k, n, k):
+            return "tn"
+        if ops.gemm_split_tn_shape_ok(Re, k, n, k, n):
+            return "tn_t"
+        return "transposes" if Re % 8 == 0 else "fp32"
+    return Route("split", wgrad(H // 2, H), "split", x3), Route("split", wgrad(H // 4, H // 2), "split", x3)
+
+
+def _wgrad(r, dz, dz_s, h, pro, h_s, products):
+    """dW = dz^T · pro(h) by the route's wgrad form: dz (fp32) or dz_s (sx8), whichever the route formed; h the stored
+    input with its prologue pro, h_s the forward's sx8 operand pro(h)."""
+    if r.wgrad == "tn":
         return ops.gemm_split_tn(dz_s, h_s, products=products)
-    return ops.gemm_split_tn(h_s, dz_s, products=products).t().contiguous()
+    if r.wgrad == "tn_t":
+        return ops.gemm_split_tn(h_s, dz_s, products=products).t().contiguous()
+    if r.wgrad == "transposes":
+        return ops.gemm_split(ops.split_transpose(dz_s, in_sx8=True), ops.split_transpose(h, pro), products=products)
+    return ops.gemm(dz, h, TN, pro=pro, x3=r.x3)
 
 
+def _dgrad(r, dz, dz_s, W, W_t, products):
+    """dh = dz · W by the route's dgrad form; W_t = W^T in sx8 when the forward split it, else None."""
+    if r.dgrad == "split":
+        return ops.gemm_split(dz_s, W_t if W_t is not None else ops.split_rows(W, transpose=True), products=products)
+    return ops.gemm(dz, W, NN, x3=r.x3)
+
+
+# ===========================================================================
+# Encoder
+# ===========================================================================
 class EncoderFn(torch.autograd.Function):
     """x[B,N,Din], params -> (pooled[B,2C] = [masked max | masked mean], point_features[B,N,C],
     upooled[B,2C] = [unmasked mean | unmasked max]).
@@ -139,43 +207,37 @@ class EncoderFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, n_hidden, precision, *params):
-        # a cloud that requires grad (train.py never asks) sends the first layer's backward down the general path, which
-        # forms dz and from it dx = dz . W
-        ctx.want_dx = ctx.needs_input_grad[0]
         B, N, Din = x.shape
         M = B * N
         x2 = x.reshape(M, Din)
         if not x2.is_contiguous():
             x2 = x2.contiguous()
-        split = precision in _SPLIT_PRODUCTS
         npr = _SPLIT_PRODUCTS.get(precision, 3)
         valid = ops.point_valid(x2)
-        # both sx8 orientations (W for the forward GEMM, W^T for its dgrad) of every split layer's weight, one launch
-        widx = [i for i in range(1, n_hidden + 1)
-                if _split_ok(M, params[4 * i].shape[1], split) and _split_ok(M, params[4 * i].shape[0], split)]
+        routes = _encoder_routes(x2, [params[4 * i] for i in range(n_hidden + 1)], precision in _SPLIT_PRODUCTS,
+                                 ctx.needs_input_grad[0])
+        # both sx8 orientations (W for the forward GEMM, W^T for its dgrad) of every layer split both ways, one launch
+        widx = [i for i, r in enumerate(routes) if r.fwd == "split" and r.dgrad == "split"]
         wsplit = dict(zip(widx, ops.split_weights([params[4 * i] for i in widx]))) if widx else {}
         zs, stats, hs = [], [], []                 # hs[i] = sx8 operand consumed by Linear i+1 (kept for its wgrad)
         a, a_s, pro = x2, None, None
-        for i in range(n_hidden + 1):
-            last = i == n_hidden
+        for i, r in enumerate(routes):
             W, b = params[4 * i], params[4 * i + 1]
-            fused0 = (i == 0 and not last and _split_ok(M, W.shape[0], split) and ops.first_layer_ok(x2, W))
-            if fused0:
+            if r.fwd == "first":
                 # first Linear + LayerNorm + ReLU + split in one pass (K = input_dim <= 8: a pure write of z and h)
                 z, mu, rs, a_s = ops.first_layer_fwd(x2, W, b, params[2], params[3], ACT_RELU)
-            elif a_s is not None:
+            elif r.fwd == "split":
                 z = ops.gemm_split(a_s, wsplit[i][0] if i in wsplit else ops.split_rows(W), bias=b, products=npr)
                 a_s = None
             else:
                 z = ops.gemm(a, W, NT, bias=b, pro=pro)
-                a_s = None
-            if last:
+            if i == n_hidden:
                 pf = z
                 break
             g, be = params[4 * i + 2], params[4 * i + 3]
-            if fused0:
+            if r.fwd == "first":
                 pass
-            elif _split_ok(M, z.shape[1], split):
+            elif routes[i + 1].fwd == "split":
                 mu, rs, a_s = ops.ln_prep(z, g, be, ACT_RELU)
             else:
                 mu, rs = ops.row_stats(z)
@@ -187,7 +249,7 @@ class EncoderFn(torch.autograd.Function):
         del a_s
         C = pf.shape[1]
         po = ops.pool4_fwd(pf.view(B, N, C), valid, packed=True)          # [max | avg] (PointNetEncoder.py:115), [mean | max]
-        ctx.n_hidden, ctx.dims, ctx.split, ctx.products = n_hidden, (B, N, C), split, npr
+        ctx.n_hidden, ctx.dims, ctx.products, ctx.routes = n_hidden, (B, N, C), npr, routes
         _keep_params(ctx, params)
         ctx.saved = (x2, valid, zs, stats, hs, po.arg_m, po.arg_u, po.cnt)
         ctx.nvalid = po.nvalid
@@ -199,12 +261,11 @@ class EncoderFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dpooled, dpf, dupooled):
-        nh, (B, N, C), split, npr = ctx.n_hidden, ctx.dims, ctx.split, ctx.products
+        nh, (B, N, C), npr, routes = ctx.n_hidden, ctx.dims, ctx.products, ctx.routes
         M = B * N
         params = _params(ctx)
         x2, valid, zs, stats, hs, arg_m, arg_u, cnt = _saved(ctx)
         grads = [None] * len(params)
-        dx = None
         # the pooled cotangents are read as strided halves of the [B, 2C] gradients: no copies
         dmmax = dmavg = dumean = dumax = None
         if dpooled is not None:
@@ -215,22 +276,19 @@ class EncoderFn(torch.autograd.Function):
             dumean, dumax = dupooled[:, :C], dupooled[:, C:]
         if dpf is not None:
             dpf = dpf.contiguous()
-        # output layer: with both of its consumers on the split path dz goes straight out as an sx8 operand
+        # output layer: in front of the TN wgrad (its dgrad is then split too) dz goes straight out as an sx8 operand
         # and its column sum (the bias gradient) follows from the [B, C] cotangents
-        W_out = params[4 * nh]
-        out_split = (nh > 0 and _split_ok(M, W_out.shape[0], split) and C % 8 == 0 and hs[nh - 1] is not None
-                     and ops.gemm_split_tn_shape_ok(M, C, hs[nh - 1].shape[1], C, hs[nh - 1].stride(0)))
-        if out_split:
+        if routes[nh].wgrad == "tn":
             dz, dz_s = None, ops.pool4_bwd(valid, cnt, arg_m, arg_u, dmmax, dmavg, dumean, dumax, dpf, B, N, C, sx8=True).view(M, C)
             grads[4 * nh + 1] = ops.pool4_bwd_colsum(ctx.nvalid, cnt, arg_m, arg_u, dmmax, dmavg, dumean, dumax, dpf, B, N, C)
         else:
             dz = ops.pool4_bwd(valid, cnt, arg_m, arg_u, dmmax, dmavg, dumean, dumax, dpf, B, N, C).view(M, C)
             dz_s = None
         # per-point MLP backward, output layer first.  Entering iteration i: dz = grad wrt the
-        # pre-LN output of Linear i (fp32) and, in split mode, dz_s = the same in sx8.
+        # pre-LN output of Linear i in fp32 and / or, on a split dgrad, dz_s = the same in sx8.
         for i in range(nh, -1, -1):
-            W = params[4 * i]
-            if i == 0 and nh > 0 and not ctx.want_dx and _split_ok(M, W.shape[0], split) and ops.first_layer_ok(x2, W):
+            r, W = routes[i], params[4 * i]
+            if r.wgrad == "first":
                 # layer 0: LN/ReLU backward, bias and WEIGHT gradient in one pass over (dh, z); dz is never written
                 g, be = params[2], params[3]
                 grads[2], grads[3], grads[1], grads[0] = ops.ln_act_bwd_first(dh, zs[0], x2, stats[0][0], stats[0][1], g, be, ACT_RELU)
@@ -238,45 +296,26 @@ class EncoderFn(torch.autograd.Function):
             if i < nh:
                 g, be = params[4 * i + 2], params[4 * i + 3]
                 mu, rs = stats[i]
-                want_s = i > 0 and _split_ok(M, W.shape[0], split)
-                dz_s = torch.empty_like(dh) if want_s else None
-                # with both consumers (dgrad, wgrad) on the split path the fp32 dz is never needed
-                tn_ok = want_s and hs[i - 1] is not None and ops.gemm_split_tn_ok(dh, hs[i - 1])
-                all_split = want_s and (tn_ok or (_split_ok(M, W.shape[1], split) and M % 8 == 0))
+                dz_s = torch.empty_like(dh) if r.dgrad == "split" else None
                 dz, grads[4 * i + 2], grads[4 * i + 3], grads[4 * i + 1] = ops.ln_act_bwd(
-                    dh, zs[i], mu, rs, g, be, ACT_RELU, inplace=True, dz_split=dz_s, want_dz=not all_split)
+                    dh, zs[i], mu, rs, g, be, ACT_RELU, inplace=True, dz_split=dz_s, want_dz=_dz32(r))
             elif dz is not None:
                 grads[4 * i + 1] = ops.colsum(dz)
-                if nh and _split_ok(M, W.shape[0], split):
+                if r.dgrad == "split":
                     dz_s = ops.split_rows(dz)
             if i > 0:
                 pg, pb = params[4 * (i - 1) + 2], params[4 * (i - 1) + 3]
-                a_prev, pro_prev = zs[i - 1], Pro(ACT_RELU, stats[i - 1][0], stats[i - 1][1], pg, pb)
+                h, pro, h_s = zs[i - 1], Pro(ACT_RELU, stats[i - 1][0], stats[i - 1][1], pg, pb), hs[i - 1]
             else:
-                a_prev, pro_prev = x2, None
-            K = W.shape[1]
-            h_prev_s = hs[i - 1] if i > 0 else None
-            if i > 0 and dz_s is not None and h_prev_s is not None and ops.gemm_split_tn_ok(dz_s, h_prev_s):
-                # wgrad dW = dz^T · h_prev straight from the reduction-major sx8 operands (transposing LDS reads)
-                grads[4 * i] = ops.gemm_split_tn(dz_s, h_prev_s, products=npr)
-                if not config.RETAIN_SAVED:
-                    hs[i - 1] = None
-            elif i > 0 and dz_s is not None and _split_ok(M, K, split) and M % 8 == 0:
-                # same through materialised transposes (shapes the TN kernel does not tile)
-                grads[4 * i] = ops.gemm_split(ops.split_transpose(dz_s, in_sx8=True), ops.split_transpose(a_prev, pro_prev),
-                                              products=npr)
-            else:
-                grads[4 * i] = ops.gemm(dz, a_prev, TN, pro=pro_prev)
-            if i > 0:
-                if dz_s is not None:
-                    dh = ops.gemm_split(dz_s, ctx.wT[i] if i in ctx.wT else ops.split_rows(W, transpose=True),     # dgrad: dz · W
-                                        products=npr)
-                else:
-                    dh = ops.gemm(dz, W, NN)
-            elif ctx.want_dx:
-                dx = ops.gemm(dz, W, NN).view(B, N, -1)           # at layer 0 dz is always the fp32 tensor
+                h, pro, h_s = x2, None, None
+            grads[4 * i] = _wgrad(r, dz, dz_s, h, pro, h_s, npr)
+            if r.wgrad == "tn" and not config.RETAIN_SAVED:
+                hs[i - 1] = None
+            if r.dgrad is not None:
+                dh = _dgrad(r, dz, dz_s, W, ctx.wT.get(i), npr)
             del dz, dz_s
             dz = dz_s = None
+        dx = dh.view(B, N, -1) if routes[0].dgrad is not None else None
         if not config.RETAIN_SAVED:
             ctx.saved = None
         return (dx, None, None, *grads)
@@ -503,35 +542,27 @@ class EdgeFn(torch.autograd.Function):
             ops.gemm(cv, Wc, NT, out=Pa, accumulate=True)
             Pb = ops.gemm(Fm, Wb, NT, x3=x3)
             ops.gemm(cv, Wd, NT, out=Pb, accumulate=True)
-        # the two wide edge-MLP layers (E rows: 52 % of the FLOPs at V=256) on the split path
-        # (H / 4, the third layer's width, is the reduction width of its dgrad and the row length of its transposed weight:
-        # it has to be made of whole 8-column groups too — EdgePredictor(hidden_dim=208) used to fail in split_weights)
         npr = _SPLIT_PRODUCTS.get(precision, 3)
-        split = _split_ok(meta.Re, H, precision in _SPLIT_PRODUCTS) and _split_ok(meta.Re, H // 2, True) and (H // 4) % 8 == 0
-        if split:
+        routes = _edge_routes(meta.Re, H, precision, x3)
+        if routes[0].fwd == "split":
             # the pair kernel holds each edge row in registers: it also emits gelu(LN(pre)) as the next GEMM's operand.
             # `pre` itself (2 KB per edge row) is stored only when something in backward reads it: with the wgrad of the
             # second edge layer on the transposing-read kernel (operand h1) and the LayerNorm backward rebuilding the
-            # row from Pa / Pb (ops.edge_pair_ln_bwd), nothing does.
-            tn2 = (ops.gemm_split_tn_shape_ok(meta.Re, H // 2, H, H // 2, H)
-                   or ops.gemm_split_tn_shape_ok(meta.Re, H, H // 2, H, H // 2))          # what backward's _tn_either(dh2, h1) will say
-            keep_pre = not (tn2 and H <= 1024) or config.KEEP_PRE
+            # row from Pa / Pb (ops.edge_pair_ln_bwd, H <= 1024), nothing does.
+            keep_pre = routes[0].wgrad not in _TN or H > 1024
             pre, mu0, rs0, delta, h1 = ops.edge_pair_fwd(Pa, Pb, cv, M0w, meta, ln=(M1g, M1b, ACT_GELU, p1_, sd[2]), keep_pre=keep_pre)
-        else:
-            pre, mu0, rs0, delta = ops.edge_pair_fwd(Pa, Pb, cv, M0w, meta)
-        if pre is not None:
-            Pa = Pb = None
-        if split:
             (M4s, M4t), (M8s, M8t) = ops.split_weights([M4w, M8w])
-            ctx.wT = (M4t, M8t)
             z2 = ops.gemm_split(h1, M4s, bias=M4b, products=npr)
             mu2, rs2, h2 = ops.ln_prep(z2, M5g, M5b, ACT_GELU, drop_p=p2_, seed=sd[3])
             s2 = (mu2, rs2)
             z3 = ops.gemm_split(h2, M8s, bias=M8b, products=npr)
         else:
-            h1 = h2 = None
+            pre, mu0, rs0, delta = ops.edge_pair_fwd(Pa, Pb, cv, M0w, meta)
+            h1 = h2 = M4t = M8t = None
             z2 = ops.gemm(pre, M4w, NT, bias=M4b, pro=Pro(ACT_GELU, mu0, rs0, M1g, M1b, p1_, sd[2]), x3=x3); s2 = ops.row_stats(z2)
             z3 = ops.gemm(z2, M8w, NT, bias=M8b, pro=Pro(ACT_GELU, s2[0], s2[1], M5g, M5b, p2_, sd[3]), x3=x3)
+        if pre is not None:
+            Pa = Pb = None
         if ops.rowdot_act_ok(z3, M10w):
             logit = ops.rowdot_act(z3, M10w, M10b, ACT_GELU)          # one-output Linear: a row dot product, not a GEMM
         else:
@@ -539,7 +570,7 @@ class EdgeFn(torch.autograd.Function):
         probs = ops.edge_prob_fwd(logit, meta)
         _keep_params(ctx, params)
         ctx.cfg = (B, V, H, heads, (pf_, pa_, p1_, p2_), sd, meta)
-        ctx.split, ctx.x3, ctx.products = split, x3, npr
+        ctx.routes, ctx.wT, ctx.x3, ctx.products = routes, (M4t, M8t), x3, npr
         ctx.saved = (cv, za, sa, zb, sb, f, qkv, cx, lse, Fm, pre, mu0, rs0, delta, z2, s2, z3, h1, h2, Pa, Pb)
         ctx.save_for_backward(probs)
         return probs
@@ -571,44 +602,27 @@ class EdgeFn(torch.autograd.Function):
             G[22], dh3 = _lin_bwd(dlogit, z3, M10w, Pro(ACT_GELU))
         p2 = Pro(ACT_GELU, s2[0], s2[1], M5g, M5b, p2_, sd[3])
         p1 = Pro(ACT_GELU, mu0, rs0, M1g, M1b, p1_, sd[2])
-        tsplit = ctx.split and meta.Re % 8 == 0              # (transposed) wgrad operands need whole 8-row groups
-        if ctx.split:
-            dz3_s = torch.empty_like(dh3)
-            tn3 = _tn_either(dh3, h2)                       # dz3_s has dh3's shape
-            if fused_tail:
-                # logits-layer backward + GELU backward + both column sums in one pass over z3
-                dz3, G[22], G[21] = ops.rowdot_act_bwd(z3, dlogit, M10w, ACT_GELU, want_dz=not (tsplit or tn3), dz_split=dz3_s)
-            else:
-                dz3, _, _, G[21] = ops.ln_act_bwd(dh3, z3, None, None, None, None, ACT_GELU, inplace=True,
-                                                  dz_split=dz3_s, want_dz=not (tsplit or tn3))
-            if tn3:
-                G[20] = lv.run(lambda: _wgrad_tn(dz3_s, h2, npr), dz3_s, h2)
-            else:
-                G[20] = lv.run(lambda: (ops.gemm_split(ops.split_transpose(dz3_s, in_sx8=True), ops.split_transpose(z2, p2), products=npr) if tsplit
-                                        else ops.gemm(dz3, z2, TN, pro=p2, x3=x3)), dz3_s, dz3, z2)
-            dh2 = ops.gemm_split(dz3_s, ctx.wT[1], products=npr)
-            del dz3, dz3_s
-            dz2_s = torch.empty_like(dh2)
-            tn2 = _tn_either(dh2, h1)
-            dz2, G[18], G[19], G[17] = ops.ln_act_bwd(dh2, z2, s2[0], s2[1], M5g, M5b, ACT_GELU, p2_, sd[3],
-                                                      inplace=True, dz_split=dz2_s, want_dz=not (tsplit or tn2))
-            if tn2:
-                G[16] = lv.run(lambda: _wgrad_tn(dz2_s, h1, npr), dz2_s, h1)
-            else:
-                G[16] = lv.run(lambda: (ops.gemm_split(ops.split_transpose(dz2_s, in_sx8=True), ops.split_transpose(pre, p1), products=npr) if tsplit
-                                        else ops.gemm(dz2, pre, TN, pro=p1, x3=x3)), dz2_s, dz2, pre)
-            dh1 = ops.gemm_split(dz2_s, ctx.wT[0], products=npr)
-            del dz2, dz2_s
+        r2, r3 = ctx.routes
+
+        def wgrad(r, dz, dz_s, h, pro, h_s):
+            return lv.run(lambda: _wgrad(r, dz, dz_s, h, pro, h_s, npr), dz_s, dz, h_s if r.wgrad in _TN else h)
+        # edge_mlp.8, then edge_mlp.4: dz in sx8 for split dgrads, in fp32 where a consumer reads it
+        dz3_s = torch.empty_like(dh3) if r3.dgrad == "split" else None            # dz3 has dh3's shape
+        if fused_tail:
+            # logits-layer backward + GELU backward + both column sums in one pass over z3
+            dz3, G[22], G[21] = ops.rowdot_act_bwd(z3, dlogit, M10w, ACT_GELU, want_dz=_dz32(r3), dz_split=dz3_s)
         else:
-            if fused_tail:
-                dz3, G[22], G[21] = ops.rowdot_act_bwd(z3, dlogit, M10w, ACT_GELU)
-            else:
-                dz3, _, _, G[21] = ops.ln_act_bwd(dh3, z3, None, None, None, None, ACT_GELU, inplace=True)
-            G[20] = lv.run(lambda: ops.gemm(dz3, z2, TN, pro=p2, x3=x3), dz3, z2)
-            dh2 = ops.gemm(dz3, M8w, NN, x3=x3)
-            dz2, G[18], G[19], G[17] = ops.ln_act_bwd(dh2, z2, s2[0], s2[1], M5g, M5b, ACT_GELU, p2_, sd[3], inplace=True)
-            G[16] = lv.run(lambda: ops.gemm(dz2, pre, TN, pro=p1, x3=x3), dz2, pre)
-            dh1 = ops.gemm(dz2, M4w, NN, x3=x3)
+            dz3, _, _, G[21] = ops.ln_act_bwd(dh3, z3, None, None, None, None, ACT_GELU, inplace=True,
+                                              dz_split=dz3_s, want_dz=_dz32(r3))
+        G[20] = wgrad(r3, dz3, dz3_s, z2, p2, h2)
+        dh2 = _dgrad(r3, dz3, dz3_s, M8w, ctx.wT[1], npr)
+        del dz3, dz3_s
+        dz2_s = torch.empty_like(dh2) if r2.dgrad == "split" else None
+        dz2, G[18], G[19], G[17] = ops.ln_act_bwd(dh2, z2, s2[0], s2[1], M5g, M5b, ACT_GELU, p2_, sd[3],
+                                                  inplace=True, dz_split=dz2_s, want_dz=_dz32(r2))
+        G[16] = wgrad(r2, dz2, dz2_s, pre, p1, h1)
+        dh1 = _dgrad(r2, dz2, dz2_s, M4w, ctx.wT[0], npr)
+        del dz2, dz2_s
         # LN/GELU backward of the first edge layer; the same pass yields the gradient of its distance-weight column
         if pre is None:
             dpre, G[14], G[15], wsum = ops.edge_pair_ln_bwd(dh1, Pa, Pb, delta, M0w, meta, mu0, rs0, M1g, M1b, ACT_GELU, p1_, sd[2])
