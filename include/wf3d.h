@@ -446,6 +446,26 @@ int wf3d_clip_adam_step(float* const* params, float* const* grads, float* const*
                         const long* numel, int ntensors, double max_norm, double lr, double beta1, double beta2, double eps,
                         double weight_decay, int step, float* ws, size_t ws_floats, float* total_norm, void* stream);
 
+/* Capturable form (torch.optim.Adam(capturable=True) layout): steps[i] is tensor i's Adam step, a device fp32 scalar
+ * (NULL where params[i] is NULL), read by the kernel — steps[i] + 1 is the step applied — and advanced by one after the
+ * last Adam launch; every optimised tensor must be at the same step.  lr_dev (device fp32 scalar) replaces lr when
+ * non-NULL.  Nothing is read on the host, so a captured launch sequence is right on every replay. */
+int wf3d_clip_adam_step_dev(float* const* params, float* const* grads, float* const* exp_avg, float* const* exp_avg_sq,
+                            float* const* steps, const long* numel, int ntensors, double max_norm, double lr,
+                            const float* lr_dev, double beta1, double beta2, double eps, double weight_decay, float* ws,
+                            size_t ws_floats, float* total_norm, void* stream);
+
+/* ------------------------------------------------------------------------
+ * Device-side dropout seeds (wf3d/random.py).  state = {key, counter} (uint64, device).  wf3d_dropout_draw: one thread
+ * writes words[0..4] = s + k * 0x9E3779B9 (k = 0..4; words[k] for k >= 1 are EdgeFn's per-site seeds) with
+ * s = low 32 bits of splitmix64 at position counter + 1 of the key's stream, then advances the counter.
+ * wf3d_set_dropout_seed_words (thread-local, host only): while `words` is non-NULL, every `drop_seed` argument of a
+ * launch with drop_p > 0 on the calling thread (wf3d_gemm_t.drop_seed included) is an index into these device words,
+ * loaded by the kernel at run time; NULL restores seeds by value.
+ * ------------------------------------------------------------------------ */
+int wf3d_dropout_draw(uint64_t* state, uint32_t* words, void* stream);
+int wf3d_set_dropout_seed_words(const uint32_t* words);
+
 /* Training-step meter (reference train.py:145-157: total_loss.item() twice and a host copy of sample 0's vertices on EVERY
  * step, for the loss history, the best loss and a monitoring RMSE).  One small launch per step folds them into a
  * device-resident record; the loop copies it back only when it logs.

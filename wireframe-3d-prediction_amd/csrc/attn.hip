@@ -29,7 +29,7 @@ struct AttnParams {
     const int32_t* voff;   // [S+1]
     int E, heads, hd, vmax, ch;          // ch = rows of K / V (or Q / dctx) staged at a time = min(vmax, 256)
     float scale;
-    uint32_t seed, thresh; float dscale;
+    wf3d_seed_t seed; uint32_t thresh; float dscale;
 };
 
 __device__ __forceinline__ float dot_lds(const float* a, const float* b, int hd) {
@@ -59,6 +59,7 @@ __device__ __forceinline__ void stage_rows(float* dst, const float* __restrict__
 // the running (lse, ctx) rows in global memory:  lse' = log(e^lse + e^lse_c),  ctx' = e^(lse - lse') ctx + e^(lse_c - lse') ctx_c.
 // With one chunk (every BASELINE config: vmax <= 256) nothing is merged and the arithmetic is the single-pass one.
 __global__ __launch_bounds__(256) void attn_fwd_kernel(const AttnParams p) {
+    const uint32_t seed = p.thresh ? wf3d_seed_load(p.seed) : 0u;
     extern __shared__ __attribute__((aligned(16))) float sm[];
     const int h = blockIdx.x, s = blockIdx.y;
     const int r0 = p.voff[s], n = p.voff[s + 1] - r0;
@@ -106,7 +107,7 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(const AttnParams p) {
                 if (j < p.ch) {
                     float pv = sc[t] * inv;
                     if (p.thresh && act && j < cn)
-                        pv = wf3d_keep(p.seed, (uint32_t)((r0 + i) * p.heads + h), (uint32_t)(kc + j), p.thresh) ? pv * p.dscale : 0.f;
+                        pv = wf3d_keep(seed, (uint32_t)((r0 + i) * p.heads + h), (uint32_t)(kc + j), p.thresh) ? pv * p.dscale : 0.f;
                     pw[j] = pv;
                 }
             }
@@ -142,6 +143,7 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(const AttnParams p) {
 // No atomics: every dq/dk/dv element is produced by exactly one wave; with more than p.ch vertices the partial sums of
 // the chunks are accumulated by that wave in global memory, in chunk order.
 __global__ __launch_bounds__(256) void attn_bwd_kernel(const AttnParams p) {
+    const uint32_t seed = p.thresh ? wf3d_seed_load(p.seed) : 0u;
     extern __shared__ __attribute__((aligned(16))) float sm[];
     const int h = blockIdx.x, s = blockIdx.y;
     const int r0 = p.voff[s], n = p.voff[s + 1] - r0;
@@ -190,7 +192,7 @@ __global__ __launch_bounds__(256) void attn_bwd_kernel(const AttnParams p) {
                     const float pr = expf(dot_lds(q, Xa + j * ldr, hd) - lse_i);
                     float g = dot_lds(o, Xb + j * ldr, hd);
                     if (p.thresh)
-                        g = wf3d_keep(p.seed, (uint32_t)((r0 + i) * p.heads + h), (uint32_t)(kc + j), p.thresh) ? g * p.dscale : 0.f;
+                        g = wf3d_keep(seed, (uint32_t)((r0 + i) * p.heads + h), (uint32_t)(kc + j), p.thresh) ? g * p.dscale : 0.f;
                     ds = pr * (g - dsum);
                 }
                 if (j < p.ch) pw[j] = ds;
@@ -239,7 +241,7 @@ __global__ __launch_bounds__(256) void attn_bwd_kernel(const AttnParams p) {
                     float g = dot_lds(Xb + i * ldr, o, hd);
                     float mk = 1.0f;
                     if (p.thresh)
-                        mk = wf3d_keep(p.seed, (uint32_t)((r0 + qc + i) * p.heads + h), (uint32_t)j, p.thresh) ? p.dscale : 0.f;
+                        mk = wf3d_keep(seed, (uint32_t)((r0 + qc + i) * p.heads + h), (uint32_t)j, p.thresh) ? p.dscale : 0.f;
                     ds = pr * (g * mk - dl[i]);
                     pt = pr * mk;
                 }
@@ -298,7 +300,7 @@ extern "C" int wf3d_attn_fwd(const float* qkv, const int32_t* voff, int S, int v
     p.qkv = qkv; p.ctx = ctx; p.lse = lse; p.voff = voff;
     p.E = E; p.heads = heads; p.hd = E / heads; p.vmax = vmax; p.ch = attn_chunk(vmax);
     p.scale = 1.0f / sqrtf((float)p.hd);
-    if (drop_p > 0.f) { p.seed = drop_seed; p.thresh = (uint32_t)((double)drop_p * 4294967296.0); p.dscale = 1.0f / (1.0f - drop_p); }
+    if (drop_p > 0.f) { p.seed = wf3d_seed_arg(drop_p, drop_seed); p.thresh = (uint32_t)((double)drop_p * 4294967296.0); p.dscale = 1.0f / (1.0f - drop_p); }
     const size_t lds = attn_lds_bytes(vmax, p.hd, false);
     if (lds > 64 * 1024) {
         hipError_t e = hipFuncSetAttribute((const void*)attn_fwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
@@ -323,7 +325,7 @@ extern "C" int wf3d_attn_bwd(const float* qkv, const float* dctx, const float* c
     p.qkv = qkv; p.dctx = dctx; p.ctx = (float*)ctx; p.lse = (float*)lse; p.dqkv = dqkv; p.voff = voff;
     p.E = E; p.heads = heads; p.hd = E / heads; p.vmax = vmax; p.ch = attn_chunk(vmax);
     p.scale = 1.0f / sqrtf((float)p.hd);
-    if (drop_p > 0.f) { p.seed = drop_seed; p.thresh = (uint32_t)((double)drop_p * 4294967296.0); p.dscale = 1.0f / (1.0f - drop_p); }
+    if (drop_p > 0.f) { p.seed = wf3d_seed_arg(drop_p, drop_seed); p.thresh = (uint32_t)((double)drop_p * 4294967296.0); p.dscale = 1.0f / (1.0f - drop_p); }
     const size_t lds = attn_lds_bytes(vmax, p.hd, true);
     if (lds > 64 * 1024) {
         hipError_t e = hipFuncSetAttribute((const void*)attn_bwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);

@@ -26,7 +26,7 @@ struct MAttn {
     const int32_t* voff;
     int E, heads, vpad;                     // vpad = rows reserved per operand in LDS (multiple of 32)
     float scale;
-    uint32_t seed, thresh; float dscale;
+    wf3d_seed_t seed; uint32_t thresh; float dscale;
 };
 
 __device__ __forceinline__ int rowof(int e, int h) { return (e & 3) + 8 * (e >> 2) + 4 * h; }
@@ -68,6 +68,7 @@ __device__ __forceinline__ f32x16 mm_rows_regs(const float* lds_row_half, const 
 }
 
 __global__ __launch_bounds__(256, 1) void attn_fwd_mfma_kernel(const MAttn p) {
+    const uint32_t seed = p.thresh ? wf3d_seed_load(p.seed) : 0u;
     extern __shared__ __attribute__((aligned(16))) float sm[];
     const int head = blockIdx.x, s = blockIdx.y;
     const int r0 = p.voff[s], n = p.voff[s + 1] - r0;
@@ -123,7 +124,7 @@ __global__ __launch_bounds__(256, 1) void attn_fwd_mfma_kernel(const MAttn p) {
                 for (int e = 0; e < 16; ++e) {
                     const int j = jt * 32 + rowof(e, h);
                     float pv = st[jt][e] * inv;
-                    if (p.thresh) pv = wf3d_keep(p.seed, (uint32_t)((r0 + i) * p.heads + head), (uint32_t)j, p.thresh) ? pv * p.dscale : 0.f;
+                    if (p.thresh) pv = wf3d_keep(seed, (uint32_t)((r0 + i) * p.heads + head), (uint32_t)j, p.thresh) ? pv * p.dscale : 0.f;
                     const float* vr = Vs + j * LDR + l31;
                     o[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(vr[0], pv, o[0], 0, 0, 0);
                     o[1] = __builtin_amdgcn_mfma_f32_32x32x2f32(vr[32], pv, o[1], 0, 0, 0);
@@ -144,6 +145,7 @@ __global__ __launch_bounds__(256, 1) void attn_fwd_mfma_kernel(const MAttn p) {
 }
 
 __global__ __launch_bounds__(256) void attn_bwd_mfma_kernel(const MAttn p) {
+    const uint32_t seed = p.thresh ? wf3d_seed_load(p.seed) : 0u;
     extern __shared__ __attribute__((aligned(16))) float sm[];
     const int head = blockIdx.x, s = blockIdx.y;
     const int r0 = p.voff[s], n = p.voff[s + 1] - r0;
@@ -196,7 +198,7 @@ __global__ __launch_bounds__(256) void attn_bwd_mfma_kernel(const MAttn p) {
                 const int j = jt * 32 + rowof(e, h);
                 const float pr = j < n ? expf(st[e] - lse_i) : 0.f;
                 float g = dp[e];
-                if (p.thresh) g = wf3d_keep(p.seed, (uint32_t)((r0 + i) * p.heads + head), (uint32_t)j, p.thresh) ? g * p.dscale : 0.f;
+                if (p.thresh) g = wf3d_keep(seed, (uint32_t)((r0 + i) * p.heads + head), (uint32_t)j, p.thresh) ? g * p.dscale : 0.f;
                 const float ds = pr * (g - delta);
                 const float* kr = Xa + j * LDR + l31;
                 dq[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(kr[0], ds, dq[0], 0, 0, 0);
@@ -238,7 +240,7 @@ __global__ __launch_bounds__(256) void attn_bwd_mfma_kernel(const MAttn p) {
                 const int i = it * 32 + rowof(e, h);
                 const float pr = expf(sc[e] - ls[i]);                                    // 0 for padded queries
                 float mk = 1.0f;
-                if (p.thresh) mk = wf3d_keep(p.seed, (uint32_t)((r0 + i) * p.heads + head), (uint32_t)j, p.thresh) ? p.dscale : 0.f;
+                if (p.thresh) mk = wf3d_keep(seed, (uint32_t)((r0 + i) * p.heads + head), (uint32_t)j, p.thresh) ? p.dscale : 0.f;
                 const float ds = pr * (dp[e] * mk - dl[i]);
                 const float pt = pr * mk;
                 const float* qr = Xa + i * LDR + l31;
@@ -274,7 +276,7 @@ extern "C" int wf3d_attn_fwd_mfma(const float* qkv, const int32_t* voff, int S, 
     p.qkv = qkv; p.ctx = ctx; p.lse = lse; p.voff = voff;
     p.E = E; p.heads = heads; p.vpad = (vmax + 31) & ~31;
     p.scale = 1.0f / sqrtf((float)HD);
-    if (drop_p > 0.f) { p.seed = drop_seed; p.thresh = (uint32_t)((double)drop_p * 4294967296.0); p.dscale = 1.0f / (1.0f - drop_p); }
+    if (drop_p > 0.f) { p.seed = wf3d_seed_arg(drop_p, drop_seed); p.thresh = (uint32_t)((double)drop_p * 4294967296.0); p.dscale = 1.0f / (1.0f - drop_p); }
     const size_t lds = (size_t)2 * p.vpad * LDR * sizeof(float);
     if (lds > 64 * 1024) {
         hipError_t e = hipFuncSetAttribute((const void*)attn_fwd_mfma_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
@@ -292,7 +294,7 @@ extern "C" int wf3d_attn_bwd_mfma(const float* qkv, const float* dctx, const flo
     p.qkv = qkv; p.dctx = dctx; p.ctx_in = ctx; p.lse = (float*)lse; p.dqkv = dqkv; p.voff = voff;
     p.E = E; p.heads = heads; p.vpad = (vmax + 31) & ~31;
     p.scale = 1.0f / sqrtf((float)HD);
-    if (drop_p > 0.f) { p.seed = drop_seed; p.thresh = (uint32_t)((double)drop_p * 4294967296.0); p.dscale = 1.0f / (1.0f - drop_p); }
+    if (drop_p > 0.f) { p.seed = wf3d_seed_arg(drop_p, drop_seed); p.thresh = (uint32_t)((double)drop_p * 4294967296.0); p.dscale = 1.0f / (1.0f - drop_p); }
     const size_t lds = ((size_t)2 * p.vpad * LDR + 2 * p.vpad) * sizeof(float);
     if (lds > 64 * 1024) {
         hipError_t e = hipFuncSetAttribute((const void*)attn_bwd_mfma_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);

@@ -51,8 +51,9 @@ __global__ __launch_bounds__(256) void pair_fwd_kernel(const float* __restrict__
                                                         float* __restrict__ pre, float* __restrict__ mu,
                                                         float* __restrict__ rs, float* __restrict__ delta,
                                                         const float* __restrict__ gamma, const float* __restrict__ beta,
-                                                        int act, uint32_t seed, uint32_t thresh, float dscale,
+                                                        int act, const wf3d_seed_t seed_src, uint32_t thresh, float dscale,
                                                         float* __restrict__ h_sx8, int vd) {
+    const uint32_t seed = thresh ? wf3d_seed_load(seed_src) : 0u;
     constexpr int EPW = 8;
     const int lane = threadIdx.x & 63;
     const int e0 = (blockIdx.x * 4 + (threadIdx.x >> 6)) * EPW;
@@ -369,9 +370,10 @@ static int pair_fwd_impl(const float* Pa, const float* Pb, const float* cv, cons
                "wf3d_edge_pair_fwd: null pointer");
     const int ns = wf3d_cdiv(H, 256);
     hipStream_t st = (hipStream_t)stream;
+    const wf3d_seed_t seed = wf3d_seed_arg(drop_p, drop_seed);
 #define WF3D_PF(NS_)                                                                                                 \
     hipLaunchKernelGGL((pair_fwd_kernel<NS_>), dim3(wf3d_cdiv(Re, 4 * 8)), dim3(256), 0, st, Pa, Pb, cv, wdelta,           \
-                       wdelta_stride, voff, eoff, esample, Re, H, eps, pre, mu, rs, delta, gamma, beta, act, drop_seed,    \
+                       wdelta_stride, voff, eoff, esample, Re, H, eps, pre, mu, rs, delta, gamma, beta, act, seed,         \
                        thresh, dscale, (float*)h_sx8, vd)
     if (ns <= 1) WF3D_PF(1); else if (ns <= 2) WF3D_PF(2); else if (ns <= 4) WF3D_PF(4); else WF3D_PF(8);
 #undef WF3D_PF

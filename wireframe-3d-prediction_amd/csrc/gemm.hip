@@ -42,7 +42,7 @@ struct GemmParams {
     int M, N, K, lda, ldb, ldc, ld_addend;
     const float* pmu; const float* prs; const float* pgam; const float* pbet;
     int has_ln, has_affine;
-    uint32_t drop_seed, drop_thresh; float drop_scale;
+    wf3d_seed_t drop_seed; uint32_t drop_thresh; float drop_scale;
     int accumulate;
     int ksplit, kt_per_split;
     float* slab;
@@ -98,11 +98,11 @@ __device__ __forceinline__ void load_tile(const float* __restrict__ base, int ld
 // ---- prologue: v' = drop(act(LN-affine(v))) on in-bounds elements, 0 elsewhere
 template <int ACT>
 __device__ __forceinline__ float pro_one(float v, float mu, float rs, float g, float b, const GemmParams& p,
-                                         uint32_t grow, uint32_t gcol, bool inb) {
+                                         uint32_t seed, uint32_t grow, uint32_t gcol, bool inb) {
     float y = p.has_ln ? (v - mu) * rs : v;
     if (p.has_affine) y = y * g + b;
     y = wf3d_act<ACT>(y);
-    if (p.drop_thresh) y = wf3d_keep(p.drop_seed, grow, gcol, p.drop_thresh) ? y * p.drop_scale : 0.f;
+    if (p.drop_thresh) y = wf3d_keep(seed, grow, gcol, p.drop_thresh) ? y * p.drop_scale : 0.f;
     return inb ? y : 0.f;
 }
 
@@ -215,7 +215,7 @@ __device__ __forceinline__ void static_steps(F&& f) {
 }
 
 template <int WAVES_M, int WAVES_N, int TM, int TN, bool A_KC, bool B_KC, int ACT, bool PRO, bool FAST, bool SPLIT, bool X3, int R, int NP>
-__device__ __forceinline__ void gemm_body(const GemmParams& p, float* smem, int m0, int n0, int kt0, int kt1) {
+__device__ __forceinline__ void gemm_body(const GemmParams& p, uint32_t seed, float* smem, int m0, int n0, int kt0, int kt1) {
     constexpr int BM = WAVES_M * TM * 32, BN = WAVES_N * TN * 32;
     constexpr int A_SZ = (A_KC || X3) ? BM * LDK : BK * BM;
     constexpr int B_SZ = (B_KC || X3) ? BN * LDK : BK * BN;
@@ -309,7 +309,7 @@ __device__ __forceinline__ void gemm_body(const GemmParams& p, float* smem, int 
                 const int grow = m0 + (tid >> 3) + 32 * i;
 #pragma unroll
                 for (int j = 0; j < 4; ++j)
-                    r.ra[i][j] = pro_one<ACT>(r.ra[i][j], mu_a[i], rs_a[i], r.pg[j], r.pbv[j], p, grow, k + j,
+                    r.ra[i][j] = pro_one<ACT>(r.ra[i][j], mu_a[i], rs_a[i], r.pg[j], r.pbv[j], p, seed, grow, k + j,
                                               FAST || (grow < p.M && k + j < p.K));
             }
         }
@@ -320,7 +320,7 @@ __device__ __forceinline__ void gemm_body(const GemmParams& p, float* smem, int 
                 const int k = kt * BK + tid / TPRB + KPPB * i;
 #pragma unroll
                 for (int j = 0; j < 4; ++j)
-                    r.rb[i][j] = pro_one<ACT>(r.rb[i][j], r.mu_b[i], r.rs_b[i], gam_b[j], bet_b[j], p, k, gcol + j,
+                    r.rb[i][j] = pro_one<ACT>(r.rb[i][j], r.mu_b[i], r.rs_b[i], gam_b[j], bet_b[j], p, seed, k, gcol + j,
                                               FAST || (k < p.K && gcol + j < p.N));
             }
         }
@@ -512,8 +512,9 @@ __global__ __launch_bounds__(256, 2) void gemm_kernel(const GemmParams p) {
     // FAST: every staged tile of this workgroup lies fully inside A and B and is
     // 16-B loadable -> branch-free staging (block-uniform choice)
     const bool fast = p.vecA && p.vecB && p.vecP && (m0 + BM <= p.M) && (n0 + BN <= p.N) && (kt1 * BK <= p.K);
-    if (fast) gemm_body<WAVES_M, WAVES_N, TM, TN, A_KC, B_KC, ACT, PRO, true, SPLIT, X3, R, NP>(p, smem, m0, n0, kt0, kt1);
-    else      gemm_body<WAVES_M, WAVES_N, TM, TN, A_KC, B_KC, ACT, PRO, false, SPLIT, X3, R, NP>(p, smem, m0, n0, kt0, kt1);
+    const uint32_t seed = PRO && p.drop_thresh ? wf3d_seed_load(p.drop_seed) : 0u;
+    if (fast) gemm_body<WAVES_M, WAVES_N, TM, TN, A_KC, B_KC, ACT, PRO, true, SPLIT, X3, R, NP>(p, seed, smem, m0, n0, kt0, kt1);
+    else      gemm_body<WAVES_M, WAVES_N, TM, TN, A_KC, B_KC, ACT, PRO, false, SPLIT, X3, R, NP>(p, seed, smem, m0, n0, kt0, kt1);
 }
 
 // split-K combine (wf3d_splitk_combine): deterministic slab sum + epilogue terms
@@ -652,7 +653,7 @@ extern "C" int wf3d_gemm(const wf3d_gemm_t* d, void* stream) {
     p.has_ln = d->pro_enable && d->pro_mu != nullptr;
     p.has_affine = d->pro_enable && d->pro_gamma != nullptr;
     if (d->pro_enable && d->drop_p > 0.f) {
-        p.drop_seed = d->drop_seed;
+        p.drop_seed = wf3d_seed_arg(d->drop_p, d->drop_seed);
         p.drop_thresh = (uint32_t)((double)d->drop_p * 4294967296.0);
         p.drop_scale = 1.0f / (1.0f - d->drop_p);
     }

@@ -10,6 +10,10 @@
 //                   Tensors with p == NULL are clip-only: the reference's lazily created point_pool_proj is in
 //                   model.parameters() (so in the norm and scaled) but not in the optimizer.
 //
+// Capturable form (wf3d_clip_adam_step_dev): the Adam step and optionally lr are read from device memory, so that one
+// captured launch sequence is right on every replay; a third launch advances the per-tensor step counters after the last
+// Adam launch (no workgroup of the step can see an advanced counter).
+//
 // HBM-bound: reads p, g, m, v and writes p, g, m, v once: 32 B per parameter (0.99 GB for the 31 M parameters).
 // Tensor tables travel as kernel arguments (<= 80 tensors per launch), so per-step gradient reallocation costs nothing.
 #include <math.h>
@@ -26,6 +30,20 @@ struct SqArgs {
     long n[OPT_MAXT];
     int blk_begin[OPT_MAXT + 1];
     int ntensors;
+};
+
+constexpr int OPT_MAXS = 256;             // step counters per advance launch (256 x 8 B + 4 B)
+
+struct StepArgs {
+    float* s[OPT_MAXS];
+    int n;
+};
+
+// the device-side scalars of the capturable form (unused by the host-step launch)
+struct AdamDev {
+    const float* step;    // the Adam step BEFORE this update (torch.optim.Adam(capturable=True) state["step"])
+    const float* lr;      // NULL: the lr argument
+    double beta1, beta2;
 };
 
 struct AdamArgs {
@@ -83,11 +101,19 @@ __global__ __launch_bounds__(256) void gradsq_kernel(const SqArgs a, float* __re
     if (threadIdx.x == 0) partials[part_off + blockIdx.x] = s;
 }
 
+template <bool DEV>
 __global__ __launch_bounds__(256) void clip_adam_kernel(const AdamArgs a, const float* __restrict__ partials, int npart,
                                                          float max_norm, float lr, float omb1, float beta2, float omb2,
                                                          float eps, float wd, float bc1, float bc2_sqrt,
-                                                         float* __restrict__ norm_out) {
+                                                         float* __restrict__ norm_out, const AdamDev dv) {
     __shared__ float s_red[4];
+    if (DEV) {
+        // as the host forms them: in double from the 1-based step, one rounding to fp32
+        const double t = (double)*dv.step + 1.0;
+        bc1 = (float)(1.0 - pow(dv.beta1, t));
+        bc2_sqrt = (float)sqrt(1.0 - pow(dv.beta2, t));
+        if (dv.lr) lr = *dv.lr;
+    }
     float s = 0.f;
     for (int i = threadIdx.x; i < npart; i += 256) s += partials[i];
     const float norm = sqrtf(block_sum(s, s_red));
@@ -139,6 +165,11 @@ __global__ __launch_bounds__(256) void clip_adam_kernel(const AdamArgs a, const 
     }
 }
 
+__global__ __launch_bounds__(256) void step_advance_kernel(const StepArgs a) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i < a.n) a.s[i][0] += 1.0f;
+}
+
 }  // namespace
 
 extern "C" size_t wf3d_clip_adam_ws_floats(const long* numel, int ntensors) {
@@ -147,19 +178,16 @@ extern "C" size_t wf3d_clip_adam_ws_floats(const long* numel, int ntensors) {
     return blocks + 1;
 }
 
-extern "C" int wf3d_clip_adam_step(float* const* params, float* const* grads, float* const* exp_avg, float* const* exp_avg_sq,
-                                   const long* numel, int ntensors, double max_norm, double lr, double beta1, double beta2,
-                                   double eps, double weight_decay, int step, float* ws, size_t ws_floats, float* total_norm,
-                                   void* stream) {
-    WF3D_CHECK(ntensors >= 0 && params && grads && exp_avg && exp_avg_sq && numel, WF3D_ERR_ARG, "wf3d_clip_adam_step: null table");
-    if (ntensors == 0) return WF3D_OK;
-    WF3D_CHECK(step >= 1 && lr >= 0. && beta1 >= 0. && beta1 < 1. && beta2 >= 0. && beta2 < 1., WF3D_ERR_ARG, "wf3d_clip_adam_step: bad hyper-parameters");
-    WF3D_CHECK(ws && ws_floats >= wf3d_clip_adam_ws_floats(numel, ntensors), WF3D_ERR_WS, "wf3d_clip_adam_step: workspace too small");
+// shared by both entry points: `dv` null for the host step (bc1 / bc2_sqrt given), else the capturable form
+static int clip_adam_launch(const char* fn, float* const* params, float* const* grads, float* const* exp_avg,
+                            float* const* exp_avg_sq, const long* numel, int ntensors, double max_norm, double lr, double beta1,
+                            double beta2, double eps, double weight_decay, float bc1, float bc2_sqrt, const AdamDev* dv,
+                            float* ws, size_t ws_floats, float* total_norm, hipStream_t st) {
+    WF3D_CHECK(ws && ws_floats >= wf3d_clip_adam_ws_floats(numel, ntensors), WF3D_ERR_WS, "%s: workspace too small", fn);
     for (int i = 0; i < ntensors; ++i) {
-        WF3D_CHECK(grads[i] && numel[i] > 0, WF3D_ERR_ARG, "wf3d_clip_adam_step: tensor %d has no gradient", i);
-        WF3D_CHECK(!params[i] || (exp_avg[i] && exp_avg_sq[i]), WF3D_ERR_ARG, "wf3d_clip_adam_step: tensor %d lacks optimizer state", i);
+        WF3D_CHECK(grads[i] && numel[i] > 0, WF3D_ERR_ARG, "%s: tensor %d has no gradient", fn, i);
+        WF3D_CHECK(!params[i] || (exp_avg[i] && exp_avg_sq[i]), WF3D_ERR_ARG, "%s: tensor %d lacks optimizer state", fn, i);
     }
-    hipStream_t st = (hipStream_t)stream;
     int npart = 0;
     for (int t0 = 0; t0 < ntensors; t0 += OPT_MAXT) {
         const int nt = ntensors - t0 < OPT_MAXT ? ntensors - t0 : OPT_MAXT;
@@ -175,10 +203,6 @@ extern "C" int wf3d_clip_adam_step(float* const* params, float* const* grads, fl
         WF3D_LAUNCH_CHECK();
         npart += blk;
     }
-    // hyper-parameters arrive as doubles (Python floats) and every derived scalar is formed in double before the one
-    // rounding to fp32, as torch does on the host: 1 - 0.999 must become 0.001f, not 1.0f - 0.999f
-    const float bc1 = (float)(1.0 - pow(beta1, (double)step));
-    const float bc2_sqrt = (float)sqrt(1.0 - pow(beta2, (double)step));
     for (int t0 = 0; t0 < ntensors; t0 += OPT_MAXT) {
         const int nt = ntensors - t0 < OPT_MAXT ? ntensors - t0 : OPT_MAXT;
         AdamArgs a;
@@ -190,8 +214,75 @@ extern "C" int wf3d_clip_adam_step(float* const* params, float* const* grads, fl
             blk += wf3d_cdiv(numel[t0 + i], OPT_CHUNK);
         }
         for (int i = nt; i <= OPT_MAXT; ++i) a.blk_begin[i] = blk;
-        hipLaunchKernelGGL(clip_adam_kernel, dim3(blk), dim3(256), 0, st, a, ws, npart, (float)max_norm, (float)lr, (float)(1.0 - beta1),
-                           (float)beta2, (float)(1.0 - beta2), (float)eps, (float)weight_decay, bc1, bc2_sqrt, t0 == 0 ? total_norm : nullptr);
+        if (dv)
+            hipLaunchKernelGGL(clip_adam_kernel<true>, dim3(blk), dim3(256), 0, st, a, ws, npart, (float)max_norm, (float)lr,
+                               (float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2), (float)eps, (float)weight_decay, 0.f,
+                               0.f, t0 == 0 ? total_norm : nullptr, *dv);
+        else
+            hipLaunchKernelGGL(clip_adam_kernel<false>, dim3(blk), dim3(256), 0, st, a, ws, npart, (float)max_norm, (float)lr,
+                               (float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2), (float)eps, (float)weight_decay, bc1,
+                               bc2_sqrt, t0 == 0 ? total_norm : nullptr, AdamDev{});
+        WF3D_LAUNCH_CHECK();
+    }
+    return WF3D_OK;
+}
+
+extern "C" int wf3d_clip_adam_step(float* const* params, float* const* grads, float* const* exp_avg, float* const* exp_avg_sq,
+                                   const long* numel, int ntensors, double max_norm, double lr, double beta1, double beta2,
+                                   double eps, double weight_decay, int step, float* ws, size_t ws_floats, float* total_norm,
+                                   void* stream) {
+    WF3D_CHECK(ntensors >= 0 && params && grads && exp_avg && exp_avg_sq && numel, WF3D_ERR_ARG, "wf3d_clip_adam_step: null table");
+    if (ntensors == 0) return WF3D_OK;
+    WF3D_CHECK(step >= 1 && lr >= 0. && beta1 >= 0. && beta1 < 1. && beta2 >= 0. && beta2 < 1., WF3D_ERR_ARG, "wf3d_clip_adam_step: bad hyper-parameters");
+    // hyper-parameters arrive as doubles (Python floats) and every derived scalar is formed in double before the one
+    // rounding to fp32, as torch does on the host: 1 - 0.999 must become 0.001f, not 1.0f - 0.999f
+    const float bc1 = (float)(1.0 - pow(beta1, (double)step));
+    const float bc2_sqrt = (float)sqrt(1.0 - pow(beta2, (double)step));
+    return clip_adam_launch("wf3d_clip_adam_step", params, grads, exp_avg, exp_avg_sq, numel, ntensors, max_norm, lr, beta1,
+                            beta2, eps, weight_decay, bc1, bc2_sqrt, nullptr, ws, ws_floats, total_norm, (hipStream_t)stream);
+}
+
+extern "C" int wf3d_clip_adam_step_dev(float* const* params, float* const* grads, float* const* exp_avg,
+                                       float* const* exp_avg_sq, float* const* steps, const long* numel, int ntensors,
+                                       double max_norm, double lr, const float* lr_dev, double beta1, double beta2, double eps,
+                                       double weight_decay, float* ws, size_t ws_floats, float* total_norm, void* stream) {
+    WF3D_CHECK(ntensors >= 0 && params && grads && exp_avg && exp_avg_sq && steps && numel, WF3D_ERR_ARG,
+               "wf3d_clip_adam_step_dev: null table");
+    if (ntensors == 0) return WF3D_OK;
+    WF3D_CHECK(lr >= 0. && beta1 >= 0. && beta1 < 1. && beta2 >= 0. && beta2 < 1., WF3D_ERR_ARG,
+               "wf3d_clip_adam_step_dev: bad hyper-parameters");
+    const float* step0 = nullptr;
+    for (int i = 0; i < ntensors; ++i) {
+        WF3D_CHECK(!params[i] || steps[i], WF3D_ERR_ARG, "wf3d_clip_adam_step_dev: tensor %d has no step counter", i);
+        if (params[i] && !step0) step0 = steps[i];
+    }
+    hipStream_t st = (hipStream_t)stream;
+    if (step0) {
+        // every optimised tensor is at the same step (the caller's rule): the first one's counter gives the bias corrections
+        const AdamDev dv{step0, lr_dev, beta1, beta2};
+        const int rc = clip_adam_launch("wf3d_clip_adam_step_dev", params, grads, exp_avg, exp_avg_sq, numel, ntensors, max_norm,
+                                        lr, beta1, beta2, eps, weight_decay, 0.f, 0.f, &dv, ws, ws_floats, total_norm, st);
+        if (rc) return rc;
+    } else {
+        // clip-only tensors: the step counter never enters
+        const int rc = clip_adam_launch("wf3d_clip_adam_step_dev", params, grads, exp_avg, exp_avg_sq, numel, ntensors, max_norm,
+                                        lr, beta1, beta2, eps, weight_decay, 1.f, 1.f, nullptr, ws, ws_floats, total_norm, st);
+        if (rc) return rc;
+    }
+    // after the last Adam launch on the same stream: no workgroup of this step reads an advanced counter
+    StepArgs a;
+    a.n = 0;
+    for (int i = 0; i < ntensors; ++i) {
+        if (!params[i]) continue;
+        a.s[a.n++] = steps[i];
+        if (a.n == OPT_MAXS) {
+            hipLaunchKernelGGL(step_advance_kernel, dim3(wf3d_cdiv(a.n, 256)), dim3(256), 0, st, a);
+            WF3D_LAUNCH_CHECK();
+            a.n = 0;
+        }
+    }
+    if (a.n) {
+        hipLaunchKernelGGL(step_advance_kernel, dim3(wf3d_cdiv(a.n, 256)), dim3(256), 0, st, a);
         WF3D_LAUNCH_CHECK();
     }
     return WF3D_OK;

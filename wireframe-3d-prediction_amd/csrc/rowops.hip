@@ -50,8 +50,9 @@ __global__ __launch_bounds__(256) void row_stats_kernel(const float* __restrict_
 __global__ __launch_bounds__(256) void ln_act_apply_kernel(const float* __restrict__ z, int R, int D,
                                                             const float* __restrict__ mu, const float* __restrict__ rs,
                                                             const float* __restrict__ gamma, const float* __restrict__ beta,
-                                                            int act, const float* __restrict__ addend, uint32_t seed,
+                                                            int act, const float* __restrict__ addend, const wf3d_seed_t seed_src,
                                                             uint32_t thresh, float scale, float* __restrict__ out) {
+    const uint32_t seed = thresh ? wf3d_seed_load(seed_src) : 0u;
     const size_t total = (size_t)R * D;
     for (size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (size_t)gridDim.x * 256) {
         const int r = (int)(idx / D), c = (int)(idx % D);
@@ -104,12 +105,13 @@ template <int NS, int WPR, int KX = 0, bool PAIR = false>
 __global__ __launch_bounds__(256) void ln_act_bwd_kernel(const float* __restrict__ dh, const float* __restrict__ z,
                                                           int R, int D, const float* __restrict__ mu,
                                                           const float* __restrict__ rs, const float* __restrict__ gamma,
-                                                          const float* __restrict__ beta, int act, uint32_t seed,
+                                                          const float* __restrict__ beta, int act, const wf3d_seed_t seed_src,
                                                           uint32_t thresh, float scale, float* __restrict__ dz,
                                                           float* __restrict__ dz_sx8, float* __restrict__ part,
                                                           const float* __restrict__ x0 = nullptr, int ldx = 0, int kx = 0,
                                                           const PairSrc ps = PairSrc{}) {
     constexpr int RPI = 4 / WPR;                       // rows per workgroup iteration
+    const uint32_t seed = thresh ? wf3d_seed_load(seed_src) : 0u;
     __shared__ float xsum[2][4][2];                    // [parity][wave][s1, s2]
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int wslice = wave % WPR, wrow = wave / WPR;
@@ -516,7 +518,7 @@ extern "C" int wf3d_ln_act_apply(const float* z, int R, int D, const float* mu, 
     int blocks = (int)((total + 255) / 256);
     if (blocks > 4096) blocks = 4096;
     hipLaunchKernelGGL(ln_act_apply_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, z, R, D, mu, rs, gamma,
-                       beta, act, addend, drop_seed, thresh, scale, out);
+                       beta, act, addend, wf3d_seed_arg(drop_p, drop_seed), thresh, scale, out);
     WF3D_LAUNCH_CHECK();
     return WF3D_OK;
 }
@@ -559,7 +561,7 @@ extern "C" int wf3d_ln_act_bwd(const float* dh, const float* z, int R, int D, co
     const int ns = wf3d_cdiv(slice_cols(D, wpr), 256);
 #define WF3D_BWD(NS_, WPR_)                                                                                       \
     hipLaunchKernelGGL((ln_act_bwd_kernel<NS_, WPR_>), dim3(nblk), dim3(256), lds, st, dh, z, R, D, mu, rs, gamma, \
-                       beta, act, drop_seed, thresh, scale, dz, (float*)dz_sx8, part)
+                       beta, act, wf3d_seed_arg(drop_p, drop_seed), thresh, scale, dz, (float*)dz_sx8, part)
     if (wpr == 4) { if (ns <= 1) WF3D_BWD(1, 4); else if (ns <= 2) WF3D_BWD(2, 4); else WF3D_BWD(4, 4); }
     else if (wpr == 2) WF3D_BWD(1, 2);
     else WF3D_BWD(1, 1);
@@ -605,7 +607,7 @@ extern "C" int wf3d_ln_act_bwd_first(const float* dh, const float* z, const floa
     const int wpr = D > 512 ? 4 : (D > 256 ? 2 : 1);
 #define WF3D_BWD1(WPR_)                                                                                                  \
     hipLaunchKernelGGL((ln_act_bwd_kernel<1, WPR_, 8>), dim3(nblk), dim3(256), lds, st, dh, z, R, D, mu, rs, gamma, beta, \
-                       act, 0u, 0u, 1.0f, (float*)nullptr, (float*)nullptr, part, x, ldx, K)
+                       act, wf3d_seed_t{0u, nullptr}, 0u, 1.0f, (float*)nullptr, (float*)nullptr, part, x, ldx, K)
     // (one wave per 512-wide row with two slots, <2, 1, 8>: 184 VGPRs, 187 us against 173)
     if (wpr == 4) WF3D_BWD1(4); else if (wpr == 2) WF3D_BWD1(2); else WF3D_BWD1(1);
 #undef WF3D_BWD1
@@ -647,7 +649,7 @@ extern "C" int wf3d_ln_act_bwd_wsum(const float* dh, const float* z, const float
     const int ns = wf3d_cdiv(slice_cols(D, wpr), 256);
 #define WF3D_BWDW(NS_, WPR_)                                                                                             \
     hipLaunchKernelGGL((ln_act_bwd_kernel<NS_, WPR_, 1>), dim3(nblk), dim3(256), lds, st, dh, z, R, D, mu, rs, gamma, beta, \
-                       act, drop_seed, thresh, scale, dz, (float*)dz_sx8, part, wrow, 1, 1)
+                       act, wf3d_seed_arg(drop_p, drop_seed), thresh, scale, dz, (float*)dz_sx8, part, wrow, 1, 1)
     if (wpr == 4) { if (ns <= 1) WF3D_BWDW(1, 4); else if (ns <= 2) WF3D_BWDW(2, 4); else WF3D_BWDW(4, 4); }
     else if (wpr == 2) WF3D_BWDW(1, 2);
     else WF3D_BWDW(1, 1);
@@ -684,7 +686,7 @@ extern "C" int wf3d_edge_pair_ln_bwd(const float* dh, const float* Pa, const flo
     const int wpr = H > 512 ? 4 : (H > 256 ? 2 : 1);
 #define WF3D_BWDP(NS_, WPR_)                                                                                                \
     hipLaunchKernelGGL((ln_act_bwd_kernel<NS_, WPR_, 1, true>), dim3(nblk), dim3(256), lds, st, dh, nullptr, Re, H, mu, rs, gamma, \
-                       beta, act, drop_seed, thresh, scale, dz, nullptr, part, delta, 1, 1, ps)
+                       beta, act, wf3d_seed_arg(drop_p, drop_seed), thresh, scale, dz, nullptr, part, delta, 1, 1, ps)
     if (wpr == 4) WF3D_BWDP(1, 4); else if (wpr == 2) WF3D_BWDP(1, 2); else WF3D_BWDP(1, 1);
 #undef WF3D_BWDP
     WF3D_LAUNCH_CHECK();

@@ -117,9 +117,10 @@ __device__ __forceinline__ float row_sum(float v) {
 template <int NS, int LPR = 64, bool FULL = false>
 __global__ __launch_bounds__(256) void ln_prep_kernel(const float* __restrict__ z, int R, int D,
                                                        const float* __restrict__ gamma, const float* __restrict__ beta,
-                                                       int act, float eps, uint32_t seed, uint32_t thresh, float dscale,
+                                                       int act, float eps, const wf3d_seed_t seed_src, uint32_t thresh, float dscale,
                                                        float* __restrict__ mu, float* __restrict__ rs,
                                                        float* __restrict__ h_sx8) {
+    const uint32_t seed = thresh ? wf3d_seed_load(seed_src) : 0u;
     // persistent: a lane group walks rows first, first + step, ... with its slice of gamma / beta in registers and
     // the next row's z already requested while this row is reduced, normalised and stored.
     // Columns of a lane: two chunks of four per slot, CH columns apart — lane l owns [s*SPAN + 4l, +4) and
@@ -323,8 +324,9 @@ __global__ __launch_bounds__(256) void split_transpose_kernel(const float* __res
                                                                const float* __restrict__ mu, const float* __restrict__ rs,
                                                                const float* __restrict__ gamma,
                                                                const float* __restrict__ beta, int act,
-                                                               uint32_t seed, uint32_t thresh, float dscale,
+                                                               const wf3d_seed_t seed_src, uint32_t thresh, float dscale,
                                                                int in_sx8, float* __restrict__ out) {
+    const uint32_t seed = thresh ? wf3d_seed_load(seed_src) : 0u;
     __shared__ float tile[64][65];
     const int r0 = blockIdx.y * 64, c0 = blockIdx.x * 64;
     const int t = threadIdx.x;
@@ -440,6 +442,7 @@ extern "C" int wf3d_ln_prep(const float* z, int R, int D, const float* gamma, co
                ((uintptr_t)beta % 16 == 0), WF3D_ERR_ARG, "wf3d_ln_prep: pointers must be 16-byte aligned");
     const int ns = wf3d_cdiv(D, 512);
     hipStream_t st = (hipStream_t)stream;
+    const wf3d_seed_t seed = wf3d_seed_arg(drop_p, drop_seed);
     // persistent grid: a few workgroups per CU
     const int rpb = D <= 256 ? 8 : 4;
     int blocks = wf3d_cdiv(R, rpb);
@@ -447,13 +450,13 @@ extern "C" int wf3d_ln_prep(const float* z, int R, int D, const float* gamma, co
 #define WF3D_LP(NS_)                                                                                              \
     if (D == NS_ * 512)                                                                                           \
         hipLaunchKernelGGL((ln_prep_kernel<NS_, 64, true>), dim3(blocks), dim3(256), 0, st, z, R, D, gamma, beta, act, eps, \
-                           drop_seed, thresh, dscale, mu, rs, (float*)h_sx8);                                      \
+                           seed, thresh, dscale, mu, rs, (float*)h_sx8);                                      \
     else                                                                                                          \
         hipLaunchKernelGGL((ln_prep_kernel<NS_>), dim3(blocks), dim3(256), 0, st, z, R, D, gamma, beta, act, eps, \
-                           drop_seed, thresh, dscale, mu, rs, (float*)h_sx8)
+                           seed, thresh, dscale, mu, rs, (float*)h_sx8)
     if (D <= 256)      // two rows per wave
         hipLaunchKernelGGL((ln_prep_kernel<1, 32>), dim3(blocks), dim3(256), 0, st, z, R, D, gamma, beta, act, eps,
-                           drop_seed, thresh, dscale, mu, rs, (float*)h_sx8);
+                           seed, thresh, dscale, mu, rs, (float*)h_sx8);
     else if (ns <= 1) { WF3D_LP(1); } else if (ns <= 2) { WF3D_LP(2); } else if (ns <= 4) { WF3D_LP(4); } else { WF3D_LP(8); }
 #undef WF3D_LP
     WF3D_LAUNCH_CHECK();
@@ -508,7 +511,7 @@ extern "C" int wf3d_split_transpose(const float* in, int R, int C, int ld, const
     WF3D_CHECK(act >= 0 && act <= 2, WF3D_ERR_ARG, "wf3d_split_transpose: bad act");
     WF3D_CHECK(wf3d_cdiv(R, 64) <= 65535, WF3D_ERR_UNSUPPORTED, "wf3d_split_transpose: too many rows");
     hipLaunchKernelGGL(split_transpose_kernel, dim3(wf3d_cdiv(C, 64), wf3d_cdiv(R, 64)), dim3(256), 0,
-                       (hipStream_t)stream, in, R, C, ld, mu, rs, gamma, beta, act, drop_seed, thresh, dscale, in_sx8,
+                       (hipStream_t)stream, in, R, C, ld, mu, rs, gamma, beta, act, wf3d_seed_arg(drop_p, drop_seed), thresh, dscale, in_sx8,
                        (float*)out_sx8);
     WF3D_LAUNCH_CHECK();
     return WF3D_OK;

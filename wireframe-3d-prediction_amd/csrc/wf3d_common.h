@@ -36,6 +36,14 @@ WF3D_INTERNAL void wf3d_set_error(const char* fmt, ...);
 
 static inline int wf3d_cdiv(long a, long b) { return (int)((a + b - 1) / b); }
 
+// ---- dropout seed source (host + device) -------------------------------------
+// Every mask kernel takes its seed as a wf3d_seed_t: the value itself (words == NULL), or, while the calling thread has
+// set device seed words (wf3d_set_dropout_seed_words), an index into those words that the kernel loads at run time.
+// The pointer is a kernel argument, so a captured graph replays with whatever words a draw kernel wrote before it.
+struct wf3d_seed_t { uint32_t v; const uint32_t* words; };
+// the seed argument of a launch that drops with probability drop_p (no words are read when nothing is dropped)
+WF3D_INTERNAL wf3d_seed_t wf3d_seed_arg(float drop_p, uint32_t drop_seed);
+
 // ---- split-K (host) --------------------------------------------------------
 // A GEMM whose output has too few tiles to fill the chip cuts its reduction into `ksplit` ranges of `kt_per` K slices;
 // each range writes a slab of M x N partial sums into the caller's workspace and wf3d_splitk_combine folds them.  One
@@ -176,6 +184,9 @@ __device__ __forceinline__ bool wf3d_keep(uint32_t seed, uint32_t row, uint32_t 
     h ^= h >> 16; h *= 0x7FEB352Du; h ^= h >> 15; h *= 0x846CA68Bu; h ^= h >> 16;
     return h >= thresh;
 }
+
+// The seed a mask kernel uses: read once at kernel entry (a wave-uniform load from the caller's device words).
+__device__ __forceinline__ uint32_t wf3d_seed_load(const wf3d_seed_t& s) { return s.words ? s.words[s.v] : s.v; }
 
 // edge rows of one sample: all pairs i < j of its v vertices in lexicographic order (EdgePredictor.py:83-86);
 // edge index e -> (i, j), and the index of pair (i, i + 1)

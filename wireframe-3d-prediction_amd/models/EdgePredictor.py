@@ -11,6 +11,7 @@ import torch.nn as nn
 
 from wf3d import config
 from wf3d.functional import EdgeFn, edge_index_lists
+from wf3d.random import default_generator
 
 
 class EdgePredictor(nn.Module):
@@ -35,6 +36,7 @@ class EdgePredictor(nn.Module):
             nn.Linear(h // 2, h // 4), nn.GELU(),
             nn.Linear(h // 4, 1))
         self._heads = num_heads
+        self.last_dropout_seeds = None      # dropout_rng "device": the int32 [5] seed words of the last train-mode forward
 
     def _get_edge_indices(self, num_vertices):
         """[E, 2] int64, all i<j in lexicographic order (reference :70-89)."""
@@ -73,7 +75,13 @@ class EdgePredictor(nn.Module):
             # the reference indexes a 1-D empty index tensor here (EdgePredictor.py:118)
             raise IndexError("too many indices for tensor of dimension 1")
         ps = self._dropout_ps()
-        seed = int(torch.empty((), dtype=torch.int64).random_().item()) if any(ps) else 0
+        if not any(ps):
+            seed = 0
+        elif config.dropout_rng() == "device":
+            # seed words drawn on the device (wf3d.random): no host read, fresh on every replay of a captured step
+            seed = self.last_dropout_seeds = default_generator(vertices.device).draw()
+        else:
+            seed = int(torch.empty((), dtype=torch.int64).random_().item())
         return EdgeFn.apply(vertices.float(), tuple(counts), self._heads, ps, seed, config.precision(),
                             *self._param_list())
 

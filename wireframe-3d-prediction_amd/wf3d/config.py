@@ -11,6 +11,14 @@ precision
              Everything else stays as in "bf16x3".  Narrower than fp32: its error is measured and gated
              (tests/test_precision_bf16_gpu.py).
 Environment override: WF3D_PRECISION.
+
+dropout_rng
+    "host" (default): each train-mode edge-head forward draws its dropout seed from torch's CPU generator and hands it
+             to the mask kernels by value.  A captured graph replays that one seed: the same masks on every replay.
+    "device": the seed words are drawn on the device (wf3d.random: one draw kernel per forward, state in device
+             memory) and the mask kernels load them at run time, so every replay of a captured training step draws
+             fresh masks.
+Environment override: WF3D_DROPOUT_RNG.
 """
 import os
 
@@ -19,6 +27,23 @@ PRECISIONS = ("fp32", "bf16x3", "bf16")
 _precision = os.environ.get("WF3D_PRECISION", "bf16x3")
 if _precision not in PRECISIONS:
     raise RuntimeError(f"WF3D_PRECISION={_precision!r}: expected 'fp32', 'bf16x3' or 'bf16'")
+
+
+DROPOUT_RNGS = ("host", "device")
+_dropout_rng = os.environ.get("WF3D_DROPOUT_RNG", "host")
+if _dropout_rng not in DROPOUT_RNGS:
+    raise RuntimeError(f"WF3D_DROPOUT_RNG={_dropout_rng!r}: expected 'host' or 'device'")
+
+
+def dropout_rng():
+    return _dropout_rng
+
+
+def set_dropout_rng(src):
+    global _dropout_rng
+    if src not in DROPOUT_RNGS:
+        raise ValueError("dropout_rng must be 'host' or 'device'")
+    _dropout_rng = src
 
 
 def precision():

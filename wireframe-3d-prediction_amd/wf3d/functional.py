@@ -22,6 +22,7 @@ import torch
 from . import config, ops
 from . import skinny as sk
 from .ops import ACT_GELU, ACT_NONE, ACT_RELU, NN, NT, TN, Pro
+from .random import seed_words
 
 
 def _saved(ctx):
@@ -510,16 +511,27 @@ class EdgeFn(torch.autograd.Function):
 
     params = [P0w,P0b, P1g,P1b, P3w,P3b, P4g,P4b, Aw,Ab, Ow,Ob,
               M0w,M0b, M1g,M1b, M4w,M4b, M5g,M5b, M8w,M8b, M10w,M10b]
-    (vertex_proj.{0,1,3,4}, attention.{in_proj,out_proj}, edge_mlp.{0,1,4,5,8,10})"""
+    (vertex_proj.{0,1,3,4}, attention.{in_proj,out_proj}, edge_mlp.{0,1,4,5,8,10})
+
+    `seed` is the host-drawn seed (an int), or the device seed words of wf3d.random (an int32 tensor, dropout_rng
+    "device"): then the four site seeds are indices 1..4 into those words, which every mask kernel of the forward and
+    of the backward loads at run time."""
 
     @staticmethod
     def forward(ctx, verts, counts, heads, drop_ps, seed, precision, *params):
+        words = seed if torch.is_tensor(seed) else None
+        ctx.words = words
+        with seed_words(words):
+            return EdgeFn._forward(ctx, verts, counts, heads, drop_ps, seed, precision, *params)
+
+    @staticmethod
+    def _forward(ctx, verts, counts, heads, drop_ps, seed, precision, *params):
         (P0w, P0b, P1g, P1b, P3w, P3b, P4g, P4b, Aw, Ab, Ow, Ob,
          M0w, M0b, M1g, M1b, M4w, M4b, M5g, M5b, M8w, M8b, M10w, M10b) = params
         B, V, _ = verts.shape
         H = P3w.shape[0]
         meta = ops.EdgeMeta.get(counts, verts.device)
-        sd = [(seed + 0x9E3779B9 * k) & 0xFFFFFFFF for k in range(1, 5)]
+        sd = [1, 2, 3, 4] if ctx.words is not None else [(seed + 0x9E3779B9 * k) & 0xFFFFFFFF for k in range(1, 5)]
         pf_, pa_, p1_, p2_ = (float(x) for x in drop_ps)   # vertex_proj.5, attention, edge_mlp.3, edge_mlp.7
         cv = ops.edge_gather_verts(verts, meta)
         za = ops.gemm(cv, P0w, NT, bias=P0b); sa = ops.row_stats(za)
@@ -577,6 +589,12 @@ class EdgeFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dprobs):
+        # autograd's own thread: the seed source is set again here (the _Leaves side stream runs inside it)
+        with seed_words(ctx.words):
+            return EdgeFn._backward(ctx, dprobs)
+
+    @staticmethod
+    def _backward(ctx, dprobs):
         params = _params(ctx)
         (P0w, P0b, P1g, P1b, P3w, P3b, P4g, P4b, Aw, Ab, Ow, Ob,
          M0w, M0b, M1g, M1b, M4w, M4b, M5g, M5b, M8w, M8b, M10w, M10b) = params
