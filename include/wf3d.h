@@ -341,7 +341,18 @@ int wf3d_vertex_finalize_bwd(const float* exist, const float* dexist, const floa
  * batch-1 loop: sample s owns vertex rows voff[s]..voff[s+1]-1 (its first
  * counts[s] predicted vertices) and edge rows eoff[s]..eoff[s+1]-1 (all pairs
  * i<j in lexicographic order); vsample/esample map a row back to its sample.
+ *
+ * PADDED layouts (wf3d_edge_layout) are built on the device, so that nothing reads a count on the host: every launch
+ * covers the worst case Rv = B*V vertex rows and Re = B*V(V-1)/2 edge rows, and the rows past voff[B] / eoff[B] (the
+ * tail) have vsample / esample = -1.  The edge-head kernels below write zeros for a tail row; the attention kernels
+ * write only the rows of real samples, so the caller zero-fills ctx / lse / dqkv of a padded layout.
  * ------------------------------------------------------------------------ */
+/* counts int64 [B] (device) -> voff / eoff int32 [B+1], vsample int32 [B*V], esample int32 [B*V(V-1)/2] (-1 past the
+ * live totals), counts_out int64 [B] = the counts clamped like Python's `[:count]` slicing of V rows (min(c, V) for
+ * c >= 0, max(V + c, 0) below) and *width (int64) = max_s c_s(c_s-1)/2.  One launch, plain stores; B <= 4096 and
+ * B*V(V-1)/2 must fit in int32. */
+int wf3d_edge_layout(const int64_t* counts, int B, int V, int32_t* voff, int32_t* eoff, int32_t* vsample,
+                     int32_t* esample, int64_t* counts_out, int64_t* width, void* stream);
 /* vd = coordinates per vertex, EdgePredictor(vertex_dim=...), 1..8 (the model uses 3: EdgePredictor.py:19,
  * PointCloudToWireframe.py:38).
  * cv[r,0:vd] = verts[s, r-voff[s], 0:vd]; strides in floats (vertices is a view of [B,V,4]) */
@@ -424,6 +435,15 @@ int wf3d_loss_terms_assigned(const float* verts, long sample_stride, long vertex
                              const float* tlabel, int Et, const int32_t* col4row, const int64_t* counts, int B, int V,
                              float w_vertex, float w_exist, float w_edge, float* dverts, float* dexist, float* dedge,
                              float* losses, void* ws, size_t ws_bytes, void* stream);
+/* Same, with the prediction's edge width read from the device (*edge_width, int64: a padded edge head's
+ * max_s E_s): the edge term runs over min(*edge_width, Ep, Et) columns, normalised by B x that width, and dedge is 0
+ * in the columns past it. */
+int wf3d_loss_terms_assigned_ew(const float* verts, long sample_stride, long vertex_stride, const float* exist,
+                                const float* edge, int Ep, const float* tverts, int Vt, const float* texist,
+                                const float* tlabel, int Et, const int64_t* edge_width, const int32_t* col4row,
+                                const int64_t* counts, int B, int V, float w_vertex, float w_exist, float w_edge,
+                                float* dverts, float* dexist, float* dedge, float* losses, void* ws, size_t ws_bytes,
+                                void* stream);
 int wf3d_loss_terms(const float* verts, long sample_stride, long vertex_stride, const float* exist,
                     const float* edge, int Ep, const float* tverts, int Vt, const float* texist,
                     const float* tlabel, int Et, const int32_t* m_pred, const int32_t* m_tgt, const int32_t* m_off,

@@ -11,9 +11,65 @@
 // Rows are COMPACT over the batch: sample s owns vertex rows voff[s]..voff[s+1]-1
 // and edge rows eoff[s]..eoff[s+1]-1 (its V_s(V_s-1)/2 pairs in the reference's
 // lexicographic i<j order, EdgePredictor.py:83-86).
+//
+// A layout built on the device (wf3d_edge_layout) is PADDED: launches cover the worst case B*V vertex rows and
+// B*V(V-1)/2 edge rows, and the rows past voff[B] / eoff[B] (the tail) have vsample / esample = -1.  Every kernel here
+// writes zeros for a tail row, so that the tail is finite in forward and exactly zero in every gradient.
 #include "wf3d_common.h"
 
 namespace {
+
+constexpr int LAYOUT_MAXB = 4096;      // samples of a device layout: two [B + 1] int tables in LDS
+
+// ---- device layout: clamped counts -> offsets, row -> sample maps, edge width ---------------------------------
+// Every workgroup rebuilds the (small) offset tables in LDS from the counts and fills its grid-stride share of the two
+// row maps by binary search; workgroup 0 also writes the tables, the clamped counts and the width.
+__global__ __launch_bounds__(256) void edge_layout_kernel(const int64_t* __restrict__ counts, int B, int V,
+                                                           int32_t* __restrict__ voff, int32_t* __restrict__ eoff,
+                                                           int32_t* __restrict__ vsample, int32_t* __restrict__ esample,
+                                                           int64_t* __restrict__ counts_out, int64_t* __restrict__ width) {
+    __shared__ int vo[LAYOUT_MAXB + 1], eo[LAYOUT_MAXB + 1];
+    __shared__ int wmax;
+    for (int s = threadIdx.x; s < B; s += 256) {
+        const long c = counts[s];
+        const long k = c >= 0 ? min(c, (long)V) : max((long)V + c, 0L);       // what `[:count]` slicing keeps
+        vo[s + 1] = (int)k;
+        eo[s + 1] = (int)(k * (k - 1) / 2);
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int w = 0;
+        vo[0] = eo[0] = 0;
+        for (int s = 0; s < B; ++s) {
+            w = max(w, eo[s + 1]);
+            vo[s + 1] += vo[s];
+            eo[s + 1] += eo[s];
+        }
+        wmax = w;
+    }
+    __syncthreads();
+    if (blockIdx.x == 0) {
+        for (int s = threadIdx.x; s <= B; s += 256) {
+            voff[s] = vo[s];
+            eoff[s] = eo[s];
+            if (s < B) counts_out[s] = vo[s + 1] - vo[s];
+        }
+        if (threadIdx.x == 0) *width = wmax;
+    }
+    const int Rv = B * V, Re = B * (V * (V - 1) / 2), nv = vo[B], ne = eo[B];
+    // sample of row r: the s with off[s] <= r < off[s + 1] (samples without rows are skipped, as repeat_interleave does)
+    auto owner = [&](const int* off, int r) {
+        int lo = 0, hi = B;
+        while (hi - lo > 1) {
+            const int mid = (lo + hi) >> 1;
+            if (off[mid] <= r) lo = mid; else hi = mid;
+        }
+        return lo;
+    };
+    const int stride = gridDim.x * 256;
+    for (int r = blockIdx.x * 256 + threadIdx.x; r < Rv; r += stride) vsample[r] = r < nv ? owner(vo, r) : -1;
+    for (int r = blockIdx.x * 256 + threadIdx.x; r < Re; r += stride) esample[r] = r < ne ? owner(eo, r) : -1;
+}
 
 // ---- vertex rows: gather counts[s] leading vertices of each sample ------------
 __global__ __launch_bounds__(256) void gather_verts_kernel(const float* __restrict__ verts, long s_stride, long v_stride,
@@ -24,7 +80,7 @@ __global__ __launch_bounds__(256) void gather_verts_kernel(const float* __restri
     if (idx >= Rv * vd) return;
     const int r = idx / vd, k = idx % vd;
     const int s = vsample[r];
-    cv[idx] = verts[(long)s * s_stride + (long)(r - voff[s]) * v_stride + k];
+    cv[idx] = s < 0 ? 0.f : verts[(long)s * s_stride + (long)(r - voff[s]) * v_stride + k];
 }
 
 __global__ __launch_bounds__(256) void scatter_dverts_kernel(const float* __restrict__ dcv, const int32_t* __restrict__ voff,
@@ -70,13 +126,31 @@ __global__ __launch_bounds__(256) void pair_fwd_kernel(const float* __restrict__
             if (h_sx8) { g4[t] = *reinterpret_cast<const f32x4*>(gamma + c); b4[t] = *reinterpret_cast<const f32x4*>(beta + c); }
         }
     }
-    int s = esample[e0], vbase = voff[s], v = voff[s + 1] - vbase, eend = eoff[s + 1];
+    // rows ea..e1-1 of a padded layout's tail (contiguous, so the rest of this wave's rows): zeros, h included
+    auto zero_tail = [&](int ea) {
+        for (int e = ea; e < e1; ++e) {
+#pragma unroll
+            for (int t = 0; t < NS; ++t) {
+                const int c = lane * 4 + 256 * t;
+                if (c < H) {
+                    if (pre) *reinterpret_cast<f32x4*>(pre + (size_t)e * H + c) = (f32x4){0.f, 0.f, 0.f, 0.f};
+                    if (h_sx8) *reinterpret_cast<f32x4*>(h_sx8 + (size_t)e * H + c) = (f32x4){0.f, 0.f, 0.f, 0.f};
+                }
+            }
+            if (lane == 0) { mu[e] = 0.f; rs[e] = 0.f; delta[e] = 0.f; }
+        }
+    };
+    int s = esample[e0];
+    if (s < 0) { zero_tail(e0); return; }
+    int vbase = voff[s], v = voff[s + 1] - vbase, eend = eoff[s + 1];
     int i, j;
     edge_ij(e0 - eoff[s], v, i, j);
     int pa_row = -1;
     for (int e = e0; e < e1; ++e) {
         if (e == eend) {                       // first edge of the next sample that has edges
-            s = esample[e]; vbase = voff[s]; v = voff[s + 1] - vbase; eend = eoff[s + 1];
+            s = esample[e];
+            if (s < 0) { zero_tail(e); return; }
+            vbase = voff[s]; v = voff[s + 1] - vbase; eend = eoff[s + 1];
             i = 0; j = 1;
         }
         const int ri = vbase + i, rj = vbase + j;
@@ -168,6 +242,11 @@ __global__ __launch_bounds__(256) void pair_bwd_kernel(const float* __restrict__
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int r = blockIdx.x;
     const int s = vsample[r];
+    if (s < 0) {                                   // padded layout's tail row (uniform over the workgroup)
+        for (int c = threadIdx.x; c < H; c += 256) { dPa[(size_t)r * H + c] = 0.f; dPb[(size_t)r * H + c] = 0.f; }
+        if ((int)threadIdx.x < vd) dcv[r * vd + threadIdx.x] = 0.f;
+        return;
+    }
     const int v0 = voff[s], nv = voff[s + 1] - v0, me = r - v0;
     const int e0 = eoff[s];
     f32x4 wv[NS], aa[NS], ab[NS];
@@ -275,6 +354,7 @@ __global__ __launch_bounds__(256) void edge_prob_bwd_kernel(const float* __restr
     const int e = blockIdx.x * 256 + threadIdx.x;
     if (e >= Re) return;
     const int s = esample[e];
+    if (s < 0) { dlogit[e] = 0.f; return; }
     const size_t o = (size_t)s * max_e + (e - eoff[s]);
     const float p = probs[o];
     dlogit[e] = dprobs[o] * p * (1.0f - p);
@@ -309,6 +389,23 @@ __global__ __launch_bounds__(256) void vertex_finalize_bwd_kernel(const float* _
 }
 
 }  // namespace
+
+extern "C" int wf3d_edge_layout(const int64_t* counts, int B, int V, int32_t* voff, int32_t* eoff, int32_t* vsample,
+                                int32_t* esample, int64_t* counts_out, int64_t* width, void* stream) {
+    WF3D_CHECK(B >= 1 && V >= 0, WF3D_ERR_ARG, "wf3d_edge_layout: bad dims B=%d V=%d", B, V);
+    WF3D_CHECK(B <= LAYOUT_MAXB, WF3D_ERR_UNSUPPORTED, "wf3d_edge_layout: more than %d samples", LAYOUT_MAXB);
+    const long re = (long)B * ((long)V * (V - 1) / 2);
+    WF3D_CHECK(re <= INT32_MAX && (long)B * V <= INT32_MAX, WF3D_ERR_UNSUPPORTED,
+               "wf3d_edge_layout: B*V(V-1)/2 = %ld edge rows do not fit in int32", re);
+    WF3D_CHECK(counts && voff && eoff && counts_out && width && (V == 0 || vsample) && (re == 0 || esample), WF3D_ERR_ARG,
+               "wf3d_edge_layout: null pointer");
+    const long rows = re > (long)B * V ? re : (long)B * V;
+    const int blocks = wf3d_cdiv(rows, 256), grid = blocks < 1 ? 1 : (blocks > 1024 ? 1024 : blocks);
+    hipLaunchKernelGGL(edge_layout_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, counts, B, V, voff, eoff, vsample,
+                       esample, counts_out, width);
+    WF3D_LAUNCH_CHECK();
+    return WF3D_OK;
+}
 
 extern "C" int wf3d_edge_gather_verts(const float* verts, long sample_stride, long vertex_stride, const int32_t* voff,
                                       const int32_t* vsample, int Rv, int vd, float* cv, void* stream) {

@@ -10,6 +10,14 @@
 
 namespace {
 
+// the edge term's common width min(prediction width, Ep, Et) when the prediction width is a device scalar
+// (a padded edge head's edge_width; its predictions tensor is Ep >= width wide)
+__device__ __forceinline__ int edge_common_width(int64_t w, int Ep, int Et) {
+    int64_t m = w < (int64_t)Ep ? w : (int64_t)Ep;
+    if ((int64_t)Et < m) m = Et;
+    return m > 0 ? (int)m : 0;
+}
+
 // cost[b,p,t] = sum_k |v[b,p,k] - tv[b,t,k]| + |e[b,p] - 1|   for t < count[b]   (real targets)
 //             = e[b,p]                                         for t >= count[b]  (dummy columns)
 __global__ __launch_bounds__(256) void loss_cost_kernel(const float* __restrict__ verts, long vs_b, long vs_v,
@@ -285,9 +293,14 @@ __global__ __launch_bounds__(256) void loss_terms_dev_kernel(const float* __rest
                                                               const int64_t* __restrict__ counts, int V, int B,
                                                               float wv, float ge, float gd,
                                                               float* __restrict__ dverts, float* __restrict__ dexist,
-                                                              float* __restrict__ dedge, float* __restrict__ part) {
+                                                              float* __restrict__ dedge, float* __restrict__ part,
+                                                              const int64_t* __restrict__ ewidth = nullptr, float we = 0.f) {
     __shared__ float red[4];
     const int b = blockIdx.x, tid = threadIdx.x;
+    if (ewidth) {               // prediction width from the device: min_e and the edge gradient scale formed here
+        min_e = edge_common_width(*ewidth, Ep, Et);
+        gd = min_e ? we / ((float)B * min_e) : 0.f;
+    }
     long nm = 0;
     for (int s = 0; s < B; ++s) nm += min((long)counts[s], (long)V);        // total matches = sum of real targets
     const float gv = nm > 0 ? wv / (3.0f * (float)nm) : 0.f;
@@ -326,7 +339,9 @@ __global__ __launch_bounds__(256) void loss_terms_dev_kernel(const float* __rest
 }
 
 __global__ void loss_final_dev_kernel(const float* __restrict__ part, const int64_t* __restrict__ counts, int B, int V,
-                                      float ne, float nd, float wv, float we, float wd, float* __restrict__ out) {
+                                      float ne, float nd, float wv, float we, float wd, float* __restrict__ out,
+                                      const int64_t* __restrict__ ewidth = nullptr, int Ep = 0, int Et = 0) {
+    if (ewidth) nd = (float)B * edge_common_width(*ewidth, Ep, Et);
     float sv = 0.f, se = 0.f, sd = 0.f;
     long nm = 0;
     for (int b = 0; b < B; ++b) { sv += part[b * 3]; se += part[b * 3 + 1]; sd += part[b * 3 + 2]; nm += min((long)counts[b], (long)V); }
@@ -409,6 +424,30 @@ extern "C" int wf3d_loss_terms_assigned(const float* verts, long sample_stride, 
     WF3D_LAUNCH_CHECK();
     hipLaunchKernelGGL(loss_final_dev_kernel, dim3(1), dim3(1), 0, st, (const float*)ws, counts, B, V, ne, nd, w_vertex,
                        w_exist, w_edge, losses);
+    WF3D_LAUNCH_CHECK();
+    return WF3D_OK;
+}
+
+extern "C" int wf3d_loss_terms_assigned_ew(const float* verts, long sample_stride, long vertex_stride, const float* exist,
+                                           const float* edge, int Ep, const float* tverts, int Vt, const float* texist,
+                                           const float* tlabel, int Et, const int64_t* edge_width, const int32_t* col4row,
+                                           const int64_t* counts, int B, int V, float w_vertex, float w_exist, float w_edge,
+                                           float* dverts, float* dexist, float* dedge, float* losses, void* ws,
+                                           size_t ws_bytes, void* stream) {
+    WF3D_CHECK(B > 0 && V > 0 && Ep >= 0 && Et >= 0, WF3D_ERR_ARG, "wf3d_loss_terms_assigned_ew: bad dims");
+    WF3D_CHECK(verts && exist && tverts && texist && col4row && counts && edge_width && dverts && dexist && losses, WF3D_ERR_ARG,
+               "wf3d_loss_terms_assigned_ew: null pointer");
+    WF3D_CHECK(Ep == 0 || (edge && dedge), WF3D_ERR_ARG, "wf3d_loss_terms_assigned_ew: null edge tensors");
+    WF3D_CHECK(Et == 0 || tlabel, WF3D_ERR_ARG, "wf3d_loss_terms_assigned_ew: null edge labels");
+    WF3D_CHECK(ws && ws_bytes >= (size_t)B * 3 * sizeof(float), WF3D_ERR_WS, "wf3d_loss_terms_assigned_ew: workspace too small");
+    const float ne = (float)B * V, ge = w_exist / ne;
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(loss_terms_dev_kernel, dim3(B), dim3(256), 0, st, verts, sample_stride, vertex_stride, exist, edge,
+                       Ep, tverts, Vt, texist, tlabel, Et, 0, col4row, counts, V, B, w_vertex, ge, 0.f, dverts, dexist,
+                       dedge, (float*)ws, edge_width, w_edge);
+    WF3D_LAUNCH_CHECK();
+    hipLaunchKernelGGL(loss_final_dev_kernel, dim3(1), dim3(1), 0, st, (const float*)ws, counts, B, V, ne, 0.f, w_vertex,
+                       w_exist, w_edge, losses, edge_width, Ep, Et);
     WF3D_LAUNCH_CHECK();
     return WF3D_OK;
 }

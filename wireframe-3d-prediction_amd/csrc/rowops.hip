@@ -155,17 +155,24 @@ __global__ __launch_bounds__(256) void ln_act_bwd_kernel(const float* __restrict
     // start: measured 0.8 ms slower than reading a stored pre at max_vertices = 256.)
     auto row_of = [&](int it) { return PAIR ? (blockIdx.x * iters + it) * RPI + wrow : (it * gridDim.x + blockIdx.x) * RPI + wrow; };
     int ps_s = 0, ps_vbase = 0, ps_v = 2, ps_eend = 0, ps_i = 0, ps_j = 1, pa_row = -1;
+    bool ps_tail = false;           // PAIR: the rows from here on are a padded layout's tail (esample -1): dz = 0
     f32x4 pa[PAIR ? NS : 1];
     if (PAIR) {
         const int r0 = min(row_of(0), R - 1);
-        ps_s = ps.esample[r0]; ps_vbase = ps.voff[ps_s]; ps_v = ps.voff[ps_s + 1] - ps_vbase; ps_eend = ps.eoff[ps_s + 1];
-        edge_ij(r0 - ps.eoff[ps_s], ps_v, ps_i, ps_j);
+        ps_s = ps.esample[r0];
+        if (ps_s < 0) {
+            ps_tail = true;
+        } else {
+            ps_vbase = ps.voff[ps_s]; ps_v = ps.voff[ps_s + 1] - ps_vbase; ps_eend = ps.eoff[ps_s + 1];
+            edge_ij(r0 - ps.eoff[ps_s], ps_v, ps_i, ps_j);
+        }
     }
     auto load_row = [&](int it) {
         // the row index is the same for every lane of a wave: say so, and the per-row scalars (mu, rs, the K input values)
         // come through the scalar cache in one or two s_load instead of 2 + K vector loads of one address each
         const int row = __builtin_amdgcn_readfirstlane(row_of(it));
         const bool live = it < iters && row < R;
+        const bool ld = live && !(PAIR && ps_tail);       // a tail row loads nothing: zero dh and pre give dz = 0
         mn = (has_ln && live) ? mu[row] : 0.f;
         rn = (has_ln && live) ? rs[row] : 1.f;
         if (KX > 0) {
@@ -177,7 +184,7 @@ __global__ __launch_bounds__(256) void ln_act_bwd_kernel(const float* __restrict
         for (int i = 0; i < NS; ++i) {
             const int c = cbeg + lane * 4 + 256 * i;
             zn[i] = dn[i] = (f32x4){0.f, 0.f, 0.f, 0.f};
-            if (live && c < cend) {
+            if (ld && c < cend) {
                 if (PAIR) {
                     if (ri != pa_row) pa[i] = *reinterpret_cast<const f32x4*>(ps.Pa + (size_t)ri * D + c);
                     const f32x4 b = *reinterpret_cast<const f32x4*>(ps.Pb + (size_t)rj * D + c);
@@ -190,15 +197,17 @@ __global__ __launch_bounds__(256) void ln_act_bwd_kernel(const float* __restrict
             }
         }
         if (PAIR) {
-            pa_row = live ? ri : pa_row;
+            pa_row = ld ? ri : pa_row;
             // step to this wave's next row: RPI edges further in the lexicographic (i, j) order, across samples
             int e = row;
 #pragma unroll
             for (int k = 0; k < RPI; ++k) {
                 ++e;
-                if (e >= R) break;
+                if (e >= R || ps_tail) break;
                 if (e == ps_eend) {                     // first edge of the next sample that has edges
-                    ps_s = ps.esample[e]; ps_vbase = ps.voff[ps_s]; ps_v = ps.voff[ps_s + 1] - ps_vbase; ps_eend = ps.eoff[ps_s + 1];
+                    ps_s = ps.esample[e];
+                    if (ps_s < 0) { ps_tail = true; break; }
+                    ps_vbase = ps.voff[ps_s]; ps_v = ps.voff[ps_s + 1] - ps_vbase; ps_eend = ps.eoff[ps_s + 1];
                     ps_i = 0; ps_j = 1;
                 } else if (++ps_j == ps_v) { ++ps_i; ps_j = ps_i + 1; }
             }

@@ -14,6 +14,9 @@ Differences to know about:
     scipy path raises like the reference.
   * exactly tied assignment costs: the device solver works on the same padded square problem in the same row
     order as scipy and reproduced its matches on every tested tie, but ties are not pinned by any fixture.
+  * a padded edge head (PointCloudToWireframe.set_edge_layout("padded")) predicts [B, V(V-1)/2] with the width
+    max_s E_s in predictions["edge_width"] (a device scalar): the edge term runs over min(that width, label width),
+    as the reference's over min(pred width, label width), so labels may be allocated at full width V(V-1)/2.
   * `set_data_parallel()`: with one process per GPU each rank sees a slice of the batch, but the reference's
     normalisers are batch-wide (matched-vertex count, :276-281; B x common edge width, :82-86).  When enabled,
     the three normalisers are exchanged (one tiny all-reduce) and each term is rescaled so that the MEAN over
@@ -30,14 +33,14 @@ class _LossDevFn(torch.autograd.Function):
     """Fully asynchronous variant: cost matrices, assignment, loss terms and gradients all on the device."""
 
     @staticmethod
-    def forward(ctx, verts, exist, edge, tverts, texist, tlabel, counts, weights, scales=None):
+    def forward(ctx, verts, exist, edge, tverts, texist, tlabel, counts, weights, scales=None, edge_width=None):
         exist_c = exist.contiguous()
         cost = ops.loss_cost_matrix(verts, exist_c, tverts, counts)
         # the square problem, rows in prediction order like scipy: L1 costs have exact ties (2 of 32 random samples
         # at V = 64) and the rectangular shortcut of ops.loss_assign(cost, counts) resolves them differently
         col4row = ops.loss_assign(cost)
         losses, dv, de, dd = ops.loss_terms_assigned(verts, exist_c, edge.contiguous(), tverts, texist, tlabel,
-                                                     col4row, counts, weights)
+                                                     col4row, counts, weights, edge_width=edge_width)
         if scales is not None:       # data-parallel renormalisation: (vertex, existence, edge) factors, device scalars
             w = torch.tensor(weights, dtype=torch.float32, device=losses.device)
             losses = torch.cat([losses[:3], (losses[:3] * w * scales).sum().reshape(1)])
@@ -49,7 +52,7 @@ class _LossDevFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g_total, _g_losses):
         dv, de, dd = ctx.saved_tensors
-        return (dv * g_total, de * g_total, dd * g_total, None, None, None, None, None, None)
+        return (dv * g_total, de * g_total, dd * g_total, None, None, None, None, None, None, None)
 
 
 class _LossFn(torch.autograd.Function):
@@ -99,8 +102,11 @@ class WireframeLoss(nn.Module):
         if W == 1:
             return None
         r = dist.get_rank(group)
-        mine = torch.stack([counts.clamp(max=V).sum().to(torch.float32),
-                            torch.tensor(float(B), device=dev), torch.tensor(float(min(e_pred, e_tgt)), device=dev)])
+        if torch.is_tensor(e_pred):       # a padded edge head's device width: min(width, e_tgt) without a host read
+            common = e_pred.clamp(max=e_tgt).to(device=dev, dtype=torch.float32).reshape(())
+        else:
+            common = torch.tensor(float(min(e_pred, e_tgt)), device=dev)
+        mine = torch.stack([counts.clamp(max=V).sum().to(torch.float32), torch.tensor(float(B), device=dev), common])
         table = torch.zeros(W, 3, dtype=torch.float32, device=dev)
         table[r] = mine
         dist.all_reduce(table, group=group)
@@ -145,8 +151,10 @@ class WireframeLoss(nn.Module):
             # the kernels index targets['vertices'][b, :counts[b]] and need counts[b] <= V real columns: clamp (docstring)
             counts = counts.clamp(min=0, max=min(V, tv.shape[1]))
             w = (self.vertex_weight, self.existence_weight, self.edge_weight)
-            scales = self._dp_scales(counts, B, V, pp.shape[1], tl.shape[1], dev)
-            total, parts = _LossDevFn.apply(pv, pe, pp, tv, te, tl, counts, w, scales)
+            ew = predictions.get("edge_width")        # padded edge head: the prediction width is a device scalar
+            ew = ew.to(device=dev, dtype=torch.int64) if ew is not None else None
+            scales = self._dp_scales(counts, B, V, pp.shape[1] if ew is None else ew, tl.shape[1], dev)
+            total, parts = _LossDevFn.apply(pv, pe, pp, tv, te, tl, counts, w, scales, ew)
             return {"total_loss": total, "vertex_loss": parts[0], "existence_loss": parts[1], "edge_loss": parts[2]}
         matches = self._hungarian_matching(predictions, targets)
         lens = [len(m[0]) for m in matches]
@@ -159,6 +167,9 @@ class WireframeLoss(nn.Module):
         tv = targets["vertices"].to(device=dev, dtype=torch.float32).contiguous()
         te = targets["vertex_existence"].to(device=dev, dtype=torch.float32).contiguous()
         tl = targets["edge_labels"].to(device=dev, dtype=torch.float32).contiguous()
+        if predictions.get("edge_width") is not None:
+            # padded edge head: this path has synced already, the width is read here and the columns past it dropped
+            pp = pp[:, :int(predictions["edge_width"])]
         # weights in the kernel's (vertex, existence, edge) order
         w = (self.vertex_weight, self.existence_weight, self.edge_weight)
         total, parts = _LossFn.apply(pv, pe, pp, tv, te, tl, m_pred, m_tgt, m_off, n_match, w)

@@ -5,11 +5,12 @@ Module tree and state_dict keys follow reference models/EdgePredictor.py:31-68
 RNG-order and state_dict compatibility).  forward() accepts a
 padded batch [B, V, vertex_dim]; `forward_ragged` runs samples with different vertex
 counts in one pass, which is how PointCloudToWireframe replaces the reference's
-serial per-sample loop."""
+serial per-sample loop; `forward_padded` does the same with the counts in device memory
+(capturable, any counts under one capture)."""
 import torch
 import torch.nn as nn
 
-from wf3d import config
+from wf3d import config, ops
 from wf3d.functional import EdgeFn, edge_index_lists
 from wf3d.random import default_generator
 
@@ -74,16 +75,38 @@ class EdgePredictor(nn.Module):
         if any(c < 2 for c in counts):
             # the reference indexes a 1-D empty index tensor here (EdgePredictor.py:118)
             raise IndexError("too many indices for tensor of dimension 1")
+        ps, seed = self._dropout(vertices.device)
+        return EdgeFn.apply(vertices.float(), tuple(counts), self._heads, ps, seed, config.precision(),
+                            *self._param_list())
+
+    def _dropout(self, device):
         ps = self._dropout_ps()
         if not any(ps):
             seed = 0
         elif config.dropout_rng() == "device":
             # seed words drawn on the device (wf3d.random): no host read, fresh on every replay of a captured step
-            seed = self.last_dropout_seeds = default_generator(vertices.device).draw()
+            seed = self.last_dropout_seeds = default_generator(device).draw()
         else:
             seed = int(torch.empty((), dtype=torch.int64).random_().item())
-        return EdgeFn.apply(vertices.float(), tuple(counts), self._heads, ps, seed, config.precision(),
-                            *self._param_list())
+        return ps, seed
+
+    def forward_padded(self, vertices, counts, return_layout=False):
+        """vertices [B, V, 3]; counts: integer tensor [B] on the device, never read on the host.  Sample s uses its
+        first c_s vertices, c_s clamped like `vertices[s, :counts[s]]` slicing.  Returns [B, V(V-1)/2]: sample s's first
+        c_s(c_s-1)/2 entries in the reference's pair order, exactly 0.0 after, so that out[:, :max_s E_s] is what
+        forward_ragged returns.  The row layout is built on the device in this call (capturable); the edge rows run at
+        their worst case, counts = V.  A sample with fewer than 2 vertices gets an all-zero row (forward_ragged raises
+        the reference's IndexError; that would need a host read here).
+        return_layout=True: also return the clamped counts (int64 [B]) and the edge width max_s E_s (0-d int64)."""
+        B, V, _ = vertices.shape
+        if not torch.is_tensor(counts) or counts.dim() != 1 or counts.shape[0] != B:
+            raise ValueError(f"forward_padded: counts must be a 1-D tensor of {B} counts")
+        if counts.dtype.is_floating_point or counts.dtype.is_complex:
+            raise ValueError("forward_padded: counts must be integers")
+        meta = ops.EdgeMeta.device(counts.to(device=vertices.device, dtype=torch.int64).contiguous(), B, V)
+        ps, seed = self._dropout(vertices.device)
+        probs = EdgeFn.apply(vertices.float(), meta, self._heads, ps, seed, config.precision(), *self._param_list())
+        return (probs, meta.counts, meta.width) if return_layout else probs
 
     def forward(self, vertices):
         b, v, _ = vertices.shape

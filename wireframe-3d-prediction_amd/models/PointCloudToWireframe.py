@@ -11,7 +11,7 @@ import torch.nn as nn
 from models.EdgePredictor import EdgePredictor
 from models.PointNetEncoder import PointNetEncoder
 from models.VertexPredictor import VertexPredictor
-from wf3d.functional import edge_index_lists
+from wf3d.functional import EdgeIndexLists, edge_index_lists
 
 
 class PointCloudToWireframe(nn.Module):
@@ -22,6 +22,7 @@ class PointCloudToWireframe(nn.Module):
         self.vertex_predictor = VertexPredictor(global_feature_dim=512, max_vertices=max_vertices)
         self.edge_predictor = EdgePredictor(vertex_dim=3)
         self._count_cache = (None, -1, None)         # (the tensor object itself, its _version, host ints)
+        self._edge_layout = "ragged"                 # set_edge_layout
 
     def set_dropout(self, p):
         """Set every dropout probability of the edge head (the only non-zero ones)."""
@@ -47,9 +48,46 @@ class PointCloudToWireframe(nn.Module):
         self._count_cache = (t, t._version, vals)
         return vals
 
+    def set_edge_layout(self, layout):
+        """"ragged" (default): the edge head's row layout is built from the counts read on the host — the output is the
+        reference's exactly.  "padded": the counts stay on the device (target counts in train mode, actual_vertex_counts
+        otherwise) and the layout is built there, so that a forward (and a training step) can be captured once and
+        replayed on batches with any counts.  Then `edge_probs` is [B, V(V-1)/2] (zeros past each sample's pairs; its
+        first `edge_width` columns are the ragged output), `edge_indices` is a read-only sequence that reads the counts
+        on first access, and two keys are added: `edge_counts` (int64 [B], the clamped counts used) and `edge_width`
+        (0-d int64 tensor, max_s E_s).  A sample with fewer than 2 vertices gets an all-zero row instead of the
+        reference's IndexError."""
+        if layout not in ("ragged", "padded"):
+            raise ValueError("edge layout must be 'ragged' or 'padded'")
+        self._edge_layout = layout
+        return self
+
+    def _forward_padded(self, g, vo, target_vertex_counts):
+        verts = vo["vertices"]
+        b = verts.shape[0]
+        if self.training and target_vertex_counts is not None:
+            tc = torch.as_tensor(target_vertex_counts)
+            if tc.dim() != 1 or tc.shape[0] < b:
+                n = tc.shape[0] if tc.dim() else 0
+                raise IndexError(f"index {n} is out of bounds for dimension 0 with size {n}")
+            counts = tc[:b]
+        else:
+            counts = vo["actual_vertex_counts"]
+        probs, ecounts, width = self.edge_predictor.forward_padded(verts, counts, return_layout=True)
+        return {"vertices": verts,
+                "existence_probabilities": vo["existence_probabilities"],
+                "edge_probs": probs,
+                "edge_indices": EdgeIndexLists(ecounts),
+                "global_features": g,
+                "actual_vertex_counts": vo["actual_vertex_counts"],
+                "edge_counts": ecounts,
+                "edge_width": width}
+
     def forward(self, point_cloud, target_vertex_counts=None):
         g, _pf, upooled = self.encoder.encode(point_cloud)
         vo = self.vertex_predictor.predict(g, upooled)
+        if getattr(self, "_edge_layout", "ragged") == "padded":
+            return self._forward_padded(g, vo, target_vertex_counts)
         verts = vo["vertices"]
         if self.training and target_vertex_counts is not None:
             counts = self._host_counts(target_vertex_counts)          # ground-truth counts (:77-86)

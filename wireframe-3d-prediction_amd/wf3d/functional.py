@@ -16,6 +16,7 @@ Which kernels a Linear of the encoder's per-point MLP or of the edge MLP's two w
 backward, is its Route: decided once in the stage's forward (_encoder_routes, _edge_routes) and only read by backward.
 """
 from collections import namedtuple
+from collections.abc import Sequence
 
 import torch
 
@@ -509,6 +510,10 @@ class VertexFn(torch.autograd.Function):
 class EdgeFn(torch.autograd.Function):
     """verts[B,V,3] (view ok) -> edge_probs[B, max_E] zero-padded.
 
+    `counts` is a tuple of host ints, or a padded ops.EdgeMeta built on the device (EdgeMeta.device): then every
+    launch covers the worst-case B*V vertex and B*V(V-1)/2 edge rows, max_E = V(V-1)/2, and the kernels keep the rows
+    past the live totals finite in forward and zero in backward (include/wf3d.h, "PADDED layouts").
+
     params = [P0w,P0b, P1g,P1b, P3w,P3b, P4g,P4b, Aw,Ab, Ow,Ob,
               M0w,M0b, M1g,M1b, M4w,M4b, M5g,M5b, M8w,M8b, M10w,M10b]
     (vertex_proj.{0,1,3,4}, attention.{in_proj,out_proj}, edge_mlp.{0,1,4,5,8,10})
@@ -530,7 +535,8 @@ class EdgeFn(torch.autograd.Function):
          M0w, M0b, M1g, M1b, M4w, M4b, M5g, M5b, M8w, M8b, M10w, M10b) = params
         B, V, _ = verts.shape
         H = P3w.shape[0]
-        meta = ops.EdgeMeta.get(counts, verts.device)
+        # counts: host ints, or an EdgeMeta already built on the device (EdgePredictor.forward_padded)
+        meta = counts if isinstance(counts, ops.EdgeMeta) else ops.EdgeMeta.get(counts, verts.device)
         sd = [1, 2, 3, 4] if ctx.words is not None else [(seed + 0x9E3779B9 * k) & 0xFFFFFFFF for k in range(1, 5)]
         pf_, pa_, p1_, p2_ = (float(x) for x in drop_ps)   # vertex_proj.5, attention, edge_mlp.3, edge_mlp.7
         cv = ops.edge_gather_verts(verts, meta)
@@ -697,6 +703,40 @@ class _FrozenList(list):
 
     append = extend = insert = remove = pop = clear = sort = reverse = _ro
     __setitem__ = __delitem__ = __iadd__ = __imul__ = _ro
+
+
+class EdgeIndexLists(Sequence):
+    """`edge_indices` of a padded edge head: a read-only sequence over the batch that equals
+    edge_index_lists(counts).  The counts stay on the device until the first access reads them (one device->host
+    copy); len() needs no read."""
+    __slots__ = ("_counts", "_lists")
+
+    def __init__(self, counts):
+        self._counts, self._lists = counts, None
+
+    def _get(self):
+        if self._lists is None:
+            self._lists = edge_index_lists([int(c) for c in self._counts.tolist()])
+        return self._lists
+
+    def __len__(self):
+        return int(self._counts.shape[0])
+
+    def __getitem__(self, i):
+        return self._get()[i]
+
+    def __eq__(self, other):
+        return list(self._get()) == list(other)
+
+    def __repr__(self):
+        return repr(self._get())
+
+    def _ro(self, *a, **k):
+        raise TypeError("edge_indices is read-only: copy first (e.g. [list(p) for p in out['edge_indices'][i]])")
+
+    append = extend = insert = remove = pop = clear = sort = reverse = _ro
+    __setitem__ = __delitem__ = __iadd__ = __imul__ = _ro
+    __hash__ = None
 
 
 _EDGE_LIST_CACHE = {}          # vertex count -> _FrozenList of _FrozenList([i, j]); LRU, bounded

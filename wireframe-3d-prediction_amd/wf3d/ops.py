@@ -370,8 +370,36 @@ def vertex_finalize_bwd(exist, dexist, d_o_in, B, V, vd):
 
 class EdgeMeta:
     """Compact ragged row layout of one batch: sample s owns vertex rows
-    voff[s]..voff[s+1]-1 and edge rows eoff[s]..eoff[s+1]-1."""
+    voff[s]..voff[s+1]-1 and edge rows eoff[s]..eoff[s+1]-1.
+
+    Built from host ints (EdgeMeta(counts) / .get), or on the device from an int64 count tensor (EdgeMeta.device):
+    then `padded` is True, the host sizes Rv, Re, vmax, max_e are the worst case of the padded width V, the rows past
+    the live totals map to sample -1, and `counts` (clamped) and `width` (max_s E_s) are device tensors."""
     _cache = {}
+    padded = False
+
+    @classmethod
+    def device(cls, counts, B, V):
+        """Layout of int64 counts [B] (device memory, never read on the host) for a batch padded to V vertices: one
+        launch of wf3d_edge_layout on the current stream, rebuilt on every call (and every replay of a capture)."""
+        _need_cuda(counts)
+        if counts.dtype != torch.int64 or counts.shape != (B,) or not counts.is_contiguous():
+            raise RuntimeError(f"wf3d.EdgeMeta.device: counts must be a contiguous int64 [{B}] tensor")
+        dev = counts.device
+        E = V * (V - 1) // 2
+        if B * E > 0x7FFFFFFF:
+            raise RuntimeError(f"wf3d.EdgeMeta.device: B*V(V-1)/2 = {B * E} edge rows do not fit in int32")
+        m = cls.__new__(cls)
+        m.padded = True
+        m.B, m.Rv, m.Re, m.vmax, m.max_e = B, B * V, B * E, V, E
+        i32 = dict(dtype=torch.int32, device=dev)
+        m.voff, m.eoff = torch.empty(B + 1, **i32), torch.empty(B + 1, **i32)
+        m.vsample, m.esample = torch.empty(B * V, **i32), torch.empty(B * E, **i32)
+        m.counts = torch.empty(B, dtype=torch.int64, device=dev)
+        m.width = torch.empty((), dtype=torch.int64, device=dev)
+        check(_lib.load().wf3d_edge_layout(_p(counts), B, V, _p(m.voff), _p(m.eoff), _p(m.vsample), _p(m.esample),
+                                           _p(m.counts), _p(m.width), _stream()), "edge_layout")
+        return m
 
     def __init__(self, counts, device):
         self.counts = tuple(int(c) for c in counts)
@@ -423,8 +451,9 @@ def edge_scatter_dverts(dcv, meta, B, V):
 
 def attn_fwd(qkv, meta, E, heads, drop_p=0.0, seed=0):
     _need_cuda(qkv)
-    ctx = torch.empty(meta.Rv, E, dtype=torch.float32, device=qkv.device)
-    lse = torch.empty(meta.Rv, heads, dtype=torch.float32, device=qkv.device)
+    alloc = torch.zeros if meta.padded else torch.empty       # the kernels write real samples' rows only
+    ctx = alloc(meta.Rv, E, dtype=torch.float32, device=qkv.device)
+    lse = alloc(meta.Rv, heads, dtype=torch.float32, device=qkv.device)
     check(_lib.load().wf3d_attn_fwd(_p(qkv), _p(meta.voff), meta.B, meta.vmax, E, heads, float(drop_p),
                                     int(seed) & 0xFFFFFFFF, _p(ctx), _p(lse), _stream()), "attn_fwd")
     return ctx, lse
@@ -434,7 +463,7 @@ def attn_bwd(qkv, dctx, ctx, lse, meta, E, heads, drop_p=0.0, seed=0):
     _need_cuda(qkv, dctx, ctx, lse)
     if not (dctx.is_contiguous() and ctx.is_contiguous()):
         raise RuntimeError("wf3d.attn_bwd: contiguous dctx / ctx required")
-    dqkv = torch.empty_like(qkv)
+    dqkv = torch.zeros_like(qkv) if meta.padded else torch.empty_like(qkv)
     check(_lib.load().wf3d_attn_bwd(_p(qkv), _p(dctx), _p(ctx), _p(lse), _p(meta.voff), meta.B, meta.vmax, E, heads,
                                     float(drop_p), int(seed) & 0xFFFFFFFF, _p(dqkv), _stream()), "attn_bwd")
     return dqkv
@@ -757,8 +786,12 @@ def loss_assign(cost, counts=None):
     return out
 
 
-def loss_terms_assigned(verts, exist, edge, tverts, texist, tlabel, col4row, counts, weights):
-    _need_cuda(verts, exist, edge, tverts, texist, tlabel, col4row, counts)
+def loss_terms_assigned(verts, exist, edge, tverts, texist, tlabel, col4row, counts, weights, edge_width=None):
+    """edge_width: int64 0-d device tensor, the prediction's edge width (a padded edge head's), read by the kernel
+    instead of edge.shape[1]."""
+    _need_cuda(verts, exist, edge, tverts, texist, tlabel, col4row, counts, edge_width)
+    if edge_width is not None:
+        return _loss_terms_assigned_ew(verts, exist, edge, tverts, texist, tlabel, col4row, counts, weights, edge_width)
     B, V, _ = verts.shape
     Ep = edge.shape[1] if edge is not None else 0
     Et = tlabel.shape[1] if tlabel is not None else 0
@@ -773,4 +806,24 @@ def loss_terms_assigned(verts, exist, edge, tverts, texist, tlabel, col4row, cou
                                                _p(counts), B, V, float(weights[0]), float(weights[1]), float(weights[2]),
                                                _p(dverts), _p(dexist), _p(dedge), _p(losses), _p(ws), ws.numel(),
                                                _stream()), "loss_terms_assigned")
+    return losses, dverts, dexist, dedge
+
+
+def _loss_terms_assigned_ew(verts, exist, edge, tverts, texist, tlabel, col4row, counts, weights, edge_width):
+    if edge_width.dtype != torch.int64 or edge_width.numel() != 1:
+        raise RuntimeError("wf3d.loss_terms_assigned: edge_width must be a one-element int64 tensor")
+    B, V, _ = verts.shape
+    Ep = edge.shape[1] if edge is not None else 0
+    Et = tlabel.shape[1] if tlabel is not None else 0
+    dev = verts.device
+    dverts = torch.empty(B, V, 3, dtype=torch.float32, device=dev)
+    dexist = torch.empty(B, V, dtype=torch.float32, device=dev)
+    dedge = torch.empty(B, Ep, dtype=torch.float32, device=dev)
+    losses = torch.empty(4, dtype=torch.float32, device=dev)
+    ws = scratch(B * 3 * 4, dev)
+    check(_lib.load().wf3d_loss_terms_assigned_ew(_p(verts), verts.stride(0), verts.stride(1), _p(exist), _p(edge), Ep,
+                                                  _p(tverts), tverts.shape[1], _p(texist), _p(tlabel), Et, _p(edge_width),
+                                                  _p(col4row), _p(counts), B, V, float(weights[0]), float(weights[1]),
+                                                  float(weights[2]), _p(dverts), _p(dexist), _p(dedge), _p(losses), _p(ws),
+                                                  ws.numel(), _stream()), "loss_terms_assigned_ew")
     return losses, dverts, dexist, dedge
