@@ -486,6 +486,51 @@ int wf3d_clip_adam_step_dev(float* const* params, float* const* grads, float* co
 int wf3d_dropout_draw(uint64_t* state, uint32_t* words, void* stream);
 int wf3d_set_dropout_seed_words(const uint32_t* words);
 
+/* ------------------------------------------------------------------------
+ * LIVE ROW COUNT.  A padded edge layout runs every edge-row launch at the worst case B*V(V-1)/2 rows.  While the calling
+ * thread has set a live-row count, wf3d_set_live_rows(rows) with rows -> one int32 in DEVICE memory (wf3d_edge_layout's
+ * eoff + B), the launches listed below skip the tail.  The pointer is a kernel argument and the value is read by the
+ * kernel at entry, never on the host: a captured graph stays valid when the value changes between replays.  NULL
+ * clears it.  Thread-local, host only, like wf3d_set_dropout_seed_words; a side stream driven from the same thread
+ * is covered.
+ *
+ * With R the launch's host-side row extent (the worst case, as without a count), live = clamp(*rows, 0, R) and
+ * R256 = min(R, 256 * ceil(live / 256)):
+ *   - no row >= R256 of a row-indexed operand is read, no row >= R256 of a row-indexed output is written;
+ *   - rows [0, R256) are read and written exactly as without a count, the dead rows [live, R256) included (zeros from
+ *     the pair kernel, bias-only values after a forward GEMM, exact zeros in every backward dz);
+ *   - reductions over rows (wf3d_colsum, the dgamma / dbeta / dbias / wsum of the LayerNorm backward, the column sums
+ *     of wf3d_rowdot_act_bwd, the K dimension of the TN weight-gradient GEMMs) cover [0, R256) only;
+ *   - grids, kernel choice, split-K plans and workspace sizes stay the host-side worst-case ones; slabs and partial
+ *     sums are folded in the same order, a workgroup whose rows lie past R256 contributes an exact zero.
+ * So every result in rows < R256 is bit-identical to the same launch without a count, and every reduced result is
+ * whenever the skipped rows of the reduced operand were zeros (every backward tail of a padded edge head is).
+ * live = 0 is legal: nothing is read, row outputs are untouched, reduced outputs are exact zeros.
+ * 256: every tile height and K slice of these kernels divides it, so no kernel needs a partial-tile path.
+ *
+ * Honoured by (rows = the dimension named):
+ *   wf3d_gemm_split, wf3d_gemm_bf16            M, every kernel form and the split-K combine
+ *   wf3d_gemm_split_tn, wf3d_gemm_bf16_tn      K, every kernel form (Mo, No are weight dimensions)
+ *   wf3d_ln_prep, wf3d_ln_act_bwd, wf3d_ln_act_bwd_wsum, wf3d_edge_pair_ln_bwd, wf3d_rowdot_act, wf3d_rowdot_act_bwd,
+ *   wf3d_colsum                                R / Re
+ *   wf3d_edge_pair_fwd, wf3d_edge_pair_fwd_ln, wf3d_edge_prob_bwd      Re
+ *   wf3d_split_rows                            R (rows of the output)
+ *   wf3d_split_transpose                       R (rows of the input), both the fp32 / prologue and the in_sx8 form.  Its
+ *                                              output is [C, R]: the input's rows are its COLUMNS, the reduction
+ *                                              dimension of the NT GEMM that consumes a pair of transposed operands.
+ *                                              No input row >= R256 (nor its mu / rs) is read, the columns < R256 are
+ *                                              written as without a count, and the columns [R256, R) are written as
+ *                                              exact zeros.  The caller runs that GEMM WITHOUT a count (its rows are a
+ *                                              weight dimension): the zero columns add exact zeros in its unchanged
+ *                                              split-K order, as the zero backward tail does without a count.
+ * wf3d_edge_pair_bwd and wf3d_edge_prob_fwd reach edge rows through eoff only and touch no tail row with or without
+ * a count.  EVERY OTHER entry point ignores the count and cannot see it: wf3d_gemm (the fp32 routes), the attention
+ * and skinny kernels, wf3d_row_stats, wf3d_ln_act_apply, wf3d_ln_act_bwd_first, wf3d_split_rows_multi (weights), the
+ * per-vertex launches.  The caller clears the count around launches over other rows (the
+ * honouring entry points apply it to whatever rows they are given).
+ * ------------------------------------------------------------------------ */
+int wf3d_set_live_rows(const int32_t* rows);
+
 /* Training-step meter (reference train.py:145-157: total_loss.item() twice and a host copy of sample 0's vertices on EVERY
  * step, for the loss history, the best loss and a monitoring RMSE).  One small launch per step folds them into a
  * device-resident record; the loop copies it back only when it logs.

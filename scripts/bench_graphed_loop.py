@@ -8,8 +8,12 @@ each batch passed as is (its counts are read on the host every step).  Padded: s
 on static buffers; per step each batch is copy_'d into them and the graph replayed (the copies are inside the timing).
 Both loops are timed with device events over --steps steps after --warmup, cycling through the batches.  Also timed:
 the padded step run eagerly, which separates the padding's extra edge rows from what capture saves.
+--tail skip adds the same two padded arms under set_edge_layout("padded", tail="skip"), whose edge-row launches stop
+at the live pair total (read from device memory by the kernels), and reports the fraction of dead edge rows of the drawn
+batches, 1 - sum E_s / (B E_max), next to the step-time difference.  The v256 shape draws its counts from 4..256.
 
-    python scripts/bench_graphed_loop.py [--steps 100] [--warmup 5] [--batches 8] [--shapes train,cfg2]
+    python scripts/bench_graphed_loop.py [--steps 100] [--warmup 5] [--batches 8] [--shapes train,cfg2,v256]
+                                         [--tail compute|skip]
 
 Prints one JSON line per shape.
 """
@@ -31,15 +35,17 @@ from wf3d.optim import ClipAdam  # noqa: E402
 from wf3d.targets import train_targets  # noqa: E402
 
 # name -> (B, N, V): train.py's batch (main.py: 3 clouds of 2,560 points, max_vertices 38) and bench.py's cfg2
-SHAPES = {"train": (3, 2560, 38), "cfg2": (32, 4096, 64)}
+# v256: cfg5's width, where the edge head is half of the FLOPs, with counts spread over 4..256
+SHAPES = {"train": (3, 2560, 38), "cfg2": (32, 4096, 64), "v256": (32, 4096, 256)}
+COUNTS_MAX = {"v256": 256}                     # upper end of the drawn counts (default: the demo set's 38)
 KEYS = ("vertices", "vertex_existence", "edge_labels", "vertex_counts")
 
 
-def batches(n, B, N, V, dev, seed=1):
+def batches(n, B, N, V, dev, seed=1, cmax=38):
     rng = np.random.default_rng(seed)
     out = []
     for _ in range(n):
-        cnt = rng.integers(4, min(38, V) + 1, size=B).tolist()
+        cnt = rng.integers(4, min(cmax, V) + 1, size=B).tolist()
         vs = [rng.standard_normal((c, 3)).astype(np.float32) for c in cnt]
         es = [np.stack([np.arange(c - 1), np.arange(1, c)], 1) for c in cnt]      # a chain: some positive labels
         t = train_targets(vs, es, V, device=dev, full_width=True)
@@ -48,14 +54,15 @@ def batches(n, B, N, V, dev, seed=1):
     return out
 
 
-def run(name, steps, warmup, nb, dev):
+def run(name, steps, warmup, nb, dev, tail="compute"):
     B, N, V = SHAPES[name]
-    data = batches(nb, B, N, V, dev)
+    cmax = min(COUNTS_MAX.get(name, 38), V)
+    data = batches(nb, B, N, V, dev, cmax=cmax)
     crit = WireframeLoss(vertex_weight=3.0, edge_weight=1.0, existence_weight=1.5, assignment="device")
 
-    def model(layout):
+    def model(layout, tail=None):
         torch.manual_seed(0)
-        m = PointCloudToWireframe(8, V).to(dev).set_dropout(0.1).train().set_edge_layout(layout)
+        m = PointCloudToWireframe(8, V).to(dev).set_dropout(0.1).train().set_edge_layout(layout, tail=tail)
         return m, ClipAdam(m.parameters(), lr=1e-3, weight_decay=1e-6, max_norm=1.0, norm_params=m.parameters,
                            capturable=True), TrainMeter(dev)
 
@@ -88,35 +95,50 @@ def run(name, steps, warmup, nb, dev):
     torch.manual_seed(2)
     m, opt, meter = model("ragged")
     ragged_ms = timed(lambda k: step(m, opt, meter, data[k % nb], True))
-    torch.manual_seed(2)
-    m, opt, meter = model("padded")
-    padded_eager_ms = timed(lambda k: step(m, opt, meter, data[k % nb], False))
+    del m, opt, meter
 
-    torch.manual_seed(2)
-    m, opt, meter = model("padded")
-    static = {k: t.clone() for k, t in data[0].items() if torch.is_tensor(t)}
-    s = torch.cuda.Stream(dev)
-    s.wait_stream(torch.cuda.current_stream())
-    with torch.cuda.stream(s):
-        for _ in range(2):
+    def padded(tail):
+        """(eager ms, replay ms, finite) of the padded step with this tail mode."""
+        torch.manual_seed(2)
+        m, opt, meter = model("padded", tail)
+        eager_ms = timed(lambda k: step(m, opt, meter, data[k % nb], False))
+        torch.manual_seed(2)
+        m, opt, meter = model("padded", tail)
+        static = {k: t.clone() for k, t in data[0].items() if torch.is_tensor(t)}
+        s = torch.cuda.Stream(dev)
+        s.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(s):
+            for _ in range(2):
+                step(m, opt, meter, static, False)
+        torch.cuda.current_stream().wait_stream(s)
+        graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(graph):
             step(m, opt, meter, static, False)
-    torch.cuda.current_stream().wait_stream(s)
-    graph = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(graph):
-        step(m, opt, meter, static, False)
 
-    def replay(k):
-        bt = data[k % nb]
-        for key, t in static.items():
-            t.copy_(bt[key])
-        graph.replay()
-    replay_ms = timed(replay)
-    hist = meter.read()["loss_history"]
-    return {"shape": name, "B": B, "N": N, "V": V, "batches": nb, "counts_range": [4, min(38, V)], "dropout": 0.1,
-            "steps": steps, "ragged_eager_ms_per_step": round(ragged_ms, 3),
-            "padded_eager_ms_per_step": round(padded_eager_ms, 3), "padded_replay_ms_per_step": round(replay_ms, 3),
-            "speedup_replay_vs_ragged": round(ragged_ms / replay_ms, 2), "finite_loss": bool(np.all(np.isfinite(hist))),
-            "precision": config.precision()}
+        def replay(k):
+            bt = data[k % nb]
+            for key, t in static.items():
+                t.copy_(bt[key])
+            graph.replay()
+        replay_ms = timed(replay)
+        return eager_ms, replay_ms, bool(np.all(np.isfinite(meter.read()["loss_history"])))
+
+    padded_eager_ms, replay_ms, finite = padded("compute")
+    res = {"shape": name, "B": B, "N": N, "V": V, "batches": nb, "counts_range": [4, cmax], "dropout": 0.1,
+           "steps": steps, "ragged_eager_ms_per_step": round(ragged_ms, 3),
+           "padded_eager_ms_per_step": round(padded_eager_ms, 3), "padded_replay_ms_per_step": round(replay_ms, 3),
+           "speedup_replay_vs_ragged": round(ragged_ms / replay_ms, 2), "finite_loss": finite,
+           "precision": config.precision()}
+    if tail == "skip":
+        skip_eager_ms, skip_replay_ms, finite = padded("skip")
+        live = sum(c * (c - 1) // 2 for bt in data for c in bt["vertex_counts"].tolist())
+        dead = 1.0 - live / (nb * B * (V * (V - 1) // 2))
+        res.update({"skip_eager_ms_per_step": round(skip_eager_ms, 3), "skip_replay_ms_per_step": round(skip_replay_ms, 3),
+                    "dead_edge_row_fraction": round(dead, 4),
+                    "replay_saving_fraction": round((replay_ms - skip_replay_ms) / replay_ms, 4),
+                    "saving_over_dead_fraction": round((replay_ms - skip_replay_ms) / replay_ms / dead, 3) if dead > 0 else None,
+                    "finite_loss": res["finite_loss"] and finite})
+    return res
 
 
 def main():
@@ -125,12 +147,13 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--batches", type=int, default=8)
     ap.add_argument("--shapes", default="train,cfg2")
+    ap.add_argument("--tail", choices=("compute", "skip"), default="compute")
     args = ap.parse_args()
     config.set_dropout_rng("device")
     dev = torch.device("cuda:0")
     ok = True
     for name in args.shapes.split(","):
-        r = run(name, args.steps, args.warmup, args.batches, dev)
+        r = run(name, args.steps, args.warmup, args.batches, dev, args.tail)
         ok = ok and r["finite_loss"]
         print(json.dumps(r), flush=True)
     sys.exit(0 if ok else 1)

@@ -14,7 +14,9 @@
 //
 // A layout built on the device (wf3d_edge_layout) is PADDED: launches cover the worst case B*V vertex rows and
 // B*V(V-1)/2 edge rows, and the rows past voff[B] / eoff[B] (the tail) have vsample / esample = -1.  Every kernel here
-// writes zeros for a tail row, so that the tail is finite in forward and exactly zero in every gradient.
+// writes zeros for a tail row, so that the tail is finite in forward and exactly zero in every gradient.  Under a
+// live-row count (wf3d_set_live_rows with eoff + B) the edge-row kernels, pair_fwd and edge_prob_bwd, stop at the
+// count's 256-row extent; pair_bwd and edge_prob_fwd reach edge rows through eoff only and never touch the tail.
 #include "wf3d_common.h"
 
 namespace {
@@ -108,9 +110,11 @@ __global__ __launch_bounds__(256) void pair_fwd_kernel(const float* __restrict__
                                                         float* __restrict__ rs, float* __restrict__ delta,
                                                         const float* __restrict__ gamma, const float* __restrict__ beta,
                                                         int act, const wf3d_seed_t seed_src, uint32_t thresh, float dscale,
-                                                        float* __restrict__ h_sx8, int vd) {
+                                                        float* __restrict__ h_sx8, int vd,
+                                                        const int32_t* __restrict__ live_rows) {
     const uint32_t seed = thresh ? wf3d_seed_load(seed_src) : 0u;
     constexpr int EPW = 8;
+    Re = wf3d_live_extent(live_rows, Re);              // under a live-row count the zero-written tail ends at its extent
     const int lane = threadIdx.x & 63;
     const int e0 = (blockIdx.x * 4 + (threadIdx.x >> 6)) * EPW;
     if (e0 >= Re) return;
@@ -350,9 +354,10 @@ __global__ __launch_bounds__(256) void edge_prob_fwd_kernel(const float* __restr
 __global__ __launch_bounds__(256) void edge_prob_bwd_kernel(const float* __restrict__ probs, const float* __restrict__ dprobs,
                                                              const int32_t* __restrict__ eoff,
                                                              const int32_t* __restrict__ esample, int Re, int max_e,
-                                                             float* __restrict__ dlogit) {
+                                                             float* __restrict__ dlogit,
+                                                             const int32_t* __restrict__ live_rows) {
     const int e = blockIdx.x * 256 + threadIdx.x;
-    if (e >= Re) return;
+    if (e >= wf3d_live_extent(live_rows, Re)) return;
     const int s = esample[e];
     if (s < 0) { dlogit[e] = 0.f; return; }
     const size_t o = (size_t)s * max_e + (e - eoff[s]);
@@ -471,7 +476,7 @@ static int pair_fwd_impl(const float* Pa, const float* Pb, const float* cv, cons
 #define WF3D_PF(NS_)                                                                                                 \
     hipLaunchKernelGGL((pair_fwd_kernel<NS_>), dim3(wf3d_cdiv(Re, 4 * 8)), dim3(256), 0, st, Pa, Pb, cv, wdelta,           \
                        wdelta_stride, voff, eoff, esample, Re, H, eps, pre, mu, rs, delta, gamma, beta, act, seed,         \
-                       thresh, dscale, (float*)h_sx8, vd)
+                       thresh, dscale, (float*)h_sx8, vd, wf3d_live_rows())
     if (ns <= 1) WF3D_PF(1); else if (ns <= 2) WF3D_PF(2); else if (ns <= 4) WF3D_PF(4); else WF3D_PF(8);
 #undef WF3D_PF
     WF3D_LAUNCH_CHECK();
@@ -516,7 +521,7 @@ extern "C" int wf3d_edge_prob_bwd(const float* probs, const float* dprobs, const
     if (Re == 0) return WF3D_OK;
     WF3D_CHECK(probs && dprobs && eoff && esample && dlogit, WF3D_ERR_ARG, "wf3d_edge_prob_bwd: null pointer");
     hipLaunchKernelGGL(edge_prob_bwd_kernel, dim3(wf3d_cdiv(Re, 256)), dim3(256), 0, (hipStream_t)stream, probs, dprobs,
-                       eoff, esample, Re, max_e, dlogit);
+                       eoff, esample, Re, max_e, dlogit, wf3d_live_rows());
     WF3D_LAUNCH_CHECK();
     return WF3D_OK;
 }

@@ -49,6 +49,7 @@ struct GemmParams {
     int vecA, vecB, vecP;
     int nbm, nbn;
     const float* lr_u; const float* lr_v; int lr_k, ld_lr_u, ld_lr_v;    // epilogue: C += U[M, lr_k] . V[N, lr_k]^T
+    const int32_t* live;   // SPLIT form only (wf3d_gemm_split_regs): live-row count over M; the fp32 routes never read it
 };
 
 // ---- staging: global -> registers ------------------------------------------
@@ -504,6 +505,7 @@ __global__ __launch_bounds__(256, 2) void gemm_kernel(const GemmParams p) {
     const int q = nwg >> 3, r = nwg & 7, xcd = bid & 7;
     const int vid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
     const int m0 = (vid / p.nbn) * BM, n0 = (vid % p.nbn) * BN;
+    if (SPLIT && m0 >= wf3d_live_extent(p.live, p.M)) return;      // a tile past the live rows: nothing read, nothing written
 
     const int ktotal = (p.K + BK - 1) / BK;
     const int kt0 = blockIdx.z * p.kt_per_split;
@@ -519,8 +521,9 @@ __global__ __launch_bounds__(256, 2) void gemm_kernel(const GemmParams p) {
 
 // split-K combine (wf3d_splitk_combine): deterministic slab sum + epilogue terms
 __global__ __launch_bounds__(256) void splitk_combine_kernel(const SplitKCombine p) {
-    const size_t total = (size_t)p.M * p.N;
-    for (size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (size_t)gridDim.x * 256) {
+    const size_t total = (size_t)p.M * p.N;                 // slab pitch: the host-side extent
+    const size_t end = (size_t)wf3d_live_extent(p.live, p.M) * p.N;
+    for (size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x; idx < end; idx += (size_t)gridDim.x * 256) {
         const int row = (int)(idx / p.N), col = (int)(idx % p.N);
         float v = 0.f;
         for (int z = 0; z < p.ksplit; ++z) v += p.slab[(size_t)z * total + idx];
@@ -542,7 +545,7 @@ __global__ __launch_bounds__(256) void splitk_combine_wide_kernel(const SplitKCo
     const int lane = threadIdx.x & 63, sl = lane >> 2, q = lane & 3;
     const size_t idx = ((size_t)blockIdx.x * 4 + (threadIdx.x >> 6)) * 16 + q * 4;
     f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-    const bool live = idx < total;
+    const bool live = idx < (size_t)wf3d_live_extent(p.live, p.M) * p.N;
     if (live) {
         const float* base = p.slab + idx;
         for (int z = sl; z < p.ksplit; z += 64) {
@@ -693,7 +696,7 @@ extern "C" int wf3d_gemm(const wf3d_gemm_t* d, void* stream) {
     WF3D_LAUNCH_CHECK();
     if (p.ksplit == 1) return WF3D_OK;
     return wf3d_splitk_combine({p.slab, p.C, p.bias, p.addend, p.lr_u, p.lr_v, p.M, p.N, p.ldc, p.ld_addend, p.lr_k, p.ld_lr_u,
-                                p.ld_lr_v, p.ksplit, p.accumulate}, false, st);
+                                p.ld_lr_v, p.ksplit, p.accumulate, nullptr}, false, st);
 }
 
 int wf3d_splitk_combine(const SplitKCombine& c, bool narrow_only, hipStream_t st) {
@@ -712,7 +715,7 @@ int wf3d_splitk_combine(const SplitKCombine& c, bool narrow_only, hipStream_t st
 // The register-staged bf16x3 / bf16 split GEMM on sx8 operands (wf3d_gemm_split / wf3d_gemm_bf16 take it for K % 32 != 0;
 // gemm_split.hip chooses and plans).  products: 3 = bf16x3, 1 = plain bf16 on the hi planes.
 int wf3d_gemm_split_regs(int products, const void* A_sx8, const void* B_sx8, float* C, const float* bias, int M, int N, int K,
-                         int lda, int ldb, int ldc, int accumulate, SplitK s, float* slab, hipStream_t st) {
+                         int lda, int ldb, int ldc, int accumulate, SplitK s, float* slab, const int32_t* live, hipStream_t st) {
     GemmParams p{};
     p.A = (const float*)A_sx8; p.B = (const float*)B_sx8; p.C = C; p.bias = bias;
     p.M = M; p.N = N; p.K = K; p.lda = lda; p.ldb = ldb; p.ldc = ldc;
@@ -721,10 +724,11 @@ int wf3d_gemm_split_regs(int products, const void* A_sx8, const void* B_sx8, flo
     p.nbm = wf3d_cdiv(M, 128); p.nbn = wf3d_cdiv(N, 128);
     p.ksplit = s.ksplit; p.kt_per_split = s.kt_per;
     p.slab = s.ksplit > 1 ? slab : nullptr;
+    p.live = live;
     dim3 grid(p.nbm * p.nbn, 1, p.ksplit);
     if (products == 1) hipLaunchKernelGGL((gemm_kernel<2, 2, 2, 2, true, true, 0, false, true, false, 1>), grid, dim3(256), 0, st, p);
     else               hipLaunchKernelGGL((gemm_kernel<2, 2, 2, 2, true, true, 0, false, true>), grid, dim3(256), 0, st, p);
     WF3D_LAUNCH_CHECK();
     if (p.ksplit == 1) return WF3D_OK;
-    return wf3d_splitk_combine({p.slab, C, bias, nullptr, nullptr, nullptr, M, N, ldc, 0, 0, 0, 0, p.ksplit, accumulate}, true, st);
+    return wf3d_splitk_combine({p.slab, C, bias, nullptr, nullptr, nullptr, M, N, ldc, 0, 0, 0, 0, p.ksplit, accumulate, live}, true, st);
 }

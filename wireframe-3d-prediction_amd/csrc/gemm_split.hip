@@ -45,7 +45,21 @@ struct SplitParams {
     int nbm, nbn;
     unsigned* ctl;     // persistent kernel: 8 tile-claim counters (64 B apart, zeroed per launch) + one mailbox word per workgroup
     int zmap;          // x16 kernel, wgrad: 1 = 1-D grid of tiles x ksplit blocks, XCD k owns the split-K ranges z = k (mod 8)
+    // Live-row count (include/wf3d.h, "LIVE ROW COUNT"; NULL: none), read once at kernel entry.  The rows are M in the
+    // forward / dgrad kernels — a tile at or past the extent leaves at once, the persistent kernel deals the live tiles
+    // only — and K in the wgrad kernels: the slice count stops at the extent, and a K range past it stores exact zeros.
+    const int32_t* live;
 };
+
+// wgrad: what a K range without live slices contributes to its 256 x TN_ output tile (512 threads)
+template <int TN_>
+__device__ __forceinline__ void store_zero_tile(const SplitParams& p, int m0, int n0, int zi) {
+    for (int idx = threadIdx.x; idx < 256 * TN_; idx += 512) {
+        const int row = m0 + idx / TN_, col = n0 + idx % TN_;
+        if (p.ksplit > 1)       p.slab[((size_t)zi * p.M + row) * p.N + col] = 0.f;
+        else if (!p.accumulate) p.C[(size_t)row * p.ldc + col] = 0.f;
+    }
+}
 
 __device__ __forceinline__ void dma16(const float* src, float* lds_wave_base) {
     __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
@@ -136,6 +150,7 @@ __global__ __launch_bounds__(512, 2) void gemm_split_dma3_kernel(const SplitPara
     const int q8 = nwg >> 3, r8 = nwg & 7, xcd = bid & 7;
     const int vid = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (bid >> 3);
     const int m0 = (vid / p.nbn) * 256, n0 = (vid % p.nbn) * 128;
+    if (m0 >= wf3d_live_extent(p.live, p.M)) return;       // tile past the live rows
     const int ktotal = p.K / SBK;
     const int kt0 = blockIdx.z * p.kt_per_split;
     const int kt1 = min(ktotal, kt0 + p.kt_per_split);
@@ -292,7 +307,7 @@ __global__ __launch_bounds__(512, 2) void gemm_split_tn_kernel(const SplitParams
     const int q8 = nwg >> 3, r8 = nwg & 7, xcd = bid & 7;
     const int vid = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (bid >> 3);
     const int m0 = (vid / p.nbn) * 256, n0 = (vid % p.nbn) * 128;      // p.M = Mo, p.N = No (full tiles only)
-    const int ktotal = p.K / SBK;
+    const int ktotal = wf3d_live_extent(p.live, p.K) / SBK;           // a range past it runs no slice and stores zeros
     const int kt0 = blockIdx.z * p.kt_per_split;
     const int kt1 = min(ktotal, kt0 + p.kt_per_split);
 
@@ -474,9 +489,15 @@ __global__ __launch_bounds__(512, 2) void gemm_split_x16_kernel(const SplitParam
         zi = blockIdx.z;
     }
     const int m0 = (vid / p.nbn) * 256, n0 = (vid % p.nbn) * 256;
-    const int ktotal = p.K / SBK;
+    const int extent = wf3d_live_extent(p.live, TN ? p.K : p.M);          // live rows: K of a wgrad, M otherwise
+    const int ktotal = (TN ? extent : p.K) / SBK;
     const int kt0 = zi * p.kt_per_split;
     const int kt1 = min(ktotal, kt0 + p.kt_per_split);
+    if (TN) {
+        if (kt0 >= kt1) { store_zero_tile<256>(p, m0, n0, zi); return; }      // K range past the live rows
+    } else if (m0 >= extent) {
+        return;                                                                // tile past the live rows
+    }
 
     // DMA sources: 4 A pieces + 4 B pieces of 1 KB per wave and slice.  NT: a piece = 8 tile rows x 128 B;
     // TN: a piece = one k-row of the tile (256 cols x 4 B).  Either way piece q lands at wave*1024 + q*256 floats.
@@ -793,7 +814,8 @@ __global__ __launch_bounds__(512, 2) void gemm_split_x16p_kernel(const SplitPara
     // mailbox word in global memory (all 160 KB of LDS are operand stages; the very first draw, before any DMA, goes
     // through LDS): draw in slice 0 of a tile, publish in slice 1, read in slice 2 — each memory operation is older
     // than its slice's DMA pieces, so the counted waits below are unchanged — first needed in slice ktotal - 2.
-    const int nwg = p.nbm * p.nbn;
+    // under a live-row count the live tiles (the first rows' tiles: ids are row-major) are the ones dealt and claimed
+    const int nwg = (wf3d_live_extent(p.live, p.M) / 256) * p.nbn;
     const int bid = blockIdx.x;
     const int q8 = nwg >> 3, r8 = nwg & 7, xcd = bid & 7;
     const int xbase = xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8;
@@ -1035,10 +1057,11 @@ void launch_split_tn(const SplitParams& p, bool big, hipStream_t st) {
     else               hipLaunchKernelGGL((gemm_split_tn_kernel<NP>), dim3(p.nbm * p.nbn, 1, p.ksplit), dim3(512), 0, st, p);
 }
 
-int combine(const SplitParams& p, hipStream_t st) {
+// rows_live: the live-row count when it runs over the output's rows (forward / dgrad), NULL for a wgrad (its rows are K)
+int combine(const SplitParams& p, const int32_t* rows_live, hipStream_t st) {
     if (p.ksplit == 1) return WF3D_OK;
-    return wf3d_splitk_combine({p.slab, p.C, p.bias, nullptr, nullptr, nullptr, p.M, p.N, p.ldc, 0, 0, 0, 0, p.ksplit, p.accumulate},
-                               false, st);
+    return wf3d_splitk_combine({p.slab, p.C, p.bias, nullptr, nullptr, nullptr, p.M, p.N, p.ldc, 0, 0, 0, 0, p.ksplit, p.accumulate,
+                                rows_live}, false, st);
 }
 
 // products: 3 = bf16x3 (wf3d_gemm_split), 1 = plain bf16 on the hi planes (wf3d_gemm_bf16).  Same checks, same kernel
@@ -1058,9 +1081,11 @@ int gemm_split_impl(const char* fn, int products, const void* A_sx8, const void*
     if (kernel == 1 || K % SBK != 0) {
         const int ktotal = wf3d_cdiv(K, SBK);
         const SplitK s = wf3d_splitk_fit(plan_regs(M, N, K), ktotal, M, N, ws, ws_bytes);
-        return wf3d_gemm_split_regs(products, A_sx8, B_sx8, C, bias, M, N, K, lda, ldb, ldc, accumulate, s, (float*)ws, st);
+        return wf3d_gemm_split_regs(products, A_sx8, B_sx8, C, bias, M, N, K, lda, ldb, ldc, accumulate, s, (float*)ws,
+                                    wf3d_live_rows(), st);
     }
     SplitParams p{};
+    p.live = wf3d_live_rows();
     p.A = (const float*)A_sx8; p.B = (const float*)B_sx8; p.C = C; p.bias = bias;
     p.M = M; p.N = N; p.K = K; p.lda = lda; p.ldb = ldb; p.ldc = ldc; p.accumulate = accumulate;
     const int variant = split_variant(M, N, kernel);
@@ -1082,7 +1107,7 @@ int gemm_split_impl(const char* fn, int products, const void* A_sx8, const void*
     if (products == 1) launch_split_dma<1>(p, variant, persist, cus, st);
     else               launch_split_dma<3>(p, variant, persist, cus, st);
     WF3D_LAUNCH_CHECK();
-    return combine(p, st);
+    return combine(p, p.live, st);
 }
 
 int gemm_split_tn_impl(const char* fn, int products, const void* A_sx8, const void* B_sx8, float* C, int Mo, int No, int K,
@@ -1101,11 +1126,12 @@ int gemm_split_tn_impl(const char* fn, int products, const void* A_sx8, const vo
     p.ksplit = s.ksplit; p.kt_per_split = s.kt_per;
     p.slab = p.ksplit > 1 ? (float*)ws : nullptr;
     p.zmap = big && p.ksplit >= 8 && p.ksplit % 8 == 0;
+    p.live = wf3d_live_rows();
     hipStream_t st = (hipStream_t)stream;
     if (products == 1) launch_split_tn<1>(p, big, st);
     else               launch_split_tn<3>(p, big, st);
     WF3D_LAUNCH_CHECK();
-    return combine(p, st);
+    return combine(p, nullptr, st);
 }
 
 }  // namespace

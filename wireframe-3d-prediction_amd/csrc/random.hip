@@ -5,6 +5,8 @@
 //                                per-site derivation of EdgeFn.forward; then counter += 1
 //   wf3d_set_dropout_seed_words  while non-NULL, the drop_seed of every mask launch on this thread is an index into
 //                                these words, loaded by the kernel itself (wf3d_seed_t, wf3d_common.h)
+//   wf3d_set_live_rows           while non-NULL, the edge-row launches on this thread stop at the 256-row boundary above
+//                                the int32 this points to (wf3d_live_extent, wf3d_common.h)
 #include "wf3d_common.h"
 
 static thread_local const uint32_t* g_seed_words = nullptr;
@@ -15,6 +17,17 @@ wf3d_seed_t wf3d_seed_arg(float drop_p, uint32_t drop_seed) {
 
 extern "C" int wf3d_set_dropout_seed_words(const uint32_t* words) {
     g_seed_words = words;
+    return WF3D_OK;
+}
+
+// The live-row count of the calling thread (include/wf3d.h, "LIVE ROW COUNT"): a device pointer that is handed to the
+// kernels and never dereferenced on the host.
+static thread_local const int32_t* g_live_rows = nullptr;
+
+const int32_t* wf3d_live_rows() { return g_live_rows; }
+
+extern "C" int wf3d_set_live_rows(const int32_t* rows) {
+    g_live_rows = rows;
     return WF3D_OK;
 }
 

@@ -109,8 +109,12 @@ __global__ __launch_bounds__(256) void ln_act_bwd_kernel(const float* __restrict
                                                           uint32_t thresh, float scale, float* __restrict__ dz,
                                                           float* __restrict__ dz_sx8, float* __restrict__ part,
                                                           const float* __restrict__ x0 = nullptr, int ldx = 0, int kx = 0,
-                                                          const PairSrc ps = PairSrc{}) {
+                                                          const PairSrc ps = PairSrc{},
+                                                          const int32_t* __restrict__ live_rows = nullptr) {
     constexpr int RPI = 4 / WPR;                       // rows per workgroup iteration
+    // Rows at or past Rl (a live-row count's extent; R without one) are neither read nor written.  Which workgroup
+    // owns which row, and so the order of every column sum, stays the host-side R's.
+    const int Rl = wf3d_live_extent(live_rows, R);
     const uint32_t seed = thresh ? wf3d_seed_load(seed_src) : 0u;
     __shared__ float xsum[2][4][2];                    // [parity][wave][s1, s2]
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -158,8 +162,8 @@ __global__ __launch_bounds__(256) void ln_act_bwd_kernel(const float* __restrict
     bool ps_tail = false;           // PAIR: the rows from here on are a padded layout's tail (esample -1): dz = 0
     f32x4 pa[PAIR ? NS : 1];
     if (PAIR) {
-        const int r0 = min(row_of(0), R - 1);
-        ps_s = ps.esample[r0];
+        const int r0 = row_of(0);
+        ps_s = r0 < Rl ? ps.esample[r0] : -1;
         if (ps_s < 0) {
             ps_tail = true;
         } else {
@@ -171,7 +175,7 @@ __global__ __launch_bounds__(256) void ln_act_bwd_kernel(const float* __restrict
         // the row index is the same for every lane of a wave: say so, and the per-row scalars (mu, rs, the K input values)
         // come through the scalar cache in one or two s_load instead of 2 + K vector loads of one address each
         const int row = __builtin_amdgcn_readfirstlane(row_of(it));
-        const bool live = it < iters && row < R;
+        const bool live = it < iters && row < Rl;
         const bool ld = live && !(PAIR && ps_tail);       // a tail row loads nothing: zero dh and pre give dz = 0
         mn = (has_ln && live) ? mu[row] : 0.f;
         rn = (has_ln && live) ? rs[row] : 1.f;
@@ -203,7 +207,7 @@ __global__ __launch_bounds__(256) void ln_act_bwd_kernel(const float* __restrict
 #pragma unroll
             for (int k = 0; k < RPI; ++k) {
                 ++e;
-                if (e >= R || ps_tail) break;
+                if (e >= Rl || ps_tail) break;
                 if (e == ps_eend) {                     // first edge of the next sample that has edges
                     ps_s = ps.esample[e];
                     if (ps_s < 0) { ps_tail = true; break; }
@@ -216,7 +220,8 @@ __global__ __launch_bounds__(256) void ln_act_bwd_kernel(const float* __restrict
     load_row(0);
     for (int it = 0; it < iters; ++it) {
         const int row = row_of(it);
-        const bool live = row < R;
+        if (row - wrow >= Rl) break;                   // rows grow with `it`: nothing live is left (workgroup-uniform)
+        const bool live = row < Rl;
         const float m = mn, r = rn;
         float xk[KX > 0 ? KX : 1];
         if (KX > 0) {
@@ -395,10 +400,10 @@ void launch_finalize(const float* part, int nblk, size_t stride, int D, float* o
 // partial column sums: block (bx, by) sums rows [by*rpb, ...) of columns bx*256..
 __global__ __launch_bounds__(256) void colsum_partial_kernel(const float* __restrict__ x, int R, int D, int ld,
                                                               const float* __restrict__ w, int act, int rpb,
-                                                              float* __restrict__ part) {
+                                                              float* __restrict__ part, const int32_t* __restrict__ live_rows) {
     const int c = blockIdx.x * 256 + threadIdx.x;
     if (c >= D) return;
-    const int r0 = blockIdx.y * rpb, r1 = min(R, r0 + rpb);
+    const int r0 = blockIdx.y * rpb, r1 = min(wf3d_live_extent(live_rows, R), r0 + rpb);
     float s = 0.f;
     for (int r = r0; r < r1; ++r) s += wf3d_act_rt(act, x[(size_t)r * ld + c]) * (w ? w[r] : 1.0f);
     part[(size_t)blockIdx.y * D + c] = s;
@@ -410,8 +415,10 @@ __global__ __launch_bounds__(256) void colsum_partial_kernel(const float* __rest
 template <int LPR>
 __global__ __launch_bounds__(256) void rowdot_act_kernel(const float* __restrict__ z, int R, int D,
                                                           const float* __restrict__ w, const float* __restrict__ bias,
-                                                          int act, float* __restrict__ out) {
+                                                          int act, float* __restrict__ out,
+                                                          const int32_t* __restrict__ live_rows) {
     constexpr int RPW = 64 / LPR;
+    R = wf3d_live_extent(live_rows, R);
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int sub = lane % LPR, rsub = lane / LPR;
     const int row = (blockIdx.x * 4 + wave) * RPW + rsub;
@@ -436,8 +443,9 @@ template <int LPR>
 __global__ __launch_bounds__(256) void rowdot_act_bwd_kernel(const float* __restrict__ z, const float* __restrict__ t,
                                                               int R, int D, const float* __restrict__ w, int act,
                                                               float* __restrict__ dz, float* __restrict__ dz_sx8,
-                                                              float* __restrict__ part) {
+                                                              float* __restrict__ part, const int32_t* __restrict__ live_rows) {
     constexpr int RPW = 64 / LPR;
+    R = wf3d_live_extent(live_rows, R);                 // the row loop below strides by the grid, not by R
     __shared__ float red[4 * RPW][2][LPR * 8];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int sub = lane % LPR, rsub = lane / LPR;
@@ -570,7 +578,8 @@ extern "C" int wf3d_ln_act_bwd(const float* dh, const float* z, int R, int D, co
     const int ns = wf3d_cdiv(slice_cols(D, wpr), 256);
 #define WF3D_BWD(NS_, WPR_)                                                                                       \
     hipLaunchKernelGGL((ln_act_bwd_kernel<NS_, WPR_>), dim3(nblk), dim3(256), lds, st, dh, z, R, D, mu, rs, gamma, \
-                       beta, act, wf3d_seed_arg(drop_p, drop_seed), thresh, scale, dz, (float*)dz_sx8, part)
+                       beta, act, wf3d_seed_arg(drop_p, drop_seed), thresh, scale, dz, (float*)dz_sx8, part, nullptr, 0, 0, \
+                       PairSrc{}, wf3d_live_rows())
     if (wpr == 4) { if (ns <= 1) WF3D_BWD(1, 4); else if (ns <= 2) WF3D_BWD(2, 4); else WF3D_BWD(4, 4); }
     else if (wpr == 2) WF3D_BWD(1, 2);
     else WF3D_BWD(1, 1);
@@ -658,7 +667,8 @@ extern "C" int wf3d_ln_act_bwd_wsum(const float* dh, const float* z, const float
     const int ns = wf3d_cdiv(slice_cols(D, wpr), 256);
 #define WF3D_BWDW(NS_, WPR_)                                                                                             \
     hipLaunchKernelGGL((ln_act_bwd_kernel<NS_, WPR_, 1>), dim3(nblk), dim3(256), lds, st, dh, z, R, D, mu, rs, gamma, beta, \
-                       act, wf3d_seed_arg(drop_p, drop_seed), thresh, scale, dz, (float*)dz_sx8, part, wrow, 1, 1)
+                       act, wf3d_seed_arg(drop_p, drop_seed), thresh, scale, dz, (float*)dz_sx8, part, wrow, 1, 1, \
+                       PairSrc{}, wf3d_live_rows())
     if (wpr == 4) { if (ns <= 1) WF3D_BWDW(1, 4); else if (ns <= 2) WF3D_BWDW(2, 4); else WF3D_BWDW(4, 4); }
     else if (wpr == 2) WF3D_BWDW(1, 2);
     else WF3D_BWDW(1, 1);
@@ -695,7 +705,8 @@ extern "C" int wf3d_edge_pair_ln_bwd(const float* dh, const float* Pa, const flo
     const int wpr = H > 512 ? 4 : (H > 256 ? 2 : 1);
 #define WF3D_BWDP(NS_, WPR_)                                                                                                \
     hipLaunchKernelGGL((ln_act_bwd_kernel<NS_, WPR_, 1, true>), dim3(nblk), dim3(256), lds, st, dh, nullptr, Re, H, mu, rs, gamma, \
-                       beta, act, wf3d_seed_arg(drop_p, drop_seed), thresh, scale, dz, nullptr, part, delta, 1, 1, ps)
+                       beta, act, wf3d_seed_arg(drop_p, drop_seed), thresh, scale, dz, nullptr, part, delta, 1, 1, ps, \
+                       wf3d_live_rows())
     if (wpr == 4) WF3D_BWDP(1, 4); else if (wpr == 2) WF3D_BWDP(1, 2); else WF3D_BWDP(1, 1);
 #undef WF3D_BWDP
     WF3D_LAUNCH_CHECK();
@@ -717,8 +728,9 @@ extern "C" int wf3d_rowdot_act(const float* z, int R, int D, const float* w, con
     if (R == 0) return WF3D_OK;
     WF3D_CHECK(z && w && out && ((uintptr_t)z % 16 == 0) && ((uintptr_t)w % 16 == 0), WF3D_ERR_ARG, "wf3d_rowdot_act: null or misaligned pointer");
     hipStream_t st = (hipStream_t)stream;
+    const int32_t* live = wf3d_live_rows();
     const int lpr = D / 8;
-#define WF3D_RD(L_) hipLaunchKernelGGL((rowdot_act_kernel<L_>), dim3(wf3d_cdiv(R, 4 * (64 / L_))), dim3(256), 0, st, z, R, D, w, bias, act, out)
+#define WF3D_RD(L_) hipLaunchKernelGGL((rowdot_act_kernel<L_>), dim3(wf3d_cdiv(R, 4 * (64 / L_))), dim3(256), 0, st, z, R, D, w, bias, act, out, live)
     switch (lpr) { case 1: WF3D_RD(1); break; case 2: WF3D_RD(2); break; case 4: WF3D_RD(4); break; case 8: WF3D_RD(8); break;
                    case 16: WF3D_RD(16); break; case 32: WF3D_RD(32); break; default: WF3D_RD(64); break; }
 #undef WF3D_RD
@@ -743,7 +755,7 @@ extern "C" int wf3d_rowdot_act_bwd(const float* z, const float* dlogit, int R, i
     WF3D_CHECK(ws && ws_bytes >= (size_t)nblk * 2 * D * sizeof(float), WF3D_ERR_WS, "wf3d_rowdot_act_bwd: workspace too small");
     hipStream_t st = (hipStream_t)stream;
     float* part = (float*)ws;
-#define WF3D_RB(L_) hipLaunchKernelGGL((rowdot_act_bwd_kernel<L_>), dim3(nblk), dim3(256), 0, st, z, dlogit, R, D, w, act, dz, (float*)dz_sx8, part)
+#define WF3D_RB(L_) hipLaunchKernelGGL((rowdot_act_bwd_kernel<L_>), dim3(nblk), dim3(256), 0, st, z, dlogit, R, D, w, act, dz, (float*)dz_sx8, part, wf3d_live_rows())
     switch (lpr) { case 1: WF3D_RB(1); break; case 2: WF3D_RB(2); break; case 4: WF3D_RB(4); break; case 8: WF3D_RB(8); break;
                    case 16: WF3D_RB(16); break; case 32: WF3D_RB(32); break; default: WF3D_RB(64); break; }
 #undef WF3D_RB
@@ -768,7 +780,7 @@ extern "C" int wf3d_colsum(const float* x, int R, int D, int ld, const float* w,
     WF3D_CHECK(ws && ws_bytes >= (size_t)nrb * D * sizeof(float), WF3D_ERR_WS, "wf3d_colsum: workspace too small");
     const int rpb = wf3d_cdiv(R, nrb);
     float* part = (float*)ws;
-    hipLaunchKernelGGL(colsum_partial_kernel, dim3(wf3d_cdiv(D, 256), nrb), dim3(256), 0, st, x, R, D, ld, w, act, rpb, part);
+    hipLaunchKernelGGL(colsum_partial_kernel, dim3(wf3d_cdiv(D, 256), nrb), dim3(256), 0, st, x, R, D, ld, w, act, rpb, part, wf3d_live_rows());
     WF3D_LAUNCH_CHECK();
     launch_finalize(part, wf3d_cdiv(R, rpb), (size_t)D, D, out, st);
     WF3D_LAUNCH_CHECK();

@@ -25,8 +25,8 @@ __device__ __forceinline__ void store_sx8(float* dst, const float (&v)[8]) {
 
 // out_sx8[r, c] = in[r*rs + c*cs]   (cs == 1: plain copy-convert; rs == 1: transpose)
 __global__ __launch_bounds__(256) void split_rows_kernel(const float* __restrict__ in, long rs, long cs, int R, int C,
-                                                          float* __restrict__ out) {
-    const long groups = (long)R * (C / 8);
+                                                          float* __restrict__ out, const int32_t* __restrict__ live_rows) {
+    const long groups = (long)wf3d_live_extent(live_rows, R) * (C / 8);     // rows past a live-row count's extent: untouched
     for (long idx = (long)blockIdx.x * 256 + threadIdx.x; idx < groups; idx += (long)gridDim.x * 256) {
         const int r = (int)(idx / (C / 8)), g = (int)(idx % (C / 8));
         const float* p = in + (long)r * rs + (long)g * 8 * cs;
@@ -119,8 +119,10 @@ __global__ __launch_bounds__(256) void ln_prep_kernel(const float* __restrict__ 
                                                        const float* __restrict__ gamma, const float* __restrict__ beta,
                                                        int act, float eps, const wf3d_seed_t seed_src, uint32_t thresh, float dscale,
                                                        float* __restrict__ mu, float* __restrict__ rs,
-                                                       float* __restrict__ h_sx8) {
+                                                       float* __restrict__ h_sx8, const int32_t* __restrict__ live_rows) {
     const uint32_t seed = thresh ? wf3d_seed_load(seed_src) : 0u;
+    R = wf3d_live_extent(live_rows, R);                 // the row walk strides by the grid: rows past the extent are not touched
+    if (R == 0) return;
     // persistent: a lane group walks rows first, first + step, ... with its slice of gamma / beta in registers and
     // the next row's z already requested while this row is reduced, normalised and stored.
     // Columns of a lane: two chunks of four per slot, CH columns apart — lane l owns [s*SPAN + 4l, +4) and
@@ -320,13 +322,18 @@ __global__ __launch_bounds__(256) void first_layer_kernel(const float* __restric
 // fp32 reads (256 B per 16 lanes) and the sx8 writes (128 B per 4 lanes) are coalesced.
 // pro = optional act(LN-affine(.)) with per-row (mu, rs) and per-column (gamma, beta):
 // this is how the wgrad operands h^T and dz^T (k = point index contiguous) are produced.
+// Under a live-row count no input row at or past its extent Rl is read (nor its mu / rs), and the output columns
+// [Rl, R) — the reduction dimension of the NT GEMM that consumes the transposed operands — are written as exact zeros:
+// that GEMM runs without a count and adds exact zeros for them, in its unchanged split-K order.
 __global__ __launch_bounds__(256) void split_transpose_kernel(const float* __restrict__ in, int R, int C, int ld,
                                                                const float* __restrict__ mu, const float* __restrict__ rs,
                                                                const float* __restrict__ gamma,
                                                                const float* __restrict__ beta, int act,
                                                                const wf3d_seed_t seed_src, uint32_t thresh, float dscale,
-                                                               int in_sx8, float* __restrict__ out) {
+                                                               int in_sx8, float* __restrict__ out,
+                                                               const int32_t* __restrict__ live_rows) {
     const uint32_t seed = thresh ? wf3d_seed_load(seed_src) : 0u;
+    const int Rl = wf3d_live_extent(live_rows, R);
     __shared__ float tile[64][65];
     const int r0 = blockIdx.y * 64, c0 = blockIdx.x * 64;
     const int t = threadIdx.x;
@@ -337,7 +344,7 @@ __global__ __launch_bounds__(256) void split_transpose_kernel(const float* __res
         for (int i = 0; i < 2; ++i) {
             const int rr = (t >> 3) + 32 * i;
             float v[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-            if (r0 + rr < R && c0 + g * 8 < C) {
+            if (r0 + rr < Rl && c0 + g * 8 < C) {
                 const float* p = in + (size_t)(r0 + rr) * ld + c0 + g * 8;
                 const bf16x8 hi = __builtin_bit_cast(bf16x8, *reinterpret_cast<const f32x4*>(p));
                 const bf16x8 lo = __builtin_bit_cast(bf16x8, *reinterpret_cast<const f32x4*>(p + 4));
@@ -355,7 +362,7 @@ __global__ __launch_bounds__(256) void split_transpose_kernel(const float* __res
         for (int i = 0; i < 4; ++i) {
             const int rr = (t >> 4) + 16 * i;
             f32x4 v = {0.f, 0.f, 0.f, 0.f};
-            if (r0 + rr < R && c0 + cc < C) {
+            if (r0 + rr < Rl && c0 + cc < C) {
                 v = *reinterpret_cast<const f32x4*>(in + (size_t)(r0 + rr) * ld + c0 + cc);
                 if (mu) {
                     const float m = mu[r0 + rr], s = rs[r0 + rr];
@@ -402,7 +409,7 @@ extern "C" int wf3d_split_rows(const float* in, long row_stride, long col_stride
     long blocks = (groups + 255) / 256;
     if (blocks > 8192) blocks = 8192;
     hipLaunchKernelGGL(split_rows_kernel, dim3((int)blocks), dim3(256), 0, (hipStream_t)stream, in, row_stride,
-                       col_stride, R, C, (float*)out_sx8);
+                       col_stride, R, C, (float*)out_sx8, wf3d_live_rows());
     WF3D_LAUNCH_CHECK();
     return WF3D_OK;
 }
@@ -443,6 +450,7 @@ extern "C" int wf3d_ln_prep(const float* z, int R, int D, const float* gamma, co
     const int ns = wf3d_cdiv(D, 512);
     hipStream_t st = (hipStream_t)stream;
     const wf3d_seed_t seed = wf3d_seed_arg(drop_p, drop_seed);
+    const int32_t* live = wf3d_live_rows();
     // persistent grid: a few workgroups per CU
     const int rpb = D <= 256 ? 8 : 4;
     int blocks = wf3d_cdiv(R, rpb);
@@ -450,13 +458,13 @@ extern "C" int wf3d_ln_prep(const float* z, int R, int D, const float* gamma, co
 #define WF3D_LP(NS_)                                                                                              \
     if (D == NS_ * 512)                                                                                           \
         hipLaunchKernelGGL((ln_prep_kernel<NS_, 64, true>), dim3(blocks), dim3(256), 0, st, z, R, D, gamma, beta, act, eps, \
-                           seed, thresh, dscale, mu, rs, (float*)h_sx8);                                      \
+                           seed, thresh, dscale, mu, rs, (float*)h_sx8, live);                                \
     else                                                                                                          \
         hipLaunchKernelGGL((ln_prep_kernel<NS_>), dim3(blocks), dim3(256), 0, st, z, R, D, gamma, beta, act, eps, \
-                           seed, thresh, dscale, mu, rs, (float*)h_sx8)
+                           seed, thresh, dscale, mu, rs, (float*)h_sx8, live)
     if (D <= 256)      // two rows per wave
         hipLaunchKernelGGL((ln_prep_kernel<1, 32>), dim3(blocks), dim3(256), 0, st, z, R, D, gamma, beta, act, eps,
-                           seed, thresh, dscale, mu, rs, (float*)h_sx8);
+                           seed, thresh, dscale, mu, rs, (float*)h_sx8, live);
     else if (ns <= 1) { WF3D_LP(1); } else if (ns <= 2) { WF3D_LP(2); } else if (ns <= 4) { WF3D_LP(4); } else { WF3D_LP(8); }
 #undef WF3D_LP
     WF3D_LAUNCH_CHECK();
@@ -512,7 +520,7 @@ extern "C" int wf3d_split_transpose(const float* in, int R, int C, int ld, const
     WF3D_CHECK(wf3d_cdiv(R, 64) <= 65535, WF3D_ERR_UNSUPPORTED, "wf3d_split_transpose: too many rows");
     hipLaunchKernelGGL(split_transpose_kernel, dim3(wf3d_cdiv(C, 64), wf3d_cdiv(R, 64)), dim3(256), 0,
                        (hipStream_t)stream, in, R, C, ld, mu, rs, gamma, beta, act, wf3d_seed_arg(drop_p, drop_seed), thresh, dscale, in_sx8,
-                       (float*)out_sx8);
+                       (float*)out_sx8, wf3d_live_rows());
     WF3D_LAUNCH_CHECK();
     return WF3D_OK;
 }

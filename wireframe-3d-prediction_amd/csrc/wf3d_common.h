@@ -44,6 +44,11 @@ struct wf3d_seed_t { uint32_t v; const uint32_t* words; };
 // the seed argument of a launch that drops with probability drop_p (no words are read when nothing is dropped)
 WF3D_INTERNAL wf3d_seed_t wf3d_seed_arg(float drop_p, uint32_t drop_seed);
 
+// ---- live-row count (host + device) -------------------------------------------
+// While the calling thread has set one (wf3d_set_live_rows), the entry points that include/wf3d.h lists under "LIVE ROW
+// COUNT" hand this pointer to their kernels, which read it once at entry; every other entry point never asks for it.
+WF3D_INTERNAL const int32_t* wf3d_live_rows();
+
 // ---- split-K (host) --------------------------------------------------------
 // A GEMM whose output has too few tiles to fill the chip cuts its reduction into `ksplit` ranges of `kt_per` K slices;
 // each range writes a slab of M x N partial sums into the caller's workspace and wf3d_splitk_combine folds them.  One
@@ -106,6 +111,7 @@ static inline SplitK wf3d_splitk_fit(SplitK s, int ktotal, int M, int N, const v
 struct SplitKCombine {
     const float* slab; float* C; const float* bias; const float* addend; const float* lr_u; const float* lr_v;
     int M, N, ldc, ld_addend, lr_k, ld_lr_u, ld_lr_v, ksplit, accumulate;
+    const int32_t* live;      // live-row count over the M rows (NULL: all of them); rows past the extent are not touched
 };
 WF3D_INTERNAL int wf3d_splitk_combine(const SplitKCombine& c, bool narrow_only, hipStream_t st);
 
@@ -114,7 +120,7 @@ WF3D_INTERNAL int wf3d_splitk_combine(const SplitKCombine& c, bool narrow_only, 
 // slab.
 WF3D_INTERNAL int wf3d_gemm_split_regs(int products, const void* A_sx8, const void* B_sx8, float* C, const float* bias,
                                        int M, int N, int K, int lda, int ldb, int ldc, int accumulate, SplitK s,
-                                       float* slab, hipStream_t st);
+                                       float* slab, const int32_t* live, hipStream_t st);
 
 // internal: MFMA attention for head_dim 64 (attn_mfma.hip)
 extern "C" WF3D_INTERNAL int wf3d_attn_fwd_mfma(const float* qkv, const int32_t* voff, int S, int vmax, int E, int heads, float drop_p,
@@ -125,6 +131,15 @@ extern "C" WF3D_INTERNAL int wf3d_attn_bwd_mfma(const float* qkv, const float* d
 
 // ---- device helpers --------------------------------------------------------
 #ifdef __HIPCC__
+// Row extent of a launch under a live-row count: R itself without one, else R256 = min(R, 256 * ceil(clamp(*live, 0, R)
+// / 256)).  One wave-uniform load at kernel entry; every tile height and K slice of the kernels divides 256, so no
+// kernel meets a partial tile at the extent.
+__device__ __forceinline__ int wf3d_live_extent(const int32_t* live, int R) {
+    if (live == nullptr) return R;
+    const int n = min(max(*live, 0), R);
+    return (int)min((long)R, ((long)n + 255) / 256 * 256);
+}
+
 // erf in fp32 to ~1 ulp, branch-free: both polynomial pieces (N. Juffa's minimax coefficients: |x| <= 0.9277 odd
 // polynomial in x; beyond, 1 - exp(-|x| * P(|x|))) are evaluated and selected — 21 VALU operations against the ~42 of
 // the library erff, whose two paths a wave with mixed arguments both walks anyway.  The edge head evaluates GELU or its

@@ -90,20 +90,27 @@ class EdgePredictor(nn.Module):
             seed = int(torch.empty((), dtype=torch.int64).random_().item())
         return ps, seed
 
-    def forward_padded(self, vertices, counts, return_layout=False):
+    def forward_padded(self, vertices, counts, return_layout=False, tail="compute"):
         """vertices [B, V, 3]; counts: integer tensor [B] on the device, never read on the host.  Sample s uses its
         first c_s vertices, c_s clamped like `vertices[s, :counts[s]]` slicing.  Returns [B, V(V-1)/2]: sample s's first
         c_s(c_s-1)/2 entries in the reference's pair order, exactly 0.0 after, so that out[:, :max_s E_s] is what
         forward_ragged returns.  The row layout is built on the device in this call (capturable); the edge rows run at
         their worst case, counts = V.  A sample with fewer than 2 vertices gets an all-zero row (forward_ragged raises
         the reference's IndexError; that would need a host read here).
-        return_layout=True: also return the clamped counts (int64 [B]) and the edge width max_s E_s (0-d int64)."""
+        return_layout=True: also return the clamped counts (int64 [B]) and the edge width max_s E_s (0-d int64).
+        tail="skip": the edge-row launches read the live pair total from device memory when they run and stop at the
+        256-row boundary above it instead of running all B*V(V-1)/2 rows; the output and every gradient are bit-identical
+        to tail="compute".  It applies where the edge MLP runs on the split route (precision "bf16x3" / "bf16", enough
+        rows, a row total B*V(V-1)/2 that is a multiple of 8, a logits layer the row-dot kernel takes, as the default
+        hidden_dim = 512); elsewhere the tail is computed."""
+        if tail not in ("compute", "skip"):
+            raise ValueError("forward_padded: tail must be 'compute' or 'skip'")
         B, V, _ = vertices.shape
         if not torch.is_tensor(counts) or counts.dim() != 1 or counts.shape[0] != B:
             raise ValueError(f"forward_padded: counts must be a 1-D tensor of {B} counts")
         if counts.dtype.is_floating_point or counts.dtype.is_complex:
             raise ValueError("forward_padded: counts must be integers")
-        meta = ops.EdgeMeta.device(counts.to(device=vertices.device, dtype=torch.int64).contiguous(), B, V)
+        meta = ops.EdgeMeta.device(counts.to(device=vertices.device, dtype=torch.int64).contiguous(), B, V, tail=tail)
         ps, seed = self._dropout(vertices.device)
         probs = EdgeFn.apply(vertices.float(), meta, self._heads, ps, seed, config.precision(), *self._param_list())
         return (probs, meta.counts, meta.width) if return_layout else probs

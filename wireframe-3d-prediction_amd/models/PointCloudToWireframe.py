@@ -23,6 +23,7 @@ class PointCloudToWireframe(nn.Module):
         self.edge_predictor = EdgePredictor(vertex_dim=3)
         self._count_cache = (None, -1, None)         # (the tensor object itself, its _version, host ints)
         self._edge_layout = "ragged"                 # set_edge_layout
+        self._edge_tail = "compute"
 
     def set_dropout(self, p):
         """Set every dropout probability of the edge head (the only non-zero ones)."""
@@ -48,7 +49,7 @@ class PointCloudToWireframe(nn.Module):
         self._count_cache = (t, t._version, vals)
         return vals
 
-    def set_edge_layout(self, layout):
+    def set_edge_layout(self, layout, tail=None):
         """"ragged" (default): the edge head's row layout is built from the counts read on the host — the output is the
         reference's exactly.  "padded": the counts stay on the device (target counts in train mode, actual_vertex_counts
         otherwise) and the layout is built there, so that a forward (and a training step) can be captured once and
@@ -56,10 +57,18 @@ class PointCloudToWireframe(nn.Module):
         first `edge_width` columns are the ragged output), `edge_indices` is a read-only sequence that reads the counts
         on first access, and two keys are added: `edge_counts` (int64 [B], the clamped counts used) and `edge_width`
         (0-d int64 tensor, max_s E_s).  A sample with fewer than 2 vertices gets an all-zero row instead of the
-        reference's IndexError."""
+        reference's IndexError.
+        tail (padded only): "compute" (default) runs every edge-row launch over all B*V(V-1)/2 rows; "skip" lets them
+        stop at the live pair total, read from device memory by the kernels (EdgePredictor.forward_padded): same
+        outputs and gradients bit for bit, less work when the counts are below max_vertices."""
         if layout not in ("ragged", "padded"):
             raise ValueError("edge layout must be 'ragged' or 'padded'")
+        if tail is not None and layout != "padded":
+            raise ValueError("tail applies to the 'padded' edge layout only")
+        if tail not in (None, "compute", "skip"):
+            raise ValueError("edge tail must be 'compute' or 'skip'")
         self._edge_layout = layout
+        self._edge_tail = tail or "compute"
         return self
 
     def _forward_padded(self, g, vo, target_vertex_counts):
@@ -73,7 +82,8 @@ class PointCloudToWireframe(nn.Module):
             counts = tc[:b]
         else:
             counts = vo["actual_vertex_counts"]
-        probs, ecounts, width = self.edge_predictor.forward_padded(verts, counts, return_layout=True)
+        probs, ecounts, width = self.edge_predictor.forward_padded(verts, counts, return_layout=True,
+                                                                     tail=getattr(self, "_edge_tail", "compute"))
         return {"vertices": verts,
                 "existence_probabilities": vo["existence_probabilities"],
                 "edge_probs": probs,

@@ -185,6 +185,7 @@ SIGNATURES = {
                                         ctypes.c_double, c_void_p, c_size_t, c_void_p, c_void_p]),
     "wf3d_dropout_draw": (c_int, [c_void_p, c_void_p, c_void_p]),
     "wf3d_set_dropout_seed_words": (c_int, [c_void_p]),
+    "wf3d_set_live_rows": (c_int, [c_void_p]),
     "wf3d_cloud_normalize": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     "wf3d_cloud_sample": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
     "wf3d_meter_update": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, ctypes.c_long, c_void_p, ctypes.c_long, c_void_p,

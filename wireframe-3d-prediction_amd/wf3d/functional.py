@@ -168,6 +168,19 @@ def _edge_routes(Re, H, precision, x3):
     return Route("split", wgrad(H // 2, H), "split", x3), Route("split", wgrad(H // 4, H // 2), "split", x3)
 
 
+def _edge_live(meta, routes, fused_tail):
+    """The live-row count the edge-row section of EdgeFn runs under, or None.  It is used for a padded layout in
+    tail="skip" mode whose two wide Linears run split, forward and dgrad, with their wgrads on sx8 operands (the TN
+    kernels or the "transposes" form), and whose logits layer is the row-dot kernel (fused_tail).  Every launch of the
+    section then honours the count (include/wf3d.h, "LIVE ROW COUNT"): rows past its extent are never written and
+    never read.  Any other route (fp32 precision, too few rows, an fp32 wgrad: a row total that is not a multiple of 8)
+    computes the tail as tail="compute" does."""
+    if not (meta.padded and meta.tail == "skip"):
+        return None
+    ok = fused_tail and all(r.fwd == "split" and r.dgrad == "split" and r.wgrad in _TN + ("transposes",) for r in routes)
+    return meta.live if ok else None
+
+
 def _wgrad(r, dz, dz_s, h, pro, h_s, products):
     """dW = dz^T · pro(h) by the route's wgrad form: dz (fp32) or dz_s (sx8), whichever the route formed; h the stored
     input with its prologue pro, h_s the forward's sx8 operand pro(h)."""
@@ -176,7 +189,11 @@ def _wgrad(r, dz, dz_s, h, pro, h_s, products):
     if r.wgrad == "tn_t":
         return ops.gemm_split_tn(h_s, dz_s, products=products).t().contiguous()
     if r.wgrad == "transposes":
-        return ops.gemm_split(ops.split_transpose(dz_s, in_sx8=True), ops.split_transpose(h, pro), products=products)
+        # under a live-row count the transposes read no tail row and zero their tail columns; those columns are the
+        # GEMM's reduction dimension, not its rows, so the GEMM runs without the count and adds exact zeros for them
+        dz_t, h_t = ops.split_transpose(dz_s, in_sx8=True), ops.split_transpose(h, pro)
+        with ops.live_rows(None):
+            return ops.gemm_split(dz_t, h_t, products=products)
     return ops.gemm(dz, h, TN, pro=pro, x3=r.x3)
 
 
@@ -562,33 +579,40 @@ class EdgeFn(torch.autograd.Function):
             ops.gemm(cv, Wd, NT, out=Pb, accumulate=True)
         npr = _SPLIT_PRODUCTS.get(precision, 3)
         routes = _edge_routes(meta.Re, H, precision, x3)
-        if routes[0].fwd == "split":
-            # the pair kernel holds each edge row in registers: it also emits gelu(LN(pre)) as the next GEMM's operand.
-            # `pre` itself (2 KB per edge row) is stored only when something in backward reads it: with the wgrad of the
-            # second edge layer on the transposing-read kernel (operand h1) and the LayerNorm backward rebuilding the
-            # row from Pa / Pb (ops.edge_pair_ln_bwd, H <= 1024), nothing does.
-            keep_pre = routes[0].wgrad not in _TN or H > 1024
-            pre, mu0, rs0, delta, h1 = ops.edge_pair_fwd(Pa, Pb, cv, M0w, meta, ln=(M1g, M1b, ACT_GELU, p1_, sd[2]), keep_pre=keep_pre)
-            (M4s, M4t), (M8s, M8t) = ops.split_weights([M4w, M8w])
-            z2 = ops.gemm_split(h1, M4s, bias=M4b, products=npr)
-            mu2, rs2, h2 = ops.ln_prep(z2, M5g, M5b, ACT_GELU, drop_p=p2_, seed=sd[3])
-            s2 = (mu2, rs2)
-            z3 = ops.gemm_split(h2, M8s, bias=M8b, products=npr)
-        else:
-            pre, mu0, rs0, delta = ops.edge_pair_fwd(Pa, Pb, cv, M0w, meta)
-            h1 = h2 = M4t = M8t = None
-            z2 = ops.gemm(pre, M4w, NT, bias=M4b, pro=Pro(ACT_GELU, mu0, rs0, M1g, M1b, p1_, sd[2]), x3=x3); s2 = ops.row_stats(z2)
-            z3 = ops.gemm(z2, M8w, NT, bias=M8b, pro=Pro(ACT_GELU, s2[0], s2[1], M5g, M5b, p2_, sd[3]), x3=x3)
+        # decided once, here; backward only reads it (and the logits kernel chosen below)
+        rowdot = M10w.shape[0] == 1 and M10w.is_contiguous() and ops.rowdot_act_shape_ok(H // 4)
+        ctx.live = live = _edge_live(meta, routes, rowdot)
+        # the launches over meta.Re edge rows: pair combine, edge_mlp.4 / .8 / .10, sigmoid
+        with ops.live_rows(live):
+            if routes[0].fwd == "split":
+                # the pair kernel holds each edge row in registers: it also emits gelu(LN(pre)) as the next GEMM's operand.
+                # `pre` itself (2 KB per edge row) is stored only when something in backward reads it: with the wgrad of the
+                # second edge layer on the transposing-read kernel (operand h1) and the LayerNorm backward rebuilding the
+                # row from Pa / Pb (ops.edge_pair_ln_bwd, H <= 1024), nothing does.
+                keep_pre = routes[0].wgrad not in _TN or H > 1024
+                pre, mu0, rs0, delta, h1 = ops.edge_pair_fwd(Pa, Pb, cv, M0w, meta, ln=(M1g, M1b, ACT_GELU, p1_, sd[2]), keep_pre=keep_pre)
+                (M4s, M4t), (M8s, M8t) = ops.split_weights([M4w, M8w])
+                z2 = ops.gemm_split(h1, M4s, bias=M4b, products=npr)
+                mu2, rs2, h2 = ops.ln_prep(z2, M5g, M5b, ACT_GELU, drop_p=p2_, seed=sd[3])
+                s2 = (mu2, rs2)
+                z3 = ops.gemm_split(h2, M8s, bias=M8b, products=npr)
+            else:
+                pre, mu0, rs0, delta = ops.edge_pair_fwd(Pa, Pb, cv, M0w, meta)
+                h1 = h2 = M4t = M8t = None
+                z2 = ops.gemm(pre, M4w, NT, bias=M4b, pro=Pro(ACT_GELU, mu0, rs0, M1g, M1b, p1_, sd[2]), x3=x3); s2 = ops.row_stats(z2)
+                z3 = ops.gemm(z2, M8w, NT, bias=M8b, pro=Pro(ACT_GELU, s2[0], s2[1], M5g, M5b, p2_, sd[3]), x3=x3)
+            fused_tail = ops.rowdot_act_ok(z3, M10w)
+            assert fused_tail or live is None           # the count was chosen for the row-dot kernel: no fp32 GEMM under it
+            if fused_tail:
+                logit = ops.rowdot_act(z3, M10w, M10b, ACT_GELU)          # one-output Linear: a row dot product, not a GEMM
+            else:
+                logit = ops.gemm(z3, M10w, NT, bias=M10b, pro=Pro(ACT_GELU))
+            probs = ops.edge_prob_fwd(logit, meta)
         if pre is not None:
             Pa = Pb = None
-        if ops.rowdot_act_ok(z3, M10w):
-            logit = ops.rowdot_act(z3, M10w, M10b, ACT_GELU)          # one-output Linear: a row dot product, not a GEMM
-        else:
-            logit = ops.gemm(z3, M10w, NT, bias=M10b, pro=Pro(ACT_GELU))
-        probs = ops.edge_prob_fwd(logit, meta)
         _keep_params(ctx, params)
         ctx.cfg = (B, V, H, heads, (pf_, pa_, p1_, p2_), sd, meta)
-        ctx.routes, ctx.wT, ctx.x3, ctx.products = routes, (M4t, M8t), x3, npr
+        ctx.routes, ctx.wT, ctx.x3, ctx.products, ctx.fused_tail = routes, (M4t, M8t), x3, npr, fused_tail
         ctx.saved = (cv, za, sa, zb, sb, f, qkv, cx, lse, Fm, pre, mu0, rs0, delta, z2, s2, z3, h1, h2, Pa, Pb)
         ctx.save_for_backward(probs)
         return probs
@@ -612,51 +636,54 @@ class EdgeFn(torch.autograd.Function):
         # weight / bias gradients run beside the dgrad chain while the launches are small enough to share the chip
         # (cfg2, 64.5 k edge rows: +0.7 % on the step; cfg5, 1.04 M rows: -1.3 %, every kernel fills it alone)
         lv = _Leaves(dprobs.device, enable=meta.Re <= (1 << 18))
-        dlogit = ops.edge_prob_bwd(probs, dprobs.contiguous(), meta)                      # [Re,1]
-        G[23] = ops.colsum(dlogit)
-        fused_tail = ops.rowdot_act_ok(z3, M10w)
-        if fused_tail:
-            dh3 = z3            # shape / dtype stand-in: the fused kernel below produces dz3 directly
-        elif M10w.shape[0] == 1:
-            # one-output Linear: dW[c] = sum_r dlogit[r]*gelu(z3[r,c]) is a weighted column sum,
-            # d gelu(z3) = dlogit (outer) W — no 128x128 MFMA tile wasted on a 1-wide problem
-            G[22] = ops.colsum(z3, dlogit.view(-1), ACT_GELU).view(1, -1)
-            dh3 = ops.gemm(dlogit, M10w, NN)
-        else:
-            G[22], dh3 = _lin_bwd(dlogit, z3, M10w, Pro(ACT_GELU))
-        p2 = Pro(ACT_GELU, s2[0], s2[1], M5g, M5b, p2_, sd[3])
-        p1 = Pro(ACT_GELU, mu0, rs0, M1g, M1b, p1_, sd[2])
-        r2, r3 = ctx.routes
+        # the edge-row section: under the live-row count the forward chose (autograd runs this in its own thread, so it is
+        # set again here; the _Leaves side stream runs inside the same thread)
+        with ops.live_rows(ctx.live):
+            dlogit = ops.edge_prob_bwd(probs, dprobs.contiguous(), meta)                      # [Re,1]
+            G[23] = ops.colsum(dlogit)
+            fused_tail = ctx.fused_tail
+            if fused_tail:
+                dh3 = z3            # shape / dtype stand-in: the fused kernel below produces dz3 directly
+            elif M10w.shape[0] == 1:
+                # one-output Linear: dW[c] = sum_r dlogit[r]*gelu(z3[r,c]) is a weighted column sum,
+                # d gelu(z3) = dlogit (outer) W — no 128x128 MFMA tile wasted on a 1-wide problem
+                G[22] = ops.colsum(z3, dlogit.view(-1), ACT_GELU).view(1, -1)
+                dh3 = ops.gemm(dlogit, M10w, NN)
+            else:
+                G[22], dh3 = _lin_bwd(dlogit, z3, M10w, Pro(ACT_GELU))
+            p2 = Pro(ACT_GELU, s2[0], s2[1], M5g, M5b, p2_, sd[3])
+            p1 = Pro(ACT_GELU, mu0, rs0, M1g, M1b, p1_, sd[2])
+            r2, r3 = ctx.routes
 
-        def wgrad(r, dz, dz_s, h, pro, h_s):
-            return lv.run(lambda: _wgrad(r, dz, dz_s, h, pro, h_s, npr), dz_s, dz, h_s if r.wgrad in _TN else h)
-        # edge_mlp.8, then edge_mlp.4: dz in sx8 for split dgrads, in fp32 where a consumer reads it
-        dz3_s = torch.empty_like(dh3) if r3.dgrad == "split" else None            # dz3 has dh3's shape
-        if fused_tail:
-            # logits-layer backward + GELU backward + both column sums in one pass over z3
-            dz3, G[22], G[21] = ops.rowdot_act_bwd(z3, dlogit, M10w, ACT_GELU, want_dz=_dz32(r3), dz_split=dz3_s)
-        else:
-            dz3, _, _, G[21] = ops.ln_act_bwd(dh3, z3, None, None, None, None, ACT_GELU, inplace=True,
-                                              dz_split=dz3_s, want_dz=_dz32(r3))
-        G[20] = wgrad(r3, dz3, dz3_s, z2, p2, h2)
-        dh2 = _dgrad(r3, dz3, dz3_s, M8w, ctx.wT[1], npr)
-        del dz3, dz3_s
-        dz2_s = torch.empty_like(dh2) if r2.dgrad == "split" else None
-        dz2, G[18], G[19], G[17] = ops.ln_act_bwd(dh2, z2, s2[0], s2[1], M5g, M5b, ACT_GELU, p2_, sd[3],
-                                                  inplace=True, dz_split=dz2_s, want_dz=_dz32(r2))
-        G[16] = wgrad(r2, dz2, dz2_s, pre, p1, h1)
-        dh1 = _dgrad(r2, dz2, dz2_s, M4w, ctx.wT[0], npr)
-        del dz2, dz2_s
-        # LN/GELU backward of the first edge layer; the same pass yields the gradient of its distance-weight column
-        if pre is None:
-            dpre, G[14], G[15], wsum = ops.edge_pair_ln_bwd(dh1, Pa, Pb, delta, M0w, meta, mu0, rs0, M1g, M1b, ACT_GELU, p1_, sd[2])
-        else:
-            dpre, G[14], G[15], wsum = ops.ln_act_bwd_wsum(dh1, pre, delta, mu0, rs0, M1g, M1b, ACT_GELU, p1_, sd[2], inplace=True)
-        # split first layer backward
-        vd = cv.shape[1]
-        dW0 = torch.empty_like(M0w)           # every column is written below: Wa | Wb | Wc | Wd | w_delta
-        dW0[:, 2 * H + 2 * vd].copy_(wsum)
-        dPa, dPb, dcv = ops.edge_pair_bwd(dpre, delta, cv, M0w, meta, coord=True)     # dcv includes dPa·Wc + dPb·Wd
+            def wgrad(r, dz, dz_s, h, pro, h_s):
+                return lv.run(lambda: _wgrad(r, dz, dz_s, h, pro, h_s, npr), dz_s, dz, h_s if r.wgrad in _TN else h)
+            # edge_mlp.8, then edge_mlp.4: dz in sx8 for split dgrads, in fp32 where a consumer reads it
+            dz3_s = torch.empty_like(dh3) if r3.dgrad == "split" else None            # dz3 has dh3's shape
+            if fused_tail:
+                # logits-layer backward + GELU backward + both column sums in one pass over z3
+                dz3, G[22], G[21] = ops.rowdot_act_bwd(z3, dlogit, M10w, ACT_GELU, want_dz=_dz32(r3), dz_split=dz3_s)
+            else:
+                dz3, _, _, G[21] = ops.ln_act_bwd(dh3, z3, None, None, None, None, ACT_GELU, inplace=True,
+                                                  dz_split=dz3_s, want_dz=_dz32(r3))
+            G[20] = wgrad(r3, dz3, dz3_s, z2, p2, h2)
+            dh2 = _dgrad(r3, dz3, dz3_s, M8w, ctx.wT[1], npr)
+            del dz3, dz3_s
+            dz2_s = torch.empty_like(dh2) if r2.dgrad == "split" else None
+            dz2, G[18], G[19], G[17] = ops.ln_act_bwd(dh2, z2, s2[0], s2[1], M5g, M5b, ACT_GELU, p2_, sd[3],
+                                                      inplace=True, dz_split=dz2_s, want_dz=_dz32(r2))
+            G[16] = wgrad(r2, dz2, dz2_s, pre, p1, h1)
+            dh1 = _dgrad(r2, dz2, dz2_s, M4w, ctx.wT[0], npr)
+            del dz2, dz2_s
+            # LN/GELU backward of the first edge layer; the same pass yields the gradient of its distance-weight column
+            if pre is None:
+                dpre, G[14], G[15], wsum = ops.edge_pair_ln_bwd(dh1, Pa, Pb, delta, M0w, meta, mu0, rs0, M1g, M1b, ACT_GELU, p1_, sd[2])
+            else:
+                dpre, G[14], G[15], wsum = ops.ln_act_bwd_wsum(dh1, pre, delta, mu0, rs0, M1g, M1b, ACT_GELU, p1_, sd[2], inplace=True)
+            # split first layer backward
+            vd = cv.shape[1]
+            dW0 = torch.empty_like(M0w)           # every column is written below: Wa | Wb | Wc | Wd | w_delta
+            dW0[:, 2 * H + 2 * vd].copy_(wsum)
+            dPa, dPb, dcv = ops.edge_pair_bwd(dpre, delta, cv, M0w, meta, coord=True)     # dcv includes dPa·Wc + dPb·Wd
 
         def first_layer_leaves():
             ops.gemm(dPa, Fm, TN, out=dW0[:, :H], x3=x3)

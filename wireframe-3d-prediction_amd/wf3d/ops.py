@@ -3,7 +3,9 @@ point of include/wf3d.h).  torch is used for device memory and the current
 stream only; every FLOP happens in libwf3d.so.  CPU tensors are rejected —
 there is no fallback path.
 """
+import contextlib
 import ctypes
+import threading
 
 import torch
 
@@ -65,6 +67,34 @@ def _rows2d(t):
     if t.dim() != 2 or (t.shape[1] > 1 and t.stride(1) != 1):
         raise RuntimeError("wf3d: expected a 2-D tensor with unit inner stride")
     return t
+
+
+_tls = threading.local()
+
+
+@contextlib.contextmanager
+def live_rows(rows):
+    """Edge-row launches on this thread inside the block run under a live-row count (wf3d_set_live_rows,
+    include/wf3d.h "LIVE ROW COUNT"): `rows` is a one-element int32 device tensor that the kernels read when they run,
+    so a captured block follows the value of each replay.  rows = None: no count (also inside an outer block, for
+    launches over other rows)."""
+    if rows is not None:
+        _need_cuda(rows)
+        if rows.dtype != torch.int32 or rows.numel() != 1:
+            raise RuntimeError("wf3d.live_rows: needs a one-element int32 device tensor")
+    prev = getattr(_tls, "live", None)
+    ptr = rows.data_ptr() if rows is not None else None
+    if ptr == prev:
+        yield
+        return
+    lib = _lib.load()
+    check(lib.wf3d_set_live_rows(ptr), "set_live_rows")
+    _tls.live = ptr
+    try:
+        yield
+    finally:
+        check(lib.wf3d_set_live_rows(prev), "set_live_rows")
+        _tls.live = prev
 
 
 class Pro:
@@ -233,6 +263,11 @@ def rowdot_act_ok(z, W):
             and bool(_lib.load().wf3d_rowdot_act_ok(z.shape[1])))
 
 
+def rowdot_act_shape_ok(D):
+    """The same width test from the shape alone (before z exists)."""
+    return bool(_lib.load().wf3d_rowdot_act_ok(D))
+
+
 def rowdot_act(z, W, bias, act):
     """[R, 1] = act(z) @ W^T + bias for a one-output Linear W [1, D]."""
     _need_cuda(z, W, bias)
@@ -374,14 +409,20 @@ class EdgeMeta:
 
     Built from host ints (EdgeMeta(counts) / .get), or on the device from an int64 count tensor (EdgeMeta.device):
     then `padded` is True, the host sizes Rv, Re, vmax, max_e are the worst case of the padded width V, the rows past
-    the live totals map to sample -1, and `counts` (clamped) and `width` (max_s E_s) are device tensors."""
+    the live totals map to sample -1, and `counts` (clamped) and `width` (max_s E_s) are device tensors.  `live` is
+    the live edge-row total, a one-element int32 view of eoff[B:] for ops.live_rows; `tail` says what the edge-row
+    launches do with the rows past it: "compute" (all Re rows) or "skip" (EdgeFn runs them under `live`)."""
     _cache = {}
     padded = False
+    live = None
+    tail = "compute"
 
     @classmethod
-    def device(cls, counts, B, V):
+    def device(cls, counts, B, V, tail="compute"):
         """Layout of int64 counts [B] (device memory, never read on the host) for a batch padded to V vertices: one
         launch of wf3d_edge_layout on the current stream, rebuilt on every call (and every replay of a capture)."""
+        if tail not in ("compute", "skip"):
+            raise ValueError("edge tail must be 'compute' or 'skip'")
         _need_cuda(counts)
         if counts.dtype != torch.int64 or counts.shape != (B,) or not counts.is_contiguous():
             raise RuntimeError(f"wf3d.EdgeMeta.device: counts must be a contiguous int64 [{B}] tensor")
@@ -390,11 +431,12 @@ class EdgeMeta:
         if B * E > 0x7FFFFFFF:
             raise RuntimeError(f"wf3d.EdgeMeta.device: B*V(V-1)/2 = {B * E} edge rows do not fit in int32")
         m = cls.__new__(cls)
-        m.padded = True
+        m.padded, m.tail = True, tail
         m.B, m.Rv, m.Re, m.vmax, m.max_e = B, B * V, B * E, V, E
         i32 = dict(dtype=torch.int32, device=dev)
         m.voff, m.eoff = torch.empty(B + 1, **i32), torch.empty(B + 1, **i32)
         m.vsample, m.esample = torch.empty(B * V, **i32), torch.empty(B * E, **i32)
+        m.live = m.eoff[B:]
         m.counts = torch.empty(B, dtype=torch.int64, device=dev)
         m.width = torch.empty((), dtype=torch.int64, device=dev)
         check(_lib.load().wf3d_edge_layout(_p(counts), B, V, _p(m.voff), _p(m.eoff), _p(m.vsample), _p(m.esample),
