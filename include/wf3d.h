@@ -61,6 +61,10 @@ const char* wf3d_last_error(void);
  *       (the three-stage LDS-DMA kernel forward / dgrad, the 256x128 kernel for wf3d_gemm_split_tn); 6 = the 256x256
  *       forward / dgrad kernel on every shape (wgrad keeps its automatic choice).  The workspace queries follow it, so
  *       a workspace sized under one value may be too small under another (the launch then does not split K).
+ *   "attn_tiled" (0, 1 or 2): which head_dim-64 calls of wf3d_attn_fwd / wf3d_attn_bwd run on the key-tiled MFMA
+ *       kernels.  1 = automatic, the default: those with vmax > 256 (smaller ones keep the kernels that hold a whole
+ *       sample in LDS); 0 = never (vmax > 256 then runs on the chunked VALU kernels; for A/B timing and tests);
+ *       2 = every head_dim-64 call whatever vmax (for tests and diagnostics).  wf3d_attn_kernel reports the outcome.
  * Returns WF3D_OK, or WF3D_ERR_ARG for an unknown name or a value out of range. */
 int wf3d_set_option(const char* name, int value);
 
@@ -364,12 +368,18 @@ int wf3d_edge_scatter_dverts(const float* dcv, const int32_t* voff, int B, int V
 /* 8-head self-attention of nn.MultiheadAttention (EdgePredictor.py:41-46,109):
  * qkv[Rv, 3E] packed in_proj output; one workgroup per (head, sample); writes
  * ctx[Rv, E] (heads concatenated, before out_proj) and lse[Rv, heads].  head_dim 64
- * runs QK^T and PV (and the five backward contractions) on fp32 MFMA; backward takes
- * the forward's ctx (delta_i = dctx_i · ctx_i). */
+ * runs QK^T and PV (and the five backward contractions) on fp32 MFMA for any vmax: up
+ * to 256 vertices with the sample's rows resident in LDS, beyond that key-tiled with an
+ * online softmax (one workgroup per head, sample and 128 rows; option "attn_tiled").
+ * Other head widths run on VALU kernels.  Backward takes the forward's ctx
+ * (delta_i = dctx_i · ctx_i); no atomics, so results are bit-reproducible. */
 int wf3d_attn_fwd(const float* qkv, const int32_t* voff, int S, int vmax, int E, int heads, float drop_p,
                   uint32_t drop_seed, float* ctx, float* lse, void* stream);
 int wf3d_attn_bwd(const float* qkv, const float* dctx, const float* ctx, const float* lse, const int32_t* voff,
                   int S, int vmax, int E, int heads, float drop_p, uint32_t drop_seed, float* dqkv, void* stream);
+/* The kernel family that serves such a call under the current options: 0 = VALU, 1 = MFMA with the sample resident in
+ * LDS, 2 = MFMA key-tiled; WF3D_ERR_ARG for dims the entry points refuse.  Host only: no device is touched. */
+int wf3d_attn_kernel(int E, int heads, int vmax);
 
 /* Split first layer of edge_mlp (EdgePredictor.py:122-137):
  * pre[e,:] = Pa[i,:] + Pb[j,:] + |c_i - c_j| * wdelta  for edge e = (i, j), plus

@@ -13,12 +13,27 @@
 // [Rv, *] matrix, so ragged batches cost nothing and no key mask is needed.
 #include "wf3d_common.h"
 
+#include <atomic>
+
 namespace {
 
 constexpr int ATT_WAVES = 4;
 
 // head_dim 64 runs on the matrix cores (attn_mfma.hip), every other one on the VALU kernels below
 bool use_mfma(int E, int heads) { return E / heads == 64; }
+
+// "attn_tiled" (wf3d_set_option): 1 = automatic, 0 = never the key-tiled MFMA kernels, 2 = always for head_dim 64
+std::atomic<int> g_attn_tiled{1};
+
+// which kernels serve a call: 0 = VALU (below), 1 = MFMA with the sample resident in LDS (up to 256 vertices),
+// 2 = MFMA key-tiled (any vertex count)
+int attn_family(int E, int heads, int vmax) {
+    if (!use_mfma(E, heads)) return 0;
+    const int tiled = g_attn_tiled.load(std::memory_order_relaxed);
+    if (tiled == 2) return 2;
+    if (vmax <= 256) return 1;
+    return tiled == 1 ? 2 : 0;
+}
 
 struct AttnParams {
     const float* qkv;      // [Rv, 3E]
@@ -280,13 +295,24 @@ int attn_check(const char* who, int S, int E, int heads, int vmax, bool bwd) {
     const int hd = E / heads;
     WF3D_CHECK(hd % 4 == 0, WF3D_ERR_UNSUPPORTED, "%s: head_dim %d must be a multiple of 4", who, hd);
     WF3D_CHECK(vmax >= 0, WF3D_ERR_ARG, "%s: bad vmax %d", who, vmax);
-    WF3D_CHECK(attn_lds_bytes(vmax, hd, bwd) <= 160 * 1024, WF3D_ERR_UNSUPPORTED,
+    WF3D_CHECK(attn_family(E, heads, vmax) != 0 || attn_lds_bytes(vmax, hd, bwd) <= 160 * 1024, WF3D_ERR_UNSUPPORTED,
                "%s: 256-row chunks of head_dim %d do not fit the 160 KiB LDS", who, hd);
     WF3D_CHECK(S <= 65535, WF3D_ERR_UNSUPPORTED, "%s: more than 65535 samples", who);
     return WF3D_OK;
 }
 
 }  // namespace
+
+int wf3d_attn_set_tiled(int value) {
+    WF3D_CHECK(value >= 0 && value <= 2, WF3D_ERR_ARG, "wf3d_set_option: attn_tiled must be 0, 1 or 2 (got %d)", value);
+    g_attn_tiled.store(value, std::memory_order_relaxed);
+    return WF3D_OK;
+}
+
+extern "C" int wf3d_attn_kernel(int E, int heads, int vmax) {
+    WF3D_CHECK(E > 0 && heads > 0 && E % heads == 0 && vmax >= 0, WF3D_ERR_ARG, "wf3d_attn_kernel: bad dims");
+    return attn_family(E, heads, vmax);
+}
 
 extern "C" int wf3d_attn_fwd(const float* qkv, const int32_t* voff, int S, int vmax, int E, int heads, float drop_p,
                              uint32_t drop_seed, float* ctx, float* lse, void* stream) {
@@ -295,7 +321,9 @@ extern "C" int wf3d_attn_fwd(const float* qkv, const int32_t* voff, int S, int v
     if (S == 0 || vmax == 0) return WF3D_OK;
     WF3D_CHECK(qkv && voff && ctx && lse, WF3D_ERR_ARG, "wf3d_attn_fwd: null pointer");
     WF3D_CHECK(drop_p >= 0.f && drop_p < 1.f, WF3D_ERR_ARG, "wf3d_attn_fwd: bad drop_p");
-    if (use_mfma(E, heads) && vmax <= 256) return wf3d_attn_fwd_mfma(qkv, voff, S, vmax, E, heads, drop_p, drop_seed, ctx, lse, stream);
+    const int family = attn_family(E, heads, vmax);
+    if (family == 1) return wf3d_attn_fwd_mfma(qkv, voff, S, vmax, E, heads, drop_p, drop_seed, ctx, lse, stream);
+    if (family == 2) return wf3d_attn_fwd_tiled(qkv, voff, S, vmax, E, heads, drop_p, drop_seed, ctx, lse, stream);
     AttnParams p{};
     p.qkv = qkv; p.ctx = ctx; p.lse = lse; p.voff = voff;
     p.E = E; p.heads = heads; p.hd = E / heads; p.vmax = vmax; p.ch = attn_chunk(vmax);
@@ -319,8 +347,9 @@ extern "C" int wf3d_attn_bwd(const float* qkv, const float* dctx, const float* c
     if (S == 0 || vmax == 0) return WF3D_OK;
     WF3D_CHECK(qkv && dctx && ctx && lse && voff && dqkv, WF3D_ERR_ARG, "wf3d_attn_bwd: null pointer");
     WF3D_CHECK(drop_p >= 0.f && drop_p < 1.f, WF3D_ERR_ARG, "wf3d_attn_bwd: bad drop_p");
-    if (use_mfma(E, heads) && vmax <= 256)
-        return wf3d_attn_bwd_mfma(qkv, dctx, ctx, lse, voff, S, vmax, E, heads, drop_p, drop_seed, dqkv, stream);
+    const int family = attn_family(E, heads, vmax);
+    if (family == 1) return wf3d_attn_bwd_mfma(qkv, dctx, ctx, lse, voff, S, vmax, E, heads, drop_p, drop_seed, dqkv, stream);
+    if (family == 2) return wf3d_attn_bwd_tiled(qkv, dctx, ctx, lse, voff, S, vmax, E, heads, drop_p, drop_seed, dqkv, stream);
     AttnParams p{};
     p.qkv = qkv; p.dctx = dctx; p.ctx = (float*)ctx; p.lse = (float*)lse; p.dqkv = dqkv; p.voff = voff;
     p.E = E; p.heads = heads; p.hd = E / heads; p.vmax = vmax; p.ch = attn_chunk(vmax);

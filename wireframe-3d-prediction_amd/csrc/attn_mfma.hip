@@ -267,6 +267,249 @@ __global__ __launch_bounds__(256) void attn_bwd_mfma_kernel(const MAttn p) {
     }
 }
 
+// ---- key-tiled ("flash" form) variant: any vertex count --------------------------------------------------------------
+// Same arithmetic and operand orientation as the resident kernels above; what changes is who owns what.  A workgroup is
+// (head, sample, group of 4 row blocks): each wave keeps ONE 32-row block for the whole kernel and the other operand is
+// walked in tiles of KT rows staged in LDS.  KT = 128: two tiles are 2 x 128 x 68 floats = 68 KiB, so two workgroups
+// share a CU's 160 KiB (one stages while the other computes; the kernels fit 256 registers per lane, the two-per-SIMD
+// budget), and a sample of V vertices is ceil(V / 128) workgroups per head instead of one, which is what fills the chip
+// at small batch.  Forward: online softmax, the running maximum m, sum l and the output tile o[2] stay in registers and
+// are rescaled by exp(m_old - m_new) per tile; dropout multiplies what goes into o, never what goes into l, so the
+// result is keep * dscale * softmax as in the resident kernel.  Backward: sweep 1 (dQ) walks K / V tiles, sweep 2
+// (dK, dV) walks tiles of scaled Q and dO with lse and delta_i = dO_i . O_i (recomputed while dO is staged) beside them.
+// Every output row is written by one wave in a fixed tile order: no atomics, bit-reproducible.
+constexpr int KT = 128;
+
+__device__ __forceinline__ void store_tile_row(float* out, const f32x16 (&o)[2], int h, float mul) {
+#pragma unroll
+    for (int dt = 0; dt < 2; ++dt)
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+            f32x4 v = {o[dt][4 * g], o[dt][4 * g + 1], o[dt][4 * g + 2], o[dt][4 * g + 3]};
+            *reinterpret_cast<f32x4*>(out + dt * 32 + 8 * g + 4 * h) = v * mul;
+        }
+}
+
+__global__ __launch_bounds__(256, 2) void attn_fwd_tiled_kernel(const MAttn p) {
+    const uint32_t seed = p.thresh ? wf3d_seed_load(p.seed) : 0u;
+    extern __shared__ __attribute__((aligned(16))) float sm[];
+    const int head = blockIdx.x, s = blockIdx.y, q0 = blockIdx.z * KT;
+    const int r0 = p.voff[s], n = p.voff[s + 1] - r0;
+    if (n <= 0 || q0 >= n) return;
+    const int E3 = 3 * p.E;
+    float* Ks = sm;
+    float* Vs = sm + KT * LDR;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int l31 = lane & 31, h = lane >> 5;
+    const bool live = q0 + wave * 32 < n;                  // a wave past the sample's rows only helps staging
+    const int i = q0 + wave * 32 + l31;                    // this lane's query
+    const bool iok = i < n;
+    float qf[32];
+    load_half_row(qf, p.qkv + (size_t)(r0 + i) * E3 + head * HD + 32 * h, iok, p.scale);
+    float m = -INFINITY, l = 0.f;
+    f32x16 o[2];
+#pragma unroll
+    for (int dt = 0; dt < 2; ++dt)
+#pragma unroll
+        for (int e = 0; e < 16; ++e) o[dt][e] = 0.f;
+    for (int k0 = 0; k0 < n; k0 += KT) {
+        const int tn = min(KT, n - k0), tpad = (tn + 31) & ~31, nt = tpad >> 5;
+        if (k0) __syncthreads();
+        stage64(Ks, p.qkv, E3, r0 + k0, tn, tpad, p.E + head * HD, 1.0f);
+        stage64(Vs, p.qkv, E3, r0 + k0, tn, tpad, 2 * p.E + head * HD, 1.0f);
+        __syncthreads();
+        if (!live) continue;
+        f32x16 st[KT / 32];                                // S^T tiles: rows = keys, column = this lane's query
+        float tm = m;
+#pragma unroll
+        for (int jt = 0; jt < KT / 32; ++jt) {
+            if (jt < nt) {
+                st[jt] = mm_rows_regs(Ks + (jt * 32 + l31) * LDR + 32 * h, qf);
+#pragma unroll
+                for (int e = 0; e < 16; ++e) {
+                    if (k0 + jt * 32 + rowof(e, h) >= n) st[jt][e] = -INFINITY;
+                    tm = fmaxf(tm, st[jt][e]);
+                }
+            }
+        }
+        tm = fmaxf(tm, __shfl_xor(tm, 32, 64));            // finite from the first tile on: key 0 exists
+        const float alpha = expf(m - tm);                  // 0 on the first tile (m = -inf)
+        m = tm;
+        l *= alpha;
+#pragma unroll
+        for (int dt = 0; dt < 2; ++dt)
+#pragma unroll
+            for (int e = 0; e < 16; ++e) o[dt][e] *= alpha;
+#pragma unroll
+        for (int jt = 0; jt < KT / 32; ++jt) {
+            if (jt < nt) {
+#pragma unroll
+                for (int e = 0; e < 16; ++e) {
+                    const int jl = jt * 32 + rowof(e, h);
+                    float pv = expf(st[jt][e] - m);
+                    l += pv;
+                    if (p.thresh) pv = wf3d_keep(seed, (uint32_t)((r0 + i) * p.heads + head), (uint32_t)(k0 + jl), p.thresh) ? pv * p.dscale : 0.f;
+                    const float* vr = Vs + jl * LDR + l31;
+                    o[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(vr[0], pv, o[0], 0, 0, 0);
+                    o[1] = __builtin_amdgcn_mfma_f32_32x32x2f32(vr[32], pv, o[1], 0, 0, 0);
+                }
+            }
+        }
+    }
+    l += __shfl_xor(l, 32, 64);
+    if (iok) {
+        if (h == 0) p.lse[(size_t)(r0 + i) * p.heads + head] = m + logf(l);
+        store_tile_row(p.ctx + (size_t)(r0 + i) * p.E + head * HD, o, h, 1.0f / l);
+    }
+}
+
+// backward sweep 1: a wave owns a query block, K / V are walked in tiles -> dQ
+__global__ __launch_bounds__(256, 2) void attn_bwd_tiled_dq_kernel(const MAttn p) {
+    const uint32_t seed = p.thresh ? wf3d_seed_load(p.seed) : 0u;
+    extern __shared__ __attribute__((aligned(16))) float sm[];
+    const int head = blockIdx.x, s = blockIdx.y, q0 = blockIdx.z * KT;
+    const int r0 = p.voff[s], n = p.voff[s + 1] - r0;
+    if (n <= 0 || q0 >= n) return;
+    const int E3 = 3 * p.E;
+    float* Ks = sm;
+    float* Vs = sm + KT * LDR;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int l31 = lane & 31, h = lane >> 5;
+    const bool live = q0 + wave * 32 < n;
+    const int i = q0 + wave * 32 + l31;
+    const bool iok = i < n;
+    float qf[32], df[32];
+    load_half_row(qf, p.qkv + (size_t)(r0 + i) * E3 + head * HD + 32 * h, iok, p.scale);
+    load_half_row(df, p.dctx + (size_t)(r0 + i) * p.E + head * HD + 32 * h, iok, 1.0f);
+    float delta = 0.f;
+    {
+        const float* op = p.ctx_in + (size_t)(r0 + i) * p.E + head * HD + 32 * h;
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+            f32x4 v = {0.f, 0.f, 0.f, 0.f};
+            if (iok) v = *reinterpret_cast<const f32x4*>(op + 4 * k);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) delta += v[j] * df[4 * k + j];
+        }
+        delta += __shfl_xor(delta, 32, 64);
+    }
+    const float lse_i = iok ? p.lse[(size_t)(r0 + i) * p.heads + head] : INFINITY;
+    f32x16 dq[2];
+#pragma unroll
+    for (int dt = 0; dt < 2; ++dt)
+#pragma unroll
+        for (int e = 0; e < 16; ++e) dq[dt][e] = 0.f;
+    for (int k0 = 0; k0 < n; k0 += KT) {
+        const int tn = min(KT, n - k0), tpad = (tn + 31) & ~31, nt = tpad >> 5;
+        if (k0) __syncthreads();
+        stage64(Ks, p.qkv, E3, r0 + k0, tn, tpad, p.E + head * HD, 1.0f);
+        stage64(Vs, p.qkv, E3, r0 + k0, tn, tpad, 2 * p.E + head * HD, 1.0f);
+        __syncthreads();
+        if (!live) continue;
+        for (int jt = 0; jt < nt; ++jt) {
+            const f32x16 st = mm_rows_regs(Ks + (jt * 32 + l31) * LDR + 32 * h, qf);
+            const f32x16 dp = mm_rows_regs(Vs + (jt * 32 + l31) * LDR + 32 * h, df);
+#pragma unroll
+            for (int e = 0; e < 16; ++e) {
+                const int jl = jt * 32 + rowof(e, h), j = k0 + jl;
+                const float pr = j < n ? expf(st[e] - lse_i) : 0.f;
+                float g = dp[e];
+                if (p.thresh) g = wf3d_keep(seed, (uint32_t)((r0 + i) * p.heads + head), (uint32_t)j, p.thresh) ? g * p.dscale : 0.f;
+                const float ds = pr * (g - delta);
+                const float* kr = Ks + jl * LDR + l31;
+                dq[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(kr[0], ds, dq[0], 0, 0, 0);
+                dq[1] = __builtin_amdgcn_mfma_f32_32x32x2f32(kr[32], ds, dq[1], 0, 0, 0);
+            }
+        }
+    }
+    if (iok) store_tile_row(p.dqkv + (size_t)(r0 + i) * E3 + head * HD, dq, h, p.scale);
+}
+
+// backward sweep 2: a wave owns a key block, scaled Q / dO (+ lse, delta) are walked in tiles -> dK, dV
+__global__ __launch_bounds__(256, 2) void attn_bwd_tiled_dkv_kernel(const MAttn p) {
+    const uint32_t seed = p.thresh ? wf3d_seed_load(p.seed) : 0u;
+    extern __shared__ __attribute__((aligned(16))) float sm[];
+    const int head = blockIdx.x, s = blockIdx.y, j0 = blockIdx.z * KT;
+    const int r0 = p.voff[s], n = p.voff[s + 1] - r0;
+    if (n <= 0 || j0 >= n) return;
+    const int E3 = 3 * p.E;
+    float* Qs = sm;                                        // scaled Q tile
+    float* Gs = sm + KT * LDR;                             // dO tile
+    float* dl = Gs + KT * LDR;                             // [KT] delta_i
+    float* ls = dl + KT;                                   // [KT] lse_i (+inf for padded queries)
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int l31 = lane & 31, h = lane >> 5;
+    const bool live = j0 + wave * 32 < n;
+    const int j = j0 + wave * 32 + l31;                    // this lane's key
+    const bool jok = j < n;
+    float kf[32], vf[32];
+    load_half_row(kf, p.qkv + (size_t)(r0 + j) * E3 + p.E + head * HD + 32 * h, jok, 1.0f);
+    load_half_row(vf, p.qkv + (size_t)(r0 + j) * E3 + 2 * p.E + head * HD + 32 * h, jok, 1.0f);
+    f32x16 dk[2], dv[2];
+#pragma unroll
+    for (int dt = 0; dt < 2; ++dt)
+#pragma unroll
+        for (int e = 0; e < 16; ++e) { dk[dt][e] = 0.f; dv[dt][e] = 0.f; }
+    for (int i0 = 0; i0 < n; i0 += KT) {
+        const int tn = min(KT, n - i0), tpad = (tn + 31) & ~31, nt = tpad >> 5;
+        if (i0) __syncthreads();
+        stage64(Qs, p.qkv, E3, r0 + i0, tn, tpad, head * HD, p.scale);
+        // dO rows, and delta_i from the 16 lanes that hold a row (tpad * 16 is a multiple of the block: no lane idles)
+        for (int idx = threadIdx.x; idx < tpad * 16; idx += blockDim.x) {
+            const int r = idx >> 4, c = (idx & 15) * 4;
+            f32x4 g = {0.f, 0.f, 0.f, 0.f};
+            float d = 0.f;
+            if (r < tn) {
+                const size_t at = (size_t)(r0 + i0 + r) * p.E + head * HD + c;
+                g = *reinterpret_cast<const f32x4*>(p.dctx + at);
+                const f32x4 ov = *reinterpret_cast<const f32x4*>(p.ctx_in + at);
+                d = g[0] * ov[0] + g[1] * ov[1] + g[2] * ov[2] + g[3] * ov[3];
+            }
+            *reinterpret_cast<f32x4*>(Gs + r * LDR + c) = g;
+#pragma unroll
+            for (int x = 8; x > 0; x >>= 1) d += __shfl_xor(d, x, 64);
+            if ((idx & 15) == 0) {
+                dl[r] = d;
+                ls[r] = r < tn ? p.lse[(size_t)(r0 + i0 + r) * p.heads + head] : INFINITY;
+            }
+        }
+        __syncthreads();
+        if (!live) continue;
+        for (int it = 0; it < nt; ++it) {
+            const f32x16 sc = mm_rows_regs(Qs + (it * 32 + l31) * LDR + 32 * h, kf);     // S[i][j], rows = queries
+            const f32x16 dp = mm_rows_regs(Gs + (it * 32 + l31) * LDR + 32 * h, vf);     // dP[i][j]
+#pragma unroll
+            for (int e = 0; e < 16; ++e) {
+                const int il = it * 32 + rowof(e, h);
+                const float pr = expf(sc[e] - ls[il]);                                   // 0 for padded queries
+                float mk = 1.0f;
+                if (p.thresh) mk = wf3d_keep(seed, (uint32_t)((r0 + i0 + il) * p.heads + head), (uint32_t)j, p.thresh) ? p.dscale : 0.f;
+                const float ds = pr * (dp[e] * mk - dl[il]);
+                const float pt = pr * mk;
+                const float* qr = Qs + il * LDR + l31;
+                const float* gr = Gs + il * LDR + l31;
+                dk[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(qr[0], ds, dk[0], 0, 0, 0);
+                dk[1] = __builtin_amdgcn_mfma_f32_32x32x2f32(qr[32], ds, dk[1], 0, 0, 0);
+                dv[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(gr[0], pt, dv[0], 0, 0, 0);
+                dv[1] = __builtin_amdgcn_mfma_f32_32x32x2f32(gr[32], pt, dv[1], 0, 0, 0);
+            }
+        }
+    }
+    if (jok) {
+        store_tile_row(p.dqkv + (size_t)(r0 + j) * E3 + p.E + head * HD, dk, h, 1.0f);
+        store_tile_row(p.dqkv + (size_t)(r0 + j) * E3 + 2 * p.E + head * HD, dv, h, 1.0f);
+    }
+}
+
+template <typename K>
+int launch_tiled(const char* who, K kernel, const MAttn& p, int S, int vmax, size_t lds, void* stream) {
+    hipError_t e = hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    WF3D_CHECK(e == hipSuccess, WF3D_ERR_LAUNCH, "%s: cannot raise dynamic LDS to %zu", who, lds);
+    hipLaunchKernelGGL(kernel, dim3(p.heads, S, wf3d_cdiv(vmax, KT)), dim3(256), lds, (hipStream_t)stream, p);
+    WF3D_LAUNCH_CHECK();
+    return WF3D_OK;
+}
+
 }  // namespace
 
 // internal entry points (dispatched from wf3d_attn_fwd / wf3d_attn_bwd when head_dim == 64)
@@ -303,4 +546,31 @@ extern "C" int wf3d_attn_bwd_mfma(const float* qkv, const float* dctx, const flo
     hipLaunchKernelGGL(attn_bwd_mfma_kernel, dim3(heads, S), dim3(256), lds, (hipStream_t)stream, p);
     WF3D_LAUNCH_CHECK();
     return WF3D_OK;
+}
+
+// key-tiled kernels: any vmax (dispatched from wf3d_attn_fwd / wf3d_attn_bwd, option "attn_tiled")
+extern "C" int wf3d_attn_fwd_tiled(const float* qkv, const int32_t* voff, int S, int vmax, int E, int heads, float drop_p,
+                                   uint32_t drop_seed, float* ctx, float* lse, void* stream) {
+    WF3D_CHECK(wf3d_cdiv(vmax, KT) <= 65535, WF3D_ERR_UNSUPPORTED, "wf3d_attn_fwd: vmax %d too large", vmax);
+    MAttn p{};
+    p.qkv = qkv; p.ctx = ctx; p.lse = lse; p.voff = voff;
+    p.E = E; p.heads = heads; p.vpad = KT;
+    p.scale = 1.0f / sqrtf((float)HD);
+    if (drop_p > 0.f) { p.seed = wf3d_seed_arg(drop_p, drop_seed); p.thresh = (uint32_t)((double)drop_p * 4294967296.0); p.dscale = 1.0f / (1.0f - drop_p); }
+    return launch_tiled("wf3d_attn_fwd", attn_fwd_tiled_kernel, p, S, vmax, (size_t)2 * KT * LDR * sizeof(float), stream);
+}
+
+extern "C" int wf3d_attn_bwd_tiled(const float* qkv, const float* dctx, const float* ctx, const float* lse,
+                                   const int32_t* voff, int S, int vmax, int E, int heads, float drop_p,
+                                   uint32_t drop_seed, float* dqkv, void* stream) {
+    WF3D_CHECK(wf3d_cdiv(vmax, KT) <= 65535, WF3D_ERR_UNSUPPORTED, "wf3d_attn_bwd: vmax %d too large", vmax);
+    MAttn p{};
+    p.qkv = qkv; p.dctx = dctx; p.ctx_in = ctx; p.lse = (float*)lse; p.dqkv = dqkv; p.voff = voff;
+    p.E = E; p.heads = heads; p.vpad = KT;
+    p.scale = 1.0f / sqrtf((float)HD);
+    if (drop_p > 0.f) { p.seed = wf3d_seed_arg(drop_p, drop_seed); p.thresh = (uint32_t)((double)drop_p * 4294967296.0); p.dscale = 1.0f / (1.0f - drop_p); }
+    const size_t tiles = (size_t)2 * KT * LDR * sizeof(float);
+    int rc = launch_tiled("wf3d_attn_bwd", attn_bwd_tiled_dq_kernel, p, S, vmax, tiles, stream);
+    if (rc) return rc;
+    return launch_tiled("wf3d_attn_bwd", attn_bwd_tiled_dkv_kernel, p, S, vmax, tiles + 2 * KT * sizeof(float), stream);
 }

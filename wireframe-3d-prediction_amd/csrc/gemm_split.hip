@@ -1160,6 +1160,7 @@ extern "C" int wf3d_set_option(const char* name, int value) {
         g_split_kernel.store(value, std::memory_order_relaxed);
         return WF3D_OK;
     }
+    if (strcmp(name, "attn_tiled") == 0) return wf3d_attn_set_tiled(value);
     wf3d_set_error("wf3d_set_option: unknown option '%s'", name);
     return WF3D_ERR_ARG;
 }

@@ -129,6 +129,15 @@ extern "C" WF3D_INTERNAL int wf3d_attn_bwd_mfma(const float* qkv, const float* d
                                   const int32_t* voff, int S, int vmax, int E, int heads, float drop_p,
                                   uint32_t drop_seed, float* dqkv, void* stream);
 
+// the same, key-tiled: any vmax (attn_mfma.hip)
+extern "C" WF3D_INTERNAL int wf3d_attn_fwd_tiled(const float* qkv, const int32_t* voff, int S, int vmax, int E, int heads, float drop_p,
+                                   uint32_t drop_seed, float* ctx, float* lse, void* stream);
+extern "C" WF3D_INTERNAL int wf3d_attn_bwd_tiled(const float* qkv, const float* dctx, const float* ctx, const float* lse,
+                                   const int32_t* voff, int S, int vmax, int E, int heads, float drop_p,
+                                   uint32_t drop_seed, float* dqkv, void* stream);
+// the "attn_tiled" value of wf3d_set_option (attn.hip holds it)
+WF3D_INTERNAL int wf3d_attn_set_tiled(int value);
+
 // ---- device helpers --------------------------------------------------------
 #ifdef __HIPCC__
 // Row extent of a launch under a live-row count: R itself without one, else R256 = min(R, 256 * ceil(clamp(*live, 0, R)

@@ -143,6 +143,7 @@ SIGNATURES = {
                               c_void_p]),
     "wf3d_attn_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_float,
                               c_u32, c_void_p, c_void_p]),
+    "wf3d_attn_kernel": (c_int, [c_int, c_int, c_int]),
     "wf3d_edge_pair_ln_bwd_ws_bytes": (c_size_t, [c_int, c_int]),
     "wf3d_edge_pair_ln_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int,
                                       c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_float, c_u32, c_void_p, c_void_p,

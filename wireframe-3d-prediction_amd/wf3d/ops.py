@@ -491,6 +491,14 @@ def edge_scatter_dverts(dcv, meta, B, V):
     return out
 
 
+def attn_kernel(E, heads, vmax):
+    """Which kernels serve attn_fwd / attn_bwd at these dims under the current options (wf3d_set_option "attn_tiled"):
+    0 = VALU, 1 = MFMA with the sample resident in LDS, 2 = MFMA key-tiled.  Needs no GPU."""
+    k = _lib.load().wf3d_attn_kernel(int(E), int(heads), int(vmax))
+    check(min(k, 0), "attn_kernel")
+    return k
+
+
 def attn_fwd(qkv, meta, E, heads, drop_p=0.0, seed=0):
     _need_cuda(qkv)
     alloc = torch.zeros if meta.padded else torch.empty       # the kernels write real samples' rows only
