@@ -327,6 +327,33 @@ int wf3d_pool4_bwd_sx8(const float* valid, const float* cnt, const int32_t* arg_
                        const float* dmmax, const float* dmavg, int ldm, const float* dumean, const float* dumax, int ldu,
                        const float* dpf_direct, int B, int N, int C, float* dpf_sx8, void* stream);
 
+/* PACKED batches: the clouds of a batch concatenated along the point axis, pf[M_pad, C] with cloud b in rows
+ * rows[b] .. rows[b+1]-1 (rows[0] = 0, rows[B] = M) and M_pad >= M; rows M .. M_pad-1 belong to no cloud.
+ * The work is described by a chunk table the host builds from the point counts (int32, device memory, 16-byte aligned):
+ *   chunks[4k .. 4k+3] = (cloud b, rows[b], r0, r1)   rows r0 .. r1-1, all of cloud b; a cloud's chunks are consecutive
+ *                                                     and in row order: cchunk[b] .. cchunk[b+1]-1
+ *   (-1, 0, M, M_pad)                                 the pad rows, the last entry when M_pad > M (backward only)
+ * wf3d_pool4_seg_fwd is wf3d_pool4_fwd over those row ranges: one partial result per chunk (the first nchunk entries,
+ * without the pad chunk), folded per cloud in chunk order by a second kernel, so the result does not depend on how the
+ * chip schedules the chunks.  Arg-max indices are local to the cloud (0 <= n < N_b), the unmasked mean divides by N_b,
+ * cnt / nvalid are per cloud as in the dense form.  Pad rows are never read. */
+size_t wf3d_pool4_seg_ws_bytes(int nchunk, int C);
+int wf3d_pool4_seg_fwd(const float* pf, const float* valid, const int32_t* rows, const int32_t* cchunk,
+                       const int32_t* chunks, int B, int M, int nchunk, int C, float* mmax, float* mavg,
+                       float* umean, float* umax, int ldo, int32_t* arg_m, int32_t* arg_u, float* cnt,
+                       float* nvalid, void* ws, size_t ws_bytes, void* stream);
+/* wf3d_pool4_bwd / wf3d_pool4_bwd_sx8 over the same table (nchunk counts the pad chunk here; chunk_rows = the longest
+ * chunk): dpf[M_pad, C], its pad rows exact zeros; dpf_direct, when given, has at least M rows.  The bias column sum of
+ * a packed batch is wf3d_pool4_bwd_bias itself: it reads the [B, C] cotangents alone and does not depend on the rows. */
+int wf3d_pool4_seg_bwd(const float* valid, const float* cnt, const int32_t* arg_m, const int32_t* arg_u,
+                       const float* dmmax, const float* dmavg, int ldm, const float* dumean, const float* dumax,
+                       int ldu, const float* dpf_direct, const int32_t* rows, const int32_t* chunks, int B, int M,
+                       int M_pad, int nchunk, int chunk_rows, int C, float* dpf, void* stream);
+int wf3d_pool4_seg_bwd_sx8(const float* valid, const float* cnt, const int32_t* arg_m, const int32_t* arg_u,
+                           const float* dmmax, const float* dmavg, int ldm, const float* dumean, const float* dumax,
+                           int ldu, const float* dpf_direct, const int32_t* rows, const int32_t* chunks, int B, int M,
+                           int M_pad, int nchunk, int chunk_rows, int C, float* dpf_sx8, void* stream);
+
 /* ------------------------------------------------------------------------
  * Vertex head tail (VertexPredictor.py:118-127): existence = sigmoid(o[:,:,3]),
  * actual_vertex_counts = sum(existence > 0.5) (int64), o = final_layer output

@@ -29,17 +29,18 @@ __global__ __launch_bounds__(256) void point_valid_kernel(const float* __restric
     valid[m] = s > 1e-9f ? 1.0f : 0.0f;
 }
 
-__global__ __launch_bounds__(256) void pool4_partial_kernel(const float* __restrict__ pf, const float* __restrict__ valid,
-                                                             int N, int C, int nsplit, int npb,
-                                                             PoolPart* __restrict__ part, float* __restrict__ cnt_part) {
-    const int b = blockIdx.z, sp = blockIdx.y;
+// The partial kernels' bodies work on one cloud: `pf` / `valid` point at its first row, n0..n1 are rows of that cloud (the
+// arg-max indices they record are local to it), `part` / `cnt_part` at the slot of this (cloud, range of rows).  The dense
+// kernels take the cloud and the range from the grid, the segmented ones (packed batches, below) from a chunk table.
+__device__ __forceinline__ void pool4_partial_rows(const float* __restrict__ pf, const float* __restrict__ valid,
+                                                   int n0, int n1, int C,
+                                                   PoolPart* __restrict__ part, float* __restrict__ cnt_part) {
     const int c = blockIdx.x * 256 + threadIdx.x;
-    const int n0 = sp * npb, n1 = min(N, n0 + npb);
     float msum = 0.f, usum = 0.f, mmax = -INFINITY, umax = -INFINITY, cnt = 0.f;
     int am = -1, au = -1;
     if (c < C) {
-        const float* p = pf + ((size_t)b * N + n0) * C + c;
-        const float* vp = valid + (size_t)b * N;
+        const float* p = pf + (size_t)n0 * C + c;
+        const float* vp = valid;
         for (int n = n0; n < n1; ++n, p += C) {
             const float v = *p;
             const float ok = vp[n];
@@ -51,9 +52,18 @@ __global__ __launch_bounds__(256) void pool4_partial_kernel(const float* __restr
             }
         }
         PoolPart o{msum, usum, mmax, umax, am, au};
-        part[((size_t)b * nsplit + sp) * C + c] = o;
+        part[c] = o;
     }
-    if (blockIdx.x == 0 && threadIdx.x == 0) cnt_part[b * nsplit + sp] = cnt;
+    if (blockIdx.x == 0 && threadIdx.x == 0) *cnt_part = cnt;
+}
+
+__global__ __launch_bounds__(256) void pool4_partial_kernel(const float* __restrict__ pf, const float* __restrict__ valid,
+                                                             int N, int C, int nsplit, int npb,
+                                                             PoolPart* __restrict__ part, float* __restrict__ cnt_part) {
+    const int b = blockIdx.z, sp = blockIdx.y;
+    const int n0 = sp * npb, n1 = min(N, n0 + npb);
+    const size_t slot = (size_t)b * nsplit + sp;
+    pool4_partial_rows(pf + (size_t)b * N * C, valid + (size_t)b * N, n0, n1, C, part + slot * C, cnt_part + slot);
 }
 
 struct Pool4 {                 // running state of 4 channels
@@ -87,23 +97,21 @@ __device__ __forceinline__ Pool4 pool4_shfl_xor(const Pool4& a, int mask) {
     return o;
 }
 
-__global__ __launch_bounds__(256) void pool4_partial_v4_kernel(const float* __restrict__ pf, const float* __restrict__ valid,
-                                                                int N, int C, int nsplit, int npb,
-                                                                PoolPart* __restrict__ part, float* __restrict__ cnt_part) {
+__device__ __forceinline__ void pool4_partial_v4_rows(const float* __restrict__ pf, const float* __restrict__ valid,
+                                                      int n0, int n1, int C,
+                                                      PoolPart* __restrict__ part, float* __restrict__ cnt_part) {
     __shared__ Pool4 s_p[3][16];
     __shared__ float s_cnt[4];
-    const int b = blockIdx.z, sp = blockIdx.y;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int rsub = lane >> 4, c = blockIdx.x * 64 + (lane & 15) * 4;
-    const int n0 = sp * npb, n1 = min(N, n0 + npb);
     Pool4 a;
     a.msum = a.usum = f32x4{0.f, 0.f, 0.f, 0.f};
     a.mmax = a.umax = f32x4{-INFINITY, -INFINITY, -INFINITY, -INFINITY};
 #pragma unroll
     for (int e = 0; e < 4; ++e) a.am[e] = a.au[e] = -1;
     float cnt = 0.f;
-    const float* base = pf + (size_t)b * N * C + c;
-    const float* vp = valid + (size_t)b * N;
+    const float* base = pf + c;
+    const float* vp = valid;
     constexpr int U = 4;                                   // 4 independent 16-B loads per lane in flight
     for (int n = n0 + wave * 4 + rsub; n < n1; n += 16 * U) {
         f32x4 v[U];
@@ -146,22 +154,31 @@ __global__ __launch_bounds__(256) void pool4_partial_v4_kernel(const float* __re
         pool4_merge(a, s_p[2][lane]);
 #pragma unroll
         for (int e = 0; e < 4; ++e)
-            part[((size_t)b * nsplit + sp) * C + c + e] = PoolPart{a.msum[e], a.usum[e], a.mmax[e], a.umax[e], a.am[e], a.au[e]};
-        if (blockIdx.x == 0 && lane == 0) cnt_part[b * nsplit + sp] = s_cnt[0] + s_cnt[1] + s_cnt[2] + s_cnt[3];
+            part[c + e] = PoolPart{a.msum[e], a.usum[e], a.mmax[e], a.umax[e], a.am[e], a.au[e]};
+        if (blockIdx.x == 0 && lane == 0) *cnt_part = s_cnt[0] + s_cnt[1] + s_cnt[2] + s_cnt[3];
     }
 }
 
-__global__ __launch_bounds__(256) void pool4_final_kernel(const PoolPart* __restrict__ part,
-                                                           const float* __restrict__ cnt_part, int N, int C,
-                                                           int nsplit, int ldo, float* __restrict__ nvalid_o,
-                                                           float* __restrict__ mmax_o,
-                                                           float* __restrict__ mavg_o, float* __restrict__ umean_o,
-                                                           float* __restrict__ umax_o, int32_t* __restrict__ arg_m_o,
-                                                           int32_t* __restrict__ arg_u_o, float* __restrict__ cnt_o) {
-    const int b = blockIdx.y;
+__global__ __launch_bounds__(256) void pool4_partial_v4_kernel(const float* __restrict__ pf, const float* __restrict__ valid,
+                                                                int N, int C, int nsplit, int npb,
+                                                                PoolPart* __restrict__ part, float* __restrict__ cnt_part) {
+    const int b = blockIdx.z, sp = blockIdx.y;
+    const int n0 = sp * npb, n1 = min(N, n0 + npb);
+    const size_t slot = (size_t)b * nsplit + sp;
+    pool4_partial_v4_rows(pf + (size_t)b * N * C, valid + (size_t)b * N, n0, n1, C, part + slot * C, cnt_part + slot);
+}
+
+// folds the `nsplit` partial results of cloud b (N points), slots s0 .. s0 + nsplit - 1, in slot order
+__device__ __forceinline__ void pool4_final_cloud(const PoolPart* __restrict__ part,
+                                                  const float* __restrict__ cnt_part, int b, size_t s0, int N, int C,
+                                                  int nsplit, int ldo, float* __restrict__ nvalid_o,
+                                                  float* __restrict__ mmax_o,
+                                                  float* __restrict__ mavg_o, float* __restrict__ umean_o,
+                                                  float* __restrict__ umax_o, int32_t* __restrict__ arg_m_o,
+                                                  int32_t* __restrict__ arg_u_o, float* __restrict__ cnt_o) {
     const int c = blockIdx.x * 256 + threadIdx.x;
     float cnt = 0.f;
-    for (int s = 0; s < nsplit; ++s) cnt += cnt_part[b * nsplit + s];
+    for (int s = 0; s < nsplit; ++s) cnt += cnt_part[s0 + s];
     const float cl = fmaxf(cnt, 1.0f);                      // clamp(min=1), PointNetEncoder.py:86
     if (blockIdx.x == 0 && threadIdx.x == 0) {
         cnt_o[b] = cl;
@@ -171,7 +188,7 @@ __global__ __launch_bounds__(256) void pool4_final_kernel(const PoolPart* __rest
     float msum = 0.f, usum = 0.f, mmax = -INFINITY, umax = -INFINITY;
     int am = -1, au = -1;
     for (int s = 0; s < nsplit; ++s) {
-        const PoolPart q = part[((size_t)b * nsplit + s) * C + c];
+        const PoolPart q = part[(s0 + s) * C + c];
         msum += q.msum; usum += q.usum;
         if (q.arg_u >= 0 && (q.umax > umax || au < 0)) { umax = q.umax; au = q.arg_u; }
         if (q.arg_m >= 0 && (q.mmax > mmax || am < 0)) { mmax = q.mmax; am = q.arg_m; }
@@ -187,25 +204,36 @@ __global__ __launch_bounds__(256) void pool4_final_kernel(const PoolPart* __rest
     arg_u_o[o] = au;
 }
 
+__global__ __launch_bounds__(256) void pool4_final_kernel(const PoolPart* __restrict__ part,
+                                                           const float* __restrict__ cnt_part, int N, int C,
+                                                           int nsplit, int ldo, float* __restrict__ nvalid_o,
+                                                           float* __restrict__ mmax_o,
+                                                           float* __restrict__ mavg_o, float* __restrict__ umean_o,
+                                                           float* __restrict__ umax_o, int32_t* __restrict__ arg_m_o,
+                                                           int32_t* __restrict__ arg_u_o, float* __restrict__ cnt_o) {
+    const int b = blockIdx.y;
+    pool4_final_cloud(part, cnt_part, b, (size_t)b * nsplit, N, C, nsplit, ldo, nvalid_o, mmax_o, mavg_o, umean_o, umax_o,
+                      arg_m_o, arg_u_o, cnt_o);
+}
+
 // dpf written 16 B per lane: a thread owns 4 channels of one cloud (its 4 pooled cotangents and
 // 2 arg-max indices live in registers) and walks the points of its split; 256/(C/4) points of a
 // split are written per pass, each a contiguous C*4-byte row.
 // SX8: dpf is written as the next GEMMs' split operand (include/wf3d.h, sx8): the two threads that own a group of 8
 // channels swap halves, one stores the group's 8 high parts, the other its 8 low parts (wf3d_store_sx8_pair).
+// The bodies work on rows n0..n1 of cloud b, whose first row is row `row0` of valid / dpf (N = its point count).
 template <bool SX8>
-__global__ __launch_bounds__(256) void pool4_bwd_kernel(const float* __restrict__ valid, const float* __restrict__ cnt,
-                                                         const int32_t* __restrict__ arg_m, const int32_t* __restrict__ arg_u,
-                                                         const float* __restrict__ dmmax, const float* __restrict__ dmavg,
-                                                         const float* __restrict__ dumean, const float* __restrict__ dumax,
-                                                         const float* __restrict__ dpf_direct, int N, int C,
-                                                         int npb, int ldm, int ldu, float* __restrict__ dpf) {
-    const int b = blockIdx.z;
+__device__ __forceinline__ void pool4_bwd_rows(const float* __restrict__ valid, const float* __restrict__ cnt,
+                                               const int32_t* __restrict__ arg_m, const int32_t* __restrict__ arg_u,
+                                               const float* __restrict__ dmmax, const float* __restrict__ dmavg,
+                                               const float* __restrict__ dumean, const float* __restrict__ dumax,
+                                               const float* __restrict__ dpf_direct, int b, size_t row0, int n0, int n1,
+                                               int N, int C, int ldm, int ldu, float* __restrict__ dpf) {
     const int tpr = C / 4 < 256 ? C / 4 : 256;             // threads per point row
     const int rpb = 256 / tpr;                             // point rows per pass
     const int rsub = threadIdx.x / tpr;
     const int c = (blockIdx.x * tpr + threadIdx.x % tpr) * 4;
     if (c >= C || rsub >= rpb) return;
-    const int n0 = blockIdx.y * npb, n1 = min(N, n0 + npb);
     const size_t o = (size_t)b * C + c, om = (size_t)b * ldm + c, ou = (size_t)b * ldu + c;
     const float inv_cnt = 1.0f / cnt[b], inv_n = 1.0f / (float)N;
     f32x4 g_avg = {0.f, 0.f, 0.f, 0.f}, g_mean = g_avg, g_mm = g_avg, g_um = g_avg;
@@ -217,8 +245,8 @@ __global__ __launch_bounds__(256) void pool4_bwd_kernel(const float* __restrict_
 #pragma unroll
     for (int j = 0; j < 4; ++j) { am[j] = arg_m[o + j]; au[j] = arg_u[o + j]; }
     for (int n = n0 + rsub; n < n1; n += rpb) {
-        const size_t idx = ((size_t)b * N + n) * C + c;
-        const float v = valid[(size_t)b * N + n];
+        const size_t idx = (row0 + n) * C + c;
+        const float v = valid[row0 + n];
         f32x4 g = g_mean + g_avg * v;
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
@@ -236,17 +264,28 @@ __global__ __launch_bounds__(256) void pool4_bwd_kernel(const float* __restrict_
     }
 }
 
-// scalar fallback for channel counts that are not a multiple of 4
-__global__ __launch_bounds__(256) void pool4_bwd_scalar_kernel(const float* __restrict__ valid, const float* __restrict__ cnt,
-                                                                const int32_t* __restrict__ arg_m, const int32_t* __restrict__ arg_u,
-                                                                const float* __restrict__ dmmax, const float* __restrict__ dmavg,
-                                                                const float* __restrict__ dumean, const float* __restrict__ dumax,
-                                                                const float* __restrict__ dpf_direct, int N, int C,
-                                                                int npb, int ldm, int ldu, float* __restrict__ dpf) {
+template <bool SX8>
+__global__ __launch_bounds__(256) void pool4_bwd_kernel(const float* __restrict__ valid, const float* __restrict__ cnt,
+                                                         const int32_t* __restrict__ arg_m, const int32_t* __restrict__ arg_u,
+                                                         const float* __restrict__ dmmax, const float* __restrict__ dmavg,
+                                                         const float* __restrict__ dumean, const float* __restrict__ dumax,
+                                                         const float* __restrict__ dpf_direct, int N, int C,
+                                                         int npb, int ldm, int ldu, float* __restrict__ dpf) {
     const int b = blockIdx.z;
+    const int n0 = blockIdx.y * npb, n1 = min(N, n0 + npb);
+    pool4_bwd_rows<SX8>(valid, cnt, arg_m, arg_u, dmmax, dmavg, dumean, dumax, dpf_direct, b, (size_t)b * N, n0, n1, N, C,
+                        ldm, ldu, dpf);
+}
+
+// scalar fallback for channel counts that are not a multiple of 4
+__device__ __forceinline__ void pool4_bwd_scalar_rows(const float* __restrict__ valid, const float* __restrict__ cnt,
+                                                      const int32_t* __restrict__ arg_m, const int32_t* __restrict__ arg_u,
+                                                      const float* __restrict__ dmmax, const float* __restrict__ dmavg,
+                                                      const float* __restrict__ dumean, const float* __restrict__ dumax,
+                                                      const float* __restrict__ dpf_direct, int b, size_t row0, int n0,
+                                                      int n1, int N, int C, int ldm, int ldu, float* __restrict__ dpf) {
     const int c = blockIdx.x * 256 + threadIdx.x;
     if (c >= C) return;
-    const int n0 = blockIdx.y * npb, n1 = min(N, n0 + npb);
     const size_t o = (size_t)b * C + c, om = (size_t)b * ldm + c, ou = (size_t)b * ldu + c;
     const float g_avg = dmavg ? dmavg[om] / cnt[b] : 0.f;
     const float g_mean = dumean ? dumean[ou] / (float)N : 0.f;
@@ -254,13 +293,25 @@ __global__ __launch_bounds__(256) void pool4_bwd_scalar_kernel(const float* __re
     const float g_um = dumax ? dumax[ou] : 0.f;
     const int am = arg_m[o], au = arg_u[o];
     for (int n = n0; n < n1; ++n) {
-        const size_t idx = ((size_t)b * N + n) * C + c;
-        float g = g_mean + valid[(size_t)b * N + n] * g_avg;
+        const size_t idx = (row0 + n) * C + c;
+        float g = g_mean + valid[row0 + n] * g_avg;
         if (n == am) g += g_mm;
         if (n == au) g += g_um;
         if (dpf_direct) g += dpf_direct[idx];
         dpf[idx] = g;
     }
+}
+
+__global__ __launch_bounds__(256) void pool4_bwd_scalar_kernel(const float* __restrict__ valid, const float* __restrict__ cnt,
+                                                                const int32_t* __restrict__ arg_m, const int32_t* __restrict__ arg_u,
+                                                                const float* __restrict__ dmmax, const float* __restrict__ dmavg,
+                                                                const float* __restrict__ dumean, const float* __restrict__ dumax,
+                                                                const float* __restrict__ dpf_direct, int N, int C,
+                                                                int npb, int ldm, int ldu, float* __restrict__ dpf) {
+    const int b = blockIdx.z;
+    const int n0 = blockIdx.y * npb, n1 = min(N, n0 + npb);
+    pool4_bwd_scalar_rows(valid, cnt, arg_m, arg_u, dmmax, dmavg, dumean, dumax, dpf_direct, b, (size_t)b * N, n0, n1, N, C,
+                          ldm, ldu, dpf);
 }
 
 // Column sums over all B*N rows of what pool4_bwd writes, from the [B, C] cotangents alone (the bias gradient of the
@@ -293,6 +344,77 @@ __global__ __launch_bounds__(256) void pool4_bwd_bias_kernel(const float* __rest
         for (int g = 0; g < 8; ++g) a += s_p[g][cl];
         out[c] = a;
     }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Segmented pools: a packed batch, the clouds concatenated along the point axis (include/wf3d.h, "PACKED batches").
+// chunks[k] = (cloud b, first row of cloud b, r0, r1): rows r0..r1-1 of the packed tensor, all of cloud b.  The chunks
+// of a cloud are consecutive and in row order (cchunk[b] .. cchunk[b+1]-1), so pool4_seg_final_kernel folds them in
+// fixed order with the first-max rule.  The table is the host's (wf3d.ops.PackedLayout builds it from validated counts) and
+// is trusted like any other offset array of the ABI.  A chunk of cloud -1 holds the pad rows M .. M_pad-1, which only the backward visits (zeros).
+// ---------------------------------------------------------------------------------------------------------------------
+struct SegChunk { int b, n0, n1; size_t row0; int N; };
+
+__device__ __forceinline__ SegChunk seg_chunk(const int32_t* __restrict__ rows, const int32_t* __restrict__ chunks, int k) {
+    const int4 q = *reinterpret_cast<const int4*>(chunks + 4 * (size_t)k);
+    return SegChunk{q.x, q.z - q.y, q.w - q.y, (size_t)q.y, rows[q.x + 1] - q.y};
+}
+
+template <bool V4>
+__global__ __launch_bounds__(256) void pool4_seg_partial_kernel(const float* __restrict__ pf, const float* __restrict__ valid,
+                                                                 const int32_t* __restrict__ rows,
+                                                                 const int32_t* __restrict__ chunks, int B, int M, int C,
+                                                                 PoolPart* __restrict__ part, float* __restrict__ cnt_part) {
+    const int k = blockIdx.y;
+    const SegChunk s = seg_chunk(rows, chunks, k);
+    if (V4) pool4_partial_v4_rows(pf + s.row0 * C, valid + s.row0, s.n0, s.n1, C, part + (size_t)k * C, cnt_part + k);
+    else    pool4_partial_rows(pf + s.row0 * C, valid + s.row0, s.n0, s.n1, C, part + (size_t)k * C, cnt_part + k);
+}
+
+__global__ __launch_bounds__(256) void pool4_seg_final_kernel(const PoolPart* __restrict__ part,
+                                                               const float* __restrict__ cnt_part,
+                                                               const int32_t* __restrict__ rows,
+                                                               const int32_t* __restrict__ cchunk, int nchunk, int C, int ldo,
+                                                               float* __restrict__ nvalid_o, float* __restrict__ mmax_o,
+                                                               float* __restrict__ mavg_o, float* __restrict__ umean_o,
+                                                               float* __restrict__ umax_o, int32_t* __restrict__ arg_m_o,
+                                                               int32_t* __restrict__ arg_u_o, float* __restrict__ cnt_o) {
+    const int b = blockIdx.y;
+    const int s0 = cchunk[b], s1 = cchunk[b + 1];
+    const int N = rows[b + 1] - rows[b];
+    pool4_final_cloud(part, cnt_part, b, (size_t)s0, N, C, s1 - s0, ldo, nvalid_o, mmax_o, mavg_o, umean_o, umax_o,
+                      arg_m_o, arg_u_o, cnt_o);
+}
+
+// grid (column blocks, parts of a chunk, chunks); MODE 0: fp32, 16 B per lane; 1: sx8; 2: scalar (C % 4 != 0).
+// The pad chunk (cloud -1: rows M .. M_pad-1) is written as exact zeros — in sx8 too, whose zero is all-zero bits.
+template <int MODE>
+__global__ __launch_bounds__(256) void pool4_seg_bwd_kernel(const float* __restrict__ valid, const float* __restrict__ cnt,
+                                                             const int32_t* __restrict__ arg_m, const int32_t* __restrict__ arg_u,
+                                                             const float* __restrict__ dmmax, const float* __restrict__ dmavg,
+                                                             const float* __restrict__ dumean, const float* __restrict__ dumax,
+                                                             const float* __restrict__ dpf_direct,
+                                                             const int32_t* __restrict__ rows, const int32_t* __restrict__ chunks,
+                                                             int B, int M, int M_pad, int C, int ldm, int ldu,
+                                                             float* __restrict__ dpf) {
+    const int k = blockIdx.z;
+    const int4 q = *reinterpret_cast<const int4*>(chunks + 4 * (size_t)k);
+    if (q.x < 0) {
+        const int r0 = q.z, r1 = q.w;
+        if (blockIdx.x != 0) return;
+        for (size_t i = (size_t)r0 * C + blockIdx.y * 256 + threadIdx.x; i < (size_t)r1 * C; i += (size_t)gridDim.y * 256)
+            dpf[i] = 0.f;
+        return;
+    }
+    const SegChunk s = seg_chunk(rows, chunks, k);
+    const int per = (s.n1 - s.n0 + (int)gridDim.y - 1) / (int)gridDim.y;
+    const int n0 = s.n0 + blockIdx.y * per, n1 = min(s.n1, n0 + per);
+    if (MODE == 2)
+        pool4_bwd_scalar_rows(valid, cnt, arg_m, arg_u, dmmax, dmavg, dumean, dumax, dpf_direct, s.b, s.row0, n0, n1, s.N, C,
+                              ldm, ldu, dpf);
+    else
+        pool4_bwd_rows<MODE == 1>(valid, cnt, arg_m, arg_u, dmmax, dmavg, dumean, dumax, dpf_direct, s.b, s.row0, n0, n1, s.N,
+                                  C, ldm, ldu, dpf);
 }
 
 bool pool_v4(const float* pf, int C) { return C % 64 == 0 && ((uintptr_t)pf % 16) == 0; }
@@ -406,4 +528,82 @@ static int pool4_bwd_impl(const float* valid, const float* cnt, const int32_t* a
     }
     WF3D_LAUNCH_CHECK();
     return WF3D_OK;
+}
+
+// ---- segmented (packed) entry points ----
+static size_t seg_part_bytes(int nchunk, int C) { return ((size_t)nchunk * C * sizeof(PoolPart) + 255) & ~(size_t)255; }
+
+extern "C" size_t wf3d_pool4_seg_ws_bytes(int nchunk, int C) {
+    if (nchunk <= 0 || C <= 0) return 0;
+    return seg_part_bytes(nchunk, C) + (size_t)nchunk * sizeof(float);
+}
+
+extern "C" int wf3d_pool4_seg_fwd(const float* pf, const float* valid, const int32_t* rows, const int32_t* cchunk,
+                                  const int32_t* chunks, int B, int M, int nchunk, int C, float* mmax, float* mavg,
+                                  float* umean, float* umax, int ldo, int32_t* arg_m, int32_t* arg_u, float* cnt,
+                                  float* nvalid, void* ws, size_t ws_bytes, void* stream) {
+    WF3D_CHECK(ldo >= C, WF3D_ERR_ARG, "wf3d_pool4_seg_fwd: ldo=%d < C=%d", ldo, C);
+    WF3D_CHECK(B > 0 && M >= B && C > 0 && nchunk >= B, WF3D_ERR_ARG, "wf3d_pool4_seg_fwd: bad dims B=%d M=%d C=%d nchunk=%d", B, M, C, nchunk);
+    WF3D_CHECK(B <= 65535 && nchunk <= 65535, WF3D_ERR_UNSUPPORTED, "wf3d_pool4_seg_fwd: more than 65535 clouds or chunks");
+    WF3D_CHECK(pf && valid && rows && cchunk && chunks && mmax && mavg && umean && umax && arg_m && arg_u && cnt, WF3D_ERR_ARG,
+               "wf3d_pool4_seg_fwd: null pointer");
+    WF3D_CHECK((uintptr_t)chunks % 16 == 0, WF3D_ERR_ARG, "wf3d_pool4_seg_fwd: the chunk table must be 16-byte aligned");
+    WF3D_CHECK(ws && ws_bytes >= wf3d_pool4_seg_ws_bytes(nchunk, C), WF3D_ERR_WS, "wf3d_pool4_seg_fwd: workspace too small");
+    PoolPart* part = (PoolPart*)ws;
+    float* cnt_part = (float*)((char*)ws + seg_part_bytes(nchunk, C));
+    hipStream_t st = (hipStream_t)stream;
+    if (pool_v4(pf, C))
+        hipLaunchKernelGGL(pool4_seg_partial_kernel<true>, dim3(C / 64, nchunk), dim3(256), 0, st, pf, valid, rows, chunks, B, M, C, part, cnt_part);
+    else
+        hipLaunchKernelGGL(pool4_seg_partial_kernel<false>, dim3(wf3d_cdiv(C, 256), nchunk), dim3(256), 0, st, pf, valid, rows, chunks, B, M, C, part, cnt_part);
+    WF3D_LAUNCH_CHECK();
+    hipLaunchKernelGGL(pool4_seg_final_kernel, dim3(wf3d_cdiv(C, 256), B), dim3(256), 0, st, part, cnt_part, rows, cchunk, nchunk, C, ldo,
+                       nvalid, mmax, mavg, umean, umax, arg_m, arg_u, cnt);
+    WF3D_LAUNCH_CHECK();
+    return WF3D_OK;
+}
+
+static int pool4_seg_bwd_impl(const float* valid, const float* cnt, const int32_t* arg_m, const int32_t* arg_u,
+                              const float* dmmax, const float* dmavg, int ldm, const float* dumean, const float* dumax, int ldu,
+                              const float* dpf_direct, const int32_t* rows, const int32_t* chunks, int B, int M, int M_pad,
+                              int nchunk, int chunk_rows, int C, float* dpf, bool sx8, void* stream) {
+    WF3D_CHECK(B > 0 && M >= B && M_pad >= M && C > 0 && nchunk >= B && chunk_rows > 0 && B <= 65535 && nchunk <= 65535, WF3D_ERR_ARG,
+               "wf3d_pool4_seg_bwd: bad dims B=%d M=%d M_pad=%d C=%d nchunk=%d chunk_rows=%d", B, M, M_pad, C, nchunk, chunk_rows);
+    WF3D_CHECK(valid && cnt && arg_m && arg_u && rows && chunks && dpf, WF3D_ERR_ARG, "wf3d_pool4_seg_bwd: null pointer");
+    WF3D_CHECK((uintptr_t)chunks % 16 == 0, WF3D_ERR_ARG, "wf3d_pool4_seg_bwd: the chunk table must be 16-byte aligned");
+    const auto al = [](const float* p, int ld) { return !p || ((uintptr_t)p % 16 == 0 && ld % 4 == 0); };
+    const bool vec = C % 4 == 0 && ((uintptr_t)dpf % 16 == 0) && (!dpf_direct || (uintptr_t)dpf_direct % 16 == 0) &&
+                     al(dmmax, ldm) && al(dmavg, ldm) && al(dumean, ldu) && al(dumax, ldu);
+    WF3D_CHECK(!sx8 || (vec && C % 8 == 0), WF3D_ERR_UNSUPPORTED, "wf3d_pool4_seg_bwd_sx8: needs C %% 8 == 0 and 16-B aligned tensors (C=%d)", C);
+    // as the dense launch: about 4096 workgroups, at least 16 rows each
+    const int cb = vec ? wf3d_cdiv(C / 4, 256) : wf3d_cdiv(C, 256);
+    int ns = 4096 / (nchunk * cb);
+    const int cap = wf3d_cdiv(chunk_rows, 16);
+    ns = ns > cap ? cap : (ns < 1 ? 1 : ns);
+    const dim3 grid(cb, ns, nchunk);
+    hipStream_t st = (hipStream_t)stream;
+#define WF3D_SEG_BWD(MODE) hipLaunchKernelGGL(pool4_seg_bwd_kernel<MODE>, grid, dim3(256), 0, st, valid, cnt, arg_m, arg_u, dmmax, dmavg, \
+                                              dumean, dumax, dpf_direct, rows, chunks, B, M, M_pad, C, ldm, ldu, dpf)
+    if (!vec) WF3D_SEG_BWD(2);
+    else if (sx8) WF3D_SEG_BWD(1);
+    else WF3D_SEG_BWD(0);
+#undef WF3D_SEG_BWD
+    WF3D_LAUNCH_CHECK();
+    return WF3D_OK;
+}
+
+extern "C" int wf3d_pool4_seg_bwd(const float* valid, const float* cnt, const int32_t* arg_m, const int32_t* arg_u,
+                                  const float* dmmax, const float* dmavg, int ldm, const float* dumean, const float* dumax,
+                                  int ldu, const float* dpf_direct, const int32_t* rows, const int32_t* chunks, int B, int M,
+                                  int M_pad, int nchunk, int chunk_rows, int C, float* dpf, void* stream) {
+    return pool4_seg_bwd_impl(valid, cnt, arg_m, arg_u, dmmax, dmavg, ldm, dumean, dumax, ldu, dpf_direct, rows, chunks, B, M,
+                              M_pad, nchunk, chunk_rows, C, dpf, false, stream);
+}
+
+extern "C" int wf3d_pool4_seg_bwd_sx8(const float* valid, const float* cnt, const int32_t* arg_m, const int32_t* arg_u,
+                                      const float* dmmax, const float* dmavg, int ldm, const float* dumean, const float* dumax,
+                                      int ldu, const float* dpf_direct, const int32_t* rows, const int32_t* chunks, int B, int M,
+                                      int M_pad, int nchunk, int chunk_rows, int C, float* dpf_sx8, void* stream) {
+    return pool4_seg_bwd_impl(valid, cnt, arg_m, arg_u, dmmax, dmavg, ldm, dumean, dumax, ldu, dpf_direct, rows, chunks, B, M,
+                              M_pad, nchunk, chunk_rows, C, dpf_sx8, true, stream);
 }

@@ -193,6 +193,19 @@ class Building3DReconstructionDataset(Dataset):
                 out[key] = torch.tensor(np.array(val))
         return out
 
+    @staticmethod
+    def collate_packed(batch):
+        """collate_batch for items whose point clouds differ in length (a dataset without num_points): `point_clouds` is the
+        clouds concatenated along the point axis, [sum N_b, Din], and `point_counts` their lengths (int64 [B]) — the packed
+        form of PointCloudToWireframe.forward_packed.  Every other field is as in collate_batch."""
+        if not batch:
+            raise ValueError("collate_packed: an empty batch")
+        clouds = [np.asarray(item["point_clouds"]) for item in batch]
+        rest = Building3DReconstructionDataset.collate_batch([{k: v for k, v in item.items() if k != "point_clouds"} for item in batch])
+        rest["point_clouds"] = torch.from_numpy(np.ascontiguousarray(np.concatenate(clouds, axis=0)))
+        rest["point_counts"] = torch.tensor([c.shape[0] for c in clouds], dtype=torch.int64)
+        return rest
+
     def load_files(self):
         data_dir = os.path.join(self.roof_dir, self.split_set)
         pc_files = list(glob.glob(os.path.join(data_dir, "xyz", "*.xyz")))

@@ -32,7 +32,7 @@ class PointCloudToWireframe(nn.Module):
         ep.attention.dropout = float(p)
         return self
 
-    def _host_counts(self, t):
+    def _host_counts(self, t, slot="_count_cache"):
         """Vertex counts as Python ints.  One device->host read per call (the reference does one
         `.item()` per sample, :80/:90).  The read is skipped only when the SAME tensor object is
         passed again unmodified, as train.py does every step (train.py:127): the cache holds a
@@ -42,11 +42,11 @@ class PointCloudToWireframe(nn.Module):
         pass a CPU tensor or a fresh tensor then.)  CPU tensors are read directly, no sync."""
         if not t.is_cuda:
             return [int(c) for c in t.tolist()]
-        ref, ver, vals = self._count_cache
+        ref, ver, vals = getattr(self, slot, (None, -1, None))
         if ref is t and ver == t._version:
             return vals
         vals = [int(c) for c in t.tolist()]
-        self._count_cache = (t, t._version, vals)
+        setattr(self, slot, (t, t._version, vals))
         return vals
 
     def set_edge_layout(self, layout, tail=None):
@@ -95,6 +95,19 @@ class PointCloudToWireframe(nn.Module):
 
     def forward(self, point_cloud, target_vertex_counts=None):
         g, _pf, upooled = self.encoder.encode(point_cloud)
+        return self._heads(g, upooled, target_vertex_counts)
+
+    def forward_packed(self, points, point_counts, target_vertex_counts=None):
+        """forward() of a packed batch: points [M, input_dim] = clouds of any lengths concatenated along the point axis
+        (wf3d.packed.pack), point_counts their lengths — host values, a list or a CPU int tensor; a CUDA tensor is read
+        once, as target_vertex_counts is.  Same output dict as forward(); sample b's entries are those of
+        forward(x_b[None]) on that cloud alone (not those of the zero-padded batch: the vertex head's pools count pad rows)."""
+        if torch.is_tensor(point_counts) and point_counts.is_cuda:
+            point_counts = self._host_counts(point_counts, "_point_count_cache")
+        g, _pf, upooled = self.encoder.encode_packed(points, point_counts)
+        return self._heads(g, upooled, target_vertex_counts)
+
+    def _heads(self, g, upooled, target_vertex_counts):
         vo = self.vertex_predictor.predict(g, upooled)
         if getattr(self, "_edge_layout", "ragged") == "padded":
             return self._forward_padded(g, vo, target_vertex_counts)

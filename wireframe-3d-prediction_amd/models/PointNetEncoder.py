@@ -5,10 +5,11 @@ Same constructor, attribute names and state_dict keys as the reference class
 indices 0,1,4,5,...,4n and `feature_fusion` at 0,1,3,4,6).  The nn modules here
 are parameter containers only: forward never calls them, it hands their tensors
 to wf3d.functional.EncoderFn (HIP kernels through the C ABI)."""
+import torch
 import torch.nn as nn
 
-from wf3d import config
-from wf3d.functional import EncoderFn, FusionFn
+from wf3d import config, ops
+from wf3d.functional import EncoderFn, EncoderFnPacked, FusionFn
 
 
 def _point_block(n_in, n_out):
@@ -62,6 +63,28 @@ class PointNetEncoder(nn.Module):
             raise ValueError(f"expected (batch, num_points, input_dim), got {tuple(x.shape)}")
         pooled, pf, upooled = EncoderFn.apply(x.float(), self._n_hidden, self.precision or config.precision(),
                                               *self._mlp_params())
+        g = FusionFn.apply(pooled, *self._fusion_params())
+        return g, pf, upooled
+
+    def encode_packed(self, points, point_counts):
+        """encode() of a packed batch (wf3d.packed.pack): points [M, input_dim] = the clouds concatenated along the point
+        axis, point_counts their lengths (host values: a list or a CPU int tensor).  Returns (global [B, C],
+        point_features [M, C], unmasked_pooled [B, 2C]); cloud b's are those of encode(x_b[None]).  Nothing is read back
+        from the device; the row layout of a list of counts is built once and cached (ops.PackedLayout.get)."""
+        counts = ops.point_counts_list(point_counts)
+        if not torch.is_tensor(points) or points.dim() != 2:
+            raise ValueError("expected packed points (sum of point counts, input_dim)")
+        if sum(counts) != points.shape[0]:
+            raise ValueError(f"point counts sum to {sum(counts)}, but there are {points.shape[0]} packed points")
+        if not points.is_cuda:
+            raise RuntimeError("wf3d: the HIP path needs CUDA (ROCm) tensors; there is no CPU fallback")
+        if not points.is_contiguous():
+            raise ValueError("packed points must be contiguous")
+        if points.requires_grad and torch.is_grad_enabled():
+            raise RuntimeError("wf3d: a packed batch that requires grad is not supported (detach the points)")
+        layout = ops.PackedLayout.get(counts, points.device)
+        pooled, pf, upooled = EncoderFnPacked.apply(points.float(), layout, self._n_hidden, self.precision or config.precision(),
+                                                    *self._mlp_params())
         g = FusionFn.apply(pooled, *self._fusion_params())
         return g, pf, upooled
 

@@ -207,6 +207,150 @@ def _dgrad(r, dz, dz_s, W, W_t, products):
 # ===========================================================================
 # Encoder
 # ===========================================================================
+class _DensePools:
+    """The pools of a dense [B, N, C] batch behind the encoder's shared forward and backward."""
+
+    def __init__(self, B, N):
+        self.B, self.N = B, N
+
+    def fwd(self, pf, valid):
+        return ops.pool4_fwd(pf.view(self.B, self.N, pf.shape[1]), valid, packed=True)
+
+    def bwd(self, valid, cnt, arg_m, arg_u, cots, dpf, C, sx8=False):
+        return ops.pool4_bwd(valid, cnt, arg_m, arg_u, *cots, dpf, self.B, self.N, C, sx8=sx8).view(self.B * self.N, C)
+
+    def colsum(self, nvalid, cnt, arg_m, arg_u, cots, dpf, C):
+        return ops.pool4_bwd_colsum(nvalid, cnt, arg_m, arg_u, *cots, dpf, self.B, self.N, C)
+
+
+class _PackedPools:
+    """The segmented pools of a packed batch (ops.PackedLayout): rows offsets[b] .. offsets[b+1]-1 are cloud b's."""
+
+    def __init__(self, layout):
+        self.layout = layout
+
+    def fwd(self, pf, valid):
+        return ops.pool4_seg_fwd(pf, valid, self.layout)
+
+    def bwd(self, valid, cnt, arg_m, arg_u, cots, dpf, C, sx8=False):
+        return ops.pool4_seg_bwd(valid, cnt, arg_m, arg_u, *cots, dpf, self.layout, C, sx8=sx8)
+
+    def colsum(self, nvalid, cnt, arg_m, arg_u, cots, dpf, C):
+        return ops.pool4_seg_bwd_colsum(nvalid, cnt, arg_m, arg_u, *cots, dpf, self.layout, C)
+
+
+def _encoder_forward(ctx, x2, pools, n_hidden, precision, params):
+    """The per-point MLP over the rows of x2 and its pools (`pools`: _DensePools or _PackedPools): the forward of EncoderFn
+    and EncoderFnPacked.  Returns (PoolOut, point_features [rows, C])."""
+    npr = _SPLIT_PRODUCTS.get(precision, 3)
+    valid = ops.point_valid(x2)
+    routes = _encoder_routes(x2, [params[4 * i] for i in range(n_hidden + 1)], precision in _SPLIT_PRODUCTS,
+                             ctx.needs_input_grad[0])
+    # both sx8 orientations (W for the forward GEMM, W^T for its dgrad) of every layer split both ways, one launch
+    widx = [i for i, r in enumerate(routes) if r.fwd == "split" and r.dgrad == "split"]
+    wsplit = dict(zip(widx, ops.split_weights([params[4 * i] for i in widx]))) if widx else {}
+    zs, stats, hs = [], [], []                 # hs[i] = sx8 operand consumed by Linear i+1 (kept for its wgrad)
+    a, a_s, pro = x2, None, None
+    for i, r in enumerate(routes):
+        W, b = params[4 * i], params[4 * i + 1]
+        if r.fwd == "first":
+            # first Linear + LayerNorm + ReLU + split in one pass (K = input_dim <= 8: a pure write of z and h)
+            z, mu, rs, a_s = ops.first_layer_fwd(x2, W, b, params[2], params[3], ACT_RELU)
+        elif r.fwd == "split":
+            z = ops.gemm_split(a_s, wsplit[i][0] if i in wsplit else ops.split_rows(W), bias=b, products=npr)
+            a_s = None
+        else:
+            z = ops.gemm(a, W, NT, bias=b, pro=pro)
+        if i == n_hidden:
+            pf = z
+            break
+        g, be = params[4 * i + 2], params[4 * i + 3]
+        if r.fwd == "first":
+            pass
+        elif routes[i + 1].fwd == "split":
+            mu, rs, a_s = ops.ln_prep(z, g, be, ACT_RELU)
+        else:
+            mu, rs = ops.row_stats(z)
+        hs.append(a_s)
+        zs.append(z)
+        stats.append((mu, rs))
+        pro = Pro(ACT_RELU, mu, rs, g, be)
+        a = z
+    del a_s
+    C = pf.shape[1]
+    po = pools.fwd(pf, valid)                                         # [max | avg] (PointNetEncoder.py:115), [mean | max]
+    ctx.n_hidden, ctx.pools, ctx.width, ctx.products, ctx.routes = n_hidden, pools, C, npr, routes
+    _keep_params(ctx, params)
+    ctx.saved = (x2, valid, zs, stats, hs, po.arg_m, po.arg_u, po.cnt)
+    ctx.nvalid = po.nvalid
+    ctx.wT = {i: ws[1] for i, ws in wsplit.items()}
+    # unused outputs (point_features when only its pools are consumed) must not come back as 268 MB of zeros
+    ctx.set_materialize_grads(False)
+    return po, pf
+
+
+def _encoder_backward(ctx, dpooled, dpf, dupooled):
+    """The backward of EncoderFn and EncoderFnPacked: (gradient of the rows of x2 or None, parameter gradients)."""
+    nh, pools, C, npr, routes = ctx.n_hidden, ctx.pools, ctx.width, ctx.products, ctx.routes
+    params = _params(ctx)
+    x2, valid, zs, stats, hs, arg_m, arg_u, cnt = _saved(ctx)
+    grads = [None] * len(params)
+    # the pooled cotangents are read as strided halves of the [B, 2C] gradients: no copies
+    dmmax = dmavg = dumean = dumax = None
+    if dpooled is not None:
+        dpooled = dpooled if dpooled.stride(1) == 1 else dpooled.contiguous()
+        dmmax, dmavg = dpooled[:, :C], dpooled[:, C:]
+    if dupooled is not None:
+        dupooled = dupooled if dupooled.stride(1) == 1 else dupooled.contiguous()
+        dumean, dumax = dupooled[:, :C], dupooled[:, C:]
+    if dpf is not None:
+        dpf = dpf.contiguous()
+    # output layer: in front of the TN wgrad (its dgrad is then split too) dz goes straight out as an sx8 operand
+    # and its column sum (the bias gradient) follows from the [B, C] cotangents
+    cots = (dmmax, dmavg, dumean, dumax)
+    if routes[nh].wgrad == "tn":
+        dz, dz_s = None, pools.bwd(valid, cnt, arg_m, arg_u, cots, dpf, C, sx8=True)
+        grads[4 * nh + 1] = pools.colsum(ctx.nvalid, cnt, arg_m, arg_u, cots, dpf, C)
+    else:
+        dz = pools.bwd(valid, cnt, arg_m, arg_u, cots, dpf, C)
+        dz_s = None
+    # per-point MLP backward, output layer first.  Entering iteration i: dz = grad wrt the
+    # pre-LN output of Linear i in fp32 and / or, on a split dgrad, dz_s = the same in sx8.
+    for i in range(nh, -1, -1):
+        r, W = routes[i], params[4 * i]
+        if r.wgrad == "first":
+            # layer 0: LN/ReLU backward, bias and WEIGHT gradient in one pass over (dh, z); dz is never written
+            g, be = params[2], params[3]
+            grads[2], grads[3], grads[1], grads[0] = ops.ln_act_bwd_first(dh, zs[0], x2, stats[0][0], stats[0][1], g, be, ACT_RELU)
+            break
+        if i < nh:
+            g, be = params[4 * i + 2], params[4 * i + 3]
+            mu, rs = stats[i]
+            dz_s = torch.empty_like(dh) if r.dgrad == "split" else None
+            dz, grads[4 * i + 2], grads[4 * i + 3], grads[4 * i + 1] = ops.ln_act_bwd(
+                dh, zs[i], mu, rs, g, be, ACT_RELU, inplace=True, dz_split=dz_s, want_dz=_dz32(r))
+        elif dz is not None:
+            grads[4 * i + 1] = ops.colsum(dz)
+            if r.dgrad == "split":
+                dz_s = ops.split_rows(dz)
+        if i > 0:
+            pg, pb = params[4 * (i - 1) + 2], params[4 * (i - 1) + 3]
+            h, pro, h_s = zs[i - 1], Pro(ACT_RELU, stats[i - 1][0], stats[i - 1][1], pg, pb), hs[i - 1]
+        else:
+            h, pro, h_s = x2, None, None
+        grads[4 * i] = _wgrad(r, dz, dz_s, h, pro, h_s, npr)
+        if r.wgrad == "tn" and not config.RETAIN_SAVED:
+            hs[i - 1] = None
+        if r.dgrad is not None:
+            dh = _dgrad(r, dz, dz_s, W, ctx.wT.get(i), npr)
+        del dz, dz_s
+        dz = dz_s = None
+    dx = dh if routes[0].dgrad is not None else None
+    if not config.RETAIN_SAVED:
+        ctx.saved = None
+    return dx, grads
+
+
 class EncoderFn(torch.autograd.Function):
     """x[B,N,Din], params -> (pooled[B,2C] = [masked max | masked mean], point_features[B,N,C],
     upooled[B,2C] = [unmasked mean | unmasked max]).
@@ -231,113 +375,41 @@ class EncoderFn(torch.autograd.Function):
         x2 = x.reshape(M, Din)
         if not x2.is_contiguous():
             x2 = x2.contiguous()
-        npr = _SPLIT_PRODUCTS.get(precision, 3)
-        valid = ops.point_valid(x2)
-        routes = _encoder_routes(x2, [params[4 * i] for i in range(n_hidden + 1)], precision in _SPLIT_PRODUCTS,
-                                 ctx.needs_input_grad[0])
-        # both sx8 orientations (W for the forward GEMM, W^T for its dgrad) of every layer split both ways, one launch
-        widx = [i for i, r in enumerate(routes) if r.fwd == "split" and r.dgrad == "split"]
-        wsplit = dict(zip(widx, ops.split_weights([params[4 * i] for i in widx]))) if widx else {}
-        zs, stats, hs = [], [], []                 # hs[i] = sx8 operand consumed by Linear i+1 (kept for its wgrad)
-        a, a_s, pro = x2, None, None
-        for i, r in enumerate(routes):
-            W, b = params[4 * i], params[4 * i + 1]
-            if r.fwd == "first":
-                # first Linear + LayerNorm + ReLU + split in one pass (K = input_dim <= 8: a pure write of z and h)
-                z, mu, rs, a_s = ops.first_layer_fwd(x2, W, b, params[2], params[3], ACT_RELU)
-            elif r.fwd == "split":
-                z = ops.gemm_split(a_s, wsplit[i][0] if i in wsplit else ops.split_rows(W), bias=b, products=npr)
-                a_s = None
-            else:
-                z = ops.gemm(a, W, NT, bias=b, pro=pro)
-            if i == n_hidden:
-                pf = z
-                break
-            g, be = params[4 * i + 2], params[4 * i + 3]
-            if r.fwd == "first":
-                pass
-            elif routes[i + 1].fwd == "split":
-                mu, rs, a_s = ops.ln_prep(z, g, be, ACT_RELU)
-            else:
-                mu, rs = ops.row_stats(z)
-            hs.append(a_s)
-            zs.append(z)
-            stats.append((mu, rs))
-            pro = Pro(ACT_RELU, mu, rs, g, be)
-            a = z
-        del a_s
-        C = pf.shape[1]
-        po = ops.pool4_fwd(pf.view(B, N, C), valid, packed=True)          # [max | avg] (PointNetEncoder.py:115), [mean | max]
-        ctx.n_hidden, ctx.dims, ctx.products, ctx.routes = n_hidden, (B, N, C), npr, routes
-        _keep_params(ctx, params)
-        ctx.saved = (x2, valid, zs, stats, hs, po.arg_m, po.arg_u, po.cnt)
-        ctx.nvalid = po.nvalid
-        ctx.wT = {i: ws[1] for i, ws in wsplit.items()}
-        # unused outputs (point_features when only its pools are consumed) must not come back as 268 MB of zeros
-        ctx.set_materialize_grads(False)
-        pf3 = pf.view(B, N, C)
-        return po.masked, pf3, po.unmasked
+        po, pf = _encoder_forward(ctx, x2, _DensePools(B, N), n_hidden, precision, params)
+        ctx.dims = (B, N, pf.shape[1])
+        return po.masked, pf.view(B, N, -1), po.unmasked
 
     @staticmethod
     def backward(ctx, dpooled, dpf, dupooled):
-        nh, (B, N, C), npr, routes = ctx.n_hidden, ctx.dims, ctx.products, ctx.routes
-        M = B * N
-        params = _params(ctx)
-        x2, valid, zs, stats, hs, arg_m, arg_u, cnt = _saved(ctx)
-        grads = [None] * len(params)
-        # the pooled cotangents are read as strided halves of the [B, 2C] gradients: no copies
-        dmmax = dmavg = dumean = dumax = None
-        if dpooled is not None:
-            dpooled = dpooled if dpooled.stride(1) == 1 else dpooled.contiguous()
-            dmmax, dmavg = dpooled[:, :C], dpooled[:, C:]
-        if dupooled is not None:
-            dupooled = dupooled if dupooled.stride(1) == 1 else dupooled.contiguous()
-            dumean, dumax = dupooled[:, :C], dupooled[:, C:]
-        if dpf is not None:
-            dpf = dpf.contiguous()
-        # output layer: in front of the TN wgrad (its dgrad is then split too) dz goes straight out as an sx8 operand
-        # and its column sum (the bias gradient) follows from the [B, C] cotangents
-        if routes[nh].wgrad == "tn":
-            dz, dz_s = None, ops.pool4_bwd(valid, cnt, arg_m, arg_u, dmmax, dmavg, dumean, dumax, dpf, B, N, C, sx8=True).view(M, C)
-            grads[4 * nh + 1] = ops.pool4_bwd_colsum(ctx.nvalid, cnt, arg_m, arg_u, dmmax, dmavg, dumean, dumax, dpf, B, N, C)
-        else:
-            dz = ops.pool4_bwd(valid, cnt, arg_m, arg_u, dmmax, dmavg, dumean, dumax, dpf, B, N, C).view(M, C)
-            dz_s = None
-        # per-point MLP backward, output layer first.  Entering iteration i: dz = grad wrt the
-        # pre-LN output of Linear i in fp32 and / or, on a split dgrad, dz_s = the same in sx8.
-        for i in range(nh, -1, -1):
-            r, W = routes[i], params[4 * i]
-            if r.wgrad == "first":
-                # layer 0: LN/ReLU backward, bias and WEIGHT gradient in one pass over (dh, z); dz is never written
-                g, be = params[2], params[3]
-                grads[2], grads[3], grads[1], grads[0] = ops.ln_act_bwd_first(dh, zs[0], x2, stats[0][0], stats[0][1], g, be, ACT_RELU)
-                break
-            if i < nh:
-                g, be = params[4 * i + 2], params[4 * i + 3]
-                mu, rs = stats[i]
-                dz_s = torch.empty_like(dh) if r.dgrad == "split" else None
-                dz, grads[4 * i + 2], grads[4 * i + 3], grads[4 * i + 1] = ops.ln_act_bwd(
-                    dh, zs[i], mu, rs, g, be, ACT_RELU, inplace=True, dz_split=dz_s, want_dz=_dz32(r))
-            elif dz is not None:
-                grads[4 * i + 1] = ops.colsum(dz)
-                if r.dgrad == "split":
-                    dz_s = ops.split_rows(dz)
-            if i > 0:
-                pg, pb = params[4 * (i - 1) + 2], params[4 * (i - 1) + 3]
-                h, pro, h_s = zs[i - 1], Pro(ACT_RELU, stats[i - 1][0], stats[i - 1][1], pg, pb), hs[i - 1]
-            else:
-                h, pro, h_s = x2, None, None
-            grads[4 * i] = _wgrad(r, dz, dz_s, h, pro, h_s, npr)
-            if r.wgrad == "tn" and not config.RETAIN_SAVED:
-                hs[i - 1] = None
-            if r.dgrad is not None:
-                dh = _dgrad(r, dz, dz_s, W, ctx.wT.get(i), npr)
-            del dz, dz_s
-            dz = dz_s = None
-        dx = dh.view(B, N, -1) if routes[0].dgrad is not None else None
-        if not config.RETAIN_SAVED:
-            ctx.saved = None
-        return (dx, None, None, *grads)
+        B, N, _ = ctx.dims
+        dx, grads = _encoder_backward(ctx, dpooled, dpf, dupooled)
+        return (None if dx is None else dx.view(B, N, -1), None, None, *grads)
+
+
+class EncoderFnPacked(torch.autograd.Function):
+    """EncoderFn on a packed batch: x [M, Din] = the clouds concatenated along the point axis, `layout` the
+    ops.PackedLayout of their point counts -> (pooled [B, 2C], point_features [M, C], upooled [B, 2C]), each cloud's those
+    of EncoderFn on that cloud alone.  The per-point MLP runs over M_pad rows (M rounded up to ops.ROW_PAD, so that every
+    route of _encoder_routes stays available whatever the counts); the pad rows have zero input, belong to no cloud, are
+    never read by the pools and get exact zeros from their backward, so they add exact zeros to every gradient.
+    ctx.saved is EncoderFn's, over the M_pad rows.  The packed input takes no gradient."""
+
+    @staticmethod
+    def forward(ctx, x, layout, n_hidden, precision, *params):
+        if ctx.needs_input_grad[0]:
+            raise RuntimeError("wf3d: a packed batch that requires grad is not supported (detach the points)")
+        M, Din = x.shape
+        x2 = x
+        if layout.M_pad != M:
+            x2 = x.new_zeros(layout.M_pad, Din)
+            x2[:M].copy_(x)
+        po, pf = _encoder_forward(ctx, x2, _PackedPools(layout), n_hidden, precision, params)
+        return po.masked, pf[:M], po.unmasked
+
+    @staticmethod
+    def backward(ctx, dpooled, dpf, dupooled):
+        _, grads = _encoder_backward(ctx, dpooled, dpf, dupooled)
+        return (None, None, None, None, *grads)
 
 
 class FusionFn(torch.autograd.Function):

@@ -379,6 +379,172 @@ def pool4_bwd_colsum(nvalid, cnt, arg_m, arg_u, dmmax, dmavg, dumean, dumax, dpf
 
 
 # ---------------------------------------------------------------------------
+# packed batches: clouds of different lengths concatenated along the point axis
+# ---------------------------------------------------------------------------
+ROW_PAD = 256        # packed row totals are rounded up to this: every GEMM route of the encoder stays available
+
+
+def point_counts_list(point_counts):
+    """Per-cloud point counts as a validated list of Python ints (a list / tuple, or a CPU int tensor)."""
+    if torch.is_tensor(point_counts):
+        if point_counts.is_cuda:
+            raise RuntimeError("wf3d: point counts are host values (a list or a CPU int tensor)")
+        if point_counts.dim() != 1 or point_counts.dtype.is_floating_point:
+            raise ValueError("wf3d: point_counts must be a 1-D integer tensor")
+        point_counts = point_counts.tolist()
+    counts = [int(c) for c in point_counts]
+    if not counts:
+        raise ValueError("wf3d: a packed batch needs at least one cloud")
+    if min(counts) < 1:
+        raise ValueError(f"wf3d: every cloud of a packed batch needs at least one point (got a count of {min(counts)})")
+    if sum(counts) + ROW_PAD > 0x7FFFFFFF:
+        raise ValueError("wf3d: the packed row total does not fit in int32")
+    return counts
+
+
+class PackedLayout:
+    """Row layout of a packed batch, from host point counts: cloud b owns rows offsets[b] .. offsets[b+1]-1 of the
+    [M_pad, ...] tensors, M = sum of the counts, M_pad = M rounded up to ROW_PAD; rows M .. M_pad-1 belong to no cloud.
+
+    `chunks` [nchunk_bwd, 4] = (cloud, its first row, r0, r1) cuts every cloud into pieces of at most `chunk_rows` rows,
+    about 256 pieces in all whatever the counts, so that a long and a short cloud both spread over the chip
+    (include/wf3d.h, "PACKED batches"); chunk_offsets[b] .. chunk_offsets[b+1]-1 are cloud b's.  The last entry, when
+    M_pad > M, is the pad rows' (-1, 0, M, M_pad).  The host arrays are numpy; to(device) puts them into device memory in
+    one asynchronous copy from pinned memory (nothing is read back), get() caches that per (device, counts): use get()."""
+    _cache = {}
+
+    def __init__(self, point_counts):
+        import numpy as np
+        self.counts = tuple(point_counts_list(point_counts))
+        self.B = len(self.counts)
+        self.offsets = np.zeros(self.B + 1, dtype=np.int32)
+        np.cumsum(self.counts, out=self.offsets[1:])
+        self.M = int(self.offsets[-1])
+        self.M_pad = -(-self.M // ROW_PAD) * ROW_PAD
+        self.chunk_rows = max(256, -(-(-(-self.M // 256)) // 64) * 64)
+        chunks, coff = [], [0]
+        for b, n in enumerate(self.counts):
+            first = int(self.offsets[b])
+            for r0 in range(first, first + n, self.chunk_rows):
+                chunks.append((b, first, r0, min(r0 + self.chunk_rows, first + n)))
+            coff.append(len(chunks))
+        self.nchunk = len(chunks)                      # the clouds' chunks (forward)
+        if self.M_pad > self.M:
+            chunks.append((-1, 0, self.M, self.M_pad))
+        self.nchunk_bwd = len(chunks)                  # ... and the pad rows' (backward)
+        self.chunks = np.array(chunks, dtype=np.int32).reshape(-1, 4)
+        self.chunk_offsets = np.array(coff, dtype=np.int32)
+        self.device = None
+
+    def row_map(self):
+        """int32 [M_pad] host array: the cloud of every row, -1 for the pad rows.  An aid for callers and tests that slice
+        per-row tensors by cloud; the kernels work from the chunk table and never see it."""
+        import numpy as np
+        m = np.full(self.M_pad, -1, dtype=np.int32)
+        m[:self.M] = np.repeat(np.arange(self.B, dtype=np.int32), self.counts)
+        return m
+
+    def to(self, device):
+        """Upload on the current stream; `ready` is recorded behind the copy so that use() can order other streams."""
+        import numpy as np
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("wf3d: the row layout of these point counts would be built inside a graph capture (its upload "
+                               "comes from a staging buffer that does not outlive the capture); run a warm-up step with the "
+                               "same point counts before capturing")
+        B = self.B
+        a0 = -(-2 * (B + 1) // 4) * 4                  # the chunk table starts 16-byte aligned
+        host = torch.zeros(a0 + 4 * self.nchunk_bwd, dtype=torch.int32).pin_memory()
+        host[:B + 1] = torch.from_numpy(self.offsets)
+        host[B + 1:2 * (B + 1)] = torch.from_numpy(self.chunk_offsets)
+        host[a0:] = torch.from_numpy(np.ascontiguousarray(self.chunks).reshape(-1))
+        buf = host.to(device, non_blocking=True)
+        self.device = device
+        self.d_rows, self.d_cchunk, self.d_chunks = buf[:B + 1], buf[B + 1:2 * (B + 1)], buf[a0:]
+        self.ready = torch.cuda.Event()
+        self.ready.record()
+        return self
+
+    def use(self):
+        """Called before the layout's launches: until the upload is known to have finished, the current stream waits for
+        it (the layout may be used from a stream other than the one that uploaded it).  Under a capture the layout is
+        marked `captured`: the graph holds its device addresses, so get() never evicts it."""
+        if torch.cuda.is_current_stream_capturing():
+            self.captured = True
+            self.ready = None                          # torch synchronizes the device when a capture begins
+        elif self.ready is not None:
+            if self.ready.query():
+                self.ready = None
+            else:
+                torch.cuda.current_stream().wait_event(self.ready)
+        return self
+
+    captured = False
+    _cache_max = 64
+
+    @classmethod
+    def get(cls, point_counts, device):
+        """The layout of these counts on `device`, built and uploaded on first use and kept in an LRU cache of _cache_max
+        lists of counts.  A layout that a graph capture has used is never evicted."""
+        key = (device.index, tuple(int(c) for c in point_counts))
+        m = cls._cache.pop(key, None)
+        if m is None:
+            m = cls(point_counts).to(device)
+            free = [k for k, v in cls._cache.items() if not v.captured]
+            if len(free) >= cls._cache_max:
+                del cls._cache[free[0]]
+        cls._cache[key] = m                            # (re-)insert as most recently used
+        return m.use()
+
+
+def pool4_seg_fwd(pf, valid, layout):
+    """pf [M_pad, C], valid [M_pad], a PackedLayout on pf's device -> PoolOut of its B clouds (pool4_fwd(packed=True))."""
+    _need_cuda(pf, valid)
+    if pf.dim() != 2 or not pf.is_contiguous() or pf.shape[0] != layout.M_pad or valid.numel() != layout.M_pad:
+        raise RuntimeError(f"wf3d.pool4_seg_fwd: contiguous point_features [{layout.M_pad}, C] and valid [{layout.M_pad}] required")
+    B, C, dev = layout.B, pf.shape[1], pf.device
+    o = PoolOut()
+    o.masked = torch.empty(B, 2 * C, dtype=torch.float32, device=dev)
+    o.unmasked = torch.empty(B, 2 * C, dtype=torch.float32, device=dev)
+    o.mmax, o.mavg = o.masked[:, :C], o.masked[:, C:]
+    o.umean, o.umax = o.unmasked[:, :C], o.unmasked[:, C:]
+    o.arg_m = torch.empty(B, C, dtype=torch.int32, device=dev)
+    o.arg_u = torch.empty(B, C, dtype=torch.int32, device=dev)
+    cn = torch.empty(2, B, dtype=torch.float32, device=dev)
+    o.cnt, o.nvalid = cn[0], cn[1]
+    lib = _lib.load()
+    ws = scratch(lib.wf3d_pool4_seg_ws_bytes(layout.nchunk, C), dev)
+    check(lib.wf3d_pool4_seg_fwd(_p(pf), _p(valid), _p(layout.d_rows), _p(layout.d_cchunk), _p(layout.d_chunks), B, layout.M,
+                                 layout.nchunk, C, _p(o.mmax), _p(o.mavg), _p(o.umean), _p(o.umax), 2 * C, _p(o.arg_m),
+                                 _p(o.arg_u), _p(o.cnt), _p(o.nvalid), _p(ws), ws.numel(), _stream()), "pool4_seg_fwd")
+    return o
+
+
+def pool4_seg_bwd(valid, cnt, arg_m, arg_u, dmmax, dmavg, dumean, dumax, dpf_direct, layout, C, sx8=False):
+    """pool4_bwd of a packed batch: dpf [M_pad, C] (sx8=True: as an sx8 operand), its pad rows exact zeros.
+    dpf_direct: [M, C] or [M_pad, C], contiguous."""
+    _need_cuda(valid, cnt, arg_m, arg_u, dmmax, dmavg, dumean, dumax, dpf_direct)
+    if dpf_direct is not None and not (dpf_direct.is_contiguous() and dpf_direct.dim() == 2 and dpf_direct.shape[1] == C
+                                       and dpf_direct.shape[0] >= layout.M):
+        raise RuntimeError("wf3d.pool4_seg_bwd: contiguous dpf_direct with at least M rows required")
+    ldm, ldu = _pair_ld(dmmax, dmavg, "masked"), _pair_ld(dumean, dumax, "unmasked")
+    dpf = torch.empty(layout.M_pad, C, dtype=torch.float32, device=valid.device)
+    fn = _lib.load().wf3d_pool4_seg_bwd_sx8 if sx8 else _lib.load().wf3d_pool4_seg_bwd
+    check(fn(_p(valid), _p(cnt), _p(arg_m), _p(arg_u), _p(dmmax), _p(dmavg), ldm, _p(dumean), _p(dumax), ldu,
+             _p(dpf_direct), _p(layout.d_rows), _p(layout.d_chunks), layout.B, layout.M, layout.M_pad, layout.nchunk_bwd,
+             layout.chunk_rows, C, _p(dpf), _stream()), "pool4_seg_bwd")
+    return dpf
+
+
+def pool4_seg_bwd_colsum(nvalid, cnt, arg_m, arg_u, dmmax, dmavg, dumean, dumax, dpf_direct, layout, C):
+    """Column sums over all rows of what pool4_seg_bwd writes.  The sum over a cloud's rows of its backward depends on
+    the [B, C] cotangents alone, not on where the rows lie, so this is the dense form's kernel."""
+    out = pool4_bwd_colsum(nvalid, cnt, arg_m, arg_u, dmmax, dmavg, dumean, dumax, None, layout.B, 0, C)
+    if dpf_direct is not None:
+        out += colsum(dpf_direct[:layout.M])
+    return out
+
+
+# ---------------------------------------------------------------------------
 # vertex-head tail and edge head
 # ---------------------------------------------------------------------------
 def vertex_finalize_fwd(o, V, vd):
