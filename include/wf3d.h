@@ -329,7 +329,8 @@ int wf3d_pool4_bwd_sx8(const float* valid, const float* cnt, const int32_t* arg_
 
 /* PACKED batches: the clouds of a batch concatenated along the point axis, pf[M_pad, C] with cloud b in rows
  * rows[b] .. rows[b+1]-1 (rows[0] = 0, rows[B] = M) and M_pad >= M; rows M .. M_pad-1 belong to no cloud.
- * The work is described by a chunk table the host builds from the point counts (int32, device memory, 16-byte aligned):
+ * The work is described by a chunk table built from the point counts (int32, device memory, 16-byte aligned; by the host,
+ * or on the device in the capacity form below):
  *   chunks[4k .. 4k+3] = (cloud b, rows[b], r0, r1)   rows r0 .. r1-1, all of cloud b; a cloud's chunks are consecutive
  *                                                     and in row order: cchunk[b] .. cchunk[b+1]-1
  *   (-1, 0, M, M_pad)                                 the pad rows, the last entry when M_pad > M (backward only)
@@ -353,6 +354,32 @@ int wf3d_pool4_seg_bwd_sx8(const float* valid, const float* cnt, const int32_t* 
                            const float* dmmax, const float* dmavg, int ldm, const float* dumean, const float* dumax,
                            int ldu, const float* dpf_direct, const int32_t* rows, const int32_t* chunks, int B, int M,
                            int M_pad, int nchunk, int chunk_rows, int C, float* dpf_sx8, void* stream);
+
+/* PACKED batches, capacity form: the same tables for a fixed row capacity (a multiple of 256), so that every launch shape
+ * depends on (B, capacity) alone and the point counts may stay in device memory.  chunk_rows = max(256, 64 *
+ * ceil(ceil(capacity / 256) / 64)), M_pad = capacity, and the table always has nchunk_cap = ceil(capacity / chunk_rows)
+ * + B + 1 entries (wf3d_packed_layout_dims), forward and backward alike:
+ *   1. the clouds' chunks as above (pieces of at most chunk_rows rows, cloud by cloud);
+ *   2. (-1, 0, r0, r1): the pad rows M .. capacity-1 in pieces of at most chunk_rows rows;
+ *   3. (-1, 0, capacity, capacity): dead entries up to nchunk_cap.
+ * The forward skips every entry of cloud -1; the backward writes exact zeros to the rows of one (none for a dead entry).
+ * Call the pools with nchunk = nchunk_cap, M_pad = capacity and M = capacity (M is only checked on the host; the live total
+ * is rows[B], in device memory); dpf_direct, when given, has capacity rows.  Results per live chunk do not depend on how
+ * many pad or dead entries follow.
+ * wf3d_packed_layout_build writes rows [B+1], cchunk [B+1], chunks [4 * nchunk_cap] (16-byte aligned) and *status from
+ * counts [B] in device memory (int64; _i32: int32): one launch of one workgroup, plain stores, no host read, nothing but
+ * (B, capacity) decides the launch.  It clamps instead of failing: a negative count is 0, a cloud that would pass
+ * `capacity` ends there and the clouds after it get no rows.  *status bit 0: something was clamped for capacity; bit 1:
+ * some cloud has no rows.  wf3d.ops.PackedLayout(counts, capacity) is the same table built on the host, integer for
+ * integer.
+ * A cloud of no rows (cchunk[b] == cchunk[b+1]) pools like the dense form's all-padded cloud where that is defined and to
+ * zeros elsewhere: mmax = mavg = umean = umax = 0, arg_m = arg_u = -1, cnt = 1 (the clamp), nvalid = 0.  Its backward
+ * writes no row, and wf3d_pool4_bwd_bias leaves its dumean / dumax out of the column sum (arg_u < 0). */
+int wf3d_packed_layout_dims(int B, int capacity, int* chunk_rows, int* nchunk_cap);
+int wf3d_packed_layout_build(const int64_t* counts, int B, int capacity, int32_t* rows, int32_t* cchunk, int32_t* chunks,
+                             int32_t* status, void* stream);
+int wf3d_packed_layout_build_i32(const int32_t* counts, int B, int capacity, int32_t* rows, int32_t* cchunk,
+                                 int32_t* chunks, int32_t* status, void* stream);
 
 /* ------------------------------------------------------------------------
  * Vertex head tail (VertexPredictor.py:118-127): existence = sigmoid(o[:,:,3]),

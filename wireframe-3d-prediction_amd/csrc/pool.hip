@@ -199,8 +199,9 @@ __device__ __forceinline__ void pool4_final_cloud(const PoolPart* __restrict__ p
     mmax_o[ov] = fin ? mmax : 0.f;
     arg_m_o[o] = fin ? am : -1;
     mavg_o[ov] = msum / cl;
-    umean_o[ov] = usum / (float)N;
-    umax_o[ov] = umax;
+    // a cloud of no rows (a capacity table built from device counts may hold one) pools to 0 like a dead cloud
+    umean_o[ov] = N > 0 ? usum / (float)N : 0.f;
+    umax_o[ov] = au >= 0 ? umax : 0.f;
     arg_u_o[o] = au;
 }
 
@@ -315,7 +316,8 @@ __global__ __launch_bounds__(256) void pool4_bwd_scalar_kernel(const float* __re
 }
 
 // Column sums over all B*N rows of what pool4_bwd writes, from the [B, C] cotangents alone (the bias gradient of the
-// Linear in front of the pool):  sum_b  dmavg*nvalid/cnt + dumean + [arg_m >= 0]*dmmax + [arg_u >= 0]*dumax.
+// Linear in front of the pool):  sum_b  dmavg*nvalid/cnt + [arg_u >= 0]*(dumean + dumax) + [arg_m >= 0]*dmmax.
+// arg_u < 0 only for a cloud of no rows (packed batches on device counts), whose backward writes nothing.
 __global__ __launch_bounds__(256) void pool4_bwd_bias_kernel(const float* __restrict__ cnt, const float* __restrict__ nvalid,
                                                               const int32_t* __restrict__ arg_m, const int32_t* __restrict__ arg_u,
                                                               const float* __restrict__ dmmax, const float* __restrict__ dmavg,
@@ -331,9 +333,10 @@ __global__ __launch_bounds__(256) void pool4_bwd_bias_kernel(const float* __rest
             const size_t o = (size_t)b * C + c, om = (size_t)b * ldm + c, ou = (size_t)b * ldu + c;
             float v = 0.f;
             if (dmavg) v += dmavg[om] * (nvalid[b] / cnt[b]);
-            if (dumean) v += dumean[ou];
+            const bool rows = arg_u[o] >= 0;
+            if (dumean && rows) v += dumean[ou];
             if (dmmax && arg_m[o] >= 0) v += dmmax[om];
-            if (dumax && arg_u[o] >= 0) v += dumax[ou];
+            if (dumax && rows) v += dumax[ou];
             acc += v;
         }
     s_p[bg][cl] = acc;
@@ -350,8 +353,10 @@ __global__ __launch_bounds__(256) void pool4_bwd_bias_kernel(const float* __rest
 // Segmented pools: a packed batch, the clouds concatenated along the point axis (include/wf3d.h, "PACKED batches").
 // chunks[k] = (cloud b, first row of cloud b, r0, r1): rows r0..r1-1 of the packed tensor, all of cloud b.  The chunks
 // of a cloud are consecutive and in row order (cchunk[b] .. cchunk[b+1]-1), so pool4_seg_final_kernel folds them in
-// fixed order with the first-max rule.  The table is the host's (wf3d.ops.PackedLayout builds it from validated counts) and
-// is trusted like any other offset array of the ABI.  A chunk of cloud -1 holds the pad rows M .. M_pad-1, which only the backward visits (zeros).
+// fixed order with the first-max rule.  The table is the host's (wf3d.ops.PackedLayout builds it from validated counts) or
+// packed_layout_kernel's (below, from device counts, for a fixed row capacity) and is trusted like any other offset array
+// of the ABI.  A chunk of cloud -1 holds pad rows, which only the backward visits (zeros); an empty one (r0 == r1) is a
+// dead entry of a capacity table and does nothing.
 // ---------------------------------------------------------------------------------------------------------------------
 struct SegChunk { int b, n0, n1; size_t row0; int N; };
 
@@ -366,6 +371,7 @@ __global__ __launch_bounds__(256) void pool4_seg_partial_kernel(const float* __r
                                                                  const int32_t* __restrict__ chunks, int B, int M, int C,
                                                                  PoolPart* __restrict__ part, float* __restrict__ cnt_part) {
     const int k = blockIdx.y;
+    if (chunks[4 * (size_t)k] < 0) return;                 // pad rows, or a dead entry of a capacity table: no cloud reads them
     const SegChunk s = seg_chunk(rows, chunks, k);
     if (V4) pool4_partial_v4_rows(pf + s.row0 * C, valid + s.row0, s.n0, s.n1, C, part + (size_t)k * C, cnt_part + k);
     else    pool4_partial_rows(pf + s.row0 * C, valid + s.row0, s.n0, s.n1, C, part + (size_t)k * C, cnt_part + k);
@@ -415,6 +421,91 @@ __global__ __launch_bounds__(256) void pool4_seg_bwd_kernel(const float* __restr
     else
         pool4_bwd_rows<MODE == 1>(valid, cnt, arg_m, arg_u, dmmax, dmavg, dumean, dumax, dpf_direct, s.b, s.row0, n0, n1, s.N,
                                   C, ldm, ldu, dpf);
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// The chunk table of a packed batch built on the device, for a fixed row capacity (include/wf3d.h, "PACKED batches",
+// capacity form): rows / cchunk / chunks from the counts in device memory, one workgroup, plain vector stores.  Thread t
+// owns clouds t*per .. t*per+per-1; two block scans (rows, then chunks) place them.  Counts are clamped: below 0 -> 0,
+// a cloud that would pass `capacity` ends there, later clouds get no rows.  status: bit 0 = clamped for capacity,
+// bit 1 = some cloud has no rows.
+// ---------------------------------------------------------------------------------------------------------------------
+__device__ __forceinline__ long long block_scan_excl(long long v, long long* s, long long* total) {
+    const int t = threadIdx.x;
+    s[t] = v;
+    __syncthreads();
+    for (int d = 1; d < 256; d <<= 1) {
+        const long long x = t >= d ? s[t - d] : 0;
+        __syncthreads();
+        s[t] += x;
+        __syncthreads();
+    }
+    const long long incl = s[t];
+    *total = s[255];
+    __syncthreads();
+    return incl - v;
+}
+
+template <typename CountT>
+__global__ __launch_bounds__(256) void packed_layout_kernel(const CountT* __restrict__ counts, int B, int capacity,
+                                                             int chunk_rows, int nchunk_cap, int32_t* __restrict__ rows,
+                                                             int32_t* __restrict__ cchunk, int32_t* __restrict__ chunks,
+                                                             int32_t* __restrict__ status) {
+    __shared__ long long s_scan[256];
+    __shared__ int s_flags;
+    const int t = threadIdx.x;
+    const int per = (B + 255) / 256;
+    const int b0 = min(t * per, B), b1 = min(b0 + per, B);
+    if (t == 0) s_flags = 0;
+    const auto clamped = [&](int b) {
+        const long long c = (long long)counts[b];
+        return c < 0 ? 0ll : (c > capacity ? (long long)capacity : c);
+    };
+    long long sum = 0;
+    for (int b = b0; b < b1; ++b) sum += clamped(b);
+    long long total;
+    const long long off = block_scan_excl(sum, s_scan, &total);
+    // rows, and the number of chunks of this thread's clouds
+    int flags = 0;
+    long long o = off, nck = 0;
+    for (int b = b0; b < b1; ++b) {
+        const int start = (int)min(o, (long long)capacity);
+        o += clamped(b);
+        const int end = (int)min(o, (long long)capacity);
+        if ((long long)counts[b] > capacity || o > capacity) flags |= 1;
+        if (end == start) flags |= 2;
+        rows[b + 1] = end;
+        nck += (end - start + chunk_rows - 1) / chunk_rows;
+    }
+    if (flags) atomicOr(&s_flags, flags);
+    long long ktotal;
+    long long k = block_scan_excl(nck, s_scan, &ktotal);
+    o = off;
+    for (int b = b0; b < b1; ++b) {
+        const int start = (int)min(o, (long long)capacity);
+        o += clamped(b);
+        const int end = (int)min(o, (long long)capacity);
+        cchunk[b] = (int)k;
+        for (int r0 = start; r0 < end; r0 += chunk_rows, ++k)
+            if (k < nchunk_cap)
+                *reinterpret_cast<int4*>(chunks + 4 * (size_t)k) = make_int4(b, start, r0, min(r0 + chunk_rows, end));
+    }
+    // the pad rows M .. capacity-1 in pieces of chunk_rows, then dead entries (capacity, capacity) up to nchunk_cap
+    const long long M = min(total, (long long)capacity);
+    for (long long kk = ktotal + t; kk < nchunk_cap; kk += 256) {
+        const int r0 = (int)min(M + (kk - ktotal) * chunk_rows, (long long)capacity);
+        *reinterpret_cast<int4*>(chunks + 4 * (size_t)kk) = make_int4(-1, 0, r0, min(r0 + chunk_rows, capacity));
+    }
+    if (t == 0) {
+        rows[0] = 0;
+        cchunk[B] = (int)ktotal;
+        *status = s_flags;                                 // every atomicOr precedes the second scan's barriers
+    }
+}
+
+int packed_chunk_rows(int rows) {                          // wf3d.ops.PackedLayout: about 256 chunks, at least 256 rows each
+    const int per = wf3d_cdiv(wf3d_cdiv(rows, 256), 64) * 64;
+    return per < 256 ? 256 : per;
 }
 
 bool pool_v4(const float* pf, int C) { return C % 64 == 0 && ((uintptr_t)pf % 16) == 0; }
@@ -606,4 +697,38 @@ extern "C" int wf3d_pool4_seg_bwd_sx8(const float* valid, const float* cnt, cons
                                       int M_pad, int nchunk, int chunk_rows, int C, float* dpf_sx8, void* stream) {
     return pool4_seg_bwd_impl(valid, cnt, arg_m, arg_u, dmmax, dmavg, ldm, dumean, dumax, ldu, dpf_direct, rows, chunks, B, M,
                               M_pad, nchunk, chunk_rows, C, dpf_sx8, true, stream);
+}
+
+// ---- the chunk table of a row capacity, built on the device ----
+extern "C" int wf3d_packed_layout_dims(int B, int capacity, int* chunk_rows, int* nchunk_cap) {
+    WF3D_CHECK(B > 0 && B <= 65535, WF3D_ERR_ARG, "wf3d_packed_layout_dims: B=%d not in 1..65535", B);
+    WF3D_CHECK(capacity > 0 && capacity % 256 == 0, WF3D_ERR_ARG, "wf3d_packed_layout_dims: capacity=%d is not a positive multiple of 256", capacity);
+    WF3D_CHECK(chunk_rows && nchunk_cap, WF3D_ERR_ARG, "wf3d_packed_layout_dims: null pointer");
+    *chunk_rows = packed_chunk_rows(capacity);
+    *nchunk_cap = wf3d_cdiv(capacity, *chunk_rows) + B + 1;
+    return WF3D_OK;
+}
+
+template <typename CountT>
+static int packed_layout_build_impl(const CountT* counts, int B, int capacity, int32_t* rows, int32_t* cchunk,
+                                    int32_t* chunks, int32_t* status, void* stream) {
+    int chunk_rows = 0, nchunk_cap = 0;
+    const int rc = wf3d_packed_layout_dims(B, capacity, &chunk_rows, &nchunk_cap);
+    if (rc != WF3D_OK) return rc;
+    WF3D_CHECK(counts && rows && cchunk && chunks && status, WF3D_ERR_ARG, "wf3d_packed_layout_build: null pointer");
+    WF3D_CHECK((uintptr_t)chunks % 16 == 0, WF3D_ERR_ARG, "wf3d_packed_layout_build: the chunk table must be 16-byte aligned");
+    hipLaunchKernelGGL(packed_layout_kernel<CountT>, dim3(1), dim3(256), 0, (hipStream_t)stream, counts, B, capacity,
+                       chunk_rows, nchunk_cap, rows, cchunk, chunks, status);
+    WF3D_LAUNCH_CHECK();
+    return WF3D_OK;
+}
+
+extern "C" int wf3d_packed_layout_build(const int64_t* counts, int B, int capacity, int32_t* rows, int32_t* cchunk,
+                                        int32_t* chunks, int32_t* status, void* stream) {
+    return packed_layout_build_impl(counts, B, capacity, rows, cchunk, chunks, status, stream);
+}
+
+extern "C" int wf3d_packed_layout_build_i32(const int32_t* counts, int B, int capacity, int32_t* rows, int32_t* cchunk,
+                                            int32_t* chunks, int32_t* status, void* stream) {
+    return packed_layout_build_impl(counts, B, capacity, rows, cchunk, chunks, status, stream);
 }

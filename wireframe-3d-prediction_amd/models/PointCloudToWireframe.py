@@ -97,15 +97,25 @@ class PointCloudToWireframe(nn.Module):
         g, _pf, upooled = self.encoder.encode(point_cloud)
         return self._heads(g, upooled, target_vertex_counts)
 
-    def forward_packed(self, points, point_counts, target_vertex_counts=None):
+    def forward_packed(self, points, point_counts, target_vertex_counts=None, capacity=None):
         """forward() of a packed batch: points [M, input_dim] = clouds of any lengths concatenated along the point axis
         (wf3d.packed.pack), point_counts their lengths — host values, a list or a CPU int tensor; a CUDA tensor is read
         once, as target_vertex_counts is.  Same output dict as forward(); sample b's entries are those of
-        forward(x_b[None]) on that cloud alone (not those of the zero-padded batch: the vertex head's pools count pad rows)."""
-        if torch.is_tensor(point_counts) and point_counts.is_cuda:
+        forward(x_b[None]) on that cloud alone (not those of the zero-padded batch: the vertex head's pools count pad rows).
+
+        capacity (a multiple of 256): points is [capacity, input_dim] with the clouds in its first rows
+        (wf3d.packed.pack_into fills such a buffer), and every launch of the encoder depends on (B, capacity) alone.  A
+        CUDA int64 / int32 point_counts [B] is then never read on the host: the row layout is built on the device in this
+        call, and the dict gains `point_status` (int32 [1] on the device: bit 0 = counts were clamped to the capacity,
+        bit 1 = some cloud has no rows; such a cloud pools to zeros and passes no gradient).  With the "padded" edge
+        layout one captured step then serves batches of any point counts."""
+        if capacity is None and torch.is_tensor(point_counts) and point_counts.is_cuda:
             point_counts = self._host_counts(point_counts, "_point_count_cache")
-        g, _pf, upooled = self.encoder.encode_packed(points, point_counts)
-        return self._heads(g, upooled, target_vertex_counts)
+        g, _pf, upooled, layout = self.encoder._encode_packed(points, point_counts, capacity)
+        out = self._heads(g, upooled, target_vertex_counts)
+        if layout.status is not None:
+            out["point_status"] = layout.status
+        return out
 
     def _heads(self, g, upooled, target_vertex_counts):
         vo = self.vertex_predictor.predict(g, upooled)

@@ -66,15 +66,29 @@ class PointNetEncoder(nn.Module):
         g = FusionFn.apply(pooled, *self._fusion_params())
         return g, pf, upooled
 
-    def encode_packed(self, points, point_counts):
+    def encode_packed(self, points, point_counts, capacity=None):
         """encode() of a packed batch (wf3d.packed.pack): points [M, input_dim] = the clouds concatenated along the point
         axis, point_counts their lengths (host values: a list or a CPU int tensor).  Returns (global [B, C],
         point_features [M, C], unmasked_pooled [B, 2C]); cloud b's are those of encode(x_b[None]).  Nothing is read back
-        from the device; the row layout of a list of counts is built once and cached (ops.PackedLayout.get)."""
-        counts = ops.point_counts_list(point_counts)
+        from the device; the row layout of a list of counts is built once and cached (ops.PackedLayout.get).
+
+        capacity (a multiple of ops.ROW_PAD): points is [capacity, input_dim], the clouds in its first rows and anything
+        finite behind them, point_features is [capacity, C], and every launch shape depends on (B, capacity) alone.
+        point_counts may then also be a CUDA int64 / int32 tensor [B]: it is never read on the host, the row layout is
+        built on the device inside this call (ops.DevicePackedLayout; counts it has to clamp are flagged in its status
+        word, which forward_packed returns), so one graph capture serves any counts."""
+        return self._encode_packed(points, point_counts, capacity)[:3]
+
+    def _encode_packed(self, points, point_counts, capacity):
+        """encode_packed, and the layout it ran on."""
+        on_device = capacity is not None and torch.is_tensor(point_counts) and point_counts.is_cuda
+        counts = None if on_device else ops.point_counts_list(point_counts)
         if not torch.is_tensor(points) or points.dim() != 2:
             raise ValueError("expected packed points (sum of point counts, input_dim)")
-        if sum(counts) != points.shape[0]:
+        if capacity is not None:
+            if points.shape[0] != ops.check_capacity(capacity):
+                raise ValueError(f"with capacity={capacity} the packed points must have {capacity} rows (got {points.shape[0]})")
+        elif sum(counts) != points.shape[0]:
             raise ValueError(f"point counts sum to {sum(counts)}, but there are {points.shape[0]} packed points")
         if not points.is_cuda:
             raise RuntimeError("wf3d: the HIP path needs CUDA (ROCm) tensors; there is no CPU fallback")
@@ -82,11 +96,18 @@ class PointNetEncoder(nn.Module):
             raise ValueError("packed points must be contiguous")
         if points.requires_grad and torch.is_grad_enabled():
             raise RuntimeError("wf3d: a packed batch that requires grad is not supported (detach the points)")
-        layout = ops.PackedLayout.get(counts, points.device)
+        if on_device:
+            if point_counts.dim() != 1 or point_counts.shape[0] < 1 or point_counts.dtype not in (torch.int64, torch.int32):
+                raise ValueError("device point counts must be a 1-D int64 or int32 tensor of at least one cloud")
+            if point_counts.device != points.device:
+                raise ValueError("device point counts must be on the points' device")
+            layout = ops.DevicePackedLayout(point_counts.shape[0], capacity, points.device).build(point_counts.contiguous())
+        else:
+            layout = ops.PackedLayout.get(counts, points.device, capacity)
         pooled, pf, upooled = EncoderFnPacked.apply(points.float(), layout, self._n_hidden, self.precision or config.precision(),
                                                     *self._mlp_params())
         g = FusionFn.apply(pooled, *self._fusion_params())
-        return g, pf, upooled
+        return g, pf, upooled, layout
 
     def forward(self, x):
         g, pf, _ = self.encode(x)

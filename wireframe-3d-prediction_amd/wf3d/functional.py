@@ -219,12 +219,14 @@ class _DensePools:
     def bwd(self, valid, cnt, arg_m, arg_u, cots, dpf, C, sx8=False):
         return ops.pool4_bwd(valid, cnt, arg_m, arg_u, *cots, dpf, self.B, self.N, C, sx8=sx8).view(self.B * self.N, C)
 
-    def colsum(self, nvalid, cnt, arg_m, arg_u, cots, dpf, C):
+    def colsum(self, valid, nvalid, cnt, arg_m, arg_u, cots, dpf, C):
         return ops.pool4_bwd_colsum(nvalid, cnt, arg_m, arg_u, *cots, dpf, self.B, self.N, C)
 
 
 class _PackedPools:
-    """The segmented pools of a packed batch (ops.PackedLayout): rows offsets[b] .. offsets[b+1]-1 are cloud b's."""
+    """The segmented pools of a packed batch: rows offsets[b] .. offsets[b+1]-1 are cloud b's.  `layout` is an
+    ops.PackedLayout (table from host counts) or an ops.DevicePackedLayout (table built on the device): one code path,
+    two table sources."""
 
     def __init__(self, layout):
         self.layout = layout
@@ -235,8 +237,8 @@ class _PackedPools:
     def bwd(self, valid, cnt, arg_m, arg_u, cots, dpf, C, sx8=False):
         return ops.pool4_seg_bwd(valid, cnt, arg_m, arg_u, *cots, dpf, self.layout, C, sx8=sx8)
 
-    def colsum(self, nvalid, cnt, arg_m, arg_u, cots, dpf, C):
-        return ops.pool4_seg_bwd_colsum(nvalid, cnt, arg_m, arg_u, *cots, dpf, self.layout, C)
+    def colsum(self, valid, nvalid, cnt, arg_m, arg_u, cots, dpf, C):
+        return ops.pool4_seg_bwd_colsum(nvalid, cnt, arg_m, arg_u, *cots, dpf, self.layout, C, valid=valid)
 
 
 def _encoder_forward(ctx, x2, pools, n_hidden, precision, params):
@@ -310,7 +312,7 @@ def _encoder_backward(ctx, dpooled, dpf, dupooled):
     cots = (dmmax, dmavg, dumean, dumax)
     if routes[nh].wgrad == "tn":
         dz, dz_s = None, pools.bwd(valid, cnt, arg_m, arg_u, cots, dpf, C, sx8=True)
-        grads[4 * nh + 1] = pools.colsum(ctx.nvalid, cnt, arg_m, arg_u, cots, dpf, C)
+        grads[4 * nh + 1] = pools.colsum(valid, ctx.nvalid, cnt, arg_m, arg_u, cots, dpf, C)
     else:
         dz = pools.bwd(valid, cnt, arg_m, arg_u, cots, dpf, C)
         dz_s = None
@@ -389,7 +391,8 @@ class EncoderFn(torch.autograd.Function):
 class EncoderFnPacked(torch.autograd.Function):
     """EncoderFn on a packed batch: x [M, Din] = the clouds concatenated along the point axis, `layout` the
     ops.PackedLayout of their point counts -> (pooled [B, 2C], point_features [M, C], upooled [B, 2C]), each cloud's those
-    of EncoderFn on that cloud alone.  The per-point MLP runs over M_pad rows (M rounded up to ops.ROW_PAD, so that every
+    of EncoderFn on that cloud alone.  With a capacity layout (host or device counts) x is [capacity, Din], its rows past
+    the live total finite and otherwise arbitrary, and point_features is [capacity, C].  The per-point MLP runs over M_pad rows (M rounded up to ops.ROW_PAD, so that every
     route of _encoder_routes stays available whatever the counts); the pad rows have zero input, belong to no cloud, are
     never read by the pools and get exact zeros from their backward, so they add exact zeros to every gradient.
     ctx.saved is EncoderFn's, over the M_pad rows.  The packed input takes no gradient."""

@@ -402,6 +402,26 @@ def point_counts_list(point_counts):
     return counts
 
 
+def check_capacity(capacity):
+    """The row capacity of a packed batch as an int: a positive multiple of ROW_PAD that fits in int32."""
+    if isinstance(capacity, bool) or not isinstance(capacity, int):
+        raise ValueError(f"wf3d: capacity must be an int (got {capacity!r})")
+    if capacity <= 0 or capacity % ROW_PAD or capacity > 0x7FFFFFFF:
+        raise ValueError(f"wf3d: capacity must be a positive multiple of {ROW_PAD} below 2^31 (got {capacity})")
+    return capacity
+
+
+def chunk_rows_of(rows):
+    """Rows per chunk of a packed batch of `rows` rows: about 256 chunks in all, at least 256 rows each."""
+    return max(256, -(-(-(-rows // 256)) // 64) * 64)
+
+
+def capacity_dims(B, capacity):
+    """(chunk_rows, nchunk_cap) of a capacity table (include/wf3d.h, "PACKED batches, capacity form")."""
+    chunk_rows = chunk_rows_of(capacity)
+    return chunk_rows, -(-capacity // chunk_rows) + B + 1
+
+
 class PackedLayout:
     """Row layout of a packed batch, from host point counts: cloud b owns rows offsets[b] .. offsets[b+1]-1 of the
     [M_pad, ...] tensors, M = sum of the counts, M_pad = M rounded up to ROW_PAD; rows M .. M_pad-1 belong to no cloud.
@@ -410,18 +430,30 @@ class PackedLayout:
     about 256 pieces in all whatever the counts, so that a long and a short cloud both spread over the chip
     (include/wf3d.h, "PACKED batches"); chunk_offsets[b] .. chunk_offsets[b+1]-1 are cloud b's.  The last entry, when
     M_pad > M, is the pad rows' (-1, 0, M, M_pad).  The host arrays are numpy; to(device) puts them into device memory in
-    one asynchronous copy from pinned memory (nothing is read back), get() caches that per (device, counts): use get()."""
-    _cache = {}
+    one asynchronous copy from pinned memory (nothing is read back), get() caches that per (device, counts, capacity):
+    use get().
 
-    def __init__(self, point_counts):
+    With `capacity` (a multiple of ROW_PAD, >= M) the table is the capacity form's: M_pad = capacity, chunk_rows from
+    capacity, and always capacity_dims(B, capacity)[1] entries, forward and backward alike — the clouds' chunks, the pad
+    rows M .. capacity-1 in pieces of chunk_rows, then dead entries (-1, 0, capacity, capacity).  Every launch shape then
+    depends on (B, capacity) alone, and DevicePackedLayout builds the same table, integer for integer, from counts in
+    device memory.  `M_abi` is the M the pools' entry points are given (capacity in this form: they only check it)."""
+    _cache = {}
+    status = None                                       # DevicePackedLayout's clamp flags; host counts are validated
+
+    def __init__(self, point_counts, capacity=None):
         import numpy as np
         self.counts = tuple(point_counts_list(point_counts))
+        self.capacity = None if capacity is None else check_capacity(capacity)
         self.B = len(self.counts)
         self.offsets = np.zeros(self.B + 1, dtype=np.int32)
         np.cumsum(self.counts, out=self.offsets[1:])
         self.M = int(self.offsets[-1])
-        self.M_pad = -(-self.M // ROW_PAD) * ROW_PAD
-        self.chunk_rows = max(256, -(-(-(-self.M // 256)) // 64) * 64)
+        if capacity is not None and self.M > capacity:
+            raise ValueError(f"wf3d: point counts sum to {self.M}, above the capacity of {capacity} rows")
+        self.M_pad = -(-self.M // ROW_PAD) * ROW_PAD if capacity is None else capacity
+        self.M_abi = self.M if capacity is None else capacity
+        self.chunk_rows = chunk_rows_of(self.M_pad if capacity is not None else self.M)
         chunks, coff = [], [0]
         for b, n in enumerate(self.counts):
             first = int(self.offsets[b])
@@ -429,7 +461,13 @@ class PackedLayout:
                 chunks.append((b, first, r0, min(r0 + self.chunk_rows, first + n)))
             coff.append(len(chunks))
         self.nchunk = len(chunks)                      # the clouds' chunks (forward)
-        if self.M_pad > self.M:
+        if capacity is not None:
+            nchunk_cap = capacity_dims(self.B, capacity)[1]
+            chunks += [(-1, 0, r0, min(r0 + self.chunk_rows, capacity)) for r0 in range(self.M, capacity, self.chunk_rows)]
+            chunks += [(-1, 0, capacity, capacity)] * (nchunk_cap - len(chunks))
+            assert len(chunks) == nchunk_cap
+            self.nchunk = nchunk_cap                   # forward and backward walk the whole table
+        elif self.M_pad > self.M:
             chunks.append((-1, 0, self.M, self.M_pad))
         self.nchunk_bwd = len(chunks)                  # ... and the pad rows' (backward)
         self.chunks = np.array(chunks, dtype=np.int32).reshape(-1, 4)
@@ -482,13 +520,13 @@ class PackedLayout:
     _cache_max = 64
 
     @classmethod
-    def get(cls, point_counts, device):
-        """The layout of these counts on `device`, built and uploaded on first use and kept in an LRU cache of _cache_max
-        lists of counts.  A layout that a graph capture has used is never evicted."""
-        key = (device.index, tuple(int(c) for c in point_counts))
+    def get(cls, point_counts, device, capacity=None):
+        """The layout of these counts (and this capacity) on `device`, built and uploaded on first use and kept in an LRU
+        cache of _cache_max entries.  A layout that a graph capture has used is never evicted."""
+        key = (device.index, tuple(int(c) for c in point_counts)) + (() if capacity is None else (capacity,))
         m = cls._cache.pop(key, None)
         if m is None:
-            m = cls(point_counts).to(device)
+            m = cls(point_counts, capacity).to(device)
             free = [k for k, v in cls._cache.items() if not v.captured]
             if len(free) >= cls._cache_max:
                 del cls._cache[free[0]]
@@ -496,8 +534,45 @@ class PackedLayout:
         return m.use()
 
 
+class DevicePackedLayout:
+    """The capacity form of PackedLayout with the table built on the device (wf3d_packed_layout_build) from a CUDA count
+    tensor that is never read on the host: PackedLayout(counts, capacity)'s d_rows / d_cchunk / d_chunks for counts that
+    pass its checks, clamped otherwise (`status`, one int32 on the device: bit 0 = clamped for capacity, bit 1 = some
+    cloud has no rows).  The buffers belong to this object; build() may be called again with other counts.  The model
+    allocates one per forward and keeps it for that forward's backward: a table shared between calls would be rewritten
+    by a second forward before the first one's backward; under a graph capture the buffers come from the capture's
+    pool, so a replay finds them where the capture left them."""
+    counts = offsets = M = None                         # live values exist on the device only (d_rows)
+
+    def __init__(self, B, capacity, device):
+        self.capacity = self.M_pad = self.M_abi = check_capacity(capacity)
+        if not 0 < B <= 65535:
+            raise ValueError(f"wf3d: a packed batch on device counts holds 1..65535 clouds (got {B})")
+        cr, nc = ctypes.c_int(), ctypes.c_int()
+        check(_lib.load().wf3d_packed_layout_dims(B, capacity, ctypes.byref(cr), ctypes.byref(nc)), "packed_layout_dims")
+        self.B, self.chunk_rows, self.nchunk = B, cr.value, nc.value
+        self.nchunk_bwd = self.nchunk
+        a0 = -(-2 * (B + 1) // 4) * 4                   # the chunk table starts 16-byte aligned, as PackedLayout.to's
+        buf = torch.empty(a0 + 4 * self.nchunk + 1, dtype=torch.int32, device=device)
+        self.device = device
+        self.d_rows, self.d_cchunk, self.d_chunks = buf[:B + 1], buf[B + 1:2 * (B + 1)], buf[a0:a0 + 4 * self.nchunk]
+        self.status = buf[a0 + 4 * self.nchunk:]
+
+    def build(self, counts):
+        """counts: CUDA int64 or int32 [B], contiguous.  One launch on the current stream; capturable."""
+        _need_cuda(counts)
+        if counts.dtype not in (torch.int64, torch.int32) or counts.dim() != 1 or counts.shape[0] != self.B \
+                or not counts.is_contiguous():
+            raise ValueError(f"wf3d: device point counts must be a contiguous int64 or int32 tensor [{self.B}]")
+        lib = _lib.load()
+        fn = lib.wf3d_packed_layout_build if counts.dtype == torch.int64 else lib.wf3d_packed_layout_build_i32
+        check(fn(_p(counts), self.B, self.capacity, _p(self.d_rows), _p(self.d_cchunk), _p(self.d_chunks), _p(self.status),
+                 _stream()), "packed_layout_build")
+        return self
+
+
 def pool4_seg_fwd(pf, valid, layout):
-    """pf [M_pad, C], valid [M_pad], a PackedLayout on pf's device -> PoolOut of its B clouds (pool4_fwd(packed=True))."""
+    """pf [M_pad, C], valid [M_pad], a PackedLayout or DevicePackedLayout on pf's device -> PoolOut of its B clouds (pool4_fwd(packed=True))."""
     _need_cuda(pf, valid)
     if pf.dim() != 2 or not pf.is_contiguous() or pf.shape[0] != layout.M_pad or valid.numel() != layout.M_pad:
         raise RuntimeError(f"wf3d.pool4_seg_fwd: contiguous point_features [{layout.M_pad}, C] and valid [{layout.M_pad}] required")
@@ -513,7 +588,7 @@ def pool4_seg_fwd(pf, valid, layout):
     o.cnt, o.nvalid = cn[0], cn[1]
     lib = _lib.load()
     ws = scratch(lib.wf3d_pool4_seg_ws_bytes(layout.nchunk, C), dev)
-    check(lib.wf3d_pool4_seg_fwd(_p(pf), _p(valid), _p(layout.d_rows), _p(layout.d_cchunk), _p(layout.d_chunks), B, layout.M,
+    check(lib.wf3d_pool4_seg_fwd(_p(pf), _p(valid), _p(layout.d_rows), _p(layout.d_cchunk), _p(layout.d_chunks), B, layout.M_abi,
                                  layout.nchunk, C, _p(o.mmax), _p(o.mavg), _p(o.umean), _p(o.umax), 2 * C, _p(o.arg_m),
                                  _p(o.arg_u), _p(o.cnt), _p(o.nvalid), _p(ws), ws.numel(), _stream()), "pool4_seg_fwd")
     return o
@@ -521,23 +596,29 @@ def pool4_seg_fwd(pf, valid, layout):
 
 def pool4_seg_bwd(valid, cnt, arg_m, arg_u, dmmax, dmavg, dumean, dumax, dpf_direct, layout, C, sx8=False):
     """pool4_bwd of a packed batch: dpf [M_pad, C] (sx8=True: as an sx8 operand), its pad rows exact zeros.
-    dpf_direct: [M, C] or [M_pad, C], contiguous."""
+    dpf_direct: [M, C] or [M_pad, C], contiguous ([capacity, C] for a capacity layout)."""
     _need_cuda(valid, cnt, arg_m, arg_u, dmmax, dmavg, dumean, dumax, dpf_direct)
     if dpf_direct is not None and not (dpf_direct.is_contiguous() and dpf_direct.dim() == 2 and dpf_direct.shape[1] == C
-                                       and dpf_direct.shape[0] >= layout.M):
+                                       and dpf_direct.shape[0] >= layout.M_abi):
         raise RuntimeError("wf3d.pool4_seg_bwd: contiguous dpf_direct with at least M rows required")
     ldm, ldu = _pair_ld(dmmax, dmavg, "masked"), _pair_ld(dumean, dumax, "unmasked")
     dpf = torch.empty(layout.M_pad, C, dtype=torch.float32, device=valid.device)
     fn = _lib.load().wf3d_pool4_seg_bwd_sx8 if sx8 else _lib.load().wf3d_pool4_seg_bwd
     check(fn(_p(valid), _p(cnt), _p(arg_m), _p(arg_u), _p(dmmax), _p(dmavg), ldm, _p(dumean), _p(dumax), ldu,
-             _p(dpf_direct), _p(layout.d_rows), _p(layout.d_chunks), layout.B, layout.M, layout.M_pad, layout.nchunk_bwd,
+             _p(dpf_direct), _p(layout.d_rows), _p(layout.d_chunks), layout.B, layout.M_abi, layout.M_pad, layout.nchunk_bwd,
              layout.chunk_rows, C, _p(dpf), _stream()), "pool4_seg_bwd")
     return dpf
 
 
-def pool4_seg_bwd_colsum(nvalid, cnt, arg_m, arg_u, dmmax, dmavg, dumean, dumax, dpf_direct, layout, C):
+def pool4_seg_bwd_colsum(nvalid, cnt, arg_m, arg_u, dmmax, dmavg, dumean, dumax, dpf_direct, layout, C, valid=None):
     """Column sums over all rows of what pool4_seg_bwd writes.  The sum over a cloud's rows of its backward depends on
-    the [B, C] cotangents alone, not on where the rows lie, so this is the dense form's kernel."""
+    the [B, C] cotangents alone, not on where the rows lie, so this is the dense form's kernel.  A capacity layout's live
+    total may exist on the device only: with a dpf_direct (never on the model's own path) the sum is taken over what the
+    backward writes (`valid` is needed for that), whose pad rows are zeros whatever dpf_direct holds there."""
+    if dpf_direct is not None and layout.capacity is not None:
+        if valid is None:
+            raise RuntimeError("wf3d.pool4_seg_bwd_colsum: a capacity layout with a dpf_direct needs `valid`")
+        return colsum(pool4_seg_bwd(valid, cnt, arg_m, arg_u, dmmax, dmavg, dumean, dumax, dpf_direct, layout, C))
     out = pool4_bwd_colsum(nvalid, cnt, arg_m, arg_u, dmmax, dmavg, dumean, dumax, None, layout.B, 0, C)
     if dpf_direct is not None:
         out += colsum(dpf_direct[:layout.M])
