@@ -137,6 +137,26 @@ def check_grad_summaries(gold, named_grads, tol, skip=()):
     return bad
 
 
+def mha64(qkv64, counts, E, heads, p=0.0, seed=0):
+    """(ctx, lse) of torch's MultiheadAttention math in fp64 over the compact rows of `counts` samples, with the host
+    dropout mask on the softmax weights (oracle/dropout.py) when p > 0."""
+    from oracle import dropout as D
+    voff, _ = D.offsets(counts)
+    hd = E // heads
+    outs, lses = [], []
+    for s, c in enumerate(counts):
+        blk = qkv64[voff[s]:voff[s] + c]
+        q, k, v = blk[:, :E], blk[:, E:2 * E], blk[:, 2 * E:]
+        sp = lambda t: t.reshape(c, heads, hd).transpose(0, 1)     # noqa: E731
+        sc = (sp(q) / hd ** 0.5) @ sp(k).transpose(-1, -2)
+        w = torch.softmax(sc, -1)
+        if p > 0:
+            w = w * torch.from_numpy(D.attention_weights(voff[s], c, heads, seed, p))
+        outs.append((w @ sp(v)).transpose(0, 1).reshape(c, E))
+        lses.append(torch.logsumexp(sc, -1).transpose(0, 1))
+    return torch.cat(outs), torch.cat(lses)
+
+
 @contextlib.contextmanager
 def lib_option(name, value, default=0):
     """wf3d_set_option(name, value) for the body of a `with`, then `default` again (process-wide switches)."""

@@ -45,21 +45,9 @@ def tiled(v=2):
 
 
 def mha64(qkv64, counts, p=0.0, seed=0):
-    """(ctx, lse) of torch's MultiheadAttention math in fp64, with the host dropout mask on the softmax weights."""
-    voff, _ = D.offsets(counts)
-    hd = E // HEADS
-    outs, lses = [], []
-    for s, c in enumerate(counts):
-        blk = qkv64[voff[s]:voff[s] + c]
-        q, k, v = blk[:, :E], blk[:, E:2 * E], blk[:, 2 * E:]
-        sp = lambda t: t.reshape(c, HEADS, hd).transpose(0, 1)     # noqa: E731
-        sc = (sp(q) / hd ** 0.5) @ sp(k).transpose(-1, -2)
-        w = torch.softmax(sc, -1)
-        if p > 0:
-            w = w * torch.from_numpy(D.attention_weights(voff[s], c, HEADS, seed, p))
-        outs.append((w @ sp(v)).transpose(0, 1).reshape(c, E))
-        lses.append(torch.logsumexp(sc, -1).transpose(0, 1))
-    return torch.cat(outs), torch.cat(lses)
+    """(ctx, lse) of torch's MultiheadAttention math in fp64, with the host dropout mask on the softmax weights
+    (helpers.mha64 at this file's E and HEADS)."""
+    return H.mha64(qkv64, counts, E, HEADS, p, seed)
 
 
 def run(ops, qkv, dctx, counts, p=0.0, seed=0):

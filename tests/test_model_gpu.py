@@ -85,8 +85,10 @@ def test_small_edge_vs_golden(V, precision):
             assert p.grad is None, n            # spatial_proj is never used
 
 
-def _edge_head_case(vd, hidden, heads, counts, precision, seed):
-    """EdgePredictor(vd, hidden, heads) on a ragged batch: forward and every gradient element against the fp64 oracle."""
+def _edge_head_case(vd, hidden, heads, counts, precision, seed, vertices=None, run=None):
+    """EdgePredictor(vd, hidden, heads) on a ragged batch: forward and every gradient element against the fp64 oracle.
+    vertices: the [B, max(counts), vd] input instead of the Gaussian draw; run(ep, v, counts) -> probs: another entry
+    point than forward_ragged (the padded layout), its output at least as wide as the widest sample."""
     from models.EdgePredictor import EdgePredictor
     torch.manual_seed(seed)
     ep = EdgePredictor(vd, hidden, heads).to(dev())
@@ -102,8 +104,11 @@ def _edge_head_case(vd, hidden, heads, counts, precision, seed):
     g = torch.Generator().manual_seed(7)
     vmax = max(counts)
     v = torch.randn(len(counts), vmax, vd, generator=g)
+    if vertices is not None:
+        assert vertices.shape == v.shape
+        v = vertices.clone().float()
     vg = v.clone().to(dev()).requires_grad_()
-    probs = ep.forward_ragged(vg, counts)
+    probs = ep.forward_ragged(vg, counts) if run is None else run(ep, vg, counts)
     cot = torch.randn(probs.shape, generator=g)
     (probs * cot.to(dev())).sum().backward()
     P = {"edge_predictor." + n: p_.detach().cpu().double().requires_grad_() for n, p_ in ep.named_parameters()}

@@ -282,7 +282,8 @@ __global__ __launch_bounds__(256) void pair_bwd_kernel(const float* __restrict__
             }
         }
         dot = wf3d_wave_sum(dot);
-        const float w = dot / delta[e];
+        const float dl = delta[e];
+        const float w = dl > 0.f ? dot / dl : 0.f;      // coincident vertices: zero subgradient of the norm (torch's rule)
         const int ro = v0 + other;
 #pragma unroll
         for (int k = 0; k < MAXD; ++k) if (k < vd) gc[k] += w * (cme[k] - cv[ro * vd + k]);
