@@ -139,6 +139,99 @@ def test_struct_layout_matches_header():
     assert fields == [f[0] for f in _lib.GemmDesc._fields_]
 
 
+def test_struct_layouts_match_the_compiler(tmp_path):
+    """sizeof and every offsetof of the four header structs, as the build's compiler lays them out for the host, against
+    the ctypes mirrors derived from the header."""
+    import subprocess
+    from wf3d import _lib
+    assert {c: k.__name__ for c, k in _lib.STRUCTS.items()} == {
+        "wf3d_gemm_t": "GemmDesc", "wf3d_skinny_fwd_t": "SkinnyFwd", "wf3d_skinny_bwd_t": "SkinnyBwd", "wf3d_skinny_red_t": "SkinnyRed"}
+    assert [len(k._fields_) for k in (_lib.GemmDesc, _lib.SkinnyFwd, _lib.SkinnyBwd, _lib.SkinnyRed)] == [30, 23, 26, 19]
+    lines = ['#include <stddef.h>', '#include <stdio.h>', '#include "wf3d.h"', 'int main() {']
+    for c, k in _lib.STRUCTS.items():
+        assert issubclass(k, ctypes.Structure)
+        lines.append(f'    printf("{c} sizeof %zu\\n", sizeof({c}));')
+        lines += [f'    printf("{c} {f[0]} %zu\\n", offsetof({c}, {f[0]}));' for f in k._fields_]
+    src, exe = tmp_path / "layout.cpp", tmp_path / "layout"
+    src.write_text("\n".join(lines + ["    return 0;", "}", ""]))
+    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+    subprocess.run([hipcc, "-x", "c++", "-I", os.path.dirname(HDR), str(src), "-o", str(exe)], check=True)
+    out = subprocess.run([str(exe)], capture_output=True, text=True, check=True).stdout
+    compiled = {tuple(ln.split()[:2]): int(ln.split()[2]) for ln in out.splitlines()}
+    mirrored = {}
+    for c, k in _lib.STRUCTS.items():
+        mirrored[(c, "sizeof")] = ctypes.sizeof(k)
+        mirrored.update({(c, f[0]): getattr(k, f[0]).offset for f in k._fields_})
+    assert len(compiled) == 4 + 30 + 23 + 26 + 19
+    assert compiled == mirrored, sorted(set(compiled.items()) ^ set(mirrored.items()))
+
+
+def test_signatures_follow_each_mapping_rule():
+    """One entry per rule of the C-type -> ctypes map, written out by hand from include/wf3d.h."""
+    from ctypes import POINTER, c_char_p, c_double, c_float, c_int, c_long, c_size_t, c_uint32, c_void_p
+    from wf3d import _lib
+    p, i, f = c_void_p, c_int, c_float
+    expect = {
+        "wf3d_last_error": (c_char_p, []),
+        "wf3d_set_option": (c_int, [c_char_p, c_int]),
+        "wf3d_gemm": (c_int, [POINTER(_lib.GemmDesc), c_void_p]),
+        "wf3d_gemm_ws_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
+        "wf3d_ln_prep": (c_int, [p, i, i, p, p, i, f, f, c_uint32, p, p, p, p]),
+        "wf3d_packed_layout_dims": (c_int, [c_int, c_int, POINTER(c_int), POINTER(c_int)]),
+        "wf3d_parse_table": (c_long, [c_char_p, c_void_p, c_long, POINTER(c_long)]),
+        "wf3d_clip_adam_step": (c_int, [p, p, p, p, p, i, c_double, c_double, c_double, c_double, c_double, c_double, i,
+                                        p, c_size_t, p, p]),
+        "wf3d_split_rows_multi": (c_int, [p, p, p, p, p, p, i, p]),
+    }
+    for name, sig in expect.items():
+        assert _lib.SIGNATURES[name] == sig, name
+    fn = _lib.load().wf3d_clip_adam_step
+    assert (fn.restype, list(fn.argtypes)) == expect["wf3d_clip_adam_step"]
+
+
+MINI_HDR = '#define WF3D_VERSION 105\n#ifdef __cplusplus\nextern "C" {\n#endif\n%s\n#ifdef __cplusplus\n}\n#endif\n'
+
+
+@pytest.mark.parametrize("decl, names", [
+    ("int wf3d_f(const float* x, wchar_t* label, void* stream);", ["wf3d_f", "label", "wchar_t*"]),       # unknown type
+    ("int wf3d_f(int n);\nint wf3d_counter;", ["int wf3d_counter"]),                                      # trailing statement
+    ("int wf3d_f(int n);\n}", ["}"]),                                                                     # stray text
+    ("int wf3d_f(const float*, int n);", ["wf3d_f", "const float*"]),                                     # nameless parameter
+    ("int wf3d_f(void (*done)(int), void* stream);", ["wf3d_f", "(*done)"]),                              # function pointer
+    ("typedef struct wf3d_gemm_t { const float* A; short M; } wf3d_gemm_t;", ["wf3d_gemm_t.M", "short"]),  # unknown field type
+])
+def test_parser_refuses_what_it_cannot_map(decl, names):
+    from wf3d import _lib
+    assert _lib.parse_header(MINI_HDR % "int wf3d_f(const float* x, int n);")[2] == {
+        "wf3d_f": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int])}
+    with pytest.raises(RuntimeError) as e:
+        _lib.parse_header(MINI_HDR % decl)
+    for n in names:
+        assert n in str(e.value), (n, str(e.value))
+
+
+def test_load_refuses_a_version_mismatch(monkeypatch):
+    """The library must report the WF3D_VERSION of the header the binding came from: the same library under a header text
+    that declares the next version is refused as stale."""
+    from wf3d import _lib
+    txt = open(HDR).read()
+    assert "#define WF3D_VERSION 105 " in txt
+    defines = _lib.parse_header(txt.replace("#define WF3D_VERSION 105 ", "#define WF3D_VERSION 106 "))[0]
+    assert defines["WF3D_VERSION"] == 106 and _lib.DEFINES["WF3D_VERSION"] == 105
+    monkeypatch.setattr(_lib, "DEFINES", defines)
+    monkeypatch.setattr(_lib, "_lib", None)
+    with pytest.raises(RuntimeError, match="stale; rebuild it"):
+        _lib.load()
+    monkeypatch.undo()
+    assert _lib.load().wf3d_version() == _lib.DEFINES["WF3D_VERSION"] == 105
+
+
+def test_constants_come_from_the_header():
+    from wf3d import _lib, ops, skinny
+    assert (ops.ACT_NONE, ops.ACT_RELU, ops.ACT_GELU, ops.NT, ops.NN, ops.TN, skinny.MAX_ROWS) == (0, 1, 2, 0, 1, 2, 32)
+    assert _lib.DEFINES["WF3D_ERR_UNSUPPORTED"] == -4 and _lib.DEFINES["WF3D_SKINNY_MAX_PROBLEMS"] == 4
+
+
 def test_ops_reject_cpu_tensors():
     import torch
     from wf3d import ops

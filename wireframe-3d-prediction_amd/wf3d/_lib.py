@@ -1,216 +1,117 @@
-"""ctypes binding of libwf3d.so (C ABI: include/wf3d.h).
+"""ctypes binding of libwf3d.so, derived from its C ABI: include/wf3d.h is parsed when this module is imported and
+yields DEFINES (the `#define` integers), the struct mirrors and SIGNATURES.  Nothing is declared here by hand.
 
-The HIP library is the product path.  There is NO fallback: if the shared
-object is missing or a symbol is absent, importing this module raises.
+The HIP library is the product path.  There is NO fallback: if the header or the shared object is missing, a
+declaration cannot be mapped or a symbol is absent, importing / loading raises.
 """
 import ctypes
 import os
+import re
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("WF3D_LIB", os.path.join(os.path.dirname(_HERE), "libwf3d.so"))   # override: timing-only ablation builds
+HEADER_PATH = os.path.join(os.path.dirname(os.path.dirname(_HERE)), "include", "wf3d.h")    # what csrc/ compiles against
 
-c_float_p = ctypes.c_void_p      # device pointers travel as plain addresses
-c_void_p = ctypes.c_void_p
-c_int = ctypes.c_int
-c_size_t = ctypes.c_size_t
-c_float = ctypes.c_float
-c_u32 = ctypes.c_uint32
-
-
-class GemmDesc(ctypes.Structure):
-    """Mirror of `wf3d_gemm_t` (include/wf3d.h)."""
-    _fields_ = [
-        ("A", c_void_p), ("B", c_void_p), ("C", c_void_p),
-        ("bias", c_void_p), ("addend", c_void_p),
-        ("M", c_int), ("N", c_int), ("K", c_int),
-        ("lda", c_int), ("ldb", c_int), ("ldc", c_int), ("ld_addend", c_int),
-        ("layout", c_int), ("pro_act", c_int), ("pro_enable", c_int),
-        ("pro_mu", c_void_p), ("pro_rs", c_void_p), ("pro_gamma", c_void_p), ("pro_beta", c_void_p),
-        ("drop_p", c_float), ("drop_seed", c_u32),
-        ("accumulate", c_int),
-        ("ws", c_void_p), ("ws_bytes", c_size_t),
-        ("x3", c_int),
-        ("lr_u", c_void_p), ("lr_v", c_void_p), ("lr_k", c_int), ("ld_lr_u", c_int), ("ld_lr_v", c_int),
-    ]
+_SCALARS = {"int": ctypes.c_int, "long": ctypes.c_long, "float": ctypes.c_float, "double": ctypes.c_double,
+            "size_t": ctypes.c_size_t, "uint32_t": ctypes.c_uint32}
+# what a pointer that travels as a plain address (c_void_p: device memory, host tables) may point to
+_POINTEES = {"void", "float", "double", "int", "long", "int32_t", "int64_t", "uint32_t", "uint64_t", "unsigned char"}
+_STRUCT_CLASSES = {"wf3d_gemm_t": "GemmDesc", "wf3d_skinny_fwd_t": "SkinnyFwd", "wf3d_skinny_bwd_t": "SkinnyBwd",
+                   "wf3d_skinny_red_t": "SkinnyRed"}
+_TYPE_WORDS = {w for t in (*_SCALARS, *_POINTEES, "char", "const") for w in t.split()}
 
 
-class SkinnyFwd(ctypes.Structure):
-    """Mirror of `wf3d_skinny_fwd_t`."""
-    _fields_ = [
-        ("X", c_void_p), ("ldx", c_int), ("W", c_void_p), ("ldw", c_int), ("bias", c_void_p),
-        ("Y", c_void_p), ("ldy", c_int), ("N", c_int), ("K", c_int),
-        ("gamma", c_void_p), ("beta", c_void_p), ("act", c_int),
-        ("in_part", c_void_p), ("in_nblk", c_int), ("mu", c_void_p), ("rs", c_void_p),
-        ("mu_out", c_void_p), ("rs_out", c_void_p),
-        ("in_addend", c_void_p), ("ld_in_addend", c_int),
-        ("out_addend", c_void_p), ("ld_out_addend", c_int),
-        ("stat_part", c_void_p),
-    ]
+def _fail(msg):
+    raise RuntimeError("wf3d: include/wf3d.h: " + msg)
 
 
-class SkinnyBwd(ctypes.Structure):
-    """Mirror of `wf3d_skinny_bwd_t`."""
-    _fields_ = [
-        ("dY", c_void_p), ("lddy", c_int),
-        ("z", c_void_p), ("ldz", c_int), ("mu", c_void_p), ("rs", c_void_p), ("rowpart", c_void_p), ("rowpart_nblk", c_int),
-        ("W", c_void_p), ("ldw", c_int), ("N", c_int), ("K", c_int),
-        ("X", c_void_p), ("ldx", c_int),
-        ("xmu", c_void_p), ("xrs", c_void_p), ("xgamma", c_void_p), ("xbeta", c_void_p), ("xact", c_int),
-        ("xadd", c_void_p), ("ldxadd", c_int),
-        ("dW", c_void_p), ("lddw", c_int), ("db", c_void_p),
-        ("slabs", c_void_p), ("nc", c_int),
-    ]
+def _ctype(spelling, structs, where):
+    """The ctypes type of one C type spelling: scalars by name; `const char*` -> c_char_p; a pointer to a header struct
+    -> POINTER(its class); a non-const `int*` / `long*` (host out-parameter) -> POINTER(c_int / c_long); every other
+    pointer to a known type -> c_void_p (device memory and host tables travel as plain addresses)."""
+    tok = re.findall(r"\w+|\*", spelling)
+    stars = tok.count("*")
+    head, tail = (tok[:tok.index("*")], tok[tok.index("*"):]) if stars else (tok, [])
+    const, base = "const" in head, " ".join(t for t in head if t != "const")
+    if "".join(tok) == spelling.replace(" ", "") and not set(tail) - {"*", "const"}:
+        if not stars and not const and base in _SCALARS:
+            return _SCALARS[base]
+        if tail == ["*"] and base == "char" and const:
+            return ctypes.c_char_p
+        if tail == ["*"] and base in structs:
+            return ctypes.POINTER(structs[base])
+        if tail == ["*"] and base in ("int", "long") and not const:
+            return ctypes.POINTER(_SCALARS[base])
+        if stars and base in _POINTEES:
+            return ctypes.c_void_p
+    _fail(f"{where}: no ctypes mapping for the type `{spelling}`")
 
 
-class SkinnyRed(ctypes.Structure):
-    """Mirror of `wf3d_skinny_red_t`."""
-    _fields_ = [
-        ("slabs", c_void_p * 3), ("nslab", c_int * 3),
-        ("extra", c_void_p), ("ldextra", c_int), ("K", c_int),
-        ("dh", c_void_p), ("lddh", c_int),
-        ("z", c_void_p), ("ldz", c_int), ("mu", c_void_p), ("rs", c_void_p), ("gamma", c_void_p), ("beta", c_void_p),
-        ("act", c_int),
-        ("G", c_void_p), ("ldg", c_int), ("dgamma", c_void_p), ("dbeta", c_void_p), ("rowpart", c_void_p),
-    ]
+def _declarator(text, where):
+    """`<type> <name>` -> (type spelling, name)."""
+    text = " ".join(text.split())
+    if "(" in text or ")" in text:
+        _fail(f"{where}: function-pointer parameter `{text}` is not supported")
+    m = re.fullmatch(r"(.*?)\s*\b([A-Za-z_]\w*)", text)
+    if not m or not m.group(1) or m.group(2) in _TYPE_WORDS:
+        _fail(f"{where}: parameter `{text}` has no name")
+    return m.groups()
 
 
-# name -> (restype, argtypes); every symbol include/wf3d.h declares
-SIGNATURES = {
-    "wf3d_version": (c_int, []),
-    "wf3d_last_error": (ctypes.c_char_p, []),
-    "wf3d_set_option": (c_int, [ctypes.c_char_p, c_int]),
-    "wf3d_gemm_ws_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
-    "wf3d_gemm": (c_int, [ctypes.POINTER(GemmDesc), c_void_p]),
-    "wf3d_row_stats": (c_int, [c_void_p, c_int, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p]),
-    "wf3d_ln_act_apply": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
-                                  c_void_p, c_float, c_u32, c_void_p, c_void_p]),
-    "wf3d_ln_act_bwd_ws_bytes": (c_size_t, [c_int, c_int]),
-    "wf3d_ln_act_bwd": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
-                                c_float, c_u32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t,
-                                c_void_p]),
-    "wf3d_gemm_split_ws_bytes": (c_size_t, [c_int, c_int, c_int]),
-    "wf3d_gemm_split": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int,
-                                c_int, c_void_p, c_size_t, c_void_p]),
-    "wf3d_gemm_split_tn_ok": (c_int, [c_int, c_int, c_int, c_int, c_int]),
-    "wf3d_gemm_split_tn_ws_bytes": (c_size_t, [c_int, c_int, c_int]),
-    "wf3d_gemm_split_tn": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
-                                   c_void_p, c_size_t, c_void_p]),
-    "wf3d_gemm_bf16": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int,
-                               c_int, c_void_p, c_size_t, c_void_p]),
-    "wf3d_gemm_bf16_tn": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
-                                  c_void_p, c_size_t, c_void_p]),
-    "wf3d_split_rows": (c_int, [c_void_p, ctypes.c_long, ctypes.c_long, c_int, c_int, c_void_p, c_void_p]),
-    "wf3d_split_rows_multi": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
-    "wf3d_split_transpose": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
-                                     c_float, c_u32, c_int, c_void_p, c_void_p]),
-    "wf3d_ln_prep": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_float, c_float, c_u32, c_void_p,
-                             c_void_p, c_void_p, c_void_p]),
-    "wf3d_colsum_ws_bytes": (c_size_t, [c_int, c_int]),
-    "wf3d_colsum": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
-    "wf3d_point_valid": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p]),
-    "wf3d_pool4_ws_bytes": (c_size_t, [c_int, c_int, c_int]),
-    "wf3d_pool4_fwd": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
-                               c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
-    "wf3d_pool4_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p,
-                               c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
-    "wf3d_pool4_bwd_bias": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p,
-                                    c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
-    "wf3d_first_layer_fwd": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p,
-                                     c_int, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
-    "wf3d_ln_act_bwd_first_ws_bytes": (c_size_t, [c_int, c_int]),
-    "wf3d_ln_act_bwd_first": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p,
-                                      c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
-                                      c_size_t, c_void_p]),
-    "wf3d_ln_act_bwd_wsum_ws_bytes": (c_size_t, [c_int, c_int]),
-    "wf3d_ln_act_bwd_wsum": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
-                                     c_int, c_float, ctypes.c_uint32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
-                                     c_void_p, c_size_t, c_void_p]),
-    "wf3d_rowdot_act_ok": (c_int, [c_int]),
-    "wf3d_rowdot_act": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
-    "wf3d_rowdot_act_bwd_ws_bytes": (c_size_t, [c_int, c_int]),
-    "wf3d_rowdot_act_bwd": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
-                                    c_void_p, c_void_p, c_size_t, c_void_p]),
-    "wf3d_pool4_bwd_sx8": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p,
-                                   c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
-    "wf3d_pool4_seg_ws_bytes": (c_size_t, [c_int, c_int]),
-    "wf3d_pool4_seg_fwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p,
-                                   c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
-                                   c_size_t, c_void_p]),
-    "wf3d_pool4_seg_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p,
-                                   c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p,
-                                   c_void_p]),
-    "wf3d_pool4_seg_bwd_sx8": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p,
-                                       c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int,
-                                       c_void_p, c_void_p]),
-    "wf3d_packed_layout_dims": (c_int, [c_int, c_int, ctypes.POINTER(c_int), ctypes.POINTER(c_int)]),
-    "wf3d_packed_layout_build": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
-    "wf3d_packed_layout_build_i32": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
-    "wf3d_vertex_finalize_fwd": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
-    "wf3d_vertex_finalize_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
-    "wf3d_edge_layout": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
-                                 c_void_p]),
-    "wf3d_edge_gather_verts": (c_int, [c_void_p, ctypes.c_long, ctypes.c_long, c_void_p, c_void_p, c_int, c_int, c_void_p,
-                                       c_void_p]),
-    "wf3d_edge_scatter_dverts": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
-    "wf3d_attn_fwd": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_float, c_u32, c_void_p, c_void_p,
-                              c_void_p]),
-    "wf3d_attn_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_float,
-                              c_u32, c_void_p, c_void_p]),
-    "wf3d_attn_kernel": (c_int, [c_int, c_int, c_int]),
-    "wf3d_edge_pair_ln_bwd_ws_bytes": (c_size_t, [c_int, c_int]),
-    "wf3d_edge_pair_ln_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int,
-                                      c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_float, c_u32, c_void_p, c_void_p,
-                                      c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
-    "wf3d_edge_pair_fwd_ln": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int,
-                                      c_int, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_float,
-                                      ctypes.c_uint32, c_void_p, c_void_p]),
-    "wf3d_edge_pair_fwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
-                                   c_int, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
-    "wf3d_edge_pair_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
-                                   c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
-    "wf3d_edge_prob_fwd": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p]),
-    "wf3d_loss_cost_matrix": (c_int, [c_void_p, ctypes.c_long, ctypes.c_long, c_void_p, c_void_p, c_int, c_void_p, c_int,
-                                      c_int, c_void_p, c_void_p]),
-    "wf3d_loss_assign": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p]),
-    "wf3d_loss_assign_counts": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p]),
-    "wf3d_loss_terms_assigned": (c_int, [c_void_p, ctypes.c_long, ctypes.c_long, c_void_p, c_void_p, c_int, c_void_p,
-                                         c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_float,
-                                         c_float, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t,
-                                         c_void_p]),
-    "wf3d_loss_terms_assigned_ew": (c_int, [c_void_p, ctypes.c_long, ctypes.c_long, c_void_p, c_void_p, c_int, c_void_p,
-                                            c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int,
-                                            c_float, c_float, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
-                                            c_size_t, c_void_p]),
-    "wf3d_loss_terms": (c_int, [c_void_p, ctypes.c_long, ctypes.c_long, c_void_p, c_void_p, c_int, c_void_p, c_int,
-                                c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_float,
-                                c_float, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t,
-                                c_void_p]),
-    "wf3d_skinny_ok": (c_int, [c_int, c_int]),
-    "wf3d_skinny_fwd": (c_int, [ctypes.POINTER(SkinnyFwd), c_int, c_int, c_float, c_void_p]),
-    "wf3d_skinny_slab_floats": (c_size_t, [c_int, c_int, c_int, c_int]),
-    "wf3d_skinny_bwd": (c_int, [ctypes.POINTER(SkinnyBwd), c_int, c_int, c_void_p]),
-    "wf3d_skinny_reduce": (c_int, [ctypes.POINTER(SkinnyRed), c_int, c_void_p]),
-    "wf3d_clip_adam_ws_floats": (c_size_t, [c_void_p, c_int]),
-    "wf3d_clip_adam_step": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, ctypes.c_double, ctypes.c_double,
-                                    ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double, c_int, c_void_p,
-                                    c_size_t, c_void_p, c_void_p]),
-    "wf3d_clip_adam_step_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, ctypes.c_double,
-                                        ctypes.c_double, c_void_p, ctypes.c_double, ctypes.c_double, ctypes.c_double,
-                                        ctypes.c_double, c_void_p, c_size_t, c_void_p, c_void_p]),
-    "wf3d_dropout_draw": (c_int, [c_void_p, c_void_p, c_void_p]),
-    "wf3d_set_dropout_seed_words": (c_int, [c_void_p]),
-    "wf3d_set_live_rows": (c_int, [c_void_p]),
-    "wf3d_cloud_normalize": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
-    "wf3d_cloud_sample": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
-    "wf3d_meter_update": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, ctypes.c_long, c_void_p, ctypes.c_long, c_void_p,
-                                  c_int, c_void_p, c_int, c_void_p]),
-    "wf3d_parse_floats": (ctypes.c_long, [ctypes.c_char_p, c_void_p, ctypes.c_long]),
-    "wf3d_parse_table": (ctypes.c_long, [ctypes.c_char_p, c_void_p, ctypes.c_long, ctypes.POINTER(ctypes.c_long)]),
-    "wf3d_edge_endpoints": (c_int, [c_void_p, ctypes.c_long, ctypes.c_long, c_void_p, c_void_p, c_int, c_int, c_int, c_float,
-                                    c_void_p, c_void_p, c_void_p]),
-    "wf3d_hausdorff_lines": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
-    "wf3d_edge_prob_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p]),
-}
+def _struct(name, body, structs):
+    """The ctypes.Structure of `typedef struct name { body } name;`.  `int M, N, K;` declares three fields, `void* slabs[3]` an array."""
+    fields = []
+    for decl in filter(None, (d.strip() for d in body.split(";"))):
+        first, *more = decl.split(",")
+        spelling = _declarator(re.sub(r"\[\d+\]", "", first), name)[0]
+        if more and "*" in spelling:
+            _fail(f"{name}: `{decl}` declares several pointers in one statement")
+        for d in (first, *(f"{spelling} {m}" for m in more)):
+            d, dim = re.fullmatch(r"(.*?)(?:\[(\d+)\])?", d.strip(), flags=re.S).groups()
+            spelling, field = _declarator(d, name)
+            ctype = _ctype(spelling, structs, f"{name}.{field}")
+            fields.append((field, ctype * int(dim) if dim else ctype))
+    return type(_STRUCT_CLASSES[name], (ctypes.Structure,), {"_fields_": fields, "__doc__": f"Mirror of `{name}` (include/wf3d.h)."})
+
+
+def parse_header(text):
+    """(defines, structs, signatures) of a header text: the `#define NAME <int>` values by name, a ctypes.Structure per
+    `typedef struct` block by C name, and name -> (restype, [argtypes]) of every prototype.  Strict: with the comments,
+    the preprocessor lines, the extern "C" wrapper and the typedef blocks taken out, every remaining statement must be
+    a prototype whose types all map; anything else raises and names the text."""
+    text = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)
+    defines = {}
+    for line in re.findall(r"^[ \t]*#[ \t]*define[ \t]+(.*)$", text, flags=re.M):
+        m = re.fullmatch(r"(\w+)(?:\s+\(?(-?\d+)\)?)?\s*", line) or _fail(f"cannot parse `#define {line.strip()}`")
+        if m.group(2) is not None:
+            defines[m.group(1)] = int(m.group(2))
+    text = re.sub(r"^[ \t]*#.*$", "", text, flags=re.M)
+    m = re.fullmatch(r'(.*?)extern\s+"C"\s*\{(.*)\}\s*', text, flags=re.S) or _fail('no extern "C" { ... } around the declarations')
+    structs = {}
+
+    def typedef(m):
+        if m.group(1) != m.group(3) or m.group(1) not in _STRUCT_CLASSES:
+            _fail(f"struct `{m.group(1)}` / `{m.group(3)}` has no class name in wf3d/_lib.py")
+        structs[m.group(1)] = _struct(m.group(1), m.group(2), structs)
+        return ""
+    text = re.sub(r"typedef\s+struct\s+(\w+)\s*\{(.*?)\}\s*(\w+)\s*;", typedef, m.group(1) + m.group(2), flags=re.S)
+    signatures = {}
+    for stmt in filter(None, (" ".join(s.split()) for s in text.split(";"))):
+        m = re.fullmatch(r"(.+?)\b([A-Za-z_]\w*) ?\((.*)\)", stmt) or _fail(f"cannot parse `{stmt}` as a function prototype")
+        ret, name, params = (g.strip() for g in m.groups())
+        params = [] if params == "void" else [_declarator(p, f"{name}, parameter {i + 1}") for i, p in enumerate(params.split(","))]
+        signatures[name] = (_ctype(ret, structs, f"{name}, return type"),
+                            [_ctype(spelling, structs, f"{name}, parameter `{pname}`") for spelling, pname in params])
+    return defines, structs, signatures
+
+
+try:
+    with open(HEADER_PATH) as _f:
+        DEFINES, STRUCTS, SIGNATURES = parse_header(_f.read())
+except OSError as _e:
+    raise RuntimeError(f"wf3d: {HEADER_PATH} not found — the binding of libwf3d.so is derived from the header it was "
+                       "compiled against (include/wf3d.h of the source tree)") from _e
+GemmDesc, SkinnyFwd, SkinnyBwd, SkinnyRed = (STRUCTS[n] for n in _STRUCT_CLASSES)
 
 _lib = None
 
@@ -236,8 +137,10 @@ def load():
             raise RuntimeError(f"wf3d: libwf3d.so lacks symbol {name}; rebuild it") from e
         fn.restype = res
         fn.argtypes = args
-    if lib.wf3d_version() < 102:
-        raise RuntimeError("wf3d: libwf3d.so is stale; rebuild it")
+    # same names with older argument lists are what a derived binding cannot see: the library must be the header's
+    if lib.wf3d_version() != DEFINES["WF3D_VERSION"]:
+        raise RuntimeError(f"wf3d: libwf3d.so is stale; rebuild it (it reports version {lib.wf3d_version()}, "
+                           f"include/wf3d.h declares {DEFINES['WF3D_VERSION']})")
     _lib = lib
     try:
         set_tn_rounds(1)

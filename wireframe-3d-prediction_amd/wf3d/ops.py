@@ -12,8 +12,8 @@ import torch
 from . import _lib
 from ._lib import GemmDesc, check
 
-ACT_NONE, ACT_RELU, ACT_GELU = 0, 1, 2
-NT, NN, TN = 0, 1, 2
+ACT_NONE, ACT_RELU, ACT_GELU = (_lib.DEFINES["WF3D_ACT_" + n] for n in ("NONE", "RELU", "GELU"))
+NT, NN, TN = (_lib.DEFINES["WF3D_" + n] for n in ("NT", "NN", "TN"))
 LN_EPS = 1e-5
 
 _scratch = {}
@@ -40,14 +40,10 @@ except AttributeError:                   # pragma: no cover
     _raw_stream = None
 
 
-def _stream_handle():
+def _stream():
     if _raw_stream is not None:
         return _raw_stream(torch.cuda.current_device())
     return torch.cuda.current_stream().cuda_stream
-
-
-def _stream():
-    return _stream_handle()
 
 
 def scratch(nbytes, device, slot=0):
@@ -55,7 +51,7 @@ def scratch(nbytes, device, slot=0):
     stream order, so reuse across consecutive calls on one stream is safe."""
     if nbytes <= 0:
         return None
-    key = (device.index, _stream_handle(), slot)
+    key = (device.index, _stream(), slot)
     buf = _scratch.get(key)
     if buf is None or buf.numel() < nbytes:
         buf = torch.empty(max(int(nbytes), 1 << 20), dtype=torch.uint8, device=device)
@@ -309,6 +305,17 @@ class PoolOut:
     mmax/mavg/umean/umax are views of their halves."""
     __slots__ = ("masked", "unmasked", "mmax", "mavg", "umean", "umax", "arg_m", "arg_u", "cnt", "nvalid")
 
+    def __init__(self, B, C, dev):
+        """Uninitialised outputs of B clouds x C channels for a pooling launch to fill."""
+        self.masked = torch.empty(B, 2 * C, dtype=torch.float32, device=dev)
+        self.unmasked = torch.empty(B, 2 * C, dtype=torch.float32, device=dev)
+        self.mmax, self.mavg = self.masked[:, :C], self.masked[:, C:]
+        self.umean, self.umax = self.unmasked[:, :C], self.unmasked[:, C:]
+        self.arg_m = torch.empty(B, C, dtype=torch.int32, device=dev)
+        self.arg_u = torch.empty(B, C, dtype=torch.int32, device=dev)
+        cn = torch.empty(2, B, dtype=torch.float32, device=dev)
+        self.cnt, self.nvalid = cn[0], cn[1]
+
 
 def pool4_fwd(pf, valid, packed=False):
     """pf [B,N,C], valid [B*N] -> (mmax, mavg, umean, umax, arg_m, arg_u, cnt), or a PoolOut with packed=True."""
@@ -317,15 +324,7 @@ def pool4_fwd(pf, valid, packed=False):
         raise RuntimeError("wf3d.pool4_fwd: contiguous point_features required")
     B, N, C = pf.shape
     dev = pf.device
-    o = PoolOut()
-    o.masked = torch.empty(B, 2 * C, dtype=torch.float32, device=dev)
-    o.unmasked = torch.empty(B, 2 * C, dtype=torch.float32, device=dev)
-    o.mmax, o.mavg = o.masked[:, :C], o.masked[:, C:]
-    o.umean, o.umax = o.unmasked[:, :C], o.unmasked[:, C:]
-    o.arg_m = torch.empty(B, C, dtype=torch.int32, device=dev)
-    o.arg_u = torch.empty(B, C, dtype=torch.int32, device=dev)
-    cn = torch.empty(2, B, dtype=torch.float32, device=dev)
-    o.cnt, o.nvalid = cn[0], cn[1]
+    o = PoolOut(B, C, dev)
     lib = _lib.load()
     ws = scratch(lib.wf3d_pool4_ws_bytes(B, N, C), dev)
     check(lib.wf3d_pool4_fwd(_p(pf), _p(valid), B, N, C, _p(o.mmax), _p(o.mavg), _p(o.umean), _p(o.umax), 2 * C,
@@ -577,15 +576,7 @@ def pool4_seg_fwd(pf, valid, layout):
     if pf.dim() != 2 or not pf.is_contiguous() or pf.shape[0] != layout.M_pad or valid.numel() != layout.M_pad:
         raise RuntimeError(f"wf3d.pool4_seg_fwd: contiguous point_features [{layout.M_pad}, C] and valid [{layout.M_pad}] required")
     B, C, dev = layout.B, pf.shape[1], pf.device
-    o = PoolOut()
-    o.masked = torch.empty(B, 2 * C, dtype=torch.float32, device=dev)
-    o.unmasked = torch.empty(B, 2 * C, dtype=torch.float32, device=dev)
-    o.mmax, o.mavg = o.masked[:, :C], o.masked[:, C:]
-    o.umean, o.umax = o.unmasked[:, :C], o.unmasked[:, C:]
-    o.arg_m = torch.empty(B, C, dtype=torch.int32, device=dev)
-    o.arg_u = torch.empty(B, C, dtype=torch.int32, device=dev)
-    cn = torch.empty(2, B, dtype=torch.float32, device=dev)
-    o.cnt, o.nvalid = cn[0], cn[1]
+    o = PoolOut(B, C, dev)
     lib = _lib.load()
     ws = scratch(lib.wf3d_pool4_seg_ws_bytes(layout.nchunk, C), dev)
     check(lib.wf3d_pool4_seg_fwd(_p(pf), _p(valid), _p(layout.d_rows), _p(layout.d_cchunk), _p(layout.d_chunks), B, layout.M_abi,
@@ -1049,9 +1040,9 @@ def loss_cost_matrix(verts, exist, tverts, counts):
     return cost
 
 
-def loss_terms(verts, exist, edge, tverts, texist, tlabel, m_pred, m_tgt, m_off, n_match, weights):
-    """Returns (losses[4] = vertex, existence, edge, total; dverts [B,V,3]; dexist [B,V]; dedge [B,Ep])."""
-    _need_cuda(verts, exist, edge, tverts, texist, tlabel, m_pred, m_tgt, m_off)
+def _loss_launch(name, verts, exist, edge, tverts, texist, tlabel, match, weights):
+    """One launch of wf3d_<name>, a wf3d_loss_terms* entry point: they differ only in `match`, the arguments between Et
+    and B that say which prediction is matched to which target.  Allocates and returns (losses, dverts, dexist, dedge)."""
     B, V, _ = verts.shape
     Ep = edge.shape[1] if edge is not None else 0
     Et = tlabel.shape[1] if tlabel is not None else 0
@@ -1061,12 +1052,18 @@ def loss_terms(verts, exist, edge, tverts, texist, tlabel, m_pred, m_tgt, m_off,
     dedge = torch.empty(B, Ep, dtype=torch.float32, device=dev)
     losses = torch.empty(4, dtype=torch.float32, device=dev)
     ws = scratch(B * 3 * 4, dev)
-    check(_lib.load().wf3d_loss_terms(_p(verts), verts.stride(0), verts.stride(1), _p(exist), _p(edge), Ep, _p(tverts),
-                                      tverts.shape[1], _p(texist), _p(tlabel), Et, _p(m_pred), _p(m_tgt), _p(m_off),
-                                      int(n_match), B, V, float(weights[0]), float(weights[1]), float(weights[2]),
-                                      _p(dverts), _p(dexist), _p(dedge), _p(losses), _p(ws), ws.numel(), _stream()),
-          "loss_terms")
+    check(getattr(_lib.load(), "wf3d_" + name)(
+        _p(verts), verts.stride(0), verts.stride(1), _p(exist), _p(edge), Ep, _p(tverts), tverts.shape[1], _p(texist),
+        _p(tlabel), Et, *match, B, V, float(weights[0]), float(weights[1]), float(weights[2]), _p(dverts), _p(dexist),
+        _p(dedge), _p(losses), _p(ws), ws.numel(), _stream()), name)
     return losses, dverts, dexist, dedge
+
+
+def loss_terms(verts, exist, edge, tverts, texist, tlabel, m_pred, m_tgt, m_off, n_match, weights):
+    """Returns (losses[4] = vertex, existence, edge, total; dverts [B,V,3]; dexist [B,V]; dedge [B,Ep])."""
+    _need_cuda(verts, exist, edge, tverts, texist, tlabel, m_pred, m_tgt, m_off)
+    return _loss_launch("loss_terms", verts, exist, edge, tverts, texist, tlabel,
+                        (_p(m_pred), _p(m_tgt), _p(m_off), int(n_match)), weights)
 
 
 def loss_assign(cost, counts=None):
@@ -1087,40 +1084,10 @@ def loss_terms_assigned(verts, exist, edge, tverts, texist, tlabel, col4row, cou
     """edge_width: int64 0-d device tensor, the prediction's edge width (a padded edge head's), read by the kernel
     instead of edge.shape[1]."""
     _need_cuda(verts, exist, edge, tverts, texist, tlabel, col4row, counts, edge_width)
-    if edge_width is not None:
-        return _loss_terms_assigned_ew(verts, exist, edge, tverts, texist, tlabel, col4row, counts, weights, edge_width)
-    B, V, _ = verts.shape
-    Ep = edge.shape[1] if edge is not None else 0
-    Et = tlabel.shape[1] if tlabel is not None else 0
-    dev = verts.device
-    dverts = torch.empty(B, V, 3, dtype=torch.float32, device=dev)
-    dexist = torch.empty(B, V, dtype=torch.float32, device=dev)
-    dedge = torch.empty(B, Ep, dtype=torch.float32, device=dev)
-    losses = torch.empty(4, dtype=torch.float32, device=dev)
-    ws = scratch(B * 3 * 4, dev)
-    check(_lib.load().wf3d_loss_terms_assigned(_p(verts), verts.stride(0), verts.stride(1), _p(exist), _p(edge), Ep,
-                                               _p(tverts), tverts.shape[1], _p(texist), _p(tlabel), Et, _p(col4row),
-                                               _p(counts), B, V, float(weights[0]), float(weights[1]), float(weights[2]),
-                                               _p(dverts), _p(dexist), _p(dedge), _p(losses), _p(ws), ws.numel(),
-                                               _stream()), "loss_terms_assigned")
-    return losses, dverts, dexist, dedge
-
-
-def _loss_terms_assigned_ew(verts, exist, edge, tverts, texist, tlabel, col4row, counts, weights, edge_width):
+    if edge_width is None:
+        return _loss_launch("loss_terms_assigned", verts, exist, edge, tverts, texist, tlabel,
+                            (_p(col4row), _p(counts)), weights)
     if edge_width.dtype != torch.int64 or edge_width.numel() != 1:
         raise RuntimeError("wf3d.loss_terms_assigned: edge_width must be a one-element int64 tensor")
-    B, V, _ = verts.shape
-    Ep = edge.shape[1] if edge is not None else 0
-    Et = tlabel.shape[1] if tlabel is not None else 0
-    dev = verts.device
-    dverts = torch.empty(B, V, 3, dtype=torch.float32, device=dev)
-    dexist = torch.empty(B, V, dtype=torch.float32, device=dev)
-    dedge = torch.empty(B, Ep, dtype=torch.float32, device=dev)
-    losses = torch.empty(4, dtype=torch.float32, device=dev)
-    ws = scratch(B * 3 * 4, dev)
-    check(_lib.load().wf3d_loss_terms_assigned_ew(_p(verts), verts.stride(0), verts.stride(1), _p(exist), _p(edge), Ep,
-                                                  _p(tverts), tverts.shape[1], _p(texist), _p(tlabel), Et, _p(edge_width),
-                                                  _p(col4row), _p(counts), B, V, float(weights[0]), float(weights[1]),
-                                                  float(weights[2]), _p(dverts), _p(dexist), _p(dedge), _p(losses), _p(ws),
-                                                  ws.numel(), _stream()), "loss_terms_assigned_ew")
-    return losses, dverts, dexist, dedge
+    return _loss_launch("loss_terms_assigned_ew", verts, exist, edge, tverts, texist, tlabel,
+                        (_p(edge_width), _p(col4row), _p(counts)), weights)

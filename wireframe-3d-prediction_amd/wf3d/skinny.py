@@ -13,7 +13,7 @@ from . import _lib
 from ._lib import SkinnyBwd, SkinnyFwd, SkinnyRed, check
 from .ops import ACT_NONE, LN_EPS, _need_cuda, _p, _stream
 
-MAX_ROWS = 32
+MAX_ROWS = _lib.DEFINES["WF3D_SKINNY_MAX_ROWS"]
 
 
 def ok(M, *mats):
