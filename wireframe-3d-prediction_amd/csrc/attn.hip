@@ -11,7 +11,7 @@
 //
 // Vertex rows are COMPACT: sample s owns rows voff[s] .. voff[s+1]-1 of every
 // [Rv, *] matrix, so ragged batches cost nothing and no key mask is needed.
-#include "wf3d_common.h"
+#include "attn_args.h"
 
 #include <atomic>
 
@@ -35,18 +35,6 @@ int attn_family(int E, int heads, int vmax) {
     return tiled == 1 ? 2 : 0;
 }
 
-struct AttnParams {
-    const float* qkv;      // [Rv, 3E]
-    float* ctx;            // fwd out [Rv, E]
-    float* lse;            // [Rv, heads]
-    const float* dctx;     // bwd in  [Rv, E]
-    float* dqkv;           // bwd out [Rv, 3E]
-    const int32_t* voff;   // [S+1]
-    int E, heads, hd, vmax, ch;          // ch = rows of K / V (or Q / dctx) staged at a time = min(vmax, 256)
-    float scale;
-    wf3d_seed_t seed; uint32_t thresh; float dscale;
-};
-
 __device__ __forceinline__ float dot_lds(const float* a, const float* b, int hd) {
     float s = 0.f;
     for (int d = 0; d < hd; d += 4) {
@@ -69,11 +57,11 @@ __device__ __forceinline__ void stage_rows(float* dst, const float* __restrict__
     }
 }
 
-// More than p.ch (= min(vmax, 256)) vertices in a sample: the keys are walked in chunks of p.ch rows staged in LDS, each
+// More than p.rows (= min(vmax, 256)) vertices in a sample: the keys are walked in chunks of p.rows rows staged in LDS, each
 // chunk's own softmax (its maximum, its sum, its dropout-masked normalised weights, its partial output) is merged into
 // the running (lse, ctx) rows in global memory:  lse' = log(e^lse + e^lse_c),  ctx' = e^(lse - lse') ctx + e^(lse_c - lse') ctx_c.
 // With one chunk (every BASELINE config: vmax <= 256) nothing is merged and the arithmetic is the single-pass one.
-__global__ __launch_bounds__(256) void attn_fwd_kernel(const AttnParams p) {
+__global__ __launch_bounds__(256) void attn_fwd_kernel(const AttnArgs p) {
     const uint32_t seed = p.thresh ? wf3d_seed_load(p.seed) : 0u;
     extern __shared__ __attribute__((aligned(16))) float sm[];
     const int h = blockIdx.x, s = blockIdx.y;
@@ -81,15 +69,15 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(const AttnParams p) {
     if (n <= 0) return;
     const int hd = p.hd, ldr = hd + 4, E3 = 3 * p.E;
     float* Ks = sm;
-    float* Vs = Ks + p.ch * ldr;
-    float* qb = Vs + p.ch * ldr;                  // [waves][hd]
+    float* Vs = Ks + p.rows * ldr;
+    float* qb = Vs + p.rows * ldr;                  // [waves][hd]
     float* pb = qb + ATT_WAVES * hd;              // [waves][ch]
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     float* q = qb + wave * hd;
-    float* pw = pb + wave * p.ch;
+    float* pw = pb + wave * p.rows;
     const int iters = (n + ATT_WAVES - 1) / ATT_WAVES;
-    for (int kc = 0; kc < n; kc += p.ch) {
-        const int cn = min(p.ch, n - kc);
+    for (int kc = 0; kc < n; kc += p.rows) {
+        const int cn = min(p.rows, n - kc);
         __syncthreads();
         stage_rows(Ks, p.qkv, E3, r0 + kc, cn, p.E + h * hd, hd, 1.0f);
         stage_rows(Vs, p.qkv, E3, r0 + kc, cn, 2 * p.E + h * hd, hd, 1.0f);
@@ -119,7 +107,7 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(const AttnParams p) {
 #pragma unroll
             for (int t = 0; t < 4; ++t) {
                 const int j = lane + 64 * t;
-                if (j < p.ch) {
+                if (j < p.rows) {
                     float pv = sc[t] * inv;
                     if (p.thresh && act && j < cn)
                         pv = wf3d_keep(seed, (uint32_t)((r0 + i) * p.heads + h), (uint32_t)(kc + j), p.thresh) ? pv * p.dscale : 0.f;
@@ -155,9 +143,9 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(const AttnParams p) {
 //            dS_i = P_i∘(dP_i - delta_i),  dQ_i = scale * dS_i·K
 //   sweep 2 (scaled Q, dctx chunks staged; wave per key j): recompute P_:j, dS_:j over queries,
 //            dK_j = dS_:j^T·(scale Q),  dV_j = P~_:j^T·dctx          
-// No atomics: every dq/dk/dv element is produced by exactly one wave; with more than p.ch vertices the partial sums of
+// No atomics: every dq/dk/dv element is produced by exactly one wave; with more than p.rows vertices the partial sums of
 // the chunks are accumulated by that wave in global memory, in chunk order.
-__global__ __launch_bounds__(256) void attn_bwd_kernel(const AttnParams p) {
+__global__ __launch_bounds__(256) void attn_bwd_kernel(const AttnArgs p) {
     const uint32_t seed = p.thresh ? wf3d_seed_load(p.seed) : 0u;
     extern __shared__ __attribute__((aligned(16))) float sm[];
     const int h = blockIdx.x, s = blockIdx.y;
@@ -165,22 +153,22 @@ __global__ __launch_bounds__(256) void attn_bwd_kernel(const AttnParams p) {
     if (n <= 0) return;
     const int hd = p.hd, ldr = hd + 4, E3 = 3 * p.E;
     float* Xa = sm;                               // sweep 1: K      sweep 2: scaled Q
-    float* Xb = Xa + p.ch * ldr;                  // sweep 1: V      sweep 2: dctx
-    float* qb = Xb + p.ch * ldr;                  // [waves][hd]
+    float* Xb = Xa + p.rows * ldr;                  // sweep 1: V      sweep 2: dctx
+    float* qb = Xb + p.rows * ldr;                  // [waves][hd]
     float* ob = qb + ATT_WAVES * hd;              // [waves][hd]
     float* pb = ob + ATT_WAVES * hd;              // [waves][ch]  dS
-    float* pb2 = pb + ATT_WAVES * p.ch;           // [waves][ch]  P~ (sweep 2)
-    float* dl = pb2 + ATT_WAVES * p.ch;           // [ch] delta_i of the staged queries (sweep 2)
-    float* ls = dl + p.ch;                        // [ch] lse_i of the staged queries (sweep 2)
+    float* pb2 = pb + ATT_WAVES * p.rows;           // [waves][ch]  P~ (sweep 2)
+    float* dl = pb2 + ATT_WAVES * p.rows;           // [ch] delta_i of the staged queries (sweep 2)
+    float* ls = dl + p.rows;                        // [ch] lse_i of the staged queries (sweep 2)
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int iters = (n + ATT_WAVES - 1) / ATT_WAVES;
     float* q = qb + wave * hd;
     float* o = ob + wave * hd;
-    float* pw = pb + wave * p.ch;
-    float* pw2 = pb2 + wave * p.ch;
+    float* pw = pb + wave * p.rows;
+    float* pw2 = pb2 + wave * p.rows;
 
-    for (int kc = 0; kc < n; kc += p.ch) {
-        const int cn = min(p.ch, n - kc);
+    for (int kc = 0; kc < n; kc += p.rows) {
+        const int cn = min(p.rows, n - kc);
         __syncthreads();
         stage_rows(Xa, p.qkv, E3, r0 + kc, cn, p.E + h * hd, hd, 1.0f);
         stage_rows(Xb, p.qkv, E3, r0 + kc, cn, 2 * p.E + h * hd, hd, 1.0f);
@@ -210,7 +198,7 @@ __global__ __launch_bounds__(256) void attn_bwd_kernel(const AttnParams p) {
                         g = wf3d_keep(seed, (uint32_t)((r0 + i) * p.heads + h), (uint32_t)(kc + j), p.thresh) ? g * p.dscale : 0.f;
                     ds = pr * (g - dsum);
                 }
-                if (j < p.ch) pw[j] = ds;
+                if (j < p.rows) pw[j] = ds;
             }
             __syncthreads();
             if (act) {
@@ -225,8 +213,8 @@ __global__ __launch_bounds__(256) void attn_bwd_kernel(const AttnParams p) {
         }
     }
     // sweep 2
-    for (int qc = 0; qc < n; qc += p.ch) {
-        const int cn = min(p.ch, n - qc);
+    for (int qc = 0; qc < n; qc += p.rows) {
+        const int cn = min(p.rows, n - qc);
         __syncthreads();
         stage_rows(Xa, p.qkv, E3, r0 + qc, cn, h * hd, hd, p.scale);
         stage_rows(Xb, p.dctx, p.E, r0 + qc, cn, h * hd, hd, 1.0f);
@@ -260,7 +248,7 @@ __global__ __launch_bounds__(256) void attn_bwd_kernel(const AttnParams p) {
                     ds = pr * (g * mk - dl[i]);
                     pt = pr * mk;
                 }
-                if (i < p.ch) { pw[i] = ds; pw2[i] = pt; }
+                if (i < p.rows) { pw[i] = ds; pw2[i] = pt; }
             }
             __syncthreads();
             if (act) {
@@ -321,22 +309,12 @@ extern "C" int wf3d_attn_fwd(const float* qkv, const int32_t* voff, int S, int v
     if (S == 0 || vmax == 0) return WF3D_OK;
     WF3D_CHECK(qkv && voff && ctx && lse, WF3D_ERR_ARG, "wf3d_attn_fwd: null pointer");
     WF3D_CHECK(drop_p >= 0.f && drop_p < 1.f, WF3D_ERR_ARG, "wf3d_attn_fwd: bad drop_p");
+    AttnArgs p = wf3d_attn_args(qkv, voff, E, heads, drop_p, drop_seed, ctx, lse, nullptr, nullptr);
     const int family = attn_family(E, heads, vmax);
-    if (family == 1) return wf3d_attn_fwd_mfma(qkv, voff, S, vmax, E, heads, drop_p, drop_seed, ctx, lse, stream);
-    if (family == 2) return wf3d_attn_fwd_tiled(qkv, voff, S, vmax, E, heads, drop_p, drop_seed, ctx, lse, stream);
-    AttnParams p{};
-    p.qkv = qkv; p.ctx = ctx; p.lse = lse; p.voff = voff;
-    p.E = E; p.heads = heads; p.hd = E / heads; p.vmax = vmax; p.ch = attn_chunk(vmax);
-    p.scale = 1.0f / sqrtf((float)p.hd);
-    if (drop_p > 0.f) { p.seed = wf3d_seed_arg(drop_p, drop_seed); p.thresh = (uint32_t)((double)drop_p * 4294967296.0); p.dscale = 1.0f / (1.0f - drop_p); }
-    const size_t lds = attn_lds_bytes(vmax, p.hd, false);
-    if (lds > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute((const void*)attn_fwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        WF3D_CHECK(e == hipSuccess, WF3D_ERR_LAUNCH, "wf3d_attn_fwd: cannot raise dynamic LDS to %zu", lds);
-    }
-    hipLaunchKernelGGL(attn_fwd_kernel, dim3(heads, S), dim3(256), lds, (hipStream_t)stream, p);
-    WF3D_LAUNCH_CHECK();
-    return WF3D_OK;
+    if (family != 0) return wf3d_attn_mfma_launch(p, family, false, S, vmax, (hipStream_t)stream);
+    p.rows = attn_chunk(vmax);
+    return wf3d_attn_launch("wf3d_attn_fwd", attn_fwd_kernel, dim3(heads, S), attn_lds_bytes(vmax, p.hd, false), p,
+                            (hipStream_t)stream);
 }
 
 extern "C" int wf3d_attn_bwd(const float* qkv, const float* dctx, const float* ctx, const float* lse,
@@ -347,20 +325,10 @@ extern "C" int wf3d_attn_bwd(const float* qkv, const float* dctx, const float* c
     if (S == 0 || vmax == 0) return WF3D_OK;
     WF3D_CHECK(qkv && dctx && ctx && lse && voff && dqkv, WF3D_ERR_ARG, "wf3d_attn_bwd: null pointer");
     WF3D_CHECK(drop_p >= 0.f && drop_p < 1.f, WF3D_ERR_ARG, "wf3d_attn_bwd: bad drop_p");
+    AttnArgs p = wf3d_attn_args(qkv, voff, E, heads, drop_p, drop_seed, ctx, lse, dctx, dqkv);
     const int family = attn_family(E, heads, vmax);
-    if (family == 1) return wf3d_attn_bwd_mfma(qkv, dctx, ctx, lse, voff, S, vmax, E, heads, drop_p, drop_seed, dqkv, stream);
-    if (family == 2) return wf3d_attn_bwd_tiled(qkv, dctx, ctx, lse, voff, S, vmax, E, heads, drop_p, drop_seed, dqkv, stream);
-    AttnParams p{};
-    p.qkv = qkv; p.dctx = dctx; p.ctx = (float*)ctx; p.lse = (float*)lse; p.dqkv = dqkv; p.voff = voff;
-    p.E = E; p.heads = heads; p.hd = E / heads; p.vmax = vmax; p.ch = attn_chunk(vmax);
-    p.scale = 1.0f / sqrtf((float)p.hd);
-    if (drop_p > 0.f) { p.seed = wf3d_seed_arg(drop_p, drop_seed); p.thresh = (uint32_t)((double)drop_p * 4294967296.0); p.dscale = 1.0f / (1.0f - drop_p); }
-    const size_t lds = attn_lds_bytes(vmax, p.hd, true);
-    if (lds > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute((const void*)attn_bwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        WF3D_CHECK(e == hipSuccess, WF3D_ERR_LAUNCH, "wf3d_attn_bwd: cannot raise dynamic LDS to %zu", lds);
-    }
-    hipLaunchKernelGGL(attn_bwd_kernel, dim3(heads, S), dim3(256), lds, (hipStream_t)stream, p);
-    WF3D_LAUNCH_CHECK();
-    return WF3D_OK;
+    if (family != 0) return wf3d_attn_mfma_launch(p, family, true, S, vmax, (hipStream_t)stream);
+    p.rows = attn_chunk(vmax);
+    return wf3d_attn_launch("wf3d_attn_bwd", attn_bwd_kernel, dim3(heads, S), attn_lds_bytes(vmax, p.hd, true), p,
+                            (hipStream_t)stream);
 }

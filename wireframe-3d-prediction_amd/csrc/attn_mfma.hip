@@ -1,6 +1,6 @@
 // MFMA self-attention for head_dim = 64 (the reference's 512/8), exact-fp32 matrix cores
-// (v_mfma_f32_32x32x2_f32), one workgroup per (head, sample), K/V (or Q/dO) rows of the sample
-// resident in LDS, each wave64 owning 32-row query (or key) blocks.
+// (v_mfma_f32_32x32x2_f32), 256 threads, each wave64 owning 32-row query (or key) blocks while the other operand's
+// rows sit in LDS.
 //
 // Orientation trick: the score tile is computed TRANSPOSED, S^T = K·Q^T, so that the softmax axis
 // (keys) runs over a lane's accumulator registers (+ one exchange with lane^32) and never across
@@ -14,20 +14,26 @@
 // Backward = two sweeps with the same LDS footprint (no atomics): sweep 1 per query block
 // (S^T, dP^T = V·dO^T, dS^T, dQ^T = K^T·dS^T), sweep 2 per key block with the roles of rows and
 // columns swapped (S = Q·K^T, dP = dO·V^T, dK^T = Q^T·dS, dV^T = dO^T·P).  delta_i = dO_i·O_i.
-#include "wf3d_common.h"
+//
+// Shared pieces ("tile steps" below): zero2, store_tile_row and row_delta serve every kernel; dq_tile (sweep 1 against a
+// 32-row block of a K / V tile) and dkv_tile (sweep 2 against a 32-row block of a scaled-Q / dO tile with its lse and
+// delta rows) state the backward arithmetic and serve the resident backward kernel.  Two ownership schemes:
+//   resident (attn_fwd/bwd_mfma_kernel, up to 256 vertices): one workgroup per (head, sample) stages the WHOLE sample
+//     once (the "tile" is the sample, first row 0), its waves loop over the 32-row blocks; softmax in two passes over
+//     the sample's score tiles held in registers; backward restages between the sweeps in one launch.
+//   key-tiled (attn_fwd_tiled_kernel, attn_bwd_tiled_dq/dkv_kernel, any vertex count): one workgroup per (head, sample,
+//     group of 4 row blocks), each wave keeps ONE block for the whole kernel and the other operand is walked in tiles
+//     of KT rows; online softmax; one launch per backward sweep.
+// The key-tiled backward kernels keep dq_tile's / dkv_tile's body (first row k0 / i0 instead of 0) and their zero fill
+// written out, and both forward kernels their score step (S^T tiles, key mask, running maximum): called as shared steps
+// these compile to other instruction streams that measured 0.1 - 0.15 % (tiled backward, per kernel) and 0.5 - 0.9 %
+// (forward) slower.  A change to one copy of a step goes into the other.
+#include "attn_args.h"
 
 namespace {
 
 constexpr int HD = 64;
 constexpr int LDR = HD + 4;                 // padded LDS row (floats): 16 lanes of a b128 group hit 16 slots
-
-struct MAttn {
-    const float* qkv; const float* ctx_in; float* ctx; float* lse; const float* dctx; float* dqkv;
-    const int32_t* voff;
-    int E, heads, vpad;                     // vpad = rows reserved per operand in LDS (multiple of 32)
-    float scale;
-    wf3d_seed_t seed; uint32_t thresh; float dscale;
-};
 
 __device__ __forceinline__ int rowof(int e, int h) { return (e & 3) + 8 * (e >> 2) + 4 * h; }
 
@@ -67,7 +73,90 @@ __device__ __forceinline__ f32x16 mm_rows_regs(const float* lds_row_half, const 
     return acc;
 }
 
-__global__ __launch_bounds__(256, 1) void attn_fwd_mfma_kernel(const MAttn p) {
+// ---- tile steps ------------------------------------------------------------------------------------------------------
+// A lane is (l31 = lane & 31: its row of the wave's 32-row block, h = lane >> 5: its half); a staged tile holds `nt`
+// 32-row blocks and starts at row k0 (keys) or i0 (queries) of the sample.
+
+__device__ __forceinline__ void zero2(f32x16 (&a)[2]) {
+#pragma unroll
+    for (int dt = 0; dt < 2; ++dt)
+#pragma unroll
+        for (int e = 0; e < 16; ++e) a[dt][e] = 0.f;
+}
+
+// this lane's row of a [32 rows x 64] transposed accumulator pair, times mul, to out[0..64)
+__device__ __forceinline__ void store_tile_row(float* out, const f32x16 (&o)[2], int h, float mul) {
+#pragma unroll
+    for (int dt = 0; dt < 2; ++dt)
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+            f32x4 v = {o[dt][4 * g], o[dt][4 * g + 1], o[dt][4 * g + 2], o[dt][4 * g + 3]};
+            *reinterpret_cast<f32x4*>(out + dt * 32 + 8 * g + 4 * h) = v * mul;
+        }
+}
+
+// delta_i = dO_i . O_i from this lane's half row of ctx (op; zero when !ok) and of dO (df), summed over both halves
+__device__ __forceinline__ float row_delta(const float* op, bool ok, const float (&df)[32]) {
+    float delta = 0.f;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+        f32x4 v = {0.f, 0.f, 0.f, 0.f};
+        if (ok) v = *reinterpret_cast<const f32x4*>(op + 4 * k);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) delta += v[j] * df[4 * k + j];
+    }
+    return delta + __shfl_xor(delta, 32, 64);
+}
+
+// backward sweep 1, block jt of a staged K / V tile: dq += (K block)^T · dS^T for this lane's query (mask row `row`,
+// scaled q in qf, dO in df).
+__device__ __forceinline__ void dq_tile(f32x16 (&dq)[2], const AttnArgs& p, uint32_t seed, const float* Ks,
+                                        const float* Vs, int jt, int k0, int n, uint32_t row, const float (&qf)[32],
+                                        const float (&df)[32], float lse_i, float delta, int l31, int h) {
+    const f32x16 st = mm_rows_regs(Ks + (jt * 32 + l31) * LDR + 32 * h, qf);
+    const f32x16 dp = mm_rows_regs(Vs + (jt * 32 + l31) * LDR + 32 * h, df);
+#pragma unroll
+    for (int e = 0; e < 16; ++e) {
+        const int jl = jt * 32 + rowof(e, h), j = k0 + jl;
+        const float pr = j < n ? expf(st[e] - lse_i) : 0.f;
+        float g = dp[e];
+        if (p.thresh) g = wf3d_keep(seed, row, (uint32_t)j, p.thresh) ? g * p.dscale : 0.f;
+        const float ds = pr * (g - delta);
+        const float* kr = Ks + jl * LDR + l31;
+        dq[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(kr[0], ds, dq[0], 0, 0, 0);
+        dq[1] = __builtin_amdgcn_mfma_f32_32x32x2f32(kr[32], ds, dq[1], 0, 0, 0);
+    }
+}
+
+// backward sweep 2, block `it` of a staged (scaled Q, dO) tile: dk += (Q block)^T · dS, dv += (dO block)^T · P~ for this
+// lane's key j (k in kf, v in vf); dl / ls = delta_i / lse_i of the tile's rows (lse = +inf for padded queries); row0 =
+// the tile's first row in [Rv, *].
+__device__ __forceinline__ void dkv_tile(f32x16 (&dk)[2], f32x16 (&dv)[2], const AttnArgs& p, uint32_t seed,
+                                         const float* Qs, const float* Gs, const float* dl, const float* ls, int it,
+                                         int row0, int head, int j, const float (&kf)[32], const float (&vf)[32],
+                                         int l31, int h) {
+    const f32x16 sc = mm_rows_regs(Qs + (it * 32 + l31) * LDR + 32 * h, kf);     // S[i][j], rows = queries
+    const f32x16 dp = mm_rows_regs(Gs + (it * 32 + l31) * LDR + 32 * h, vf);     // dP[i][j]
+#pragma unroll
+    for (int e = 0; e < 16; ++e) {
+        const int il = it * 32 + rowof(e, h);
+        const float pr = expf(sc[e] - ls[il]);                                   // 0 for padded queries
+        float mk = 1.0f;
+        if (p.thresh) mk = wf3d_keep(seed, (uint32_t)((row0 + il) * p.heads + head), (uint32_t)j, p.thresh) ? p.dscale : 0.f;
+        const float ds = pr * (dp[e] * mk - dl[il]);
+        const float pt = pr * mk;
+        const float* qr = Qs + il * LDR + l31;
+        const float* gr = Gs + il * LDR + l31;
+        dk[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(qr[0], ds, dk[0], 0, 0, 0);
+        dk[1] = __builtin_amdgcn_mfma_f32_32x32x2f32(qr[32], ds, dk[1], 0, 0, 0);
+        dv[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(gr[0], pt, dv[0], 0, 0, 0);
+        dv[1] = __builtin_amdgcn_mfma_f32_32x32x2f32(gr[32], pt, dv[1], 0, 0, 0);
+    }
+}
+
+// ---- resident: the sample's rows in LDS, p.rows (a multiple of 32) reserved per operand -----------------------------
+
+__global__ __launch_bounds__(256, 1) void attn_fwd_mfma_kernel(const AttnArgs p) {
     const uint32_t seed = p.thresh ? wf3d_seed_load(p.seed) : 0u;
     extern __shared__ __attribute__((aligned(16))) float sm[];
     const int head = blockIdx.x, s = blockIdx.y;
@@ -76,7 +165,7 @@ __global__ __launch_bounds__(256, 1) void attn_fwd_mfma_kernel(const MAttn p) {
     const int npad = (n + 31) & ~31, nt = npad >> 5;
     const int E3 = 3 * p.E;
     float* Ks = sm;
-    float* Vs = sm + p.vpad * LDR;
+    float* Vs = sm + p.rows * LDR;
     stage64(Ks, p.qkv, E3, r0, n, npad, p.E + head * HD, 1.0f);
     stage64(Vs, p.qkv, E3, r0, n, npad, 2 * p.E + head * HD, 1.0f);
     __syncthreads();
@@ -113,10 +202,7 @@ __global__ __launch_bounds__(256, 1) void attn_fwd_mfma_kernel(const MAttn p) {
         const float inv = 1.0f / l;
         if (iok && h == 0) p.lse[(size_t)(r0 + i) * p.heads + head] = m + logf(l);
         f32x16 o[2];
-#pragma unroll
-        for (int dt = 0; dt < 2; ++dt)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) o[dt][e] = 0.f;
+        zero2(o);
 #pragma unroll
         for (int jt = 0; jt < 8; ++jt) {
             if (jt < nt) {
@@ -131,20 +217,11 @@ __global__ __launch_bounds__(256, 1) void attn_fwd_mfma_kernel(const MAttn p) {
                 }
             }
         }
-        if (iok) {
-            float* out = p.ctx + (size_t)(r0 + i) * p.E + head * HD;
-#pragma unroll
-            for (int dt = 0; dt < 2; ++dt)
-#pragma unroll
-                for (int g = 0; g < 4; ++g) {
-                    f32x4 v = {o[dt][4 * g], o[dt][4 * g + 1], o[dt][4 * g + 2], o[dt][4 * g + 3]};
-                    *reinterpret_cast<f32x4*>(out + dt * 32 + 8 * g + 4 * h) = v;
-                }
-        }
+        if (iok) store_tile_row(p.ctx + (size_t)(r0 + i) * p.E + head * HD, o, h, 1.0f);
     }
 }
 
-__global__ __launch_bounds__(256) void attn_bwd_mfma_kernel(const MAttn p) {
+__global__ __launch_bounds__(256) void attn_bwd_mfma_kernel(const AttnArgs p) {
     const uint32_t seed = p.thresh ? wf3d_seed_load(p.seed) : 0u;
     extern __shared__ __attribute__((aligned(16))) float sm[];
     const int head = blockIdx.x, s = blockIdx.y;
@@ -152,10 +229,11 @@ __global__ __launch_bounds__(256) void attn_bwd_mfma_kernel(const MAttn p) {
     if (n <= 0) return;
     const int npad = (n + 31) & ~31, nt = npad >> 5;
     const int E3 = 3 * p.E;
+    const float* ctx = p.ctx;
     float* Xa = sm;                                        // sweep 1: K        sweep 2: scaled Q
-    float* Xb = sm + p.vpad * LDR;                         // sweep 1: V        sweep 2: dO
-    float* dl = Xb + p.vpad * LDR;                         // [vpad] delta_i
-    float* ls = dl + p.vpad;                               // [vpad] lse_i (+inf for padded queries)
+    float* Xb = sm + p.rows * LDR;                         // sweep 1: V        sweep 2: dO
+    float* dl = Xb + p.rows * LDR;                         // [rows] delta_i
+    float* ls = dl + p.rows;                               // [rows] lse_i (+inf for padded queries)
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int l31 = lane & 31, h = lane >> 5;
 
@@ -171,50 +249,14 @@ __global__ __launch_bounds__(256) void attn_bwd_mfma_kernel(const MAttn p) {
         float qf[32], df[32];
         load_half_row(qf, p.qkv + (size_t)(r0 + i) * E3 + head * HD + 32 * h, iok, p.scale);
         load_half_row(df, p.dctx + (size_t)(r0 + i) * p.E + head * HD + 32 * h, iok, 1.0f);
-        float delta = 0.f;
-        {
-            const float* op = p.ctx_in + (size_t)(r0 + i) * p.E + head * HD + 32 * h;
-#pragma unroll
-            for (int k = 0; k < 8; ++k) {
-                f32x4 v = {0.f, 0.f, 0.f, 0.f};
-                if (iok) v = *reinterpret_cast<const f32x4*>(op + 4 * k);
-#pragma unroll
-                for (int j = 0; j < 4; ++j) delta += v[j] * df[4 * k + j];
-            }
-            delta += __shfl_xor(delta, 32, 64);
-        }
+        const float delta = row_delta(ctx + (size_t)(r0 + i) * p.E + head * HD + 32 * h, iok, df);
         if (h == 0) dl[i] = delta;
         const float lse_i = iok ? ls[i] : INFINITY;
         f32x16 dq[2];
-#pragma unroll
-        for (int dt = 0; dt < 2; ++dt)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) dq[dt][e] = 0.f;
-        for (int jt = 0; jt < nt; ++jt) {
-            const f32x16 st = mm_rows_regs(Xa + (jt * 32 + l31) * LDR + 32 * h, qf);
-            const f32x16 dp = mm_rows_regs(Xb + (jt * 32 + l31) * LDR + 32 * h, df);
-#pragma unroll
-            for (int e = 0; e < 16; ++e) {
-                const int j = jt * 32 + rowof(e, h);
-                const float pr = j < n ? expf(st[e] - lse_i) : 0.f;
-                float g = dp[e];
-                if (p.thresh) g = wf3d_keep(seed, (uint32_t)((r0 + i) * p.heads + head), (uint32_t)j, p.thresh) ? g * p.dscale : 0.f;
-                const float ds = pr * (g - delta);
-                const float* kr = Xa + j * LDR + l31;
-                dq[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(kr[0], ds, dq[0], 0, 0, 0);
-                dq[1] = __builtin_amdgcn_mfma_f32_32x32x2f32(kr[32], ds, dq[1], 0, 0, 0);
-            }
-        }
-        if (iok) {
-            float* out = p.dqkv + (size_t)(r0 + i) * E3 + head * HD;
-#pragma unroll
-            for (int dt = 0; dt < 2; ++dt)
-#pragma unroll
-                for (int g = 0; g < 4; ++g) {
-                    f32x4 v = {dq[dt][4 * g], dq[dt][4 * g + 1], dq[dt][4 * g + 2], dq[dt][4 * g + 3]};
-                    *reinterpret_cast<f32x4*>(out + dt * 32 + 8 * g + 4 * h) = v * p.scale;
-                }
-        }
+        zero2(dq);
+        for (int jt = 0; jt < nt; ++jt)
+            dq_tile(dq, p, seed, Xa, Xb, jt, 0, n, (uint32_t)((r0 + i) * p.heads + head), qf, df, lse_i, delta, l31, h);
+        if (iok) store_tile_row(p.dqkv + (size_t)(r0 + i) * E3 + head * HD, dq, h, p.scale);
     }
     __syncthreads();
     // ---- sweep 2: per key block -> dK, dV   (Xa = scaled Q, Xb = dO)
@@ -228,69 +270,28 @@ __global__ __launch_bounds__(256) void attn_bwd_mfma_kernel(const MAttn p) {
         load_half_row(kf, p.qkv + (size_t)(r0 + j) * E3 + p.E + head * HD + 32 * h, jok, 1.0f);
         load_half_row(vf, p.qkv + (size_t)(r0 + j) * E3 + 2 * p.E + head * HD + 32 * h, jok, 1.0f);
         f32x16 dk[2], dv[2];
-#pragma unroll
-        for (int dt = 0; dt < 2; ++dt)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) { dk[dt][e] = 0.f; dv[dt][e] = 0.f; }
-        for (int it = 0; it < nt; ++it) {
-            const f32x16 sc = mm_rows_regs(Xa + (it * 32 + l31) * LDR + 32 * h, kf);     // S[i][j], rows = queries
-            const f32x16 dp = mm_rows_regs(Xb + (it * 32 + l31) * LDR + 32 * h, vf);     // dP[i][j]
-#pragma unroll
-            for (int e = 0; e < 16; ++e) {
-                const int i = it * 32 + rowof(e, h);
-                const float pr = expf(sc[e] - ls[i]);                                    // 0 for padded queries
-                float mk = 1.0f;
-                if (p.thresh) mk = wf3d_keep(seed, (uint32_t)((r0 + i) * p.heads + head), (uint32_t)j, p.thresh) ? p.dscale : 0.f;
-                const float ds = pr * (dp[e] * mk - dl[i]);
-                const float pt = pr * mk;
-                const float* qr = Xa + i * LDR + l31;
-                const float* gr = Xb + i * LDR + l31;
-                dk[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(qr[0], ds, dk[0], 0, 0, 0);
-                dk[1] = __builtin_amdgcn_mfma_f32_32x32x2f32(qr[32], ds, dk[1], 0, 0, 0);
-                dv[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(gr[0], pt, dv[0], 0, 0, 0);
-                dv[1] = __builtin_amdgcn_mfma_f32_32x32x2f32(gr[32], pt, dv[1], 0, 0, 0);
-            }
-        }
+        zero2(dk);
+        zero2(dv);
+        for (int it = 0; it < nt; ++it) dkv_tile(dk, dv, p, seed, Xa, Xb, dl, ls, it, r0, head, j, kf, vf, l31, h);
         if (jok) {
-            float* ok_ = p.dqkv + (size_t)(r0 + j) * E3 + p.E + head * HD;
-            float* ov_ = p.dqkv + (size_t)(r0 + j) * E3 + 2 * p.E + head * HD;
-#pragma unroll
-            for (int dt = 0; dt < 2; ++dt)
-#pragma unroll
-                for (int g = 0; g < 4; ++g) {
-                    f32x4 a = {dk[dt][4 * g], dk[dt][4 * g + 1], dk[dt][4 * g + 2], dk[dt][4 * g + 3]};
-                    f32x4 b = {dv[dt][4 * g], dv[dt][4 * g + 1], dv[dt][4 * g + 2], dv[dt][4 * g + 3]};
-                    *reinterpret_cast<f32x4*>(ok_ + dt * 32 + 8 * g + 4 * h) = a;
-                    *reinterpret_cast<f32x4*>(ov_ + dt * 32 + 8 * g + 4 * h) = b;
-                }
+            store_tile_row(p.dqkv + (size_t)(r0 + j) * E3 + p.E + head * HD, dk, h, 1.0f);
+            store_tile_row(p.dqkv + (size_t)(r0 + j) * E3 + 2 * p.E + head * HD, dv, h, 1.0f);
         }
     }
 }
 
-// ---- key-tiled ("flash" form) variant: any vertex count --------------------------------------------------------------
-// Same arithmetic and operand orientation as the resident kernels above; what changes is who owns what.  A workgroup is
-// (head, sample, group of 4 row blocks): each wave keeps ONE 32-row block for the whole kernel and the other operand is
-// walked in tiles of KT rows staged in LDS.  KT = 128: two tiles are 2 x 128 x 68 floats = 68 KiB, so two workgroups
-// share a CU's 160 KiB (one stages while the other computes; the kernels fit 256 registers per lane, the two-per-SIMD
-// budget), and a sample of V vertices is ceil(V / 128) workgroups per head instead of one, which is what fills the chip
-// at small batch.  Forward: online softmax, the running maximum m, sum l and the output tile o[2] stay in registers and
-// are rescaled by exp(m_old - m_new) per tile; dropout multiplies what goes into o, never what goes into l, so the
-// result is keep * dscale * softmax as in the resident kernel.  Backward: sweep 1 (dQ) walks K / V tiles, sweep 2
-// (dK, dV) walks tiles of scaled Q and dO with lse and delta_i = dO_i . O_i (recomputed while dO is staged) beside them.
+// ---- key-tiled ("flash" form): any vertex count ----------------------------------------------------------------------
+// A workgroup is (head, sample, group of 4 row blocks).  KT = 128: two tiles are 2 x 128 x 68 floats = 68 KiB, so two
+// workgroups share a CU's 160 KiB (one stages while the other computes; the kernels fit 256 registers per lane, the
+// two-per-SIMD budget), and a sample of V vertices is ceil(V / 128) workgroups per head instead of one, which is what
+// fills the chip at small batch.  Forward: online softmax, the running maximum m, sum l and the output tile o[2] stay
+// in registers and are rescaled by exp(m_old - m_new) per tile; dropout multiplies what goes into o, never what goes
+// into l, so the result is keep * dscale * softmax as in the resident kernel.  Backward: sweep 1 (dQ) walks K / V tiles,
+// sweep 2 (dK, dV) walks tiles of scaled Q and dO with lse and delta_i (recomputed while dO is staged) beside them.
 // Every output row is written by one wave in a fixed tile order: no atomics, bit-reproducible.
 constexpr int KT = 128;
 
-__device__ __forceinline__ void store_tile_row(float* out, const f32x16 (&o)[2], int h, float mul) {
-#pragma unroll
-    for (int dt = 0; dt < 2; ++dt)
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-            f32x4 v = {o[dt][4 * g], o[dt][4 * g + 1], o[dt][4 * g + 2], o[dt][4 * g + 3]};
-            *reinterpret_cast<f32x4*>(out + dt * 32 + 8 * g + 4 * h) = v * mul;
-        }
-}
-
-__global__ __launch_bounds__(256, 2) void attn_fwd_tiled_kernel(const MAttn p) {
+__global__ __launch_bounds__(256, 2) void attn_fwd_tiled_kernel(const AttnArgs p) {
     const uint32_t seed = p.thresh ? wf3d_seed_load(p.seed) : 0u;
     extern __shared__ __attribute__((aligned(16))) float sm[];
     const int head = blockIdx.x, s = blockIdx.y, q0 = blockIdx.z * KT;
@@ -308,10 +309,7 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_tiled_kernel(const MAttn p) {
     load_half_row(qf, p.qkv + (size_t)(r0 + i) * E3 + head * HD + 32 * h, iok, p.scale);
     float m = -INFINITY, l = 0.f;
     f32x16 o[2];
-#pragma unroll
-    for (int dt = 0; dt < 2; ++dt)
-#pragma unroll
-        for (int e = 0; e < 16; ++e) o[dt][e] = 0.f;
+    zero2(o);
     for (int k0 = 0; k0 < n; k0 += KT) {
         const int tn = min(KT, n - k0), tpad = (tn + 31) & ~31, nt = tpad >> 5;
         if (k0) __syncthreads();
@@ -363,14 +361,16 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_tiled_kernel(const MAttn p) {
     }
 }
 
-// backward sweep 1: a wave owns a query block, K / V are walked in tiles -> dQ
-__global__ __launch_bounds__(256, 2) void attn_bwd_tiled_dq_kernel(const MAttn p) {
+// backward sweep 1: a wave owns a query block, K / V are walked in tiles -> dQ.  The dQ step (dq_tile's body) and the
+// zero fill are written out: called, they cost 0.1 % at 8 x 513.
+__global__ __launch_bounds__(256, 2) void attn_bwd_tiled_dq_kernel(const AttnArgs p) {
     const uint32_t seed = p.thresh ? wf3d_seed_load(p.seed) : 0u;
     extern __shared__ __attribute__((aligned(16))) float sm[];
     const int head = blockIdx.x, s = blockIdx.y, q0 = blockIdx.z * KT;
     const int r0 = p.voff[s], n = p.voff[s + 1] - r0;
     if (n <= 0 || q0 >= n) return;
     const int E3 = 3 * p.E;
+    const float* ctx = p.ctx;
     float* Ks = sm;
     float* Vs = sm + KT * LDR;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -381,18 +381,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_tiled_dq_kernel(const MAttn p
     float qf[32], df[32];
     load_half_row(qf, p.qkv + (size_t)(r0 + i) * E3 + head * HD + 32 * h, iok, p.scale);
     load_half_row(df, p.dctx + (size_t)(r0 + i) * p.E + head * HD + 32 * h, iok, 1.0f);
-    float delta = 0.f;
-    {
-        const float* op = p.ctx_in + (size_t)(r0 + i) * p.E + head * HD + 32 * h;
-#pragma unroll
-        for (int k = 0; k < 8; ++k) {
-            f32x4 v = {0.f, 0.f, 0.f, 0.f};
-            if (iok) v = *reinterpret_cast<const f32x4*>(op + 4 * k);
-#pragma unroll
-            for (int j = 0; j < 4; ++j) delta += v[j] * df[4 * k + j];
-        }
-        delta += __shfl_xor(delta, 32, 64);
-    }
+    const float delta = row_delta(ctx + (size_t)(r0 + i) * p.E + head * HD + 32 * h, iok, df);
     const float lse_i = iok ? p.lse[(size_t)(r0 + i) * p.heads + head] : INFINITY;
     f32x16 dq[2];
 #pragma unroll
@@ -425,14 +414,16 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_tiled_dq_kernel(const MAttn p
     if (iok) store_tile_row(p.dqkv + (size_t)(r0 + i) * E3 + head * HD, dq, h, p.scale);
 }
 
-// backward sweep 2: a wave owns a key block, scaled Q / dO (+ lse, delta) are walked in tiles -> dK, dV
-__global__ __launch_bounds__(256, 2) void attn_bwd_tiled_dkv_kernel(const MAttn p) {
+// backward sweep 2: a wave owns a key block, scaled Q / dO (+ lse, delta) are walked in tiles -> dK, dV.  As in the dQ
+// kernel the step (dkv_tile's body) and the zero fill are written out: called, they cost 0.1 - 0.15 % at 8 x 513.
+__global__ __launch_bounds__(256, 2) void attn_bwd_tiled_dkv_kernel(const AttnArgs p) {
     const uint32_t seed = p.thresh ? wf3d_seed_load(p.seed) : 0u;
     extern __shared__ __attribute__((aligned(16))) float sm[];
     const int head = blockIdx.x, s = blockIdx.y, j0 = blockIdx.z * KT;
     const int r0 = p.voff[s], n = p.voff[s + 1] - r0;
     if (n <= 0 || j0 >= n) return;
     const int E3 = 3 * p.E;
+    const float* ctx = p.ctx;
     float* Qs = sm;                                        // scaled Q tile
     float* Gs = sm + KT * LDR;                             // dO tile
     float* dl = Gs + KT * LDR;                             // [KT] delta_i
@@ -462,7 +453,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_tiled_dkv_kernel(const MAttn 
             if (r < tn) {
                 const size_t at = (size_t)(r0 + i0 + r) * p.E + head * HD + c;
                 g = *reinterpret_cast<const f32x4*>(p.dctx + at);
-                const f32x4 ov = *reinterpret_cast<const f32x4*>(p.ctx_in + at);
+                const f32x4 ov = *reinterpret_cast<const f32x4*>(ctx + at);
                 d = g[0] * ov[0] + g[1] * ov[1] + g[2] * ov[2] + g[3] * ov[3];
             }
             *reinterpret_cast<f32x4*>(Gs + r * LDR + c) = g;
@@ -501,76 +492,23 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_tiled_dkv_kernel(const MAttn 
     }
 }
 
-template <typename K>
-int launch_tiled(const char* who, K kernel, const MAttn& p, int S, int vmax, size_t lds, void* stream) {
-    hipError_t e = hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    WF3D_CHECK(e == hipSuccess, WF3D_ERR_LAUNCH, "%s: cannot raise dynamic LDS to %zu", who, lds);
-    hipLaunchKernelGGL(kernel, dim3(p.heads, S, wf3d_cdiv(vmax, KT)), dim3(256), lds, (hipStream_t)stream, p);
-    WF3D_LAUNCH_CHECK();
-    return WF3D_OK;
-}
-
 }  // namespace
 
-// internal entry points (dispatched from wf3d_attn_fwd / wf3d_attn_bwd when head_dim == 64)
-extern "C" int wf3d_attn_fwd_mfma(const float* qkv, const int32_t* voff, int S, int vmax, int E, int heads, float drop_p,
-                                  uint32_t drop_seed, float* ctx, float* lse, void* stream) {
-    MAttn p{};
-    p.qkv = qkv; p.ctx = ctx; p.lse = lse; p.voff = voff;
-    p.E = E; p.heads = heads; p.vpad = (vmax + 31) & ~31;
-    p.scale = 1.0f / sqrtf((float)HD);
-    if (drop_p > 0.f) { p.seed = wf3d_seed_arg(drop_p, drop_seed); p.thresh = (uint32_t)((double)drop_p * 4294967296.0); p.dscale = 1.0f / (1.0f - drop_p); }
-    const size_t lds = (size_t)2 * p.vpad * LDR * sizeof(float);
-    if (lds > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute((const void*)attn_fwd_mfma_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        WF3D_CHECK(e == hipSuccess, WF3D_ERR_LAUNCH, "wf3d_attn_fwd: cannot raise dynamic LDS to %zu", lds);
+int wf3d_attn_mfma_launch(AttnArgs p, int family, bool backward, int S, int vmax, hipStream_t stream) {
+    const char* who = backward ? "wf3d_attn_bwd" : "wf3d_attn_fwd";
+    if (family == 1) {                                     // resident: K / V (or Q / dO) of the padded sample, + lse, delta
+        p.rows = (vmax + 31) & ~31;
+        const dim3 grid(p.heads, S);
+        const size_t rows = (size_t)2 * p.rows * LDR * sizeof(float);
+        if (!backward) return wf3d_attn_launch(who, attn_fwd_mfma_kernel, grid, rows, p, stream);
+        return wf3d_attn_launch(who, attn_bwd_mfma_kernel, grid, rows + 2 * p.rows * sizeof(float), p, stream);
     }
-    hipLaunchKernelGGL(attn_fwd_mfma_kernel, dim3(heads, S), dim3(256), lds, (hipStream_t)stream, p);
-    WF3D_LAUNCH_CHECK();
-    return WF3D_OK;
-}
-
-extern "C" int wf3d_attn_bwd_mfma(const float* qkv, const float* dctx, const float* ctx, const float* lse,
-                                  const int32_t* voff, int S, int vmax, int E, int heads, float drop_p,
-                                  uint32_t drop_seed, float* dqkv, void* stream) {
-    MAttn p{};
-    p.qkv = qkv; p.dctx = dctx; p.ctx_in = ctx; p.lse = (float*)lse; p.dqkv = dqkv; p.voff = voff;
-    p.E = E; p.heads = heads; p.vpad = (vmax + 31) & ~31;
-    p.scale = 1.0f / sqrtf((float)HD);
-    if (drop_p > 0.f) { p.seed = wf3d_seed_arg(drop_p, drop_seed); p.thresh = (uint32_t)((double)drop_p * 4294967296.0); p.dscale = 1.0f / (1.0f - drop_p); }
-    const size_t lds = ((size_t)2 * p.vpad * LDR + 2 * p.vpad) * sizeof(float);
-    if (lds > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute((const void*)attn_bwd_mfma_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        WF3D_CHECK(e == hipSuccess, WF3D_ERR_LAUNCH, "wf3d_attn_bwd: cannot raise dynamic LDS to %zu", lds);
-    }
-    hipLaunchKernelGGL(attn_bwd_mfma_kernel, dim3(heads, S), dim3(256), lds, (hipStream_t)stream, p);
-    WF3D_LAUNCH_CHECK();
-    return WF3D_OK;
-}
-
-// key-tiled kernels: any vmax (dispatched from wf3d_attn_fwd / wf3d_attn_bwd, option "attn_tiled")
-extern "C" int wf3d_attn_fwd_tiled(const float* qkv, const int32_t* voff, int S, int vmax, int E, int heads, float drop_p,
-                                   uint32_t drop_seed, float* ctx, float* lse, void* stream) {
-    WF3D_CHECK(wf3d_cdiv(vmax, KT) <= 65535, WF3D_ERR_UNSUPPORTED, "wf3d_attn_fwd: vmax %d too large", vmax);
-    MAttn p{};
-    p.qkv = qkv; p.ctx = ctx; p.lse = lse; p.voff = voff;
-    p.E = E; p.heads = heads; p.vpad = KT;
-    p.scale = 1.0f / sqrtf((float)HD);
-    if (drop_p > 0.f) { p.seed = wf3d_seed_arg(drop_p, drop_seed); p.thresh = (uint32_t)((double)drop_p * 4294967296.0); p.dscale = 1.0f / (1.0f - drop_p); }
-    return launch_tiled("wf3d_attn_fwd", attn_fwd_tiled_kernel, p, S, vmax, (size_t)2 * KT * LDR * sizeof(float), stream);
-}
-
-extern "C" int wf3d_attn_bwd_tiled(const float* qkv, const float* dctx, const float* ctx, const float* lse,
-                                   const int32_t* voff, int S, int vmax, int E, int heads, float drop_p,
-                                   uint32_t drop_seed, float* dqkv, void* stream) {
-    WF3D_CHECK(wf3d_cdiv(vmax, KT) <= 65535, WF3D_ERR_UNSUPPORTED, "wf3d_attn_bwd: vmax %d too large", vmax);
-    MAttn p{};
-    p.qkv = qkv; p.dctx = dctx; p.ctx_in = ctx; p.lse = (float*)lse; p.dqkv = dqkv; p.voff = voff;
-    p.E = E; p.heads = heads; p.vpad = KT;
-    p.scale = 1.0f / sqrtf((float)HD);
-    if (drop_p > 0.f) { p.seed = wf3d_seed_arg(drop_p, drop_seed); p.thresh = (uint32_t)((double)drop_p * 4294967296.0); p.dscale = 1.0f / (1.0f - drop_p); }
+    WF3D_CHECK(wf3d_cdiv(vmax, KT) <= 65535, WF3D_ERR_UNSUPPORTED, "%s: vmax %d too large", who, vmax);
+    p.rows = KT;
+    const dim3 grid(p.heads, S, wf3d_cdiv(vmax, KT));
     const size_t tiles = (size_t)2 * KT * LDR * sizeof(float);
-    int rc = launch_tiled("wf3d_attn_bwd", attn_bwd_tiled_dq_kernel, p, S, vmax, tiles, stream);
+    if (!backward) return wf3d_attn_launch(who, attn_fwd_tiled_kernel, grid, tiles, p, stream);
+    int rc = wf3d_attn_launch(who, attn_bwd_tiled_dq_kernel, grid, tiles, p, stream);
     if (rc) return rc;
-    return launch_tiled("wf3d_attn_bwd", attn_bwd_tiled_dkv_kernel, p, S, vmax, tiles + 2 * KT * sizeof(float), stream);
+    return wf3d_attn_launch(who, attn_bwd_tiled_dkv_kernel, grid, tiles + 2 * KT * sizeof(float), p, stream);
 }

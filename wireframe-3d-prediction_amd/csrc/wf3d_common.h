@@ -122,19 +122,8 @@ WF3D_INTERNAL int wf3d_gemm_split_regs(int products, const void* A_sx8, const vo
                                        int M, int N, int K, int lda, int ldb, int ldc, int accumulate, SplitK s,
                                        float* slab, const int32_t* live, hipStream_t st);
 
-// internal: MFMA attention for head_dim 64 (attn_mfma.hip)
-extern "C" WF3D_INTERNAL int wf3d_attn_fwd_mfma(const float* qkv, const int32_t* voff, int S, int vmax, int E, int heads, float drop_p,
-                                  uint32_t drop_seed, float* ctx, float* lse, void* stream);
-extern "C" WF3D_INTERNAL int wf3d_attn_bwd_mfma(const float* qkv, const float* dctx, const float* ctx, const float* lse,
-                                  const int32_t* voff, int S, int vmax, int E, int heads, float drop_p,
-                                  uint32_t drop_seed, float* dqkv, void* stream);
-
-// the same, key-tiled: any vmax (attn_mfma.hip)
-extern "C" WF3D_INTERNAL int wf3d_attn_fwd_tiled(const float* qkv, const int32_t* voff, int S, int vmax, int E, int heads, float drop_p,
-                                   uint32_t drop_seed, float* ctx, float* lse, void* stream);
-extern "C" WF3D_INTERNAL int wf3d_attn_bwd_tiled(const float* qkv, const float* dctx, const float* ctx, const float* lse,
-                                   const int32_t* voff, int S, int vmax, int E, int heads, float drop_p,
-                                   uint32_t drop_seed, float* dqkv, void* stream);
+// Attention: the kernels' argument block, its builder, the launch helper and the entry to the MFMA kernels
+// (attn_mfma.hip) are declared in attn_args.h, which attn.hip and attn_mfma.hip include.
 // the "attn_tiled" value of wf3d_set_option (attn.hip holds it)
 WF3D_INTERNAL int wf3d_attn_set_tiled(int value);
 
