@@ -619,6 +619,30 @@ int wf3d_cloud_normalize(const double* raw, const long* first, int nclouds, int 
                          double* out, double* centroid, double* max_distance, void* stream);
 int wf3d_cloud_sample(const double* norm, const long* first, const int* cloud, const int* choice, const double* aug, int B,
                       int P, int C, float* out, void* stream);
+/* Packed batches from the resident clouds (wf3d.packed, "PACKED batches, capacity form"): two launches fill the static
+ * buffers of a captured step.  Both read one PARAMETER BLOCK in device memory, 8-byte aligned, B * 40 + 4 bytes:
+ *     double aug[B][4]         {flip_x (+-1), flip_y (+-1), cos t, sin t} of sample b          at byte 0
+ *     int    cloud[B]          the resident cloud of sample b, 0 .. nclouds-1                  at byte 32 * B
+ *     int    out_first[B + 1]  sample b's first output row; out_first[0] = 0,                  at byte 36 * B
+ *                              out_first[b+1] - out_first[b] = first[cloud[b]+1] - first[cloud[b]], out_first[B] <= capacity
+ * The host fills it (numpy draws in the reference's order) and copies it up; the launches take only its address, so a
+ * captured graph replays them on whatever block is there.  1 <= B <= 4096.
+ * wf3d_cloud_pack: points [capacity, C] fp32 — cloud[b]'s rows in file order at rows out_first[b] .. out_first[b+1]-1, each
+ *   with the flips and the z-rotation of wf3d_cloud_sample (float64, one rounding), rows out_first[B] .. capacity-1 exact
+ *   zeros — and point_counts[b] = the rows of cloud[b].  Every element of both is written, by plain stores of this one
+ *   launch.  C = 8 moves 16 bytes per access (norm and points 16-byte aligned); other C take a row per lane.  A row whose
+ *   cloud index or position falls outside the resident clouds (a block that breaks the rules above) is written as zeros.
+ * wf3d_wireframe_targets: wf3d.targets.train_targets(..., full_width=True) of the samples' wireframes.  Resident:
+ *   wf_vertices [sum c, 3] float64 (centred and scaled like the clouds), wf_edges [sum e, 2] int32 vertex indices inside
+ *   their wireframe, vfirst / efirst [nclouds + 1] row offsets.  Writes every element of vertices [B, V, 3] (c_s vertices,
+ *   augmented like the points, then zeros), vertex_existence [B, V], vertex_counts [B] = c_s and edge_labels
+ *   [B, V(V-1)/2]: 1.0 at pair (i, j)'s position among the pairs of c_s vertices for every edge with 0 <= i < j < c_s,
+ *   0.0 elsewhere.  The host refuses c_s > V before the launch; the kernel would treat such a sample as c_s = V. */
+int wf3d_cloud_pack(const double* norm, const long* first, int nclouds, const void* params, int B, int capacity, int C,
+                    float* points, int64_t* point_counts, void* stream);
+int wf3d_wireframe_targets(const double* wf_vertices, const int32_t* wf_edges, const long* vfirst, const long* efirst, int nclouds,
+                           const void* params, int B, int V, float* vertices, float* vertex_existence, int64_t* vertex_counts,
+                           float* edge_labels, void* stream);
 /* HOST function: the numbers of a whitespace-separated text file (.xyz: 8 per row; np.loadtxt, :98) into out[0..max_vals);
  * returns the count in the file (call again with a larger buffer if > max_vals), -1 unreadable, -2 not a number. */
 long wf3d_parse_floats(const char* path, double* out, long max_vals);

@@ -1,0 +1,164 @@
+"""Preparing one packed batch for a captured step ("One capture for packed batches"): the host recipe
+against the resident data set, on the three fixture clouds of tests/golden/building3d (1,276 / 1,504 / 2,479 points; 8 / 4 /
+4 wireframe vertices) cycled to B = 3 and B = 32, augmentation on, max_vertices = 16, capacity = the batch's rows rounded
+up to a multiple of 256.
+
+Arm "host": `dataset[i]` per sample (file read, normalisation, augmentation) + `collate_packed` + `wf3d.packed.pack_into` +
+`wf3d.targets.train_targets(full_width=True)` + the four target `copy_`s into static device buffers.
+Arm "resident": `DeviceCloudCache.stage` + `fill` into buffers of the same shapes.
+Both: host wall time of one batch's preparation, ended by a synchronize.  2 warm-up batches per arm, then --blocks
+alternating blocks of --block-steps batches; the median of block medians of each arm and its block-to-block spread (max -
+min of its block medians), the protocol of scripts/bench_packed_capture.py's capacity arm.
+
+"fill": the two launches alone between device events, same blocks; GB/s over the bytes the point launch must move (96 B
+per cloud row at 8 columns, 32 B per zero row) beside `roofline.hbm.rows.achieved` of the newest committed
+profiles/r*_bench_cfg2.json (bench.py's line: the encoder's row passes at cfg2, hundreds of MB per launch).  At B = 3 and
+B = 32 the two launches move 0.5 and 5 MB: --batch-sizes 1024 shows the point launch at a size where bytes count.
+
+    python scripts/bench_resident_batches.py [--blocks 5] [--block-steps 7] [--warmup 2] [--out profiles/r06_resident_batches.jsonl]
+
+Prints one JSON line per batch size and appends them to --out.
+"""
+import argparse
+import glob
+import json
+import os
+import sys
+import time
+import types
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "wireframe-3d-prediction_amd"))
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+from datasets import Building3DReconstructionDataset, DeviceCloudCache  # noqa: E402
+from wf3d.packed import pack_into  # noqa: E402
+from wf3d.targets import train_targets  # noqa: E402
+
+KEYS = ("vertices", "vertex_existence", "edge_labels", "vertex_counts")
+V = 16
+
+
+def fixture_dataset():
+    """the train split's two clouds and the test split's one in one data set, num_points = 0"""
+    cfg = types.SimpleNamespace(root_dir=os.path.join(ROOT, "tests", "golden", "building3d"), num_points=0, use_color=True,
+                                use_intensity=True, normalize=True, augment=True)
+    ds = Building3DReconstructionDataset(cfg, "train")
+    other = Building3DReconstructionDataset(cfg, "test")
+    ds.pc_files, ds.wireframe_files = ds.pc_files + other.pc_files, ds.wireframe_files + other.wireframe_files
+    order = np.argsort([os.path.basename(f) for f in ds.pc_files])
+    ds.pc_files, ds.wireframe_files = [ds.pc_files[i] for i in order], [ds.wireframe_files[i] for i in order]
+    return ds
+
+
+def rows_figure():
+    files = sorted(glob.glob(os.path.join(ROOT, "profiles", "r*_bench_cfg2.json")))
+    if not files:
+        return None
+
+    def find(o):
+        if isinstance(o, dict):
+            if isinstance(o.get("hbm"), dict) and "rows" in o["hbm"]:
+                return o["hbm"]["rows"].get("achieved")
+            o = list(o.values())
+        for v in o if isinstance(o, list) else []:
+            r = find(v)
+            if r is not None:
+                return r
+        return None
+    with open(files[-1]) as f:
+        r = find(json.load(f))
+    return None if r is None else {"file": os.path.basename(files[-1]), "GB/s": round(float(r), 1)}
+
+
+def blocks_of(arms, blocks, steps, warmup):
+    """{arm: block medians} of the per-call figures fn() returns, in alternating blocks"""
+    for fn in arms.values():
+        for _ in range(warmup):
+            fn()
+    med = {k: [] for k in arms}
+    for _ in range(blocks):
+        for name, fn in arms.items():
+            torch.cuda.synchronize()
+            med[name].append(float(np.median([fn() for _ in range(steps)])))
+    return med
+
+
+def summary(v, digits=4):
+    return {"median": round(float(np.median(v)), digits), "block_spread": round(max(v) - min(v), digits)}
+
+
+def run(B, ds, cache, dev, args):
+    idxs = [i % len(ds) for i in range(B)]
+    rows = sum(cache.n[i] for i in idxs)
+    cap = -(-rows // 256) * 256
+    buf = cache.packed_buffers(B, cap, V)
+    points = torch.zeros(cap, cache.ncol, device=dev)
+    counts = torch.zeros(B, dtype=torch.int64, device=dev)
+    static = {k: torch.zeros_like(buf[k]) for k in KEYS}
+
+    def host():
+        t0 = time.perf_counter()
+        batch = ds.collate_packed([ds[i] for i in idxs])
+        pack_into(points, counts, batch["point_clouds"].split(batch["point_counts"].tolist()))
+        t = train_targets(batch["wf_vertices"], batch["wf_edges"], V, full_width=True)
+        for k in KEYS:
+            static[k].copy_(t[k])
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) * 1e3
+
+    def resident():
+        t0 = time.perf_counter()
+        cache.stage(buf, idxs)
+        cache.fill(buf)
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) * 1e3
+
+    ev = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+
+    def fill():
+        ev[0].record()
+        cache.fill(buf)
+        ev[1].record()
+        torch.cuda.synchronize()
+        return ev[0].elapsed_time(ev[1])
+
+    np.random.seed(0)
+    med = blocks_of({"host": host, "resident": resident}, args.blocks, args.block_steps, args.warmup)
+    # the two arms built the same batch last (same draws are not needed for that: compare what does not depend on them)
+    same = bool(torch.equal(counts, buf["point_counts"]) and torch.equal(static["edge_labels"], buf["edge_labels"])
+                and torch.equal(static["vertex_counts"], buf["vertex_counts"]))
+    fmed = blocks_of({"fill": fill}, args.blocks, args.block_steps, args.warmup)["fill"]
+    nbytes = rows * cache.ncol * 12 + (cap - rows) * cache.ncol * 4
+    fill_ms = float(np.median(fmed))
+    h, r = summary(med["host"]), summary(med["resident"])
+    return {"bench": "resident_batches", "B": B, "rows": rows, "capacity": cap, "max_vertices": V, "columns": cache.ncol,
+            "blocks": args.blocks, "steps_per_block": args.block_steps, "host_prepare_ms": h, "resident_prepare_ms": r,
+            "host_over_resident": round(h["median"] / r["median"], 1), "h2d_bytes_resident": 40 * B + 4,
+            "h2d_bytes_host": cap * cache.ncol * 4 + 8 * B + sum(static[k].numel() * static[k].element_size() for k in KEYS),
+            "same_counts_and_labels": same, "fill_ms": summary(fmed), "fill_point_bytes": nbytes,
+            "fill_GB/s": round(nbytes / fill_ms / 1e6, 1), "row_passes": rows_figure()}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--blocks", type=int, default=5)
+    ap.add_argument("--block-steps", type=int, default=7)
+    ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--batch-sizes", default="3,32")
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "r06_resident_batches.jsonl"))
+    args = ap.parse_args()
+    dev = torch.device("cuda:0")
+    ds = fixture_dataset()
+    cache = DeviceCloudCache(ds, dev)
+    for B in (int(b) for b in args.batch_sizes.split(",")):
+        r = run(B, ds, cache, dev, args)
+        print(json.dumps(r), flush=True)
+        if args.out:
+            with open(args.out, "a") as f:
+                f.write(json.dumps(r) + "\n")
+
+
+if __name__ == "__main__":
+    main()

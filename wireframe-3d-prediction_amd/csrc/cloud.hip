@@ -10,6 +10,13 @@
 //                            to fp32 once at the end like its final astype(np.float32) (:158).  The random choices and
 //                            augmentation parameters come from the host, drawn from numpy in the reference's order, so a
 //                            seeded run reproduces the reference's batches.
+//   cloud_pack_kernel        per packed batch: whole clouds, in file order, one after the other into the [capacity, C] fp32
+//                            input buffer of a captured step, with cloud_sample_kernel's augmentation; the rows behind
+//                            the last cloud are written as zeros and point_counts[b] by the same launch.
+//   wireframe_targets_kernel per packed batch: wf3d.targets.train_targets(..., full_width=True) from resident wireframes,
+//                            one workgroup per sample.
+//                            Both read one parameter block in device memory (include/wf3d.h), so a captured graph that
+//                            holds the two launches serves every batch.
 // Plus the host-side text parser for .xyz files (np.loadtxt replacement): wf3d_parse_floats.
 #include <locale.h>
 #include <stdio.h>
@@ -82,6 +89,140 @@ __global__ __launch_bounds__(256) void cloud_sample_kernel(const double* __restr
     for (int k = 2; k < C; ++k) o[k] = (float)row[k];
 }
 
+// ---- packed batches from resident clouds ------------------------------------------------------------------------------
+// The parameter block of a batch of B samples (include/wf3d.h): aug [B, 4] doubles, cloud [B] ints, out_first [B + 1] ints.
+struct BatchParams { const double* aug; const int* cloud; const int* out_first; };
+__device__ __forceinline__ BatchParams batch_params(const void* params, int B) {
+    const char* p = (const char*)params;
+    return {(const double*)p, (const int*)(p + (size_t)B * 32), (const int*)(p + (size_t)B * 36)};
+}
+
+// the sample that owns output row r < out_first[B]: the last b with out_first[b] <= r (an empty sample owns nothing)
+__device__ __forceinline__ int sample_of_row(const int* __restrict__ out_first, int B, int r) {
+    int lo = 0, hi = B;                              // out_first[lo] <= r < out_first[hi]
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (out_first[mid] <= r) lo = mid; else hi = mid;
+    }
+    return lo;
+}
+
+// Source row of output row r, or -1 for a row that belongs to no cloud (it is written as zeros): rows from out_first[B]
+// on, and — so that a block the host did not build can never make the kernel read outside `norm` — rows whose
+// cloud index or position is outside the resident clouds.
+__device__ __forceinline__ long pack_source_row(const BatchParams& P, const long* __restrict__ first, int B, int nclouds,
+                                                int r, int& b) {
+    if (r >= P.out_first[B]) return -1;
+    b = sample_of_row(P.out_first, B, r);
+    const int cl = P.cloud[b];
+    if (cl < 0 || cl >= nclouds) return -1;
+    const long k = r - P.out_first[b], r0 = first[cl];
+    return k < first[cl + 1] - r0 ? r0 + k : -1;
+}
+
+__device__ __forceinline__ void pack_counts(const BatchParams& P, const long* __restrict__ first, int B, int nclouds, long t,
+                                            int64_t* __restrict__ point_counts) {
+    if (t < B) {
+        const int cl = P.cloud[t];
+        point_counts[t] = cl >= 0 && cl < nclouds ? first[cl + 1] - first[cl] : 0;
+    }
+}
+
+// C = 8: a row is 64 B of float64 in, 32 B of fp32 out.  Two lanes per row: the even lane loads x y | z r (two 16-B
+// loads, 32 contiguous bytes), the odd lane g b | a i, each stores its four fp32 as one 16-B store — consecutive lanes
+// write consecutive 16 bytes, a wave reads 2 KiB and writes 1 KiB contiguous, and x and y (the rotation's operands) sit
+// in one lane.
+typedef double f64x2 __attribute__((ext_vector_type(2)));
+__global__ __launch_bounds__(256) void cloud_pack8_kernel(const double* __restrict__ norm, const long* __restrict__ first,
+                                                           int nclouds, const void* __restrict__ params, int B, int capacity,
+                                                           float* __restrict__ out, int64_t* __restrict__ point_counts) {
+    const BatchParams P = batch_params(params, B);
+    const long t = (long)blockIdx.x * 256 + threadIdx.x;
+    pack_counts(P, first, B, nclouds, t, point_counts);
+    const long r = t >> 1;
+    const int half = (int)(t & 1);
+    if (r >= capacity) return;
+    f32x4 o = {0.f, 0.f, 0.f, 0.f};
+    int b = 0;
+    const long src = pack_source_row(P, first, B, nclouds, (int)r, b);
+    if (src >= 0) {
+        const f64x2* row = reinterpret_cast<const f64x2*>(norm + src * 8) + half * 2;
+        const f64x2 u = row[0], v = row[1];
+        if (half == 0) {
+            const double fx = P.aug[b * 4], fy = P.aug[b * 4 + 1], c = P.aug[b * 4 + 2], s = P.aug[b * 4 + 3];
+            const double x = fx * u[0], y = fy * u[1];
+            o = f32x4{(float)(x * c - y * s), (float)(x * s + y * c), (float)v[0], (float)v[1]};
+        } else {
+            o = f32x4{(float)u[0], (float)u[1], (float)v[0], (float)v[1]};
+        }
+    }
+    *reinterpret_cast<f32x4*>(out + r * 8 + half * 4) = o;
+}
+
+// any C (3 and 7 in this project): one lane per row
+__global__ __launch_bounds__(256) void cloud_pack_kernel(const double* __restrict__ norm, const long* __restrict__ first,
+                                                          int nclouds, const void* __restrict__ params, int B, int capacity,
+                                                          int C, float* __restrict__ out, int64_t* __restrict__ point_counts) {
+    const BatchParams P = batch_params(params, B);
+    const long r = (long)blockIdx.x * 256 + threadIdx.x;
+    pack_counts(P, first, B, nclouds, r, point_counts);
+    if (r >= capacity) return;
+    float* o = out + r * C;
+    int b = 0;
+    const long src = pack_source_row(P, first, B, nclouds, (int)r, b);
+    if (src < 0) {
+        for (int k = 0; k < C; ++k) o[k] = 0.f;
+        return;
+    }
+    const double* row = norm + src * C;
+    const double fx = P.aug[b * 4], fy = P.aug[b * 4 + 1], c = P.aug[b * 4 + 2], s = P.aug[b * 4 + 3];
+    const double x = fx * row[0], y = fy * row[1];
+    o[0] = (float)(x * c - y * s);
+    o[1] = (float)(x * s + y * c);
+    for (int k = 2; k < C; ++k) o[k] = (float)row[k];
+}
+
+// wf3d/targets.py train_targets(..., full_width=True) for sample b = blockIdx.x: c_s vertices augmented like the points,
+// zeros after; existence; the count; labels of all pairs of V vertices: the row is zeroed, then (after a barrier) every
+// edge min < max < c_s stores 1.0 at its pair's position among the pairs of c_s vertices.
+__global__ __launch_bounds__(256) void wireframe_targets_kernel(const double* __restrict__ wfv, const int32_t* __restrict__ wfe,
+                                                                 const long* __restrict__ vfirst, const long* __restrict__ efirst,
+                                                                 int nclouds, const void* __restrict__ params, int B, int V,
+                                                                 float* __restrict__ vertices, float* __restrict__ existence,
+                                                                 int64_t* __restrict__ counts, float* __restrict__ labels) {
+    const BatchParams P = batch_params(params, B);
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const int cl = P.cloud[b];
+    const bool known = cl >= 0 && cl < nclouds;
+    const long v0 = known ? vfirst[cl] : 0, e0 = known ? efirst[cl] : 0;
+    const long cs = known ? vfirst[cl + 1] - v0 : 0, ne = known ? efirst[cl + 1] - e0 : 0;
+    const int c = (int)(cs < V ? cs : V);            // the host refuses c_s > V; the writes stay inside the row regardless
+    const double fx = P.aug[b * 4], fy = P.aug[b * 4 + 1], co = P.aug[b * 4 + 2], si = P.aug[b * 4 + 3];
+    if (tid == 0) counts[b] = cs;
+    for (int i = tid; i < V; i += 256) {
+        float* o = vertices + ((long)b * V + i) * 3;
+        if (i < c) {
+            const double* v = wfv + (v0 + i) * 3;
+            const double x = fx * v[0], y = fy * v[1];
+            o[0] = (float)(x * co - y * si);
+            o[1] = (float)(x * si + y * co);
+            o[2] = (float)v[2];
+        } else {
+            o[0] = o[1] = o[2] = 0.f;
+        }
+        existence[(long)b * V + i] = i < c ? 1.f : 0.f;
+    }
+    const long W = (long)V * (V - 1) / 2;
+    float* lab = labels + (long)b * W;
+    for (long k = tid; k < W; k += 256) lab[k] = 0.f;
+    __syncthreads();
+    for (long e = tid; e < ne; e += 256) {
+        const int a = wfe[(e0 + e) * 2], d = wfe[(e0 + e) * 2 + 1];
+        const int i = min(a, d), j = max(a, d);
+        if (i >= 0 && i < j && j < c) lab[(long)i * c - (long)i * (i + 1) / 2 + (j - i - 1)] = 1.f;
+    }
+}
+
 }  // namespace
 
 extern "C" int wf3d_cloud_normalize(const double* raw, const long* first, int nclouds, int C, int color_lo, int color_hi,
@@ -103,6 +244,37 @@ extern "C" int wf3d_cloud_sample(const double* norm, const long* first, const in
     WF3D_CHECK(B <= 65535, WF3D_ERR_UNSUPPORTED, "wf3d_cloud_sample: B > 65535");
     hipLaunchKernelGGL(cloud_sample_kernel, dim3(wf3d_cdiv(P, 256), B), dim3(256), 0, (hipStream_t)stream, norm, first, cloud, choice,
                        aug, P, C, out);
+    WF3D_LAUNCH_CHECK();
+    return WF3D_OK;
+}
+
+extern "C" int wf3d_cloud_pack(const double* norm, const long* first, int nclouds, const void* params, int B, int capacity,
+                               int C, float* points, int64_t* point_counts, void* stream) {
+    WF3D_CHECK(nclouds >= 1 && B >= 1 && B <= 4096 && capacity >= 1 && C >= 3 && C <= 16, WF3D_ERR_ARG, "wf3d_cloud_pack: bad dims");
+    WF3D_CHECK(norm && first && params && points && point_counts, WF3D_ERR_ARG, "wf3d_cloud_pack: null pointer");
+    WF3D_CHECK(((uintptr_t)params & 7) == 0, WF3D_ERR_ARG, "wf3d_cloud_pack: params must be 8-byte aligned");
+    if (C == 8) {
+        WF3D_CHECK((((uintptr_t)norm | (uintptr_t)points) & 15) == 0, WF3D_ERR_ARG, "wf3d_cloud_pack: norm and points must be 16-byte aligned");
+        hipLaunchKernelGGL(cloud_pack8_kernel, dim3(wf3d_cdiv(2L * capacity > B ? 2L * capacity : B, 256)), dim3(256), 0, (hipStream_t)stream, norm, first,
+                           nclouds, params, B, capacity, points, point_counts);
+    } else {
+        hipLaunchKernelGGL(cloud_pack_kernel, dim3(wf3d_cdiv(capacity > B ? capacity : B, 256)), dim3(256), 0, (hipStream_t)stream,
+                           norm, first, nclouds, params, B, capacity, C, points, point_counts);
+    }
+    WF3D_LAUNCH_CHECK();
+    return WF3D_OK;
+}
+
+extern "C" int wf3d_wireframe_targets(const double* wf_vertices, const int32_t* wf_edges, const long* vfirst, const long* efirst,
+                                      int nclouds, const void* params, int B, int V, float* vertices, float* vertex_existence,
+                                      int64_t* vertex_counts, float* edge_labels, void* stream) {
+    WF3D_CHECK(nclouds >= 1 && B >= 1 && B <= 4096 && V >= 1 && V <= 32768, WF3D_ERR_ARG, "wf3d_wireframe_targets: bad dims");
+    // wf_vertices / wf_edges / edge_labels may be NULL where they hold nothing (no vertices, no edges, V = 1)
+    WF3D_CHECK(vfirst && efirst && params && vertices && vertex_existence && vertex_counts && (edge_labels || V < 2), WF3D_ERR_ARG,
+               "wf3d_wireframe_targets: null pointer");
+    WF3D_CHECK(((uintptr_t)params & 7) == 0, WF3D_ERR_ARG, "wf3d_wireframe_targets: params must be 8-byte aligned");
+    hipLaunchKernelGGL(wireframe_targets_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, wf_vertices, wf_edges, vfirst, efirst,
+                       nclouds, params, B, V, vertices, vertex_existence, vertex_counts, edge_labels);
     WF3D_LAUNCH_CHECK();
     return WF3D_OK;
 }

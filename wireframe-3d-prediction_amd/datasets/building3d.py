@@ -9,7 +9,12 @@ reference's samples.  The .xyz text is read by the library's C parser instead of
 `DeviceCloudCache(dataset, device)` is the resident form: every cloud is parsed once, uploaded as float64 (the raw
 coordinates are UTM metres — fp32 cannot hold them), normalised once on the device (csrc/cloud.hip) and kept in HBM;
 `cache.batch(indices)` then costs one small host->device copy of the random choices and ONE gather/augment kernel that
-writes the model's `[B, num_points, C]` fp32 input directly — no per-sample file I/O, no per-sample host arrays."""
+writes the model's `[B, num_points, C]` fp32 input directly — no per-sample file I/O, no per-sample host arrays.
+
+The packed form (whole clouds, `forward_packed`): `cache.packed_batch(indices)` is `collate_packed` of the same data set
+with `num_points = 0`; `cache.packed_buffers` / `stage` / `fill` feed the static buffers of a captured step — `stage`
+draws the augmentation and copies one 40·B + 4 byte parameter block, `fill` is two launches (points + point counts,
+training targets) that read everything else from resident device memory.  `packed_plan` is the host part on its own."""
 import ctypes
 import glob
 import operator
@@ -213,19 +218,57 @@ class Building3DReconstructionDataset(Dataset):
         return pc_files, wf_files
 
 
+PARAM_BYTES = 40       # per sample in the parameter block of a packed batch: aug 4 doubles, cloud int32, out_first int32
+
+
+def packed_plan(n, vertex_counts, indices, draw=None, capacity=None, max_vertices=None, who="packed_plan"):
+    """The host part of a packed batch from resident clouds; needs no GPU.  `n` / `vertex_counts`: rows and wireframe
+    vertices per resident cloud; `indices`: the batch (negative indices count from the end, as for a list); `draw`: the
+    data set's `_draw_augmentation` when it augments, else None.  Returns (indices, out_first, aug): the normalised
+    indices, int32 [B + 1] first output rows (out_first[B] = the batch's rows) and float64 [B, 4] {flip_x, flip_y, cos t,
+    sin t} — the parameter block of include/wf3d.h.  np.random is consumed as `[ds0[i] for i in indices]` consumes it
+    (ds0 = the data set with num_points = 0): per sample flip-x, flip-y, angle, and nothing without `draw`.  Every check
+    comes before the first draw: IndexError for an index out of range, ValueError for an empty batch, for more than
+    `capacity` rows and for a wireframe of more than `max_vertices` vertices."""
+    indices = [operator.index(i) for i in indices]
+    indices = [i + len(n) if i < 0 else i for i in indices]
+    if any(not 0 <= i < len(n) for i in indices):
+        raise IndexError(f"DeviceCloudCache.{who}: index out of range for {len(n)} clouds")
+    if not indices:
+        raise ValueError(f"DeviceCloudCache.{who}: an empty batch")
+    out_first = np.zeros(len(indices) + 1, dtype=np.int64)
+    np.cumsum([n[i] for i in indices], out=out_first[1:])
+    rows = int(out_first[-1])
+    if rows > (0x7FFFFFFF if capacity is None else capacity):
+        raise ValueError(f"DeviceCloudCache.{who}: the clouds hold {rows} points, above the capacity of {capacity} rows")
+    most = max(vertex_counts[i] for i in indices)
+    if max_vertices is not None and most > max_vertices:
+        raise ValueError(f"a wireframe has {most} vertices, more than max_vertices = {max_vertices}")
+    aug = np.empty((len(indices), 4), dtype=np.float64)
+    for b in range(len(indices)):
+        fx, fy, angle = draw() if draw is not None else (1.0, 1.0, 0.0)
+        aug[b] = (fx, fy, np.cos(angle), np.sin(angle))
+    return indices, out_first.astype(np.int32), aug
+
+
 class DeviceCloudCache:
     """All clouds of a dataset resident in HBM, normalised once; batches are produced by one kernel.
 
         cache = DeviceCloudCache(dataset, torch.device("cuda:0"))
         batch = cache.batch([3, 0, 7])      # same dict as collate_batch([dataset[3], dataset[0], dataset[7]]), with
                                             # batch["point_clouds"] a device tensor; np.random is consumed identically
+
+    Whole clouds for forward_packed (the data set's num_points is not used; a data set without one is accepted):
+
+        batch = cache.packed_batch([3, 0, 7])          # collate_packed of the same data set with num_points = 0
+        buf = cache.packed_buffers(B, capacity, max_vertices)      # static buffers of a captured step
+        info = cache.stage(buf, [3, 0, 7])             # host: checks, np.random draws, one small non-blocking copy
+        cache.fill(buf)                                # two launches; inside the capture, or before graph.replay()
     """
 
     def __init__(self, dataset, device):
         from wf3d import _lib
         from wf3d.ops import _stream
-        if not dataset.num_points:
-            raise ValueError("DeviceCloudCache needs dataset.num_points (fixed-size batches)")
         self.ds, self.device = dataset, device
         self.ncol, (clo, chi) = _columns(dataset.use_color, dataset.use_intensity)
         raws = [_read_xyz(f)[:, :self.ncol] for f in dataset.pc_files]
@@ -243,10 +286,44 @@ class DeviceCloudCache:
                                             _stream()), "cloud_normalize")
         self.centroid, self.max_distance = cen.cpu().numpy(), md.cpu().numpy()      # one read-back, at build time
         self.wireframes = [load_wireframe(f) for f in dataset.wireframe_files]
+        # the wireframes resident too (wireframe_targets_kernel): vertices centred and scaled as batch() does per call
+        verts = [self._normalised_vertices(i)[0] for i in range(len(raws))]
+        edges = [np.asarray(e, dtype=np.int32).reshape(-1, 2) for _, e in self.wireframes]
+        self.nv = [v.shape[0] for v in verts]
+        vfirst, efirst = np.zeros(len(raws) + 1, dtype=np.int64), np.zeros(len(raws) + 1, dtype=np.int64)
+        np.cumsum(self.nv, out=vfirst[1:])
+        np.cumsum([e.shape[0] for e in edges], out=efirst[1:])
+        self.wf_vertices = torch.from_numpy(np.ascontiguousarray(np.concatenate(verts, axis=0).reshape(-1, 3))).to(device)
+        self.wf_edges = torch.from_numpy(np.ascontiguousarray(np.concatenate(edges, axis=0))).to(device)
+        self.vfirst, self.efirst = torch.from_numpy(vfirst).to(device), torch.from_numpy(efirst).to(device)
+
+    def _normalised_vertices(self, idx):
+        """(float64 copy of cloud idx's wireframe vertices, centred and scaled when the data set normalises; centroid; max_distance)"""
+        wf_vertices = self.wireframes[idx][0].copy()
+        cen = md = None
+        if self.ds.normalize:
+            cen, md = self.centroid[idx].copy(), self.max_distance[idx]
+            wf_vertices -= cen
+            wf_vertices /= md
+        return wf_vertices, cen, md
+
+    def _item(self, idx, fx, fy, rot):
+        """__getitem__'s dict for cloud idx under one augmentation draw (flips, rot = rotz(angle)), without its point cloud."""
+        ds = self.ds
+        wf_vertices, cen, md = self._normalised_vertices(idx)
+        if ds.augment:
+            wf_vertices[:, 0] *= fx
+            wf_vertices[:, 1] *= fy
+            wf_vertices[:, 0:3] = np.dot(wf_vertices[:, 0:3], np.transpose(rot))
+        it = ds._finish(np.empty((0, self.ncol)), wf_vertices, self.wireframes[idx][1], cen, md, ds.pc_files[idx])
+        del it["point_clouds"]
+        return it
 
     def batch(self, indices):
         from wf3d import _lib
         from wf3d.ops import _stream
+        if not self.ds.num_points:
+            raise ValueError("DeviceCloudCache needs dataset.num_points (fixed-size batches)")
         ds, P = self.ds, self.ds.num_points
         # the kernel indexes device arrays with these: normalise Python's negative indices and refuse anything out of
         # range here (the host arrays would wrap around silently, the device read would not)
@@ -263,20 +340,7 @@ class DeviceCloudCache:
             choice[b] = np.random.choice(n, P, replace=n < P)                     # same draws, same order as __getitem__
             fx, fy, angle = ds._draw_augmentation() if ds.augment else (1.0, 1.0, 0.0)
             aug[b] = (fx, fy, np.cos(angle), np.sin(angle))
-            wf_vertices, wf_edges = self.wireframes[idx]
-            wf_vertices = wf_vertices.copy()
-            cen = md = None
-            if ds.normalize:
-                cen, md = self.centroid[idx].copy(), self.max_distance[idx]
-                wf_vertices -= cen
-                wf_vertices /= md
-            if ds.augment:
-                wf_vertices[:, 0] *= fx
-                wf_vertices[:, 1] *= fy
-                wf_vertices[:, 0:3] = np.dot(wf_vertices[:, 0:3], np.transpose(rotz(angle)))
-            it = ds._finish(np.empty((0, self.ncol)), wf_vertices, wf_edges, cen, md, ds.pc_files[idx])
-            del it["point_clouds"]
-            items.append(it)
+            items.append(self._item(idx, fx, fy, rotz(angle)))
         out = ds.collate_batch(items)
         dev = self.device
         ids = torch.tensor(list(indices), dtype=torch.int32).to(dev, non_blocking=True)
@@ -287,3 +351,91 @@ class DeviceCloudCache:
                                                  ag.data_ptr(), B, P, self.ncol, pcs.data_ptr(), _stream()), "cloud_sample")
         out["point_clouds"] = pcs
         return out
+
+    # ---- packed batches: whole clouds, one after the other ----------------------------------------------------------
+    def _plan(self, indices, who, capacity=None, max_vertices=None):
+        ds = self.ds
+        return packed_plan(self.n, self.nv, indices, ds._draw_augmentation if ds.augment else None, capacity, max_vertices, who)
+
+    @staticmethod
+    def _block_views(block, B):
+        """(aug [B, 4] float64, cloud [B] int32, out_first [B + 1] int32) views of a host parameter block (include/wf3d.h)"""
+        raw = block.numpy()
+        return raw[:32 * B].view(np.float64).reshape(B, 4), raw[32 * B:36 * B].view(np.int32), raw[36 * B:].view(np.int32)
+
+    def _pack(self, params, B, rows, points, point_counts):
+        from wf3d import _lib
+        from wf3d.ops import _stream
+        _lib.check(_lib.load().wf3d_cloud_pack(self.norm.data_ptr(), self.first.data_ptr(), len(self.n), params.data_ptr(), B,
+                                               rows, self.ncol, points.data_ptr(), point_counts.data_ptr(), _stream()), "cloud_pack")
+
+    def packed_batch(self, indices):
+        """collate_packed([ds0[i] for i in indices]), ds0 = the data set with num_points = 0, with `point_clouds`
+        [sum n_b, C] on the device; np.random is consumed as those __getitem__ calls consume it."""
+        indices, out_first, aug = self._plan(indices, "packed_batch")
+        B, rows = len(indices), int(out_first[-1])
+        items = [self._item(idx, fx, fy, np.array([[c, -s, 0], [s, c, 0], [0, 0, 1]])) for idx, (fx, fy, c, s) in zip(indices, aug)]
+        out = self.ds.collate_batch(items)
+        block = torch.empty(PARAM_BYTES * B + 4, dtype=torch.uint8)
+        v_aug, v_cloud, v_first = self._block_views(block, B)
+        v_aug[:], v_cloud[:], v_first[:] = aug, indices, out_first
+        points = torch.empty(rows, self.ncol, dtype=torch.float32, device=self.device)
+        counts = torch.empty(B, dtype=torch.int64, device=self.device)
+        self._pack(block.to(self.device), B, rows, points, counts)
+        out["point_clouds"] = points
+        out["point_counts"] = torch.tensor([self.n[i] for i in indices], dtype=torch.int64)
+        return out
+
+    def packed_buffers(self, B, capacity, max_vertices):
+        """Static device tensors of a captured step for batches of B whole clouds: `points` [capacity, C],
+        `point_counts` int64 [B], train_targets' `vertices` / `vertex_existence` / `edge_labels` (full width) /
+        `vertex_counts`, the parameter block `params` (uint8 [40 B + 4]) and its pinned host mirror `params_host`."""
+        from wf3d.ops import check_capacity
+        capacity = check_capacity(capacity)
+        B, V = operator.index(B), operator.index(max_vertices)
+        if not 1 <= B <= 4096 or V < 1:
+            raise ValueError(f"DeviceCloudCache.packed_buffers: needs 1 <= B <= 4096 and max_vertices >= 1 (got {B}, {V})")
+        dev = self.device
+        f32 = dict(dtype=torch.float32, device=dev)
+        return {"points": torch.zeros(capacity, self.ncol, **f32),
+                "point_counts": torch.zeros(B, dtype=torch.int64, device=dev),
+                "vertices": torch.zeros(B, V, 3, **f32),
+                "vertex_existence": torch.zeros(B, V, **f32),
+                "edge_labels": torch.zeros(B, V * (V - 1) // 2, **f32),
+                "vertex_counts": torch.zeros(B, dtype=torch.int64, device=dev),
+                "params": torch.zeros(PARAM_BYTES * B + 4, dtype=torch.uint8, device=dev),
+                "params_host": torch.zeros(PARAM_BYTES * B + 4, dtype=torch.uint8).pin_memory(),
+                "params_copied": torch.cuda.Event()}
+
+    def stage(self, buffers, indices):
+        """Host only, outside any capture: check the batch against the buffers (IndexError / ValueError, nothing touched),
+        draw its augmentation from np.random, fill the pinned mirror and issue ONE non-blocking copy of the parameter
+        block.  Returns the batch's host-side fields `scan_idx`, `centroid`, `max_distance` as collate_batch builds them."""
+        B, capacity = buffers["point_counts"].shape[0], buffers["points"].shape[0]
+        if len(indices) != B:
+            raise ValueError(f"DeviceCloudCache.stage: {len(indices)} clouds for buffers of {B}")
+        indices, out_first, aug = self._plan(indices, "stage", capacity, buffers["vertices"].shape[1])
+        buffers["params_copied"].synchronize()             # the mirror's last copy has left it (no wait when it has)
+        v_aug, v_cloud, v_first = self._block_views(buffers["params_host"], B)
+        v_aug[:], v_cloud[:], v_first[:] = aug, indices, out_first
+        buffers["params"].copy_(buffers["params_host"], non_blocking=True)
+        buffers["params_copied"].record()
+        ds = self.ds
+        info = {"scan_idx": torch.tensor(np.array([np.array(os.path.splitext(os.path.basename(ds.pc_files[i]))[0]).astype(np.int64)
+                                                   for i in indices]))}
+        if ds.normalize:
+            info["centroid"] = torch.tensor(np.array([self.centroid[i] for i in indices]))
+            info["max_distance"] = torch.tensor(np.array([self.max_distance[i] for i in indices]))
+        return info
+
+    def fill(self, buffers):
+        """The two launches that fill `buffers` from the staged parameter block: every element of `points`, `point_counts`
+        and the four target tensors is written.  Capturable: everything the kernels read is in device memory."""
+        from wf3d import _lib
+        from wf3d.ops import _stream
+        B, V = buffers["vertices"].shape[0], buffers["vertices"].shape[1]
+        self._pack(buffers["params"], B, buffers["points"].shape[0], buffers["points"], buffers["point_counts"])
+        _lib.check(_lib.load().wf3d_wireframe_targets(
+            self.wf_vertices.data_ptr(), self.wf_edges.data_ptr(), self.vfirst.data_ptr(), self.efirst.data_ptr(), len(self.n),
+            buffers["params"].data_ptr(), B, V, buffers["vertices"].data_ptr(), buffers["vertex_existence"].data_ptr(),
+            buffers["vertex_counts"].data_ptr(), buffers["edge_labels"].data_ptr(), _stream()), "wireframe_targets")
