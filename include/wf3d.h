@@ -551,9 +551,10 @@ int wf3d_dropout_draw(uint64_t* state, uint32_t* words, void* stream);
 int wf3d_set_dropout_seed_words(const uint32_t* words);
 
 /* ------------------------------------------------------------------------
- * LIVE ROW COUNT.  A padded edge layout runs every edge-row launch at the worst case B*V(V-1)/2 rows.  While the calling
+ * LIVE ROW COUNT.  A padded edge layout runs every edge-row launch at the worst case B*V(V-1)/2 rows, a packed batch with
+ * a capacity every per-point launch at `capacity` rows.  While the calling
  * thread has set a live-row count, wf3d_set_live_rows(rows) with rows -> one int32 in DEVICE memory (wf3d_edge_layout's
- * eoff + B), the launches listed below skip the tail.  The pointer is a kernel argument and the value is read by the
+ * eoff + B; wf3d_packed_layout_build's rows + B), the launches listed below skip the tail.  The pointer is a kernel argument and the value is read by the
  * kernel at entry, never on the host: a captured graph stays valid when the value changes between replays.  NULL
  * clears it.  Thread-local, host only, like wf3d_set_dropout_seed_words; a side stream driven from the same thread
  * is covered.
@@ -587,9 +588,16 @@ int wf3d_set_dropout_seed_words(const uint32_t* words);
  *                                              exact zeros.  The caller runs that GEMM WITHOUT a count (its rows are a
  *                                              weight dimension): the zero columns add exact zeros in its unchanged
  *                                              split-K order, as the zero backward tail does without a count.
+ *   wf3d_first_layer_fwd                       R, both kernel forms: z, mu, rs and h_sx8 are written for rows < R256 only
+ *   wf3d_ln_act_bwd_first                      R; dgamma / dbeta / dbias and dW are sums over [0, R256)
+ *   wf3d_point_valid                           M
+ *   wf3d_pool4_seg_bwd, wf3d_pool4_seg_bwd_sx8 M_pad, with the count in rows of the packed batch (the layout's
+ *                                              rows[B]): a pad chunk (-1, 0, r0, r1) zero-fills [r0, min(r1, R256)).
+ *                                              The clouds' chunks lie below the live total and run as without a count.
+ * wf3d_pool4_seg_fwd reads rows through the clouds' chunks only and touches no pad row with or without a count, as
  * wf3d_edge_pair_bwd and wf3d_edge_prob_fwd reach edge rows through eoff only and touch no tail row with or without
  * a count.  EVERY OTHER entry point ignores the count and cannot see it: wf3d_gemm (the fp32 routes), the attention
- * and skinny kernels, wf3d_row_stats, wf3d_ln_act_apply, wf3d_ln_act_bwd_first, wf3d_split_rows_multi (weights), the
+ * and skinny kernels, wf3d_row_stats, wf3d_ln_act_apply, wf3d_split_rows_multi (weights), the
  * per-vertex launches.  The caller clears the count around launches over other rows (the
  * honouring entry points apply it to whatever rows they are given).
  * ------------------------------------------------------------------------ */

@@ -21,9 +21,10 @@ struct PoolPart {           // per (b, split, c)
 };
 
 __global__ __launch_bounds__(256) void point_valid_kernel(const float* __restrict__ x, int M, int in_dim,
-                                                           float* __restrict__ valid) {
+                                                           float* __restrict__ valid,
+                                                           const int32_t* __restrict__ live_rows) {
     const int m = blockIdx.x * 256 + threadIdx.x;
-    if (m >= M) return;
+    if (m >= wf3d_live_extent(live_rows, M)) return;       // rows past a live-row count's extent: neither read nor written
     float s = 0.f;
     for (int k = 0; k < in_dim; ++k) s += fabsf(x[(size_t)m * in_dim + k]);
     valid[m] = s > 1e-9f ? 1.0f : 0.0f;
@@ -394,6 +395,8 @@ __global__ __launch_bounds__(256) void pool4_seg_final_kernel(const PoolPart* __
 
 // grid (column blocks, parts of a chunk, chunks); MODE 0: fp32, 16 B per lane; 1: sx8; 2: scalar (C % 4 != 0).
 // The pad chunk (cloud -1: rows M .. M_pad-1) is written as exact zeros — in sx8 too, whose zero is all-zero bits.
+// Under a live-row count (the packed batch's row total, rows[B]) the zero fill stops at its extent over M_pad rows: no
+// pad row at or past it is written.  The clouds' chunks lie below the live total and are walked as without a count.
 template <int MODE>
 __global__ __launch_bounds__(256) void pool4_seg_bwd_kernel(const float* __restrict__ valid, const float* __restrict__ cnt,
                                                              const int32_t* __restrict__ arg_m, const int32_t* __restrict__ arg_u,
@@ -402,12 +405,12 @@ __global__ __launch_bounds__(256) void pool4_seg_bwd_kernel(const float* __restr
                                                              const float* __restrict__ dpf_direct,
                                                              const int32_t* __restrict__ rows, const int32_t* __restrict__ chunks,
                                                              int B, int M, int M_pad, int C, int ldm, int ldu,
-                                                             float* __restrict__ dpf) {
+                                                             float* __restrict__ dpf, const int32_t* __restrict__ live_rows) {
     const int k = blockIdx.z;
     const int4 q = *reinterpret_cast<const int4*>(chunks + 4 * (size_t)k);
     if (q.x < 0) {
-        const int r0 = q.z, r1 = q.w;
         if (blockIdx.x != 0) return;
+        const int r0 = q.z, r1 = min(q.w, wf3d_live_extent(live_rows, M_pad));
         for (size_t i = (size_t)r0 * C + blockIdx.y * 256 + threadIdx.x; i < (size_t)r1 * C; i += (size_t)gridDim.y * 256)
             dpf[i] = 0.f;
         return;
@@ -527,7 +530,8 @@ extern "C" int wf3d_point_valid(const float* x, int M, int in_dim, float* valid,
     WF3D_CHECK(M >= 0 && in_dim > 0, WF3D_ERR_ARG, "wf3d_point_valid: bad dims");
     if (M == 0) return WF3D_OK;
     WF3D_CHECK(x && valid, WF3D_ERR_ARG, "wf3d_point_valid: null pointer");
-    hipLaunchKernelGGL(point_valid_kernel, dim3(wf3d_cdiv(M, 256)), dim3(256), 0, (hipStream_t)stream, x, M, in_dim, valid);
+    hipLaunchKernelGGL(point_valid_kernel, dim3(wf3d_cdiv(M, 256)), dim3(256), 0, (hipStream_t)stream, x, M, in_dim, valid,
+                       wf3d_live_rows());
     WF3D_LAUNCH_CHECK();
     return WF3D_OK;
 }
@@ -674,7 +678,8 @@ static int pool4_seg_bwd_impl(const float* valid, const float* cnt, const int32_
     const dim3 grid(cb, ns, nchunk);
     hipStream_t st = (hipStream_t)stream;
 #define WF3D_SEG_BWD(MODE) hipLaunchKernelGGL(pool4_seg_bwd_kernel<MODE>, grid, dim3(256), 0, st, valid, cnt, arg_m, arg_u, dmmax, dmavg, \
-                                              dumean, dumax, dpf_direct, rows, chunks, B, M, M_pad, C, ldm, ldu, dpf)
+                                              dumean, dumax, dpf_direct, rows, chunks, B, M, M_pad, C, ldm, ldu, dpf, \
+                                              wf3d_live_rows())
     if (!vec) WF3D_SEG_BWD(2);
     else if (sx8) WF3D_SEG_BWD(1);
     else WF3D_SEG_BWD(0);

@@ -625,7 +625,8 @@ extern "C" int wf3d_ln_act_bwd_first(const float* dh, const float* z, const floa
     const int wpr = D > 512 ? 4 : (D > 256 ? 2 : 1);
 #define WF3D_BWD1(WPR_)                                                                                                  \
     hipLaunchKernelGGL((ln_act_bwd_kernel<1, WPR_, 8>), dim3(nblk), dim3(256), lds, st, dh, z, R, D, mu, rs, gamma, beta, \
-                       act, wf3d_seed_t{0u, nullptr}, 0u, 1.0f, (float*)nullptr, (float*)nullptr, part, x, ldx, K)
+                       act, wf3d_seed_t{0u, nullptr}, 0u, 1.0f, (float*)nullptr, (float*)nullptr, part, x, ldx, K, \
+                       PairSrc{}, wf3d_live_rows())
     // (one wave per 512-wide row with two slots, <2, 1, 8>: 184 VGPRs, 187 us against 173)
     if (wpr == 4) WF3D_BWD1(4); else if (wpr == 2) WF3D_BWD1(2); else WF3D_BWD1(1);
 #undef WF3D_BWD1

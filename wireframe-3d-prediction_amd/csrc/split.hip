@@ -216,7 +216,11 @@ __global__ __launch_bounds__(256) void first_layer_kernel(const float* __restric
                                                            const float* __restrict__ gamma, const float* __restrict__ beta,
                                                            int act, float eps, float* __restrict__ z,
                                                            float* __restrict__ mu, float* __restrict__ rs,
-                                                           float* __restrict__ h_sx8) {
+                                                           float* __restrict__ h_sx8, const int32_t* __restrict__ live_rows) {
+    // one scalar load at entry, before the W slice: the row walk and the prefetch clamp below stop at the extent, so no
+    // row at or past it is read or written (z, mu, rs, h_sx8)
+    R = wf3d_live_extent(live_rows, R);
+    if (R == 0) return;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const bool odd = lane & 1;
     // columns of a lane, slot i: [512 i + 4 lane, +4) (values 0..3) and [512 i + 256 + 4 lane, +4) (values 4..7)
@@ -492,7 +496,7 @@ extern "C" int wf3d_first_layer_fwd(const float* x, int R, int K, int ldx, const
                       ((uintptr_t)W % 16 == 0) && (!bias || (uintptr_t)bias % 16 == 0);
 #define WF3D_FL(NS_, F_)                                                                                               \
     hipLaunchKernelGGL((first_layer_kernel<NS_, F_>), dim3(blocks), dim3(256), 0, st, x, ldx, K, W, ldw, bias, R, D, gamma, \
-                       beta, act, eps, z, mu, rs, (float*)h_sx8)
+                       beta, act, eps, z, mu, rs, (float*)h_sx8, wf3d_live_rows())
     if (D <= 512) { if (fast) WF3D_FL(1, true); else WF3D_FL(1, false); }
     else          { if (fast) WF3D_FL(2, true); else WF3D_FL(2, false); }
 #undef WF3D_FL

@@ -97,6 +97,12 @@ class PointCloudToWireframe(nn.Module):
         g, _pf, upooled = self.encoder.encode(point_cloud)
         return self._heads(g, upooled, target_vertex_counts)
 
+    def set_packed_tail(self, tail):
+        """The encoder's tail mode for packed batches with a capacity: "compute" (default) or "skip"
+        (PointNetEncoder.set_packed_tail; forward_packed says what changes).  Returns self."""
+        self.encoder.set_packed_tail(tail)
+        return self
+
     def forward_packed(self, points, point_counts, target_vertex_counts=None, capacity=None):
         """forward() of a packed batch: points [M, input_dim] = clouds of any lengths concatenated along the point axis
         (wf3d.packed.pack), point_counts their lengths — host values, a list or a CPU int tensor; a CUDA tensor is read
@@ -108,7 +114,14 @@ class PointCloudToWireframe(nn.Module):
         CUDA int64 / int32 point_counts [B] is then never read on the host: the row layout is built on the device in this
         call, and the dict gains `point_status` (int32 [1] on the device: bit 0 = counts were clamped to the capacity,
         bit 1 = some cloud has no rows; such a cloud pools to zeros and passes no gradient).  With the "padded" edge
-        layout one captured step then serves batches of any point counts."""
+        layout one captured step then serves batches of any point counts.
+
+        set_packed_tail("skip") (with a capacity) stops the encoder's per-point MLP at the live row total rounded up to
+        256 rows instead of computing all `capacity` rows (PointNetEncoder.encode_packed): the rows of `points` behind
+        that are not read and may hold anything, every output and gradient equals the "compute" mode bit for bit; without
+        a capacity the call raises ValueError.  It composes with set_edge_layout("padded", tail="skip"), which does the
+        same for the edge rows."""
+        self.encoder._check_tail(capacity)
         if capacity is None and torch.is_tensor(point_counts) and point_counts.is_cuda:
             point_counts = self._host_counts(point_counts, "_point_count_cache")
         g, _pf, upooled, layout = self.encoder._encode_packed(points, point_counts, capacity)

@@ -9,7 +9,7 @@ import torch
 import torch.nn as nn
 
 from wf3d import config, ops
-from wf3d.functional import EncoderFn, EncoderFnPacked, FusionFn
+from wf3d.functional import EncoderFn, EncoderFnPacked, EncoderFnPackedSkip, FusionFn
 
 
 def _point_block(n_in, n_out):
@@ -41,6 +41,7 @@ class PointNetEncoder(nn.Module):
             nn.Linear(2 * d, d))
         self._n_hidden = len(hidden_dims)
         self.precision = None          # None -> wf3d.config.precision() ("bf16x3" | "bf16" | "fp32")
+        self._packed_tail = "compute"  # set_packed_tail
 
     def _mlp_params(self):
         ps = []
@@ -66,6 +67,24 @@ class PointNetEncoder(nn.Module):
         g = FusionFn.apply(pooled, *self._fusion_params())
         return g, pf, upooled
 
+    def set_packed_tail(self, tail):
+        """What encode_packed does with the rows of a capacity batch behind its clouds: "compute" (default) runs the
+        per-point MLP over all `capacity` rows; "skip" stops it at the live row total (encode_packed).  A setting of
+        the module, like PointCloudToWireframe.set_edge_layout's tail, so that encode_packed / forward_packed keep
+        their signatures.  Returns self."""
+        if tail not in ("compute", "skip"):
+            raise ValueError(f"tail must be 'compute' or 'skip' (got {tail!r})")
+        self._packed_tail = tail
+        return self
+
+    def _check_tail(self, capacity):
+        """The packed tail mode of this call, checked on the host before any device work."""
+        tail = getattr(self, "_packed_tail", "compute")
+        if tail == "skip" and capacity is None:
+            raise ValueError("the packed tail mode 'skip' needs a capacity: without one there are no rows to skip "
+                             "(pass capacity=, or set_packed_tail('compute'))")
+        return tail
+
     def encode_packed(self, points, point_counts, capacity=None):
         """encode() of a packed batch (wf3d.packed.pack): points [M, input_dim] = the clouds concatenated along the point
         axis, point_counts their lengths (host values: a list or a CPU int tensor).  Returns (global [B, C],
@@ -76,11 +95,24 @@ class PointNetEncoder(nn.Module):
         finite behind them, point_features is [capacity, C], and every launch shape depends on (B, capacity) alone.
         point_counts may then also be a CUDA int64 / int32 tensor [B]: it is never read on the host, the row layout is
         built on the device inside this call (ops.DevicePackedLayout; counts it has to clamp are flagged in its status
-        word, which forward_packed returns), so one graph capture serves any counts."""
+        word, which forward_packed returns), so one graph capture serves any counts.
+
+        set_packed_tail (the mode of calls with a capacity): "compute" (default) runs the per-point MLP over all `capacity`
+        rows; "skip" stops it, forward and backward, at R256 = the live row total rounded up to 256 rows (at most capacity), read on the device
+        by each launch, so one capture still serves any counts.  Under "skip"
+          - rows >= R256 of points are not read: they may hold anything, where "compute" needs them finite;
+          - rows >= R256 of the returned point_features are unspecified;
+          - rows >= R256 of a gradient arriving for point_features are not read;
+        and every other output and every gradient equals the "compute" mode bit for bit: the skipped rows are pad rows, whose
+        backward is exact zeros.  The mode needs the split routes (bf16x3 / bf16 precision, capacity >=
+        config.SPLIT_MIN_ROWS, the fused first layer, hidden widths the split kernels take: the default ones do); any
+        other configuration computes the tail as "compute" does (functional._encoder_live).  "skip" without a capacity
+        raises ValueError."""
         return self._encode_packed(points, point_counts, capacity)[:3]
 
     def _encode_packed(self, points, point_counts, capacity):
         """encode_packed, and the layout it ran on."""
+        tail = self._check_tail(capacity)
         on_device = capacity is not None and torch.is_tensor(point_counts) and point_counts.is_cuda
         counts = None if on_device else ops.point_counts_list(point_counts)
         if not torch.is_tensor(points) or points.dim() != 2:
@@ -104,8 +136,9 @@ class PointNetEncoder(nn.Module):
             layout = ops.DevicePackedLayout(point_counts.shape[0], capacity, points.device).build(point_counts.contiguous())
         else:
             layout = ops.PackedLayout.get(counts, points.device, capacity)
-        pooled, pf, upooled = EncoderFnPacked.apply(points.float(), layout, self._n_hidden, self.precision or config.precision(),
-                                                    *self._mlp_params())
+        fn = EncoderFnPackedSkip if tail == "skip" else EncoderFnPacked
+        pooled, pf, upooled = fn.apply(points.float(), layout, self._n_hidden, self.precision or config.precision(),
+                                       *self._mlp_params())
         g = FusionFn.apply(pooled, *self._fusion_params())
         return g, pf, upooled, layout
 

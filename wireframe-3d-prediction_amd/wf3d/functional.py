@@ -181,6 +181,22 @@ def _edge_live(meta, routes, fused_tail):
     return meta.live if ok else None
 
 
+def _encoder_live(layout, routes, tail):
+    """The live-row count the per-point MLP of a packed batch runs under, forward and backward, or None.  It is used in
+    tail="skip" mode for a capacity layout (ops.PackedLayout(counts, capacity) or ops.DevicePackedLayout: the live row
+    total is layout.d_rows[B]) whose first Linear is the fused first-layer pass, forward and backward, and whose later
+    Linears all run split, forward and dgrad, with their wgrads on sx8 operands (the TN kernel or the "transposes"
+    form).  Every launch over point rows then honours the count (include/wf3d.h, "LIVE ROW COUNT"): rows past its
+    extent are never written and never read.  Any other route (fp32 precision, a capacity below SPLIT_MIN_ROWS, a width
+    the split kernels do not take, a first layer first_layer_ok refuses) computes the tail as tail="compute" does: the
+    fp32 GEMMs and wf3d_row_stats do not see a count."""
+    if tail != "skip" or layout is None or layout.capacity is None:
+        return None
+    ok = routes[0] == Route("first", "first", None) and all(
+        r.fwd == "split" and r.dgrad == "split" and r.wgrad in ("tn", "transposes") for r in routes[1:])
+    return layout.d_rows[layout.B:layout.B + 1] if ok else None
+
+
 def _wgrad(r, dz, dz_s, h, pro, h_s, products):
     """dW = dz^T · pro(h) by the route's wgrad form: dz (fp32) or dz_s (sx8), whichever the route formed; h the stored
     input with its prologue pro, h_s the forward's sx8 operand pro(h)."""
@@ -200,7 +216,10 @@ def _wgrad(r, dz, dz_s, h, pro, h_s, products):
 def _dgrad(r, dz, dz_s, W, W_t, products):
     """dh = dz · W by the route's dgrad form; W_t = W^T in sx8 when the forward split it, else None."""
     if r.dgrad == "split":
-        return ops.gemm_split(dz_s, W_t if W_t is not None else ops.split_rows(W, transpose=True), products=products)
+        if W_t is None:
+            with ops.live_rows(None):                  # a weight's rows are not the count's
+                W_t = ops.split_rows(W, transpose=True)
+        return ops.gemm_split(dz_s, W_t, products=products)
     return ops.gemm(dz, W, NN, x3=r.x3)
 
 
@@ -241,13 +260,20 @@ class _PackedPools:
         return ops.pool4_seg_bwd_colsum(nvalid, cnt, arg_m, arg_u, *cots, dpf, self.layout, C, valid=valid)
 
 
-def _encoder_forward(ctx, x2, pools, n_hidden, precision, params):
+def _encoder_forward(ctx, x2, pools, n_hidden, precision, params, tail="compute"):
     """The per-point MLP over the rows of x2 and its pools (`pools`: _DensePools or _PackedPools): the forward of EncoderFn
-    and EncoderFnPacked.  Returns (PoolOut, point_features [rows, C])."""
-    npr = _SPLIT_PRODUCTS.get(precision, 3)
-    valid = ops.point_valid(x2)
+    and EncoderFnPacked.  Returns (PoolOut, point_features [rows, C]).  tail="skip": a packed batch with a capacity runs
+    under its live row total where the routes allow it (_encoder_live); the backward follows ctx.live."""
     routes = _encoder_routes(x2, [params[4 * i] for i in range(n_hidden + 1)], precision in _SPLIT_PRODUCTS,
                              ctx.needs_input_grad[0])
+    ctx.live = live = _encoder_live(getattr(pools, "layout", None), routes, tail)
+    with ops.live_rows(live):
+        return _encoder_forward_rows(ctx, x2, pools, n_hidden, precision, params, routes)
+
+
+def _encoder_forward_rows(ctx, x2, pools, n_hidden, precision, params, routes):
+    npr = _SPLIT_PRODUCTS.get(precision, 3)
+    valid = ops.point_valid(x2)
     # both sx8 orientations (W for the forward GEMM, W^T for its dgrad) of every layer split both ways, one launch
     widx = [i for i, r in enumerate(routes) if r.fwd == "split" and r.dgrad == "split"]
     wsplit = dict(zip(widx, ops.split_weights([params[4 * i] for i in widx]))) if widx else {}
@@ -259,7 +285,12 @@ def _encoder_forward(ctx, x2, pools, n_hidden, precision, params):
             # first Linear + LayerNorm + ReLU + split in one pass (K = input_dim <= 8: a pure write of z and h)
             z, mu, rs, a_s = ops.first_layer_fwd(x2, W, b, params[2], params[3], ACT_RELU)
         elif r.fwd == "split":
-            z = ops.gemm_split(a_s, wsplit[i][0] if i in wsplit else ops.split_rows(W), bias=b, products=npr)
+            if i in wsplit:
+                W_s = wsplit[i][0]
+            else:
+                with ops.live_rows(None):              # a weight's rows are not the count's
+                    W_s = ops.split_rows(W)
+            z = ops.gemm_split(a_s, W_s, bias=b, products=npr)
             a_s = None
         else:
             z = ops.gemm(a, W, NT, bias=b, pro=pro)
@@ -292,7 +323,13 @@ def _encoder_forward(ctx, x2, pools, n_hidden, precision, params):
 
 
 def _encoder_backward(ctx, dpooled, dpf, dupooled):
-    """The backward of EncoderFn and EncoderFnPacked: (gradient of the rows of x2 or None, parameter gradients)."""
+    """The backward of EncoderFn and EncoderFnPacked: (gradient of the rows of x2 or None, parameter gradients), under the
+    live-row count the forward chose (ctx.live)."""
+    with ops.live_rows(ctx.live):
+        return _encoder_backward_rows(ctx, dpooled, dpf, dupooled)
+
+
+def _encoder_backward_rows(ctx, dpooled, dpf, dupooled):
     nh, pools, C, npr, routes = ctx.n_hidden, ctx.pools, ctx.width, ctx.products, ctx.routes
     params = _params(ctx)
     x2, valid, zs, stats, hs, arg_m, arg_u, cnt = _saved(ctx)
@@ -399,6 +436,10 @@ class EncoderFnPacked(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, layout, n_hidden, precision, *params):
+        return EncoderFnPacked._forward(ctx, "compute", x, layout, n_hidden, precision, *params)
+
+    @staticmethod
+    def _forward(ctx, tail, x, layout, n_hidden, precision, *params):
         if ctx.needs_input_grad[0]:
             raise RuntimeError("wf3d: a packed batch that requires grad is not supported (detach the points)")
         M, Din = x.shape
@@ -406,13 +447,28 @@ class EncoderFnPacked(torch.autograd.Function):
         if layout.M_pad != M:
             x2 = x.new_zeros(layout.M_pad, Din)
             x2[:M].copy_(x)
-        po, pf = _encoder_forward(ctx, x2, _PackedPools(layout), n_hidden, precision, params)
+        po, pf = _encoder_forward(ctx, x2, _PackedPools(layout), n_hidden, precision, params, tail)
         return po.masked, pf[:M], po.unmasked
 
     @staticmethod
     def backward(ctx, dpooled, dpf, dupooled):
         _, grads = _encoder_backward(ctx, dpooled, dpf, dupooled)
         return (None, None, None, None, *grads)
+
+
+class EncoderFnPackedSkip(torch.autograd.Function):
+    """EncoderFnPacked in tail="skip" mode: with a capacity layout whose routes all honour a live-row count
+    (_encoder_live) the per-point MLP stops, forward and backward, at the 256-row boundary R256 above the live row total
+    that the layout holds on the device.  Rows >= R256 of x are then not read (they may hold anything), rows >= R256 of
+    point_features are unspecified, and rows >= R256 of a gradient arriving for point_features are not read; the skipped
+    rows are pad rows, whose backward is exact zeros, so every other output and every gradient equals EncoderFnPacked's
+    bit for bit.  Any other layout or route runs exactly as EncoderFnPacked."""
+
+    @staticmethod
+    def forward(ctx, x, layout, n_hidden, precision, *params):
+        return EncoderFnPacked._forward(ctx, "skip", x, layout, n_hidden, precision, *params)
+
+    backward = staticmethod(EncoderFnPacked.backward)
 
 
 class FusionFn(torch.autograd.Function):
