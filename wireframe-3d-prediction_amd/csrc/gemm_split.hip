@@ -14,14 +14,18 @@
 // a compile-time product count NP = 1 (wf3d_gemm_bf16 / wf3d_gemm_bf16_tn): acc += ah*bh only, a plain bf16 GEMM on the
 // round-to-nearest hi planes of the same sx8 operands — the lo fragments are neither read from LDS nor held in registers,
 // the DMA pieces are re-spread over the shorter MFMA sequence.  Kernels in this file:
+//   gemm_split_dma3_kernel<false>                            forward + dgrad: 256x128 tile, 32x32x16 MFMA, three LDS stages:
+//                                                            problems with < 192 tiles of 256x256, N not a multiple of 256
+//   gemm_split_dma3_kernel<true>                             wgrad on reduction-major operands (ds_read_b64_tr_b16): outputs
+//                                                            that are not multiples of 256 wide
 //   gemm_split_x16p_kernel / gemm_split_x16_kernel<false>   forward + dgrad: 256x256x32 tile, v_mfma_f32_16x16x32_bf16,
 //                                                            3 A + 2 B LDS stages (persistent / plain launch)
-//   gemm_split_x16_kernel<true>                              wgrad on reduction-major operands (ds_read_b64_tr_b16)
-//   gemm_split_dma3_kernel / gemm_split_tn_kernel            256x128 tile, 32x32x16 MFMA: problems with < 512 tiles /
-//                                                            wgrad outputs that are not multiples of 256
+//   gemm_split_x16_kernel<true>                              wgrad on reduction-major operands, 256x256 outputs
+// The workgroup -> tile mapping of every kernel is xcd_tiles().
 #include <string.h>
 
 #include <atomic>
+#include <type_traits>
 
 #include "wf3d_common.h"
 
@@ -76,17 +80,42 @@ __device__ __forceinline__ void dma16_asm(const float* src, float* lds_wave_base
                  :: "v"(src), "s"(lds) : "memory");      // m0 is reserved: the compiler never keeps a value in it across statements
 }
 
+// Workgroup -> tile.  Workgroups are dealt to the 8 XCDs round-robin (XCD = blockIdx.x & 7: speed only, no result
+// depends on it) and XCD x owns a contiguous range of the row-major tile ids, the first `ntiles & 7` XCDs one tile more
+// than the rest: tiles that share rows of A or columns of B meet in one L2.  `bid`: blockIdx.x or the XCD index itself
+// (its low three bits are what counts).
+struct XcdTiles { int first; unsigned count; };
+__device__ __forceinline__ XcdTiles xcd_tiles(int ntiles, int bid) {
+    const int q8 = ntiles >> 3, r8 = ntiles & 7, xcd = bid & 7;
+    return {xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8, (unsigned)(xcd < r8 ? q8 + 1 : q8)};
+}
+// the tile of workgroup `bid` in a grid of exactly `ntiles` workgroups
+__device__ __forceinline__ int xcd_tile_id(int ntiles, int bid) { return xcd_tiles(ntiles, bid).first + (bid >> 3); }
+
 // ---------------------------------------------------------------------------
-// Deep-pipelined variant: 256x128 tile, 8 waves (4 x 2, 64x64 each), THREE LDS
-// stages (144 KB, one workgroup per CU, two waves per SIMD).  The DMA of slice
-// t+2 is issued before the MFMAs of slice t and stays in flight across the
-// barrier: a counted `s_waitcnt vmcnt(6)` (the 6 youngest = slice t+2's pieces)
-// retires slice t+1 only, and a raw s_barrier publishes it (never __syncthreads,
-// whose fence would drain vmcnt to 0 — cdna_hip_programming.md "Pipelining
-// across barriers").  The 2-stage kernel above stalls every slice for the DMA
-// latency (issue -> landed ~1-2k cycles vs 768 MFMA cycles per slice).
+// 256x128 tile, 8 waves (4 x 2, 64x64 each), THREE LDS stages (144 KB, one
+// workgroup per CU, two waves per SIMD).  The DMA of slice t+2 is issued before
+// the MFMAs of slice t and stays in flight across the barrier: a counted
+// `s_waitcnt vmcnt(6)` (the 6 youngest = slice t+2's pieces) retires slice t+1
+// only, and a raw s_barrier publishes it (never __syncthreads, whose fence would
+// drain vmcnt to 0 — cdna_hip_programming.md "Pipelining across barriers").
+// With two stages every slice would stall for the DMA latency (issue -> landed
+// ~1-2k cycles vs 768 MFMA cycles per slice).
+//
+// TN form (wgrad): C[Mo,No] = A^T·B with A = sx8[K,Mo], B = sx8[K,No] — both operands
+// reduction-major exactly as the forward/backward passes leave them (h and dz), so no
+// transposed copies are materialised.  Tiles [32 k-rows][cols] are DMA'd row by row and
+// the MFMA fragments (8 consecutive k of one column) are gathered by the hardware
+// transposing read ds_read_b64_tr_b16: a 16-lane group reads a 4-row x 16-column block of
+// 16-bit elements and each lane receives one column of it.  An sx8 row keeps the 8 high
+// (or low) parts of 8 consecutive columns in one 16-B chunk, which is exactly the 4-column
+// 8-B pieces that instruction addresses.  Swizzle: chunk' = chunk ^ ((k&1) | (k&2)<<2)
+// puts the 4 rows x 4 chunks a half-wave reads on 16 distinct 16-B slots (conflict-free).
 // ---------------------------------------------------------------------------
 constexpr int T3_A = 256 * SBK, T3_B = 128 * SBK, T3_STAGE = T3_A + T3_B;
+
+typedef short s16x4 __attribute__((ext_vector_type(4)));
+typedef short s16x8 __attribute__((ext_vector_type(8)));
 
 struct Frag { f32x4 ah[2], al[2], bh[2], bl[2]; };
 
@@ -108,170 +137,19 @@ __device__ __forceinline__ void load_frag(Frag& f, const float* As, const float*
     }
 }
 
-// 12 MFMAs of one k16 step (NP = 3; 4 with NP = 1); DMA pieces P0, P0+1, P0+2 of the slice two ahead are issued
-// one at a time after the 3rd, 6th and 9th MFMA (NP = 1: after the 1st, 2nd and 3rd) (pieces 0..3 = A rows, 4..5 = B rows).
-template <int P0, int NP>
-__device__ __forceinline__ void mma12(f32x16 (&acc)[2][2], const Frag& f, bool ahead, const float* const (&asrc)[4],
-                                      const float* const (&bsrc)[2], int kn, float* dA, float* dB) {
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            if (NP == 3) {
-                acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, f.al[i]), __builtin_bit_cast(bf16x8, f.bh[j]), acc[i][j], 0, 0, 0);
-                acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, f.ah[i]), __builtin_bit_cast(bf16x8, f.bl[j]), acc[i][j], 0, 0, 0);
-            }
-            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, f.ah[i]), __builtin_bit_cast(bf16x8, f.bh[j]), acc[i][j], 0, 0, 0);
-            if (i * 2 + j < 3) {
-                constexpr int dummy = 0; (void)dummy;
-                const int piece = P0 + i * 2 + j;
-                __builtin_amdgcn_sched_barrier(0);
-                if (ahead) {
-                    if (piece < 4) dma16(asrc[piece < 4 ? piece : 0] + kn, dA + piece * 8 * SBK);
-                    else           dma16(bsrc[piece >= 4 ? piece - 4 : 0] + kn, dB + (piece - 4) * 8 * SBK);
-                }
-                __builtin_amdgcn_sched_barrier(0);
-            }
-        }
-    }
-}
-
-
-template <int NP>
-__global__ __launch_bounds__(512, 2) void gemm_split_dma3_kernel(const SplitParams p) {
-    __shared__ __attribute__((aligned(16))) float smem[3 * T3_STAGE];      // 147,456 B
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int wm = wave >> 1, wn = wave & 1;
-    const int h = lane >> 5, l31 = lane & 31;
-
-    const int nwg = p.nbm * p.nbn;
-    const int bid = blockIdx.x;
-    const int q8 = nwg >> 3, r8 = nwg & 7, xcd = bid & 7;
-    const int vid = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (bid >> 3);
-    const int m0 = (vid / p.nbn) * 256, n0 = (vid % p.nbn) * 128;
-    if (m0 >= wf3d_live_extent(p.live, p.M)) return;       // tile past the live rows
-    const int ktotal = p.K / SBK;
-    const int kt0 = blockIdx.z * p.kt_per_split;
-    const int kt1 = min(ktotal, kt0 + p.kt_per_split);
-
-    const float* asrc[4];
-    const float* bsrc[2];
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        const int row = (wave * 4 + q) * 8 + (lane >> 3);
-        asrc[q] = p.A + (size_t)min(m0 + row, p.M - 1) * p.lda + ((lane & 7) ^ ((row >> 1) & 7)) * 4;
-    }
-#pragma unroll
-    for (int q = 0; q < 2; ++q) {
-        const int row = (wave * 2 + q) * 8 + (lane >> 3);
-        bsrc[q] = p.B + (size_t)min(n0 + row, p.N - 1) * p.ldb + ((lane & 7) ^ ((row >> 1) & 7)) * 4;
-    }
-    auto issue = [&](int kt, int stage) {
-        float* As = smem + stage * T3_STAGE + wave * 4 * 8 * SBK;
-        float* Bs = smem + stage * T3_STAGE + T3_A + wave * 2 * 8 * SBK;
-#pragma unroll
-        for (int q = 0; q < 4; ++q) dma16(asrc[q] + kt * SBK, As + q * 8 * SBK);
-#pragma unroll
-        for (int q = 0; q < 2; ++q) dma16(bsrc[q] + kt * SBK, Bs + q * 8 * SBK);
-    };
-
-    f32x16 acc[2][2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
-
-    const int fsw = (l31 >> 1) & 7;
-    if (kt0 < kt1) issue(kt0, 0);
-    if (kt0 + 1 < kt1) {
-        issue(kt0 + 1, 1);
-        asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
-    } else {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    }
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
-
-    // Measured alternatives that LOST on this structure (same shapes, same process): a half-slice
-    // stagger of waves 4-7 against their SIMD partners (-11 %: duplicated bodies, +70 VGPRs) and
-    // fetching both k16 steps' fragments up front (-4 %).  Bunching the 6 DMA pieces at the loop
-    // top instead of spreading them between MFMA groups: -7 %.
-    Frag X, Y;
-    int stage = 0;
-    for (int kt = kt0; kt < kt1; ++kt) {
-        const bool ahead = kt + 2 < kt1;
-        const int nstage = stage == 0 ? 2 : stage - 1;                   // (stage + 2) % 3
-        float* dA = smem + nstage * T3_STAGE + wave * 4 * 8 * SBK;
-        float* dB = smem + nstage * T3_STAGE + T3_A + wave * 2 * 8 * SBK;
-        const int kn = (kt + 2) * SBK;
-        const float* As = smem + stage * T3_STAGE;
-        const float* Bs = As + T3_A;
-        load_frag<NP>(X, As, Bs, wm, wn, l31, h, fsw, 0);
-        mma12<0, NP>(acc, X, ahead, asrc, bsrc, kn, dA, dB);
-        load_frag<NP>(Y, As, Bs, wm, wn, l31, h, fsw, 1);
-        mma12<3, NP>(acc, Y, ahead, asrc, bsrc, kn, dA, dB);
-        // retire slice kt+1 (all but the 6 youngest DMA pieces), make sure this wave's LDS reads
-        // of slice kt are done (lgkmcnt) before anyone may overwrite the stage, then publish.
-        if (ahead) asm volatile("s_waitcnt vmcnt(6) lgkmcnt(0)" ::: "memory");
-        else       asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();
-        asm volatile("" ::: "memory");
-        stage = stage == 2 ? 0 : stage + 1;
-    }
-
-    const bool split = p.ksplit > 1;
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            const int col = n0 + (wn * 2 + j) * 32 + l31;
-            if (col >= p.N) continue;
-            const float bv = (!split && p.bias) ? p.bias[col] : 0.f;
-#pragma unroll
-            for (int e = 0; e < 16; ++e) {
-                const int row = m0 + (wm * 2 + i) * 32 + (e & 3) + 8 * (e >> 2) + 4 * h;
-                if (row >= p.M) continue;
-                float v = acc[i][j][e];
-                if (split) {
-                    p.slab[((size_t)blockIdx.z * p.M + row) * p.N + col] = v;
-                } else {
-                    v += bv;
-                    float* c = p.C + (size_t)row * p.ldc + col;
-                    if (p.accumulate) v += *c;
-                    *c = v;
-                }
-            }
-        }
-    }
-}
-
-// ---------------------------------------------------------------------------
-// TN form (wgrad): C[Mo,No] = A^T·B with A = sx8[K,Mo], B = sx8[K,No] — both operands
-// reduction-major exactly as the forward/backward passes leave them (h and dz), so no
-// transposed copies are materialised.  Tiles [32 k-rows][cols] are DMA'd row by row and
-// the MFMA fragments (8 consecutive k of one column) are gathered by the hardware
-// transposing read ds_read_b64_tr_b16: a 16-lane group reads a 4-row x 16-column block of
-// 16-bit elements and each lane receives one column of it.  An sx8 row keeps the 8 high
-// (or low) parts of 8 consecutive columns in one 16-B chunk, which is exactly the 4-column
-// 8-B pieces that instruction addresses.  Swizzle: chunk' = chunk ^ ((k&1) | (k&2)<<2)
-// puts the 4 rows x 4 chunks a half-wave reads on 16 distinct 16-B slots (conflict-free).
-// Same pipeline as gemm_split_dma3_kernel (256x128 tile, 8 waves, 3 stages, counted vmcnt).
-// ---------------------------------------------------------------------------
-typedef short s16x4 __attribute__((ext_vector_type(4)));
-typedef short s16x8 __attribute__((ext_vector_type(8)));
-
 __device__ __forceinline__ f32x4 tr_frag(const char* base, int off, int row_bytes) {
     const s16x4 a = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(base + off));
     const s16x4 b = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(base + off + 4 * row_bytes));
     return __builtin_bit_cast(f32x4, __builtin_shufflevector(a, b, 0, 1, 2, 3, 4, 5, 6, 7));
 }
 
-template <int P0, int NP>
-__device__ __forceinline__ void mma12_tn(f32x16 (&acc)[2][2], const Frag& f, bool ahead, const float* const (&asrc)[4],
-                                         const float* const (&bsrc)[2], size_t ka, size_t kb, float* dA, float* dB) {
+// 12 MFMAs of one k16 step (NP = 3; 4 with NP = 1); DMA pieces P0, P0+1, P0+2 of the slice two ahead are issued
+// one at a time after the 3rd, 6th and 9th MFMA (NP = 1: after the 1st, 2nd and 3rd) (pieces 0..3 = A, 4..5 = B; every
+// piece is 1 KB = 256 floats of LDS).  ka / kb: float offsets of that slice in A / B (Off: int in the NT form, whose
+// slices are 32 floats apart in a row; size_t in the TN form, 32 rows apart).
+template <int P0, int NP, typename Off>
+__device__ __forceinline__ void mma12(f32x16 (&acc)[2][2], const Frag& f, bool ahead, const float* const (&asrc)[4],
+                                      const float* const (&bsrc)[2], Off ka, Off kb, float* dA, float* dB) {
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
 #pragma unroll
@@ -294,41 +172,56 @@ __device__ __forceinline__ void mma12_tn(f32x16 (&acc)[2][2], const Frag& f, boo
     }
 }
 
-template <int NP>
-__global__ __launch_bounds__(512, 2) void gemm_split_tn_kernel(const SplitParams p) {
-    __shared__ __attribute__((aligned(16))) float smem[3 * T3_STAGE];      // A slice 32x256, B slice 32x128 floats
+// TN = false:  C[M,N] (+)= A·B^T (+ bias), A = sx8[M,K], B = sx8[N,K]; partial tiles in M and N.
+// TN = true :  C[M,N] (+)= A^T·B, A = sx8[K,M], B = sx8[K,N]; full tiles only (M % 256 == 0, N % 128 == 0), no bias.
+template <bool TN, int NP>
+__global__ __launch_bounds__(512, 2) void gemm_split_dma3_kernel(const SplitParams p) {
+    __shared__ __attribute__((aligned(16))) float smem[3 * T3_STAGE];      // 147,456 B; TN: A slice 32x256, B slice 32x128 floats
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wm = wave >> 1, wn = wave & 1;
     const int h = lane >> 5, l31 = lane & 31;
 
-    const int nwg = p.nbm * p.nbn;
-    const int bid = blockIdx.x;
-    const int q8 = nwg >> 3, r8 = nwg & 7, xcd = bid & 7;
-    const int vid = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (bid >> 3);
-    const int m0 = (vid / p.nbn) * 256, n0 = (vid % p.nbn) * 128;      // p.M = Mo, p.N = No (full tiles only)
-    const int ktotal = wf3d_live_extent(p.live, p.K) / SBK;           // a range past it runs no slice and stores zeros
+    const int vid = xcd_tile_id(p.nbm * p.nbn, blockIdx.x);
+    const int m0 = (vid / p.nbn) * 256, n0 = (vid % p.nbn) * 128;
+    // live rows: M of the NT form (a tile past them leaves), K of a wgrad (a range past them runs no slice and stores zeros)
+    if (!TN && m0 >= wf3d_live_extent(p.live, p.M)) return;
+    const int ktotal = (TN ? wf3d_live_extent(p.live, p.K) : p.K) / SBK;
     const int kt0 = blockIdx.z * p.kt_per_split;
     const int kt1 = min(ktotal, kt0 + p.kt_per_split);
 
-    // DMA: A piece = one k-row of the tile (1 KB, 64 chunks); B piece = two k-rows (2 x 512 B)
+    // DMA sources: 4 A pieces + 2 B pieces of 1 KB per wave and slice.  NT: a piece = 8 tile rows x 128 B.
+    // TN: an A piece = one k-row of the tile (1 KB, 64 chunks); a B piece = two k-rows (2 x 512 B).
     const float* asrc[4];
     const float* bsrc[2];
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
-        const int kr = wave * 4 + q;
-        const int f = (kr & 1) | ((kr & 2) << 2);
-        asrc[q] = p.A + (size_t)kr * p.lda + m0 + (lane ^ f) * 4;
+        if (TN) {
+            const int kr = wave * 4 + q;
+            const int f = (kr & 1) | ((kr & 2) << 2);
+            asrc[q] = p.A + (size_t)kr * p.lda + m0 + (lane ^ f) * 4;
+        } else {
+            const int row = (wave * 4 + q) * 8 + (lane >> 3);
+            asrc[q] = p.A + (size_t)min(m0 + row, p.M - 1) * p.lda + ((lane & 7) ^ ((row >> 1) & 7)) * 4;
+        }
     }
 #pragma unroll
     for (int q = 0; q < 2; ++q) {
-        const int kr = (wave * 2 + q) * 2 + (lane >> 5);
-        const int f = (kr & 1) | ((kr & 2) << 2);
-        bsrc[q] = p.B + (size_t)kr * p.ldb + n0 + ((lane & 31) ^ f) * 4;
+        if (TN) {
+            const int kr = (wave * 2 + q) * 2 + (lane >> 5);
+            const int f = (kr & 1) | ((kr & 2) << 2);
+            bsrc[q] = p.B + (size_t)kr * p.ldb + n0 + ((lane & 31) ^ f) * 4;
+        } else {
+            const int row = (wave * 2 + q) * 8 + (lane >> 3);
+            bsrc[q] = p.B + (size_t)min(n0 + row, p.N - 1) * p.ldb + ((lane & 7) ^ ((row >> 1) & 7)) * 4;
+        }
     }
-    const size_t astep = (size_t)SBK * p.lda, bstep = (size_t)SBK * p.ldb;   // floats per 32-row slice
+    using Off = std::conditional_t<TN, size_t, int>;                       // see mma12
+    const Off astep = TN ? (Off)((size_t)SBK * p.lda) : (Off)SBK, bstep = TN ? (Off)((size_t)SBK * p.ldb) : (Off)SBK;   // floats per slice
 
-    // fragment byte offsets inside a stage (transposing reads): lane = 16*gi + 4*q + pp
+    // fragment addressing.  NT: the swizzle of this lane's row (load_frag).  TN: byte offsets inside a stage for the
+    // transposing reads, lane = 16*gi + 4*tq + tp
+    const int fsw = (l31 >> 1) & 7;
     const int gi = lane >> 4, li = lane & 15, tq = li >> 2, tp = li & 3;
     const int fq = (tq & 1) | ((tq & 2) << 2);
     int aoff[2], boff[2];
@@ -342,16 +235,19 @@ __global__ __launch_bounds__(512, 2) void gemm_split_tn_kernel(const SplitParams
         const int c0 = (wn * 2 + j) * 32 + 16 * (gi & 1) + 4 * tp;                 // column inside the 128-wide B tile
         boff[j] = (8 * (gi >> 1) + tq) * 512 + (((2 * (c0 >> 3)) ^ fq) * 16) + (c0 & 7) * 2;
     }
-    auto load_frag_tn = [&](Frag& f, const char* As, const char* Bs, int s2) {
+    auto load = [&](Frag& f, const float* As, const float* Bs, int s2) {
+        if (!TN) { load_frag<NP>(f, As, Bs, wm, wn, l31, h, fsw, s2); return; }
+        const char* Ab = reinterpret_cast<const char*>(As);
+        const char* Bb = reinterpret_cast<const char*>(Bs);
 #pragma unroll
         for (int i = 0; i < 2; ++i) {
-            f.ah[i] = tr_frag(As, aoff[i] + s2 * 16 * 1024, 1024);
-            if (NP == 3) f.al[i] = tr_frag(As, (aoff[i] ^ 16) + s2 * 16 * 1024, 1024);
+            f.ah[i] = tr_frag(Ab, aoff[i] + s2 * 16 * 1024, 1024);
+            if (NP == 3) f.al[i] = tr_frag(Ab, (aoff[i] ^ 16) + s2 * 16 * 1024, 1024);
         }
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
-            f.bh[j] = tr_frag(Bs, boff[j] + s2 * 16 * 512, 512);
-            if (NP == 3) f.bl[j] = tr_frag(Bs, (boff[j] ^ 16) + s2 * 16 * 512, 512);
+            f.bh[j] = tr_frag(Bb, boff[j] + s2 * 16 * 512, 512);
+            if (NP == 3) f.bl[j] = tr_frag(Bb, (boff[j] ^ 16) + s2 * 16 * 512, 512);
         }
     };
     auto issue = [&](int kt, int stage) {
@@ -381,20 +277,26 @@ __global__ __launch_bounds__(512, 2) void gemm_split_tn_kernel(const SplitParams
     __builtin_amdgcn_s_barrier();
     asm volatile("" ::: "memory");
 
+    // Measured alternatives that LOST on this structure (same shapes, same process): a half-slice
+    // stagger of waves 4-7 against their SIMD partners (-11 %: duplicated bodies, +70 VGPRs) and
+    // fetching both k16 steps' fragments up front (-4 %).  Bunching the 6 DMA pieces at the loop
+    // top instead of spreading them between MFMA groups: -7 %.
     Frag X, Y;
     int stage = 0;
     for (int kt = kt0; kt < kt1; ++kt) {
         const bool ahead = kt + 2 < kt1;
-        const int nstage = stage == 0 ? 2 : stage - 1;
+        const int nstage = stage == 0 ? 2 : stage - 1;                   // (stage + 2) % 3
         float* dA = smem + nstage * T3_STAGE + wave * 4 * 256;
         float* dB = smem + nstage * T3_STAGE + T3_A + wave * 2 * 256;
-        const size_t ka = (size_t)(kt + 2) * astep, kb = (size_t)(kt + 2) * bstep;
-        const char* As = reinterpret_cast<const char*>(smem + stage * T3_STAGE);
-        const char* Bs = As + T3_A * 4;
-        load_frag_tn(X, As, Bs, 0);
-        mma12_tn<0, NP>(acc, X, ahead, asrc, bsrc, ka, kb, dA, dB);
-        load_frag_tn(Y, As, Bs, 1);
-        mma12_tn<3, NP>(acc, Y, ahead, asrc, bsrc, ka, kb, dA, dB);
+        const Off ka = (Off)(kt + 2) * astep, kb = (Off)(kt + 2) * bstep;
+        const float* As = smem + stage * T3_STAGE;
+        const float* Bs = As + T3_A;
+        load(X, As, Bs, 0);
+        mma12<0, NP>(acc, X, ahead, asrc, bsrc, ka, kb, dA, dB);
+        load(Y, As, Bs, 1);
+        mma12<3, NP>(acc, Y, ahead, asrc, bsrc, ka, kb, dA, dB);
+        // retire slice kt+1 (all but the 6 youngest DMA pieces), make sure this wave's LDS reads
+        // of slice kt are done (lgkmcnt) before anyone may overwrite the stage, then publish.
         if (ahead) asm volatile("s_waitcnt vmcnt(6) lgkmcnt(0)" ::: "memory");
         else       asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
         __builtin_amdgcn_s_barrier();
@@ -408,13 +310,17 @@ __global__ __launch_bounds__(512, 2) void gemm_split_tn_kernel(const SplitParams
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
             const int col = n0 + (wn * 2 + j) * 32 + l31;
+            if (!TN && col >= p.N) continue;
+            const float bv = (!TN && !split && p.bias) ? p.bias[col] : 0.f;
 #pragma unroll
             for (int e = 0; e < 16; ++e) {
                 const int row = m0 + (wm * 2 + i) * 32 + (e & 3) + 8 * (e >> 2) + 4 * h;
+                if (!TN && row >= p.M) continue;
                 float v = acc[i][j][e];
                 if (split) {
                     p.slab[((size_t)blockIdx.z * p.M + row) * p.N + col] = v;
                 } else {
+                    if (!TN) v += bv;
                     float* c = p.C + (size_t)row * p.ldc + col;
                     if (p.accumulate) v += *c;
                     *c = v;
@@ -424,12 +330,12 @@ __global__ __launch_bounds__(512, 2) void gemm_split_tn_kernel(const SplitParams
     }
 }
 
-// tile constants of the 256x256 kernels below (x16 / x16p): one operand slice = 256 rows x 32 floats = 32 KB
-constexpr int T4_A = 256 * SBK, T4_STAGE = 2 * T4_A;
+// tile constant of the 256x256 kernels below (x16 / x16p): one operand slice = 256 rows x 32 floats = 32 KB
+constexpr int T4_A = 256 * SBK;
 
 // ---------------------------------------------------------------------------
-// 256x256x32 tile on v_mfma_f32_16x16x32_bf16.  Same LDS image, DMA and two stages as the
-// 256x256 kernel above, different MFMA shape: in an MFMA-dense loop on real data this chip is
+// 256x256x32 tile on v_mfma_f32_16x16x32_bf16.  Same LDS image and DMA as the 256x128 kernel
+// above, different MFMA shape: in an MFMA-dense loop on real data this chip is
 // clock-limited by power (scripts/micro/mfma_peak.hip, register-only, random operands: the
 // 32x32x16 loop holds 1.89 PF, the 16x16x32 loop 2.06-2.21 PF at equal cycles per FLOP), so the
 // shape that costs less energy per FLOP wins.  LDS bytes per FLOP are unchanged (128x64 per
@@ -463,9 +369,9 @@ template <bool TN, int NP>
 __global__ __launch_bounds__(512, 2) void gemm_split_x16_kernel(const SplitParams p) {
     // All 160 KB of LDS: THREE stages for A (the operand streamed from HBM: its slice t+2 is in flight while t
     // is multiplied) and two for B (weights / the other streamed operand: slice t+1).  Measured with in-kernel
-    // stamps (round 1, instrumentation since removed) on the two-stage forward/dgrad kernel: 9-35 % of every slice was spent waiting for
-    // the A pieces issued one slice earlier — HBM read latency under the kernel's own C-store traffic is more
-    // than one slice (wgrad, which stores almost nothing: 2 %).
+    // stamps (round 1) on an earlier form of this kernel with two stages per operand: 9-35 % of every slice was
+    // spent waiting for the A pieces issued one slice earlier — HBM read latency under the kernel's own C-store
+    // traffic is more than one slice (wgrad, which stores almost nothing: 2 %).
     __shared__ __attribute__((aligned(16))) float smem[5 * T4_A];          // 163,840 B
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -473,8 +379,7 @@ __global__ __launch_bounds__(512, 2) void gemm_split_x16_kernel(const SplitParam
     const int r16 = lane & 15, g = lane >> 4;
 
     const int nwg = p.nbm * p.nbn;
-    const int bid = blockIdx.x;
-    const int q8 = nwg >> 3, r8 = nwg & 7, xcd = bid & 7;
+    const int bid = blockIdx.x, xcd = bid & 7;
     int vid, zi;
     if (p.zmap) {
         // wgrad: every tile of one split-K range z reads the same rows of both operands.  Workgroups are dealt to the
@@ -485,7 +390,7 @@ __global__ __launch_bounds__(512, 2) void gemm_split_x16_kernel(const SplitParam
         vid = q % nwg;
         zi = (q / nwg) * 8 + xcd;
     } else {
-        vid = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (bid >> 3);
+        vid = xcd_tile_id(nwg, bid);
         zi = blockIdx.z;
     }
     const int m0 = (vid / p.nbn) * 256, n0 = (vid % p.nbn) * 256;
@@ -816,10 +721,10 @@ __global__ __launch_bounds__(512, 2) void gemm_split_x16p_kernel(const SplitPara
     // than its slice's DMA pieces, so the counted waits below are unchanged — first needed in slice ktotal - 2.
     // under a live-row count the live tiles (the first rows' tiles: ids are row-major) are the ones dealt and claimed
     const int nwg = (wf3d_live_extent(p.live, p.M) / 256) * p.nbn;
-    const int bid = blockIdx.x;
-    const int q8 = nwg >> 3, r8 = nwg & 7, xcd = bid & 7;
-    const int xbase = xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8;
-    const unsigned xcnt = xcd < r8 ? q8 + 1 : q8;
+    const int bid = blockIdx.x, xcd = bid & 7;
+    const XcdTiles mine = xcd_tiles(nwg, xcd);
+    const int xbase = mine.first;
+    const unsigned xcnt = mine.count;
     unsigned* const ctr = p.ctl + xcd * 16;
     unsigned* const mbox = p.ctl + 128 + bid;
     if (tid == 0) reinterpret_cast<unsigned*>(smem)[0] = __hip_atomic_fetch_add(ctr, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -907,8 +812,10 @@ __global__ __launch_bounds__(512, 2) void gemm_split_x16p_kernel(const SplitPara
             }
         }
     };
-    int trip = 0;            // (slice counter of the diagnostic stamps)
-    for (;; ++trip) {
+#if WF3D_STAMP
+    int nstamp = 0;          // slices stamped so far
+#endif
+    for (;;) {
         if (kt == ktotal) {
             // ---- tile `cur` is complete (checked at the TOP of the trip, so that nothing but the loop edge follows a
             // slice's tail: the compiler sinks the tail's fragment reads into whatever block comes next) ----
@@ -957,7 +864,8 @@ __global__ __launch_bounds__(512, 2) void gemm_split_x16p_kernel(const SplitPara
             const float* Asn = smem + astage1 * T4_A;
             const float* Bsn = smemB + (stage ^ 1) * T4_A;
 #if WF3D_STAMP
-            if (tid == 0 && 2 * trip + half < STAMP_PER_WG) g_stamps[bid * STAMP_PER_WG + 2 * trip + half] = __builtin_amdgcn_s_memtime();    // older than this slice's DMA pieces
+            if (tid == 0 && nstamp < STAMP_PER_WG) g_stamps[bid * STAMP_PER_WG + nstamp] = __builtin_amdgcn_s_memtime();    // older than this slice's DMA pieces
+            ++nstamp;
 #endif
             if (BIAS && half == 1 && has_next && kt == ktotal - 1) {
                 // the next tile's bias, requested before this slice's DMA pieces: the slice's vmcnt(4) retires it
@@ -1037,24 +945,45 @@ SplitK plan_tn(int Mo, int No, int K) {
     return wf3d_splitk_plan(big ? WF3D_SPLITK_TN16 : WF3D_SPLITK_TN, tiles, K / SBK, rounds);
 }
 
+// The kernel forms and their grids.  DMA3 / X16: one workgroup per tile and K range; X16P: `cus` persistent workgroups;
+// X16_TN under zmap: a 1-D grid of tiles x K ranges (SplitParams::zmap).
+enum class Form { DMA3, X16, X16P, DMA3_TN, X16_TN };
+
 template <int NP>
-void launch_split_dma(const SplitParams& p, int variant, bool persist, int cus, hipStream_t st) {
-    if (variant == 6) {
-        if (persist) {
-            if (p.bias) hipLaunchKernelGGL((gemm_split_x16p_kernel<true, NP>), dim3(cus, 1, 1), dim3(512), 0, st, p);
-            else        hipLaunchKernelGGL((gemm_split_x16p_kernel<false, NP>), dim3(cus, 1, 1), dim3(512), 0, st, p);
-        } else
-            hipLaunchKernelGGL((gemm_split_x16_kernel<false, NP>), dim3(p.nbm * p.nbn, 1, p.ksplit), dim3(512), 0, st, p);
-    } else {
-        hipLaunchKernelGGL((gemm_split_dma3_kernel<NP>), dim3(p.nbm * p.nbn, 1, p.ksplit), dim3(512), 0, st, p);
+void launch_form(Form form, const SplitParams& p, int cus, hipStream_t st) {
+    const dim3 tiles(p.nbm * p.nbn, 1, p.ksplit), block(512);
+    switch (form) {
+    case Form::DMA3:    hipLaunchKernelGGL((gemm_split_dma3_kernel<false, NP>), tiles, block, 0, st, p); break;
+    case Form::X16:     hipLaunchKernelGGL((gemm_split_x16_kernel<false, NP>), tiles, block, 0, st, p); break;
+    case Form::X16P:
+        if (p.bias) hipLaunchKernelGGL((gemm_split_x16p_kernel<true, NP>), dim3(cus, 1, 1), block, 0, st, p);
+        else        hipLaunchKernelGGL((gemm_split_x16p_kernel<false, NP>), dim3(cus, 1, 1), block, 0, st, p);
+        break;
+    case Form::DMA3_TN: hipLaunchKernelGGL((gemm_split_dma3_kernel<true, NP>), tiles, block, 0, st, p); break;
+    case Form::X16_TN:
+        hipLaunchKernelGGL((gemm_split_x16_kernel<true, NP>), p.zmap ? dim3(p.nbm * p.nbn * p.ksplit, 1, 1) : tiles, block, 0, st, p);
+        break;
     }
 }
 
-template <int NP>
-void launch_split_tn(const SplitParams& p, bool big, hipStream_t st) {
-    if (big && p.zmap) hipLaunchKernelGGL((gemm_split_x16_kernel<true, NP>), dim3(p.nbm * p.nbn * p.ksplit, 1, 1), dim3(512), 0, st, p);
-    else if (big)      hipLaunchKernelGGL((gemm_split_x16_kernel<true, NP>), dim3(p.nbm * p.nbn, 1, p.ksplit), dim3(512), 0, st, p);
-    else               hipLaunchKernelGGL((gemm_split_tn_kernel<NP>), dim3(p.nbm * p.nbn, 1, p.ksplit), dim3(512), 0, st, p);
+// products: 3 = bf16x3, 1 = plain bf16 on the hi planes — the kernels' compile-time NP
+void launch(int products, Form form, const SplitParams& p, int cus, hipStream_t st) {
+    if (products == 1) launch_form<1>(form, p, cus, st);
+    else               launch_form<3>(form, p, cus, st);
+}
+
+// Operands, tile grid (256 x tile_n) and the split-K plan fitted to the workspace, for either operand layout
+SplitParams split_params(const void* A_sx8, const void* B_sx8, float* C, const float* bias, int M, int N, int K, int lda,
+                         int ldb, int ldc, int accumulate, int tile_n, const SplitK& plan, void* ws, size_t ws_bytes) {
+    SplitParams p{};
+    p.A = (const float*)A_sx8; p.B = (const float*)B_sx8; p.C = C; p.bias = bias;
+    p.M = M; p.N = N; p.K = K; p.lda = lda; p.ldb = ldb; p.ldc = ldc; p.accumulate = accumulate;
+    p.nbm = wf3d_cdiv(M, 256); p.nbn = wf3d_cdiv(N, tile_n);
+    const SplitK s = wf3d_splitk_fit(plan, K / SBK, M, N, ws, ws_bytes);
+    p.ksplit = s.ksplit; p.kt_per_split = s.kt_per;
+    p.slab = p.ksplit > 1 ? (float*)ws : nullptr;
+    p.live = wf3d_live_rows();
+    return p;
 }
 
 // rows_live: the live-row count when it runs over the output's rows (forward / dgrad), NULL for a wgrad (its rows are K)
@@ -1084,28 +1013,21 @@ int gemm_split_impl(const char* fn, int products, const void* A_sx8, const void*
         return wf3d_gemm_split_regs(products, A_sx8, B_sx8, C, bias, M, N, K, lda, ldb, ldc, accumulate, s, (float*)ws,
                                     wf3d_live_rows(), st);
     }
-    SplitParams p{};
-    p.live = wf3d_live_rows();
-    p.A = (const float*)A_sx8; p.B = (const float*)B_sx8; p.C = C; p.bias = bias;
-    p.M = M; p.N = N; p.K = K; p.lda = lda; p.ldb = ldb; p.ldc = ldc; p.accumulate = accumulate;
     const int variant = split_variant(M, N, kernel);
-    p.nbm = wf3d_cdiv(M, 256); p.nbn = wf3d_cdiv(N, variant == 6 ? 256 : 128);
-    const SplitK s = wf3d_splitk_fit(plan_dma(M, N, K, variant), K / SBK, M, N, ws, ws_bytes);
-    p.ksplit = s.ksplit; p.kt_per_split = s.kt_per;
-    p.slab = p.ksplit > 1 ? (float*)ws : nullptr;
-    bool persist = false;
+    SplitParams p = split_params(A_sx8, B_sx8, C, bias, M, N, K, lda, ldb, ldc, accumulate, variant == 6 ? 256 : 128,
+                                 plan_dma(M, N, K, variant), ws, ws_bytes);
+    Form form = variant == 6 ? Form::X16 : Form::DMA3;
     int cus = 0;
     if (variant == 6) {
         cus = cu_count();
         { const int lim = g_gemm_cus.load(std::memory_order_relaxed); if (lim >= 8 && lim < cus) cus = lim / 8 * 8; }
-        persist = persistent_ok(p, cus, ws, ws_bytes);
-        if (persist) {
+        if (persistent_ok(p, cus, ws, ws_bytes)) {
+            form = Form::X16P;
             p.ctl = (unsigned*)ws;
             if (hipMemsetAsync(ws, 0, 512, st) != hipSuccess) { wf3d_set_error("%s: hipMemsetAsync failed", fn); return WF3D_ERR_LAUNCH; }
         }
     }
-    if (products == 1) launch_split_dma<1>(p, variant, persist, cus, st);
-    else               launch_split_dma<3>(p, variant, persist, cus, st);
+    launch(products, form, p, cus, st);
     WF3D_LAUNCH_CHECK();
     return combine(p, p.live, st);
 }
@@ -1117,19 +1039,12 @@ int gemm_split_tn_impl(const char* fn, int products, const void* A_sx8, const vo
     WF3D_CHECK(A_sx8 && B_sx8 && C, WF3D_ERR_ARG, "%s: null operand", fn);
     WF3D_CHECK(lda >= Mo && ldb >= No && ldc >= No, WF3D_ERR_ARG, "%s: leading dimension too small", fn);
     WF3D_CHECK(((uintptr_t)A_sx8 % 16 == 0) && ((uintptr_t)B_sx8 % 16 == 0), WF3D_ERR_ARG, "%s: misaligned operand", fn);
-    SplitParams p{};
-    p.A = (const float*)A_sx8; p.B = (const float*)B_sx8; p.C = C; p.bias = nullptr;
-    p.M = Mo; p.N = No; p.K = K; p.lda = lda; p.ldb = ldb; p.ldc = ldc; p.accumulate = accumulate;
     const bool big = tn16(Mo, No);
-    p.nbm = Mo / 256; p.nbn = No / (big ? 256 : 128);
-    const SplitK s = wf3d_splitk_fit(plan_tn(Mo, No, K), K / SBK, Mo, No, ws, ws_bytes);
-    p.ksplit = s.ksplit; p.kt_per_split = s.kt_per;
-    p.slab = p.ksplit > 1 ? (float*)ws : nullptr;
+    SplitParams p = split_params(A_sx8, B_sx8, C, nullptr, Mo, No, K, lda, ldb, ldc, accumulate, big ? 256 : 128,
+                                 plan_tn(Mo, No, K), ws, ws_bytes);
     p.zmap = big && p.ksplit >= 8 && p.ksplit % 8 == 0;
-    p.live = wf3d_live_rows();
     hipStream_t st = (hipStream_t)stream;
-    if (products == 1) launch_split_tn<1>(p, big, st);
-    else               launch_split_tn<3>(p, big, st);
+    launch(products, big ? Form::X16_TN : Form::DMA3_TN, p, 0, st);
     WF3D_LAUNCH_CHECK();
     return combine(p, nullptr, st);
 }
