@@ -26,7 +26,7 @@ static inline AttnArgs wf3d_attn_args(const float* qkv, const int32_t* voff, int
     a.qkv = qkv; a.ctx = (float*)ctx; a.lse = (float*)lse; a.dctx = dctx; a.dqkv = dqkv; a.voff = voff;
     a.E = E; a.heads = heads; a.hd = E / heads;
     a.scale = 1.0f / sqrtf((float)a.hd);
-    if (drop_p > 0.f) { a.seed = wf3d_seed_arg(drop_p, drop_seed); a.thresh = (uint32_t)((double)drop_p * 4294967296.0); a.dscale = 1.0f / (1.0f - drop_p); }
+    if (drop_p > 0.f) { const wf3d_drop_t d = wf3d_drop_args(drop_p, drop_seed); a.seed = d.seed; a.thresh = d.thresh; a.dscale = d.scale; }
     return a;
 }
 

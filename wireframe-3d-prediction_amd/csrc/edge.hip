@@ -464,8 +464,7 @@ static int pair_fwd_impl(const float* Pa, const float* Pb, const float* cv, cons
                          const int32_t* voff, const int32_t* eoff, const int32_t* esample, int Re, int H, float eps,
                          float* pre, float* mu, float* rs, float* delta, const float* gamma, const float* beta, int act,
                          float drop_p, uint32_t drop_seed, void* h_sx8, int vd, void* stream) {
-    const uint32_t thresh = drop_p > 0.f ? (uint32_t)((double)drop_p * 4294967296.0) : 0u;
-    const float dscale = 1.0f / (1.0f - drop_p);
+    const wf3d_drop_t drop = wf3d_drop_args(drop_p, drop_seed);
     WF3D_CHECK(Re >= 0 && H > 0 && vd >= 1 && vd <= 8, WF3D_ERR_ARG, "wf3d_edge_pair_fwd: bad dims (vertex_dim must be 1..8)");
     WF3D_CHECK(H % 4 == 0 && H <= 2048, WF3D_ERR_UNSUPPORTED, "wf3d_edge_pair_fwd: hidden %d must be a multiple of 4, <= 2048", H);
     if (Re == 0) return WF3D_OK;
@@ -473,11 +472,10 @@ static int pair_fwd_impl(const float* Pa, const float* Pb, const float* cv, cons
                "wf3d_edge_pair_fwd: null pointer");
     const int ns = wf3d_cdiv(H, 256);
     hipStream_t st = (hipStream_t)stream;
-    const wf3d_seed_t seed = wf3d_seed_arg(drop_p, drop_seed);
 #define WF3D_PF(NS_)                                                                                                 \
     hipLaunchKernelGGL((pair_fwd_kernel<NS_>), dim3(wf3d_cdiv(Re, 4 * 8)), dim3(256), 0, st, Pa, Pb, cv, wdelta,           \
-                       wdelta_stride, voff, eoff, esample, Re, H, eps, pre, mu, rs, delta, gamma, beta, act, seed,         \
-                       thresh, dscale, (float*)h_sx8, vd, wf3d_live_rows())
+                       wdelta_stride, voff, eoff, esample, Re, H, eps, pre, mu, rs, delta, gamma, beta, act, drop.seed,    \
+                       drop.thresh, drop.scale, (float*)h_sx8, vd, wf3d_live_rows())
     if (ns <= 1) WF3D_PF(1); else if (ns <= 2) WF3D_PF(2); else if (ns <= 4) WF3D_PF(4); else WF3D_PF(8);
 #undef WF3D_PF
     WF3D_LAUNCH_CHECK();

@@ -656,9 +656,8 @@ extern "C" int wf3d_gemm(const wf3d_gemm_t* d, void* stream) {
     p.has_ln = d->pro_enable && d->pro_mu != nullptr;
     p.has_affine = d->pro_enable && d->pro_gamma != nullptr;
     if (d->pro_enable && d->drop_p > 0.f) {
-        p.drop_seed = wf3d_seed_arg(d->drop_p, d->drop_seed);
-        p.drop_thresh = (uint32_t)((double)d->drop_p * 4294967296.0);
-        p.drop_scale = 1.0f / (1.0f - d->drop_p);
+        const wf3d_drop_t drop = wf3d_drop_args(d->drop_p, d->drop_seed);
+        p.drop_seed = drop.seed; p.drop_thresh = drop.thresh; p.drop_scale = drop.scale;
     }
     p.accumulate = d->accumulate;
     p.vecA = ((uintptr_t)d->A % 16 == 0) && (d->lda % 4 == 0);

@@ -5,6 +5,8 @@
 // 4l + 256i ...), so every wave-instruction moves 1 KiB contiguous.
 #include "wf3d_common.h"
 
+#include <type_traits>
+
 namespace {
 
 __device__ __forceinline__ bool vec_ok(const void* p, int ld, int D) {
@@ -509,6 +511,86 @@ int colsum_nrb(int R) {
     return n > 2048 ? 2048 : (n < 1 ? 1 : n);
 }
 
+// ---- the one launch of the ln_act_bwd_kernel family ---------------------------------------------------------------
+// What one call of wf3d_ln_act_bwd / _first / _wsum / wf3d_edge_pair_ln_bwd asks for.  The entry point checks what only
+// it requires (its row count, its pointers, the layout of its sum buffers) and fills this in; ln_bwd_launch<KX, PAIR>
+// does the rest.
+struct LnBwdSum { size_t off; int cols; float* out; int tD, tK; };     // out = the workgroups' partials [off, off + cols) summed
+                                                                       // (tK > 0: stored transposed, colsum_finalize_kernel)
+struct LnBwdCall {
+    const char* who;                                   // the entry point, for its error messages
+    void* ws; size_t ws_bytes; void* stream;
+    const float* dh; const float* z; int R, D;
+    const float* mu; const float* rs; const float* gamma; const float* beta; int act;
+    float drop_p; uint32_t drop_seed;
+    float* dz; void* dz_sx8;
+    const float* x0; int ldx, kx;                      // KX > 0: the rows' kx <= KX weights of the extra column sums
+    PairSrc ps;                                        // PAIR: what z is rebuilt from
+    bool ptrs_ok;                                      // the entry point's own pointers are there (asked once R > 0 is known)
+    LnBwdSum sums[3];                                  // the column sums to finish; rows without `out` are skipped
+};
+
+// the workgroups' partials: [nblk][3 + KX][D] floats
+size_t ln_bwd_ws_bytes(int R, int D, int kx) { return R <= 0 || D <= 0 ? 0 : (size_t)bwd_nblk(R) * (3 + kx) * D * sizeof(float); }
+
+template <int N> using Int = std::integral_constant<int, N>;
+
+template <int KX, bool PAIR>
+int ln_bwd_launch(const LnBwdCall& c) {
+    // the first layer and the pair form serve widths of one float4 slot per lane only: no NS = 2 / 4 kernels for them
+    constexpr int MAXD = (KX > 1 || PAIR) ? 1024 : 4096;
+    const int R = c.R, D = c.D;
+    hipStream_t st = (hipStream_t)c.stream;
+    WF3D_CHECK(!c.dz_sx8 || (D % 8 == 0 && (uintptr_t)c.dz_sx8 % 16 == 0), WF3D_ERR_UNSUPPORTED,
+               "%s: the sx8 output needs D %% 8 == 0 and 16-byte alignment", c.who);
+    WF3D_CHECK(D % 4 == 0 && D <= MAXD, WF3D_ERR_UNSUPPORTED, "%s: D=%d must be a multiple of 4, <= %d", c.who, D, MAXD);
+    WF3D_CHECK(c.act >= 0 && c.act <= 2 && c.drop_p >= 0.f && c.drop_p < 1.f, WF3D_ERR_ARG, "%s: bad act/drop", c.who);
+    if (R == 0) {                                      // only wf3d_ln_act_bwd lets an empty input through: zero sums
+        for (const LnBwdSum& s : c.sums)
+            if (s.out) (void)hipMemsetAsync(s.out, 0, s.cols * sizeof(float), st);
+        return WF3D_OK;
+    }
+    WF3D_CHECK(c.ptrs_ok, WF3D_ERR_ARG, "%s: null pointer, or its column sums are not the one buffer it takes", c.who);
+    WF3D_CHECK(((uintptr_t)c.dh % 16 == 0) && ((uintptr_t)c.z % 16 == 0) && ((uintptr_t)c.dz % 16 == 0) &&
+               ((uintptr_t)c.gamma % 16 == 0) && ((uintptr_t)c.beta % 16 == 0), WF3D_ERR_ARG,
+               "%s: pointers must be 16-byte aligned", c.who);
+    const int nblk = bwd_nblk(R);
+    const size_t stride = (size_t)(3 + KX) * D;        // floats per workgroup partial, and in LDS
+    WF3D_CHECK(c.ws && c.ws_bytes >= ln_bwd_ws_bytes(R, D, KX), WF3D_ERR_WS, "%s: workspace too small", c.who);
+    float* part = (float*)c.ws;
+    const wf3d_drop_t drop = wf3d_drop_args(c.drop_p, c.drop_seed);
+    const int32_t* live = wf3d_live_rows();
+    auto launch = [&](auto ns, auto wpr) {
+        hipLaunchKernelGGL((ln_act_bwd_kernel<decltype(ns)::value, decltype(wpr)::value, KX, PAIR>), dim3(nblk), dim3(256),
+                           stride * sizeof(float), st, c.dh, c.z, R, D, c.mu, c.rs, c.gamma, c.beta, c.act, drop.seed,
+                           drop.thresh, drop.scale, c.dz, (float*)c.dz_sx8, part, c.x0, c.ldx, c.kx, c.ps, live);
+    };
+    // waves per row: keep <= 2 float4 slots per lane (NS) wherever possible
+    // (first layer, one wave per 512-wide row with two slots, <2, 1, 8>: 184 VGPRs, 187 us against 173)
+    const int wpr = D > 512 ? 4 : (D > 256 ? 2 : 1);
+    const int ns = wf3d_cdiv(slice_cols(D, wpr), 256);
+    if (wpr == 1) launch(Int<1>{}, Int<1>{});
+    else if (wpr == 2) launch(Int<1>{}, Int<2>{});
+    else if (MAXD <= 1024 || ns <= 1) launch(Int<1>{}, Int<4>{});
+    else if constexpr (MAXD > 1024) { if (ns <= 2) launch(Int<2>{}, Int<4>{}); else launch(Int<4>{}, Int<4>{}); }
+    WF3D_LAUNCH_CHECK();
+    for (const LnBwdSum& s : c.sums) {
+        if (!s.out) continue;
+        launch_finalize(part + s.off, nblk, stride, s.cols, s.out, st, s.tD, s.tK);
+        WF3D_LAUNCH_CHECK();
+    }
+    return WF3D_OK;
+}
+
+// lanes per row of the row-dot pair (D / 8, a power of two <= 64) as a compile-time constant: f(Int<lpr>{})
+template <typename F>
+void rowdot_width(int lpr, F&& f) {
+    switch (lpr) {
+        case 1: f(Int<1>{}); break;   case 2: f(Int<2>{}); break;   case 4: f(Int<4>{}); break;   case 8: f(Int<8>{}); break;
+        case 16: f(Int<16>{}); break; case 32: f(Int<32>{}); break; default: f(Int<64>{}); break;
+    }
+}
+
 }  // namespace
 
 extern "C" int wf3d_row_stats(const float* z, int R, int D, int ld, float eps, float* mu, float* rs, void* stream) {
@@ -529,119 +611,53 @@ extern "C" int wf3d_ln_act_apply(const float* z, int R, int D, const float* mu, 
     WF3D_CHECK(!mu || rs, WF3D_ERR_ARG, "wf3d_ln_act_apply: mu without rs");
     WF3D_CHECK(!gamma || beta, WF3D_ERR_ARG, "wf3d_ln_act_apply: gamma without beta");
     WF3D_CHECK(act >= 0 && act <= 2 && drop_p >= 0.f && drop_p < 1.f, WF3D_ERR_ARG, "wf3d_ln_act_apply: bad act/drop");
-    const uint32_t thresh = drop_p > 0.f ? (uint32_t)((double)drop_p * 4294967296.0) : 0u;
-    const float scale = 1.0f / (1.0f - drop_p);
+    const wf3d_drop_t drop = wf3d_drop_args(drop_p, drop_seed);
     const size_t total = (size_t)R * D;
     int blocks = (int)((total + 255) / 256);
     if (blocks > 4096) blocks = 4096;
     hipLaunchKernelGGL(ln_act_apply_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, z, R, D, mu, rs, gamma,
-                       beta, act, addend, wf3d_seed_arg(drop_p, drop_seed), thresh, scale, out);
+                       beta, act, addend, drop.seed, drop.thresh, drop.scale, out);
     WF3D_LAUNCH_CHECK();
     return WF3D_OK;
 }
 
-extern "C" size_t wf3d_ln_act_bwd_ws_bytes(int R, int D) {
-    if (R <= 0 || D <= 0) return 0;
-    return (size_t)bwd_nblk(R) * 3 * D * sizeof(float);
-}
+extern "C" size_t wf3d_ln_act_bwd_ws_bytes(int R, int D) { return ln_bwd_ws_bytes(R, D, 0); }
 
 extern "C" int wf3d_ln_act_bwd(const float* dh, const float* z, int R, int D, const float* mu, const float* rs,
                                const float* gamma, const float* beta, int act, float drop_p, uint32_t drop_seed,
                                float* dz, void* dz_sx8, float* dgamma, float* dbeta, float* dbias, void* ws,
                                size_t ws_bytes, void* stream) {
     WF3D_CHECK(R >= 0 && D > 0, WF3D_ERR_ARG, "wf3d_ln_act_bwd: bad dims");
-    WF3D_CHECK(!dz_sx8 || (D % 8 == 0 && (uintptr_t)dz_sx8 % 16 == 0), WF3D_ERR_UNSUPPORTED,
-               "wf3d_ln_act_bwd: the sx8 output needs D %% 8 == 0 and 16-byte alignment");
-    WF3D_CHECK(D % 4 == 0 && D <= 4096, WF3D_ERR_UNSUPPORTED, "wf3d_ln_act_bwd: D=%d must be a multiple of 4, <= 4096", D);
-    WF3D_CHECK(act >= 0 && act <= 2 && drop_p >= 0.f && drop_p < 1.f, WF3D_ERR_ARG, "wf3d_ln_act_bwd: bad act/drop");
     WF3D_CHECK(!mu || rs, WF3D_ERR_ARG, "wf3d_ln_act_bwd: mu without rs");
     WF3D_CHECK(!gamma || beta, WF3D_ERR_ARG, "wf3d_ln_act_bwd: gamma without beta");
-    hipStream_t st = (hipStream_t)stream;
-    if (R == 0) {
-        if (dgamma) (void)hipMemsetAsync(dgamma, 0, D * sizeof(float), st);
-        if (dbeta) (void)hipMemsetAsync(dbeta, 0, D * sizeof(float), st);
-        if (dbias) (void)hipMemsetAsync(dbias, 0, D * sizeof(float), st);
-        return WF3D_OK;
-    }
-    WF3D_CHECK(dh && z && (dz || dz_sx8), WF3D_ERR_ARG, "wf3d_ln_act_bwd: null pointer");
-    WF3D_CHECK(((uintptr_t)dh % 16 == 0) && ((uintptr_t)z % 16 == 0) && ((uintptr_t)dz % 16 == 0) &&
-               (!gamma || ((uintptr_t)gamma % 16 == 0 && (uintptr_t)beta % 16 == 0)),
-               WF3D_ERR_ARG, "wf3d_ln_act_bwd: pointers must be 16-byte aligned");
-    const int nblk = bwd_nblk(R);
-    WF3D_CHECK(ws && ws_bytes >= (size_t)nblk * 3 * D * sizeof(float), WF3D_ERR_WS, "wf3d_ln_act_bwd: workspace too small");
-    const uint32_t thresh = drop_p > 0.f ? (uint32_t)((double)drop_p * 4294967296.0) : 0u;
-    const float scale = 1.0f / (1.0f - drop_p);
-    float* part = (float*)ws;
-    const size_t lds = (size_t)3 * D * sizeof(float);
-    // waves per row: keep <= 2 float4 slots per lane (NS) wherever possible
-    const int wpr = D > 512 ? 4 : (D > 256 ? 2 : 1);
-    const int ns = wf3d_cdiv(slice_cols(D, wpr), 256);
-#define WF3D_BWD(NS_, WPR_)                                                                                       \
-    hipLaunchKernelGGL((ln_act_bwd_kernel<NS_, WPR_>), dim3(nblk), dim3(256), lds, st, dh, z, R, D, mu, rs, gamma, \
-                       beta, act, wf3d_seed_arg(drop_p, drop_seed), thresh, scale, dz, (float*)dz_sx8, part, nullptr, 0, 0, \
-                       PairSrc{}, wf3d_live_rows())
-    if (wpr == 4) { if (ns <= 1) WF3D_BWD(1, 4); else if (ns <= 2) WF3D_BWD(2, 4); else WF3D_BWD(4, 4); }
-    else if (wpr == 2) WF3D_BWD(1, 2);
-    else WF3D_BWD(1, 1);
-#undef WF3D_BWD
-    WF3D_LAUNCH_CHECK();
-    float* outs[3] = {dgamma, dbeta, dbias};
+    LnBwdCall c{"wf3d_ln_act_bwd", ws, ws_bytes, stream, dh, z, R, D, mu, rs, gamma, beta, act, drop_p, drop_seed, dz, dz_sx8};
+    c.ptrs_ok = dh && z && (dz || dz_sx8);
     if (dgamma && dbeta == dgamma + D && dbias == dbeta + D) {
-        // the three outputs are one contiguous [3][D] buffer: a single finalize pass
-        launch_finalize(part, nblk, (size_t)3 * D, 3 * D, dgamma, st);
-        WF3D_LAUNCH_CHECK();
-        return WF3D_OK;
+        c.sums[0] = {0, 3 * D, dgamma};       // the three outputs are one contiguous [3][D] buffer: a single finalize pass
+    } else {
+        float* outs[3] = {dgamma, dbeta, dbias};
+        for (int k = 0; k < 3; ++k) c.sums[k] = {(size_t)k * D, D, outs[k]};
     }
-    for (int k = 0; k < 3; ++k) {
-        if (!outs[k]) continue;
-        launch_finalize(part + (size_t)k * D, nblk, (size_t)3 * D, D, outs[k], st);
-        WF3D_LAUNCH_CHECK();
-    }
-    return WF3D_OK;
+    return ln_bwd_launch<0, false>(c);
 }
 
-extern "C" size_t wf3d_ln_act_bwd_first_ws_bytes(int R, int D) {
-    if (R <= 0 || D <= 0) return 0;
-    return (size_t)bwd_nblk(R) * (3 + 8) * D * sizeof(float);
-}
+extern "C" size_t wf3d_ln_act_bwd_first_ws_bytes(int R, int D) { return ln_bwd_ws_bytes(R, D, 8); }
 
 extern "C" int wf3d_ln_act_bwd_first(const float* dh, const float* z, const float* x, int R, int D, int K, int ldx,
                                      const float* mu, const float* rs, const float* gamma, const float* beta, int act,
                                      float* dgamma, float* dbeta, float* dbias, float* dW, void* ws, size_t ws_bytes,
                                      void* stream) {
     WF3D_CHECK(R > 0 && D > 0 && K > 0 && K <= 8 && ldx >= K, WF3D_ERR_UNSUPPORTED, "wf3d_ln_act_bwd_first: needs R > 0, 1 <= K <= 8");
-    WF3D_CHECK(D % 4 == 0 && D <= 1024, WF3D_ERR_UNSUPPORTED, "wf3d_ln_act_bwd_first: D=%d must be a multiple of 4, <= 1024", D);
-    WF3D_CHECK(act >= 0 && act <= 2, WF3D_ERR_ARG, "wf3d_ln_act_bwd_first: bad act");
-    WF3D_CHECK(dh && z && x && mu && rs && gamma && beta && dgamma && dbeta && dbias && dW, WF3D_ERR_ARG,
-               "wf3d_ln_act_bwd_first: null pointer");
-    WF3D_CHECK(dbeta == dgamma + D && dbias == dbeta + D, WF3D_ERR_ARG, "wf3d_ln_act_bwd_first: dgamma/dbeta/dbias must be one [3][D] buffer");
-    WF3D_CHECK(((uintptr_t)dh % 16 == 0) && ((uintptr_t)z % 16 == 0) && ((uintptr_t)gamma % 16 == 0) && ((uintptr_t)beta % 16 == 0),
-               WF3D_ERR_ARG, "wf3d_ln_act_bwd_first: pointers must be 16-byte aligned");
-    const int nblk = bwd_nblk(R);
-    WF3D_CHECK(ws && ws_bytes >= (size_t)nblk * 11 * D * sizeof(float), WF3D_ERR_WS, "wf3d_ln_act_bwd_first: workspace too small");
-    hipStream_t st = (hipStream_t)stream;
-    float* part = (float*)ws;
-    const size_t lds = (size_t)11 * D * sizeof(float);
-    const int wpr = D > 512 ? 4 : (D > 256 ? 2 : 1);
-#define WF3D_BWD1(WPR_)                                                                                                  \
-    hipLaunchKernelGGL((ln_act_bwd_kernel<1, WPR_, 8>), dim3(nblk), dim3(256), lds, st, dh, z, R, D, mu, rs, gamma, beta, \
-                       act, wf3d_seed_t{0u, nullptr}, 0u, 1.0f, (float*)nullptr, (float*)nullptr, part, x, ldx, K, \
-                       PairSrc{}, wf3d_live_rows())
-    // (one wave per 512-wide row with two slots, <2, 1, 8>: 184 VGPRs, 187 us against 173)
-    if (wpr == 4) WF3D_BWD1(4); else if (wpr == 2) WF3D_BWD1(2); else WF3D_BWD1(1);
-#undef WF3D_BWD1
-    WF3D_LAUNCH_CHECK();
-    launch_finalize(part, nblk, (size_t)11 * D, 3 * D, dgamma, st);
-    WF3D_LAUNCH_CHECK();
-    launch_finalize(part + 3 * D, nblk, (size_t)11 * D, D * K, dW, st, D, K);
-    WF3D_LAUNCH_CHECK();
-    return WF3D_OK;
+    // no dropout on this layer, and dz — which nothing else needs — is not written
+    LnBwdCall c{"wf3d_ln_act_bwd_first", ws, ws_bytes, stream, dh, z, R, D, mu, rs, gamma, beta, act, 0.f, 0u, nullptr, nullptr, x, ldx, K};
+    c.ptrs_ok = dh && z && x && mu && rs && gamma && beta && dgamma && dbeta && dbias && dW &&
+                dbeta == dgamma + D && dbias == dbeta + D;             // one [3][D] buffer
+    c.sums[0] = {0, 3 * D, dgamma};
+    c.sums[1] = {(size_t)3 * D, D * K, dW, D, K};      // [K][D] partials -> the weight's own [D][K]
+    return ln_bwd_launch<8, false>(c);
 }
 
-extern "C" size_t wf3d_ln_act_bwd_wsum_ws_bytes(int R, int D) {
-    if (R <= 0 || D <= 0) return 0;
-    return (size_t)bwd_nblk(R) * 4 * D * sizeof(float);
-}
+extern "C" size_t wf3d_ln_act_bwd_wsum_ws_bytes(int R, int D) { return ln_bwd_ws_bytes(R, D, 1); }
 
 // LayerNorm / activation backward that also returns one weighted column sum of the dz it produces:
 // wsum[c] = sum_r dz[r, c] * wrow[r]   (first edge layer: the gradient of the distance column of its weight,
@@ -650,36 +666,13 @@ extern "C" int wf3d_ln_act_bwd_wsum(const float* dh, const float* z, const float
                                     const float* rs, const float* gamma, const float* beta, int act, float drop_p,
                                     uint32_t drop_seed, float* dz, void* dz_sx8, float* dgamma, float* dbeta, float* wsum,
                                     void* ws, size_t ws_bytes, void* stream) {
-    WF3D_CHECK(R > 0 && D > 0 && D % 4 == 0 && D <= 4096, WF3D_ERR_UNSUPPORTED, "wf3d_ln_act_bwd_wsum: bad dims R=%d D=%d", R, D);
-    WF3D_CHECK(act >= 0 && act <= 2 && drop_p >= 0.f && drop_p < 1.f, WF3D_ERR_ARG, "wf3d_ln_act_bwd_wsum: bad act/drop");
-    WF3D_CHECK(dh && z && wrow && mu && rs && gamma && beta && (dz || dz_sx8) && dgamma && dbeta && wsum && dbeta == dgamma + D,
-               WF3D_ERR_ARG, "wf3d_ln_act_bwd_wsum: null pointer, or dgamma / dbeta not one [2][D] buffer");
-    WF3D_CHECK(!dz_sx8 || (D % 8 == 0 && (uintptr_t)dz_sx8 % 16 == 0), WF3D_ERR_UNSUPPORTED, "wf3d_ln_act_bwd_wsum: sx8 output needs D %% 8 == 0");
-    WF3D_CHECK(((uintptr_t)dh % 16 == 0) && ((uintptr_t)z % 16 == 0) && ((uintptr_t)dz % 16 == 0) && ((uintptr_t)gamma % 16 == 0) &&
-               ((uintptr_t)beta % 16 == 0), WF3D_ERR_ARG, "wf3d_ln_act_bwd_wsum: pointers must be 16-byte aligned");
-    const int nblk = bwd_nblk(R);
-    WF3D_CHECK(ws && ws_bytes >= (size_t)nblk * 4 * D * sizeof(float), WF3D_ERR_WS, "wf3d_ln_act_bwd_wsum: workspace too small");
-    const uint32_t thresh = drop_p > 0.f ? (uint32_t)((double)drop_p * 4294967296.0) : 0u;
-    const float scale = 1.0f / (1.0f - drop_p);
-    hipStream_t st = (hipStream_t)stream;
-    float* part = (float*)ws;
-    const size_t lds = (size_t)4 * D * sizeof(float);
-    const int wpr = D > 512 ? 4 : (D > 256 ? 2 : 1);
-    const int ns = wf3d_cdiv(slice_cols(D, wpr), 256);
-#define WF3D_BWDW(NS_, WPR_)                                                                                             \
-    hipLaunchKernelGGL((ln_act_bwd_kernel<NS_, WPR_, 1>), dim3(nblk), dim3(256), lds, st, dh, z, R, D, mu, rs, gamma, beta, \
-                       act, wf3d_seed_arg(drop_p, drop_seed), thresh, scale, dz, (float*)dz_sx8, part, wrow, 1, 1, \
-                       PairSrc{}, wf3d_live_rows())
-    if (wpr == 4) { if (ns <= 1) WF3D_BWDW(1, 4); else if (ns <= 2) WF3D_BWDW(2, 4); else WF3D_BWDW(4, 4); }
-    else if (wpr == 2) WF3D_BWDW(1, 2);
-    else WF3D_BWDW(1, 1);
-#undef WF3D_BWDW
-    WF3D_LAUNCH_CHECK();
-    launch_finalize(part, nblk, (size_t)4 * D, 2 * D, dgamma, st);
-    WF3D_LAUNCH_CHECK();
-    launch_finalize(part + 3 * D, nblk, (size_t)4 * D, D, wsum, st);
-    WF3D_LAUNCH_CHECK();
-    return WF3D_OK;
+    WF3D_CHECK(R > 0 && D > 0, WF3D_ERR_UNSUPPORTED, "wf3d_ln_act_bwd_wsum: bad dims R=%d D=%d", R, D);
+    LnBwdCall c{"wf3d_ln_act_bwd_wsum", ws, ws_bytes, stream, dh, z, R, D, mu, rs, gamma, beta, act, drop_p, drop_seed, dz, dz_sx8, wrow, 1, 1};
+    c.ptrs_ok = dh && z && wrow && mu && rs && gamma && beta && (dz || dz_sx8) && dgamma && dbeta && wsum &&
+                dbeta == dgamma + D;                                   // one [2][D] buffer
+    c.sums[0] = {0, 2 * D, dgamma};
+    c.sums[1] = {(size_t)3 * D, D, wsum};
+    return ln_bwd_launch<1, false>(c);
 }
 
 // The same pass for the first edge layer with its pre-activation rebuilt from the per-vertex tables (PairSrc above):
@@ -689,33 +682,15 @@ extern "C" int wf3d_edge_pair_ln_bwd(const float* dh, const float* Pa, const flo
                                      int H, const float* mu, const float* rs, const float* gamma, const float* beta, int act,
                                      float drop_p, uint32_t drop_seed, float* dz, float* dgamma, float* dbeta, float* wsum,
                                      void* ws, size_t ws_bytes, void* stream) {
-    WF3D_CHECK(Re > 0 && H > 0 && H % 4 == 0 && H <= 1024, WF3D_ERR_UNSUPPORTED, "wf3d_edge_pair_ln_bwd: bad dims Re=%d H=%d", Re, H);
-    WF3D_CHECK(act >= 0 && act <= 2 && drop_p >= 0.f && drop_p < 1.f, WF3D_ERR_ARG, "wf3d_edge_pair_ln_bwd: bad act/drop");
-    WF3D_CHECK(dh && Pa && Pb && delta && wdelta && voff && eoff && esample && mu && rs && gamma && beta && dz && dgamma && dbeta &&
-               wsum && dbeta == dgamma + H, WF3D_ERR_ARG, "wf3d_edge_pair_ln_bwd: null pointer, or dgamma / dbeta not one [2][H] buffer");
-    WF3D_CHECK(((uintptr_t)dh % 16 == 0) && ((uintptr_t)Pa % 16 == 0) && ((uintptr_t)Pb % 16 == 0) && ((uintptr_t)dz % 16 == 0) &&
-               ((uintptr_t)gamma % 16 == 0) && ((uintptr_t)beta % 16 == 0), WF3D_ERR_ARG, "wf3d_edge_pair_ln_bwd: pointers must be 16-byte aligned");
-    const int nblk = bwd_nblk(Re);
-    WF3D_CHECK(ws && ws_bytes >= (size_t)nblk * 4 * H * sizeof(float), WF3D_ERR_WS, "wf3d_edge_pair_ln_bwd: workspace too small");
-    const uint32_t thresh = drop_p > 0.f ? (uint32_t)((double)drop_p * 4294967296.0) : 0u;
-    const float scale = 1.0f / (1.0f - drop_p);
-    hipStream_t st = (hipStream_t)stream;
-    float* part = (float*)ws;
-    const size_t lds = (size_t)4 * H * sizeof(float);
-    const PairSrc ps{Pa, Pb, wdelta, wdelta_stride, voff, eoff, esample};
-    const int wpr = H > 512 ? 4 : (H > 256 ? 2 : 1);
-#define WF3D_BWDP(NS_, WPR_)                                                                                                \
-    hipLaunchKernelGGL((ln_act_bwd_kernel<NS_, WPR_, 1, true>), dim3(nblk), dim3(256), lds, st, dh, nullptr, Re, H, mu, rs, gamma, \
-                       beta, act, wf3d_seed_arg(drop_p, drop_seed), thresh, scale, dz, nullptr, part, delta, 1, 1, ps, \
-                       wf3d_live_rows())
-    if (wpr == 4) WF3D_BWDP(1, 4); else if (wpr == 2) WF3D_BWDP(1, 2); else WF3D_BWDP(1, 1);
-#undef WF3D_BWDP
-    WF3D_LAUNCH_CHECK();
-    launch_finalize(part, nblk, (size_t)4 * H, 2 * H, dgamma, st);
-    WF3D_LAUNCH_CHECK();
-    launch_finalize(part + 3 * H, nblk, (size_t)4 * H, H, wsum, st);
-    WF3D_LAUNCH_CHECK();
-    return WF3D_OK;
+    WF3D_CHECK(Re > 0 && H > 0, WF3D_ERR_UNSUPPORTED, "wf3d_edge_pair_ln_bwd: bad dims Re=%d H=%d", Re, H);
+    WF3D_CHECK(((uintptr_t)Pa % 16 == 0) && ((uintptr_t)Pb % 16 == 0), WF3D_ERR_ARG, "wf3d_edge_pair_ln_bwd: pointers must be 16-byte aligned");
+    LnBwdCall c{"wf3d_edge_pair_ln_bwd", ws, ws_bytes, stream, dh, nullptr, Re, H, mu, rs, gamma, beta, act, drop_p, drop_seed, dz, nullptr, delta, 1, 1};
+    c.ps = PairSrc{Pa, Pb, wdelta, wdelta_stride, voff, eoff, esample};
+    c.ptrs_ok = dh && Pa && Pb && delta && wdelta && voff && eoff && esample && mu && rs && gamma && beta && dz && dgamma &&
+                dbeta && wsum && dbeta == dgamma + H;                  // one [2][H] buffer
+    c.sums[0] = {0, 2 * H, dgamma};
+    c.sums[1] = {(size_t)3 * H, H, wsum};
+    return ln_bwd_launch<1, true>(c);
 }
 
 extern "C" size_t wf3d_edge_pair_ln_bwd_ws_bytes(int Re, int H) { return wf3d_ln_act_bwd_wsum_ws_bytes(Re, H); }
@@ -731,10 +706,10 @@ extern "C" int wf3d_rowdot_act(const float* z, int R, int D, const float* w, con
     hipStream_t st = (hipStream_t)stream;
     const int32_t* live = wf3d_live_rows();
     const int lpr = D / 8;
-#define WF3D_RD(L_) hipLaunchKernelGGL((rowdot_act_kernel<L_>), dim3(wf3d_cdiv(R, 4 * (64 / L_))), dim3(256), 0, st, z, R, D, w, bias, act, out, live)
-    switch (lpr) { case 1: WF3D_RD(1); break; case 2: WF3D_RD(2); break; case 4: WF3D_RD(4); break; case 8: WF3D_RD(8); break;
-                   case 16: WF3D_RD(16); break; case 32: WF3D_RD(32); break; default: WF3D_RD(64); break; }
-#undef WF3D_RD
+    rowdot_width(lpr, [&](auto L) {
+        hipLaunchKernelGGL((rowdot_act_kernel<decltype(L)::value>), dim3(wf3d_cdiv(R, 4 * (64 / decltype(L)::value))), dim3(256), 0, st,
+                           z, R, D, w, bias, act, out, live);
+    });
     WF3D_LAUNCH_CHECK();
     return WF3D_OK;
 }
@@ -756,10 +731,10 @@ extern "C" int wf3d_rowdot_act_bwd(const float* z, const float* dlogit, int R, i
     WF3D_CHECK(ws && ws_bytes >= (size_t)nblk * 2 * D * sizeof(float), WF3D_ERR_WS, "wf3d_rowdot_act_bwd: workspace too small");
     hipStream_t st = (hipStream_t)stream;
     float* part = (float*)ws;
-#define WF3D_RB(L_) hipLaunchKernelGGL((rowdot_act_bwd_kernel<L_>), dim3(nblk), dim3(256), 0, st, z, dlogit, R, D, w, act, dz, (float*)dz_sx8, part, wf3d_live_rows())
-    switch (lpr) { case 1: WF3D_RB(1); break; case 2: WF3D_RB(2); break; case 4: WF3D_RB(4); break; case 8: WF3D_RB(8); break;
-                   case 16: WF3D_RB(16); break; case 32: WF3D_RB(32); break; default: WF3D_RB(64); break; }
-#undef WF3D_RB
+    rowdot_width(lpr, [&](auto L) {
+        hipLaunchKernelGGL((rowdot_act_bwd_kernel<decltype(L)::value>), dim3(nblk), dim3(256), 0, st, z, dlogit, R, D, w, act, dz,
+                           (float*)dz_sx8, part, wf3d_live_rows());
+    });
     WF3D_LAUNCH_CHECK();
     launch_finalize(part, nblk, (size_t)2 * D, 2 * D, dw, st);
     WF3D_LAUNCH_CHECK();

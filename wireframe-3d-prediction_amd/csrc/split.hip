@@ -442,8 +442,7 @@ extern "C" int wf3d_split_rows_multi(const float* const* in, const long* row_str
 extern "C" int wf3d_ln_prep(const float* z, int R, int D, const float* gamma, const float* beta, int act, float eps,
                             float drop_p, uint32_t drop_seed, float* mu, float* rs, void* h_sx8, void* stream) {
     WF3D_CHECK(drop_p >= 0.f && drop_p < 1.f, WF3D_ERR_ARG, "wf3d_ln_prep: bad drop_p");
-    const uint32_t thresh = drop_p > 0.f ? (uint32_t)((double)drop_p * 4294967296.0) : 0u;
-    const float dscale = 1.0f / (1.0f - drop_p);
+    const wf3d_drop_t drop = wf3d_drop_args(drop_p, drop_seed);
     WF3D_CHECK(R >= 0 && D > 0, WF3D_ERR_ARG, "wf3d_ln_prep: bad dims");
     WF3D_CHECK(D % 8 == 0 && D <= 4096, WF3D_ERR_UNSUPPORTED, "wf3d_ln_prep: D=%d must be a multiple of 8, <= 4096", D);
     WF3D_CHECK(act >= 0 && act <= 2, WF3D_ERR_ARG, "wf3d_ln_prep: bad act");
@@ -453,7 +452,6 @@ extern "C" int wf3d_ln_prep(const float* z, int R, int D, const float* gamma, co
                ((uintptr_t)beta % 16 == 0), WF3D_ERR_ARG, "wf3d_ln_prep: pointers must be 16-byte aligned");
     const int ns = wf3d_cdiv(D, 512);
     hipStream_t st = (hipStream_t)stream;
-    const wf3d_seed_t seed = wf3d_seed_arg(drop_p, drop_seed);
     const int32_t* live = wf3d_live_rows();
     // persistent grid: a few workgroups per CU
     const int rpb = D <= 256 ? 8 : 4;
@@ -462,13 +460,13 @@ extern "C" int wf3d_ln_prep(const float* z, int R, int D, const float* gamma, co
 #define WF3D_LP(NS_)                                                                                              \
     if (D == NS_ * 512)                                                                                           \
         hipLaunchKernelGGL((ln_prep_kernel<NS_, 64, true>), dim3(blocks), dim3(256), 0, st, z, R, D, gamma, beta, act, eps, \
-                           seed, thresh, dscale, mu, rs, (float*)h_sx8, live);                                \
+                           drop.seed, drop.thresh, drop.scale, mu, rs, (float*)h_sx8, live);                                \
     else                                                                                                          \
         hipLaunchKernelGGL((ln_prep_kernel<NS_>), dim3(blocks), dim3(256), 0, st, z, R, D, gamma, beta, act, eps, \
-                           seed, thresh, dscale, mu, rs, (float*)h_sx8, live)
+                           drop.seed, drop.thresh, drop.scale, mu, rs, (float*)h_sx8, live)
     if (D <= 256)      // two rows per wave
         hipLaunchKernelGGL((ln_prep_kernel<1, 32>), dim3(blocks), dim3(256), 0, st, z, R, D, gamma, beta, act, eps,
-                           seed, thresh, dscale, mu, rs, (float*)h_sx8, live);
+                           drop.seed, drop.thresh, drop.scale, mu, rs, (float*)h_sx8, live);
     else if (ns <= 1) { WF3D_LP(1); } else if (ns <= 2) { WF3D_LP(2); } else if (ns <= 4) { WF3D_LP(4); } else { WF3D_LP(8); }
 #undef WF3D_LP
     WF3D_LAUNCH_CHECK();
@@ -508,8 +506,7 @@ extern "C" int wf3d_split_transpose(const float* in, int R, int C, int ld, const
                                     const float* gamma, const float* beta, int act, float drop_p, uint32_t drop_seed,
                                     int in_sx8, void* out_sx8, void* stream) {
     WF3D_CHECK(drop_p >= 0.f && drop_p < 1.f && (!in_sx8 || drop_p == 0.f), WF3D_ERR_ARG, "wf3d_split_transpose: bad drop_p");
-    const uint32_t thresh = drop_p > 0.f ? (uint32_t)((double)drop_p * 4294967296.0) : 0u;
-    const float dscale = 1.0f / (1.0f - drop_p);
+    const wf3d_drop_t drop = wf3d_drop_args(drop_p, drop_seed);
     WF3D_CHECK(R > 0 && C > 0 && ld >= C, WF3D_ERR_ARG, "wf3d_split_transpose: bad dims");
     WF3D_CHECK(!in_sx8 || (C % 8 == 0 && ld % 8 == 0 && !mu && !gamma && act == 0), WF3D_ERR_UNSUPPORTED,
                "wf3d_split_transpose: an sx8 input needs C %% 8 == 0 and takes no prologue");
@@ -523,7 +520,7 @@ extern "C" int wf3d_split_transpose(const float* in, int R, int C, int ld, const
     WF3D_CHECK(act >= 0 && act <= 2, WF3D_ERR_ARG, "wf3d_split_transpose: bad act");
     WF3D_CHECK(wf3d_cdiv(R, 64) <= 65535, WF3D_ERR_UNSUPPORTED, "wf3d_split_transpose: too many rows");
     hipLaunchKernelGGL(split_transpose_kernel, dim3(wf3d_cdiv(C, 64), wf3d_cdiv(R, 64)), dim3(256), 0,
-                       (hipStream_t)stream, in, R, C, ld, mu, rs, gamma, beta, act, wf3d_seed_arg(drop_p, drop_seed), thresh, dscale, in_sx8,
+                       (hipStream_t)stream, in, R, C, ld, mu, rs, gamma, beta, act, drop.seed, drop.thresh, drop.scale, in_sx8,
                        (float*)out_sx8, wf3d_live_rows());
     WF3D_LAUNCH_CHECK();
     return WF3D_OK;

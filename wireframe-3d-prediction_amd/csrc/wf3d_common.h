@@ -43,6 +43,13 @@ static inline int wf3d_cdiv(long a, long b) { return (int)((a + b - 1) / b); }
 struct wf3d_seed_t { uint32_t v; const uint32_t* words; };
 // the seed argument of a launch that drops with probability drop_p (no words are read when nothing is dropped)
 WF3D_INTERNAL wf3d_seed_t wf3d_seed_arg(float drop_p, uint32_t drop_seed);
+// The three dropout arguments of a mask launch: the seed source, the 32-bit threshold an element's hash must reach to be
+// kept (0: nothing is dropped, and no kernel then reads the other two) and the keep scale 1 / (1 - drop_p).
+struct wf3d_drop_t { wf3d_seed_t seed; uint32_t thresh; float scale; };
+static inline wf3d_drop_t wf3d_drop_args(float drop_p, uint32_t drop_seed) {
+    return {wf3d_seed_arg(drop_p, drop_seed), drop_p > 0.f ? (uint32_t)((double)drop_p * 4294967296.0) : 0u,
+            1.0f / (1.0f - drop_p)};
+}
 
 // ---- live-row count (host + device) -------------------------------------------
 // While the calling thread has set one (wf3d_set_live_rows), the entry points that include/wf3d.h lists under "LIVE ROW
