@@ -645,9 +645,21 @@ int wf3d_cloud_sample(const double* norm, const long* first, const int* cloud, c
  *   their wireframe, vfirst / efirst [nclouds + 1] row offsets.  Writes every element of vertices [B, V, 3] (c_s vertices,
  *   augmented like the points, then zeros), vertex_existence [B, V], vertex_counts [B] = c_s and edge_labels
  *   [B, V(V-1)/2]: 1.0 at pair (i, j)'s position among the pairs of c_s vertices for every edge with 0 <= i < j < c_s,
- *   0.0 elsewhere.  The host refuses c_s > V before the launch; the kernel would treat such a sample as c_s = V. */
+ *   0.0 elsewhere.  The host refuses c_s > V before the launch; the kernel would treat such a sample as c_s = V.
+ * wf3d_cloud_sample_dev: the FIXED-SIZE batch of the same block, sampled in the kernel: points [B, P, C] fp32 with
+ *   points[b, p, :] = fp32(augment(norm[first[cloud[b]] + idx(b, p), :])), the flips and the z-rotation of
+ *   wf3d_cloud_sample (float64, one rounding), and idx(b, .) = wf3d.sampling.choice_indices(seed_words[0], b, n_b, P),
+ *   n_b the rows of cloud[b]: P distinct rows when n_b >= P (a keyed Feistel permutation, cycle-walked), P independent
+ *   uniform rows when n_b < P — np.random.choice(n_b, P, replace=n_b < P) in distribution, another random stream.
+ *   seed_words: DEVICE memory, 4-byte aligned; word 0 is read by the kernel at run time (wf3d_dropout_draw on a generator
+ *   state of the caller's own writes it), so a captured launch samples afresh on every replay.  out_first is ignored (the
+ *   host writes out_first[b] = b * P).  Every element of points is written, by plain stores of this one launch; a sample
+ *   whose cloud index is outside 0 .. nclouds-1 or whose cloud is empty is written as zeros.  1 <= P, B * P < 2^31;
+ *   C = 8 moves 16 bytes per access (norm and points 16-byte aligned), other C take a row per lane. */
 int wf3d_cloud_pack(const double* norm, const long* first, int nclouds, const void* params, int B, int capacity, int C,
                     float* points, int64_t* point_counts, void* stream);
+int wf3d_cloud_sample_dev(const double* norm, const long* first, int nclouds, const void* params, const uint32_t* seed_words,
+                          int B, int P, int C, float* points, void* stream);
 int wf3d_wireframe_targets(const double* wf_vertices, const int32_t* wf_edges, const long* vfirst, const long* efirst, int nclouds,
                            const void* params, int B, int V, float* vertices, float* vertex_existence, int64_t* vertex_counts,
                            float* edge_labels, void* stream);

@@ -17,6 +17,17 @@ B = 32 the two launches move 0.5 and 5 MB: --batch-sizes 1024 shows the point la
 
     python scripts/bench_resident_batches.py [--blocks 5] [--block-steps 7] [--warmup 2] [--out profiles/r06_resident_batches.jsonl]
 
+--form fixed: FIXED-SIZE batches [B, --num-points, C] of the same clouds ("One capture for fixed-size
+batches").  Arm "batch": `cache.batch(idxs)` — per sample an np.random.choice draw and the augmentation draws, three
+uploads, one gather launch.  Arm "sampled": `cache.stage` + one replay of a graph captured around `cache.fill` on
+`sampled_buffers` (seed draw, sampler, targets) — the augmentation draws and one 40 B + 4 byte copy.  Host wall time per
+batch as above, both ended by a synchronize; then the device time of each form's launches between events (--reps
+back-to-back launches per reading): the gather kernel on a resident choice table, the sampler kernel, the replayed graph.
+GB/s of the two point kernels over B * P * (64 + 32) bytes.  Note that "batch" also builds the host dict fields of
+collate_batch (wireframe lists), which "sampled" replaces by device targets: the arms are the two ways to feed a step.
+
+    python scripts/bench_resident_batches.py --form fixed --batch-sizes 32 --num-points 4096 --out profiles/r10_sampled_batches.jsonl
+
 Prints one JSON line per batch size and appends them to --out.
 """
 import argparse
@@ -141,19 +152,84 @@ def run(B, ds, cache, dev, args):
             "fill_GB/s": round(nbytes / fill_ms / 1e6, 1), "row_passes": rows_figure()}
 
 
+def run_fixed(B, ds, cache, dev, args):
+    from wf3d import _lib
+    from wf3d.ops import _stream
+    P = args.num_points
+    ds.num_points = P
+    idxs = [i % len(ds) for i in range(B)]
+    buf = cache.sampled_buffers(B, V, P)
+    np.random.seed(0)
+    cache.stage(buf, idxs)
+    cache.fill(buf)
+    torch.cuda.synchronize()
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph):
+        cache.fill(buf)
+
+    def batch():
+        t0 = time.perf_counter()
+        cache.batch(idxs)
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) * 1e3
+
+    def sampled():
+        t0 = time.perf_counter()
+        cache.stage(buf, idxs)
+        graph.replay()
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) * 1e3
+
+    med = blocks_of({"batch": batch, "sampled": sampled}, args.blocks, args.block_steps, args.warmup)
+    lib = _lib.load()
+    ids = torch.tensor(idxs, dtype=torch.int32, device=dev)
+    choice = torch.from_numpy(np.stack([np.random.choice(cache.n[i], P, replace=cache.n[i] < P) for i in idxs]).astype(np.int32)).to(dev)
+    aug = torch.from_numpy(cache._block_views(buf["params_host"], B)[0].copy()).to(dev)
+    out = torch.empty_like(buf["points"])
+    ev = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+
+    def timed(launch):
+        def fn():
+            ev[0].record()
+            for _ in range(args.reps):
+                launch()
+            ev[1].record()
+            torch.cuda.synchronize()
+            return ev[0].elapsed_time(ev[1]) * 1e3 / args.reps
+        return fn
+
+    dmed = blocks_of({"gather": timed(lambda: _lib.check(lib.wf3d_cloud_sample(
+                          cache.norm.data_ptr(), cache.first.data_ptr(), ids.data_ptr(), choice.data_ptr(), aug.data_ptr(), B, P,
+                          cache.ncol, out.data_ptr(), _stream()), "cloud_sample")),
+                      "sampler": timed(lambda: cache._sample(buf["params"], buf["sample_words"], out)),
+                      "graph": timed(graph.replay)}, args.blocks, args.block_steps, args.warmup)
+    nbytes = B * P * cache.ncol * 12
+    b, r = summary(med["batch"]), summary(med["sampled"])
+    dev_us = {k: summary(v, 2) for k, v in dmed.items()}
+    return {"bench": "sampled_batches", "B": B, "num_points": P, "columns": cache.ncol, "max_vertices": V,
+            "cloud_rows": sorted(set(cache.n[i] for i in idxs)), "blocks": args.blocks, "steps_per_block": args.block_steps,
+            "reps": args.reps, "batch_ms": b, "sampled_ms": r, "batch_over_sampled": round(b["median"] / r["median"], 2),
+            "h2d_bytes_batch": B * P * 4 + 36 * B, "h2d_bytes_sampled": 40 * B + 4, "device_us": dev_us, "point_bytes": nbytes,
+            "gather_GB/s": round(nbytes / dev_us["gather"]["median"] / 1e3, 1),
+            "sampler_GB/s": round(nbytes / dev_us["sampler"]["median"] / 1e3, 1)}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--blocks", type=int, default=5)
     ap.add_argument("--block-steps", type=int, default=7)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--batch-sizes", default="3,32")
+    ap.add_argument("--form", choices=("packed", "fixed"), default="packed")
+    ap.add_argument("--num-points", type=int, default=4096)
+    ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "r06_resident_batches.jsonl"))
     args = ap.parse_args()
     dev = torch.device("cuda:0")
     ds = fixture_dataset()
     cache = DeviceCloudCache(ds, dev)
     for B in (int(b) for b in args.batch_sizes.split(",")):
-        r = run(B, ds, cache, dev, args)
+        r = (run_fixed if args.form == "fixed" else run)(B, ds, cache, dev, args)
         print(json.dumps(r), flush=True)
         if args.out:
             with open(args.out, "a") as f:

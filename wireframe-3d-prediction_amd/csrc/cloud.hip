@@ -17,6 +17,9 @@
 //                            one workgroup per sample.
 //                            Both read one parameter block in device memory (include/wf3d.h), so a captured graph that
 //                            holds the two launches serves every batch.
+//   cloud_sample_dev kernels per fixed-size batch: cloud_sample_kernel's output with the random choice computed in the
+//                            kernel (wf3d/sampling.py) from a seed word in device memory and the same parameter block:
+//                            no per-point host data, capturable.
 // Plus the host-side text parser for .xyz files (np.loadtxt replacement): wf3d_parse_floats.
 #include <locale.h>
 #include <stdio.h>
@@ -182,6 +185,119 @@ __global__ __launch_bounds__(256) void cloud_pack_kernel(const double* __restric
     for (int k = 2; k < C; ++k) o[k] = (float)row[k];
 }
 
+// ---- fixed-size batches sampled on the device -------------------------------------------------------------------------
+// wf3d/sampling.py choice_indices(seed_word, b, n, P)[p], the specification, in uint32 arithmetic: a keyed 6-round
+// balanced Feistel permutation of 2h bits cycle-walked into [0, n) between two keyed offsets when n >= P (distinct
+// rows), a hash scaled by multiply-high when n < P (independent rows).  O(1) state per sample, no scratch, no sort.
+__device__ __forceinline__ uint32_t fmix32(uint32_t x) {
+    x ^= x >> 16; x *= 0x85EBCA6Bu; x ^= x >> 13; x *= 0xC2B2AE35u; x ^= x >> 16;
+    return x;
+}
+
+// what is the same for every row of sample b: block-uniform, so the compiler keeps it in scalar registers
+struct SamplePlan { long r0; uint32_t n, key, key2, a, c, mask; int h; bool replace; };
+
+// false: the sample has no source (cloud index outside the resident clouds, an empty cloud) and is written as zeros
+__device__ __forceinline__ bool sample_plan(const BatchParams& Q, const long* __restrict__ first, int nclouds,
+                                            const uint32_t* __restrict__ seed_words, int b, int P, SamplePlan& s) {
+    const int cl = Q.cloud[b];
+    if (cl < 0 || cl >= nclouds) return false;
+    s.r0 = first[cl];
+    const long n = first[cl + 1] - s.r0;
+    if (n < 1 || n > 0x7FFFFFFFL) return false;
+    s.n = (uint32_t)n;
+    s.key = fmix32(fmix32(seed_words[0] + 0x9E3779B9u) ^ ((uint32_t)(b + 1) * 0x85EBCA6Bu));
+    s.key2 = fmix32(s.key ^ 0x68E31DA4u);
+    s.a = __umulhi(fmix32(s.key ^ 0xB5297A4Du), s.n);
+    s.c = __umulhi(fmix32(s.key ^ 0x1B56C4E9u), s.n);
+    s.h = (32 - __clz((int)(s.n - 1)) + 1) >> 1;                 // n = 1: h = 0, the permutation of one value
+    s.mask = (1u << s.h) - 1u;
+    s.replace = n < P;
+    return true;
+}
+
+__device__ __forceinline__ uint32_t sample_index(const SamplePlan& s, uint32_t p) {
+    if (s.replace) return __umulhi(fmix32(fmix32(p ^ s.key) + s.key2), s.n);
+    uint32_t x = p + s.a;                                        // p < P <= n and a < n < 2^31: no wrap
+    x = x >= s.n ? x - s.n : x;
+    // The cycle walk: pi permutes [0, 4^h) and x starts below n, so the walk returns below n after at most
+    // 4^h - n + 1 applications (4^h < 4n: fewer than 4 expected).  The only divergent loop of the kernel.
+    do {
+        uint32_t l = x >> s.h, r = x & s.mask;
+#pragma unroll
+        for (uint32_t k = 0; k < 6; ++k) {
+            const uint32_t t = l ^ (fmix32(r * 0x9E3779B1u + s.key + k * 0x7F4A7C15u) & s.mask);
+            l = r;
+            r = t;
+        }
+        x = (l << s.h) | r;
+    } while (x >= s.n);
+    x += s.c;
+    return x >= s.n ? x - s.n : x;
+}
+
+// C = 8, cloud_pack8_kernel's layout: two lanes per row, 16-byte accesses, consecutive lanes store consecutive 16 bytes.
+// A wave owns 64 output rows: lane l computes the index of row l ONCE, and the two passes of 32 rows fetch theirs with
+// one ds_bpermute each (from lane j * 32 + l / 2) — against computing every index in both lanes of its pair, this
+// halves the Feistel rounds per row (6 x 11 VALU operations per application, times the longest walk of the wave) for
+// two cross-lane reads per 64 rows.  The shuffles come before any store guard, with the whole wave active.
+__global__ __launch_bounds__(256) void cloud_sample_dev8_kernel(const double* __restrict__ norm, const long* __restrict__ first,
+                                                                 int nclouds, const void* __restrict__ params,
+                                                                 const uint32_t* __restrict__ seed_words, int B, int P,
+                                                                 float* __restrict__ out) {
+    const BatchParams Q = batch_params(params, B);
+    const int b = blockIdx.y, lane = threadIdx.x & 63;
+    const long wave_row = (long)blockIdx.x * 256 + (threadIdx.x & ~63);
+    SamplePlan s;
+    const bool live = sample_plan(Q, first, nclouds, seed_words, b, P, s);
+    uint32_t idx = 0;
+    if (live && wave_row + lane < P) idx = sample_index(s, (uint32_t)(wave_row + lane));
+    const uint32_t idx0 = __shfl(idx, lane >> 1, 64), idx1 = __shfl(idx, 32 + (lane >> 1), 64);
+    const int half = lane & 1;
+    double fx = 1, fy = 1, c = 1, sn = 0;
+    if (live) { fx = Q.aug[b * 4]; fy = Q.aug[b * 4 + 1]; c = Q.aug[b * 4 + 2]; sn = Q.aug[b * 4 + 3]; }
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+        const long p = wave_row + j * 32 + (lane >> 1);
+        if (p >= P) continue;
+        f32x4 o = {0.f, 0.f, 0.f, 0.f};
+        if (live) {
+            const f64x2* row = reinterpret_cast<const f64x2*>(norm + (s.r0 + (j ? idx1 : idx0)) * 8) + half * 2;
+            const f64x2 u = row[0], v = row[1];
+            if (half == 0) {
+                const double x = fx * u[0], y = fy * u[1];
+                o = f32x4{(float)(x * c - y * sn), (float)(x * sn + y * c), (float)v[0], (float)v[1]};
+            } else {
+                o = f32x4{(float)u[0], (float)u[1], (float)v[0], (float)v[1]};
+            }
+        }
+        *reinterpret_cast<f32x4*>(out + ((long)b * P + p) * 8 + half * 4) = o;
+    }
+}
+
+// any C (3 and 7 in this project): one lane per row
+__global__ __launch_bounds__(256) void cloud_sample_dev_kernel(const double* __restrict__ norm, const long* __restrict__ first,
+                                                                int nclouds, const void* __restrict__ params,
+                                                                const uint32_t* __restrict__ seed_words, int B, int P, int C,
+                                                                float* __restrict__ out) {
+    const BatchParams Q = batch_params(params, B);
+    const int b = blockIdx.y;
+    const long p = (long)blockIdx.x * 256 + threadIdx.x;
+    if (p >= P) return;
+    float* o = out + ((long)b * P + p) * C;
+    SamplePlan s;
+    if (!sample_plan(Q, first, nclouds, seed_words, b, P, s)) {
+        for (int k = 0; k < C; ++k) o[k] = 0.f;
+        return;
+    }
+    const double* row = norm + (s.r0 + sample_index(s, (uint32_t)p)) * C;
+    const double fx = Q.aug[b * 4], fy = Q.aug[b * 4 + 1], c = Q.aug[b * 4 + 2], sn = Q.aug[b * 4 + 3];
+    const double x = fx * row[0], y = fy * row[1];
+    o[0] = (float)(x * c - y * sn);
+    o[1] = (float)(x * sn + y * c);
+    for (int k = 2; k < C; ++k) o[k] = (float)row[k];
+}
+
 // wf3d/targets.py train_targets(..., full_width=True) for sample b = blockIdx.x: c_s vertices augmented like the points,
 // zeros after; existence; the count; labels of all pairs of V vertices: the row is zeroed, then (after a barrier) every
 // edge min < max < c_s stores 1.0 at its pair's position among the pairs of c_s vertices.
@@ -260,6 +376,26 @@ extern "C" int wf3d_cloud_pack(const double* norm, const long* first, int ncloud
     } else {
         hipLaunchKernelGGL(cloud_pack_kernel, dim3(wf3d_cdiv(capacity > B ? capacity : B, 256)), dim3(256), 0, (hipStream_t)stream,
                            norm, first, nclouds, params, B, capacity, C, points, point_counts);
+    }
+    WF3D_LAUNCH_CHECK();
+    return WF3D_OK;
+}
+
+extern "C" int wf3d_cloud_sample_dev(const double* norm, const long* first, int nclouds, const void* params,
+                                     const uint32_t* seed_words, int B, int P, int C, float* points, void* stream) {
+    WF3D_CHECK(nclouds >= 1 && B >= 1 && B <= 4096 && P >= 1 && C >= 3 && C <= 16, WF3D_ERR_ARG, "wf3d_cloud_sample_dev: bad dims");
+    WF3D_CHECK((long)B * P <= 0x7FFFFFFFL, WF3D_ERR_ARG, "wf3d_cloud_sample_dev: B * P must stay below 2^31");
+    WF3D_CHECK(norm && first && params && seed_words && points, WF3D_ERR_ARG, "wf3d_cloud_sample_dev: null pointer");
+    WF3D_CHECK(((uintptr_t)params & 7) == 0 && ((uintptr_t)seed_words & 3) == 0, WF3D_ERR_ARG,
+               "wf3d_cloud_sample_dev: params must be 8-byte aligned, seed_words 4-byte aligned");
+    const dim3 grid(wf3d_cdiv(P, 256), B);
+    if (C == 8) {
+        WF3D_CHECK((((uintptr_t)norm | (uintptr_t)points) & 15) == 0, WF3D_ERR_ARG, "wf3d_cloud_sample_dev: norm and points must be 16-byte aligned");
+        hipLaunchKernelGGL(cloud_sample_dev8_kernel, grid, dim3(256), 0, (hipStream_t)stream, norm, first, nclouds, params,
+                           seed_words, B, P, points);
+    } else {
+        hipLaunchKernelGGL(cloud_sample_dev_kernel, grid, dim3(256), 0, (hipStream_t)stream, norm, first, nclouds, params,
+                           seed_words, B, P, C, points);
     }
     WF3D_LAUNCH_CHECK();
     return WF3D_OK;

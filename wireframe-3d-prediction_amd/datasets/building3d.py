@@ -14,7 +14,12 @@ writes the model's `[B, num_points, C]` fp32 input directly — no per-sample fi
 The packed form (whole clouds, `forward_packed`): `cache.packed_batch(indices)` is `collate_packed` of the same data set
 with `num_points = 0`; `cache.packed_buffers` / `stage` / `fill` feed the static buffers of a captured step — `stage`
 draws the augmentation and copies one 40·B + 4 byte parameter block, `fill` is two launches (points + point counts,
-training targets) that read everything else from resident device memory.  `packed_plan` is the host part on its own."""
+training targets) that read everything else from resident device memory.  `packed_plan` is the host part on its own.
+
+The fixed-size form without per-point host data: `cache.sampled_buffers` / `stage` / `fill` do the same for
+`[B, num_points, C]` batches whose rows are chosen IN the kernel (wf3d/sampling.py states the index function) under a seed
+word that `fill` draws on the device, so one captured step trains as the reference trains — random fixed-size subsets,
+flips, z-rotation; `cache.batch(indices, sampler="device")` is the same sampler for one batch."""
 import ctypes
 import glob
 import operator
@@ -221,7 +226,7 @@ class Building3DReconstructionDataset(Dataset):
 PARAM_BYTES = 40       # per sample in the parameter block of a packed batch: aug 4 doubles, cloud int32, out_first int32
 
 
-def packed_plan(n, vertex_counts, indices, draw=None, capacity=None, max_vertices=None, who="packed_plan"):
+def packed_plan(n, vertex_counts, indices, draw=None, capacity=None, max_vertices=None, who="packed_plan", num_points=None):
     """The host part of a packed batch from resident clouds; needs no GPU.  `n` / `vertex_counts`: rows and wireframe
     vertices per resident cloud; `indices`: the batch (negative indices count from the end, as for a list); `draw`: the
     data set's `_draw_augmentation` when it augments, else None.  Returns (indices, out_first, aug): the normalised
@@ -229,18 +234,27 @@ def packed_plan(n, vertex_counts, indices, draw=None, capacity=None, max_vertice
     sin t} — the parameter block of include/wf3d.h.  np.random is consumed as `[ds0[i] for i in indices]` consumes it
     (ds0 = the data set with num_points = 0): per sample flip-x, flip-y, angle, and nothing without `draw`.  Every check
     comes before the first draw: IndexError for an index out of range, ValueError for an empty batch, for more than
-    `capacity` rows and for a wireframe of more than `max_vertices` vertices."""
+    `capacity` rows and for a wireframe of more than `max_vertices` vertices.
+    `num_points` = P: the plan of a FIXED-SIZE batch sampled on the device (wf3d_cloud_sample_dev) — out_first[b] = b * P,
+    no row capacity (a cloud of any length fits; ValueError only for B * P >= 2^31), the same checks otherwise and the
+    same draws in the same order."""
     indices = [operator.index(i) for i in indices]
     indices = [i + len(n) if i < 0 else i for i in indices]
     if any(not 0 <= i < len(n) for i in indices):
         raise IndexError(f"DeviceCloudCache.{who}: index out of range for {len(n)} clouds")
     if not indices:
         raise ValueError(f"DeviceCloudCache.{who}: an empty batch")
-    out_first = np.zeros(len(indices) + 1, dtype=np.int64)
-    np.cumsum([n[i] for i in indices], out=out_first[1:])
-    rows = int(out_first[-1])
-    if rows > (0x7FFFFFFF if capacity is None else capacity):
-        raise ValueError(f"DeviceCloudCache.{who}: the clouds hold {rows} points, above the capacity of {capacity} rows")
+    if num_points is None:
+        out_first = np.zeros(len(indices) + 1, dtype=np.int64)
+        np.cumsum([n[i] for i in indices], out=out_first[1:])
+        rows = int(out_first[-1])
+        if rows > (0x7FFFFFFF if capacity is None else capacity):
+            raise ValueError(f"DeviceCloudCache.{who}: the clouds hold {rows} points, above the capacity of {capacity} rows")
+    else:
+        P = operator.index(num_points)
+        if P < 1 or len(indices) * P > 0x7FFFFFFF:
+            raise ValueError(f"DeviceCloudCache.{who}: needs num_points >= 1 and B * num_points < 2^31 (got {len(indices)} x {P})")
+        out_first = np.arange(len(indices) + 1, dtype=np.int64) * P
     most = max(vertex_counts[i] for i in indices)
     if max_vertices is not None and most > max_vertices:
         raise ValueError(f"a wireframe has {most} vertices, more than max_vertices = {max_vertices}")
@@ -264,6 +278,11 @@ class DeviceCloudCache:
         buf = cache.packed_buffers(B, capacity, max_vertices)      # static buffers of a captured step
         info = cache.stage(buf, [3, 0, 7])             # host: checks, np.random draws, one small non-blocking copy
         cache.fill(buf)                                # two launches; inside the capture, or before graph.replay()
+
+    Fixed-size batches sampled on the device (another random stream than np.random.choice, the same distribution):
+
+        batch = cache.batch([3, 0, 7], sampler="device")
+        buf = cache.sampled_buffers(B, max_vertices)   # points [B, num_points, C]; stage / fill as above, three launches
     """
 
     def __init__(self, dataset, device):
@@ -296,6 +315,11 @@ class DeviceCloudCache:
         self.wf_vertices = torch.from_numpy(np.ascontiguousarray(np.concatenate(verts, axis=0).reshape(-1, 3))).to(device)
         self.wf_edges = torch.from_numpy(np.ascontiguousarray(np.concatenate(edges, axis=0))).to(device)
         self.vfirst, self.efirst = torch.from_numpy(vfirst).to(device), torch.from_numpy(efirst).to(device)
+        # the seed stream of the device sampler: a generator of the cache's own (never the dropout stream), keyed from
+        # torch's CPU generator (two draws from it, here) and created now, so that it exists before any capture
+        from wf3d.random import DropoutGenerator
+        self.sample_generator = DropoutGenerator(device)
+        self.last_sample_words = None
 
     def _normalised_vertices(self, idx):
         """(float64 copy of cloud idx's wireframe vertices, centred and scaled when the data set normalises; centroid; max_distance)"""
@@ -319,9 +343,17 @@ class DeviceCloudCache:
         del it["point_clouds"]
         return it
 
-    def batch(self, indices):
+    def batch(self, indices, sampler="numpy"):
+        """collate_batch([dataset[i] for i in indices]) with `point_clouds` [B, num_points, C] on the device.
+        sampler="numpy": the rows are np.random.choice draws in the reference's order, so a seeded run reproduces the
+        reference's batches.  sampler="device": the rows are chosen in the kernel (wf3d_cloud_sample_dev,
+        wf3d.sampling.choice_indices) under a seed word drawn from `sample_generator` and kept as `last_sample_words`
+        (int32 [5] on the device, word 0) — the same distribution, another random stream; np.random then sees the
+        augmentation draws only (per sample flip-x, flip-y, angle), NO choice draws.  Every other key is the same."""
         from wf3d import _lib
         from wf3d.ops import _stream
+        if sampler not in ("numpy", "device"):
+            raise ValueError(f"DeviceCloudCache.batch: sampler must be 'numpy' or 'device' (got {sampler!r})")
         if not self.ds.num_points:
             raise ValueError("DeviceCloudCache needs dataset.num_points (fixed-size batches)")
         ds, P = self.ds, self.ds.num_points
@@ -332,6 +364,8 @@ class DeviceCloudCache:
         if any(not 0 <= i < len(self.n) for i in indices):
             raise IndexError(f"DeviceCloudCache.batch: index out of range for {len(self.n)} clouds")
         B = len(indices)
+        if sampler == "device":
+            return self._batch_sampled(indices, P)
         choice = np.empty((B, P), dtype=np.int32)
         aug = np.empty((B, 4), dtype=np.float64)
         items = []
@@ -352,10 +386,38 @@ class DeviceCloudCache:
         out["point_clouds"] = pcs
         return out
 
+    def _batch_sampled(self, indices, P):
+        """batch(..., sampler="device") behind its index checks"""
+        ds, B = self.ds, len(indices)
+        if not 1 <= B <= 4096 or B * P > 0x7FFFFFFF:
+            raise ValueError(f"DeviceCloudCache.batch: sampler='device' needs 1 <= B <= 4096 and B * num_points < 2^31 (got {B} x {P})")
+        block = torch.empty(PARAM_BYTES * B + 4, dtype=torch.uint8)
+        v_aug, v_cloud, v_first = self._block_views(block, B)
+        v_cloud[:], v_first[:] = indices, np.arange(B + 1, dtype=np.int64) * P
+        items = []
+        for b, idx in enumerate(indices):
+            fx, fy, angle = ds._draw_augmentation() if ds.augment else (1.0, 1.0, 0.0)
+            v_aug[b] = (fx, fy, np.cos(angle), np.sin(angle))
+            items.append(self._item(idx, fx, fy, rotz(angle)))
+        out = ds.collate_batch(items)
+        pcs = torch.empty(B, P, self.ncol, dtype=torch.float32, device=self.device)
+        self.last_sample_words = self.sample_generator.draw()
+        self._sample(block.to(self.device), self.last_sample_words, pcs)
+        out["point_clouds"] = pcs
+        return out
+
+    def _sample(self, params, words, points):
+        from wf3d import _lib
+        from wf3d.ops import _stream
+        B, P = points.shape[0], points.shape[1]
+        _lib.check(_lib.load().wf3d_cloud_sample_dev(self.norm.data_ptr(), self.first.data_ptr(), len(self.n), params.data_ptr(),
+                                                     words.data_ptr(), B, P, self.ncol, points.data_ptr(), _stream()), "cloud_sample_dev")
+
     # ---- packed batches: whole clouds, one after the other ----------------------------------------------------------
-    def _plan(self, indices, who, capacity=None, max_vertices=None):
+    def _plan(self, indices, who, capacity=None, max_vertices=None, num_points=None):
         ds = self.ds
-        return packed_plan(self.n, self.nv, indices, ds._draw_augmentation if ds.augment else None, capacity, max_vertices, who)
+        return packed_plan(self.n, self.nv, indices, ds._draw_augmentation if ds.augment else None, capacity, max_vertices, who,
+                           num_points)
 
     @staticmethod
     def _block_views(block, B):
@@ -407,14 +469,45 @@ class DeviceCloudCache:
                 "params_host": torch.zeros(PARAM_BYTES * B + 4, dtype=torch.uint8).pin_memory(),
                 "params_copied": torch.cuda.Event()}
 
+    def sampled_buffers(self, B, max_vertices, num_points=None):
+        """Static device tensors of a captured step for FIXED-SIZE batches sampled on the device: `points`
+        [B, P, C] (P = num_points or the data set's; the dense forward takes it as it is), train_targets' `vertices` /
+        `vertex_existence` / `edge_labels` (full width) / `vertex_counts`, the parameter block `params` with its pinned
+        mirror `params_host`, and `sample_words` (int32 [5]: the seed words `fill` draws, word 0 is the batch's)."""
+        B, V = operator.index(B), operator.index(max_vertices)
+        P = operator.index(num_points or self.ds.num_points or 0)
+        if P < 1:
+            raise ValueError("DeviceCloudCache.sampled_buffers: needs num_points or dataset.num_points")
+        if not 1 <= B <= 4096 or V < 1 or B * P > 0x7FFFFFFF:
+            raise ValueError(f"DeviceCloudCache.sampled_buffers: needs 1 <= B <= 4096, max_vertices >= 1 and B * num_points < 2^31 "
+                             f"(got {B}, {V}, {P})")
+        dev = self.device
+        f32 = dict(dtype=torch.float32, device=dev)
+        return {"points": torch.zeros(B, P, self.ncol, **f32),
+                "vertices": torch.zeros(B, V, 3, **f32),
+                "vertex_existence": torch.zeros(B, V, **f32),
+                "edge_labels": torch.zeros(B, V * (V - 1) // 2, **f32),
+                "vertex_counts": torch.zeros(B, dtype=torch.int64, device=dev),
+                "params": torch.zeros(PARAM_BYTES * B + 4, dtype=torch.uint8, device=dev),
+                "params_host": torch.zeros(PARAM_BYTES * B + 4, dtype=torch.uint8).pin_memory(),
+                "params_copied": torch.cuda.Event(),
+                "sample_words": torch.zeros(5, dtype=torch.int32, device=dev)}
+
     def stage(self, buffers, indices):
         """Host only, outside any capture: check the batch against the buffers (IndexError / ValueError, nothing touched),
         draw its augmentation from np.random, fill the pinned mirror and issue ONE non-blocking copy of the parameter
-        block.  Returns the batch's host-side fields `scan_idx`, `centroid`, `max_distance` as collate_batch builds them."""
-        B, capacity = buffers["point_counts"].shape[0], buffers["points"].shape[0]
+        block.  Returns the batch's host-side fields `scan_idx`, `centroid`, `max_distance` as collate_batch builds them.
+        `buffers` from packed_buffers or from sampled_buffers: the same checks (without the row capacity, which a
+        fixed-size batch does not have) and the same draws in the same order — per sample flip-x, flip-y, angle.  The
+        sampled form draws NO np.random.choice: it leaves np.random elsewhere than batch() does."""
+        sampled = "sample_words" in buffers
+        B = buffers["vertices"].shape[0]
         if len(indices) != B:
             raise ValueError(f"DeviceCloudCache.stage: {len(indices)} clouds for buffers of {B}")
-        indices, out_first, aug = self._plan(indices, "stage", capacity, buffers["vertices"].shape[1])
+        if sampled:
+            indices, out_first, aug = self._plan(indices, "stage", None, buffers["vertices"].shape[1], buffers["points"].shape[1])
+        else:
+            indices, out_first, aug = self._plan(indices, "stage", buffers["points"].shape[0], buffers["vertices"].shape[1])
         buffers["params_copied"].synchronize()             # the mirror's last copy has left it (no wait when it has)
         v_aug, v_cloud, v_first = self._block_views(buffers["params_host"], B)
         v_aug[:], v_cloud[:], v_first[:] = aug, indices, out_first
@@ -430,11 +523,16 @@ class DeviceCloudCache:
 
     def fill(self, buffers):
         """The two launches that fill `buffers` from the staged parameter block: every element of `points`, `point_counts`
-        and the four target tensors is written.  Capturable: everything the kernels read is in device memory."""
+        and the four target tensors is written.  Capturable: everything the kernels read is in device memory.
+        Sampled buffers take three: a draw of `sample_generator` into `sample_words`, the sampler (every element of
+        `points`), the targets — so every replay of a capture samples afresh."""
         from wf3d import _lib
         from wf3d.ops import _stream
         B, V = buffers["vertices"].shape[0], buffers["vertices"].shape[1]
-        self._pack(buffers["params"], B, buffers["points"].shape[0], buffers["points"], buffers["point_counts"])
+        if "sample_words" in buffers:
+            self._sample(buffers["params"], self.sample_generator.draw(out=buffers["sample_words"]), buffers["points"])
+        else:
+            self._pack(buffers["params"], B, buffers["points"].shape[0], buffers["points"], buffers["point_counts"])
         _lib.check(_lib.load().wf3d_wireframe_targets(
             self.wf_vertices.data_ptr(), self.wf_edges.data_ptr(), self.vfirst.data_ptr(), self.efirst.data_ptr(), len(self.n),
             buffers["params"].data_ptr(), B, V, buffers["vertices"].data_ptr(), buffers["vertex_existence"].data_ptr(),

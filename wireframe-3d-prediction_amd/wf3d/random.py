@@ -45,9 +45,15 @@ class DropoutGenerator:
         self.device = device
         self.state = torch.tensor([key, 0], dtype=torch.int64, device=device)
 
-    def draw(self):
-        """Launch the draw kernel on the current stream: a fresh int32 [5] tensor of seed words."""
-        words = torch.empty(5, dtype=torch.int32, device=self.device)
+    def draw(self, out=None):
+        """Launch the draw kernel on the current stream: a fresh int32 [5] tensor of seed words, or `out` (a static
+        int32 [5] tensor on this device: what a captured launch writes on every replay)."""
+        if out is None:
+            words = torch.empty(5, dtype=torch.int32, device=self.device)
+        elif out.dtype != torch.int32 or out.shape != (5,) or out.device != self.device or not out.is_contiguous():
+            raise ValueError(f"DropoutGenerator.draw: out must be a contiguous int32 [5] tensor on {self.device}")
+        else:
+            words = out
         check(_lib.load().wf3d_dropout_draw(self.state.data_ptr(), words.data_ptr(), _stream()), "dropout_draw")
         return words
 
