@@ -276,7 +276,8 @@ typedef struct wf3d_skinny_bwd_t {
     const float* xmu; const float* xrs; const float* xgamma; const float* xbeta; int xact;
     const float* xadd; int ldxadd;
     float* dW; int lddw; float* db;
-    float* slabs; int nc;
+    float* slabs; int nc;               /* nc: any even chunk height in 2..128 (a multiple of 4, with N % 4 == 0 and 16-byte
+                                           aligned dY / z rows, loads dz 16 bytes per lane; every other case by element) */
 } wf3d_skinny_bwd_t;
 size_t wf3d_skinny_slab_floats(int M, int N, int K, int nc);
 int wf3d_skinny_bwd(const wf3d_skinny_bwd_t* probs, int nprob, int M, void* stream);

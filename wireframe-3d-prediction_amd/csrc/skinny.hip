@@ -230,7 +230,8 @@ __device__ __forceinline__ void sk_load_dz(const wf3d_skinny_bwd_t& q, int M, in
         }
         __syncthreads();
     }
-    if (q.N % 4 == 0 && q.lddy % 4 == 0 && (!ln || q.ldz % 4 == 0) && aligned16d(q.dY) && (!ln || aligned16d(q.z))) {
+    // ncount % 4: a dgrad chunk of nc = 2, 6, 10, ... columns starts off a 16-byte boundary and is not whole float4's
+    if (ncount % 4 == 0 && q.N % 4 == 0 && q.lddy % 4 == 0 && (!ln || q.ldz % 4 == 0) && aligned16d(q.dY) && (!ln || aligned16d(q.z))) {
         // 16 B per lane, all of a thread's loads independent: thread = (4 columns, row m0 + rstep*i)
         const int ncq = ncount >> 2;                       // float4 per row: 16 (wgrad tile) or <= 32 (dgrad chunk)
         const int n4 = tid % ncq, m0 = tid / ncq, rstep = 256 / ncq;
