@@ -490,10 +490,18 @@ int wf3d_loss_cost_matrix(const float* verts, long sample_stride, long vertex_st
 /* Hungarian assignment on the device (Jonker-Volgenant shortest augmenting paths, fp64 duals,
  * one wave per sample) — replaces scipy.optimize.linear_sum_assignment + the per-sample
  * .cpu().numpy() sync of WireframeLoss.py:235-236.  col4row[b,p] = column of prediction p;
- * p is matched to a real target iff col4row[b,p] < counts[b]. */
+ * p is matched to a real target iff col4row[b,p] < counts[b].  Any square matrix, V <= 1024.
+ * Ties: among the columns of minimal path cost the unassigned one of lowest index, else the lowest index
+ * (tests/lsa_model.py states the solver in numpy; the result equals it element for element).
+ * Non-finite costs: the solver reads NaN and +inf as FLT_MAX and -inf as -FLT_MAX, so it terminates on every input
+ * and col4row[b, :] is always a permutation of 0..V-1 (optimal for the costs so read); it reports nothing.  The loss
+ * terms computed from that assignment then carry the NaN of their inputs, as torch's would. */
 int wf3d_loss_assign(const float* cost, int B, int V, int32_t* col4row, void* stream);
 /* Same result for the wireframe cost (dummy columns >= counts[b] identical per row): solves the count x V rectangular
- * problem "real targets -> distinct predictions, cost c[p,t] - e_p" instead of the padded square one (V <= 64). */
+ * problem "real targets -> distinct predictions, cost c[p,t] - e_p" instead of the padded square one (V <= 64; above
+ * that it is wf3d_loss_assign, counts unread).  counts[b] may be any int64 and is clamped to 0..V: a negative count
+ * matches nothing (col4row[b, p] = p), one above V is V.  Unmatched predictions get the dummy columns count, count+1,
+ * ... in index order.  Same tie rule and the same reading of non-finite costs. */
 int wf3d_loss_assign_counts(const float* cost, const int64_t* counts, int B, int V, int32_t* col4row, void* stream);
 int wf3d_loss_terms_assigned(const float* verts, long sample_stride, long vertex_stride, const float* exist,
                              const float* edge, int Ep, const float* tverts, int Vt, const float* texist,

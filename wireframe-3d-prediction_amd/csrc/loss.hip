@@ -6,6 +6,8 @@
 // the whole batch; the assignment itself stays scipy on the host, as in the reference), and one
 // kernel evaluates the three loss terms AND their gradients w.r.t. the model outputs — which are
 // exactly the cotangents entering the hot path's backward.
+#include <cfloat>
+
 #include "wf3d_common.h"
 
 namespace {
@@ -120,8 +122,24 @@ __global__ void loss_final_kernel(const float* __restrict__ part, int B, float n
 // whole train step is asynchronous.  Output col4row[b, p] = column assigned to prediction p.
 // Ties: a lane-order rule (unassigned column first, then lowest index); the dummy columns of
 // the wireframe cost are identical, so only assignments to real targets are meaningful and
-// those are unique whenever the optimum is.
+// those are unique whenever the optimum is.  tests/lsa_model.py states algorithm and tie rule in numpy; the kernels'
+// col4row equals it element for element (only additions and subtractions here: nothing contracts to an FMA).
+//
+// Non-finite costs.  All three kernels read the cost matrix through lsa_cost(): NaN and +inf become FLT_MAX, -inf
+// becomes -FLT_MAX, a finite value is unchanged.  That is what makes them terminate on any input: `r < spc` is false
+// for a NaN and for +inf against the initial +inf, so a raw row without a finite entry would leave path[j] unset for a
+// column that is still picked once only such columns remain, and the augmenting walk would then follow an unset entry
+// and never meet `r == cur`.  With finite costs every r of a row's first scan is finite (the duals are sums and
+// differences of finite costs, far below fp64's range) and less than the initial +inf, so the first scan sets path[j]
+// for every column; later scans only overwrite it with rows scanned in this same search.  Every path entry the walk
+// reads therefore names a row of this search's tree, each step moves one edge towards its root `cur`, and the walk ends
+// after at most V steps.  The result is always a permutation; a NaN in the model outputs then reaches the loss through
+// the term kernels, as it would in torch.
 // ---------------------------------------------------------------------------
+__device__ __forceinline__ float lsa_cost(float c) {
+    return c < FLT_MAX ? (c > -FLT_MAX ? c : -FLT_MAX) : FLT_MAX;       // NaN fails the first comparison
+}
+
 __global__ __launch_bounds__(64) void lsa_kernel(const float* __restrict__ cost, int V, int32_t* __restrict__ col4row_out) {
     extern __shared__ __attribute__((aligned(16))) unsigned char lsm[];
     double* u = reinterpret_cast<double*>(lsm);            // [V] row duals
@@ -149,7 +167,7 @@ __global__ __launch_bounds__(64) void lsa_kernel(const float* __restrict__ cost,
             int bestj = 0x7fffffff, best_free = 0;
             for (int j = lane; j < V; j += 64) {
                 if (in_sc[j]) continue;
-                const double r = min_val + (double)C[(size_t)i * V + j] - ui - v[j];
+                const double r = min_val + (double)lsa_cost(C[(size_t)i * V + j]) - ui - v[j];
                 double cur_spc = spc[j];
                 if (r < cur_spc) { cur_spc = r; spc[j] = r; path[j] = i; }
                 const int fr = row4col[j] < 0;
@@ -211,20 +229,21 @@ __device__ __forceinline__ double lane_read_f64(double x, int lane_uniform) {
 // square problem equals the rectangular one "assign each of the count real targets to a distinct prediction, cost
 // c[p,t] - e_p" (+ a constant): rows = targets, lane = prediction, only `count` augmentations instead of V (the
 // dataset's counts are 4..38 of 64).  Unmatched predictions get the dummy columns count, count+1, ... in lane order.
+// counts[b] is clamped to 0..V: a negative count is 0 (nothing matched), one above V is V.
 template <bool RECT>
 __global__ __launch_bounds__(64) void lsa64_kernel(const float* __restrict__ cost, const int64_t* __restrict__ counts, int V,
                                                     int32_t* __restrict__ col4row_out) {
     __shared__ float Cs[64 * 64];
     const int lane = threadIdx.x, b = blockIdx.x;
     const float* C = cost + (size_t)b * V * V;
-    const int nrow = RECT ? min((int)counts[b], V) : V;
+    const int nrow = RECT ? (int)min(max(counts[b], (int64_t)0), (int64_t)V) : V;
     const bool col_ok = lane < V;
     double ep = 0.0;
     if (RECT) {
-        for (int idx = lane; idx < nrow * V; idx += 64) Cs[idx] = C[(size_t)(idx % V) * V + idx / V];      // Cs[t][p] = cost[p][t]
-        if (col_ok && nrow < V) ep = (double)C[(size_t)lane * V + V - 1];
+        for (int idx = lane; idx < nrow * V; idx += 64) Cs[idx] = lsa_cost(C[(size_t)(idx % V) * V + idx / V]);      // Cs[t][p] = cost[p][t]
+        if (col_ok && nrow < V) ep = (double)lsa_cost(C[(size_t)lane * V + V - 1]);
     } else {
-        for (int idx = lane; idx < V * V; idx += 64) Cs[idx] = C[idx];
+        for (int idx = lane; idx < V * V; idx += 64) Cs[idx] = lsa_cost(C[idx]);
     }
     __syncthreads();
     double u = 0.0, v = 0.0;

@@ -13,7 +13,14 @@ Differences to know about:
     (the reference's inf-padded cost matrix makes scipy raise there; raising would need a host sync); the
     scipy path raises like the reference.
   * exactly tied assignment costs: the device solver works on the same padded square problem in the same row
-    order as scipy and reproduced its matches on every tested tie, but ties are not pinned by any fixture.
+    order as scipy, but its tie rule is its own — among the columns of minimal path cost the unassigned one of
+    lowest index, else the lowest index — and on tied problems (lattice coordinates, say) it may return another
+    optimal matching than scipy.  The rule is pinned: tests/lsa_model.py states the solver in numpy and
+    tests/test_loss_assign_forms_gpu.py holds every kernel form to it element for element, tied inputs included.
+  * non-finite costs (NaN model outputs after a poisoned optimizer step, say): the device solver reads NaN and
+    +inf as FLT_MAX and -inf as -FLT_MAX, so it always terminates and always returns a permutation; the loss
+    terms then produce NaN from NaN inputs as torch would, and the step goes on without a host check.  The
+    reference and the scipy path raise a ValueError there.
   * a padded edge head (PointCloudToWireframe.set_edge_layout("padded")) predicts [B, V(V-1)/2] with the width
     max_s E_s in predictions["edge_width"] (a device scalar): the edge term runs over min(that width, label width),
     as the reference's over min(pred width, label width), so labels may be allocated at full width V(V-1)/2.
