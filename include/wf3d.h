@@ -382,6 +382,42 @@ int wf3d_packed_layout_build(const int64_t* counts, int B, int capacity, int32_t
 int wf3d_packed_layout_build_i32(const int32_t* counts, int B, int capacity, int32_t* rows, int32_t* cchunk,
                                  int32_t* chunks, int32_t* status, void* stream);
 
+/* FORWARD-ONLY encoder (wf3d.infer): the per-point MLP walks the flat row space in blocks and keeps nothing for a
+ * backward; these are the two pieces it needs beyond the training forward's entry points.
+ *
+ * STREAMING 4-way pool.  `state` (wf3d_pool4_stream_state_bytes, 16-byte aligned, device memory) holds per cloud and
+ * channel the masked sum, unmasked sum, masked max and unmasked max, and per cloud the number of valid rows seen.
+ *   wf3d_pool4_stream_init    sums and counts = 0, maxima = -inf.
+ *   wf3d_pool4_stream         folds the rows [r0, r0 + rows) of the flat row space into the state of the clouds they
+ *                             belong to; pf [rows, C] (contiguous) and valid [rows] point at row r0.  The cloud of a
+ *                             row comes from `offsets`, int32 [B + 1] in device memory (a packed layout's `rows` table;
+ *                             b * N for a dense batch), which is never read on the host.  A block may start and end
+ *                             anywhere: inside one cloud, across several, over clouds of no rows.  Rows at or past
+ *                             offsets[B] (pad and capacity rows) belong to no cloud and are not read.  Every row below
+ *                             offsets[B] must be folded exactly once before the finish; the blocks may come in any
+ *                             order, the sums are formed in the order they come in.
+ *   wf3d_pool4_stream_finish  writes what wf3d_pool4_seg_fwd writes, without the arg-max rows (nothing reads them
+ *                             without a backward): mmax (0 where a cloud has no valid row), mavg = masked sum /
+ *                             max(count, 1), umean = sum / the cloud's row count, umax — a cloud of no rows pools to
+ *                             zeros — each [B, C] with row stride ldo, cnt[b] = max(count, 1), nvalid[b] (optional)
+ *                             = count.
+ * No floating-point atomics: a block is cut into slices of a height that (rows, C) alone decide, a slice inside one
+ * cloud is reduced by one workgroup per 64 channels (C % 64 == 0 and a 16-byte aligned pf: 16 bytes per lane; any other
+ * C: one thread per channel), and one owner thread per (cloud, channel) adds the slices to the state in ascending row
+ * order, reading the rows of a slice that straddles a cloud boundary itself.  Same calls, same bits. */
+size_t wf3d_pool4_stream_state_bytes(int B, int C);
+int wf3d_pool4_stream_init(void* state, int B, int C, void* stream);
+size_t wf3d_pool4_stream_ws_bytes(int rows, int C);
+int wf3d_pool4_stream(const float* pf, const float* valid, const int32_t* offsets, int B, int r0, int rows, int C,
+                      void* state, void* ws, size_t ws_bytes, void* stream);
+int wf3d_pool4_stream_finish(const void* state, const int32_t* offsets, int B, int C, float* mmax, float* mavg,
+                             float* umean, float* umax, int ldo, float* cnt, float* nvalid, void* stream);
+/* FIRST LAYER WITHOUT z.  wf3d_first_layer_fwd's shapes (K <= 8, D % 8 == 0, D <= 1024) and arithmetic, in its order:
+ * h_sx8 = act(LN(x·W^T + b)) is that entry point's h_sx8 bit for bit; z, mu and rs are not written (2 KB per row at
+ * D = 512 that nothing reads without a backward).  It takes no live-row count. */
+int wf3d_first_layer_infer(const float* x, int R, int K, int ldx, const float* W, int ldw, const float* bias, int D,
+                           const float* gamma, const float* beta, int act, float eps, void* h_sx8, void* stream);
+
 /* ------------------------------------------------------------------------
  * Vertex head tail (VertexPredictor.py:118-127): existence = sigmoid(o[:,:,3]),
  * actual_vertex_counts = sum(existence > 0.5) (int64), o = final_layer output

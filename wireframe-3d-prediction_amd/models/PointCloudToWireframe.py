@@ -11,6 +11,7 @@ import torch.nn as nn
 from models.EdgePredictor import EdgePredictor
 from models.PointNetEncoder import PointNetEncoder
 from models.VertexPredictor import VertexPredictor
+from wf3d import config
 from wf3d.functional import EdgeIndexLists, edge_index_lists
 
 
@@ -93,8 +94,17 @@ class PointCloudToWireframe(nn.Module):
                 "edge_counts": ecounts,
                 "edge_width": width}
 
+    @staticmethod
+    def _stream():
+        """The encoder stage takes the forward-only path (wf3d.infer): the setting asks for it and grad mode is off.
+        train() / eval() does not enter the decision."""
+        return config.inference() == "stream" and not torch.is_grad_enabled()
+
     def forward(self, point_cloud, target_vertex_counts=None):
-        g, _pf, upooled = self.encoder.encode(point_cloud)
+        if self._stream():
+            g, _pf, upooled = self.encoder.encode_stream(point_cloud)
+        else:
+            g, _pf, upooled = self.encoder.encode(point_cloud)
         return self._heads(g, upooled, target_vertex_counts)
 
     def set_packed_tail(self, tail):
@@ -124,7 +134,10 @@ class PointCloudToWireframe(nn.Module):
         self.encoder._check_tail(capacity)
         if capacity is None and torch.is_tensor(point_counts) and point_counts.is_cuda:
             point_counts = self._host_counts(point_counts, "_point_count_cache")
-        g, _pf, upooled, layout = self.encoder._encode_packed(points, point_counts, capacity)
+        if self._stream():
+            g, _pf, upooled, layout = self.encoder._encode_packed_stream(points, point_counts, capacity)
+        else:
+            g, _pf, upooled, layout = self.encoder._encode_packed(points, point_counts, capacity)
         out = self._heads(g, upooled, target_vertex_counts)
         if layout.status is not None:
             out["point_status"] = layout.status

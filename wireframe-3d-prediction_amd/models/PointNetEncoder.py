@@ -8,7 +8,7 @@ to wf3d.functional.EncoderFn (HIP kernels through the C ABI)."""
 import torch
 import torch.nn as nn
 
-from wf3d import config, ops
+from wf3d import config, infer, ops
 from wf3d.functional import EncoderFn, EncoderFnPacked, EncoderFnPackedSkip, FusionFn
 
 
@@ -113,6 +113,15 @@ class PointNetEncoder(nn.Module):
     def _encode_packed(self, points, point_counts, capacity):
         """encode_packed, and the layout it ran on."""
         tail = self._check_tail(capacity)
+        layout = self._packed_layout(points, point_counts, capacity)
+        fn = EncoderFnPackedSkip if tail == "skip" else EncoderFnPacked
+        pooled, pf, upooled = fn.apply(points.float(), layout, self._n_hidden, self.precision or config.precision(),
+                                       *self._mlp_params())
+        g = FusionFn.apply(pooled, *self._fusion_params())
+        return g, pf, upooled, layout
+
+    def _packed_layout(self, points, point_counts, capacity):
+        """The arguments of a packed call checked on the host, and the row layout of its counts."""
         on_device = capacity is not None and torch.is_tensor(point_counts) and point_counts.is_cuda
         counts = None if on_device else ops.point_counts_list(point_counts)
         if not torch.is_tensor(points) or points.dim() != 2:
@@ -133,15 +142,45 @@ class PointNetEncoder(nn.Module):
                 raise ValueError("device point counts must be a 1-D int64 or int32 tensor of at least one cloud")
             if point_counts.device != points.device:
                 raise ValueError("device point counts must be on the points' device")
-            layout = ops.DevicePackedLayout(point_counts.shape[0], capacity, points.device).build(point_counts.contiguous())
-        else:
-            layout = ops.PackedLayout.get(counts, points.device, capacity)
-        fn = EncoderFnPackedSkip if tail == "skip" else EncoderFnPacked
-        pooled, pf, upooled = fn.apply(points.float(), layout, self._n_hidden, self.precision or config.precision(),
-                                       *self._mlp_params())
-        g = FusionFn.apply(pooled, *self._fusion_params())
-        return g, pf, upooled, layout
+            return ops.DevicePackedLayout(point_counts.shape[0], capacity, points.device).build(point_counts.contiguous())
+        return ops.PackedLayout.get(counts, points.device, capacity)
+
+    def encode_stream(self, x, want_pf=False, rows=None):
+        """encode() on the forward-only path (wf3d.infer): the per-point MLP walks the B * N rows in blocks of `rows`
+        (a positive multiple of 8; None: wf3d.config.INFER_ROWS), keeps nothing for a backward and pools the blocks as
+        they pass.  Returns (global, point_features [B, N, C] if want_pf else None, unmasked_pooled); runs under
+        torch.no_grad() whatever the caller's grad mode."""
+        if x.dim() != 3:
+            raise ValueError(f"expected (batch, num_points, input_dim), got {tuple(x.shape)}")
+        if not x.is_cuda:
+            raise RuntimeError("wf3d: the HIP path needs CUDA (ROCm) tensors; there is no CPU fallback")
+        B, N, Din = x.shape
+        with torch.no_grad():
+            x2 = x.float().reshape(B * N, Din).contiguous()
+            po, pf = infer.encoder_stream(x2, infer.DenseRows(B, N, x.device), self._n_hidden,
+                                          self.precision or config.precision(), self._mlp_params(), rows, want_pf)
+            g = FusionFn.apply(po.masked, *self._fusion_params())
+        return g, (pf.view(B, N, -1) if want_pf else None), po.unmasked
+
+    def encode_packed_stream(self, points, point_counts, capacity=None, want_pf=False, rows=None):
+        """encode_packed() on the forward-only path (encode_stream).  With host counts the blocks stop at the live row
+        total rounded up to 8 (rows of a requested point_features behind that are zeros); with device counts and a
+        capacity all `capacity` rows are walked, the pools ignore the rows behind the clouds, and nothing is read on the
+        host.  The packed tail mode does not apply: there is no backward whose rows could be skipped."""
+        return self._encode_packed_stream(points, point_counts, capacity, want_pf, rows)[:3]
+
+    def _encode_packed_stream(self, points, point_counts, capacity, want_pf=False, rows=None):
+        """encode_packed_stream, and the layout it ran on."""
+        layout = self._packed_layout(points, point_counts, capacity)
+        walk = points.shape[0] if layout.M is None else min(points.shape[0], -(-layout.M // 8) * 8)
+        with torch.no_grad():
+            po, pf = infer.encoder_stream(points.float(), layout, self._n_hidden, self.precision or config.precision(),
+                                          self._mlp_params(), rows, want_pf, walk=walk)
+            g = FusionFn.apply(po.masked, *self._fusion_params())
+        return g, pf, po.unmasked, layout
 
     def forward(self, x):
+        if config.inference() == "stream" and not torch.is_grad_enabled():
+            return self.encode_stream(x, want_pf=True)[:2]
         g, pf, _ = self.encode(x)
         return g, pf

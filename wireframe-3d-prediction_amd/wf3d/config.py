@@ -19,6 +19,15 @@ dropout_rng
              memory) and the mask kernels load them at run time, so every replay of a captured training step draws
              fresh masks.
 Environment override: WF3D_DROPOUT_RNG.
+
+inference
+    "train" (default): a forward under torch.no_grad() is the training forward, which keeps every layer's activations
+             until it returns.
+    "stream": with grad mode off, the encoder stage of PointNetEncoder.forward and PointCloudToWireframe.forward /
+             forward_packed takes the forward-only path (wf3d.infer): the per-point MLP walks the rows in blocks of
+             INFER_ROWS, keeps nothing for a backward and pools the blocks as they pass.  With grad mode on nothing
+             changes; the module's train() / eval() mode does not enter the decision.
+Environment override: WF3D_INFERENCE.
 """
 import os
 
@@ -44,6 +53,29 @@ def set_dropout_rng(src):
     if src not in DROPOUT_RNGS:
         raise ValueError("dropout_rng must be 'host' or 'device'")
     _dropout_rng = src
+
+
+INFERENCES = ("train", "stream")
+_inference = os.environ.get("WF3D_INFERENCE", "train")
+if _inference not in INFERENCES:
+    raise RuntimeError(f"WF3D_INFERENCE={_inference!r}: expected 'train' or 'stream'")
+
+# Rows per block of the forward-only encoder (a positive multiple of 8; wf3d.infer.block_plan).  Chosen by measurement
+# ("Forward only"): the fastest fixed height of the sweep 4096 .. 32768 at cfg2 and at cfg4, 6 - 7 %
+# behind the training forward at 1/7 of its peak memory.  8192 rows (z plus h of the 2048-wide layer = 128 MiB, half of
+# the Infinity Cache) measured 42 % behind: per block, the GEMMs have too few tiles and the host too many launches.
+INFER_ROWS = 32768
+
+
+def inference():
+    return _inference
+
+
+def set_inference(mode):
+    global _inference
+    if mode not in INFERENCES:
+        raise ValueError("inference must be 'train' or 'stream'")
+    _inference = mode
 
 
 def precision():

@@ -59,6 +59,14 @@ def scratch(nbytes, device, slot=0):
     return buf
 
 
+def _row_bufs(what, R, *bufs):
+    """Caller-provided per-row outputs: contiguous float32 [R] device tensors."""
+    for t in bufs:
+        _need_cuda(t)
+        if t.dtype != torch.float32 or t.dim() != 1 or t.shape[0] != R or not t.is_contiguous():
+            raise RuntimeError(f"wf3d.{what}: an out buffer must be a contiguous float32 [{R}] tensor")
+
+
 def _rows2d(t):
     if t.dim() != 2 or (t.shape[1] > 1 and t.stride(1) != 1):
         raise RuntimeError("wf3d: expected a 2-D tensor with unit inner stride")
@@ -171,12 +179,17 @@ def gemm(a, b, layout, bias=None, addend=None, out=None, accumulate=False, pro=N
     return out
 
 
-def row_stats(z, eps=LN_EPS):
+def row_stats(z, eps=LN_EPS, out=None):
+    """(mu, rs) of the rows of z; out = (mu, rs): contiguous float32 [R] buffers to write instead of new ones."""
     _need_cuda(z)
     z = _rows2d(z)
     R, D = z.shape
-    mu = torch.empty(R, dtype=torch.float32, device=z.device)
-    rs = torch.empty(R, dtype=torch.float32, device=z.device)
+    if out is not None:
+        mu, rs = out
+        _row_bufs("row_stats", R, mu, rs)
+    else:
+        mu = torch.empty(R, dtype=torch.float32, device=z.device)
+        rs = torch.empty(R, dtype=torch.float32, device=z.device)
     ld = z.stride(0) if R > 1 else D
     check(_lib.load().wf3d_row_stats(_p(z), R, D, ld, eps, _p(mu), _p(rs), _stream()), "row_stats")
     return mu, rs
@@ -289,12 +302,14 @@ def rowdot_act_bwd(z, dlogit, W, act, want_dz=True, dz_split=None):
     return dz, duo[0].view(1, D), duo[1]
 
 
-def point_valid(x):
+def point_valid(x, out=None):
     _need_cuda(x)
     if not x.is_contiguous():
         raise RuntimeError("wf3d.point_valid: contiguous input required")
     M, D = x.numel() // x.shape[-1], x.shape[-1]
-    valid = torch.empty(M, dtype=torch.float32, device=x.device)
+    if out is not None:
+        _row_bufs("point_valid", M, out)
+    valid = out if out is not None else torch.empty(M, dtype=torch.float32, device=x.device)
     check(_lib.load().wf3d_point_valid(_p(x), M, D, _p(valid), _stream()), "point_valid")
     return valid
 
@@ -305,14 +320,14 @@ class PoolOut:
     mmax/mavg/umean/umax are views of their halves."""
     __slots__ = ("masked", "unmasked", "mmax", "mavg", "umean", "umax", "arg_m", "arg_u", "cnt", "nvalid")
 
-    def __init__(self, B, C, dev):
+    def __init__(self, B, C, dev, argmax=True):
         """Uninitialised outputs of B clouds x C channels for a pooling launch to fill."""
         self.masked = torch.empty(B, 2 * C, dtype=torch.float32, device=dev)
         self.unmasked = torch.empty(B, 2 * C, dtype=torch.float32, device=dev)
         self.mmax, self.mavg = self.masked[:, :C], self.masked[:, C:]
         self.umean, self.umax = self.unmasked[:, :C], self.unmasked[:, C:]
-        self.arg_m = torch.empty(B, C, dtype=torch.int32, device=dev)
-        self.arg_u = torch.empty(B, C, dtype=torch.int32, device=dev)
+        self.arg_m = torch.empty(B, C, dtype=torch.int32, device=dev) if argmax else None
+        self.arg_u = torch.empty(B, C, dtype=torch.int32, device=dev) if argmax else None
         cn = torch.empty(2, B, dtype=torch.float32, device=dev)
         self.cnt, self.nvalid = cn[0], cn[1]
 
@@ -617,6 +632,46 @@ def pool4_seg_bwd_colsum(nvalid, cnt, arg_m, arg_u, dmmax, dmavg, dumean, dumax,
 
 
 # ---------------------------------------------------------------------------
+# streaming pools of the forward-only encoder (wf3d.infer)
+# ---------------------------------------------------------------------------
+class PoolStream:
+    """The running 4-way pool of B clouds x C channels (include/wf3d.h, "STREAMING 4-way pool"): fold() the blocks of
+    point_features as they pass, then finish().  `offsets`: int32 [B + 1] row offsets in device memory (a packed
+    layout's d_rows; b * N for a dense batch); they are never read on the host."""
+
+    def __init__(self, offsets, C):
+        _need_cuda(offsets)
+        if offsets.dtype != torch.int32 or offsets.dim() != 1 or offsets.shape[0] < 2 or not offsets.is_contiguous():
+            raise RuntimeError("wf3d.PoolStream: offsets must be a contiguous int32 [B + 1] device tensor")
+        self.offsets, self.B, self.C = offsets, offsets.shape[0] - 1, int(C)
+        lib = _lib.load()
+        nb = lib.wf3d_pool4_stream_state_bytes(self.B, self.C)
+        self.state = torch.empty(nb // 4, dtype=torch.float32, device=offsets.device)
+        check(lib.wf3d_pool4_stream_init(_p(self.state), self.B, self.C, _stream()), "pool4_stream_init")
+
+    def fold(self, pf, valid, r0):
+        """pf [rows, C] (contiguous), valid [rows]: rows r0 .. r0 + rows - 1 of the flat row space."""
+        _need_cuda(pf, valid)
+        if pf.dim() != 2 or pf.shape[1] != self.C or not pf.is_contiguous() or pf.dtype != torch.float32:
+            raise RuntimeError(f"wf3d.PoolStream.fold: contiguous float32 point_features [rows, {self.C}] required")
+        rows = pf.shape[0]
+        if valid.dtype != torch.float32 or valid.numel() != rows or not valid.is_contiguous():
+            raise RuntimeError(f"wf3d.PoolStream.fold: valid must be a contiguous float32 [{rows}]")
+        lib = _lib.load()
+        ws = scratch(lib.wf3d_pool4_stream_ws_bytes(rows, self.C), pf.device)
+        check(lib.wf3d_pool4_stream(_p(pf), _p(valid), _p(self.offsets), self.B, int(r0), rows, self.C, _p(self.state),
+                                    _p(ws), ws.numel() if ws is not None else 0, _stream()), "pool4_stream")
+
+    def finish(self):
+        """PoolOut of the B clouds, without arg-max rows (arg_m = arg_u = None)."""
+        o = PoolOut(self.B, self.C, self.state.device, argmax=False)
+        check(_lib.load().wf3d_pool4_stream_finish(_p(self.state), _p(self.offsets), self.B, self.C, _p(o.mmax), _p(o.mavg),
+                                                   _p(o.umean), _p(o.umax), 2 * self.C, _p(o.cnt), _p(o.nvalid), _stream()),
+              "pool4_stream_finish")
+        return o
+
+
+# ---------------------------------------------------------------------------
 # vertex-head tail and edge head
 # ---------------------------------------------------------------------------
 def vertex_finalize_fwd(o, V, vd):
@@ -898,15 +953,23 @@ def split_weights(weights):
     return out
 
 
-def ln_prep(z, gamma, beta, act, eps=LN_EPS, drop_p=0.0, seed=0):
-    """(mu, rs, h_sx8) with h = drop(act(LayerNorm(z))); z contiguous [R, D], D % 8 == 0."""
+def ln_prep(z, gamma, beta, act, eps=LN_EPS, drop_p=0.0, seed=0, out=None):
+    """(mu, rs, h_sx8) with h = drop(act(LayerNorm(z))); z contiguous [R, D], D % 8 == 0.  out = (mu, rs, h): buffers
+    to write instead of new ones (mu, rs contiguous float32 [R], h contiguous [R, D])."""
     _need_cuda(z, gamma, beta)
     if not z.is_contiguous():
         raise RuntimeError("wf3d.ln_prep: contiguous z required")
     R, D = z.shape
-    mu = torch.empty(R, dtype=torch.float32, device=z.device)
-    rs = torch.empty(R, dtype=torch.float32, device=z.device)
-    h = torch.empty_like(z)
+    if out is not None:
+        mu, rs, h = out
+        _row_bufs("ln_prep", R, mu, rs)
+        _need_cuda(h)
+        if tuple(h.shape) != (R, D) or not h.is_contiguous() or h.dtype != torch.float32:
+            raise RuntimeError(f"wf3d.ln_prep: out h must be a contiguous float32 [{R}, {D}]")
+    else:
+        mu = torch.empty(R, dtype=torch.float32, device=z.device)
+        rs = torch.empty(R, dtype=torch.float32, device=z.device)
+        h = torch.empty_like(z)
     check(_lib.load().wf3d_ln_prep(_p(z), R, D, _p(gamma), _p(beta), act, eps, float(drop_p), int(seed) & 0xFFFFFFFF,
                                    _p(mu), _p(rs), _p(h), _stream()), "ln_prep")
     return mu, rs, h
@@ -929,6 +992,21 @@ def first_layer_fwd(x, W, bias, gamma, beta, act, eps=LN_EPS):
     check(_lib.load().wf3d_first_layer_fwd(_p(x), R, K, x.stride(0), _p(W), W.stride(0), _p(bias), D, _p(gamma), _p(beta),
                                            act, eps, _p(z), _p(mu), _p(rs), _p(h), _stream()), "first_layer_fwd")
     return z, mu, rs, h
+
+
+def first_layer_infer(x, W, bias, gamma, beta, act, eps=LN_EPS, out=None):
+    """x [R, K<=8] -> h_sx8 = act(LayerNorm(x·W^T + b)) alone: first_layer_fwd's h bit for bit, no z, mu or rs
+    (forward-only path).  out: a contiguous float32 [R, D] buffer to write instead of a new one."""
+    _need_cuda(x, W, bias, gamma, beta, out)
+    R, K = x.shape
+    D = W.shape[0]
+    if out is None:
+        out = torch.empty(R, D, dtype=torch.float32, device=x.device)
+    elif tuple(out.shape) != (R, D) or not out.is_contiguous() or out.dtype != torch.float32:
+        raise RuntimeError(f"wf3d.first_layer_infer: out must be a contiguous float32 [{R}, {D}]")
+    check(_lib.load().wf3d_first_layer_infer(_p(x), R, K, x.stride(0), _p(W), W.stride(0), _p(bias), D, _p(gamma), _p(beta),
+                                             act, eps, _p(out), _stream()), "first_layer_infer")
+    return out
 
 
 def ln_act_bwd_first(dh, z, x, mu, rs, gamma, beta, act):
