@@ -418,6 +418,29 @@ int wf3d_pool4_stream_finish(const void* state, const int32_t* offsets, int B, i
 int wf3d_first_layer_infer(const float* x, int R, int K, int ldx, const float* W, int ldw, const float* bias, int D,
                            const float* gamma, const float* beta, int act, float eps, void* h_sx8, void* stream);
 
+/* FORWARD-ONLY edge head (wf3d.infer.edge_stream): the edge rows of a layout are walked in blocks through reused
+ * buffers; these are the two pieces the walk needs beyond the training forward's entry points.
+ *
+ * PAIR COMBINE OF A BLOCK.  wf3d_edge_pair_fwd / _fwd_ln (below, "Edge head") over the edge rows [e0, e0 + n) of the
+ * layout, written at the block-local row e - e0, without dropout and without the stores only a backward reads.  Two
+ * forms, chosen by the pointers given (anything else is refused):
+ *   h_sx8 alone        h = act(LayerNorm(pre)) [n, H] as the sx8 operand of the next Linear (pre = mu = rs = NULL;
+ *                      needs gamma, beta, H % 8 == 0 and 16-byte aligned h_sx8 / gamma / beta)
+ *   pre, mu, rs alone  pre [n, H], mu [n], rs [n] (h_sx8 = NULL; gamma, beta and act are not read)
+ * The arithmetic per row and its order are those entry points': each output equals their rows [e0, e0 + n) bit for bit
+ * (drop_p = 0).  e0 is a non-negative multiple of 8, n >= 0 is any count: a block may start in the middle of a sample and
+ * end anywhere.  Rows whose esample is negative (a padded layout's tail) get zeros in every output.  Neither esample
+ * nor any output is touched at or past row e0 + n.  The calling thread's live-row count is honoured as
+ * wf3d_edge_pair_fwd_ln honours it, read as a count over the n rows of THIS block (wf3d_block_live). */
+int wf3d_edge_pair_infer(const float* Pa, const float* Pb, const float* cv, const float* wdelta, int wdelta_stride,
+                         const int32_t* voff, const int32_t* eoff, const int32_t* esample, int e0, int n, int H, int vd,
+                         float eps, const float* gamma, const float* beta, int act, float* pre, float* mu, float* rs,
+                         void* h_sx8, void* stream);
+/* blive[k] = clamp(*total - k * rows, 0, min(rows, Re - k * rows)) for k < nblocks, int32: the live rows of block k of
+ * a walk of Re rows in blocks of `rows`, from the live total in device memory (wf3d_edge_layout's eoff + B), which is
+ * never read on the host.  One launch, plain stores. */
+int wf3d_block_live(const int32_t* total, int rows, int Re, int nblocks, int32_t* blive, void* stream);
+
 /* ------------------------------------------------------------------------
  * Vertex head tail (VertexPredictor.py:118-127): existence = sigmoid(o[:,:,3]),
  * actual_vertex_counts = sum(existence > 0.5) (int64), o = final_layer output
@@ -624,6 +647,7 @@ int wf3d_set_dropout_seed_words(const uint32_t* words);
  *   wf3d_ln_prep, wf3d_ln_act_bwd, wf3d_ln_act_bwd_wsum, wf3d_edge_pair_ln_bwd, wf3d_rowdot_act, wf3d_rowdot_act_bwd,
  *   wf3d_colsum                                R / Re
  *   wf3d_edge_pair_fwd, wf3d_edge_pair_fwd_ln, wf3d_edge_prob_bwd      Re
+ *   wf3d_edge_pair_infer                       n, the rows of the block (a block-local count)
  *   wf3d_split_rows                            R (rows of the output)
  *   wf3d_split_transpose                       R (rows of the input), both the fp32 / prologue and the in_sx8 form.  Its
  *                                              output is [C, R]: the input's rows are its COLUMNS, the reduction

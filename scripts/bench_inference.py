@@ -9,7 +9,14 @@
 --rows   block heights of the stream path, comma separated; M = all rows in one block.
 Every configuration is warmed up, then --iters (>= 20) forwards of each are timed with device events, round robin, so
 that clocks and cache state are shared between the paths.  Peak allocated bytes are those of one more forward per
-configuration, over what was allocated before it.  One JSON line per configuration (also appended to --out)."""
+configuration, over what was allocated before it.  One JSON line per configuration (also appended to --out).
+
+Edge-head mode: the shapes edge-cfg2 (B=32, V=64: 64,512 edge rows), edge-cfg5 (B=32, V=256: 1,044,480) and
+edge-cfg5-padded run EdgePredictor alone, eval(), no_grad, on EdgeFn ("train") and on wf3d.infer.edge_stream ("stream",
+--rows = its block heights, M = all edge rows).  The first two take forward_ragged with counts = V; the padded one takes
+forward_padded(tail="skip") with device counts drawn from U{4..38}, the data set's range, at max_vertices = 256.
+
+  python scripts/bench_inference.py --shape edge-cfg5 --rows 8192,16384,32768,65536,131072"""
 import argparse
 import json
 import os
@@ -20,17 +27,19 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "wireframe-3d-prediction_amd"))
 import torch  # noqa: E402
 
+from models.EdgePredictor import EdgePredictor  # noqa: E402
 from models.PointCloudToWireframe import PointCloudToWireframe  # noqa: E402
 from wf3d import config  # noqa: E402
 
 SHAPES = {"cfg2": (32, 4096, 64), "cfg4": (8, 16384, 64), "tile": (1, 1 << 20, 64)}
+EDGE_SHAPES = {"edge-cfg2": (32, 64, False), "edge-cfg5": (32, 256, False), "edge-cfg5-padded": (32, 256, True)}   # B, V, padded
 
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--shape", default="cfg2", choices=sorted(SHAPES))
+    ap.add_argument("--shape", default="cfg2", choices=sorted(SHAPES) + sorted(EDGE_SHAPES))
     ap.add_argument("--path", default="both", choices=["train", "stream", "both"])
-    ap.add_argument("--rows", default=str(config.INFER_ROWS))
+    ap.add_argument("--rows", default=None, help="default: config.INFER_ROWS, or config.INFER_EDGE_ROWS for an edge shape")
     ap.add_argument("--precision", default=config.precision(), choices=config.PRECISIONS)
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
@@ -38,15 +47,29 @@ def main():
     a = ap.parse_args()
     if a.iters < 20:
         ap.error("--iters must be at least 20")
-    B, N, V = SHAPES[a.shape]
-    M = B * N
     config.set_precision(a.precision)
     dev = torch.device("cuda:0")
     torch.manual_seed(0)
-    model = PointCloudToWireframe(input_dim=8, max_vertices=V).to(dev).eval()
-    with torch.no_grad():                          # make the untrained model predict >= 2 vertices per sample
-        model.vertex_predictor.final_layer.bias.view(V, 4)[:, 3].fill_(3.0)
-    x = torch.randn(B, N, 8, device=dev)
+    edge = a.shape in EDGE_SHAPES
+    if edge:
+        B, V, padded = EDGE_SHAPES[a.shape]
+        N, M = None, B * (V * (V - 1) // 2)        # the rows the stream path walks: edge rows
+        head = EdgePredictor().to(dev).eval()
+        verts = torch.randn(B, V, 3, device=dev)
+        counts = torch.randint(4, 39, (B,), generator=torch.Generator().manual_seed(1)).to(dev) if padded else [V] * B
+        extra = {"edge_rows": M, "layout": "padded/skip" if padded else "ragged"}
+        if padded:
+            extra["live_edge_rows"] = int((counts * (counts - 1) // 2).sum())
+    else:
+        B, N, V = SHAPES[a.shape]
+        M = B * N
+        model = PointCloudToWireframe(input_dim=8, max_vertices=V).to(dev).eval()
+        with torch.no_grad():                          # make the untrained model predict >= 2 vertices per sample
+            model.vertex_predictor.final_layer.bias.view(V, 4)[:, 3].fill_(3.0)
+        x = torch.randn(B, N, 8, device=dev)
+        extra = {}
+    if a.rows is None:
+        a.rows = str(config.INFER_EDGE_ROWS if edge else config.INFER_ROWS)
 
     cfgs = []                                      # (label, path, rows)
     if a.path in ("train", "both"):
@@ -57,10 +80,15 @@ def main():
             cfgs.append((f"stream-{rows}", "stream", rows))
 
     def forward(path, rows):
-        config.set_inference(path)
-        if rows is not None:
-            config.INFER_ROWS = rows
         with torch.no_grad():
+            if edge:
+                config.set_edge_inference(path)
+                if rows is not None:
+                    config.INFER_EDGE_ROWS = rows
+                return head.forward_padded(verts, counts, tail="skip") if padded else head.forward_ragged(verts, counts)
+            config.set_inference(path)
+            if rows is not None:
+                config.INFER_ROWS = rows
             return model(x)
 
     times = {c[0]: [] for c in cfgs}
@@ -86,13 +114,14 @@ def main():
         peaks[label] = torch.cuda.max_memory_allocated() - before
         del out
     config.set_inference("train")
+    config.set_edge_inference("train")
     lines = []
     for label, path, rows in cfgs:
         t = statistics.median(times[label])
         lines.append(json.dumps({"shape": a.shape, "B": B, "N": N, "V": V, "precision": a.precision, "config": label,
                                  "path": path, "rows": rows, "iters": a.iters, "median_ms": round(t, 4),
                                  "min_ms": round(min(times[label]), 4), "max_ms": round(max(times[label]), 4),
-                                 "clouds_per_s": round(B / t * 1e3, 1), "peak_bytes": int(peaks[label])}))
+                                 "clouds_per_s": round(B / t * 1e3, 1), "peak_bytes": int(peaks[label]), **extra}))
     for ln in lines:
         print(ln, flush=True)
     if a.out:

@@ -18,6 +18,11 @@
 //
 // First layer without z.  first_layer_infer_kernel is first_layer_kernel (split.hip) with the stores of z, mu and rs
 // taken out: the same expressions in the same order, so its h is that kernel's h_sx8 bit for bit.
+//
+// Forward-only edge head (wf3d.infer.edge_stream).  pair_infer_kernel is pair_fwd_kernel (edge.hip) over the edge rows
+// [e0, e0 + n) of a layout, written into block buffers indexed by e - e0, without the stores nobody reads and without
+// dropout: the same expressions in the same order, so its outputs are that kernel's rows bit for bit.
+// block_live_kernel cuts a layout's live edge-row total into one count per block of the walk.
 #include "wf3d_common.h"
 
 namespace {
@@ -358,6 +363,147 @@ __global__ __launch_bounds__(256) void first_layer_infer_kernel(const float* __r
     }
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// forward-only edge head
+// ---------------------------------------------------------------------------------------------------------------------
+// pair_fwd_kernel (edge.hip) with a row origin: one wave per 8 consecutive edge rows e0 + l, l in [l0, l0 + 8), of the
+// layout; every output is indexed by the block-local row l.  e0 % 8 == 0, so a wave's 8 rows are the 8 rows one wave of
+// pair_fwd_kernel walks.  Two forms, by the pointers given:
+//   h_sx8        : h = act(LN(pre)) as the sx8 operand alone (split route); pre, mu, rs are NULL
+//   pre, mu, rs  : the pre-activation and its row statistics (fp32 route); h_sx8 is NULL
+// No delta (only a backward reads it), no dropout.  `live_rows` is the BLOCK's live-row count: rows l at or past its
+// 256-row extent are neither read (esample) nor written.  Nothing at or past row n is touched.
+template <int NS>
+__global__ __launch_bounds__(256) void pair_infer_kernel(const float* __restrict__ Pa, const float* __restrict__ Pb,
+                                                          const float* __restrict__ cv, const float* __restrict__ wd,
+                                                          int wd_stride, const int32_t* __restrict__ voff,
+                                                          const int32_t* __restrict__ eoff,
+                                                          const int32_t* __restrict__ esample, int e0, int n, int H,
+                                                          float eps, float* __restrict__ pre, float* __restrict__ mu,
+                                                          float* __restrict__ rs, const float* __restrict__ gamma,
+                                                          const float* __restrict__ beta, int act,
+                                                          float* __restrict__ h_sx8, int vd,
+                                                          const int32_t* __restrict__ live_rows) {
+    constexpr int EPW = 8;
+    n = wf3d_live_extent(live_rows, n);
+    const int lane = threadIdx.x & 63;
+    const int l0 = (blockIdx.x * 4 + (threadIdx.x >> 6)) * EPW;
+    if (l0 >= n) return;
+    const int l1 = min(n, l0 + EPW);
+    f32x4 wdv[NS], g4[NS], b4[NS], pa[NS];
+#pragma unroll
+    for (int t = 0; t < NS; ++t) {
+        const int c = lane * 4 + 256 * t;
+        wdv[t] = g4[t] = b4[t] = pa[t] = (f32x4){0.f, 0.f, 0.f, 0.f};
+        if (c < H) {
+#pragma unroll
+            for (int k = 0; k < 4; ++k) wdv[t][k] = wd[(size_t)(c + k) * wd_stride];
+            if (h_sx8) { g4[t] = *reinterpret_cast<const f32x4*>(gamma + c); b4[t] = *reinterpret_cast<const f32x4*>(beta + c); }
+        }
+    }
+    // rows la..l1-1 of a padded layout's tail (contiguous, so the rest of this wave's rows): zeros in every output
+    auto zero_tail = [&](int la) {
+        for (int l = la; l < l1; ++l) {
+#pragma unroll
+            for (int t = 0; t < NS; ++t) {
+                const int c = lane * 4 + 256 * t;
+                if (c < H) {
+                    if (pre) *reinterpret_cast<f32x4*>(pre + (size_t)l * H + c) = (f32x4){0.f, 0.f, 0.f, 0.f};
+                    if (h_sx8) *reinterpret_cast<f32x4*>(h_sx8 + (size_t)l * H + c) = (f32x4){0.f, 0.f, 0.f, 0.f};
+                }
+            }
+            if (pre && lane == 0) { mu[l] = 0.f; rs[l] = 0.f; }
+        }
+    };
+    int s = esample[e0 + l0];
+    if (s < 0) { zero_tail(l0); return; }
+    int vbase = voff[s], v = voff[s + 1] - vbase, eend = eoff[s + 1];
+    int i, j;
+    edge_ij(e0 + l0 - eoff[s], v, i, j);                   // a block, like a wave, may start in the middle of a sample
+    int pa_row = -1;
+    for (int l = l0; l < l1; ++l) {
+        const int e = e0 + l;
+        if (e == eend) {                       // first edge of the next sample that has edges
+            s = esample[e];
+            if (s < 0) { zero_tail(l); return; }
+            vbase = voff[s]; v = voff[s + 1] - vbase; eend = eoff[s + 1];
+            i = 0; j = 1;
+        }
+        const int ri = vbase + i, rj = vbase + j;
+        float dl2 = 0.f;                                   // |c_i - c_j|^2 over the vd coordinates, in pair_fwd_kernel's order
+        for (int k = 0; k < vd; ++k) { const float d = cv[ri * vd + k] - cv[rj * vd + k]; dl2 = fmaf(d, d, dl2); }
+        const float dl = sqrtf(dl2);
+        f32x4 val[NS];
+        float sum = 0.f;
+#pragma unroll
+        for (int t = 0; t < NS; ++t) {
+            const int c = lane * 4 + 256 * t;
+            val[t] = (f32x4){0.f, 0.f, 0.f, 0.f};
+            if (c < H) {
+                if (ri != pa_row) pa[t] = *reinterpret_cast<const f32x4*>(Pa + (size_t)ri * H + c);
+                const f32x4 b = *reinterpret_cast<const f32x4*>(Pb + (size_t)rj * H + c);
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    val[t][k] = pa[t][k] + b[k] + dl * wdv[t][k];
+                    sum += val[t][k];
+                }
+                if (pre) *reinterpret_cast<f32x4*>(pre + (size_t)l * H + c) = val[t];
+            }
+        }
+        pa_row = ri;
+        const float mean = wf3d_wave_sum(sum) / (float)H;
+        float q = 0.f;
+#pragma unroll
+        for (int t = 0; t < NS; ++t) {
+            const int c = lane * 4 + 256 * t;
+            if (c < H) {
+#pragma unroll
+                for (int k = 0; k < 4; ++k) { const float d = val[t][k] - mean; q += d * d; }
+            }
+        }
+        const float var = wf3d_wave_sum(q) / (float)H;
+        const float rstd = 1.0f / sqrtf(var + eps);
+        if (pre && lane == 0) {
+            mu[l] = mean;
+            rs[l] = rstd;
+        }
+        if (h_sx8) {
+#pragma unroll
+            for (int t = 0; t < NS; ++t) {
+                const int c = lane * 4 + 256 * t;
+                if (c < H) {
+                    float o[4];
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) o[k] = wf3d_act_rt(act, (val[t][k] - mean) * rstd * g4[t][k] + b4[t][k]);
+                    // sx8 group = 8 columns = lanes (2m, 2m+1): even lane stores the 8 high parts, odd lane the 8 low parts
+                    typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
+                    bf16x4 hi, lo;
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) { hi[k] = (__bf16)o[k]; lo[k] = (__bf16)(o[k] - (float)hi[k]); }
+                    const uint2 mine_hi = __builtin_bit_cast(uint2, hi), mine_lo = __builtin_bit_cast(uint2, lo);
+                    const bool odd = lane & 1;
+                    uint2 send = odd ? mine_hi : mine_lo, got;
+                    got.x = __shfl_xor((int)send.x, 1, 64);
+                    got.y = __shfl_xor((int)send.y, 1, 64);
+                    const uint4 w = odd ? make_uint4(got.x, got.y, mine_lo.x, mine_lo.y) : make_uint4(mine_hi.x, mine_hi.y, got.x, got.y);
+                    *reinterpret_cast<uint4*>(h_sx8 + (size_t)l * H + (c & ~7) + (odd ? 4 : 0)) = w;
+                }
+            }
+        }
+        if (++j == v) { ++i; j = i + 1; }
+    }
+}
+
+// blive[k] = clamp(*total - k * rows, 0, min(rows, Re - k * rows)): the live rows of block k of the walk
+__global__ __launch_bounds__(256) void block_live_kernel(const int32_t* __restrict__ total, int rows, int Re, int nblocks,
+                                                          int32_t* __restrict__ blive) {
+    const int k = blockIdx.x * 256 + threadIdx.x;
+    if (k >= nblocks) return;
+    const long r0 = (long)k * rows;
+    const long cap = max(0L, min((long)rows, (long)Re - r0));
+    blive[k] = (int32_t)min(max((long)*total - r0, 0L), cap);
+}
+
 }  // namespace
 
 extern "C" size_t wf3d_pool4_stream_state_bytes(int B, int C) {
@@ -447,6 +593,45 @@ extern "C" int wf3d_first_layer_infer(const float* x, int R, int K, int ldx, con
     if (D <= 512) { if (fast) WF3D_FLI(1, true); else WF3D_FLI(1, false); }
     else          { if (fast) WF3D_FLI(2, true); else WF3D_FLI(2, false); }
 #undef WF3D_FLI
+    WF3D_LAUNCH_CHECK();
+    return WF3D_OK;
+}
+
+extern "C" int wf3d_edge_pair_infer(const float* Pa, const float* Pb, const float* cv, const float* wdelta,
+                                    int wdelta_stride, const int32_t* voff, const int32_t* eoff, const int32_t* esample,
+                                    int e0, int n, int H, int vd, float eps, const float* gamma, const float* beta, int act,
+                                    float* pre, float* mu, float* rs, void* h_sx8, void* stream) {
+    WF3D_CHECK(e0 >= 0 && e0 % 8 == 0 && n >= 0 && (long)e0 + n <= 0x7FFFFFFFL, WF3D_ERR_ARG,
+               "wf3d_edge_pair_infer: bad rows e0=%d n=%d (e0 must be a non-negative multiple of 8)", e0, n);
+    WF3D_CHECK(H > 0 && vd >= 1 && vd <= 8, WF3D_ERR_ARG, "wf3d_edge_pair_infer: bad dims (vertex_dim must be 1..8)");
+    WF3D_CHECK(H % 4 == 0 && H <= 2048, WF3D_ERR_UNSUPPORTED, "wf3d_edge_pair_infer: hidden %d must be a multiple of 4, <= 2048", H);
+    if (n == 0) return WF3D_OK;
+    WF3D_CHECK(Pa && Pb && cv && wdelta && voff && eoff && esample, WF3D_ERR_ARG, "wf3d_edge_pair_infer: null pointer");
+    const bool split = h_sx8 && !pre && !mu && !rs, fp32 = !h_sx8 && pre && mu && rs;
+    WF3D_CHECK(split || fp32, WF3D_ERR_ARG, "wf3d_edge_pair_infer: give h_sx8 alone, or pre, mu and rs alone");
+    if (split) {
+        WF3D_CHECK(gamma && beta && act >= 0 && act <= 2, WF3D_ERR_ARG, "wf3d_edge_pair_infer: null gamma / beta or bad act");
+        WF3D_CHECK(H % 8 == 0 && ((uintptr_t)h_sx8 % 16 == 0) && ((uintptr_t)gamma % 16 == 0) && ((uintptr_t)beta % 16 == 0),
+                   WF3D_ERR_UNSUPPORTED, "wf3d_edge_pair_infer: needs hidden %% 8 == 0 and 16-byte aligned pointers");
+    }
+    const int ns = wf3d_cdiv(H, 256);
+    hipStream_t st = (hipStream_t)stream;
+#define WF3D_PI(NS_)                                                                                                   \
+    hipLaunchKernelGGL((pair_infer_kernel<NS_>), dim3(wf3d_cdiv(n, 4 * 8)), dim3(256), 0, st, Pa, Pb, cv, wdelta,            \
+                       wdelta_stride, voff, eoff, esample, e0, n, H, eps, pre, mu, rs, gamma, beta, act, (float*)h_sx8, vd,  \
+                       wf3d_live_rows())
+    if (ns <= 1) WF3D_PI(1); else if (ns <= 2) WF3D_PI(2); else if (ns <= 4) WF3D_PI(4); else WF3D_PI(8);
+#undef WF3D_PI
+    WF3D_LAUNCH_CHECK();
+    return WF3D_OK;
+}
+
+extern "C" int wf3d_block_live(const int32_t* total, int rows, int Re, int nblocks, int32_t* blive, void* stream) {
+    WF3D_CHECK(rows > 0 && Re >= 0 && nblocks >= 0, WF3D_ERR_ARG, "wf3d_block_live: bad dims rows=%d Re=%d nblocks=%d", rows, Re, nblocks);
+    if (nblocks == 0) return WF3D_OK;
+    WF3D_CHECK(total && blive, WF3D_ERR_ARG, "wf3d_block_live: null pointer");
+    hipLaunchKernelGGL(block_live_kernel, dim3(wf3d_cdiv(nblocks, 256)), dim3(256), 0, (hipStream_t)stream, total, rows, Re,
+                       nblocks, blive);
     WF3D_LAUNCH_CHECK();
     return WF3D_OK;
 }

@@ -6,11 +6,13 @@ RNG-order and state_dict compatibility).  forward() accepts a
 padded batch [B, V, vertex_dim]; `forward_ragged` runs samples with different vertex
 counts in one pass, which is how PointCloudToWireframe replaces the reference's
 serial per-sample loop; `forward_padded` does the same with the counts in device memory
-(capturable, any counts under one capture)."""
+(capturable, any counts under one capture).  Under torch.no_grad() with no dropout active,
+wf3d.config.set_edge_inference("stream") sends all three to the forward-only path (wf3d.infer.edge_stream), which
+`forward_stream` calls directly."""
 import torch
 import torch.nn as nn
 
-from wf3d import config, ops
+from wf3d import config, infer, ops
 from wf3d.functional import EdgeFn, edge_index_lists
 from wf3d.random import default_generator
 
@@ -66,18 +68,58 @@ class EdgePredictor(nn.Module):
                                  "(needs 0 <= p < 1)")
         return ps
 
-    def forward_ragged(self, vertices, counts):
-        """vertices [B, Vmax, 3]; sample s uses its first counts[s] vertices.
-        Returns zero-padded probabilities [B, max_s E_s]."""
+    @staticmethod
+    def _ragged_counts(vertices, counts, who):
         if len(counts) != vertices.shape[0]:
-            raise ValueError(f"forward_ragged: {len(counts)} counts for a batch of {vertices.shape[0]}")
+            raise ValueError(f"{who}: {len(counts)} counts for a batch of {vertices.shape[0]}")
         counts = [min(int(c), vertices.shape[1]) for c in counts]      # `vertices[i, :count]` cannot take more than there is
         if any(c < 2 for c in counts):
             # the reference indexes a 1-D empty index tensor here (EdgePredictor.py:118)
             raise IndexError("too many indices for tensor of dimension 1")
+        return counts
+
+    @staticmethod
+    def _padded_meta(vertices, counts, tail, who):
+        if tail not in ("compute", "skip"):
+            raise ValueError(f"{who}: tail must be 'compute' or 'skip'")
+        B, V, _ = vertices.shape
+        if not torch.is_tensor(counts) or counts.dim() != 1 or counts.shape[0] != B:
+            raise ValueError(f"{who}: counts must be a 1-D tensor of {B} counts")
+        if counts.dtype.is_floating_point or counts.dtype.is_complex:
+            raise ValueError(f"{who}: counts must be integers")
+        return ops.EdgeMeta.device(counts.to(device=vertices.device, dtype=torch.int64).contiguous(), B, V, tail=tail)
+
+    def forward_ragged(self, vertices, counts):
+        """vertices [B, Vmax, 3]; sample s uses its first counts[s] vertices.
+        Returns zero-padded probabilities [B, max_s E_s]."""
+        counts = self._ragged_counts(vertices, counts, "forward_ragged")
+        if self._stream():
+            return self._edge_stream(vertices, ops.EdgeMeta.get(counts, vertices.device))
         ps, seed = self._dropout(vertices.device)
         return EdgeFn.apply(vertices.float(), tuple(counts), self._heads, ps, seed, config.precision(),
                             *self._param_list())
+
+    def _stream(self):
+        """The forward-only path (wf3d.infer.edge_stream) serves this call: the edge setting asks for it, grad mode is
+        off and no dropout probability is active (the block kernels draw no masks)."""
+        return config.edge_inference() == "stream" and not torch.is_grad_enabled() and not any(self._dropout_ps())
+
+    def _edge_stream(self, vertices, meta, rows=None):
+        return infer.edge_stream(vertices.float(), meta, self._heads, config.precision(), self._param_list(), rows)
+
+    def forward_stream(self, vertices, counts, rows=None, tail="compute"):
+        """The forward-only edge head called directly, whatever the setting: edge_probs as forward_ragged (counts: a
+        list of host ints) or forward_padded (counts: an integer tensor [B] on the device, never read on the host; `tail`
+        as there) return them, with the edge rows walked in blocks of `rows` (default config.INFER_EDGE_ROWS, a
+        multiple of 8) and no activation kept.  No autograd graph is recorded.  It has no dropout: ValueError while a
+        dropout probability is active (train mode with p > 0)."""
+        if any(self._dropout_ps()):
+            raise ValueError("EdgePredictor.forward_stream: the forward-only path has no dropout; call eval() or set every "
+                             "dropout probability of the edge head to 0")
+        if torch.is_tensor(counts):
+            return self._edge_stream(vertices, self._padded_meta(vertices, counts, tail, "forward_stream"), rows)
+        return self._edge_stream(vertices, ops.EdgeMeta.get(self._ragged_counts(vertices, counts, "forward_stream"),
+                                                            vertices.device), rows)
 
     def _dropout(self, device):
         ps = self._dropout_ps()
@@ -103,16 +145,12 @@ class EdgePredictor(nn.Module):
         to tail="compute".  It applies where the edge MLP runs on the split route (precision "bf16x3" / "bf16", enough
         rows, a row total B*V(V-1)/2 that is a multiple of 8, a logits layer the row-dot kernel takes, as the default
         hidden_dim = 512); elsewhere the tail is computed."""
-        if tail not in ("compute", "skip"):
-            raise ValueError("forward_padded: tail must be 'compute' or 'skip'")
-        B, V, _ = vertices.shape
-        if not torch.is_tensor(counts) or counts.dim() != 1 or counts.shape[0] != B:
-            raise ValueError(f"forward_padded: counts must be a 1-D tensor of {B} counts")
-        if counts.dtype.is_floating_point or counts.dtype.is_complex:
-            raise ValueError("forward_padded: counts must be integers")
-        meta = ops.EdgeMeta.device(counts.to(device=vertices.device, dtype=torch.int64).contiguous(), B, V, tail=tail)
-        ps, seed = self._dropout(vertices.device)
-        probs = EdgeFn.apply(vertices.float(), meta, self._heads, ps, seed, config.precision(), *self._param_list())
+        meta = self._padded_meta(vertices, counts, tail, "forward_padded")
+        if self._stream():
+            probs = self._edge_stream(vertices, meta)
+        else:
+            ps, seed = self._dropout(vertices.device)
+            probs = EdgeFn.apply(vertices.float(), meta, self._heads, ps, seed, config.precision(), *self._param_list())
         return (probs, meta.counts, meta.width) if return_layout else probs
 
     def forward(self, vertices):

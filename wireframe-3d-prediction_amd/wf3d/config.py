@@ -28,6 +28,15 @@ inference
              INFER_ROWS, keeps nothing for a backward and pools the blocks as they pass.  With grad mode on nothing
              changes; the module's train() / eval() mode does not enter the decision.
 Environment override: WF3D_INFERENCE.
+
+edge_inference
+    "train" (default): the edge head's forward under torch.no_grad() is EdgeFn's, which holds every edge-row tensor
+             (4,608 B per edge row at hidden_dim = 512) until it returns.
+    "stream": with grad mode off and no dropout probability active (eval(), or set_dropout(0)), EdgePredictor.forward /
+             forward_ragged / forward_padded take the forward-only path (wf3d.infer.edge_stream): the edge rows are walked
+             in blocks of INFER_EDGE_ROWS and nothing per edge row outlives its block.  With grad mode on, or with dropout
+             active, nothing changes.  A setting of its own: "inference" above keeps meaning the encoder stage alone.
+Environment override: WF3D_EDGE_INFERENCE.
 """
 import os
 
@@ -65,6 +74,32 @@ if _inference not in INFERENCES:
 # behind the training forward at 1/7 of its peak memory.  8192 rows (z plus h of the 2048-wide layer = 128 MiB, half of
 # the Infinity Cache) measured 42 % behind: per block, the GEMMs have too few tiles and the host too many launches.
 INFER_ROWS = 32768
+
+
+EDGE_INFERENCES = ("train", "stream")
+_edge_inference = os.environ.get("WF3D_EDGE_INFERENCE", "train")
+if _edge_inference not in EDGE_INFERENCES:
+    raise RuntimeError(f"WF3D_EDGE_INFERENCE={_edge_inference!r}: expected 'train' or 'stream'")
+
+# Edge rows per block of the forward-only edge head (a positive multiple of 256, the extent of a live-row count;
+# wf3d.infer.edge_stream).  Chosen by measurement ("Forward only, edge head";
+# profiles/r12_edge_inference.jsonl): the fastest fixed height of the sweep 8192 .. 131072 at the edge shapes of cfg2
+# (64,512 rows: one block, 4 % ahead of the training forward) and of cfg5 (1,044,480 rows: 3.25 ms against 3.05 / 3.13 ms).
+# At cfg5 NO height matches the training forward within its run-to-run spread (2.7 %): this one is 4 - 7 % behind it at
+# 1/7.7 of its peak memory (648 MB against 5.0 GB), so the path ships on footprint.  Smaller blocks cost host time, not
+# GPU time: five launches per block at ~16 us each (65536: +8 %, 1/14.5; 32768: +40 %, 1/26; 8192: 3.4 x the time).
+INFER_EDGE_ROWS = 131072
+
+
+def edge_inference():
+    return _edge_inference
+
+
+def set_edge_inference(mode):
+    global _edge_inference
+    if mode not in EDGE_INFERENCES:
+        raise ValueError("edge_inference must be 'train' or 'stream'")
+    _edge_inference = mode
 
 
 def inference():

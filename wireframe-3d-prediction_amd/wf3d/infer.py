@@ -1,4 +1,5 @@
-"""The forward-only path of the per-point encoder: no autograd Function, nothing kept for a backward.
+"""The forward-only paths of the per-point encoder (encoder_stream) and of the edge head (edge_stream): no autograd
+Function, nothing kept for a backward.
 
 The training forward (functional._encoder_forward_rows) keeps every layer's pre-LayerNorm z and every sx8 operand h
 until it returns, and writes mu, rs, the arg-max rows and the whole point_features tensor: 18.4 KB + 18.4 KB + 2 KB per
@@ -10,12 +11,16 @@ allocated does not grow with the row count, apart from the [B, .] results and a 
 for.  The first layer runs without writing z (ops.first_layer_infer).
 
 Opt-in: wf3d.config.set_inference("stream") / WF3D_INFERENCE=stream sends the encoder stage of the drop-in classes here
-when grad mode is off; PointNetEncoder.encode_stream / encode_packed_stream call it directly."""
+when grad mode is off; PointNetEncoder.encode_stream / encode_packed_stream call it directly.
+
+The edge head is the other stage whose activations grow with the batch: 4,608 B per edge row at hidden_dim = 512 on the
+split route.  edge_stream walks the edge rows the same way; its own opt-in is wf3d.config.set_edge_inference("stream") /
+WF3D_EDGE_INFERENCE=stream, and EdgePredictor.forward_stream calls it directly."""
 import torch
 
 from . import config, ops
-from .functional import _SPLIT_PRODUCTS, _encoder_routes
-from .ops import ACT_RELU, NT, Pro
+from .functional import _SPLIT_PRODUCTS, _edge_routes, _encoder_routes
+from .ops import ACT_GELU, ACT_NONE, ACT_RELU, NT, Pro
 
 
 def check_rows(rows):
@@ -116,3 +121,88 @@ def encoder_stream(x2, pools_layout, n_hidden, precision, params, rows=None, wan
                 a, pro = z, Pro(ACT_RELU, mu, rs, g, be)
             pool.fold(z, valid, r0)
         return pool.finish(), pf
+
+
+def edge_stream(verts, meta, heads, precision, params, rows=None):
+    """The forward-only edge head: EdgeFn's forward without dropout, with the edge rows walked in blocks of `rows`
+    (default config.INFER_EDGE_ROWS) through buffers that are allocated once, sized by the block height, and reused.
+    Nothing per edge row outlives its block except its logit (4 B per row).
+
+    verts [B, V, vertex_dim] float32 (a view is fine); meta: an ops.EdgeMeta, host-built or EdgeMeta.device; params as
+    EdgeFn's.  Returns edge_probs [B, meta.max_e], zero padding included, as EdgeFn returns it: bit for bit when one
+    block covers all rows (rows >= meta.Re), within the forward bound at other heights (the GEMMs' split-K plans follow
+    the block's row count).
+
+    The per-vertex section (sum-of-counts rows: vertex_proj, attention, Pa / Pb) runs whole, on EdgeFn's ops in its
+    order.  The routes of the two wide Linears and the logits kernel are decided once, from the row total, as EdgeFn
+    decides them.  A padded layout in tail="skip" mode whose two wide Linears run split and whose logits layer is the
+    row-dot kernel (what functional._edge_live asks of the forward) runs each block under its own live-row count
+    (ops.block_live): a block past the live pair total costs its launches' entry checks and nothing more, and no count
+    is read on the host.  The result equals tail="compute" bit for bit."""
+    if not verts.is_cuda:
+        raise RuntimeError("wf3d: the HIP path needs CUDA (ROCm) tensors; there is no CPU fallback")
+    rows = check_rows(config.INFER_EDGE_ROWS if rows is None else rows)
+    (P0w, P0b, P1g, P1b, P3w, P3b, P4g, P4b, Aw, Ab, Ow, Ob,
+     M0w, M0b, M1g, M1b, M4w, M4b, M5g, M5b, M8w, M8b, M10w, M10b) = params
+    H, dev = P3w.shape[0], verts.device
+    with torch.no_grad():
+        # ---- per-vertex section: functional.EdgeFn._forward, drop p = 0 ----
+        cv = ops.edge_gather_verts(verts, meta)
+        za = ops.gemm(cv, P0w, NT, bias=P0b); sa = ops.row_stats(za)
+        x3 = precision == "bf16x3" and config.EDGE_X3
+        zb = ops.gemm(za, P3w, NT, bias=P3b, pro=Pro(ACT_GELU, sa[0], sa[1], P1g, P1b), x3=x3); sb = ops.row_stats(zb)
+        f = ops.ln_act_apply(zb, sb[0], sb[1], P4g, P4b, ACT_NONE)
+        qkv = ops.gemm(f, Aw, NT, bias=Ab, x3=x3)
+        cx, _lse = ops.attn_fwd(qkv, meta, H, heads)
+        Fm = ops.gemm(cx, Ow, NT, bias=Ob, addend=f, x3=x3)
+        vd = cv.shape[1]
+        Wa, Wb, Wc, Wd = M0w[:, :H], M0w[:, H:2 * H], M0w[:, 2 * H:2 * H + vd], M0w[:, 2 * H + vd:2 * H + 2 * vd]
+        if vd <= 4:
+            Pa = ops.gemm(Fm, Wa, NT, bias=M0b, x3=x3, lowrank=(cv, Wc))
+            Pb = ops.gemm(Fm, Wb, NT, x3=x3, lowrank=(cv, Wd))
+        else:
+            Pa = ops.gemm(Fm, Wa, NT, bias=M0b, x3=x3)
+            ops.gemm(cv, Wc, NT, out=Pa, accumulate=True)
+            Pb = ops.gemm(Fm, Wb, NT, x3=x3)
+            ops.gemm(cv, Wd, NT, out=Pb, accumulate=True)
+        del za, sa, zb, sb, f, qkv, cx, _lse, Fm
+        # ---- edge-row section: decided once, from the row total; a short last block flips nothing ----
+        npr = _SPLIT_PRODUCTS.get(precision, 3)
+        routes = _edge_routes(meta.Re, H, precision, x3)
+        split = routes[0].fwd == "split"
+        rowdot = M10w.shape[0] == 1 and M10w.is_contiguous() and ops.rowdot_act_shape_ok(H // 4)
+        # functional._edge_live's conditions on the forward launches (its wgrad condition is about backward kernels): every
+        # launch of the loop below then honours the count; on any other route the tail is computed, as EdgeFn does
+        live = meta.live if (meta.padded and meta.tail == "skip" and split and routes[1].fwd == "split" and rowdot) else None
+        plan = block_plan(meta.Re, rows)
+        R = plan[0][1] if plan else 0
+        f32 = dict(dtype=torch.float32, device=dev)
+        logit = torch.empty(meta.Re, 1, **f32)
+        z2, z3 = torch.empty(R, H // 2, **f32), torch.empty(R, H // 4, **f32)
+        if split:
+            h1, h2 = torch.empty(R, H, **f32), torch.empty(R, H // 2, **f32)
+            (M4s, _), (M8s, _) = ops.split_weights([M4w, M8w])
+        else:
+            pre = torch.empty(R, H, **f32)
+        rowbuf = torch.empty(2, max(R, 1), **f32)            # mu / rs of the layer at hand (launches run in stream order)
+        fused_tail = ops.rowdot_act_ok(z3, M10w)
+        assert fused_tail or live is None
+        blive = ops.block_live(live, rows, meta.Re, len(plan)) if live is not None else None
+        for k, (e0, n) in enumerate(plan):
+            mu, rs = rowbuf[0, :n], rowbuf[1, :n]
+            with ops.live_rows(blive[k:k + 1] if blive is not None else None):
+                if split:
+                    ops.edge_pair_infer(Pa, Pb, cv, M0w, meta, e0, n, h1[:n], ln=(M1g, M1b, ACT_GELU))
+                    ops.gemm_split(h1[:n], M4s, bias=M4b, out=z2[:n], products=npr)
+                    ops.ln_prep(z2[:n], M5g, M5b, ACT_GELU, out=(mu, rs, h2[:n]))
+                    ops.gemm_split(h2[:n], M8s, bias=M8b, out=z3[:n], products=npr)
+                else:
+                    ops.edge_pair_infer(Pa, Pb, cv, M0w, meta, e0, n, (pre[:n], mu, rs))
+                    ops.gemm(pre[:n], M4w, NT, bias=M4b, pro=Pro(ACT_GELU, mu, rs, M1g, M1b), x3=x3, out=z2[:n])
+                    ops.row_stats(z2[:n], out=(mu, rs))
+                    ops.gemm(z2[:n], M8w, NT, bias=M8b, pro=Pro(ACT_GELU, mu, rs, M5g, M5b), x3=x3, out=z3[:n])
+                if fused_tail:
+                    ops.rowdot_act(z3[:n], M10w, M10b, ACT_GELU, out=logit[e0:e0 + n])
+                else:
+                    ops.gemm(z3[:n], M10w, NT, bias=M10b, pro=Pro(ACT_GELU), out=logit[e0:e0 + n])
+        return ops.edge_prob_fwd(logit, meta)

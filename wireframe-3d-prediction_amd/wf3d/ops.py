@@ -277,11 +277,15 @@ def rowdot_act_shape_ok(D):
     return bool(_lib.load().wf3d_rowdot_act_ok(D))
 
 
-def rowdot_act(z, W, bias, act):
-    """[R, 1] = act(z) @ W^T + bias for a one-output Linear W [1, D]."""
-    _need_cuda(z, W, bias)
+def rowdot_act(z, W, bias, act, out=None):
+    """[R, 1] = act(z) @ W^T + bias for a one-output Linear W [1, D].  out: a contiguous float32 buffer of R elements to
+    write instead of a new one."""
+    _need_cuda(z, W, bias, out)
     R, D = z.shape
-    out = torch.empty(R, 1, dtype=torch.float32, device=z.device)
+    if out is None:
+        out = torch.empty(R, 1, dtype=torch.float32, device=z.device)
+    elif out.dtype != torch.float32 or out.numel() != R or not out.is_contiguous():
+        raise RuntimeError(f"wf3d.rowdot_act: out must be a contiguous float32 buffer of {R} elements")
     check(_lib.load().wf3d_rowdot_act(_p(z), R, D, _p(W), _p(bias), act, _p(out), _stream()), "rowdot_act")
     return out
 
@@ -853,6 +857,55 @@ def edge_pair_fwd(Pa, Pb, cv, W0, meta, eps=LN_EPS, ln=None, keep_pre=True):
                                             _p(gamma), _p(beta), act, float(drop_p), int(seed) & 0xFFFFFFFF, _p(h),
                                             _stream()), "edge_pair_fwd_ln")
     return pre, mu, rs, delta, h
+
+
+def edge_pair_infer(Pa, Pb, cv, W0, meta, e0, n, out, ln=None, eps=LN_EPS):
+    """The pair combine of edge rows [e0, e0 + n) of the layout into block buffers indexed by e - e0 (forward-only path;
+    include/wf3d.h, "PAIR COMBINE OF A BLOCK"): the rows of edge_pair_fwd bit for bit, without dropout, delta or any store
+    that only a backward reads.  e0: a multiple of 8.
+    ln = (gamma, beta, act): out = h [n, H], which receives act(LayerNorm(pre)) as an sx8 operand; returns h.
+    ln = None: out = (pre [n, H], mu [n], rs [n]); returns them."""
+    _need_cuda(Pa, Pb, cv, W0)
+    H = Pa.shape[1]
+    e0, n = int(e0), int(n)
+    if e0 < 0 or n < 0 or e0 + n > meta.Re:
+        raise RuntimeError(f"wf3d.edge_pair_infer: rows [{e0}, {e0 + n}) are not inside the layout's {meta.Re} edge rows")
+    wd, stride = _wdelta(W0, H)
+
+    def buf(t, what):
+        _need_cuda(t)
+        if t.dtype != torch.float32 or tuple(t.shape) != (n, H) or not t.is_contiguous():
+            raise RuntimeError(f"wf3d.edge_pair_infer: {what} must be a contiguous float32 [{n}, {H}]")
+        return t
+    if ln is not None:
+        gamma, beta, act = ln
+        _need_cuda(gamma, beta)
+        pre = mu = rs = None
+        h = buf(out, "out h")
+    else:
+        gamma = beta = h = None
+        act = ACT_NONE
+        pre, mu, rs = out
+        buf(pre, "out pre")
+        _row_bufs("edge_pair_infer", n, mu, rs)
+    check(_lib.load().wf3d_edge_pair_infer(_p(Pa), _p(Pb), _p(cv), _p(wd), stride, _p(meta.voff), _p(meta.eoff),
+                                           _p(meta.esample), e0, n, H, cv.shape[1], eps, _p(gamma), _p(beta), act,
+                                           _p(pre), _p(mu), _p(rs), _p(h), _stream()), "edge_pair_infer")
+    return out
+
+
+def block_live(total, rows, Re, nblocks):
+    """int32 [nblocks]: the live rows of each block of a walk of Re rows in blocks of `rows`, from the live total `total`
+    (a one-element int32 device tensor, EdgeMeta.live), which is not read on the host."""
+    _need_cuda(total)
+    if total.dtype != torch.int32 or total.numel() != 1:
+        raise RuntimeError("wf3d.block_live: needs a one-element int32 device tensor")
+    rows, Re, nblocks = int(rows), int(Re), int(nblocks)
+    if rows <= 0 or Re < 0 or nblocks < 0:
+        raise ValueError(f"wf3d.block_live: bad dims rows={rows} Re={Re} nblocks={nblocks}")
+    blive = torch.empty(nblocks, dtype=torch.int32, device=total.device)
+    check(_lib.load().wf3d_block_live(_p(total), rows, Re, nblocks, _p(blive), _stream()), "block_live")
+    return blive
 
 
 def edge_pair_ln_bwd(dh, Pa, Pb, delta, W0, meta, mu, rs, gamma, beta, act, drop_p=0.0, seed=0):
