@@ -748,11 +748,33 @@ long wf3d_parse_table(const char* path, double* out, long max_vals, long* ncols)
  * verts strides in floats (the `vertices` output is a view).  Entries e >= E_s are left untouched.
  * wf3d_hausdorff_lines: out[n, m] = max(h(P_n, T_m), h(T_m, P_n)) over `sample_points` (<= 32) equidistant points per
  * segment, point k = start + w_k * diff with np.linspace's weights; float64.
+ *
+ * wf3d_edge_compact: the same selection as a stable stream compaction, so that what the host reads scales with the KEPT
+ * edges.  Candidate e of sample s is kept iff e < c_s (c_s - 1) / 2, e < max_e and probs[s, e] > threshold (a NaN or a
+ * value equal to the threshold is not kept), c_s = counts[s] clamped to 0 .. V.  koff[B + 1] = exclusive prefix of the
+ * per-sample kept counts (koff[B] = K); packed over k in [0, K), in sample order and within a sample in increasing e:
+ * pairs[k] = (i, j), i < j; seg[k] = the two end points, higher z first (equal z: vertex j first); kprob[k] = the
+ * probability.  pairs / seg / kprob hold B * max_e rows (the worst case); rows k >= K are left untouched.  Three
+ * launches (kept count per 256-candidate chunk, one scan over the B * ceil(max_e / 256) chunk counts, placement by wave
+ * ballot ranks): no atomics, the same bits on every run.  ws: wf3d_edge_compact_ws_bytes(B, max_e) bytes.
+ * B <= 65535 and B * max_e < 2^31, else WF3D_ERR_UNSUPPORTED; B = 0, V < 2 or max_e = 0 write koff = 0 and launch nothing.
+ * wf3d_hausdorff_lines_batch: the [n_s, m_s] matrices of wf3d_hausdorff_lines for every sample of a batch in one launch,
+ * n_s = koff[s + 1] - koff[s] predicted segments of seg [K, 2, 3] (wf3d_edge_compact's) against m_s = loff[s + 1] -
+ * loff[s] label segments of lseg [L, 2, 3], both float32: diff = end - start is an fp32 subtraction (the common dtype
+ * of float32 predictions and labels), widened to float64 afterwards.  Sample s's matrix is written row-major at
+ * out + ooff[s]; ooff[B + 1] = exclusive prefix of n_s * m_s (the caller's, device memory), max_pairs = max_s n_s * m_s
+ * sizes the grid.  Samples with n_s * m_s = 0 write nothing.  B <= 65535.
  * ------------------------------------------------------------------------ */
 int wf3d_edge_endpoints(const float* verts, long sample_stride, long vertex_stride, const int32_t* counts, const float* probs,
                         int B, int V, int max_e, float threshold, float* edge_vertices, unsigned char* keep, void* stream);
 int wf3d_hausdorff_lines(const double* p_start, const double* p_diff, const double* t_start, const double* t_diff, int N, int M,
                          int sample_points, double* out, void* stream);
+size_t wf3d_edge_compact_ws_bytes(int B, int max_e);
+int wf3d_edge_compact(const float* verts, long sample_stride, long vertex_stride, const int32_t* counts, const float* probs,
+                      int B, int V, int max_e, float threshold, int32_t* koff, int32_t* pairs, float* seg, float* kprob,
+                      void* ws, size_t ws_bytes, void* stream);
+int wf3d_hausdorff_lines_batch(const float* seg, const int32_t* koff, const float* lseg, const int32_t* loff,
+                               const int64_t* ooff, int B, long max_pairs, int sample_points, double* out, void* stream);
 
 #ifdef __cplusplus
 }

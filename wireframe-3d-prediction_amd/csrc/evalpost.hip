@@ -10,6 +10,12 @@
 //                           at S <= 32 points: one thread per pair, the S x S point distances stay in registers (the
 //                           reference materialises a (20 N) x (20 M) cdist matrix: 310 MB at N = 2016, M = 48).  float64,
 //                           sample points a + w_k * (b - a) with numpy's linspace weights.
+//   compact_{count,scan,place}_kernel   the same selection as a stable stream compaction (wf3d_edge_compact): kept count per
+//                           256-candidate chunk, one exclusive scan over all chunk counts (which also yields the per-sample
+//                           offsets), placement by wave-ballot rank.  The host then reads B + 1 offsets and K packed rows
+//                           instead of B * max_e of them, and never needs the (i, j) index lists.
+//   hausdorff_lines_batch_kernel   every sample's [n_s, m_s] matrix in one launch, from the packed float32 segments that are
+//                           already on the device; the per-pair arithmetic is hausdorff_pair, shared with the kernel above.
 #include "wf3d_common.h"
 
 namespace {
@@ -38,16 +44,12 @@ __global__ __launch_bounds__(256) void edge_endpoints_kernel(const float* __rest
     keep[(size_t)s * max_e + e] = probs[(size_t)s * max_e + e] > thr ? 1 : 0;
 }
 
+// One (query, target) pair: segments a + w * d and b + w * e sampled at S <= SMAX points each; the S x S point distances
+// stay in registers.  Shared by the single-matrix and the batched kernel: the arithmetic is written once.
 template <int SMAX>
-__global__ __launch_bounds__(256) void hausdorff_lines_kernel(const double* __restrict__ pa, const double* __restrict__ pd,
-                                                               const double* __restrict__ ta, const double* __restrict__ td,
-                                                               int N, int M, int S, double* __restrict__ out) {
-    const long idx = (long)blockIdx.x * 256 + threadIdx.x;
-    if (idx >= (long)N * M) return;
-    const int n = (int)(idx / M), m = (int)(idx - (long)n * M);
+__device__ __forceinline__ double hausdorff_pair(double ax, double ay, double az, double dx, double dy, double dz, double bx,
+                                                 double by, double bz, double ex, double ey, double ez, int S) {
     const double step = S > 1 ? 1.0 / (double)(S - 1) : 0.0;
-    const double ax = pa[n * 3], ay = pa[n * 3 + 1], az = pa[n * 3 + 2], dx = pd[n * 3], dy = pd[n * 3 + 1], dz = pd[n * 3 + 2];
-    const double bx = ta[m * 3], by = ta[m * 3 + 1], bz = ta[m * 3 + 2], ex = td[m * 3], ey = td[m * 3 + 1], ez = td[m * 3 + 2];
     double tmin[SMAX];
 #pragma unroll
     for (int j = 0; j < SMAX; ++j) tmin[j] = INFINITY;
@@ -72,7 +74,133 @@ __global__ __launch_bounds__(256) void hausdorff_lines_kernel(const double* __re
 #pragma unroll
     for (int j = 0; j < SMAX; ++j)
         if (j < S) h_tp = fmax(h_tp, tmin[j]);
-    out[idx] = fmax(h_pt, h_tp);
+    return fmax(h_pt, h_tp);
+}
+
+template <int SMAX>
+__global__ __launch_bounds__(256) void hausdorff_lines_kernel(const double* __restrict__ pa, const double* __restrict__ pd,
+                                                               const double* __restrict__ ta, const double* __restrict__ td,
+                                                               int N, int M, int S, double* __restrict__ out) {
+    const long idx = (long)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= (long)N * M) return;
+    const int n = (int)(idx / M), m = (int)(idx - (long)n * M);
+    out[idx] = hausdorff_pair<SMAX>(pa[n * 3], pa[n * 3 + 1], pa[n * 3 + 2], pd[n * 3], pd[n * 3 + 1], pd[n * 3 + 2], ta[m * 3],
+                                    ta[m * 3 + 1], ta[m * 3 + 2], td[m * 3], td[m * 3 + 1], td[m * 3 + 2], S);
+}
+
+// blockIdx.y = sample, blockIdx.x over the largest n_s * m_s of the batch; float32 end points, direction = an fp32
+// subtraction widened afterwards (what numpy's concatenate-then-subtract gives for float32 predictions and labels).
+template <int SMAX>
+__global__ __launch_bounds__(256) void hausdorff_lines_batch_kernel(const float* __restrict__ seg, const int32_t* __restrict__ koff,
+                                                                     const float* __restrict__ lseg, const int32_t* __restrict__ loff,
+                                                                     const int64_t* __restrict__ ooff, int S, double* __restrict__ out) {
+    const int s = blockIdx.y;
+    const int k0 = koff[s], l0 = loff[s];
+    const long N = koff[s + 1] - k0, M = loff[s + 1] - l0;
+    const long idx = (long)blockIdx.x * 256 + threadIdx.x;
+    if (N <= 0 || M <= 0 || idx >= N * M) return;
+    const long n = idx / M, m = idx - n * M;
+    const float* p = seg + (k0 + n) * 6;
+    const float* t = lseg + (l0 + m) * 6;
+    const float dx = p[3] - p[0], dy = p[4] - p[1], dz = p[5] - p[2];
+    const float ex = t[3] - t[0], ey = t[4] - t[1], ez = t[5] - t[2];
+    out[ooff[s] + idx] = hausdorff_pair<SMAX>((double)p[0], (double)p[1], (double)p[2], (double)dx, (double)dy, (double)dz,
+                                              (double)t[0], (double)t[1], (double)t[2], (double)ex, (double)ey, (double)ez, S);
+}
+
+// ---- stable compaction of the kept candidate edges ---------------------------------------------------------------------
+// A chunk is the 256 candidates of one workgroup: 4 waves of 64, each lane one candidate.  The kept flag is the same
+// expression in the count and in the placement pass.
+constexpr int CHUNK = 256, SCAN_TILE = 1024;
+
+__device__ __forceinline__ int clamp_count(int c, int V) { return min(max(c, 0), V); }
+
+__device__ __forceinline__ bool edge_kept(const float* __restrict__ probs, int s, int e, int c, int max_e, float thr) {
+    const long E = (long)c * (c - 1) / 2;
+    return e < max_e && (long)e < E && probs[(size_t)s * max_e + e] > thr;          // NaN > thr is false
+}
+
+// kept lanes of this wave below this lane, and in the whole wave (wave64: the ballot is 64 bits wide)
+__device__ __forceinline__ int wave_rank(bool kept, int lane, int& total) {
+    const unsigned long long b = __ballot(kept);
+    total = __popcll(b);
+    return __popcll(b & ((1ull << lane) - 1ull));
+}
+
+__global__ __launch_bounds__(CHUNK) void compact_count_kernel(const int32_t* __restrict__ counts, const float* __restrict__ probs,
+                                                              int max_e, int V, float thr, int32_t* __restrict__ chunk_cnt) {
+    __shared__ int wsum[CHUNK / 64];
+    const int s = blockIdx.y, e = blockIdx.x * CHUNK + threadIdx.x;
+    int total;
+    wave_rank(edge_kept(probs, s, e, clamp_count(counts[s], V), max_e, thr), threadIdx.x & 63, total);
+    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = total;
+    __syncthreads();
+    if (threadIdx.x == 0) chunk_cnt[(size_t)s * gridDim.x + blockIdx.x] = wsum[0] + wsum[1] + wsum[2] + wsum[3];
+}
+
+// One workgroup walks the T = B * nchunk chunk counts in tiles of SCAN_TILE and turns them into their exclusive prefix in
+// place; the entry of a sample's first chunk is that sample's koff.
+__global__ __launch_bounds__(SCAN_TILE) void compact_scan_kernel(int32_t* __restrict__ chunk, int T, int nchunk, int B,
+                                                                 int32_t* __restrict__ koff) {
+    __shared__ int wtot[SCAN_TILE / 64];
+    __shared__ int carry_s;
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    if (threadIdx.x == 0) carry_s = 0;
+    __syncthreads();
+    for (int base = 0; base < T; base += SCAN_TILE) {
+        const int t = base + threadIdx.x;
+        const int v = t < T ? chunk[t] : 0;
+        int inc = v;                                             // inclusive scan inside the wave
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) {
+            const int up = __shfl_up(inc, o, 64);
+            if (lane >= o) inc += up;
+        }
+        if (lane == 63) wtot[w] = inc;
+        const int carry = carry_s;
+        __syncthreads();
+        int before = 0;                                          // kept edges of this tile's earlier waves
+        for (int k = 0; k < w; ++k) before += wtot[k];
+        const int excl = carry + before + inc - v;
+        if (t < T) {
+            chunk[t] = excl;
+            if (t % nchunk == 0) koff[t / nchunk] = excl;
+        }
+        __syncthreads();
+        if (threadIdx.x == SCAN_TILE - 1) carry_s = excl + v;
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) koff[B] = carry_s;
+}
+
+__global__ __launch_bounds__(CHUNK) void compact_place_kernel(const float* __restrict__ verts, long sstride, long vstride,
+                                                              const int32_t* __restrict__ counts, const float* __restrict__ probs,
+                                                              int max_e, int V, float thr, const int32_t* __restrict__ chunk_off,
+                                                              int32_t* __restrict__ pairs, float* __restrict__ seg,
+                                                              float* __restrict__ kprob) {
+    __shared__ int wsum[CHUNK / 64];
+    const int s = blockIdx.y, e = blockIdx.x * CHUNK + threadIdx.x;
+    const int c = clamp_count(counts[s], V);
+    const bool kept = edge_kept(probs, s, e, c, max_e, thr);
+    int total;
+    const int rank = wave_rank(kept, threadIdx.x & 63, total);
+    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = total;
+    __syncthreads();
+    if (!kept) return;
+    int pos = chunk_off[(size_t)s * gridDim.x + blockIdx.x] + rank;
+    for (int k = 0; k < (int)(threadIdx.x >> 6); ++k) pos += wsum[k];
+    int i, j;
+    edge_ij(e, c, i, j);                                         // float estimate, integer fix-up: exact
+    const float* vi = verts + s * sstride + i * vstride;
+    const float* vj = verts + s * sstride + j * vstride;
+    const bool i_first = vi[2] > vj[2];
+    const float* a = i_first ? vi : vj;
+    const float* b = i_first ? vj : vi;
+    float* o = seg + (size_t)pos * 6;
+    o[0] = a[0]; o[1] = a[1]; o[2] = a[2]; o[3] = b[0]; o[4] = b[1]; o[5] = b[2];
+    pairs[(size_t)pos * 2] = i;
+    pairs[(size_t)pos * 2 + 1] = j;
+    kprob[pos] = probs[(size_t)s * max_e + e];
 }
 
 }  // namespace
@@ -98,6 +226,59 @@ extern "C" int wf3d_hausdorff_lines(const double* p_start, const double* p_diff,
     WF3D_CHECK(p_start && p_diff && t_start && t_diff && out, WF3D_ERR_ARG, "wf3d_hausdorff_lines: null pointer");
     hipLaunchKernelGGL(hausdorff_lines_kernel<32>, dim3(wf3d_cdiv((long)N * M, 256)), dim3(256), 0, (hipStream_t)stream, p_start,
                        p_diff, t_start, t_diff, N, M, sample_points, out);
+    WF3D_LAUNCH_CHECK();
+    return WF3D_OK;
+}
+
+extern "C" size_t wf3d_edge_compact_ws_bytes(int B, int max_e) {
+    if (B <= 0 || max_e <= 0) return 0;
+    return (size_t)B * (size_t)wf3d_cdiv(max_e, CHUNK) * sizeof(int32_t);
+}
+
+extern "C" int wf3d_edge_compact(const float* verts, long sample_stride, long vertex_stride, const int32_t* counts,
+                                 const float* probs, int B, int V, int max_e, float threshold, int32_t* koff, int32_t* pairs,
+                                 float* seg, float* kprob, void* ws, size_t ws_bytes, void* stream) {
+    WF3D_CHECK(B >= 0 && V >= 0 && max_e >= 0, WF3D_ERR_ARG, "wf3d_edge_compact: bad dims");
+    WF3D_CHECK(koff, WF3D_ERR_ARG, "wf3d_edge_compact: null koff");
+    WF3D_CHECK(B <= 65535, WF3D_ERR_UNSUPPORTED, "wf3d_edge_compact: B > 65535 (got %d)", B);
+    WF3D_CHECK((long)B * max_e < (1L << 31), WF3D_ERR_UNSUPPORTED, "wf3d_edge_compact: B * max_e >= 2^31 (B %d, max_e %d)", B,
+               max_e);
+    hipStream_t st = (hipStream_t)stream;
+    if (B == 0 || V < 2 || max_e == 0) {
+        if (hipMemsetAsync(koff, 0, (size_t)(B + 1) * sizeof(int32_t), st) != hipSuccess) {
+            (void)hipGetLastError();
+            WF3D_CHECK(false, WF3D_ERR_LAUNCH, "wf3d_edge_compact: clearing koff failed");
+        }
+        return WF3D_OK;
+    }
+    WF3D_CHECK(verts && counts && probs && pairs && seg && kprob, WF3D_ERR_ARG, "wf3d_edge_compact: null pointer");
+    WF3D_CHECK(ws && ws_bytes >= wf3d_edge_compact_ws_bytes(B, max_e), WF3D_ERR_ARG,
+               "wf3d_edge_compact: workspace of %zu bytes, %zu needed", ws_bytes, wf3d_edge_compact_ws_bytes(B, max_e));
+    const int nchunk = wf3d_cdiv(max_e, CHUNK);
+    int32_t* chunk = (int32_t*)ws;
+    hipLaunchKernelGGL(compact_count_kernel, dim3(nchunk, B), dim3(CHUNK), 0, st, counts, probs, max_e, V, threshold, chunk);
+    WF3D_LAUNCH_CHECK();
+    hipLaunchKernelGGL(compact_scan_kernel, dim3(1), dim3(SCAN_TILE), 0, st, chunk, B * nchunk, nchunk, B, koff);
+    WF3D_LAUNCH_CHECK();
+    hipLaunchKernelGGL(compact_place_kernel, dim3(nchunk, B), dim3(CHUNK), 0, st, verts, sample_stride, vertex_stride, counts,
+                       probs, max_e, V, threshold, chunk, pairs, seg, kprob);
+    WF3D_LAUNCH_CHECK();
+    return WF3D_OK;
+}
+
+extern "C" int wf3d_hausdorff_lines_batch(const float* seg, const int32_t* koff, const float* lseg, const int32_t* loff,
+                                          const int64_t* ooff, int B, long max_pairs, int sample_points, double* out,
+                                          void* stream) {
+    WF3D_CHECK(sample_points >= 1 && sample_points <= 32, WF3D_ERR_UNSUPPORTED,
+               "wf3d_hausdorff_lines_batch: 1..32 sample points per segment (got %d)", sample_points);
+    WF3D_CHECK(B >= 0 && max_pairs >= 0, WF3D_ERR_ARG, "wf3d_hausdorff_lines_batch: bad dims");
+    WF3D_CHECK(B <= 65535, WF3D_ERR_UNSUPPORTED, "wf3d_hausdorff_lines_batch: B > 65535 (got %d)", B);
+    WF3D_CHECK((max_pairs + 255) / 256 < (1L << 31), WF3D_ERR_UNSUPPORTED, "wf3d_hausdorff_lines_batch: max_pairs %ld too large",
+               max_pairs);
+    if (B == 0 || max_pairs == 0) return WF3D_OK;
+    WF3D_CHECK(seg && koff && lseg && loff && ooff && out, WF3D_ERR_ARG, "wf3d_hausdorff_lines_batch: null pointer");
+    hipLaunchKernelGGL(hausdorff_lines_batch_kernel<32>, dim3(wf3d_cdiv(max_pairs, 256), B), dim3(256), 0, (hipStream_t)stream,
+                       seg, koff, lseg, loff, ooff, sample_points, out);
     WF3D_LAUNCH_CHECK();
     return WF3D_OK;
 }

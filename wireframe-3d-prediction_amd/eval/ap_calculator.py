@@ -118,9 +118,10 @@ class APCalculator(object):
                         "corners_recall": 0, "corner_f1": 0, "edges_precision": 0, "edges_recall": 0, "edges_f1": 0}
 
     # -- one sample ----------------------------------------------------------------------------------------------
-    def _with_edges(self, corners, edges, edge_pts, gt_corners_all, gt_edges, gt_edge_pts):
+    def _with_edges(self, corners, edges, edge_pts, gt_corners_all, gt_edges, gt_edge_pts, hd=None):
         thr = self.distance_thresh
-        hd = hausdorff_distance_line(edge_pts, gt_edge_pts)
+        if hd is None:
+            hd = hausdorff_distance_line(edge_pts, gt_edge_pts)
         pi, li = linear_sum_assignment(hd)
         ok = hd[pi, li] <= thr
         pr_c, gt_c = edge_pts[pi[ok]], gt_edge_pts[li[ok]]
@@ -151,14 +152,18 @@ class APCalculator(object):
 
     def compute_metrics(self, batch):
         """batch: predicted_vertices [B, V, 3], predicted_edges [B, E, 2], pred_edges_vertices [B, E, 2, 3] and the
-        labels wf_vertices, wf_edges, wf_edges_vertices (reference :121-272); accumulates into self.ap_dict."""
+        labels wf_vertices, wf_edges, wf_edges_vertices (reference :121-272); accumulates into self.ap_dict.
+        Optional batch["hausdorff"]: per sample an [E, M] float64 Hausdorff matrix of its predicted against its label
+        edges computed elsewhere (wf3d.postprocess.evaluate_batch(compact=True): one launch per batch), or None to have
+        hausdorff_distance_line compute it as without the key."""
         self.batch_size = len(batch["predicted_vertices"])
+        given = batch.get("hausdorff")
         for b in range(self.batch_size):
             corners, edges = batch["predicted_vertices"][b], batch["predicted_edges"][b]
             args = (batch["wf_vertices"][b], batch["wf_edges"][b])
             if len(edges) != 0:
                 counts, dist, wed = self._with_edges(corners, edges, batch["pred_edges_vertices"][b], args[0], args[1],
-                                                     batch["wf_edges_vertices"][b])
+                                                     batch["wf_edges_vertices"][b], None if given is None else given[b])
             else:       # corners without any edge: an empty model
                 counts, dist, wed = self._corners_only(corners, *args)
             for k, v in counts.items():

@@ -3,6 +3,11 @@
     samples = wireframes_from_predictions(model(x))        # ONE kernel + ONE device->host copy for the whole batch
     evaluate_batch(predictions, wf_vertices, wf_edges, ap_calculator)      # the reference's per-sample loop, fed from it
 
+Opt-in, for evaluating a data set: device work and host traffic that scale with the KEPT edges, not with V^2.
+
+    samples = wireframes_compact(model(x))                 # compaction on the device; B + 1 offsets, then K packed rows
+    evaluate_batch(..., compact=True)                      # + all Hausdorff matrices of the batch from one launch
+
 `hausdorff_lines` is the device form of eval.ap_calculator.hausdorff_distance_line (csrc/evalpost.hip)."""
 import numpy as np
 import torch
@@ -69,9 +74,118 @@ def _gt_edge_vertices(gt_vertices, gt_edges):
     return ev[np.arange(ev.shape[0])[:, np.newaxis], np.flip(np.argsort(ev[:, :, -1]), axis=1)]
 
 
-def evaluate_batch(predictions, wf_vertices, wf_edges, ap_calculator, threshold=0.5):
+def wireframes_compact(predictions, threshold=0.5, keep_device=False):
+    """wireframes_from_predictions with the kept edges compacted on the device (wf3d_edge_compact): the same list of
+    per-sample dicts (equal values, dtypes and shapes, the empty (0, 2) / (0, 2, 3) included) plus `pd_edge_probs`
+    float32 [k].  The host reads the B + 1 offsets `koff` (the one extra synchronisation), then one buffer of the
+    vertices and the first K = koff[B] packed rows: 12 B V + 36 K bytes instead of B (3 V + 7 max_e) 4.
+    The contents of `edge_indices` are never touched: with `edge_counts` in the dict (padded edge layout) the counts are
+    that device tensor and nothing of it is read on the host; otherwise each count comes from len(edge_indices[s]).
+    keep_device=True: returns (samples, {"koff": int32 [B + 1], "seg": float32 [B * max_e, 2, 3] (first K rows valid),
+    "koff_host": numpy int32 [B + 1]}) — the device tensors wf3d_hausdorff_lines_batch takes."""
+    verts, probs = predictions["vertices"], predictions["edge_probs"]
+    B, V, _ = verts.shape
+    max_e = probs.shape[1]
+    dev = verts.device
+    if predictions.get("edge_counts") is not None:
+        cnt = predictions["edge_counts"].detach().to(device=dev, dtype=torch.int32)
+    else:
+        lens = [len(e) for e in predictions["edge_indices"]]
+        cnt = torch.tensor([int(round((1 + (1 + 8 * n) ** 0.5) / 2)) if n else 0 for n in lens], dtype=torch.int32).to(dev)
+    v = verts.detach().float()
+    if v.stride(2) != 1:
+        v = v.contiguous()
+    pr = probs.detach().float().contiguous()
+    lib = _lib.load()
+    cap = B * max_e
+    koff = torch.empty(B + 1, dtype=torch.int32, device=dev)
+    pairs = torch.empty(cap, 2, dtype=torch.int32, device=dev)
+    seg = torch.empty(cap, 2, 3, dtype=torch.float32, device=dev)
+    kprob = torch.empty(cap, dtype=torch.float32, device=dev)
+    ws_bytes = lib.wf3d_edge_compact_ws_bytes(B, max_e)
+    ws = torch.empty(max(ws_bytes // 4, 1), dtype=torch.int32, device=dev)
+    check(lib.wf3d_edge_compact(v.data_ptr(), v.stride(0), v.stride(1), cnt.data_ptr(), pr.data_ptr(), B, V, max_e,
+                                float(threshold), koff.data_ptr(), pairs.data_ptr(), seg.data_ptr(), kprob.data_ptr(),
+                                ws.data_ptr(), ws_bytes, _stream()), "edge_compact")
+    koff_h = koff.cpu().numpy()
+    K = int(koff_h[B])
+    # one packed device->host transfer: vertices | pairs | segments | probabilities, as raw 32-bit words
+    words = torch.cat([v.reshape(-1).view(torch.int32), pairs[:K].reshape(-1), seg[:K].reshape(-1).view(torch.int32),
+                       kprob[:K].view(torch.int32)]).cpu().numpy()
+    nv = B * V * 3
+    pv = words[:nv].view(np.float32).reshape(B, V, 3)
+    pe = words[nv:nv + 2 * K].reshape(K, 2).astype(np.int64)
+    ps = words[nv + 2 * K:nv + 8 * K].view(np.float32).reshape(K, 2, 3)
+    pp = words[nv + 8 * K:].view(np.float32)
+    out = []
+    for s in range(B):
+        a, b = int(koff_h[s]), int(koff_h[s + 1])
+        out.append({"pred_vertices": pv[s].copy(), "pd_edges": pe[a:b].copy(), "pd_edges_vertices": ps[a:b].copy(),
+                    "pd_edge_probs": pp[a:b].copy()})
+    if keep_device:
+        return out, {"koff": koff, "seg": seg, "koff_host": koff_h}
+    return out
+
+
+def _as_numpy(x):
+    return x.numpy() if torch.is_tensor(x) else np.asarray(x)
+
+
+def _evaluate_batch_compact(predictions, wf_vertices, wf_edges, ap_calculator, threshold, sample_points=20):
+    """evaluate_batch on the compacted edges: every sample's Hausdorff matrix from ONE launch over the segments that
+    wireframes_compact left on the device, the label segments uploaded once, the matrices read back in one copy."""
+    samples, d = wireframes_compact(predictions, threshold, keep_device=True)
+    B = len(samples)
+    dev = d["seg"].device
+    n = np.diff(d["koff_host"]).astype(np.int64)
+    gt = []
+    m = np.zeros(B, dtype=np.int64)
+    for s in range(B):
+        gt_v, gt_e = _as_numpy(wf_vertices[s]), _as_numpy(wf_edges[s]).astype(np.int64)
+        gt_ev = _gt_edge_vertices(gt_v, gt_e)
+        gt.append((gt_v, gt_e, gt_ev))
+        if n[s] > 0 and gt_ev.dtype == np.float32:            # else: compute_metrics computes this sample's matrix itself
+            m[s] = gt_ev.shape[0]
+    ooff = np.concatenate(([0], np.cumsum(n * m)))
+    loff = np.concatenate(([0], np.cumsum(m)))
+    hd = [None] * B
+    if ooff[-1] > 0:
+        if loff[-1] >= 2 ** 31:
+            raise ValueError("evaluate_batch(compact=True): more than 2^31 label segments in one batch")
+        lseg = np.concatenate([g[2].reshape(-1) for s, g in enumerate(gt) if m[s] > 0])
+        # one upload: ooff (int64, 8-byte aligned at the front) | loff | label segments, as raw 32-bit words
+        up = torch.from_numpy(np.concatenate((ooff.astype(np.int64).view(np.int32), loff.astype(np.int32),
+                                              lseg.view(np.int32)))).to(dev)
+        n_o = 2 * (B + 1)
+        d_ooff, d_loff, d_lseg = up[:n_o].view(torch.int64), up[n_o:n_o + B + 1], up[n_o + B + 1:].view(torch.float32)
+        out = torch.empty(int(ooff[-1]), dtype=torch.float64, device=dev)
+        check(_lib.load().wf3d_hausdorff_lines_batch(d["seg"].data_ptr(), d["koff"].data_ptr(), d_lseg.data_ptr(),
+                                                     d_loff.data_ptr(), d_ooff.data_ptr(), B, int((n * m).max()),
+                                                     int(sample_points), out.data_ptr(), _stream()), "hausdorff_lines_batch")
+        flat = out.cpu().numpy()
+        hd = [flat[ooff[s]:ooff[s + 1]].reshape(n[s], m[s]) if n[s] * m[s] > 0 else None for s in range(B)]
+    for s, w in enumerate(samples):
+        gt_v, gt_e, gt_ev = gt[s]
+        pd_ev = w["pd_edges_vertices"] if len(w["pd_edges"]) > 0 else np.empty((0, 2, 3))
+        ap_calculator.compute_metrics({"predicted_vertices": w["pred_vertices"][np.newaxis, :],
+                                       "predicted_edges": w["pd_edges"][np.newaxis, :],
+                                       "pred_edges_vertices": pd_ev.reshape((1, -1, 2, 3)),
+                                       "wf_vertices": gt_v[np.newaxis, :],
+                                       "wf_edges": gt_e[np.newaxis, :],
+                                       "wf_edges_vertices": gt_ev.reshape((1, -1, 2, 3)),
+                                       "hausdorff": [hd[s]]})
+
+
+def evaluate_batch(predictions, wf_vertices, wf_edges, ap_calculator, threshold=0.5, compact=False):
     """The body of the reference's evaluation loop (evaluate.py:74-110) for one batch: `wf_vertices` / `wf_edges` are the
-    collate_batch lists of tensors; accumulates into `ap_calculator`."""
+    collate_batch lists of tensors; accumulates into `ap_calculator`.
+    compact=True: the kept edges are compacted on the device (wireframes_compact) and all Hausdorff matrices of the batch
+    come from one launch (wf3d_hausdorff_lines_batch) and one copy each way; `ap_calculator.compute_metrics` receives
+    them as batch["hausdorff"].  Three kinds of sample silently take today's per-sample call instead: one that keeps no
+    edge (the corners-only branch needs no matrix), one whose label has no edge, and one whose label vertices are not
+    float32 (the batched kernel forms the segment directions in float32, which is the common dtype only then)."""
+    if compact:
+        return _evaluate_batch_compact(predictions, wf_vertices, wf_edges, ap_calculator, threshold)
     for s, w in enumerate(wireframes_from_predictions(predictions, threshold)):
         gt_v = wf_vertices[s].numpy() if torch.is_tensor(wf_vertices[s]) else np.asarray(wf_vertices[s])
         gt_e = (wf_edges[s].numpy() if torch.is_tensor(wf_edges[s]) else np.asarray(wf_edges[s])).astype(np.int64)
