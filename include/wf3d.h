@@ -412,18 +412,20 @@ int wf3d_pool4_stream(const float* pf, const float* valid, const int32_t* offset
                       void* state, void* ws, size_t ws_bytes, void* stream);
 int wf3d_pool4_stream_finish(const void* state, const int32_t* offsets, int B, int C, float* mmax, float* mavg,
                              float* umean, float* umax, int ldo, float* cnt, float* nvalid, void* stream);
-/* FIRST LAYER WITHOUT z.  wf3d_first_layer_fwd's shapes (K <= 8, D % 8 == 0, D <= 1024) and arithmetic, in its order:
- * h_sx8 = act(LN(x·W^T + b)) is that entry point's h_sx8 bit for bit; z, mu and rs are not written (2 KB per row at
- * D = 512 that nothing reads without a backward).  It takes no live-row count. */
+/* FIRST LAYER WITHOUT z.  The other instantiation of wf3d_first_layer_fwd's kernel body: its shapes (K <= 8,
+ * D % 8 == 0, D <= 1024), its launch and its arithmetic, so h_sx8 = act(LN(x·W^T + b)) is that entry point's h_sx8 bit
+ * for bit; z, mu and rs are compiled out (2 KB per row at D = 512 that nothing reads without a backward).  It takes no
+ * live-row count. */
 int wf3d_first_layer_infer(const float* x, int R, int K, int ldx, const float* W, int ldw, const float* bias, int D,
                            const float* gamma, const float* beta, int act, float eps, void* h_sx8, void* stream);
 
 /* FORWARD-ONLY edge head (wf3d.infer.edge_stream): the edge rows of a layout are walked in blocks through reused
  * buffers; these are the two pieces the walk needs beyond the training forward's entry points.
  *
- * PAIR COMBINE OF A BLOCK.  wf3d_edge_pair_fwd / _fwd_ln (below, "Edge head") over the edge rows [e0, e0 + n) of the
- * layout, written at the block-local row e - e0, without dropout and without the stores only a backward reads.  Two
- * forms, chosen by the pointers given (anything else is refused):
+ * PAIR COMBINE OF A BLOCK.  The kernel body of wf3d_edge_pair_fwd / _fwd_ln (below, "Edge head"), which walks rows
+ * e0 + l of the layout and writes at row l (those entry points: e0 = 0), over the edge rows [e0, e0 + n), in its
+ * forward-only instantiation: dropout and the stores only a backward reads are compiled out.  Two forms, chosen by the
+ * pointers given (anything else is refused):
  *   h_sx8 alone        h = act(LayerNorm(pre)) [n, H] as the sx8 operand of the next Linear (pre = mu = rs = NULL;
  *                      needs gamma, beta, H % 8 == 0 and 16-byte aligned h_sx8 / gamma / beta)
  *   pre, mu, rs alone  pre [n, H], mu [n], rs [n] (h_sx8 = NULL; gamma, beta and act are not read)

@@ -112,7 +112,7 @@ def bits(t):
 
 
 @pytest.mark.parametrize("rows", [8, 16, 24, 4096])
-@pytest.mark.parametrize("Hd, vd", [(64, 3), (144, 2), (512, 3)])
+@pytest.mark.parametrize("Hd, vd", [(64, 3), (144, 2), (512, 3), (520, 3), (1032, 3)])      # NS = 1, 1, 2, 4, 8
 @pytest.mark.parametrize("layout", ["ragged", "padded"])
 def test_pair_infer_is_pair_fwd_bit_for_bit(layout, Hd, vd, rows):
     from wf3d import infer, ops

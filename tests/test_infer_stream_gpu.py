@@ -129,8 +129,10 @@ def test_pool_stream_vs_numpy_model(C, rows):
 # ----------------------------------------------------------------------------------------------------------------------
 # 2. the first layer without z
 # ----------------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("R, K, D", [(33, 8, 512), (33, 5, 136)], ids=["fast", "general"])
+@pytest.mark.parametrize("R, K, D", [(33, 8, 512), (33, 5, 136), (33, 8, 1024), (33, 5, 520)],
+                         ids=["fast", "general", "fast-ns2", "general-ns2"])
 def test_first_layer_infer_is_first_layer_fwd_bit_for_bit(R, K, D):
+    """The two instantiations of the one first-layer body against each other, in all four NS x FAST forms (NS = 2: D > 512)."""
     from wf3d import ops
     g = torch.Generator().manual_seed(R + K + D)
     x, W = torch.randn(R, K, generator=g).to(dev()), (0.3 * torch.randn(D, K, generator=g)).to(dev())

@@ -100,25 +100,53 @@ __global__ __launch_bounds__(256) void scatter_dverts_kernel(const float* __rest
 // Each wave walks EPW consecutive edge rows: the per-column constants (distance weight, gamma, beta) are loaded once,
 // and consecutive edges share their first vertex i (lexicographic order), so the Pa row stays in registers until i
 // changes.
-template <int NS>
+// The rows are e0 + l, l in [0, n), of the layout: esample / eoff and the dropout counter are indexed by the layout row
+// e0 + l, every output by l.  e0 % 8 == 0, so a wave's 8 rows are the 8 rows one wave of a whole-layout launch walks.
+// KEEP: the training forward (e0 = 0, n = Re): mu, rs and delta of every row for the backward, dropout, and any of
+// pre / h_sx8.  !KEEP is the forward-only form (wf3d.infer.edge_stream) over a block of rows, by the pointers given:
+//   h_sx8        : h = act(LN(pre)) as the sx8 operand alone (split route); pre, mu, rs are NULL
+//   pre, mu, rs  : the pre-activation and its row statistics (fp32 route); h_sx8 is NULL
+// with no delta and no dropout.  One body, so what both forms write is the same expressions in the same order: bit for
+// bit.  `live_rows` counts rows of [e0, e0 + n): rows l at or past its 256-row extent are neither read (esample) nor
+// written.  Nothing at or past row n is touched.
+
+// One 4-column piece of an sx8 row: sx8 group = 8 columns = lanes (2m, 2m+1); the even lane stores the 8 high parts, the
+// odd lane the 8 low parts.  `row` is the output row, c the lane's first column.
+__device__ __forceinline__ void pair_store_sx8(float* __restrict__ row, int c, const float (&o)[4], int lane) {
+    typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
+    bf16x4 hi, lo;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) { hi[k] = (__bf16)o[k]; lo[k] = (__bf16)(o[k] - (float)hi[k]); }
+    const uint2 mine_hi = __builtin_bit_cast(uint2, hi), mine_lo = __builtin_bit_cast(uint2, lo);
+    const bool odd = lane & 1;
+    uint2 send = odd ? mine_hi : mine_lo, got;
+    got.x = __shfl_xor((int)send.x, 1, 64);
+    got.y = __shfl_xor((int)send.y, 1, 64);
+    const uint4 w = odd ? make_uint4(got.x, got.y, mine_lo.x, mine_lo.y) : make_uint4(mine_hi.x, mine_hi.y, got.x, got.y);
+    *reinterpret_cast<uint4*>(row + (c & ~7) + (odd ? 4 : 0)) = w;
+}
+
+template <int NS, bool KEEP>
 __global__ __launch_bounds__(256) void pair_fwd_kernel(const float* __restrict__ Pa, const float* __restrict__ Pb,
                                                         const float* __restrict__ cv, const float* __restrict__ wd,
                                                         int wd_stride, const int32_t* __restrict__ voff,
                                                         const int32_t* __restrict__ eoff,
-                                                        const int32_t* __restrict__ esample, int Re, int H, float eps,
-                                                        float* __restrict__ pre, float* __restrict__ mu,
+                                                        const int32_t* __restrict__ esample, int e0, int n, int H,
+                                                        float eps, float* __restrict__ pre, float* __restrict__ mu,
                                                         float* __restrict__ rs, float* __restrict__ delta,
                                                         const float* __restrict__ gamma, const float* __restrict__ beta,
                                                         int act, const wf3d_seed_t seed_src, uint32_t thresh, float dscale,
                                                         float* __restrict__ h_sx8, int vd,
                                                         const int32_t* __restrict__ live_rows) {
-    const uint32_t seed = thresh ? wf3d_seed_load(seed_src) : 0u;
+    const uint32_t seed = (KEEP && thresh) ? wf3d_seed_load(seed_src) : 0u;
     constexpr int EPW = 8;
-    Re = wf3d_live_extent(live_rows, Re);              // under a live-row count the zero-written tail ends at its extent
+    if (KEEP) e0 = 0;                                  // a compile-time origin: layout row and output row are one register
+    n = wf3d_live_extent(live_rows, n);                // under a live-row count the zero-written tail ends at its extent
     const int lane = threadIdx.x & 63;
-    const int e0 = (blockIdx.x * 4 + (threadIdx.x >> 6)) * EPW;
-    if (e0 >= Re) return;
-    const int e1 = min(Re, e0 + EPW);
+    const int l0 = (blockIdx.x * 4 + (threadIdx.x >> 6)) * EPW;
+    if (l0 >= n) return;
+    const int l1 = min(n, l0 + EPW);
+    const bool stats = KEEP || pre;                    // mu / rs: always for a backward, else only beside pre
     f32x4 wdv[NS], g4[NS], b4[NS], pa[NS];
 #pragma unroll
     for (int t = 0; t < NS; ++t) {
@@ -130,30 +158,32 @@ __global__ __launch_bounds__(256) void pair_fwd_kernel(const float* __restrict__
             if (h_sx8) { g4[t] = *reinterpret_cast<const f32x4*>(gamma + c); b4[t] = *reinterpret_cast<const f32x4*>(beta + c); }
         }
     }
-    // rows ea..e1-1 of a padded layout's tail (contiguous, so the rest of this wave's rows): zeros, h included
-    auto zero_tail = [&](int ea) {
-        for (int e = ea; e < e1; ++e) {
+    // rows la..l1-1 of a padded layout's tail (contiguous, so the rest of this wave's rows): zeros in every output
+    auto zero_tail = [&](int la) {
+        for (int l = la; l < l1; ++l) {
 #pragma unroll
             for (int t = 0; t < NS; ++t) {
                 const int c = lane * 4 + 256 * t;
                 if (c < H) {
-                    if (pre) *reinterpret_cast<f32x4*>(pre + (size_t)e * H + c) = (f32x4){0.f, 0.f, 0.f, 0.f};
-                    if (h_sx8) *reinterpret_cast<f32x4*>(h_sx8 + (size_t)e * H + c) = (f32x4){0.f, 0.f, 0.f, 0.f};
+                    if (pre) *reinterpret_cast<f32x4*>(pre + (size_t)l * H + c) = (f32x4){0.f, 0.f, 0.f, 0.f};
+                    if (h_sx8) *reinterpret_cast<f32x4*>(h_sx8 + (size_t)l * H + c) = (f32x4){0.f, 0.f, 0.f, 0.f};
                 }
             }
-            if (lane == 0) { mu[e] = 0.f; rs[e] = 0.f; delta[e] = 0.f; }
+            if (stats && lane == 0) { mu[l] = 0.f; rs[l] = 0.f; }
+            if (KEEP && lane == 0) delta[l] = 0.f;
         }
     };
-    int s = esample[e0];
-    if (s < 0) { zero_tail(e0); return; }
+    int s = esample[e0 + l0];
+    if (s < 0) { zero_tail(l0); return; }
     int vbase = voff[s], v = voff[s + 1] - vbase, eend = eoff[s + 1];
     int i, j;
-    edge_ij(e0 - eoff[s], v, i, j);
+    edge_ij(e0 + l0 - eoff[s], v, i, j);               // a block, like a wave, may start in the middle of a sample
     int pa_row = -1;
-    for (int e = e0; e < e1; ++e) {
+    for (int l = l0; l < l1; ++l) {
+        const int e = e0 + l;
         if (e == eend) {                       // first edge of the next sample that has edges
             s = esample[e];
-            if (s < 0) { zero_tail(e); return; }
+            if (s < 0) { zero_tail(l); return; }
             vbase = voff[s]; v = voff[s + 1] - vbase; eend = eoff[s + 1];
             i = 0; j = 1;
         }
@@ -175,7 +205,7 @@ __global__ __launch_bounds__(256) void pair_fwd_kernel(const float* __restrict__
                     val[t][k] = pa[t][k] + b[k] + dl * wdv[t][k];
                     sum += val[t][k];
                 }
-                if (pre) *reinterpret_cast<f32x4*>(pre + (size_t)e * H + c) = val[t];
+                if (pre) *reinterpret_cast<f32x4*>(pre + (size_t)l * H + c) = val[t];
             }
         }
         pa_row = ri;
@@ -191,10 +221,10 @@ __global__ __launch_bounds__(256) void pair_fwd_kernel(const float* __restrict__
         }
         const float var = wf3d_wave_sum(q) / (float)H;
         const float rstd = 1.0f / sqrtf(var + eps);
-        if (lane == 0) {
-            mu[e] = mean;
-            rs[e] = rstd;
-            delta[e] = dl;
+        if (stats && lane == 0) {
+            mu[l] = mean;
+            rs[l] = rstd;
+            if (KEEP) delta[l] = dl;
         }
         // h = drop(act(LN(pre))) as the sx8 operand of the next Linear, from the row the wave still holds
         // (what wf3d_ln_prep would produce from a second read of pre; same dropout counter: row e, column c).
@@ -207,20 +237,9 @@ __global__ __launch_bounds__(256) void pair_fwd_kernel(const float* __restrict__
 #pragma unroll
                     for (int k = 0; k < 4; ++k) {
                         o[k] = wf3d_act_rt(act, (val[t][k] - mean) * rstd * g4[t][k] + b4[t][k]);
-                        if (thresh) o[k] = wf3d_keep(seed, (uint32_t)e, (uint32_t)(c + k), thresh) ? o[k] * dscale : 0.f;
+                        if (KEEP && thresh) o[k] = wf3d_keep(seed, (uint32_t)e, (uint32_t)(c + k), thresh) ? o[k] * dscale : 0.f;
                     }
-                    // sx8 group = 8 columns = lanes (2m, 2m+1): even lane stores the 8 high parts, odd lane the 8 low parts
-                    typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-                    bf16x4 hi, lo;
-#pragma unroll
-                    for (int k = 0; k < 4; ++k) { hi[k] = (__bf16)o[k]; lo[k] = (__bf16)(o[k] - (float)hi[k]); }
-                    const uint2 mine_hi = __builtin_bit_cast(uint2, hi), mine_lo = __builtin_bit_cast(uint2, lo);
-                    const bool odd = lane & 1;
-                    uint2 send = odd ? mine_hi : mine_lo, got;
-                    got.x = __shfl_xor((int)send.x, 1, 64);
-                    got.y = __shfl_xor((int)send.y, 1, 64);
-                    const uint4 w = odd ? make_uint4(got.x, got.y, mine_lo.x, mine_lo.y) : make_uint4(mine_hi.x, mine_hi.y, got.x, got.y);
-                    *reinterpret_cast<uint4*>(h_sx8 + (size_t)e * H + (c & ~7) + (odd ? 4 : 0)) = w;
+                    pair_store_sx8(h_sx8 + (size_t)l * H, c, o, lane);
                 }
             }
         }
@@ -460,6 +479,24 @@ extern "C" int wf3d_edge_pair_fwd_ln(const float* Pa, const float* Pb, const flo
                          act, drop_p, drop_seed, h_sx8, vd, stream);
 }
 
+// The NS dispatch of both forms of pair_fwd_kernel; the callers have checked their arguments.
+template <bool KEEP>
+static int pair_fwd_launch(const float* Pa, const float* Pb, const float* cv, const float* wdelta, int wdelta_stride,
+                           const int32_t* voff, const int32_t* eoff, const int32_t* esample, int e0, int n, int H, float eps,
+                           float* pre, float* mu, float* rs, float* delta, const float* gamma, const float* beta, int act,
+                           const wf3d_drop_t& drop, void* h_sx8, int vd, void* stream) {
+    const int ns = wf3d_cdiv(H, 256);
+    hipStream_t st = (hipStream_t)stream;
+#define WF3D_PF(NS_)                                                                                                 \
+    hipLaunchKernelGGL((pair_fwd_kernel<NS_, KEEP>), dim3(wf3d_cdiv(n, 4 * 8)), dim3(256), 0, st, Pa, Pb, cv, wdelta,      \
+                       wdelta_stride, voff, eoff, esample, e0, n, H, eps, pre, mu, rs, delta, gamma, beta, act, drop.seed, \
+                       drop.thresh, drop.scale, (float*)h_sx8, vd, wf3d_live_rows())
+    if (ns <= 1) WF3D_PF(1); else if (ns <= 2) WF3D_PF(2); else if (ns <= 4) WF3D_PF(4); else WF3D_PF(8);
+#undef WF3D_PF
+    WF3D_LAUNCH_CHECK();
+    return WF3D_OK;
+}
+
 static int pair_fwd_impl(const float* Pa, const float* Pb, const float* cv, const float* wdelta, int wdelta_stride,
                          const int32_t* voff, const int32_t* eoff, const int32_t* esample, int Re, int H, float eps,
                          float* pre, float* mu, float* rs, float* delta, const float* gamma, const float* beta, int act,
@@ -470,16 +507,30 @@ static int pair_fwd_impl(const float* Pa, const float* Pb, const float* cv, cons
     if (Re == 0) return WF3D_OK;
     WF3D_CHECK(Pa && Pb && cv && wdelta && voff && eoff && esample && (pre || h_sx8) && mu && rs && delta, WF3D_ERR_ARG,
                "wf3d_edge_pair_fwd: null pointer");
-    const int ns = wf3d_cdiv(H, 256);
-    hipStream_t st = (hipStream_t)stream;
-#define WF3D_PF(NS_)                                                                                                 \
-    hipLaunchKernelGGL((pair_fwd_kernel<NS_>), dim3(wf3d_cdiv(Re, 4 * 8)), dim3(256), 0, st, Pa, Pb, cv, wdelta,           \
-                       wdelta_stride, voff, eoff, esample, Re, H, eps, pre, mu, rs, delta, gamma, beta, act, drop.seed,    \
-                       drop.thresh, drop.scale, (float*)h_sx8, vd, wf3d_live_rows())
-    if (ns <= 1) WF3D_PF(1); else if (ns <= 2) WF3D_PF(2); else if (ns <= 4) WF3D_PF(4); else WF3D_PF(8);
-#undef WF3D_PF
-    WF3D_LAUNCH_CHECK();
-    return WF3D_OK;
+    return pair_fwd_launch<true>(Pa, Pb, cv, wdelta, wdelta_stride, voff, eoff, esample, 0, Re, H, eps, pre, mu, rs, delta,
+                                 gamma, beta, act, drop, h_sx8, vd, stream);
+}
+
+// The forward-only form over the edge rows [e0, e0 + n) of a layout; outputs are indexed by e - e0.
+extern "C" int wf3d_edge_pair_infer(const float* Pa, const float* Pb, const float* cv, const float* wdelta,
+                                    int wdelta_stride, const int32_t* voff, const int32_t* eoff, const int32_t* esample,
+                                    int e0, int n, int H, int vd, float eps, const float* gamma, const float* beta, int act,
+                                    float* pre, float* mu, float* rs, void* h_sx8, void* stream) {
+    WF3D_CHECK(e0 >= 0 && e0 % 8 == 0 && n >= 0 && (long)e0 + n <= 0x7FFFFFFFL, WF3D_ERR_ARG,
+               "wf3d_edge_pair_infer: bad rows e0=%d n=%d (e0 must be a non-negative multiple of 8)", e0, n);
+    WF3D_CHECK(H > 0 && vd >= 1 && vd <= 8, WF3D_ERR_ARG, "wf3d_edge_pair_infer: bad dims (vertex_dim must be 1..8)");
+    WF3D_CHECK(H % 4 == 0 && H <= 2048, WF3D_ERR_UNSUPPORTED, "wf3d_edge_pair_infer: hidden %d must be a multiple of 4, <= 2048", H);
+    if (n == 0) return WF3D_OK;
+    WF3D_CHECK(Pa && Pb && cv && wdelta && voff && eoff && esample, WF3D_ERR_ARG, "wf3d_edge_pair_infer: null pointer");
+    const bool split = h_sx8 && !pre && !mu && !rs, fp32 = !h_sx8 && pre && mu && rs;
+    WF3D_CHECK(split || fp32, WF3D_ERR_ARG, "wf3d_edge_pair_infer: give h_sx8 alone, or pre, mu and rs alone");
+    if (split) {
+        WF3D_CHECK(gamma && beta && act >= 0 && act <= 2, WF3D_ERR_ARG, "wf3d_edge_pair_infer: null gamma / beta or bad act");
+        WF3D_CHECK(H % 8 == 0 && ((uintptr_t)h_sx8 % 16 == 0) && ((uintptr_t)gamma % 16 == 0) && ((uintptr_t)beta % 16 == 0),
+                   WF3D_ERR_UNSUPPORTED, "wf3d_edge_pair_infer: needs hidden %% 8 == 0 and 16-byte aligned pointers");
+    }
+    return pair_fwd_launch<false>(Pa, Pb, cv, wdelta, wdelta_stride, voff, eoff, esample, e0, n, H, eps, pre, mu, rs, nullptr,
+                                  gamma, beta, act, wf3d_drop_args(0.f, 0u), h_sx8, vd, stream);
 }
 
 extern "C" int wf3d_edge_pair_bwd(const float* dpre, const float* delta, const float* cv, const float* wdelta,

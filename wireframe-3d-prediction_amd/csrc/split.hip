@@ -205,11 +205,13 @@ __global__ __launch_bounds__(256) void ln_prep_kernel(const float* __restrict__ 
 // (PointNetEncoder.py:35-45 with in_features = input_dim = 8): z = x·W^T + b is a pure
 // 2 KB-per-row WRITE (K <= 8: 8 FMAs per output), so instead of a GEMM that writes z and an
 // ln_prep pass that reads it back, one wave per row computes the row in registers from its
-// slice of W (kept in registers across rows), and writes z (kept for backward), (mu, rstd)
-// and h = act(LN(z)) in sx8.  Column layout per lane as in ln_prep_kernel (lane-contiguous 16-B pieces, lane pairs
-// share an sx8 group; z and h leave through non-temporal stores).
+// slice of W (kept in registers across rows), and writes h = act(LN(z)) in sx8.  Column layout per lane as in
+// ln_prep_kernel (lane-contiguous 16-B pieces, lane pairs share an sx8 group; z and h leave through non-temporal stores).
+// KEEP: the training forward, which also writes what a backward reads — z and (mu, rstd) — and stops at the live-row
+// extent.  !KEEP is the forward-only form (wf3d.infer): z, mu, rs and live_rows are not touched, which is worth a wave
+// of occupancy at NS = 1.  One body, so the h of the two forms is the same expressions in the same order: bit for bit.
 // FAST: K == 8, D a multiple of 512, 16-byte aligned x / W rows and ReLU — two float4 loads per row, no per-element branches.
-template <int NS, bool FAST>
+template <int NS, bool FAST, bool KEEP>
 __global__ __launch_bounds__(256) void first_layer_kernel(const float* __restrict__ x, int ldx, int K,
                                                            const float* __restrict__ W, int ldw,
                                                            const float* __restrict__ bias, int R, int D,
@@ -219,7 +221,7 @@ __global__ __launch_bounds__(256) void first_layer_kernel(const float* __restric
                                                            float* __restrict__ h_sx8, const int32_t* __restrict__ live_rows) {
     // one scalar load at entry, before the W slice: the row walk and the prefetch clamp below stop at the extent, so no
     // row at or past it is read or written (z, mu, rs, h_sx8)
-    R = wf3d_live_extent(live_rows, R);
+    if (KEEP) R = wf3d_live_extent(live_rows, R);
     if (R == 0) return;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const bool odd = lane & 1;
@@ -291,7 +293,7 @@ __global__ __launch_bounds__(256) void first_layer_kernel(const float* __restric
             }
 #pragma unroll
             for (int hf = 0; hf < 2; ++hf)
-                if (FAST || col(i, 4 * hf) < D)
+                if (KEEP && (FAST || col(i, 4 * hf) < D))
                     __builtin_nontemporal_store(f32x4{v[i][4 * hf], v[i][4 * hf + 1], v[i][4 * hf + 2], v[i][4 * hf + 3]},
                                                 reinterpret_cast<f32x4*>(z + (size_t)row * D + col(i, 4 * hf)));
         }
@@ -303,7 +305,7 @@ __global__ __launch_bounds__(256) void first_layer_kernel(const float* __restric
             for (int j = 0; j < 8; ++j)
                 if (FAST || col(i, j) < D) { const float d = v[i][j] - mean; q += d * d; }
         const float rstd = 1.0f / sqrtf(wf3d_wave_sum(q) / (float)D + eps);
-        if (lane == 0) { mu[row] = mean; rs[row] = rstd; }
+        if (KEEP && lane == 0) { mu[row] = mean; rs[row] = rstd; }
 #pragma unroll
         for (int i = 0; i < NS; ++i)
 #pragma unroll
@@ -473,17 +475,17 @@ extern "C" int wf3d_ln_prep(const float* z, int R, int D, const float* gamma, co
     return WF3D_OK;
 }
 
-extern "C" int wf3d_first_layer_fwd(const float* x, int R, int K, int ldx, const float* W, int ldw, const float* bias,
-                                    int D, const float* gamma, const float* beta, int act, float eps, float* z,
-                                    float* mu, float* rs, void* h_sx8, void* stream) {
-    WF3D_CHECK(R >= 0 && K > 0 && K <= 8 && ldx >= K && ldw >= K, WF3D_ERR_UNSUPPORTED,
-               "wf3d_first_layer_fwd: needs 1 <= K <= 8 (K=%d)", K);
-    WF3D_CHECK(D > 0 && D % 8 == 0 && D <= 1024, WF3D_ERR_UNSUPPORTED, "wf3d_first_layer_fwd: D=%d must be a multiple of 8, <= 1024", D);
-    WF3D_CHECK(act >= 0 && act <= 2, WF3D_ERR_ARG, "wf3d_first_layer_fwd: bad act");
+// Both first-layer entry points.  `keep`: the training forward (z, mu, rs kept, the thread's live-row count honoured).
+static int first_layer_launch(const char* who, bool keep, const float* x, int R, int K, int ldx, const float* W, int ldw,
+                              const float* bias, int D, const float* gamma, const float* beta, int act, float eps, float* z,
+                              float* mu, float* rs, void* h_sx8, void* stream) {
+    WF3D_CHECK(R >= 0 && K > 0 && K <= 8 && ldx >= K && ldw >= K, WF3D_ERR_UNSUPPORTED, "%s: needs 1 <= K <= 8 (K=%d)", who, K);
+    WF3D_CHECK(D > 0 && D % 8 == 0 && D <= 1024, WF3D_ERR_UNSUPPORTED, "%s: D=%d must be a multiple of 8, <= 1024", who, D);
+    WF3D_CHECK(act >= 0 && act <= 2, WF3D_ERR_ARG, "%s: bad act", who);
     if (R == 0) return WF3D_OK;
-    WF3D_CHECK(x && W && gamma && beta && z && mu && rs && h_sx8, WF3D_ERR_ARG, "wf3d_first_layer_fwd: null pointer");
+    WF3D_CHECK(x && W && gamma && beta && h_sx8 && (!keep || (z && mu && rs)), WF3D_ERR_ARG, "%s: null pointer", who);
     WF3D_CHECK(((uintptr_t)z % 16 == 0) && ((uintptr_t)h_sx8 % 16 == 0) && ((uintptr_t)gamma % 16 == 0) &&
-               ((uintptr_t)beta % 16 == 0), WF3D_ERR_ARG, "wf3d_first_layer_fwd: pointers must be 16-byte aligned");
+               ((uintptr_t)beta % 16 == 0), WF3D_ERR_ARG, "%s: pointers must be 16-byte aligned", who);
     // each wave keeps its slice of W in registers for all its rows; 4096 workgroups measured best of 512..32768 with the
     // vector prologue (118 / 124 / 112 / 106 / 129 us at 512 / 1024 / 2048 / 4096 / 8192; 512 was best while the prologue
     // was 72 single loads)
@@ -492,14 +494,32 @@ extern "C" int wf3d_first_layer_fwd(const float* x, int R, int K, int ldx, const
     hipStream_t st = (hipStream_t)stream;
     const bool fast = K == 8 && ldx % 4 == 0 && ((uintptr_t)x % 16 == 0) && act == WF3D_ACT_RELU && D % 512 == 0 && ldw % 4 == 0 &&
                       ((uintptr_t)W % 16 == 0) && (!bias || (uintptr_t)bias % 16 == 0);
-#define WF3D_FL(NS_, F_)                                                                                               \
-    hipLaunchKernelGGL((first_layer_kernel<NS_, F_>), dim3(blocks), dim3(256), 0, st, x, ldx, K, W, ldw, bias, R, D, gamma, \
-                       beta, act, eps, z, mu, rs, (float*)h_sx8, wf3d_live_rows())
-    if (D <= 512) { if (fast) WF3D_FL(1, true); else WF3D_FL(1, false); }
-    else          { if (fast) WF3D_FL(2, true); else WF3D_FL(2, false); }
+    const int32_t* live = keep ? wf3d_live_rows() : nullptr;
+#define WF3D_FL(NS_, F_, K_)                                                                                                \
+    hipLaunchKernelGGL((first_layer_kernel<NS_, F_, K_>), dim3(blocks), dim3(256), 0, st, x, ldx, K, W, ldw, bias, R, D, gamma, \
+                       beta, act, eps, z, mu, rs, (float*)h_sx8, live)
+#define WF3D_FLK(NS_, F_) do { if (keep) WF3D_FL(NS_, F_, true); else WF3D_FL(NS_, F_, false); } while (0)
+    if (D <= 512) { if (fast) WF3D_FLK(1, true); else WF3D_FLK(1, false); }
+    else          { if (fast) WF3D_FLK(2, true); else WF3D_FLK(2, false); }
+#undef WF3D_FLK
 #undef WF3D_FL
     WF3D_LAUNCH_CHECK();
     return WF3D_OK;
+}
+
+extern "C" int wf3d_first_layer_fwd(const float* x, int R, int K, int ldx, const float* W, int ldw, const float* bias,
+                                    int D, const float* gamma, const float* beta, int act, float eps, float* z,
+                                    float* mu, float* rs, void* h_sx8, void* stream) {
+    return first_layer_launch("wf3d_first_layer_fwd", true, x, R, K, ldx, W, ldw, bias, D, gamma, beta, act, eps, z, mu, rs,
+                              h_sx8, stream);
+}
+
+// The forward-only form: no z, mu or rs, and no live-row count (wf3d.infer walks row blocks of its own).
+extern "C" int wf3d_first_layer_infer(const float* x, int R, int K, int ldx, const float* W, int ldw, const float* bias,
+                                      int D, const float* gamma, const float* beta, int act, float eps, void* h_sx8,
+                                      void* stream) {
+    return first_layer_launch("wf3d_first_layer_infer", false, x, R, K, ldx, W, ldw, bias, D, gamma, beta, act, eps, nullptr,
+                              nullptr, nullptr, h_sx8, stream);
 }
 
 extern "C" int wf3d_split_transpose(const float* in, int R, int C, int ld, const float* mu, const float* rs,

@@ -168,17 +168,22 @@ def _edge_routes(Re, H, precision, x3):
     return Route("split", wgrad(H // 2, H), "split", x3), Route("split", wgrad(H // 4, H // 2), "split", x3)
 
 
-def _edge_live(meta, routes, fused_tail):
-    """The live-row count the edge-row section of EdgeFn runs under, or None.  It is used for a padded layout in
-    tail="skip" mode whose two wide Linears run split, forward and dgrad, with their wgrads on sx8 operands (the TN
-    kernels or the "transposes" form), and whose logits layer is the row-dot kernel (fused_tail).  Every launch of the
-    section then honours the count (include/wf3d.h, "LIVE ROW COUNT"): rows past its extent are never written and
-    never read.  Any other route (fp32 precision, too few rows, an fp32 wgrad: a row total that is not a multiple of 8)
-    computes the tail as tail="compute" does."""
-    if not (meta.padded and meta.tail == "skip"):
-        return None
-    ok = fused_tail and all(r.fwd == "split" and r.dgrad == "split" and r.wgrad in _TN + ("transposes",) for r in routes)
+def _edge_live_fwd(meta, routes, fused_tail):
+    """The live-row count the forward launches over edge rows can run under, or None.  It is used for a padded layout in
+    tail="skip" mode whose two wide Linears run split in forward and whose logits layer is the row-dot kernel
+    (fused_tail).  Every forward launch of the section then honours the count (include/wf3d.h, "LIVE ROW COUNT"): rows
+    past its extent are never written and never read.  Any other route (fp32 precision, too few rows) computes the tail
+    as tail="compute" does."""
+    ok = meta.padded and meta.tail == "skip" and fused_tail and all(r.fwd == "split" for r in routes)
     return meta.live if ok else None
+
+
+def _edge_live(meta, routes, fused_tail):
+    """The live-row count the edge-row section of EdgeFn runs under, forward and backward, or None: the forward
+    condition (_edge_live_fwd), and the backward's: split dgrads, with the wgrads on sx8 operands (the TN kernels or
+    the "transposes" form; an fp32 wgrad, for a row total that is not a multiple of 8, does not see a count)."""
+    ok = all(r.dgrad == "split" and r.wgrad in _TN + ("transposes",) for r in routes)
+    return _edge_live_fwd(meta, routes, fused_tail) if ok else None
 
 
 def _encoder_live(layout, routes, tail):
@@ -655,6 +660,36 @@ class VertexFn(torch.autograd.Function):
 # ===========================================================================
 # Edge head (all samples of the batch in one pass, ragged)
 # ===========================================================================
+def _edge_vertex_section(verts, meta, heads, x3, params, drop_ps=(0.0, 0.0), seeds=(0, 0)):
+    """The per-vertex section of the edge head (sum-of-counts rows): vertex_proj, attention with its residual, and the
+    two projections Pa / Pb of edge_mlp.0 that the pair combine adds per edge.  EdgeFn._forward and infer.edge_stream
+    both run it; drop_ps / seeds: vertex_proj.5 and attention.
+    Returns cv, za, sa, zb, sb, f, qkv, cx, lse, Fm, Pa, Pb."""
+    P0w, P0b, P1g, P1b, P3w, P3b, P4g, P4b, Aw, Ab, Ow, Ob, M0w, M0b = params[:14]
+    H = P3w.shape[0]
+    cv = ops.edge_gather_verts(verts, meta)
+    za = ops.gemm(cv, P0w, NT, bias=P0b); sa = ops.row_stats(za)
+    # per-vertex Linears: in bf16x3 mode the fp32 operands are split inside the GEMM's staging pass (x3), forward and
+    # backward; the K = 3 coordinate products stay exact fp32
+    zb = ops.gemm(za, P3w, NT, bias=P3b, pro=Pro(ACT_GELU, sa[0], sa[1], P1g, P1b), x3=x3); sb = ops.row_stats(zb)
+    f = ops.ln_act_apply(zb, sb[0], sb[1], P4g, P4b, ACT_NONE, drop_p=drop_ps[0], seed=seeds[0])
+    qkv = ops.gemm(f, Aw, NT, bias=Ab, x3=x3)
+    cx, lse = ops.attn_fwd(qkv, meta, H, heads, drop_ps[1], seeds[1])
+    Fm = ops.gemm(cx, Ow, NT, bias=Ob, addend=f, x3=x3)              # residual (EdgePredictor.py:114)
+    vd = cv.shape[1]                                   # coordinates per vertex (EdgePredictor(vertex_dim=...): 3 in the model)
+    Wa, Wb, Wc, Wd = M0w[:, :H], M0w[:, H:2 * H], M0w[:, 2 * H:2 * H + vd], M0w[:, 2 * H + vd:2 * H + 2 * vd]
+    if vd <= 4:
+        # the coordinate columns ride on the two GEMMs as a rank-vd epilogue term (exact fp32)
+        Pa = ops.gemm(Fm, Wa, NT, bias=M0b, x3=x3, lowrank=(cv, Wc))
+        Pb = ops.gemm(Fm, Wb, NT, x3=x3, lowrank=(cv, Wd))
+    else:
+        Pa = ops.gemm(Fm, Wa, NT, bias=M0b, x3=x3)
+        ops.gemm(cv, Wc, NT, out=Pa, accumulate=True)
+        Pb = ops.gemm(Fm, Wb, NT, x3=x3)
+        ops.gemm(cv, Wd, NT, out=Pb, accumulate=True)
+    return cv, za, sa, zb, sb, f, qkv, cx, lse, Fm, Pa, Pb
+
+
 class EdgeFn(torch.autograd.Function):
     """verts[B,V,3] (view ok) -> edge_probs[B, max_E] zero-padded.
 
@@ -687,27 +722,8 @@ class EdgeFn(torch.autograd.Function):
         meta = counts if isinstance(counts, ops.EdgeMeta) else ops.EdgeMeta.get(counts, verts.device)
         sd = [1, 2, 3, 4] if ctx.words is not None else [(seed + 0x9E3779B9 * k) & 0xFFFFFFFF for k in range(1, 5)]
         pf_, pa_, p1_, p2_ = (float(x) for x in drop_ps)   # vertex_proj.5, attention, edge_mlp.3, edge_mlp.7
-        cv = ops.edge_gather_verts(verts, meta)
-        za = ops.gemm(cv, P0w, NT, bias=P0b); sa = ops.row_stats(za)
-        # per-vertex Linears (sum-of-counts rows): in bf16x3 mode the fp32 operands are split inside the GEMM's
-        # staging pass (x3), forward and backward; the K = 3 coordinate products stay exact fp32
         x3 = precision == "bf16x3" and config.EDGE_X3
-        zb = ops.gemm(za, P3w, NT, bias=P3b, pro=Pro(ACT_GELU, sa[0], sa[1], P1g, P1b), x3=x3); sb = ops.row_stats(zb)
-        f = ops.ln_act_apply(zb, sb[0], sb[1], P4g, P4b, ACT_NONE, drop_p=pf_, seed=sd[0])
-        qkv = ops.gemm(f, Aw, NT, bias=Ab, x3=x3)
-        cx, lse = ops.attn_fwd(qkv, meta, H, heads, pa_, sd[1])
-        Fm = ops.gemm(cx, Ow, NT, bias=Ob, addend=f, x3=x3)              # residual (EdgePredictor.py:114)
-        vd = cv.shape[1]                                   # coordinates per vertex (EdgePredictor(vertex_dim=...): 3 in the model)
-        Wa, Wb, Wc, Wd = M0w[:, :H], M0w[:, H:2 * H], M0w[:, 2 * H:2 * H + vd], M0w[:, 2 * H + vd:2 * H + 2 * vd]
-        if vd <= 4:
-            # the coordinate columns ride on the two GEMMs as a rank-vd epilogue term (exact fp32)
-            Pa = ops.gemm(Fm, Wa, NT, bias=M0b, x3=x3, lowrank=(cv, Wc))
-            Pb = ops.gemm(Fm, Wb, NT, x3=x3, lowrank=(cv, Wd))
-        else:
-            Pa = ops.gemm(Fm, Wa, NT, bias=M0b, x3=x3)
-            ops.gemm(cv, Wc, NT, out=Pa, accumulate=True)
-            Pb = ops.gemm(Fm, Wb, NT, x3=x3)
-            ops.gemm(cv, Wd, NT, out=Pb, accumulate=True)
+        cv, za, sa, zb, sb, f, qkv, cx, lse, Fm, Pa, Pb = _edge_vertex_section(verts, meta, heads, x3, params, (pf_, pa_), sd[:2])
         npr = _SPLIT_PRODUCTS.get(precision, 3)
         routes = _edge_routes(meta.Re, H, precision, x3)
         # decided once, here; backward only reads it (and the logits kernel chosen below)

@@ -19,8 +19,8 @@ WF3D_EDGE_INFERENCE=stream, and EdgePredictor.forward_stream calls it directly."
 import torch
 
 from . import config, ops
-from .functional import _SPLIT_PRODUCTS, _edge_routes, _encoder_routes
-from .ops import ACT_GELU, ACT_NONE, ACT_RELU, NT, Pro
+from .functional import _SPLIT_PRODUCTS, _edge_live_fwd, _edge_routes, _edge_vertex_section, _encoder_routes
+from .ops import ACT_GELU, ACT_RELU, NT, Pro
 
 
 def check_rows(rows):
@@ -136,44 +136,26 @@ def edge_stream(verts, meta, heads, precision, params, rows=None):
     The per-vertex section (sum-of-counts rows: vertex_proj, attention, Pa / Pb) runs whole, on EdgeFn's ops in its
     order.  The routes of the two wide Linears and the logits kernel are decided once, from the row total, as EdgeFn
     decides them.  A padded layout in tail="skip" mode whose two wide Linears run split and whose logits layer is the
-    row-dot kernel (what functional._edge_live asks of the forward) runs each block under its own live-row count
+    row-dot kernel (functional._edge_live_fwd) runs each block under its own live-row count
     (ops.block_live): a block past the live pair total costs its launches' entry checks and nothing more, and no count
     is read on the host.  The result equals tail="compute" bit for bit."""
     if not verts.is_cuda:
         raise RuntimeError("wf3d: the HIP path needs CUDA (ROCm) tensors; there is no CPU fallback")
     rows = check_rows(config.INFER_EDGE_ROWS if rows is None else rows)
-    (P0w, P0b, P1g, P1b, P3w, P3b, P4g, P4b, Aw, Ab, Ow, Ob,
-     M0w, M0b, M1g, M1b, M4w, M4b, M5g, M5b, M8w, M8b, M10w, M10b) = params
-    H, dev = P3w.shape[0], verts.device
+    M0w, _M0b, M1g, M1b, M4w, M4b, M5g, M5b, M8w, M8b, M10w, M10b = params[12:]
+    H, dev = M0w.shape[0], verts.device
     with torch.no_grad():
-        # ---- per-vertex section: functional.EdgeFn._forward, drop p = 0 ----
-        cv = ops.edge_gather_verts(verts, meta)
-        za = ops.gemm(cv, P0w, NT, bias=P0b); sa = ops.row_stats(za)
+        # ---- per-vertex section: EdgeFn's, drop p = 0 ----
         x3 = precision == "bf16x3" and config.EDGE_X3
-        zb = ops.gemm(za, P3w, NT, bias=P3b, pro=Pro(ACT_GELU, sa[0], sa[1], P1g, P1b), x3=x3); sb = ops.row_stats(zb)
-        f = ops.ln_act_apply(zb, sb[0], sb[1], P4g, P4b, ACT_NONE)
-        qkv = ops.gemm(f, Aw, NT, bias=Ab, x3=x3)
-        cx, _lse = ops.attn_fwd(qkv, meta, H, heads)
-        Fm = ops.gemm(cx, Ow, NT, bias=Ob, addend=f, x3=x3)
-        vd = cv.shape[1]
-        Wa, Wb, Wc, Wd = M0w[:, :H], M0w[:, H:2 * H], M0w[:, 2 * H:2 * H + vd], M0w[:, 2 * H + vd:2 * H + 2 * vd]
-        if vd <= 4:
-            Pa = ops.gemm(Fm, Wa, NT, bias=M0b, x3=x3, lowrank=(cv, Wc))
-            Pb = ops.gemm(Fm, Wb, NT, x3=x3, lowrank=(cv, Wd))
-        else:
-            Pa = ops.gemm(Fm, Wa, NT, bias=M0b, x3=x3)
-            ops.gemm(cv, Wc, NT, out=Pa, accumulate=True)
-            Pb = ops.gemm(Fm, Wb, NT, x3=x3)
-            ops.gemm(cv, Wd, NT, out=Pb, accumulate=True)
-        del za, sa, zb, sb, f, qkv, cx, _lse, Fm
+        cv, *_, Pa, Pb = _edge_vertex_section(verts, meta, heads, x3, params)
+        del _
         # ---- edge-row section: decided once, from the row total; a short last block flips nothing ----
         npr = _SPLIT_PRODUCTS.get(precision, 3)
         routes = _edge_routes(meta.Re, H, precision, x3)
         split = routes[0].fwd == "split"
         rowdot = M10w.shape[0] == 1 and M10w.is_contiguous() and ops.rowdot_act_shape_ok(H // 4)
-        # functional._edge_live's conditions on the forward launches (its wgrad condition is about backward kernels): every
-        # launch of the loop below then honours the count; on any other route the tail is computed, as EdgeFn does
-        live = meta.live if (meta.padded and meta.tail == "skip" and split and routes[1].fwd == "split" and rowdot) else None
+        # every launch of the loop below then honours the count; on any other route the tail is computed, as EdgeFn does
+        live = _edge_live_fwd(meta, routes, rowdot)
         plan = block_plan(meta.Re, rows)
         R = plan[0][1] if plan else 0
         f32 = dict(dtype=torch.float32, device=dev)
