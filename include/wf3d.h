@@ -778,6 +778,62 @@ int wf3d_edge_compact(const float* verts, long sample_stride, long vertex_stride
 int wf3d_hausdorff_lines_batch(const float* seg, const int32_t* koff, const float* lseg, const int32_t* loff,
                                const int64_t* ooff, int B, long max_pairs, int sample_points, double* out, void* stream);
 
+/* ------------------------------------------------------------------------
+ * Evaluation metrics on the device (csrc/evalmetrics.hip): what eval/ap_calculator.py's compute_metrics derives from a
+ * sample's Hausdorff matrix — two rectangular assignments, the corner sets, the counters and the corner distance sum —
+ * for a whole batch in four launches.
+ *
+ * wf3d_lsa_rect_batch: B rectangular linear sum assignments in one launch, one wave per sample.  Sample s's fp64 cost
+ * matrix [n_s, m_s] lies row-major at cost + ooff[s] (the layout wf3d_hausdorff_lines_batch writes), with
+ * n_s = noff[s * off_stride + 1] - noff[s * off_stride] and m_s likewise from moff (off_stride 1: prefix arrays such as
+ * koff / loff; 2: one (begin, end) pair per sample).  Algorithm, association and tie rule are those of wf3d_loss_assign
+ * (tests/lsa_model.py::_augmenting_paths).  The solver's rows are the shorter side: the matrix is read transposed
+ * (strided, never copied) iff n_s > m_s, as scipy.optimize.linear_sum_assignment does.  col4row + aoff[s] receives
+ * min(n_s, m_s) entries: n_s <= m_s: entry i = the column of row i; n_s > m_s: entry j = the row of column j.  Samples
+ * with n_s * m_s = 0 write nothing.  A cost that is NaN, +-inf or beyond +-FLT_MAX is read as +-FLT_MAX (NaN: +FLT_MAX),
+ * so the search terminates on any input; the scan count of a search and the augmenting walk are also bounded by the row
+ * count.  status[s] (always written): WF3D_EVAL_NONFINITE such a cost was met; WF3D_EVAL_STEPS a bound was hit (the
+ * entries are then not an assignment); WF3D_EVAL_RANGE max(n_s, m_s) > max_long or a negative extent (nothing written).
+ * The solver state lies in LDS while max(n_s, m_s) <= 1024, else in ws: wf3d_lsa_rect_ws_bytes(B, max_long) bytes
+ * (0 when max_long <= 1024).  B <= 65535, else WF3D_ERR_UNSUPPORTED.
+ *
+ * wf3d_eval_metrics: for every sample the counters of APCalculator._with_edges (n_s > 0 kept edges) or _corners_only
+ * (n_s = 0) from the Hausdorff matrices hd / ooff of wf3d_hausdorff_lines_batch, in four launches on `stream`:
+ *   1. wf3d_lsa_rect_batch on hd -> assign + aoff[s] (aoff: the caller's exclusive prefix of min(n_s, m_s));
+ *   2. one workgroup per sample: ok = matched pairs with hd <= thresh, tp_edges their number; pr_u / gt_u = the distinct
+ *      end points of the matched predicted / label segments (value equality on the three floats, -0.0 == 0.0); free_pr /
+ *      free_gt = the distinct rows of the V predicted / the label vertices not among them, in lexicographic (x, y, z)
+ *      order; dm = ||free_pr_i - free_gt_j|| in fp64 ((dx dx + dy dy) + dz dz, no FMA); e_term = sum_i min_j
+ *      ||pr_u_i - gt_u_j|| over pr_u in lexicographic order.  n_s = 0: dm over the V and the label vertices as given;
+ *   3. wf3d_lsa_rect_batch on the dm matrices;
+ *   4. fok = assigned dm <= thresh; distances[s] = (sum of dm[fok] in row order) + e_term; counters[s, 0..8) =
+ *      (tp_corners = |pr_u| + sum fok, V, label vertices, tp_edges, n_s, m_s, status, 0).
+ * The end points of seg / lseg must be rows of verts / lverts, as wf3d_edge_compact and a gather of the label vertices
+ * make them.  status: the solver bits of both launches, WF3D_EVAL_NONFINITE also for a non-finite vertex, matrix entry
+ * or thresh; WF3D_EVAL_NO_MATCH kept edges of which none matched (the host path raises there); WF3D_EVAL_RANGE an
+ * assignment entry out of range; WF3D_EVAL_ENDPOINT a matched end point that is no vertex row.  A sample with a
+ * non-zero status must be evaluated on the host.
+ * lvoff / loff: prefix arrays of the label vertices / segments per sample.  max_long >= every n_s and m_s.
+ * ws: wf3d_eval_metrics_ws_bytes(B, V, total_lverts, max_long) bytes, total_lverts = lvoff[B].
+ * B <= 65535, V <= 1024, max_lverts (>= every sample's label vertex count) <= 1024, B * V and V * total_lverts below
+ * 2^31, else WF3D_ERR_UNSUPPORTED; B = 0 launches nothing.
+ * ------------------------------------------------------------------------ */
+#define WF3D_EVAL_NONFINITE 1
+#define WF3D_EVAL_NO_MATCH 2
+#define WF3D_EVAL_STEPS 4
+#define WF3D_EVAL_RANGE 8
+#define WF3D_EVAL_ENDPOINT 16
+size_t wf3d_lsa_rect_ws_bytes(int B, long max_long);
+int wf3d_lsa_rect_batch(const double* cost, const int64_t* ooff, const int32_t* noff, const int32_t* moff, int off_stride,
+                        const int32_t* aoff, int B, long max_long, int32_t* col4row, int32_t* status, void* ws,
+                        size_t ws_bytes, void* stream);
+size_t wf3d_eval_metrics_ws_bytes(int B, int V, long total_lverts, long max_long);
+int wf3d_eval_metrics(const float* verts, long sample_stride, long vertex_stride, int B, int V, const float* seg,
+                      const int32_t* koff, const float* lverts, const int32_t* lvoff, const float* lseg, const int32_t* loff,
+                      const double* hd, const int64_t* ooff, const int32_t* aoff, int32_t* assign, double thresh,
+                      int max_lverts, long total_lverts, long max_long, int32_t* counters, double* distances, void* ws,
+                      size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

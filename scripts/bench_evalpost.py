@@ -20,6 +20,13 @@ batches; the median of block medians of each arm and its block-to-block spread (
 
 Prints one JSON line per arm and appends them to --out.  `d2h_bytes` are the formulas' values, not measurements:
 old B (3 V + 7 max_e) 4; new (B + 1) 4 + 12 B V + 36 K.
+
+    python scripts/bench_evalpost.py --what metrics [--out profiles/r15_evalmetrics.jsonl]
+
+measures evaluate_batch(compact=True) three ways in the same alternating blocks: "compact" (metrics="host": the yardstick),
+"device" (metrics="device", the EvalLabels built inside the timed call) and "device_labels" (an EvalLabels built once,
+outside).  Then one worst-case row: V = 64 with every one of the 2016 candidates kept, against a label of 120 vertices
+and 300 edges (few blocks: the host arm solves 32 assignments of 2016 x 300 per batch).
 """
 import argparse
 import json
@@ -129,25 +136,80 @@ def run(V, layout, data, args):
     return lines
 
 
+def worst_case(gen, dev):
+    """V = 64, every candidate kept, a 300-edge label on 120 random vertices"""
+    V, max_e = 64, 2016
+    gt_v = gen.uniform(-8, 8, (120, 3)).astype(np.float32)
+    every = np.stack(np.triu_indices(120, 1), axis=1)
+    gt_e = every[np.sort(gen.choice(len(every), 300, replace=False))].astype(np.int64)
+    verts = gen.uniform(-8, 8, (B, V, 4)).astype(np.float32)
+    verts[:, :, :3] = gt_v[:V] + gen.normal(0, 0.02, (B, V, 3))
+    return {"vertices": torch.from_numpy(verts).to(dev)[:, :, :3], "edge_probs": torch.full((B, max_e), 0.9, device=dev),
+            "counts": torch.full((B,), V, dtype=torch.int64, device=dev), "kept": B * max_e,
+            "labels": ([torch.from_numpy(gt_v)] * B, [torch.from_numpy(gt_e.astype(np.float32))] * B)}
+
+
+def run_metrics(V, layout, data, args, thresh, blocks, steps, warmup, tag=None):
+    pred = lambda: predictions(data, V, layout)                              # noqa: E731
+    labels = postprocess.EvalLabels(*data["labels"], data["vertices"].device)
+
+    def evaluate(metrics, lab=None):
+        calc = ap.APCalculator(distance_thresh=thresh)
+        postprocess.evaluate_batch(pred(), *data["labels"], calc, compact=True, metrics=metrics, labels=lab)
+        return calc
+
+    arms = {"compact": lambda: evaluate("host"), "device": lambda: evaluate("device"),
+            "device_labels": lambda: evaluate("device", labels)}
+    ref = arms["compact"]()
+    same = {}
+    for name in ("device", "device_labels"):
+        got = arms[name]()
+        same[name] = all(int(ref.ap_dict[k]) == int(got.ap_dict[k]) for k in ("tp_corners", "tp_fp_corners", "tp_fn_corners",
+                                                                                "tp_edges", "tp_fp_edges", "tp_fn_edges")) and \
+            all(np.isclose(float(ref.ap_dict[k]), float(got.ap_dict[k]), rtol=1e-12, atol=0.0) for k in ("distance", "wed"))
+    med = blocks_of(arms, blocks, steps, warmup)
+    c = summary(med["compact"])
+    common = {"bench": "evalmetrics", "what": tag or "evaluate", "B": B, "V": V, "max_e": V * (V - 1) // 2, "layout": layout,
+              "kept_edges": data["kept"], "label_edges": int(len(data["labels"][1][0])), "blocks": blocks, "steps_per_block": steps}
+    lines = [dict(common, arm="compact", ms=c)]
+    for name in ("device", "device_labels"):
+        n = summary(med[name])
+        lines.append(dict(common, arm=name, ms=n, same_results=same[name], compact_over_device=round(c["median"] / n["median"], 2),
+                          ahead_by_more_than_the_larger_spread=bool(c["median"] - n["median"] > max(c["block_spread"], n["block_spread"]))))
+    return lines
+
+
 def main():
     p = argparse.ArgumentParser()
     p.add_argument("--blocks", type=int, default=5)
     p.add_argument("--block-steps", type=int, default=7)
     p.add_argument("--warmup", type=int, default=2)
     p.add_argument("--vertices", default="64,256")
-    p.add_argument("--out", default=os.path.join(ROOT, "profiles", "r13_evalpost.jsonl"))
+    p.add_argument("--what", choices=("compact", "metrics"), default="compact")
+    p.add_argument("--out", default=None)
     args = p.parse_args()
+    if args.out is None:
+        args.out = os.path.join(ROOT, "profiles", "r13_evalpost.jsonl" if args.what == "compact" else "r15_evalmetrics.jsonl")
     dev = torch.device("cuda:0")
     ap.set_device(dev)
     gen = np.random.RandomState(0)
+
+    def emit(lines):
+        for r in lines:
+            print(json.dumps(r), flush=True)
+            if args.out:
+                with open(args.out, "a") as f:
+                    f.write(json.dumps(r) + "\n")
+
     for V in (int(v) for v in args.vertices.split(",")):
         data = synthetic(V, gen, dev)
         for layout in ("ragged", "padded"):
-            for r in run(V, layout, data, args):
-                print(json.dumps(r), flush=True)
-                if args.out:
-                    with open(args.out, "a") as f:
-                        f.write(json.dumps(r) + "\n")
+            if args.what == "compact":
+                emit(run(V, layout, data, args))
+            else:
+                emit(run_metrics(V, layout, data, args, 0.1, args.blocks, args.block_steps, args.warmup))
+    if args.what == "metrics":
+        emit(run_metrics(64, "padded", worst_case(gen, dev), args, 0.1, 3, 2, 1, tag="worst_case_all_kept"))
 
 
 if __name__ == "__main__":

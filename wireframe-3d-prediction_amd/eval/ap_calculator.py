@@ -62,6 +62,14 @@ def graph_edit_distance(pd_vertices, pd_edges, gt_vertices, gt_edges, wed_v):
     """Weighted wireframe edit distance (reference :39-88): predicted corners are snapped to their nearest label corner
     (cost: the snap distances, added to `wed_v`), predicted edges that do not exist in the label graph cost their
     length, label edges left unexplained cost theirs; normalised by the total label edge length."""
+    wed_e, wed_v, total = edit_distance_terms(pd_vertices, pd_edges, gt_vertices, gt_edges, wed_v)
+    return (wed_e + wed_v) / total
+
+
+def edit_distance_terms(pd_vertices, pd_edges, gt_vertices, gt_edges, wed_v):
+    """The three terms of graph_edit_distance, which returns (wed_e + wed_v) / total: the edge cost, `wed_v` plus the snap
+    distances, and the total label edge length.  compute_metrics passes the LABEL's own points and edges as the
+    "prediction", so wed_e, the snap distances and total depend on the labels alone (wf3d.postprocess.EvalLabels)."""
     wed_e = 0
     remaining = gt_edges.copy()
     if len(pd_vertices) > 0:
@@ -90,7 +98,7 @@ def graph_edit_distance(pd_vertices, pd_edges, gt_vertices, gt_edges, wed_v):
     total = 0
     for edge in gt_edges:
         total += _length(gt_vertices, edge)
-    return (wed_e + wed_v) / total
+    return wed_e, wed_v, total
 
 
 def computer_edges(edges, vertices):

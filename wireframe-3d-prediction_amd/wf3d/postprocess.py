@@ -8,6 +8,11 @@ Opt-in, for evaluating a data set: device work and host traffic that scale with 
     samples = wireframes_compact(model(x))                 # compaction on the device; B + 1 offsets, then K packed rows
     evaluate_batch(..., compact=True)                      # + all Hausdorff matrices of the batch from one launch
 
+Opt-in on top of that: the metrics themselves on the device (csrc/evalmetrics.hip), the labels prepared once.
+
+    labels = EvalLabels(wf_vertices, wf_edges, device)     # once per label set: device copy + edit-distance constants
+    evaluate_batch(..., compact=True, metrics="device", labels=labels)     # both assignments, corner sets, counters: 4 launches
+
 `hausdorff_lines` is the device form of eval.ap_calculator.hausdorff_distance_line (csrc/evalpost.hip)."""
 import numpy as np
 import torch
@@ -131,6 +136,18 @@ def _as_numpy(x):
     return x.numpy() if torch.is_tensor(x) else np.asarray(x)
 
 
+def _compute_sample(ap_calculator, w, gt_v, gt_e, gt_ev, hd):
+    """compute_metrics on one sample of wireframes_compact with its Hausdorff matrix (None: compute_metrics makes it)."""
+    pd_ev = w["pd_edges_vertices"] if len(w["pd_edges"]) > 0 else np.empty((0, 2, 3))
+    ap_calculator.compute_metrics({"predicted_vertices": w["pred_vertices"][np.newaxis, :],
+                                   "predicted_edges": w["pd_edges"][np.newaxis, :],
+                                   "pred_edges_vertices": pd_ev.reshape((1, -1, 2, 3)),
+                                   "wf_vertices": gt_v[np.newaxis, :],
+                                   "wf_edges": gt_e[np.newaxis, :],
+                                   "wf_edges_vertices": gt_ev.reshape((1, -1, 2, 3)),
+                                   "hausdorff": [hd]})
+
+
 def _evaluate_batch_compact(predictions, wf_vertices, wf_edges, ap_calculator, threshold, sample_points=20):
     """evaluate_batch on the compacted edges: every sample's Hausdorff matrix from ONE launch over the segments that
     wireframes_compact left on the device, the label segments uploaded once, the matrices read back in one copy."""
@@ -165,25 +182,149 @@ def _evaluate_batch_compact(predictions, wf_vertices, wf_edges, ap_calculator, t
         flat = out.cpu().numpy()
         hd = [flat[ooff[s]:ooff[s + 1]].reshape(n[s], m[s]) if n[s] * m[s] > 0 else None for s in range(B)]
     for s, w in enumerate(samples):
-        gt_v, gt_e, gt_ev = gt[s]
-        pd_ev = w["pd_edges_vertices"] if len(w["pd_edges"]) > 0 else np.empty((0, 2, 3))
-        ap_calculator.compute_metrics({"predicted_vertices": w["pred_vertices"][np.newaxis, :],
-                                       "predicted_edges": w["pd_edges"][np.newaxis, :],
-                                       "pred_edges_vertices": pd_ev.reshape((1, -1, 2, 3)),
-                                       "wf_vertices": gt_v[np.newaxis, :],
-                                       "wf_edges": gt_e[np.newaxis, :],
-                                       "wf_edges_vertices": gt_ev.reshape((1, -1, 2, 3)),
-                                       "hausdorff": [hd[s]]})
+        _compute_sample(ap_calculator, w, *gt[s], hd[s])
 
 
-def evaluate_batch(predictions, wf_vertices, wf_edges, ap_calculator, threshold=0.5, compact=False):
+class EvalLabels:
+    """The labels of a batch (or of a whole data set) as evaluate_batch(metrics="device") needs them, built once and
+    reused across batches and epochs:
+      * the host arrays (`verts`, `edges`, `segs`: per sample the label vertices, the int64 edges and the
+        _gt_edge_vertices segments) for the samples that take the host call;
+      * ONE device upload: label vertices, label segments and their offsets (`lvoff`, `loff`, `lverts`, `lseg`);
+      * per sample the label-only constants (wed_e, s, total) of the wireframe edit distance.  compute_metrics calls
+        graph_edit_distance on the label's own points and edges, so the prediction enters only through the scalar
+        `distances`: wed = (wed_e + (distances + s)) / total, in that association, is the reference's value exactly.
+    `host[s]`: the sample's label vertices are not float32 or its label has no edge; it is evaluated by today's
+    per-sample call (and contributes no vertex or segment to the upload).
+    labels[indices] is the EvalLabels of those samples, in that order: equal to a fresh build, without recomputing the
+    constants."""
+
+    def __init__(self, wf_vertices, wf_edges, device, _parts=None):
+        from eval.ap_calculator import computer_edges, edit_distance_terms
+        self.device = torch.device(device)
+        if _parts is not None:
+            self.verts, self.edges, self.segs, self.consts = _parts
+        else:
+            self.verts = [_as_numpy(v) for v in wf_vertices]
+            self.edges = [_as_numpy(e).astype(np.int64) for e in wf_edges]
+            self.segs = [_gt_edge_vertices(v, e) for v, e in zip(self.verts, self.edges)]
+            self.consts = []
+            for gt_v, gt_e, gt_ev in zip(self.verts, self.edges, self.segs):
+                if len(gt_e) == 0:
+                    self.consts.append(None)
+                    continue
+                label_pts = np.unique(gt_ev.reshape(-1, 3), axis=0)
+                self.consts.append(edit_distance_terms(label_pts, computer_edges(gt_ev, label_pts).copy(), gt_v.copy(),
+                                                       gt_e.copy(), 0))
+        B = len(self.verts)
+        self.host = np.array([v.dtype != np.float32 or len(e) == 0 for v, e in zip(self.verts, self.edges)], dtype=bool)
+        self.nverts = np.array([0 if h else len(v) for v, h in zip(self.verts, self.host)], dtype=np.int64)
+        self.nsegs = np.array([0 if h else len(g) for g, h in zip(self.segs, self.host)], dtype=np.int64)
+        lvoff, loff = np.concatenate(([0], np.cumsum(self.nverts))), np.concatenate(([0], np.cumsum(self.nsegs)))
+        if lvoff[-1] >= 2 ** 31 or loff[-1] >= 2 ** 31:
+            raise ValueError("EvalLabels: more than 2^31 label vertices or segments")
+        keep = [s for s in range(B) if not self.host[s]]
+        words = [lvoff.astype(np.int32), loff.astype(np.int32)]
+        words += [np.ascontiguousarray(self.verts[s]).reshape(-1).view(np.int32) for s in keep]
+        words += [np.ascontiguousarray(self.segs[s]).reshape(-1).view(np.int32) for s in keep]
+        up = torch.from_numpy(np.concatenate(words)).to(self.device)     # one upload, as raw 32-bit words
+        nv, ns = 3 * int(lvoff[-1]), 6 * int(loff[-1])
+        self.lvoff, self.loff = up[:B + 1], up[B + 1:2 * B + 2]
+        self.lverts = up[2 * B + 2:2 * B + 2 + nv].view(torch.float32)
+        self.lseg = up[2 * B + 2 + nv:2 * B + 2 + nv + ns].view(torch.float32)
+
+    def __len__(self):
+        return len(self.verts)
+
+    def __getitem__(self, indices):
+        idx = [int(i) for i in (range(*indices.indices(len(self))) if isinstance(indices, slice) else indices)]
+        return EvalLabels(None, None, self.device, _parts=tuple([part[i] for i in idx] for part in
+                                                                (self.verts, self.edges, self.segs, self.consts)))
+
+    def wed(self, s, distances):
+        """The reference's wireframe edit distance of sample s given its corner distance sum."""
+        wed_e, snap, total = self.consts[s]
+        return (wed_e + (distances + snap)) / total
+
+
+def _evaluate_batch_device(predictions, wf_vertices, wf_edges, ap_calculator, threshold, labels, sample_points=20):
+    """evaluate_batch(compact=True) with everything that follows the Hausdorff matrices on the device too
+    (wf3d_eval_metrics): the matrices stay there, [B] distances and [B, 8] counters come back in one copy."""
+    if labels is None:
+        labels = EvalLabels(wf_vertices, wf_edges, predictions["vertices"].device)
+    samples, d = wireframes_compact(predictions, threshold, keep_device=True)
+    B = len(samples)
+    dev = d["seg"].device
+    if len(labels) != B or labels.device != dev:
+        raise ValueError(f"evaluate_batch(metrics='device'): labels of {len(labels)} samples on {labels.device} for a batch "
+                         f"of {B} on {dev}")
+    verts = predictions["vertices"].detach().float()
+    if verts.stride(2) != 1:
+        verts = verts.contiguous()
+    V = verts.shape[1]
+    n = np.diff(d["koff_host"]).astype(np.int64)
+    m = labels.nsegs
+    ooff = np.concatenate(([0], np.cumsum(n * m)))
+    aoff = np.concatenate(([0], np.cumsum(np.minimum(n, m))))
+    if aoff[-1] >= 2 ** 31:
+        raise ValueError("evaluate_batch(metrics='device'): more than 2^31 assignment entries in one batch")
+    lib = _lib.load()
+    # one upload: ooff (int64, 8-byte aligned at the front) | aoff, as raw 32-bit words
+    up = torch.from_numpy(np.concatenate((ooff.astype(np.int64).view(np.int32), aoff.astype(np.int32)))).to(dev)
+    d_ooff, d_aoff = up[:2 * (B + 1)].view(torch.int64), up[2 * (B + 1):]
+    hd = torch.empty(max(int(ooff[-1]), 1), dtype=torch.float64, device=dev)
+    if ooff[-1] > 0:
+        check(lib.wf3d_hausdorff_lines_batch(d["seg"].data_ptr(), d["koff"].data_ptr(), labels.lseg.data_ptr(),
+                                             labels.loff.data_ptr(), d_ooff.data_ptr(), B, int((n * m).max()),
+                                             int(sample_points), hd.data_ptr(), _stream()), "hausdorff_lines_batch")
+    assign = torch.empty(max(int(aoff[-1]), 1), dtype=torch.int32, device=dev)
+    out = torch.empty(2 * B + 8 * B, dtype=torch.int32, device=dev)      # [B] float64 distances | [B, 8] int32 counters
+    total_lv, max_lv = int(labels.nverts.sum()), int(labels.nverts.max()) if B else 0
+    max_long = int(max(n.max(), m.max())) if B else 0
+    ws_bytes = lib.wf3d_eval_metrics_ws_bytes(B, V, total_lv, max_long)
+    ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=dev)
+    check(lib.wf3d_eval_metrics(verts.data_ptr(), verts.stride(0), verts.stride(1), B, V, d["seg"].data_ptr(),
+                                d["koff"].data_ptr(), labels.lverts.data_ptr(), labels.lvoff.data_ptr(), labels.lseg.data_ptr(),
+                                labels.loff.data_ptr(), hd.data_ptr(), d_ooff.data_ptr(), d_aoff.data_ptr(), assign.data_ptr(),
+                                float(ap_calculator.distance_thresh), max_lv, total_lv, max_long, out[2 * B:].data_ptr(),
+                                out.data_ptr(), ws.data_ptr(), ws_bytes, _stream()), "eval_metrics")
+    words = out.cpu().numpy()                                            # the one copy back
+    dist, cnt = words[:2 * B].view(np.float64), words[2 * B:].reshape(B, 8)
+    names = ("tp_corners", "tp_fp_corners", "tp_fn_corners", "tp_edges", "tp_fp_edges", "tp_fn_edges")
+    for s, w in enumerate(samples):
+        if labels.host[s] or cnt[s, 6] != 0:
+            # today's per-sample call, with the sample's own matrix where the batch launch made one
+            mat = hd[ooff[s]:ooff[s + 1]].cpu().numpy().reshape(n[s], m[s]) if n[s] * m[s] > 0 else None
+            _compute_sample(ap_calculator, w, labels.verts[s], labels.edges[s], labels.segs[s], mat)
+            continue
+        ap_calculator.batch_size = 1
+        for k, name in enumerate(names):
+            ap_calculator.ap_dict[name] += int(cnt[s, k])
+        ap_calculator.ap_dict["distance"] += dist[s]
+        ap_calculator.ap_dict["wed"] += labels.wed(s, dist[s]) if n[s] > 0 else 1
+
+
+def evaluate_batch(predictions, wf_vertices, wf_edges, ap_calculator, threshold=0.5, compact=False, metrics="host", labels=None):
     """The body of the reference's evaluation loop (evaluate.py:74-110) for one batch: `wf_vertices` / `wf_edges` are the
     collate_batch lists of tensors; accumulates into `ap_calculator`.
     compact=True: the kept edges are compacted on the device (wireframes_compact) and all Hausdorff matrices of the batch
     come from one launch (wf3d_hausdorff_lines_batch) and one copy each way; `ap_calculator.compute_metrics` receives
     them as batch["hausdorff"].  Three kinds of sample silently take today's per-sample call instead: one that keeps no
     edge (the corners-only branch needs no matrix), one whose label has no edge, and one whose label vertices are not
-    float32 (the batched kernel forms the segment directions in float32, which is the common dtype only then)."""
+    float32 (the batched kernel forms the segment directions in float32, which is the common dtype only then).
+    metrics="device" (with compact=True): the two assignments, the corner sets, the counters and the corner distance sum
+    of every sample come from the device as well (wf3d_eval_metrics; csrc/evalmetrics.hip), the Hausdorff matrices are not
+    copied back, and `labels` may be an EvalLabels built once for these samples (else one is built here from
+    wf_vertices / wf_edges, which are otherwise unused).  A sample the device flags (a non-finite value, kept edges of
+    which none matches — the reference raises there, and so does this —, a matched end point that is no vertex row), one
+    whose label vertices are not float32 and one whose label has no edge take today's per-sample call.  Where a sample's
+    optimal assignment is not unique, the device's choice (the tie rule of tests/lsa_model.py) may differ from scipy's."""
+    if metrics not in ("host", "device"):
+        raise ValueError(f"evaluate_batch: metrics must be 'host' or 'device' (got {metrics!r})")
+    if metrics == "device":
+        if not compact:
+            raise ValueError("evaluate_batch: metrics='device' needs compact=True")
+        return _evaluate_batch_device(predictions, wf_vertices, wf_edges, ap_calculator, threshold, labels)
     if compact:
         return _evaluate_batch_compact(predictions, wf_vertices, wf_edges, ap_calculator, threshold)
     for s, w in enumerate(wireframes_from_predictions(predictions, threshold)):
