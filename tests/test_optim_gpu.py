@@ -30,7 +30,9 @@ def test_clip_adam_matches_torch_over_several_steps(max_norm):
     opt = ClipAdam(pb, lr=1e-3, weight_decay=1e-6, max_norm=max_norm, norm_params=lambda: pb + [lazy_b])
     for step in range(4):
         grads = _make(10 + step, shapes + [(512, 1024)])
-        scale = 3.0 if step % 2 else 0.01                     # both sides of the clip threshold
+        # two gradient scales, BOTH above max_norm = 1 (0.01 over 3.2 M elements is a norm of about 18): only the
+        # max_norm = 1e9 and None runs here step unclipped; tests/test_optim_forms_gpu.py has both sides of the threshold
+        scale = 3.0 if step % 2 else 0.01
         ref.zero_grad(); opt.zero_grad()
         for p, q, g in zip(pa + [lazy_a], pb + [lazy_b], grads):
             # the lazy parameter's gradient ACCUMULATES (no optimizer ever zeroes it), as in the reference

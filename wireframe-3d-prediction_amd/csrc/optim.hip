@@ -103,8 +103,8 @@ __global__ __launch_bounds__(256) void gradsq_kernel(const SqArgs a, float* __re
 
 template <bool DEV>
 __global__ __launch_bounds__(256) void clip_adam_kernel(const AdamArgs a, const float* __restrict__ partials, int npart,
-                                                         float max_norm, float lr, float omb1, float beta2, float omb2,
-                                                         float eps, float wd, float bc1, float bc2_sqrt,
+                                                         float max_norm, float lr, float beta1, float omb1, float beta2,
+                                                         float omb2, float eps, float wd, float bc1, float bc2_sqrt,
                                                          float* __restrict__ norm_out, const AdamDev dv) {
     __shared__ float s_red[4];
     if (DEV) {
@@ -134,7 +134,9 @@ __global__ __launch_bounds__(256) void clip_adam_kernel(const AdamArgs a, const 
     auto upd = [&](float& pp, float& gg, float& mm, float& vv) {
         gg *= coef;                                   // the clipped gradient is what stays in .grad
         const float ge = fmaf(wd, pp, gg);            // L2 weight decay folded into the gradient (torch Adam)
-        mm = fmaf(omb1, ge - mm, mm);                 // exp_avg.lerp_(grad, 1 - beta1)
+        // exp_avg.lerp_(grad, 1 - beta1), from the nearer end as torch.lerp does: at beta1 <= 0.5 (weight >= 0.5) the
+        // form m + w (ge - m) leaves a rounding of m's size in a result of ge's size, which sqrt(v) ~ |ge| then divides
+        mm = omb1 < 0.5f ? fmaf(omb1, ge - mm, mm) : fmaf(-beta1, ge - mm, ge);
         vv = fmaf(omb2 * ge, ge, beta2 * vv);         // exp_avg_sq.mul_(beta2).addcmul_(grad, grad, value = 1 - beta2)
         pp -= step * (mm / (sqrtf(vv) / bc2_sqrt + eps));
     };
@@ -216,11 +218,11 @@ static int clip_adam_launch(const char* fn, float* const* params, float* const* 
         for (int i = nt; i <= OPT_MAXT; ++i) a.blk_begin[i] = blk;
         if (dv)
             hipLaunchKernelGGL(clip_adam_kernel<true>, dim3(blk), dim3(256), 0, st, a, ws, npart, (float)max_norm, (float)lr,
-                               (float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2), (float)eps, (float)weight_decay, 0.f,
+                               (float)beta1, (float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2), (float)eps, (float)weight_decay, 0.f,
                                0.f, t0 == 0 ? total_norm : nullptr, *dv);
         else
             hipLaunchKernelGGL(clip_adam_kernel<false>, dim3(blk), dim3(256), 0, st, a, ws, npart, (float)max_norm, (float)lr,
-                               (float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2), (float)eps, (float)weight_decay, bc1,
+                               (float)beta1, (float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2), (float)eps, (float)weight_decay, bc1,
                                bc2_sqrt, t0 == 0 ? total_norm : nullptr, AdamDev{});
         WF3D_LAUNCH_CHECK();
     }

@@ -25,6 +25,8 @@ from .ops import _p, _stream
 class TrainMeter:
     def __init__(self, device, history=4096):
         self.capacity = int(history)
+        if self.capacity < 0:
+            raise ValueError(f"wf3d.TrainMeter: history must be >= 0, got {history}")
         self.state = torch.zeros(8 + self.capacity, dtype=torch.float32, device=device)
 
     @torch.no_grad()
@@ -61,7 +63,7 @@ class TrainMeter:
         steps = int(s[0])
         n = min(steps, self.capacity)
         ring = s[8:8 + self.capacity]
-        if steps <= self.capacity:
+        if steps <= self.capacity or self.capacity == 0:       # history=0: no ring, the other fields as usual
             hist = ring[:n]
         else:
             k = steps % self.capacity
