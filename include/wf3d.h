@@ -169,6 +169,15 @@ int wf3d_ln_prep(const float* z, int R, int D, const float* gamma, const float* 
 int wf3d_first_layer_fwd(const float* x, int R, int K, int ldx, const float* W, int ldw, const float* bias, int D,
                          const float* gamma, const float* beta, int act, float eps, float* z, float* mu, float* rs,
                          void* h_sx8, void* stream);
+/* The same with the train-mode dropout that follows the activation (PointNetEncoder.mlp[3], p > 0 in train() mode):
+ * h = drop(act(LN(z))) — exact zeros where element (row, col) is dropped, the kept value times 1 / (1 - drop_p) in fp32
+ * elsewhere, the keep bit that of every other mask kernel for (drop_seed, row, col) — while z, mu and rs are the bits
+ * wf3d_first_layer_fwd writes.  drop_seed is a value, or an index into the calling thread's device seed words
+ * (wf3d_set_dropout_seed_words); the live-row count is honoured as by wf3d_first_layer_fwd.  drop_p = 0 (or below 2^-32)
+ * is wf3d_first_layer_fwd itself: the same launch, no seed is read. */
+int wf3d_first_layer_fwd_drop(const float* x, int R, int K, int ldx, const float* W, int ldw, const float* bias, int D,
+                              const float* gamma, const float* beta, int act, float eps, float drop_p, uint32_t drop_seed,
+                              float* z, float* mu, float* rs, void* h_sx8, void* stream);
 /* ... and its backward: LayerNorm/activation backward of layer 0 that also accumulates that layer's weight
  * gradient dW[D, K] = dz^T·x (K more weighted column sums) and never writes dz (the input takes no gradient).
  * dgamma, dbeta, dbias must be one contiguous [3][D] buffer. */
@@ -176,6 +185,13 @@ size_t wf3d_ln_act_bwd_first_ws_bytes(int R, int D);
 int wf3d_ln_act_bwd_first(const float* dh, const float* z, const float* x, int R, int D, int K, int ldx,
                           const float* mu, const float* rs, const float* gamma, const float* beta, int act,
                           float* dgamma, float* dbeta, float* dbias, float* dW, void* ws, size_t ws_bytes, void* stream);
+/* The same as the backward of wf3d_first_layer_fwd_drop: dh is multiplied by the mask of (drop_seed, row, col) and
+ * 1 / (1 - drop_p) where the row enters, so dgamma, dbeta, dbias and dW are sums over the masked dh.  Workspace, buffers
+ * and the live-row count as wf3d_ln_act_bwd_first, which is this call with drop_p = 0. */
+int wf3d_ln_act_bwd_first_drop(const float* dh, const float* z, const float* x, int R, int D, int K, int ldx,
+                               const float* mu, const float* rs, const float* gamma, const float* beta, int act,
+                               float drop_p, uint32_t drop_seed, float* dgamma, float* dbeta, float* dbias, float* dW,
+                               void* ws, size_t ws_bytes, void* stream);
 /* LayerNorm / activation backward that also returns one weighted column sum of the dz it produces,
  * wsum[c] = sum_r dz[r, c] * wrow[r] — for the first edge layer (models/EdgePredictor.py:130-137) the gradient of the
  * weight column that multiplies the pair distance — instead of a second pass over dz.  dgamma, dbeta: one [2][D] buffer. */
@@ -659,8 +675,8 @@ int wf3d_set_dropout_seed_words(const uint32_t* words);
  *                                              exact zeros.  The caller runs that GEMM WITHOUT a count (its rows are a
  *                                              weight dimension): the zero columns add exact zeros in its unchanged
  *                                              split-K order, as the zero backward tail does without a count.
- *   wf3d_first_layer_fwd                       R, both kernel forms: z, mu, rs and h_sx8 are written for rows < R256 only
- *   wf3d_ln_act_bwd_first                      R; dgamma / dbeta / dbias and dW are sums over [0, R256)
+ *   wf3d_first_layer_fwd, _fwd_drop            R, every kernel form: z, mu, rs and h_sx8 are written for rows < R256 only
+ *   wf3d_ln_act_bwd_first, _first_drop         R; dgamma / dbeta / dbias and dW are sums over [0, R256)
  *   wf3d_point_valid                           M
  *   wf3d_pool4_seg_bwd, wf3d_pool4_seg_bwd_sx8 M_pad, with the count in rows of the packed batch (the layout's
  *                                              rows[B]): a pad chunk (-1, 0, r0, r1) zero-fills [r0, min(r1, R256)).

@@ -643,18 +643,28 @@ extern "C" int wf3d_ln_act_bwd(const float* dh, const float* z, int R, int D, co
 
 extern "C" size_t wf3d_ln_act_bwd_first_ws_bytes(int R, int D) { return ln_bwd_ws_bytes(R, D, 8); }
 
-extern "C" int wf3d_ln_act_bwd_first(const float* dh, const float* z, const float* x, int R, int D, int K, int ldx,
-                                     const float* mu, const float* rs, const float* gamma, const float* beta, int act,
-                                     float* dgamma, float* dbeta, float* dbias, float* dW, void* ws, size_t ws_bytes,
-                                     void* stream) {
+// The first layer's LayerNorm / activation backward with the layer's dropout re-applied to dh (drop_p = 0: none): the
+// mask multiplies dh where the row enters, so dgamma, dbeta, dbias and the weight-gradient sums all see the masked dh.
+extern "C" int wf3d_ln_act_bwd_first_drop(const float* dh, const float* z, const float* x, int R, int D, int K, int ldx,
+                                          const float* mu, const float* rs, const float* gamma, const float* beta, int act,
+                                          float drop_p, uint32_t drop_seed, float* dgamma, float* dbeta, float* dbias,
+                                          float* dW, void* ws, size_t ws_bytes, void* stream) {
     WF3D_CHECK(R > 0 && D > 0 && K > 0 && K <= 8 && ldx >= K, WF3D_ERR_UNSUPPORTED, "wf3d_ln_act_bwd_first: needs R > 0, 1 <= K <= 8");
-    // no dropout on this layer, and dz — which nothing else needs — is not written
-    LnBwdCall c{"wf3d_ln_act_bwd_first", ws, ws_bytes, stream, dh, z, R, D, mu, rs, gamma, beta, act, 0.f, 0u, nullptr, nullptr, x, ldx, K};
+    // dz — which nothing else needs — is not written
+    LnBwdCall c{"wf3d_ln_act_bwd_first", ws, ws_bytes, stream, dh, z, R, D, mu, rs, gamma, beta, act, drop_p, drop_seed, nullptr, nullptr, x, ldx, K};
     c.ptrs_ok = dh && z && x && mu && rs && gamma && beta && dgamma && dbeta && dbias && dW &&
                 dbeta == dgamma + D && dbias == dbeta + D;             // one [3][D] buffer
     c.sums[0] = {0, 3 * D, dgamma};
     c.sums[1] = {(size_t)3 * D, D * K, dW, D, K};      // [K][D] partials -> the weight's own [D][K]
     return ln_bwd_launch<8, false>(c);
+}
+
+extern "C" int wf3d_ln_act_bwd_first(const float* dh, const float* z, const float* x, int R, int D, int K, int ldx,
+                                     const float* mu, const float* rs, const float* gamma, const float* beta, int act,
+                                     float* dgamma, float* dbeta, float* dbias, float* dW, void* ws, size_t ws_bytes,
+                                     void* stream) {
+    return wf3d_ln_act_bwd_first_drop(dh, z, x, R, D, K, ldx, mu, rs, gamma, beta, act, 0.f, 0u, dgamma, dbeta, dbias, dW, ws,
+                                      ws_bytes, stream);
 }
 
 extern "C" size_t wf3d_ln_act_bwd_wsum_ws_bytes(int R, int D) { return ln_bwd_ws_bytes(R, D, 1); }

@@ -211,18 +211,25 @@ __global__ __launch_bounds__(256) void ln_prep_kernel(const float* __restrict__ 
 // extent.  !KEEP is the forward-only form (wf3d.infer): z, mu, rs and live_rows are not touched, which is worth a wave
 // of occupancy at NS = 1.  One body, so the h of the two forms is the same expressions in the same order: bit for bit.
 // FAST: K == 8, D a multiple of 512, 16-byte aligned x / W rows and ReLU — two float4 loads per row, no per-element branches.
-template <int NS, bool FAST, bool KEEP>
+// DROP: the train-mode dropout behind the ReLU (PointNetEncoder.mlp[3]): h = keep(seed, row, col) ? act(LN(z)) * dscale : 0,
+// the mask a function of (row, col) alone, so the backward and a wgrad that re-applies it recompute the same bits.  z, mu
+// and rs are those of the !DROP form.  The hash is ~10 integer VALU operations per element beside the pass's 8 FMAs and
+// two bf16 roundings; !DROP compiles none of it and is the code that ran before the template parameter existed.
+template <int NS, bool FAST, bool KEEP, bool DROP = false>
 __global__ __launch_bounds__(256) void first_layer_kernel(const float* __restrict__ x, int ldx, int K,
                                                            const float* __restrict__ W, int ldw,
                                                            const float* __restrict__ bias, int R, int D,
                                                            const float* __restrict__ gamma, const float* __restrict__ beta,
                                                            int act, float eps, float* __restrict__ z,
                                                            float* __restrict__ mu, float* __restrict__ rs,
-                                                           float* __restrict__ h_sx8, const int32_t* __restrict__ live_rows) {
+                                                           float* __restrict__ h_sx8, const int32_t* __restrict__ live_rows,
+                                                           const wf3d_seed_t seed_src = wf3d_seed_t{0u, nullptr},
+                                                           uint32_t thresh = 0u, float dscale = 1.f) {
     // one scalar load at entry, before the W slice: the row walk and the prefetch clamp below stop at the extent, so no
     // row at or past it is read or written (z, mu, rs, h_sx8)
     if (KEEP) R = wf3d_live_extent(live_rows, R);
     if (R == 0) return;
+    const uint32_t seed = DROP ? wf3d_seed_load(seed_src) : 0u;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const bool odd = lane & 1;
     // columns of a lane, slot i: [512 i + 4 lane, +4) (values 0..3) and [512 i + 256 + 4 lane, +4) (values 4..7)
@@ -317,6 +324,7 @@ __global__ __launch_bounds__(256) void first_layer_kernel(const float* __restric
                     for (int j = 0; j < 4; ++j) {
                         const float y0 = (v[i][4 * hf + j] - mean) * rstd * gm[i][4 * hf + j] + bt[i][4 * hf + j];
                         o[j] = FAST ? fmaxf(y0, 0.f) : wf3d_act_rt(act, y0);
+                        if (DROP) o[j] = wf3d_keep(seed, (uint32_t)row, (uint32_t)(c + j), thresh) ? o[j] * dscale : 0.f;
                     }
                     wf3d_store_sx8_pair(h_sx8 + (size_t)row * D + c, o, odd);
                 }
@@ -476,12 +484,13 @@ extern "C" int wf3d_ln_prep(const float* z, int R, int D, const float* gamma, co
 }
 
 // Both first-layer entry points.  `keep`: the training forward (z, mu, rs kept, the thread's live-row count honoured).
-static int first_layer_launch(const char* who, bool keep, const float* x, int R, int K, int ldx, const float* W, int ldw,
+static int first_layer_launch(const char* who, bool keep, float drop_p, uint32_t drop_seed, const float* x, int R, int K, int ldx, const float* W, int ldw,
                               const float* bias, int D, const float* gamma, const float* beta, int act, float eps, float* z,
                               float* mu, float* rs, void* h_sx8, void* stream) {
     WF3D_CHECK(R >= 0 && K > 0 && K <= 8 && ldx >= K && ldw >= K, WF3D_ERR_UNSUPPORTED, "%s: needs 1 <= K <= 8 (K=%d)", who, K);
     WF3D_CHECK(D > 0 && D % 8 == 0 && D <= 1024, WF3D_ERR_UNSUPPORTED, "%s: D=%d must be a multiple of 8, <= 1024", who, D);
     WF3D_CHECK(act >= 0 && act <= 2, WF3D_ERR_ARG, "%s: bad act", who);
+    WF3D_CHECK(drop_p >= 0.f && drop_p < 1.f && (keep || drop_p == 0.f), WF3D_ERR_ARG, "%s: bad drop_p", who);
     if (R == 0) return WF3D_OK;
     WF3D_CHECK(x && W && gamma && beta && h_sx8 && (!keep || (z && mu && rs)), WF3D_ERR_ARG, "%s: null pointer", who);
     WF3D_CHECK(((uintptr_t)z % 16 == 0) && ((uintptr_t)h_sx8 % 16 == 0) && ((uintptr_t)gamma % 16 == 0) &&
@@ -495,13 +504,19 @@ static int first_layer_launch(const char* who, bool keep, const float* x, int R,
     const bool fast = K == 8 && ldx % 4 == 0 && ((uintptr_t)x % 16 == 0) && act == WF3D_ACT_RELU && D % 512 == 0 && ldw % 4 == 0 &&
                       ((uintptr_t)W % 16 == 0) && (!bias || (uintptr_t)bias % 16 == 0);
     const int32_t* live = keep ? wf3d_live_rows() : nullptr;
+    // a drop_p below 2^-32 has threshold 0: nothing is dropped, and the launch is the one without a mask
+    const wf3d_drop_t drop = wf3d_drop_args(drop_p, drop_seed);
 #define WF3D_FL(NS_, F_, K_)                                                                                                \
     hipLaunchKernelGGL((first_layer_kernel<NS_, F_, K_>), dim3(blocks), dim3(256), 0, st, x, ldx, K, W, ldw, bias, R, D, gamma, \
                        beta, act, eps, z, mu, rs, (float*)h_sx8, live)
-#define WF3D_FLK(NS_, F_) do { if (keep) WF3D_FL(NS_, F_, true); else WF3D_FL(NS_, F_, false); } while (0)
+#define WF3D_FLD(NS_, F_)                                                                                                   \
+    hipLaunchKernelGGL((first_layer_kernel<NS_, F_, true, true>), dim3(blocks), dim3(256), 0, st, x, ldx, K, W, ldw, bias, R, D, \
+                       gamma, beta, act, eps, z, mu, rs, (float*)h_sx8, live, drop.seed, drop.thresh, drop.scale)
+#define WF3D_FLK(NS_, F_) do { if (drop.thresh) WF3D_FLD(NS_, F_); else if (keep) WF3D_FL(NS_, F_, true); else WF3D_FL(NS_, F_, false); } while (0)
     if (D <= 512) { if (fast) WF3D_FLK(1, true); else WF3D_FLK(1, false); }
     else          { if (fast) WF3D_FLK(2, true); else WF3D_FLK(2, false); }
 #undef WF3D_FLK
+#undef WF3D_FLD
 #undef WF3D_FL
     WF3D_LAUNCH_CHECK();
     return WF3D_OK;
@@ -510,15 +525,23 @@ static int first_layer_launch(const char* who, bool keep, const float* x, int R,
 extern "C" int wf3d_first_layer_fwd(const float* x, int R, int K, int ldx, const float* W, int ldw, const float* bias,
                                     int D, const float* gamma, const float* beta, int act, float eps, float* z,
                                     float* mu, float* rs, void* h_sx8, void* stream) {
-    return first_layer_launch("wf3d_first_layer_fwd", true, x, R, K, ldx, W, ldw, bias, D, gamma, beta, act, eps, z, mu, rs,
-                              h_sx8, stream);
+    return first_layer_launch("wf3d_first_layer_fwd", true, 0.f, 0u, x, R, K, ldx, W, ldw, bias, D, gamma, beta, act, eps, z,
+                              mu, rs, h_sx8, stream);
+}
+
+// The same with the train-mode dropout behind the activation: h = drop(act(LN(z))).  drop_p = 0 is wf3d_first_layer_fwd.
+extern "C" int wf3d_first_layer_fwd_drop(const float* x, int R, int K, int ldx, const float* W, int ldw, const float* bias,
+                                         int D, const float* gamma, const float* beta, int act, float eps, float drop_p,
+                                         uint32_t drop_seed, float* z, float* mu, float* rs, void* h_sx8, void* stream) {
+    return first_layer_launch("wf3d_first_layer_fwd_drop", true, drop_p, drop_seed, x, R, K, ldx, W, ldw, bias, D, gamma, beta,
+                              act, eps, z, mu, rs, h_sx8, stream);
 }
 
 // The forward-only form: no z, mu or rs, and no live-row count (wf3d.infer walks row blocks of its own).
 extern "C" int wf3d_first_layer_infer(const float* x, int R, int K, int ldx, const float* W, int ldw, const float* bias,
                                       int D, const float* gamma, const float* beta, int act, float eps, void* h_sx8,
                                       void* stream) {
-    return first_layer_launch("wf3d_first_layer_infer", false, x, R, K, ldx, W, ldw, bias, D, gamma, beta, act, eps, nullptr,
+    return first_layer_launch("wf3d_first_layer_infer", false, 0.f, 0u, x, R, K, ldx, W, ldw, bias, D, gamma, beta, act, eps, nullptr,
                               nullptr, nullptr, h_sx8, stream);
 }
 

@@ -27,10 +27,26 @@ class PointCloudToWireframe(nn.Module):
         self._edge_tail = "compute"
 
     def set_dropout(self, p):
-        """Set every dropout probability of the edge head (the only non-zero ones)."""
+        """Set every dropout probability of the edge head (the only non-zero ones by default)."""
         ep = self.edge_predictor
         ep.vertex_proj[5].p = ep.edge_mlp[3].p = ep.edge_mlp[7].p = float(p)
         ep.attention.dropout = float(p)
+        return self
+
+    def set_encoder_dropout(self, p):
+        """Set the dropout probability behind every Linear, LayerNorm, ReLU block of the encoder's per-point MLP
+        (encoder.mlp[3], [7], ...; 0.0 by default).  Returns self."""
+        for m in self.encoder.mlp:
+            if isinstance(m, nn.Dropout):
+                m.p = float(p)
+        return self
+
+    def set_vertex_dropout(self, p):
+        """Set the dropout probability that closes each of the vertex head's four stages (vertex_mlp{1..4}[3]; 0.0 by
+        default).  Returns self."""
+        vp = self.vertex_predictor
+        for st in (vp.vertex_mlp1, vp.vertex_mlp2, vp.vertex_mlp3, vp.vertex_mlp4):
+            st[3].p = float(p)
         return self
 
     def _host_counts(self, t, slot="_count_cache"):
@@ -94,11 +110,11 @@ class PointCloudToWireframe(nn.Module):
                 "edge_counts": ecounts,
                 "edge_width": width}
 
-    @staticmethod
-    def _stream():
-        """The encoder stage takes the forward-only path (wf3d.infer): the setting asks for it and grad mode is off.
-        train() / eval() does not enter the decision."""
-        return config.inference() == "stream" and not torch.is_grad_enabled()
+    def _stream(self):
+        """The encoder stage takes the forward-only path (wf3d.infer): the setting asks for it, grad mode is off and no
+        dropout site of the encoder is active (the block walk draws no masks; EdgePredictor._stream's rule).  Without
+        an active site train() / eval() does not enter the decision."""
+        return config.inference() == "stream" and not torch.is_grad_enabled() and self.encoder._stream_ok()
 
     def forward(self, point_cloud, target_vertex_counts=None):
         if self._stream():

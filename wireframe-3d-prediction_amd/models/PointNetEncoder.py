@@ -4,12 +4,15 @@ Same constructor, attribute names and state_dict keys as the reference class
 (reference models/PointNetEncoder.py:19-65: `mlp` Sequential with parameters at
 indices 0,1,4,5,...,4n and `feature_fusion` at 0,1,3,4,6).  The nn modules here
 are parameter containers only: forward never calls them, it hands their tensors
-to wf3d.functional.EncoderFn (HIP kernels through the C ABI)."""
+to wf3d.functional.EncoderFn (HIP kernels through the C ABI).  The `nn.Dropout` after each
+Linear, LayerNorm, ReLU block of `mlp` (p = 0.0 by default, as in the reference) is honoured in
+train() mode: its `p` is read on every call and the kernels draw the masks."""
 import torch
 import torch.nn as nn
 
 from wf3d import config, infer, ops
-from wf3d.functional import EncoderFn, EncoderFnPacked, EncoderFnPackedSkip, FusionFn
+from wf3d.functional import Drop, EncoderFn, EncoderFnPacked, EncoderFnPackedSkip, FusionFn
+from wf3d.random import default_generator
 
 
 def _point_block(n_in, n_out):
@@ -40,8 +43,11 @@ class PointNetEncoder(nn.Module):
             nn.Linear(4 * d, 2 * d), nn.LayerNorm(2 * d), nn.ReLU(inplace=True),
             nn.Linear(2 * d, d))
         self._n_hidden = len(hidden_dims)
+        self._site_keys = tuple(str(4 * i + 3) for i in range(len(hidden_dims)))      # mlp's nn.Dropout modules
         self.precision = None          # None -> wf3d.config.precision() ("bf16x3" | "bf16" | "fp32")
         self._packed_tail = "compute"  # set_packed_tail
+        self.last_dropout_seed = None       # the seed the last train-mode call with an active site drew on the host
+        self.last_dropout_seeds = None      # dropout_rng "device": the int32 [5] seed words of that call instead
 
     def _mlp_params(self):
         ps = []
@@ -57,13 +63,51 @@ class PointNetEncoder(nn.Module):
                 ff[3].weight, ff[3].bias, ff[4].weight, ff[4].bias,
                 ff[6].weight, ff[6].bias]
 
+    def _dropout_ps(self):
+        """The probabilities of the sites mlp.{4i+3}, i = 0 .. n_hidden-1, of this call: all 0 outside train mode."""
+        if not self.training:
+            return (0.0,) * self._n_hidden
+        # plain dict lookups (this runs on every forward; Sequential.__getitem__ walks its modules): whatever module sits
+        # at the index now, a replaced nn.Dropout included
+        mods = self._modules["mlp"]._modules
+        ps = tuple([mods[k].p for k in self._site_keys])
+        if not any(ps):                      # every site at 0: nothing to check
+            return ps
+        for i, p in enumerate(ps):
+            if not 0.0 <= float(p) < 1.0:
+                # torch would zero the whole site at p = 1; the dropout kernels take p in [0, 1) (INTEGRATION.md)
+                raise ValueError(f"PointNetEncoder: dropout p = {p} at mlp.{4 * i + 3} is not supported by the HIP encoder in "
+                                 "train mode (needs 0 <= p < 1)")
+        return ps
+
+    def _dropout(self, device):
+        """The trailing arguments of this call's EncoderFn: nothing while no site is active (no seed is drawn, every
+        launch is the one without a mask), else one Drop(ps, seed) — the seed drawn as EdgePredictor._dropout draws
+        its own, one value per module and forward."""
+        ps = self._dropout_ps()
+        if not any(ps):
+            return ()
+        if config.dropout_rng() == "device":
+            if any(ps[4:]):
+                raise ValueError(f"PointNetEncoder: dropout_rng 'device' draws five seed words per forward, which serve the "
+                                 f"first four sites; mlp.{4 * max(i for i, p in enumerate(ps) if p) + 3} is active "
+                                 "(set it to 0, or use wf3d.config.set_dropout_rng('host'))")
+            seed = self.last_dropout_seeds = default_generator(device).draw()
+        else:
+            seed = self.last_dropout_seed = int(torch.empty((), dtype=torch.int64).random_().item())
+        return (Drop(ps, seed),)
+
+    def _stream_ok(self):
+        """The forward-only path draws no masks: it serves a call only while no dropout site is active."""
+        return not any(self._dropout_ps())
+
     def encode(self, x):
         """(global, point_features, unmasked_pooled [B, 2C] = [mean | max]): the extra pools are what
         VertexPredictor would recompute from point_features (VertexPredictor.py:86-88)."""
         if x.dim() != 3:
             raise ValueError(f"expected (batch, num_points, input_dim), got {tuple(x.shape)}")
         pooled, pf, upooled = EncoderFn.apply(x.float(), self._n_hidden, self.precision or config.precision(),
-                                              *self._mlp_params())
+                                              *self._mlp_params(), *self._dropout(x.device))
         g = FusionFn.apply(pooled, *self._fusion_params())
         return g, pf, upooled
 
@@ -116,7 +160,7 @@ class PointNetEncoder(nn.Module):
         layout = self._packed_layout(points, point_counts, capacity)
         fn = EncoderFnPackedSkip if tail == "skip" else EncoderFnPacked
         pooled, pf, upooled = fn.apply(points.float(), layout, self._n_hidden, self.precision or config.precision(),
-                                       *self._mlp_params())
+                                       *self._mlp_params(), *self._dropout(points.device))
         g = FusionFn.apply(pooled, *self._fusion_params())
         return g, pf, upooled, layout
 
@@ -149,7 +193,9 @@ class PointNetEncoder(nn.Module):
         """encode() on the forward-only path (wf3d.infer): the per-point MLP walks the B * N rows in blocks of `rows`
         (a positive multiple of 8; None: wf3d.config.INFER_ROWS), keeps nothing for a backward and pools the blocks as
         they pass.  Returns (global, point_features [B, N, C] if want_pf else None, unmasked_pooled); runs under
-        torch.no_grad() whatever the caller's grad mode."""
+        torch.no_grad() whatever the caller's grad mode.  It has no dropout: ValueError while a site of `mlp` is active
+        (train mode with p > 0)."""
+        self._check_stream("encode_stream")
         if x.dim() != 3:
             raise ValueError(f"expected (batch, num_points, input_dim), got {tuple(x.shape)}")
         if not x.is_cuda:
@@ -169,8 +215,14 @@ class PointNetEncoder(nn.Module):
         host.  The packed tail mode does not apply: there is no backward whose rows could be skipped."""
         return self._encode_packed_stream(points, point_counts, capacity, want_pf, rows)[:3]
 
+    def _check_stream(self, who):
+        if not self._stream_ok():
+            raise ValueError(f"PointNetEncoder.{who}: the forward-only path has no dropout; call eval() or set every "
+                             "dropout probability of the encoder to 0")
+
     def _encode_packed_stream(self, points, point_counts, capacity, want_pf=False, rows=None):
         """encode_packed_stream, and the layout it ran on."""
+        self._check_stream("encode_packed_stream")
         layout = self._packed_layout(points, point_counts, capacity)
         walk = points.shape[0] if layout.M is None else min(points.shape[0], -(-layout.M // 8) * 8)
         with torch.no_grad():
@@ -180,7 +232,7 @@ class PointNetEncoder(nn.Module):
         return g, pf, po.unmasked, layout
 
     def forward(self, x):
-        if config.inference() == "stream" and not torch.is_grad_enabled():
+        if config.inference() == "stream" and not torch.is_grad_enabled() and self._stream_ok():
             return self.encode_stream(x, want_pf=True)[:2]
         g, pf, _ = self.encode(x)
         return g, pf

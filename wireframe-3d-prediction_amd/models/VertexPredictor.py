@@ -3,10 +3,16 @@
 Keeps the reference's module tree (models/VertexPredictor.py:27-61) including the
 LAZILY created `point_pool_proj` (reference :94-97): it is built
 on the first forward with default nn.Linear init from the global RNG, exactly
-when and how the reference does, so optimizer/state_dict behaviour is identical."""
+when and how the reference does, so optimizer/state_dict behaviour is identical.
+The `nn.Dropout` that closes each vertex_mlp stage (p = 0.0 by default, as in the reference) is
+honoured in train() mode: its `p` is read on every call; while one is active the head runs on the
+generic GEMM kernels, which draw the masks, whatever the batch size."""
+import torch
 import torch.nn as nn
 
-from wf3d.functional import UnmaskedPoolFn, VertexFn
+from wf3d import config
+from wf3d.functional import Drop, UnmaskedPoolFn, VertexFn
+from wf3d.random import default_generator
 
 
 def _stage(n_in, n_out):
@@ -25,6 +31,8 @@ class VertexPredictor(nn.Module):
         self.final_layer = nn.Linear(1024, max_vertices * vertex_dim)
         self.residual_proj1 = nn.Linear(global_feature_dim, 2048)
         self.residual_proj2 = nn.Linear(global_feature_dim, 1024)
+        self.last_dropout_seed = None       # the seed the last train-mode call with an active site drew on the host
+        self.last_dropout_seeds = None      # dropout_rng "device": the int32 [5] seed words of that call instead
 
     def ensure_point_pool_proj(self, in_features, device):
         """Create the lazy layer if absent (same moment/shape/init as the reference)."""
@@ -43,13 +51,43 @@ class VertexPredictor(nn.Module):
             ps += [self.point_pool_proj.weight, self.point_pool_proj.bias]
         return ps
 
+    def _dropout_ps(self):
+        """The probabilities of the sites vertex_mlp{k}.3, k = 1..4, of this call: all 0 outside train mode."""
+        if not self.training:
+            return (0.0, 0.0, 0.0, 0.0)
+        # plain dict lookups (this runs on every forward): whatever module sits at index 3 of each stage now
+        m = self._modules
+        ps = (m["vertex_mlp1"]._modules["3"].p, m["vertex_mlp2"]._modules["3"].p, m["vertex_mlp3"]._modules["3"].p,
+              m["vertex_mlp4"]._modules["3"].p)
+        if not any(ps):                      # every site at 0: nothing to check
+            return ps
+        for k, p in enumerate(ps, 1):
+            if not 0.0 <= float(p) < 1.0:
+                # torch would zero the whole site at p = 1; the dropout kernels take p in [0, 1) (INTEGRATION.md)
+                raise ValueError(f"VertexPredictor: dropout p = {p} at vertex_mlp{k}.3 is not supported by the HIP vertex head "
+                                 "in train mode (needs 0 <= p < 1)")
+        return ps
+
+    def _dropout(self, device):
+        """The trailing arguments of this call's VertexFn: nothing while no site is active (no seed is drawn), else one
+        Drop(ps, seed), the seed drawn as EdgePredictor._dropout draws its own."""
+        ps = self._dropout_ps()
+        if not any(ps):
+            return ()
+        if config.dropout_rng() == "device":
+            seed = self.last_dropout_seeds = default_generator(device).draw()
+        else:
+            seed = self.last_dropout_seed = int(torch.empty((), dtype=torch.int64).random_().item())
+        return (Drop(ps, seed),)
+
     def predict(self, global_features, upooled):
         """Vertex head from already-pooled point features, upooled = [mean | max] [B, 2C] (None -> no fusion)."""
         with_pool = upooled is not None
         if with_pool:
             self.ensure_point_pool_proj(upooled.shape[1], upooled.device)
         o, exist, counts = VertexFn.apply(global_features, upooled, self.max_vertices,
-                                          self.vertex_dim, *self._param_list(with_pool))
+                                          self.vertex_dim, *self._param_list(with_pool),
+                                          *self._dropout(global_features.device))
         return {"vertices": o,                            # non-contiguous [B, V, 3] view of the [B, V, 4] output (:122)
                 "existence_probabilities": exist,
                 "actual_vertex_counts": counts}

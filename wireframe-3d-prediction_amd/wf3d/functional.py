@@ -15,6 +15,7 @@ normalised activations never exist in memory.
 Which kernels a Linear of the encoder's per-point MLP or of the edge MLP's two wide layers runs on, forward and
 backward, is its Route: decided once in the stage's forward (_encoder_routes, _edge_routes) and only read by backward.
 """
+import contextlib
 from collections import namedtuple
 from collections.abc import Sequence
 
@@ -59,6 +60,45 @@ def _lin_bwd(dz, a, W, pro_a):
     dW = dz^T·pro(a) (TN, prologue re-applied to the stored pre-activation),
     d pro(a) = dz·W (NN)."""
     return ops.gemm(dz, a, TN, pro=pro_a), ops.gemm(dz, W, NN)
+
+
+# Train-mode dropout of the encoder's per-point MLP and of the vertex head (the edge head's is EdgeFn's own arguments).
+# A stage takes it as an optional LAST argument after its parameters — EncoderFn.apply(x, n_hidden, precision, *params,
+# Drop(ps, seed)) — so that a call without one is the call it always was.  ps: the probability of every site of the
+# stage in module order (encoder: mlp.{4i+3}, i = 0 .. n_hidden-1; vertex head: vertex_mlp{k}.3, k = 1..4), each in
+# [0, 1).  seed: the value the module drew on the host (site k = 1, 2, ... masks with (seed + 0x9E3779B9 k) mod 2^32,
+# EdgeFn's rule), or the five device seed words of wf3d.random (an int32 tensor; site k masks with words[k], k <= 4).
+# The mask of a site is wf3d_keep(site seed, row, col): row = the row of the matrix the stage's Linears run on (point
+# row b * N + n of a dense batch, buffer row of a packed one; sample index in the vertex head), col = the feature.
+Drop = namedtuple("Drop", "ps seed")
+
+_GOLDEN = 0x9E3779B9
+
+
+def _take_drop(params, n_sites, who):
+    """(params, ps, site seeds, device words or None) of a stage's trailing arguments.  No Drop, or one whose sites are all
+    0: no site is active — ps all 0.0, no words, and every launch of the stage is the one without a mask."""
+    drop = None
+    if params and isinstance(params[-1], Drop):
+        params, drop = params[:-1], params[-1]
+    if drop is None or not any(drop.ps):
+        return params, (0.0,) * n_sites, (0,) * n_sites, None
+    ps = tuple(float(p) for p in drop.ps)
+    if len(ps) != n_sites or not all(0.0 <= p < 1.0 for p in ps):
+        raise ValueError(f"{who}: Drop.ps must be {n_sites} probabilities in [0, 1) (got {drop.ps})")
+    if torch.is_tensor(drop.seed):
+        if any(p > 0 for p in ps[4:]):
+            raise ValueError(f"{who}: a draw of device seed words serves four dropout sites; site "
+                             f"{max(k for k, p in enumerate(ps, 1) if p > 0)} is active (use the host seed mode, "
+                             "wf3d.config.set_dropout_rng('host'))")
+        return params, ps, tuple(range(1, n_sites + 1)), drop.seed
+    return params, ps, tuple((int(drop.seed) + _GOLDEN * k) & 0xFFFFFFFF for k in range(1, n_sites + 1)), None
+
+
+def _seeded(words):
+    """The seed source of a stage's launches: the device words of its Drop (set for this thread, forward and again in
+    backward, which autograd runs on a thread of its own), or nothing to set."""
+    return seed_words(words) if words is not None else contextlib.nullcontext()
 
 
 _side_streams = {}
@@ -268,16 +308,21 @@ class _PackedPools:
 def _encoder_forward(ctx, x2, pools, n_hidden, precision, params, tail="compute"):
     """The per-point MLP over the rows of x2 and its pools (`pools`: _DensePools or _PackedPools): the forward of EncoderFn
     and EncoderFnPacked.  Returns (PoolOut, point_features [rows, C]).  tail="skip": a packed batch with a capacity runs
-    under its live row total where the routes allow it (_encoder_live); the backward follows ctx.live."""
+    under its live row total where the routes allow it (_encoder_live); the backward follows ctx.live.
+    params may end in a Drop (train-mode dropout at mlp.{4i+3}): site i masks h_i = relu(LN(z_i)) in whichever launch
+    produces or re-applies it, forward and backward (ctx.drop = (ps, site seeds, device words))."""
+    params, ps, sd, words = _take_drop(params, n_hidden, "EncoderFn")
+    ctx.drop = (ps, sd, words)
     routes = _encoder_routes(x2, [params[4 * i] for i in range(n_hidden + 1)], precision in _SPLIT_PRODUCTS,
                              ctx.needs_input_grad[0])
     ctx.live = live = _encoder_live(getattr(pools, "layout", None), routes, tail)
-    with ops.live_rows(live):
+    with ops.live_rows(live), _seeded(words):
         return _encoder_forward_rows(ctx, x2, pools, n_hidden, precision, params, routes)
 
 
 def _encoder_forward_rows(ctx, x2, pools, n_hidden, precision, params, routes):
     npr = _SPLIT_PRODUCTS.get(precision, 3)
+    ps, sd, _ = ctx.drop
     valid = ops.point_valid(x2)
     # both sx8 orientations (W for the forward GEMM, W^T for its dgrad) of every layer split both ways, one launch
     widx = [i for i, r in enumerate(routes) if r.fwd == "split" and r.dgrad == "split"]
@@ -288,7 +333,7 @@ def _encoder_forward_rows(ctx, x2, pools, n_hidden, precision, params, routes):
         W, b = params[4 * i], params[4 * i + 1]
         if r.fwd == "first":
             # first Linear + LayerNorm + ReLU + split in one pass (K = input_dim <= 8: a pure write of z and h)
-            z, mu, rs, a_s = ops.first_layer_fwd(x2, W, b, params[2], params[3], ACT_RELU)
+            z, mu, rs, a_s = ops.first_layer_fwd(x2, W, b, params[2], params[3], ACT_RELU, drop_p=ps[0], seed=sd[0])
         elif r.fwd == "split":
             if i in wsplit:
                 W_s = wsplit[i][0]
@@ -306,13 +351,13 @@ def _encoder_forward_rows(ctx, x2, pools, n_hidden, precision, params, routes):
         if r.fwd == "first":
             pass
         elif routes[i + 1].fwd == "split":
-            mu, rs, a_s = ops.ln_prep(z, g, be, ACT_RELU)
+            mu, rs, a_s = ops.ln_prep(z, g, be, ACT_RELU, drop_p=ps[i], seed=sd[i])
         else:
             mu, rs = ops.row_stats(z)
         hs.append(a_s)
         zs.append(z)
         stats.append((mu, rs))
-        pro = Pro(ACT_RELU, mu, rs, g, be)
+        pro = Pro(ACT_RELU, mu, rs, g, be, ps[i], sd[i])
         a = z
     del a_s
     C = pf.shape[1]
@@ -330,13 +375,14 @@ def _encoder_forward_rows(ctx, x2, pools, n_hidden, precision, params, routes):
 def _encoder_backward(ctx, dpooled, dpf, dupooled):
     """The backward of EncoderFn and EncoderFnPacked: (gradient of the rows of x2 or None, parameter gradients), under the
     live-row count the forward chose (ctx.live)."""
-    with ops.live_rows(ctx.live):
+    with ops.live_rows(ctx.live), _seeded(ctx.drop[2]):
         return _encoder_backward_rows(ctx, dpooled, dpf, dupooled)
 
 
 def _encoder_backward_rows(ctx, dpooled, dpf, dupooled):
     nh, pools, C, npr, routes = ctx.n_hidden, ctx.pools, ctx.width, ctx.products, ctx.routes
     params = _params(ctx)
+    ps, sd, _ = ctx.drop
     x2, valid, zs, stats, hs, arg_m, arg_u, cnt = _saved(ctx)
     grads = [None] * len(params)
     # the pooled cotangents are read as strided halves of the [B, 2C] gradients: no copies
@@ -365,21 +411,22 @@ def _encoder_backward_rows(ctx, dpooled, dpf, dupooled):
         if r.wgrad == "first":
             # layer 0: LN/ReLU backward, bias and WEIGHT gradient in one pass over (dh, z); dz is never written
             g, be = params[2], params[3]
-            grads[2], grads[3], grads[1], grads[0] = ops.ln_act_bwd_first(dh, zs[0], x2, stats[0][0], stats[0][1], g, be, ACT_RELU)
+            grads[2], grads[3], grads[1], grads[0] = ops.ln_act_bwd_first(dh, zs[0], x2, stats[0][0], stats[0][1], g, be, ACT_RELU,
+                                                                          drop_p=ps[0], seed=sd[0])
             break
         if i < nh:
             g, be = params[4 * i + 2], params[4 * i + 3]
             mu, rs = stats[i]
             dz_s = torch.empty_like(dh) if r.dgrad == "split" else None
             dz, grads[4 * i + 2], grads[4 * i + 3], grads[4 * i + 1] = ops.ln_act_bwd(
-                dh, zs[i], mu, rs, g, be, ACT_RELU, inplace=True, dz_split=dz_s, want_dz=_dz32(r))
+                dh, zs[i], mu, rs, g, be, ACT_RELU, ps[i], sd[i], inplace=True, dz_split=dz_s, want_dz=_dz32(r))
         elif dz is not None:
             grads[4 * i + 1] = ops.colsum(dz)
             if r.dgrad == "split":
                 dz_s = ops.split_rows(dz)
         if i > 0:
             pg, pb = params[4 * (i - 1) + 2], params[4 * (i - 1) + 3]
-            h, pro, h_s = zs[i - 1], Pro(ACT_RELU, stats[i - 1][0], stats[i - 1][1], pg, pb), hs[i - 1]
+            h, pro, h_s = zs[i - 1], Pro(ACT_RELU, stats[i - 1][0], stats[i - 1][1], pg, pb, ps[i - 1], sd[i - 1]), hs[i - 1]
         else:
             h, pro, h_s = x2, None, None
         grads[4 * i] = _wgrad(r, dz, dz_s, h, pro, h_s, npr)
@@ -399,7 +446,8 @@ class EncoderFn(torch.autograd.Function):
     """x[B,N,Din], params -> (pooled[B,2C] = [masked max | masked mean], point_features[B,N,C],
     upooled[B,2C] = [unmasked mean | unmasked max]).
 
-    params = [W_i, b_i, gamma_i, beta_i]*n_hidden + [W_out, b_out]   (the per-point shared MLP)
+    params = [W_i, b_i, gamma_i, beta_i]*n_hidden + [W_out, b_out]   (the per-point shared MLP), optionally followed
+    by one Drop(ps, seed): train-mode dropout at mlp.{4i+3} (see Drop)
     upooled holds the UNMASKED pools the vertex head needs, already in its concatenation order
     (VertexPredictor.py:86-88), produced by the same pass as the masked ones.  The fusion MLP is its own Function (FusionFn) so that
     its gradients are handed to autograd — and to the data-parallel reducer — before the long
@@ -421,13 +469,14 @@ class EncoderFn(torch.autograd.Function):
             x2 = x2.contiguous()
         po, pf = _encoder_forward(ctx, x2, _DensePools(B, N), n_hidden, precision, params)
         ctx.dims = (B, N, pf.shape[1])
+        ctx.n_extra = len(params) - len(ctx.params)              # a trailing Drop takes a (None) gradient slot
         return po.masked, pf.view(B, N, -1), po.unmasked
 
     @staticmethod
     def backward(ctx, dpooled, dpf, dupooled):
         B, N, _ = ctx.dims
         dx, grads = _encoder_backward(ctx, dpooled, dpf, dupooled)
-        return (None if dx is None else dx.view(B, N, -1), None, None, *grads)
+        return (None if dx is None else dx.view(B, N, -1), None, None, *grads, *[None] * ctx.n_extra)
 
 
 class EncoderFnPacked(torch.autograd.Function):
@@ -453,12 +502,13 @@ class EncoderFnPacked(torch.autograd.Function):
             x2 = x.new_zeros(layout.M_pad, Din)
             x2[:M].copy_(x)
         po, pf = _encoder_forward(ctx, x2, _PackedPools(layout), n_hidden, precision, params, tail)
+        ctx.n_extra = len(params) - len(ctx.params)
         return po.masked, pf[:M], po.unmasked
 
     @staticmethod
     def backward(ctx, dpooled, dpf, dupooled):
         _, grads = _encoder_backward(ctx, dpooled, dpf, dupooled)
-        return (None, None, None, None, *grads)
+        return (None, None, None, None, *grads, *[None] * ctx.n_extra)
 
 
 class EncoderFnPackedSkip(torch.autograd.Function):
@@ -541,10 +591,25 @@ class VertexFn(torch.autograd.Function):
 
     B <= 32 rows: six weight-streaming launches forward (the three Linears that read `e` share one; the residual sums
     c = relu(LN(z3)) + r1, d = relu(LN(z4)) + r2 are applied on load and never materialised), thirteen backward
-    (csrc/skinny.hip); otherwise the generic GEMM path."""
+    (csrc/skinny.hip); otherwise the generic GEMM path.
+
+    params may end in one Drop(ps, seed): train-mode dropout at vertex_mlp{k}.3, k = 1..4, on relu(LN(z_k)) — before the
+    residual add for k = 3, 4 (VertexPredictor.py:110,114) — with row = sample index.  While a site is active the stage
+    takes the generic GEMM path whatever B is (the skinny kernels draw no masks); with none active the choice is
+    unchanged."""
 
     @staticmethod
     def forward(ctx, g, upooled, V, vd, *params):
+        ctx.n_extra = len(params)
+        params, ps, sd, words = _take_drop(params, 4, "VertexFn")
+        ctx.n_extra -= len(params)
+        ctx.drop = (ps, sd, words)
+        with _seeded(words):
+            return VertexFn._forward(ctx, g, upooled, V, vd, *params)
+
+    @staticmethod
+    def _forward(ctx, g, upooled, V, vd, *params):
+        ps, sd, _ = ctx.drop
         g = g.contiguous()
         B = g.shape[0]
         (W1, b1, g1, be1, W2, b2, g2, be2, W3, b3, g3, be3, W4, b4, g4, be4, Wf, bf, Wr1, br1, Wr2, br2) = params[:22]
@@ -552,7 +617,7 @@ class VertexFn(torch.autograd.Function):
             upooled = upooled if upooled.stride(1) == 1 else upooled.contiguous()
         mats = [W1, W2, W3, W4, Wf, Wr1, Wr2] + ([params[22]] if upooled is not None else [])
         ctx.skinny = sk.ok(B, *mats) and all(w.shape[0] % 16 == 0 for w in (W1, W2, W3, W4)) \
-            and (upooled is None or upooled.stride(0) % 4 == 0)
+            and (upooled is None or upooled.stride(0) % 4 == 0) and not any(ps)
         if ctx.skinny:
             if upooled is not None:
                 (e, _, _), = sk.fwd(B, sk.Fwd(upooled, params[22], params[23], out_add=g))     # enhanced = g + proj (:99-100)
@@ -571,13 +636,14 @@ class VertexFn(torch.autograd.Function):
             else:
                 e = g
             z1 = ops.gemm(e, W1, NT, bias=b1); s1 = ops.row_stats(z1)
-            z2 = ops.gemm(z1, W2, NT, bias=b2, pro=Pro(ACT_RELU, s1[0], s1[1], g1, be1)); s2 = ops.row_stats(z2)
-            z3 = ops.gemm(z2, W3, NT, bias=b3, pro=Pro(ACT_RELU, s2[0], s2[1], g2, be2)); s3 = ops.row_stats(z3)
+            z2 = ops.gemm(z1, W2, NT, bias=b2, pro=Pro(ACT_RELU, s1[0], s1[1], g1, be1, ps[0], sd[0])); s2 = ops.row_stats(z2)
+            z3 = ops.gemm(z2, W3, NT, bias=b3, pro=Pro(ACT_RELU, s2[0], s2[1], g2, be2, ps[1], sd[1])); s3 = ops.row_stats(z3)
             r1 = ops.gemm(e, Wr1, NT, bias=br1)
-            c = ops.ln_act_apply(z3, s3[0], s3[1], g3, be3, ACT_RELU, addend=r1)   # residual after ReLU (:110)
+            # residual after the ReLU and its dropout (:110)
+            c = ops.ln_act_apply(z3, s3[0], s3[1], g3, be3, ACT_RELU, addend=r1, drop_p=ps[2], seed=sd[2])
             z4 = ops.gemm(c, W4, NT, bias=b4); s4 = ops.row_stats(z4)
             r2 = ops.gemm(e, Wr2, NT, bias=br2)
-            d = ops.ln_act_apply(z4, s4[0], s4[1], g4, be4, ACT_RELU, addend=r2)
+            d = ops.ln_act_apply(z4, s4[0], s4[1], g4, be4, ACT_RELU, addend=r2, drop_p=ps[3], seed=sd[3])
             o = ops.gemm(d, Wf, NT, bias=bf)
         exist, counts = ops.vertex_finalize_fwd(o, V, vd)
         _keep_params(ctx, params)
@@ -592,7 +658,13 @@ class VertexFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, do3, dexist, _dcounts):
+        with _seeded(ctx.drop[2]):
+            return (*VertexFn._backward(ctx, do3, dexist), *[None] * ctx.n_extra)
+
+    @staticmethod
+    def _backward(ctx, do3, dexist):
         params = _params(ctx)
+        ps, sd, _ = ctx.drop
         B, V, vd = ctx.dims
         (W1, b1, g1, be1, W2, b2, g2, be2, W3, b3, g3, be3, W4, b4, g4, be4, Wf, bf, Wr1, br1, Wr2, br2) = params[:22]
         pooled, e, z1, s1, z2, s2, z3, s3, c, z4, s4, d = _saved(ctx)
@@ -633,17 +705,17 @@ class VertexFn(torch.autograd.Function):
         G[21] = ops.colsum(dd)
         G[20] = ops.gemm(dd, e, TN)
         de = ops.gemm(dd, Wr2, NN)
-        dz4, G[14], G[15], G[13] = ops.ln_act_bwd(dd, z4, s4[0], s4[1], g4, be4, ACT_RELU)
+        dz4, G[14], G[15], G[13] = ops.ln_act_bwd(dd, z4, s4[0], s4[1], g4, be4, ACT_RELU, ps[3], sd[3])
         G[12], dc = _lin_bwd(dz4, c, W4, None)
         # c = relu(LN(z3)) + r1
         G[19] = ops.colsum(dc)
         G[18] = ops.gemm(dc, e, TN)
         ops.gemm(dc, Wr1, NN, out=de, accumulate=True)
-        dz3, G[10], G[11], G[9] = ops.ln_act_bwd(dc, z3, s3[0], s3[1], g3, be3, ACT_RELU)
-        G[8], dh = _lin_bwd(dz3, z2, W3, Pro(ACT_RELU, s2[0], s2[1], g2, be2))
-        dz2, G[6], G[7], G[5] = ops.ln_act_bwd(dh, z2, s2[0], s2[1], g2, be2, ACT_RELU, inplace=True)
-        G[4], dh = _lin_bwd(dz2, z1, W2, Pro(ACT_RELU, s1[0], s1[1], g1, be1))
-        dz1, G[2], G[3], G[1] = ops.ln_act_bwd(dh, z1, s1[0], s1[1], g1, be1, ACT_RELU, inplace=True)
+        dz3, G[10], G[11], G[9] = ops.ln_act_bwd(dc, z3, s3[0], s3[1], g3, be3, ACT_RELU, ps[2], sd[2])
+        G[8], dh = _lin_bwd(dz3, z2, W3, Pro(ACT_RELU, s2[0], s2[1], g2, be2, ps[1], sd[1]))
+        dz2, G[6], G[7], G[5] = ops.ln_act_bwd(dh, z2, s2[0], s2[1], g2, be2, ACT_RELU, ps[1], sd[1], inplace=True)
+        G[4], dh = _lin_bwd(dz2, z1, W2, Pro(ACT_RELU, s1[0], s1[1], g1, be1, ps[0], sd[0]))
+        dz1, G[2], G[3], G[1] = ops.ln_act_bwd(dh, z1, s1[0], s1[1], g1, be1, ACT_RELU, ps[0], sd[0], inplace=True)
         G[0] = ops.gemm(dz1, e, TN)
         ops.gemm(dz1, W1, NN, out=de, accumulate=True)
         dupooled = None

@@ -1033,8 +1033,9 @@ def first_layer_ok(x, W):
     return x.dim() == 2 and x.shape[1] <= 8 and W.shape[0] % 8 == 0 and W.shape[0] <= 1024 and x.stride(1) == 1 and W.stride(1) == 1
 
 
-def first_layer_fwd(x, W, bias, gamma, beta, act, eps=LN_EPS):
-    """x [R, K<=8] -> (z = x·W^T + b, mu, rs, h_sx8 = act(LayerNorm(z))) in one pass."""
+def first_layer_fwd(x, W, bias, gamma, beta, act, eps=LN_EPS, drop_p=0.0, seed=0):
+    """x [R, K<=8] -> (z = x·W^T + b, mu, rs, h_sx8 = drop(act(LayerNorm(z)))) in one pass.  drop_p = 0 is the call
+    without a mask (wf3d_first_layer_fwd), whatever the seed."""
     _need_cuda(x, W, bias, gamma, beta)
     R, K = x.shape
     D = W.shape[0]
@@ -1042,6 +1043,11 @@ def first_layer_fwd(x, W, bias, gamma, beta, act, eps=LN_EPS):
     h = torch.empty_like(z)
     mu = torch.empty(R, dtype=torch.float32, device=x.device)
     rs = torch.empty(R, dtype=torch.float32, device=x.device)
+    if drop_p:
+        check(_lib.load().wf3d_first_layer_fwd_drop(_p(x), R, K, x.stride(0), _p(W), W.stride(0), _p(bias), D, _p(gamma),
+                                                    _p(beta), act, eps, float(drop_p), int(seed) & 0xFFFFFFFF, _p(z), _p(mu),
+                                                    _p(rs), _p(h), _stream()), "first_layer_fwd_drop")
+        return z, mu, rs, h
     check(_lib.load().wf3d_first_layer_fwd(_p(x), R, K, x.stride(0), _p(W), W.stride(0), _p(bias), D, _p(gamma), _p(beta),
                                            act, eps, _p(z), _p(mu), _p(rs), _p(h), _stream()), "first_layer_fwd")
     return z, mu, rs, h
@@ -1062,8 +1068,8 @@ def first_layer_infer(x, W, bias, gamma, beta, act, eps=LN_EPS, out=None):
     return out
 
 
-def ln_act_bwd_first(dh, z, x, mu, rs, gamma, beta, act):
-    """Backward of act(LayerNorm(z)) for the first layer: (dgamma, dbeta, dbias, dW[D, K]); dz is not materialised."""
+def ln_act_bwd_first(dh, z, x, mu, rs, gamma, beta, act, drop_p=0.0, seed=0):
+    """Backward of drop(act(LayerNorm(z))) for the first layer: (dgamma, dbeta, dbias, dW[D, K]); dz is not materialised."""
     _need_cuda(dh, z, x, mu, rs, gamma, beta)
     if not (dh.is_contiguous() and z.is_contiguous()):
         raise RuntimeError("wf3d.ln_act_bwd_first: contiguous tensors required")
@@ -1073,6 +1079,11 @@ def ln_act_bwd_first(dh, z, x, mu, rs, gamma, beta, act):
     dW = torch.empty(D, K, dtype=torch.float32, device=z.device)
     lib = _lib.load()
     ws = scratch(lib.wf3d_ln_act_bwd_first_ws_bytes(R, D), z.device)
+    if drop_p:
+        check(lib.wf3d_ln_act_bwd_first_drop(_p(dh), _p(z), _p(x), R, D, K, x.stride(0), _p(mu), _p(rs), _p(gamma), _p(beta),
+                                             act, float(drop_p), int(seed) & 0xFFFFFFFF, _p(trio[0]), _p(trio[1]), _p(trio[2]),
+                                             _p(dW), _p(ws), ws.numel(), _stream()), "ln_act_bwd_first_drop")
+        return trio[0], trio[1], trio[2], dW
     check(lib.wf3d_ln_act_bwd_first(_p(dh), _p(z), _p(x), R, D, K, x.stride(0), _p(mu), _p(rs), _p(gamma), _p(beta), act,
                                     _p(trio[0]), _p(trio[1]), _p(trio[2]), _p(dW), _p(ws), ws.numel(), _stream()),
           "ln_act_bwd_first")
