@@ -751,9 +751,11 @@ int wf3d_wireframe_targets(const double* wf_vertices, const int32_t* wf_edges, c
                            const void* params, int B, int V, float* vertices, float* vertex_existence, int64_t* vertex_counts,
                            float* edge_labels, void* stream);
 /* HOST function: the numbers of a whitespace-separated text file (.xyz: 8 per row; np.loadtxt, :98) into out[0..max_vals);
- * returns the count in the file (call again with a larger buffer if > max_vals), -1 unreadable, -2 not a number. */
+ * returns the count in the file (call again with a larger buffer if > max_vals), -1 unreadable, -2 not a number: a token
+ * is every character up to whitespace, `#` or the end, and the whole of it must be one decimal number, inf or nan, as
+ * for np.loadtxt (`3.4.5`, `1.0-2.0`, `1e5x`, `1,2,3` and hexadecimal forms such as `0x10` are refused). */
 long wf3d_parse_floats(const char* path, double* out, long max_vals);
-/* Same (`#` comments skipped, C-locale numbers), and *ncols = values per row — np.loadtxt's second dimension;
+/* Same (`#` comments skipped, C-locale numbers; \n, \r\n and a lone \r end a row), and *ncols = values per row — np.loadtxt's second dimension;
  * -3 if two non-empty rows hold different numbers of values. */
 long wf3d_parse_table(const char* path, double* out, long max_vals, long* ncols);
 

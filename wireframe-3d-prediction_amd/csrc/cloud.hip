@@ -119,8 +119,8 @@ __device__ __forceinline__ long pack_source_row(const BatchParams& P, const long
     b = sample_of_row(P.out_first, B, r);
     const int cl = P.cloud[b];
     if (cl < 0 || cl >= nclouds) return -1;
-    const long k = r - P.out_first[b], r0 = first[cl];
-    return k < first[cl + 1] - r0 ? r0 + k : -1;
+    const long k = r - P.out_first[b], r0 = first[cl];       // k < 0: a row in front of out_first[0] > 0
+    return k >= 0 && k < first[cl + 1] - r0 ? r0 + k : -1;
 }
 
 __device__ __forceinline__ void pack_counts(const BatchParams& P, const long* __restrict__ first, int B, int nclouds, long t,
@@ -415,10 +415,11 @@ extern "C" int wf3d_wireframe_targets(const double* wf_vertices, const int32_t* 
     return WF3D_OK;
 }
 
-// Host: the numbers of a whitespace-separated text table.  `#` starts a comment (to the end of the line); numbers are
+// Host: the numbers of a whitespace-separated text table.  `#` starts a comment (to the end of the line: \n, \r\n or \r); numbers are
 // parsed in the C locale whatever the process locale is.  out[0..max_vals) receives the values in file order; returns
 // how many the file holds (> max_vals: call again with a larger buffer), -1 if the file cannot be read, -2 on a token
-// that is not a number, -3 (wf3d_parse_table only) if two non-empty rows hold different numbers of values.
+// (the characters up to whitespace, `#` or the end) that is not, as a whole, a decimal number, inf or nan,
+// -3 (wf3d_parse_table only) if two non-empty rows hold different numbers of values.
 static long parse_numbers(const char* path, double* out, long max_vals, long* ncols) {
     static locale_t c_loc = newlocale(LC_ALL_MASK, "C", (locale_t)0);
     FILE* f = fopen(path, "rb");
@@ -442,13 +443,19 @@ static long parse_numbers(const char* path, double* out, long max_vals, long* nc
         }
     };
     for (;;) {
-        while (*p == ' ' || *p == '\t' || *p == '\r') ++p;
-        if (*p == '#') { while (*p && *p != '\n') ++p; }
-        if (*p == '\n') { end_row(); ++p; continue; }
+        while (*p == ' ' || *p == '\t' || *p == '\v' || *p == '\f') ++p;
+        if (*p == '#') { while (*p && *p != '\n' && *p != '\r') ++p; }
+        if (*p == '\n' || *p == '\r') { end_row(); ++p; continue; }       // \n, \r\n and a lone \r end a row, as for np.loadtxt
         if (!*p) break;
+        // the token: up to whitespace, `#` or the end.  The number must be all of it (np.loadtxt refuses `3.4.5`,
+        // `1.0-2.0`, `1e5x`), and strtod's hexadecimal and `nan(...)` forms are not numbers of a table either.
+        const char* q = p;
+        bool plain = true;
+        for (; *q && *q != ' ' && *q != '\t' && *q != '\r' && *q != '\n' && *q != '\v' && *q != '\f' && *q != '#'; ++q)
+            plain = plain && *q != 'x' && *q != 'X' && *q != '(';
         char* end;
         const double v = c_loc ? strtod_l(p, &end, c_loc) : strtod(p, &end);
-        if (end == p) { free(buf); return -2; }
+        if (!plain || end != q) { free(buf); return -2; }
         if (n < max_vals && out) out[n] = v;
         ++n; ++in_row;
         p = end;
