@@ -122,6 +122,12 @@ int wf3d_gemm(const wf3d_gemm_t* desc, void* stream);
  * of the bf16 rate).  Operands are in the "sx8" format: a logical fp32 [R, C]
  * matrix (C % 8 == 0) with the same bytes/pitch as fp32, each 32-byte group of
  * 8 consecutive columns holding [8 x bf16 high | 8 x bf16 low], v ~= hi + lo.
+ * Every producer writes hi = bf16_rne(v), lo = bf16_rne(v - hi), so that
+ * |v - hi - lo| <= 2^-17 |v| (finite v whose hi and lo are normal bf16 numbers;
+ * tests/sx8_model.py states the split on integer bits).  The pair is NOT a
+ * function of the sum hi + lo: where lo was rounded up onto half an ulp of an odd
+ * hi, splitting hi + lo again gives the even neighbour and the opposite low part.
+ * An entry point that takes an sx8 input and hands it on moves the two planes.
  * ------------------------------------------------------------------------ */
 /* C[M,N] (+)= A·B^T + bias, A = sx8[M,K], B = sx8[N,K] (nn.Linear forward with
  * B = W; its dgrad with A = dY, B = W^T in sx8).  The workspace is written by every call that is given one (split-K
@@ -154,7 +160,8 @@ int wf3d_split_rows_multi(const float* const* in, const long* row_stride, const 
 /* out_sx8[C, R] = split(drop(act(LN-affine(in[R, C]))))^T — the wgrad operands (reduction
  * index = row index made contiguous): dW = dY^T·X becomes the NT-form
  * wf3d_gemm_split(dY^T_sx8, X^T_sx8).  mu/gamma NULL skip the respective part;
- * in_sx8 != 0: `in` is itself an sx8 matrix (no prologue), transposed plane-wise. */
+ * in_sx8 != 0: `in` is itself an sx8 matrix (no prologue), transposed plane-wise:
+ * out's high and low planes are the input's, bit for bit (no second split). */
 int wf3d_split_transpose(const float* in, int R, int C, int ld, const float* mu, const float* rs,
                          const float* gamma, const float* beta, int act, float drop_p, uint32_t drop_seed,
                          int in_sx8, void* out_sx8, void* stream);

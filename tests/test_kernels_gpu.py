@@ -259,6 +259,7 @@ def test_pool4_fwd_bwd(ops, B, N, C):
             s8 = ops.pool4_bwd(valid, cnt, arg_m, arg_u, cot[0], cot[1], cot[2], cot[3], d, B, N, C, sx8=True)
             sh, sl = unpack_sx8(s8.view(B * N, C))
             assert torch.equal(sh, full.view(B * N, C).bfloat16().float())
+            assert torch.equal(sl, (full.view(B * N, C) - sh).bfloat16().float())      # both planes: the RNE split of the fp32 form
             assert rel(sh + sl, full.view(B * N, C)) < 2e-5
 
 

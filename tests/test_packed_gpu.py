@@ -159,7 +159,8 @@ def test_seg_pool_backward_three_forms(ops, C, counts):
         if C % 8 == 0:
             s8 = ops.pool4_seg_bwd(valid, po.cnt, po.arg_m, po.arg_u, *cots, d, lay, C, sx8=True)
             hi, lo = H.unpack_sx8(s8)
-            assert torch.equal(hi, dpf.bfloat16().float())                          # the RNE split of the fp32 form
+            assert torch.equal(hi, dpf.bfloat16().float())                          # the RNE split of the fp32 form,
+            assert torch.equal(lo, (dpf - hi).bfloat16().float())                   # both planes
             assert rel(hi + lo, dpf) < 2e-5                                         # the split format's 2^-17
             assert lay.M_pad == M or (float(hi[M:].abs().max()) == 0.0 and float(lo[M:].abs().max()) == 0.0)
     # no cotangent for one of the pairs

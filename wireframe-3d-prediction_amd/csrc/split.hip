@@ -6,11 +6,15 @@
 // hi = bf16_rne(v), lo = bf16_rne(v - hi)  (|v - hi - lo| <= 2^-17 |v|).  A staged
 // row slice then delivers each lane's v_mfma_f32_32x32x16_bf16 fragment (8
 // consecutive k) as one 16-byte chunk, with no conversion inside the GEMM.
+// The split is written four times (store_sx8 here, wf3d_store_sx8_pair in wf3d_common.h, pair_store_sx8 in edge.hip,
+// the dz_sx8 stores of rowops.hip): the same two casts in each, held to tests/sx8_model.py bit for bit by
+// tests/test_sx8_producers_gpu.py.  (hi, lo) is not a function of hi + lo: an sx8 input is moved, never split again.
 #include "wf3d_common.h"
 
 namespace {
 
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+typedef unsigned short u16x8 __attribute__((ext_vector_type(8)));
 
 __device__ __forceinline__ void store_sx8(float* dst, const float (&v)[8]) {
     bf16x8 hi, lo;
@@ -352,21 +356,21 @@ __global__ __launch_bounds__(256) void split_transpose_kernel(const float* __res
     const int r0 = blockIdx.y * 64, c0 = blockIdx.x * 64;
     const int t = threadIdx.x;
     if (in_sx8) {
-        // input already split (e.g. dz written by ln_act_bwd): rebuild v = hi + lo (exact in fp32)
+        // input already split (e.g. dz written by ln_act_bwd): its two planes are MOVED, one 32-bit word (hi << 16 | lo)
+        // per element through the tile.  Splitting hi + lo again would not always return them: where lo was rounded up
+        // onto half an ulp of an odd hi, the sum is a tie that goes to the even neighbour (same value, other planes).
         const int g = t & 7;
 #pragma unroll
         for (int i = 0; i < 2; ++i) {
             const int rr = (t >> 3) + 32 * i;
-            float v[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+            u16x8 hi = {0, 0, 0, 0, 0, 0, 0, 0}, lo = hi;
             if (r0 + rr < Rl && c0 + g * 8 < C) {
                 const float* p = in + (size_t)(r0 + rr) * ld + c0 + g * 8;
-                const bf16x8 hi = __builtin_bit_cast(bf16x8, *reinterpret_cast<const f32x4*>(p));
-                const bf16x8 lo = __builtin_bit_cast(bf16x8, *reinterpret_cast<const f32x4*>(p + 4));
-#pragma unroll
-                for (int j = 0; j < 8; ++j) v[j] = (float)hi[j] + (float)lo[j];
+                hi = __builtin_bit_cast(u16x8, *reinterpret_cast<const f32x4*>(p));
+                lo = __builtin_bit_cast(u16x8, *reinterpret_cast<const f32x4*>(p + 4));
             }
 #pragma unroll
-            for (int j = 0; j < 8; ++j) tile[rr][g * 8 + j] = v[j];
+            for (int j = 0; j < 8; ++j) tile[rr][g * 8 + j] = __uint_as_float(((unsigned)hi[j] << 16) | (unsigned)lo[j]);
         }
     } else {
         const int cc = (t & 15) * 4;
@@ -407,7 +411,16 @@ __global__ __launch_bounds__(256) void split_transpose_kernel(const float* __res
             float v[8];
 #pragma unroll
             for (int k = 0; k < 8; ++k) v[k] = tile[g8 * 8 + k][c];
-            store_sx8(out + (size_t)(c0 + c) * R + r0 + g8 * 8, v);
+            float* dst = out + (size_t)(c0 + c) * R + r0 + g8 * 8;
+            if (in_sx8) {
+                u16x8 hi, lo;
+#pragma unroll
+                for (int k = 0; k < 8; ++k) { const unsigned w = __float_as_uint(v[k]); hi[k] = (unsigned short)(w >> 16); lo[k] = (unsigned short)w; }
+                *reinterpret_cast<f32x4*>(dst) = __builtin_bit_cast(f32x4, hi);
+                *reinterpret_cast<f32x4*>(dst + 4) = __builtin_bit_cast(f32x4, lo);
+            } else {
+                store_sx8(dst, v);
+            }
         }
     }
 }
