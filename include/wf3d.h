@@ -61,10 +61,13 @@ const char* wf3d_last_error(void);
  *       (the three-stage LDS-DMA kernel forward / dgrad, the 256x128 kernel for wf3d_gemm_split_tn); 6 = the 256x256
  *       forward / dgrad kernel on every shape (wgrad keeps its automatic choice).  The workspace queries follow it, so
  *       a workspace sized under one value may be too small under another (the launch then does not split K).
- *   "attn_tiled" (0, 1 or 2): which head_dim-64 calls of wf3d_attn_fwd / wf3d_attn_bwd run on the key-tiled MFMA
- *       kernels.  1 = automatic, the default: those with vmax > 256 (smaller ones keep the kernels that hold a whole
- *       sample in LDS); 0 = never (vmax > 256 then runs on the chunked VALU kernels; for A/B timing and tests);
- *       2 = every head_dim-64 call whatever vmax (for tests and diagnostics).  wf3d_attn_kernel reports the outcome.
+ *   "attn_tiled" (0, 1 or 2): which calls of wf3d_attn_fwd / wf3d_attn_bwd run on the key-tiled MFMA kernels.
+ *       1 = automatic, the default: head_dim 64 with vmax > 256 (smaller ones keep the kernels that hold a whole
+ *       sample in LDS), and every head_dim in 68..128 at every vmax; 0 = never (head_dim 64 with vmax > 256 and every
+ *       head_dim in 68..128 then run on the VALU kernels, which refuse a head_dim above 64 beyond their LDS limit; for
+ *       A/B timing and tests); 2 = every call with a head_dim in 64..128 whatever vmax (for tests and diagnostics).
+ *       Head widths up to 60 and above 128 run on the VALU kernels under every value.  wf3d_attn_kernel reports the
+ *       outcome.
  * Returns WF3D_OK, or WF3D_ERR_ARG for an unknown name or a value out of range. */
 int wf3d_set_option(const char* name, int value);
 
@@ -510,14 +513,21 @@ int wf3d_edge_scatter_dverts(const float* dcv, const int32_t* voff, int B, int V
  * runs QK^T and PV (and the five backward contractions) on fp32 MFMA for any vmax: up
  * to 256 vertices with the sample's rows resident in LDS, beyond that key-tiled with an
  * online softmax (one workgroup per head, sample and 128 rows; option "attn_tiled").
- * Other head widths run on VALU kernels.  Backward takes the forward's ctx
- * (delta_i = dctx_i · ctx_i); no atomics, so results are bit-reproducible. */
+ * Every other head_dim that is a multiple of 4 up to 128 (68..128: hidden 512 / 4 heads,
+ * 1024 / 8, 768 / 8) runs key-tiled on fp32 MFMA at any vmax, on kernels of padded width
+ * 96 or 128 that neither read nor write past a head's columns.  Head widths up to 60 and
+ * above 128 run on VALU kernels that stage up to 256 rows of two operands in LDS: above
+ * 128 (and for 68..128 under "attn_tiled" = 0) a call whose rows do not fit the 160 KiB is
+ * refused with WF3D_ERR_UNSUPPORTED before anything is launched (width 132: vmax >= 147
+ * forward, >= 142 backward).  head_dim % 4 != 0 is refused.  Backward takes the forward's
+ * ctx (delta_i = dctx_i · ctx_i); no atomics, so results are bit-reproducible. */
 int wf3d_attn_fwd(const float* qkv, const int32_t* voff, int S, int vmax, int E, int heads, float drop_p,
                   uint32_t drop_seed, float* ctx, float* lse, void* stream);
 int wf3d_attn_bwd(const float* qkv, const float* dctx, const float* ctx, const float* lse, const int32_t* voff,
                   int S, int vmax, int E, int heads, float drop_p, uint32_t drop_seed, float* dqkv, void* stream);
 /* The kernel family that serves such a call under the current options: 0 = VALU, 1 = MFMA with the sample resident in
- * LDS, 2 = MFMA key-tiled; WF3D_ERR_ARG for dims the entry points refuse.  Host only: no device is touched. */
+ * LDS (head_dim 64, vmax <= 256), 2 = MFMA key-tiled (head_dim 64 beyond that, head_dim 68..128 at every vmax);
+ * WF3D_ERR_ARG for dims the entry points refuse.  Host only: no device is touched. */
 int wf3d_attn_kernel(int E, int heads, int vmax);
 
 /* Split first layer of edge_mlp (EdgePredictor.py:122-137):

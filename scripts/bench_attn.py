@@ -1,9 +1,11 @@
-"""Times ops.attn_fwd + ops.attn_bwd (E = 512, 8 heads, B = 32) per kernel family: the key-tiled MFMA kernels against
-the parent dispatch (wf3d_set_option "attn_tiled" = 0: chunked VALU kernels beyond 256 vertices) and against the resident
-MFMA kernels where both apply.  Device events, median over --iters calls after --warmup; the arms alternate per repeat, so
-the spread between two runs of the same arm is in the output.  One JSON line per (shape, arm, repeat).
+"""Times ops.attn_fwd + ops.attn_bwd (--E 512 --heads 8 by default, B = 32) per kernel family.  Head width 64: the key-tiled
+MFMA kernels against the parent dispatch (wf3d_set_option "attn_tiled" = 0: chunked VALU kernels beyond 256 vertices) and
+against the resident MFMA kernels where both apply.  Other widths (--E 1024 --heads 8, --E 768 --heads 8): the key-tiled
+kernels against the VALU kernels (option 0) at 64 and 128 vertices, where the VALU kernels' operands fit the LDS, and
+alone at 256 and 512.  Device events, median over --iters calls after --warmup; the arms alternate per repeat, so the
+spread between two runs of the same arm is in the output.  One JSON line per (shape, arm, repeat).
 
-    python scripts/bench_attn.py [--iters 50] [--warmup 10] [--repeats 2] [--out FILE]
+    python scripts/bench_attn.py [--E 512] [--heads 8] [--iters 50] [--warmup 10] [--repeats 2] [--out FILE]
 """
 import argparse
 import json
@@ -16,17 +18,18 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "wireframe-3d-prediction_amd"))
 
-E, HEADS, B = 512, 8, 32
+B = 32
 PEAK_TF = 157.3                       # fp32 MFMA
 
 
-def flops(counts):
-    """MFMA work of the algorithm: forward 2 contractions, backward 5 + the recomputed S in both sweeps = 7; 2*n*n*64 each."""
-    per = sum(2.0 * n * n * 64 for n in counts) * HEADS
+def flops(counts, E, HEADS):
+    """MFMA work of the algorithm: forward 2 contractions, backward 5 + the recomputed S in both sweeps = 7; 2*n*n*head_dim
+    each (the live head_dim E / heads: the zero columns a padded width adds are not counted)."""
+    per = sum(2.0 * n * n * (E // HEADS) for n in counts) * HEADS
     return 2 * per, 7 * per
 
 
-def time_arm(ops, lib, option, counts, iters, warmup):
+def time_arm(ops, lib, option, counts, iters, warmup, E, HEADS):
     assert lib.wf3d_set_option(b"attn_tiled", option) == 0
     try:
         dev = torch.device("cuda:0")
@@ -54,6 +57,8 @@ def time_arm(ops, lib, option, counts, iters, warmup):
 
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--E", type=int, default=512)
+    ap.add_argument("--heads", type=int, default=8)
     ap.add_argument("--iters", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--repeats", type=int, default=2)
@@ -64,15 +69,22 @@ def main():
     from wf3d import _lib, ops
     lib = _lib.load()
     ragged = [4 + (i * 508) // (B - 1) for i in range(B)]
-    shapes = [("all512", [512] * B, (0, 1)), ("all1024", [1024] * B, (0, 1)), ("ragged4..512", ragged, (0, 1)),
-              ("all256", [256] * B, (1, 2))]
+    E, HEADS = a.E, a.heads
+    if E % HEADS:
+        raise SystemExit("bench_attn: --E must be a multiple of --heads")
+    if E // HEADS == 64:
+        shapes = [("all512", [512] * B, (0, 1)), ("all1024", [1024] * B, (0, 1)), ("ragged4..512", ragged, (0, 1)),
+                  ("all256", [256] * B, (1, 2))]
+    else:
+        shapes = [("all64", [64] * B, (0, 1)), ("all128", [128] * B, (0, 1)), ("all256", [256] * B, (1,)),
+                  ("all512", [512] * B, (1,))]
     lines = []
     for name, counts, arms in shapes:
-        ff, fb = flops(counts)
+        ff, fb = flops(counts, E, HEADS)
         for rep in range(a.repeats):
             for option in arms:
-                fam, mf, mb = time_arm(ops, lib, option, counts, a.iters, a.warmup)
-                rec = {"shape": name, "attn_tiled": option, "family": fam, "repeat": rep, "fwd_ms": round(mf, 4),
+                fam, mf, mb = time_arm(ops, lib, option, counts, a.iters, a.warmup, E, HEADS)
+                rec = {"E": E, "heads": HEADS, "shape": name, "attn_tiled": option, "family": fam, "repeat": rep, "fwd_ms": round(mf, 4),
                        "bwd_ms": round(mb, 4), "fwd_bwd_ms": round(mf + mb, 4), "fwd_tflops": round(ff / mf / 1e9, 2),
                        "bwd_tflops": round(fb / mb / 1e9, 2), "peak_tflops": PEAK_TF, "iters": a.iters}
                 print(json.dumps(rec), flush=True)

@@ -9,6 +9,10 @@
 // query rows.  Rows are padded to hd+4 floats so that the ds_read_b128 of 16
 // different key rows land on 16 distinct 16-B slots.
 //
+// These VALU kernels serve head widths up to 60 and above 128, and any width under option "attn_tiled" = 0; widths
+// 64..128 otherwise run on the matrix cores (attn_mfma.hip, attn_family below).  Above width 64 two 256-row operands no
+// longer fit the LDS at every vertex count: attn_check refuses such a call before anything is launched.
+//
 // Vertex rows are COMPACT: sample s owns rows voff[s] .. voff[s+1]-1 of every
 // [Rv, *] matrix, so ragged batches cost nothing and no key mask is needed.
 #include "attn_args.h"
@@ -19,17 +23,20 @@ namespace {
 
 constexpr int ATT_WAVES = 4;
 
-// head_dim 64 runs on the matrix cores (attn_mfma.hip), every other one on the VALU kernels below
-bool use_mfma(int E, int heads) { return E / heads == 64; }
+// head_dim 64 and every multiple of 4 in 68..128 run on the matrix cores (attn_mfma.hip), every other one (<= 60, > 128)
+// on the VALU kernels below
+bool use_mfma(int E, int heads) { const int hd = E / heads; return hd == 64 || (hd > 64 && hd <= 128 && hd % 4 == 0); }
 
-// "attn_tiled" (wf3d_set_option): 1 = automatic, 0 = never the key-tiled MFMA kernels, 2 = always for head_dim 64
+// "attn_tiled" (wf3d_set_option): 1 = automatic, 0 = never the key-tiled MFMA kernels, 2 = always where they exist
 std::atomic<int> g_attn_tiled{1};
 
-// which kernels serve a call: 0 = VALU (below), 1 = MFMA with the sample resident in LDS (up to 256 vertices),
-// 2 = MFMA key-tiled (any vertex count)
+// which kernels serve a call: 0 = VALU (below), 1 = MFMA with the sample resident in LDS (head_dim 64, up to 256
+// vertices), 2 = MFMA key-tiled (any vertex count).  Head widths 68..128 have no resident form: key-tiled at every vmax
+// unless the option is 0, which is the VALU kernels with their LDS check (attn_check).
 int attn_family(int E, int heads, int vmax) {
     if (!use_mfma(E, heads)) return 0;
     const int tiled = g_attn_tiled.load(std::memory_order_relaxed);
+    if (E / heads != 64) return tiled == 0 ? 0 : 2;
     if (tiled == 2) return 2;
     if (vmax <= 256) return 1;
     return tiled == 1 ? 2 : 0;

@@ -1,5 +1,5 @@
-// The argument block of the seven attention kernels (attn.hip: VALU, any head width; attn_mfma.hip: MFMA, head_dim 64),
-// its builder, and the one launch helper.  wf3d_attn_fwd / wf3d_attn_bwd (attn.hip) validate, build the block once and
+// The argument block of the attention kernels (attn.hip: VALU, any head width; attn_mfma.hip: MFMA, head_dim 64 and the
+// multiples of 4 up to 128), its builder, and the one launch helper.  wf3d_attn_fwd / wf3d_attn_bwd (attn.hip) validate, build the block once and
 // launch the VALU kernels themselves or hand the block to wf3d_attn_mfma_launch.
 #pragma once
 #include "wf3d_common.h"
@@ -44,6 +44,7 @@ static int wf3d_attn_launch(const char* who, K kernel, dim3 grid, size_t lds, co
     return WF3D_OK;
 }
 
-// The MFMA kernels (attn_mfma.hip): family 1 = sample resident in LDS (vmax <= 256), 2 = key-tiled (any vmax); the
-// families are attn.hip's attn_family.  Owns their LDS layout (`rows`), LDS sizes and launches.
+// The MFMA kernels (attn_mfma.hip): family 1 = sample resident in LDS (head_dim 64, vmax <= 256), 2 = key-tiled (any
+// vmax; head_dim 64, or 68..128 on the kernels of padded width 96 / 128 chosen from p.hd); the families are attn.hip's
+// attn_family.  Owns their LDS layout (`rows`), LDS sizes and launches.
 WF3D_INTERNAL int wf3d_attn_mfma_launch(AttnArgs p, int family, bool backward, int S, int vmax, hipStream_t stream);

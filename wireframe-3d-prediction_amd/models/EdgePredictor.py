@@ -24,7 +24,9 @@ class EdgePredictor(nn.Module):
             raise ValueError("the HIP edge head takes 1..8 coordinates per vertex (reference default: 3)")
         if hidden_dim % 16 or hidden_dim % num_heads or (hidden_dim // num_heads) % 4:
             # said at construction, not by a kernel in the middle of a backward pass: the row kernels work on 16-byte
-            # pieces of the hidden_dim / 4-wide layer, the attention kernels on 4-column pieces of a head
+            # pieces of the hidden_dim / 4-wide layer, the attention kernels on 4-column pieces of a head.  Head widths 64
+            # to 128 run on the matrix cores at any vertex count; widths up to 60 and above 128 on the VALU kernels, which
+            # above 128 refuse a call whose staged rows do not fit the LDS (about 140 vertices at width 132)
             raise ValueError(f"the HIP edge head needs hidden_dim % 16 == 0 and a head width (hidden_dim / num_heads) % 4 == 0 "
                              f"(got hidden_dim={hidden_dim}, num_heads={num_heads})")
         h = hidden_dim

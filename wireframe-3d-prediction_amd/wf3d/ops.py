@@ -790,13 +790,17 @@ def edge_scatter_dverts(dcv, meta, B, V):
 
 def attn_kernel(E, heads, vmax):
     """Which kernels serve attn_fwd / attn_bwd at these dims under the current options (wf3d_set_option "attn_tiled"):
-    0 = VALU, 1 = MFMA with the sample resident in LDS, 2 = MFMA key-tiled.  Needs no GPU."""
+    0 = VALU, 1 = MFMA with the sample resident in LDS (head width 64, vmax <= 256), 2 = MFMA key-tiled (head width 64
+    beyond 256 vertices; head widths 68..128 at every vmax).  Needs no GPU."""
     k = _lib.load().wf3d_attn_kernel(int(E), int(heads), int(vmax))
     check(min(k, 0), "attn_kernel")
     return k
 
 
 def attn_fwd(qkv, meta, E, heads, drop_p=0.0, seed=0):
+    """(ctx [Rv, E], lse [Rv, heads]) of the self-attention over each sample's rows of qkv [Rv, 3E].  Head widths E / heads
+    in 64..128 (multiples of 4) run on the matrix cores at any vertex count; widths up to 60 and above 128 on the VALU
+    kernels, which refuse a width above 64 once its staged rows no longer fit the LDS (include/wf3d.h)."""
     _need_cuda(qkv)
     alloc = torch.zeros if meta.padded else torch.empty       # the kernels write real samples' rows only
     ctx = alloc(meta.Rv, E, dtype=torch.float32, device=qkv.device)
@@ -807,6 +811,7 @@ def attn_fwd(qkv, meta, E, heads, drop_p=0.0, seed=0):
 
 
 def attn_bwd(qkv, dctx, ctx, lse, meta, E, heads, drop_p=0.0, seed=0):
+    """dqkv [Rv, 3E] from the forward's ctx and lse; served by the kernel family that served attn_fwd (attn_kernel)."""
     _need_cuda(qkv, dctx, ctx, lse)
     if not (dctx.is_contiguous() and ctx.is_contiguous()):
         raise RuntimeError("wf3d.attn_bwd: contiguous dctx / ctx required")
