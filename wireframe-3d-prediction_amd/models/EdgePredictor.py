@@ -12,9 +12,8 @@ wf3d.config.set_edge_inference("stream") sends all three to the forward-only pat
 import torch
 import torch.nn as nn
 
-from wf3d import config, infer, ops
-from wf3d.functional import EdgeFn, edge_index_lists
-from wf3d.random import default_generator
+from wf3d import config, dropout, infer, ops
+from wf3d.functional import EdgeFn, EdgeParams, edge_index_lists
 
 
 class EdgePredictor(nn.Module):
@@ -41,7 +40,8 @@ class EdgePredictor(nn.Module):
             nn.Linear(h // 2, h // 4), nn.GELU(),
             nn.Linear(h // 4, 1))
         self._heads = num_heads
-        self.last_dropout_seeds = None      # dropout_rng "device": the int32 [5] seed words of the last train-mode forward
+        self.last_dropout_seed = None       # the seed the last train-mode call with an active site drew on the host
+        self.last_dropout_seeds = None      # dropout_rng "device": the int32 [5] seed words of that call instead
 
     def _get_edge_indices(self, num_vertices):
         """[E, 2] int64, all i<j in lexicographic order (reference :70-89)."""
@@ -52,23 +52,25 @@ class EdgePredictor(nn.Module):
 
     def _param_list(self):
         vp, at, em = self.vertex_proj, self.attention, self.edge_mlp
-        return [vp[0].weight, vp[0].bias, vp[1].weight, vp[1].bias,
-                vp[3].weight, vp[3].bias, vp[4].weight, vp[4].bias,
-                at.in_proj_weight, at.in_proj_bias, at.out_proj.weight, at.out_proj.bias,
-                em[0].weight, em[0].bias, em[1].weight, em[1].bias,
-                em[4].weight, em[4].bias, em[5].weight, em[5].bias,
-                em[8].weight, em[8].bias, em[10].weight, em[10].bias]
+        return EdgeParams(P0w=vp[0].weight, P0b=vp[0].bias, P1g=vp[1].weight, P1b=vp[1].bias,
+                          P3w=vp[3].weight, P3b=vp[3].bias, P4g=vp[4].weight, P4b=vp[4].bias,
+                          Aw=at.in_proj_weight, Ab=at.in_proj_bias, Ow=at.out_proj.weight, Ob=at.out_proj.bias,
+                          M0w=em[0].weight, M0b=em[0].bias, M1g=em[1].weight, M1b=em[1].bias,
+                          M4w=em[4].weight, M4b=em[4].bias, M5g=em[5].weight, M5b=em[5].bias,
+                          M8w=em[8].weight, M8b=em[8].bias, M10w=em[10].weight, M10b=em[10].bias)
+
+    def _sites(self):
+        # plain dict lookups (this runs on every forward): whatever module sits at the index now
+        m = self._modules
+        vp, em = m["vertex_proj"]._modules, m["edge_mlp"]._modules
+        return (("vertex_proj.5", vp["5"].p), ("attention", m["attention"].dropout),
+                ("edge_mlp.3", em["3"].p), ("edge_mlp.7", em["7"].p))
 
     def _dropout_ps(self):
-        if not self.training:
-            return (0.0, 0.0, 0.0, 0.0)
-        ps = (self.vertex_proj[5].p, self.attention.dropout, self.edge_mlp[3].p, self.edge_mlp[7].p)
-        for name, p in zip(("vertex_proj.5", "attention", "edge_mlp.3", "edge_mlp.7"), ps):
-            if not 0.0 <= float(p) < 1.0:
-                # torch would zero the whole site at p = 1; the dropout kernels take p in [0, 1)
-                raise ValueError(f"EdgePredictor: dropout p = {p} at {name} is not supported by the HIP edge head in train mode "
-                                 "(needs 0 <= p < 1)")
-        return ps
+        return dropout.site_ps(self, "edge head", self._sites())
+
+    def _dropout(self, device):
+        return dropout.module_drop(self, "edge head", self._sites(), device)
 
     @staticmethod
     def _ragged_counts(vertices, counts, who):
@@ -97,9 +99,8 @@ class EdgePredictor(nn.Module):
         counts = self._ragged_counts(vertices, counts, "forward_ragged")
         if self._stream():
             return self._edge_stream(vertices, ops.EdgeMeta.get(counts, vertices.device))
-        ps, seed = self._dropout(vertices.device)
-        return EdgeFn.apply(vertices.float(), tuple(counts), self._heads, ps, seed, config.precision(),
-                            *self._param_list())
+        return EdgeFn.apply(vertices.float(), tuple(counts), self._heads, config.precision(), *self._param_list(),
+                            *self._dropout(vertices.device))
 
     def _stream(self):
         """The forward-only path (wf3d.infer.edge_stream) serves this call: the edge setting asks for it, grad mode is
@@ -123,17 +124,6 @@ class EdgePredictor(nn.Module):
         return self._edge_stream(vertices, ops.EdgeMeta.get(self._ragged_counts(vertices, counts, "forward_stream"),
                                                             vertices.device), rows)
 
-    def _dropout(self, device):
-        ps = self._dropout_ps()
-        if not any(ps):
-            seed = 0
-        elif config.dropout_rng() == "device":
-            # seed words drawn on the device (wf3d.random): no host read, fresh on every replay of a captured step
-            seed = self.last_dropout_seeds = default_generator(device).draw()
-        else:
-            seed = int(torch.empty((), dtype=torch.int64).random_().item())
-        return ps, seed
-
     def forward_padded(self, vertices, counts, return_layout=False, tail="compute"):
         """vertices [B, V, 3]; counts: integer tensor [B] on the device, never read on the host.  Sample s uses its
         first c_s vertices, c_s clamped like `vertices[s, :counts[s]]` slicing.  Returns [B, V(V-1)/2]: sample s's first
@@ -151,8 +141,8 @@ class EdgePredictor(nn.Module):
         if self._stream():
             probs = self._edge_stream(vertices, meta)
         else:
-            ps, seed = self._dropout(vertices.device)
-            probs = EdgeFn.apply(vertices.float(), meta, self._heads, ps, seed, config.precision(), *self._param_list())
+            probs = EdgeFn.apply(vertices.float(), meta, self._heads, config.precision(), *self._param_list(),
+                                 *self._dropout(vertices.device))
         return (probs, meta.counts, meta.width) if return_layout else probs
 
     def forward(self, vertices):

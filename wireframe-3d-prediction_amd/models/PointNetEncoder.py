@@ -10,9 +10,8 @@ train() mode: its `p` is read on every call and the kernels draw the masks (INTE
 import torch
 import torch.nn as nn
 
-from wf3d import config, infer, ops
-from wf3d.functional import Drop, EncoderFn, EncoderFnPacked, EncoderFnPackedSkip, FusionFn
-from wf3d.random import default_generator
+from wf3d import config, dropout, infer, ops
+from wf3d.functional import EncoderFn, EncoderFnPacked, EncoderFnPackedSkip, FusionFn, FusionParams
 
 
 def _point_block(n_in, n_out):
@@ -59,43 +58,21 @@ class PointNetEncoder(nn.Module):
 
     def _fusion_params(self):
         ff = self.feature_fusion
-        return [ff[0].weight, ff[0].bias, ff[1].weight, ff[1].bias,
-                ff[3].weight, ff[3].bias, ff[4].weight, ff[4].bias,
-                ff[6].weight, ff[6].bias]
+        return FusionParams(F0w=ff[0].weight, F0b=ff[0].bias, F1g=ff[1].weight, F1b=ff[1].bias,
+                            F3w=ff[3].weight, F3b=ff[3].bias, F4g=ff[4].weight, F4b=ff[4].bias,
+                            F6w=ff[6].weight, F6b=ff[6].bias)
 
-    def _dropout_ps(self):
-        """The probabilities of the sites mlp.{4i+3}, i = 0 .. n_hidden-1, of this call: all 0 outside train mode."""
-        if not self.training:
-            return (0.0,) * self._n_hidden
+    def _sites(self):
         # plain dict lookups (this runs on every forward; Sequential.__getitem__ walks its modules): whatever module sits
         # at the index now, a replaced nn.Dropout included
         mods = self._modules["mlp"]._modules
-        ps = tuple([mods[k].p for k in self._site_keys])
-        if not any(ps):                      # every site at 0: nothing to check
-            return ps
-        for i, p in enumerate(ps):
-            if not 0.0 <= float(p) < 1.0:
-                # torch would zero the whole site at p = 1; the dropout kernels take p in [0, 1) (INTEGRATION.md)
-                raise ValueError(f"PointNetEncoder: dropout p = {p} at mlp.{4 * i + 3} is not supported by the HIP encoder in "
-                                 "train mode (needs 0 <= p < 1)")
-        return ps
+        return tuple([("mlp." + k, mods[k].p) for k in self._site_keys])
+
+    def _dropout_ps(self):
+        return dropout.site_ps(self, "encoder", self._sites())
 
     def _dropout(self, device):
-        """The trailing arguments of this call's EncoderFn: nothing while no site is active (no seed is drawn, every
-        launch is the one without a mask), else one Drop(ps, seed) — the seed drawn as EdgePredictor._dropout draws
-        its own, one value per module and forward."""
-        ps = self._dropout_ps()
-        if not any(ps):
-            return ()
-        if config.dropout_rng() == "device":
-            if any(ps[4:]):
-                raise ValueError(f"PointNetEncoder: dropout_rng 'device' draws five seed words per forward, which serve the "
-                                 f"first four sites; mlp.{4 * max(i for i, p in enumerate(ps) if p) + 3} is active "
-                                 "(set it to 0, or use wf3d.config.set_dropout_rng('host'))")
-            seed = self.last_dropout_seeds = default_generator(device).draw()
-        else:
-            seed = self.last_dropout_seed = int(torch.empty((), dtype=torch.int64).random_().item())
-        return (Drop(ps, seed),)
+        return dropout.module_drop(self, "encoder", self._sites(), device)
 
     def _stream_ok(self):
         """The forward-only path draws no masks: it serves a call only while no dropout site is active."""

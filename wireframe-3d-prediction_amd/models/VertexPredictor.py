@@ -10,9 +10,8 @@ generic GEMM kernels, which draw the masks, whatever the batch size (INTEGRATION
 import torch
 import torch.nn as nn
 
-from wf3d import config
-from wf3d.functional import Drop, UnmaskedPoolFn, VertexFn
-from wf3d.random import default_generator
+from wf3d import dropout
+from wf3d.functional import UnmaskedPoolFn, VertexFn, VertexParams
 
 
 def _stage(n_in, n_out):
@@ -41,44 +40,27 @@ class VertexPredictor(nn.Module):
         return self.point_pool_proj
 
     def _param_list(self, with_pool):
-        ps = []
-        for st in (self.vertex_mlp1, self.vertex_mlp2, self.vertex_mlp3, self.vertex_mlp4):
-            ps += [st[0].weight, st[0].bias, st[1].weight, st[1].bias]
-        ps += [self.final_layer.weight, self.final_layer.bias,
-               self.residual_proj1.weight, self.residual_proj1.bias,
-               self.residual_proj2.weight, self.residual_proj2.bias]
-        if with_pool:
-            ps += [self.point_pool_proj.weight, self.point_pool_proj.bias]
-        return ps
+        m1, m2, m3, m4 = self.vertex_mlp1, self.vertex_mlp2, self.vertex_mlp3, self.vertex_mlp4
+        fl, r1, r2 = self.final_layer, self.residual_proj1, self.residual_proj2
+        return VertexParams(W1=m1[0].weight, b1=m1[0].bias, g1=m1[1].weight, be1=m1[1].bias,
+                            W2=m2[0].weight, b2=m2[0].bias, g2=m2[1].weight, be2=m2[1].bias,
+                            W3=m3[0].weight, b3=m3[0].bias, g3=m3[1].weight, be3=m3[1].bias,
+                            W4=m4[0].weight, b4=m4[0].bias, g4=m4[1].weight, be4=m4[1].bias,
+                            Wf=fl.weight, bf=fl.bias, Wr1=r1.weight, br1=r1.bias, Wr2=r2.weight, br2=r2.bias,
+                            Wpp=self.point_pool_proj.weight if with_pool else None,
+                            bpp=self.point_pool_proj.bias if with_pool else None)
 
-    def _dropout_ps(self):
-        """The probabilities of the sites vertex_mlp{k}.3, k = 1..4, of this call: all 0 outside train mode."""
-        if not self.training:
-            return (0.0, 0.0, 0.0, 0.0)
+    def _sites(self):
         # plain dict lookups (this runs on every forward): whatever module sits at index 3 of each stage now
         m = self._modules
-        ps = (m["vertex_mlp1"]._modules["3"].p, m["vertex_mlp2"]._modules["3"].p, m["vertex_mlp3"]._modules["3"].p,
-              m["vertex_mlp4"]._modules["3"].p)
-        if not any(ps):                      # every site at 0: nothing to check
-            return ps
-        for k, p in enumerate(ps, 1):
-            if not 0.0 <= float(p) < 1.0:
-                # torch would zero the whole site at p = 1; the dropout kernels take p in [0, 1) (INTEGRATION.md)
-                raise ValueError(f"VertexPredictor: dropout p = {p} at vertex_mlp{k}.3 is not supported by the HIP vertex head "
-                                 "in train mode (needs 0 <= p < 1)")
-        return ps
+        return (("vertex_mlp1.3", m["vertex_mlp1"]._modules["3"].p), ("vertex_mlp2.3", m["vertex_mlp2"]._modules["3"].p),
+                ("vertex_mlp3.3", m["vertex_mlp3"]._modules["3"].p), ("vertex_mlp4.3", m["vertex_mlp4"]._modules["3"].p))
+
+    def _dropout_ps(self):
+        return dropout.site_ps(self, "vertex head", self._sites())
 
     def _dropout(self, device):
-        """The trailing arguments of this call's VertexFn: nothing while no site is active (no seed is drawn), else one
-        Drop(ps, seed), the seed drawn as EdgePredictor._dropout draws its own."""
-        ps = self._dropout_ps()
-        if not any(ps):
-            return ()
-        if config.dropout_rng() == "device":
-            seed = self.last_dropout_seeds = default_generator(device).draw()
-        else:
-            seed = self.last_dropout_seed = int(torch.empty((), dtype=torch.int64).random_().item())
-        return (Drop(ps, seed),)
+        return dropout.module_drop(self, "vertex head", self._sites(), device)
 
     def predict(self, global_features, upooled):
         """Vertex head from already-pooled point features, upooled = [mean | max] [B, 2C] (None -> no fusion)."""

@@ -15,7 +15,6 @@ normalised activations never exist in memory.
 Which kernels a Linear of the encoder's per-point MLP or of the edge MLP's two wide layers runs on, forward and
 backward, is its Route: decided once in the stage's forward (_encoder_routes, _edge_routes) and only read by backward.
 """
-import contextlib
 from collections import namedtuple
 from collections.abc import Sequence
 
@@ -23,8 +22,8 @@ import torch
 
 from . import config, ops
 from . import skinny as sk
+from .dropout import Drop, _seeded, _take_drop  # noqa: F401  (Drop: the stages' optional last argument)
 from .ops import ACT_GELU, ACT_NONE, ACT_RELU, NN, NT, TN, Pro
-from .random import seed_words
 
 
 def _saved(ctx):
@@ -62,43 +61,31 @@ def _lin_bwd(dz, a, W, pro_a):
     return ops.gemm(dz, a, TN, pro=pro_a), ops.gemm(dz, W, NN)
 
 
-# Train-mode dropout of the encoder's per-point MLP and of the vertex head (the edge head's is EdgeFn's own arguments).
-# A stage takes it as an optional LAST argument after its parameters — EncoderFn.apply(x, n_hidden, precision, *params,
-# Drop(ps, seed)) — so that a call without one is the call it always was.  ps: the probability of every site of the
-# stage in module order (encoder: mlp.{4i+3}, i = 0 .. n_hidden-1; vertex head: vertex_mlp{k}.3, k = 1..4), each in
-# [0, 1).  seed: the value the module drew on the host (site k = 1, 2, ... masks with (seed + 0x9E3779B9 k) mod 2^32,
-# EdgeFn's rule), or the five device seed words of wf3d.random (an int32 tensor; site k masks with words[k], k <= 4).
-# The mask of a site is wf3d_keep(site seed, row, col): row = the row of the matrix the stage's Linears run on (point
-# row b * N + n of a dense batch, buffer row of a packed one; sample index in the vertex head), col = the feature.
-Drop = namedtuple("Drop", "ps seed")
-
-_GOLDEN = 0x9E3779B9
+# Parameter blocks: a stage's parameters by name.  Each Function takes them positionally (*params, in field order) and
+# rebuilds its block once in forward and once in backward; the models build the blocks by keyword, next to their module trees.
+FusionParams = namedtuple("FusionParams", "F0w F0b F1g F1b F3w F3b F4g F4b F6w F6b")
+VertexParams = namedtuple("VertexParams", "W1 b1 g1 be1 W2 b2 g2 be2 W3 b3 g3 be3 W4 b4 g4 be4 Wf bf Wr1 br1 Wr2 br2 Wpp bpp",
+                          defaults=(None, None))                 # Wpp, bpp: point_pool_proj, created lazily
+EdgeParams = namedtuple("EdgeParams", "P0w P0b P1g P1b P3w P3b P4g P4b Aw Ab Ow Ob "
+                                      "M0w M0b M1g M1b M4w M4b M5g M5b M8w M8b M10w M10b")
+MlpLayer = namedtuple("MlpLayer", "W b gamma beta", defaults=(None, None))
 
 
-def _take_drop(params, n_sites, who):
-    """(params, ps, site seeds, device words or None) of a stage's trailing arguments.  No Drop, or one whose sites are all
-    0: no site is active — ps all 0.0, no words, and every launch of the stage is the one without a mask."""
-    drop = None
-    if params and isinstance(params[-1], Drop):
-        params, drop = params[:-1], params[-1]
-    if drop is None or not any(drop.ps):
-        return params, (0.0,) * n_sites, (0,) * n_sites, None
-    ps = tuple(float(p) for p in drop.ps)
-    if len(ps) != n_sites or not all(0.0 <= p < 1.0 for p in ps):
-        raise ValueError(f"{who}: Drop.ps must be {n_sites} probabilities in [0, 1) (got {drop.ps})")
-    if torch.is_tensor(drop.seed):
-        if any(p > 0 for p in ps[4:]):
-            raise ValueError(f"{who}: a draw of device seed words serves four dropout sites; site "
-                             f"{max(k for k, p in enumerate(ps, 1) if p > 0)} is active (use the host seed mode, "
-                             "wf3d.config.set_dropout_rng('host'))")
-        return params, ps, tuple(range(1, n_sites + 1)), drop.seed
-    return params, ps, tuple((int(drop.seed) + _GOLDEN * k) & 0xFFFFFFFF for k in range(1, n_sites + 1)), None
+def _grads_of(block):
+    """The gradient collector of a parameter block: one slot per field, set by name (a name the block does not have
+    raises); out() is the gradients in field order, None where none was set."""
+    def out(self):
+        return [getattr(self, f, None) for f in block._fields]
+    return type(block.__name__ + "Grads", (), {"__slots__": block._fields, "out": out})
 
 
-def _seeded(words):
-    """The seed source of a stage's launches: the device words of its Drop (set for this thread, forward and again in
-    backward, which autograd runs on a thread of its own), or nothing to set."""
-    return seed_words(words) if words is not None else contextlib.nullcontext()
+FusionGrads, VertexGrads, EdgeGrads, MlpLayerGrads = map(_grads_of, (FusionParams, VertexParams, EdgeParams, MlpLayer))
+
+
+def mlp_layers(params, n_hidden):
+    """The encoder's flat [W_i, b_i, gamma_i, beta_i] * n_hidden + [W_out, b_out] as one MlpLayer per Linear; the output
+    layer's gamma and beta are None."""
+    return [MlpLayer(*params[4 * i:4 * i + 4]) for i in range(n_hidden + 1)]
 
 
 _side_streams = {}
@@ -310,30 +297,29 @@ def _encoder_forward(ctx, x2, pools, n_hidden, precision, params, tail="compute"
     and EncoderFnPacked.  Returns (PoolOut, point_features [rows, C]).  tail="skip": a packed batch with a capacity runs
     under its live row total where the routes allow it (_encoder_live); the backward follows ctx.live.
     params may end in a Drop (train-mode dropout at mlp.{4i+3}): site i masks h_i = relu(LN(z_i)) in whichever launch
-    produces or re-applies it, forward and backward (ctx.drop = (ps, site seeds, device words))."""
-    params, ps, sd, words = _take_drop(params, n_hidden, "EncoderFn")
-    ctx.drop = (ps, sd, words)
-    routes = _encoder_routes(x2, [params[4 * i] for i in range(n_hidden + 1)], precision in _SPLIT_PRODUCTS,
-                             ctx.needs_input_grad[0])
+    produces or re-applies it, forward and backward (ctx.drop = [ps, site seeds, device words])."""
+    rest, *ctx.drop = _take_drop(params, n_hidden, "EncoderFn")
+    ctx.n_extra = len(params) - len(rest)                        # a trailing Drop takes a (None) gradient slot
+    params, layers = rest, mlp_layers(rest, n_hidden)
+    routes = _encoder_routes(x2, [L.W for L in layers], precision in _SPLIT_PRODUCTS, ctx.needs_input_grad[0])
     ctx.live = live = _encoder_live(getattr(pools, "layout", None), routes, tail)
-    with ops.live_rows(live), _seeded(words):
-        return _encoder_forward_rows(ctx, x2, pools, n_hidden, precision, params, routes)
+    with ops.live_rows(live), _seeded(ctx.drop[2]):
+        return _encoder_forward_rows(ctx, x2, pools, n_hidden, precision, params, layers, routes)
 
 
-def _encoder_forward_rows(ctx, x2, pools, n_hidden, precision, params, routes):
+def _encoder_forward_rows(ctx, x2, pools, n_hidden, precision, params, layers, routes):
     npr = _SPLIT_PRODUCTS.get(precision, 3)
     ps, sd, _ = ctx.drop
     valid = ops.point_valid(x2)
     # both sx8 orientations (W for the forward GEMM, W^T for its dgrad) of every layer split both ways, one launch
     widx = [i for i, r in enumerate(routes) if r.fwd == "split" and r.dgrad == "split"]
-    wsplit = dict(zip(widx, ops.split_weights([params[4 * i] for i in widx]))) if widx else {}
+    wsplit = dict(zip(widx, ops.split_weights([layers[i].W for i in widx]))) if widx else {}
     zs, stats, hs = [], [], []                 # hs[i] = sx8 operand consumed by Linear i+1 (kept for its wgrad)
     a, a_s, pro = x2, None, None
-    for i, r in enumerate(routes):
-        W, b = params[4 * i], params[4 * i + 1]
+    for i, (r, (W, b, g, be)) in enumerate(zip(routes, layers)):
         if r.fwd == "first":
             # first Linear + LayerNorm + ReLU + split in one pass (K = input_dim <= 8: a pure write of z and h)
-            z, mu, rs, a_s = ops.first_layer_fwd(x2, W, b, params[2], params[3], ACT_RELU, drop_p=ps[0], seed=sd[0])
+            z, mu, rs, a_s = ops.first_layer_fwd(x2, W, b, g, be, ACT_RELU, drop_p=ps[i], seed=sd[i])
         elif r.fwd == "split":
             if i in wsplit:
                 W_s = wsplit[i][0]
@@ -347,7 +333,6 @@ def _encoder_forward_rows(ctx, x2, pools, n_hidden, precision, params, routes):
         if i == n_hidden:
             pf = z
             break
-        g, be = params[4 * i + 2], params[4 * i + 3]
         if r.fwd == "first":
             pass
         elif routes[i + 1].fwd == "split":
@@ -381,10 +366,10 @@ def _encoder_backward(ctx, dpooled, dpf, dupooled):
 
 def _encoder_backward_rows(ctx, dpooled, dpf, dupooled):
     nh, pools, C, npr, routes = ctx.n_hidden, ctx.pools, ctx.width, ctx.products, ctx.routes
-    params = _params(ctx)
+    layers = mlp_layers(_params(ctx), nh)
     ps, sd, _ = ctx.drop
     x2, valid, zs, stats, hs, arg_m, arg_u, cnt = _saved(ctx)
-    grads = [None] * len(params)
+    Gs = [MlpLayerGrads() for _ in layers]
     # the pooled cotangents are read as strided halves of the [B, 2C] gradients: no copies
     dmmax = dmavg = dumean = dumax = None
     if dpooled is not None:
@@ -400,36 +385,34 @@ def _encoder_backward_rows(ctx, dpooled, dpf, dupooled):
     cots = (dmmax, dmavg, dumean, dumax)
     if routes[nh].wgrad == "tn":
         dz, dz_s = None, pools.bwd(valid, cnt, arg_m, arg_u, cots, dpf, C, sx8=True)
-        grads[4 * nh + 1] = pools.colsum(valid, ctx.nvalid, cnt, arg_m, arg_u, cots, dpf, C)
+        Gs[nh].b = pools.colsum(valid, ctx.nvalid, cnt, arg_m, arg_u, cots, dpf, C)
     else:
         dz = pools.bwd(valid, cnt, arg_m, arg_u, cots, dpf, C)
         dz_s = None
     # per-point MLP backward, output layer first.  Entering iteration i: dz = grad wrt the
     # pre-LN output of Linear i in fp32 and / or, on a split dgrad, dz_s = the same in sx8.
     for i in range(nh, -1, -1):
-        r, W = routes[i], params[4 * i]
+        r, (W, _, g, be), G = routes[i], layers[i], Gs[i]
         if r.wgrad == "first":
             # layer 0: LN/ReLU backward, bias and WEIGHT gradient in one pass over (dh, z); dz is never written
-            g, be = params[2], params[3]
-            grads[2], grads[3], grads[1], grads[0] = ops.ln_act_bwd_first(dh, zs[0], x2, stats[0][0], stats[0][1], g, be, ACT_RELU,
-                                                                          drop_p=ps[0], seed=sd[0])
+            G.gamma, G.beta, G.b, G.W = ops.ln_act_bwd_first(dh, zs[i], x2, stats[i][0], stats[i][1], g, be, ACT_RELU,
+                                                             drop_p=ps[i], seed=sd[i])
             break
         if i < nh:
-            g, be = params[4 * i + 2], params[4 * i + 3]
             mu, rs = stats[i]
             dz_s = torch.empty_like(dh) if r.dgrad == "split" else None
-            dz, grads[4 * i + 2], grads[4 * i + 3], grads[4 * i + 1] = ops.ln_act_bwd(
+            dz, G.gamma, G.beta, G.b = ops.ln_act_bwd(
                 dh, zs[i], mu, rs, g, be, ACT_RELU, ps[i], sd[i], inplace=True, dz_split=dz_s, want_dz=_dz32(r))
         elif dz is not None:
-            grads[4 * i + 1] = ops.colsum(dz)
+            G.b = ops.colsum(dz)
             if r.dgrad == "split":
                 dz_s = ops.split_rows(dz)
         if i > 0:
-            pg, pb = params[4 * (i - 1) + 2], params[4 * (i - 1) + 3]
-            h, pro, h_s = zs[i - 1], Pro(ACT_RELU, stats[i - 1][0], stats[i - 1][1], pg, pb, ps[i - 1], sd[i - 1]), hs[i - 1]
+            prev = layers[i - 1]
+            h, pro, h_s = zs[i - 1], Pro(ACT_RELU, stats[i - 1][0], stats[i - 1][1], prev.gamma, prev.beta, ps[i - 1], sd[i - 1]), hs[i - 1]
         else:
             h, pro, h_s = x2, None, None
-        grads[4 * i] = _wgrad(r, dz, dz_s, h, pro, h_s, npr)
+        G.W = _wgrad(r, dz, dz_s, h, pro, h_s, npr)
         if r.wgrad == "tn" and not config.RETAIN_SAVED:
             hs[i - 1] = None
         if r.dgrad is not None:
@@ -439,7 +422,7 @@ def _encoder_backward_rows(ctx, dpooled, dpf, dupooled):
     dx = dh if routes[0].dgrad is not None else None
     if not config.RETAIN_SAVED:
         ctx.saved = None
-    return dx, grads
+    return dx, [g for G in Gs for g in G.out()][:len(ctx.params)]            # the output layer has no gamma, beta
 
 
 class EncoderFn(torch.autograd.Function):
@@ -469,7 +452,6 @@ class EncoderFn(torch.autograd.Function):
             x2 = x2.contiguous()
         po, pf = _encoder_forward(ctx, x2, _DensePools(B, N), n_hidden, precision, params)
         ctx.dims = (B, N, pf.shape[1])
-        ctx.n_extra = len(params) - len(ctx.params)              # a trailing Drop takes a (None) gradient slot
         return po.masked, pf.view(B, N, -1), po.unmasked
 
     @staticmethod
@@ -502,7 +484,6 @@ class EncoderFnPacked(torch.autograd.Function):
             x2 = x.new_zeros(layout.M_pad, Din)
             x2[:M].copy_(x)
         po, pf = _encoder_forward(ctx, x2, _PackedPools(layout), n_hidden, precision, params, tail)
-        ctx.n_extra = len(params) - len(ctx.params)
         return po.masked, pf[:M], po.unmasked
 
     @staticmethod
@@ -534,51 +515,52 @@ class FusionFn(torch.autograd.Function):
     (csrc/skinny.hip); otherwise the generic GEMM path."""
 
     @staticmethod
-    def forward(ctx, pooled, *F):
+    def forward(ctx, pooled, *params):
         pooled = pooled if pooled.stride(1) == 1 else pooled.contiguous()
         M = pooled.shape[0]
-        _keep_params(ctx, F)
-        ctx.skinny = sk.ok(M, F[0], F[4], F[8]) and F[0].shape[0] % 16 == 0 and F[4].shape[0] % 16 == 0 \
+        _keep_params(ctx, params)
+        P = FusionParams(*params)
+        ctx.skinny = sk.ok(M, P.F0w, P.F3w, P.F6w) and P.F0w.shape[0] % 16 == 0 and P.F3w.shape[0] % 16 == 0 \
             and pooled.stride(0) % 4 == 0
         if ctx.skinny:
-            (f0, p0, _), = sk.fwd(M, sk.Fwd(pooled, F[0], F[1], stats=True))
-            (f3, p3, s0), = sk.fwd(M, sk.Fwd(f0, F[4], F[5], ln=sk.LNIn(F[2], F[3], ACT_RELU, part=p0), stats=True))
-            (gl, _, s3), = sk.fwd(M, sk.Fwd(f3, F[8], F[9], ln=sk.LNIn(F[6], F[7], ACT_RELU, part=p3)))
+            (f0, p0, _), = sk.fwd(M, sk.Fwd(pooled, P.F0w, P.F0b, stats=True))
+            (f3, p3, s0), = sk.fwd(M, sk.Fwd(f0, P.F3w, P.F3b, ln=sk.LNIn(P.F1g, P.F1b, ACT_RELU, part=p0), stats=True))
+            (gl, _, s3), = sk.fwd(M, sk.Fwd(f3, P.F6w, P.F6b, ln=sk.LNIn(P.F4g, P.F4b, ACT_RELU, part=p3)))
         else:
-            f0 = ops.gemm(pooled, F[0], NT, bias=F[1])
+            f0 = ops.gemm(pooled, P.F0w, NT, bias=P.F0b)
             s0 = ops.row_stats(f0)
-            f3 = ops.gemm(f0, F[4], NT, bias=F[5], pro=Pro(ACT_RELU, s0[0], s0[1], F[2], F[3]))
+            f3 = ops.gemm(f0, P.F3w, NT, bias=P.F3b, pro=Pro(ACT_RELU, s0[0], s0[1], P.F1g, P.F1b))
             s3 = ops.row_stats(f3)
-            gl = ops.gemm(f3, F[8], NT, bias=F[9], pro=Pro(ACT_RELU, s3[0], s3[1], F[6], F[7]))
+            gl = ops.gemm(f3, P.F6w, NT, bias=P.F6b, pro=Pro(ACT_RELU, s3[0], s3[1], P.F4g, P.F4b))
         ctx.saved = (pooled, f0, s0, f3, s3)
         return gl
 
     @staticmethod
     def backward(ctx, dgl):
-        F = _params(ctx)
+        P = FusionParams(*_params(ctx))
         pooled, f0, s0, f3, s3 = _saved(ctx)
-        G = [None] * 10
+        G = FusionGrads()
         dgl = dgl.contiguous()
         if ctx.skinny:
             M = dgl.shape[0]
-            l3 = sk.LNIn(F[6], F[7], ACT_RELU, mu=s3[0], rs=s3[1])
-            l0 = sk.LNIn(F[2], F[3], ACT_RELU, mu=s0[0], rs=s0[1])
-            (G[8], G[9], sl), = sk.bwd(M, sk.Bwd(dgl, F[8], f3, x_ln=l3))
-            _, g3, G[6], G[7], rp3 = sk.reduce(M, F[8].shape[1], [sl], want_dh=False, ln=(f3, s3[0], s3[1], F[6], F[7], ACT_RELU))
-            (G[4], G[5], sl), = sk.bwd(M, sk.Bwd(g3, F[4], f0, ln_out=sk.LNOut(f3, s3[0], s3[1], rp3), x_ln=l0))
-            _, g0, G[2], G[3], rp0 = sk.reduce(M, F[4].shape[1], [sl], want_dh=False, ln=(f0, s0[0], s0[1], F[2], F[3], ACT_RELU))
-            (G[0], G[1], sl), = sk.bwd(M, sk.Bwd(g0, F[0], pooled, ln_out=sk.LNOut(f0, s0[0], s0[1], rp0)))
-            dpooled, *_ = sk.reduce(M, F[0].shape[1], [sl])
+            l3 = sk.LNIn(P.F4g, P.F4b, ACT_RELU, mu=s3[0], rs=s3[1])
+            l0 = sk.LNIn(P.F1g, P.F1b, ACT_RELU, mu=s0[0], rs=s0[1])
+            (G.F6w, G.F6b, sl), = sk.bwd(M, sk.Bwd(dgl, P.F6w, f3, x_ln=l3))
+            _, g3, G.F4g, G.F4b, rp3 = sk.reduce(M, P.F6w.shape[1], [sl], want_dh=False, ln=(f3, s3[0], s3[1], P.F4g, P.F4b, ACT_RELU))
+            (G.F3w, G.F3b, sl), = sk.bwd(M, sk.Bwd(g3, P.F3w, f0, ln_out=sk.LNOut(f3, s3[0], s3[1], rp3), x_ln=l0))
+            _, g0, G.F1g, G.F1b, rp0 = sk.reduce(M, P.F3w.shape[1], [sl], want_dh=False, ln=(f0, s0[0], s0[1], P.F1g, P.F1b, ACT_RELU))
+            (G.F0w, G.F0b, sl), = sk.bwd(M, sk.Bwd(g0, P.F0w, pooled, ln_out=sk.LNOut(f0, s0[0], s0[1], rp0)))
+            dpooled, *_ = sk.reduce(M, P.F0w.shape[1], [sl])
         else:
-            G[9] = ops.colsum(dgl)
-            G[8], dh = _lin_bwd(dgl, f3, F[8], Pro(ACT_RELU, s3[0], s3[1], F[6], F[7]))
-            dz, G[6], G[7], G[5] = ops.ln_act_bwd(dh, f3, s3[0], s3[1], F[6], F[7], ACT_RELU, inplace=True)
-            G[4], dh = _lin_bwd(dz, f0, F[4], Pro(ACT_RELU, s0[0], s0[1], F[2], F[3]))
-            dz, G[2], G[3], G[1] = ops.ln_act_bwd(dh, f0, s0[0], s0[1], F[2], F[3], ACT_RELU, inplace=True)
-            G[0], dpooled = _lin_bwd(dz, pooled, F[0], None)
+            G.F6b = ops.colsum(dgl)
+            G.F6w, dh = _lin_bwd(dgl, f3, P.F6w, Pro(ACT_RELU, s3[0], s3[1], P.F4g, P.F4b))
+            dz, G.F4g, G.F4b, G.F3b = ops.ln_act_bwd(dh, f3, s3[0], s3[1], P.F4g, P.F4b, ACT_RELU, inplace=True)
+            G.F3w, dh = _lin_bwd(dz, f0, P.F3w, Pro(ACT_RELU, s0[0], s0[1], P.F1g, P.F1b))
+            dz, G.F1g, G.F1b, G.F0b = ops.ln_act_bwd(dh, f0, s0[0], s0[1], P.F1g, P.F1b, ACT_RELU, inplace=True)
+            G.F0w, dpooled = _lin_bwd(dz, pooled, P.F0w, None)
         if not config.RETAIN_SAVED:
             ctx.saved = None
-        return (dpooled, *G)
+        return (dpooled, *G.out())
 
 
 # ===========================================================================
@@ -600,51 +582,49 @@ class VertexFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, g, upooled, V, vd, *params):
-        ctx.n_extra = len(params)
-        params, ps, sd, words = _take_drop(params, 4, "VertexFn")
-        ctx.n_extra -= len(params)
-        ctx.drop = (ps, sd, words)
-        with _seeded(words):
-            return VertexFn._forward(ctx, g, upooled, V, vd, *params)
+        rest, *ctx.drop = _take_drop(params, 4, "VertexFn")
+        ctx.n_extra = len(params) - len(rest)                    # a trailing Drop takes a (None) gradient slot
+        with _seeded(ctx.drop[2]):
+            return VertexFn._forward(ctx, g, upooled, V, vd, *rest)
 
     @staticmethod
     def _forward(ctx, g, upooled, V, vd, *params):
         ps, sd, _ = ctx.drop
         g = g.contiguous()
         B = g.shape[0]
-        (W1, b1, g1, be1, W2, b2, g2, be2, W3, b3, g3, be3, W4, b4, g4, be4, Wf, bf, Wr1, br1, Wr2, br2) = params[:22]
+        P = VertexParams(*params)
         if upooled is not None:
             upooled = upooled if upooled.stride(1) == 1 else upooled.contiguous()
-        mats = [W1, W2, W3, W4, Wf, Wr1, Wr2] + ([params[22]] if upooled is not None else [])
-        ctx.skinny = sk.ok(B, *mats) and all(w.shape[0] % 16 == 0 for w in (W1, W2, W3, W4)) \
+        mats = [P.W1, P.W2, P.W3, P.W4, P.Wf, P.Wr1, P.Wr2] + ([P.Wpp] if upooled is not None else [])
+        ctx.skinny = sk.ok(B, *mats) and all(w.shape[0] % 16 == 0 for w in (P.W1, P.W2, P.W3, P.W4)) \
             and (upooled is None or upooled.stride(0) % 4 == 0) and not any(ps)
         if ctx.skinny:
             if upooled is not None:
-                (e, _, _), = sk.fwd(B, sk.Fwd(upooled, params[22], params[23], out_add=g))     # enhanced = g + proj (:99-100)
+                (e, _, _), = sk.fwd(B, sk.Fwd(upooled, P.Wpp, P.bpp, out_add=g))     # enhanced = g + proj (:99-100)
             else:
                 e = g
-            (z1, p1, _), (r1, _, _), (r2, _, _) = sk.fwd(B, sk.Fwd(e, W1, b1, stats=True), sk.Fwd(e, Wr1, br1), sk.Fwd(e, Wr2, br2))
-            (z2, p2, s1), = sk.fwd(B, sk.Fwd(z1, W2, b2, ln=sk.LNIn(g1, be1, ACT_RELU, part=p1), stats=True))
-            (z3, p3, s2), = sk.fwd(B, sk.Fwd(z2, W3, b3, ln=sk.LNIn(g2, be2, ACT_RELU, part=p2), stats=True))
+            (z1, p1, _), (r1, _, _), (r2, _, _) = sk.fwd(B, sk.Fwd(e, P.W1, P.b1, stats=True), sk.Fwd(e, P.Wr1, P.br1), sk.Fwd(e, P.Wr2, P.br2))
+            (z2, p2, s1), = sk.fwd(B, sk.Fwd(z1, P.W2, P.b2, ln=sk.LNIn(P.g1, P.be1, ACT_RELU, part=p1), stats=True))
+            (z3, p3, s2), = sk.fwd(B, sk.Fwd(z2, P.W3, P.b3, ln=sk.LNIn(P.g2, P.be2, ACT_RELU, part=p2), stats=True))
             # residual after the ReLU (:110,:114), applied on load
-            (z4, p4, s3), = sk.fwd(B, sk.Fwd(z3, W4, b4, ln=sk.LNIn(g3, be3, ACT_RELU, part=p3), in_add=r1, stats=True))
-            (o, _, s4), = sk.fwd(B, sk.Fwd(z4, Wf, bf, ln=sk.LNIn(g4, be4, ACT_RELU, part=p4), in_add=r2))
+            (z4, p4, s3), = sk.fwd(B, sk.Fwd(z3, P.W4, P.b4, ln=sk.LNIn(P.g3, P.be3, ACT_RELU, part=p3), in_add=r1, stats=True))
+            (o, _, s4), = sk.fwd(B, sk.Fwd(z4, P.Wf, P.bf, ln=sk.LNIn(P.g4, P.be4, ACT_RELU, part=p4), in_add=r2))
             c, d = r1, r2
         else:
             if upooled is not None:
-                e = ops.gemm(upooled, params[22], NT, bias=params[23], addend=g)
+                e = ops.gemm(upooled, P.Wpp, NT, bias=P.bpp, addend=g)
             else:
                 e = g
-            z1 = ops.gemm(e, W1, NT, bias=b1); s1 = ops.row_stats(z1)
-            z2 = ops.gemm(z1, W2, NT, bias=b2, pro=Pro(ACT_RELU, s1[0], s1[1], g1, be1, ps[0], sd[0])); s2 = ops.row_stats(z2)
-            z3 = ops.gemm(z2, W3, NT, bias=b3, pro=Pro(ACT_RELU, s2[0], s2[1], g2, be2, ps[1], sd[1])); s3 = ops.row_stats(z3)
-            r1 = ops.gemm(e, Wr1, NT, bias=br1)
+            z1 = ops.gemm(e, P.W1, NT, bias=P.b1); s1 = ops.row_stats(z1)
+            z2 = ops.gemm(z1, P.W2, NT, bias=P.b2, pro=Pro(ACT_RELU, s1[0], s1[1], P.g1, P.be1, ps[0], sd[0])); s2 = ops.row_stats(z2)
+            z3 = ops.gemm(z2, P.W3, NT, bias=P.b3, pro=Pro(ACT_RELU, s2[0], s2[1], P.g2, P.be2, ps[1], sd[1])); s3 = ops.row_stats(z3)
+            r1 = ops.gemm(e, P.Wr1, NT, bias=P.br1)
             # residual after the ReLU and its dropout (:110)
-            c = ops.ln_act_apply(z3, s3[0], s3[1], g3, be3, ACT_RELU, addend=r1, drop_p=ps[2], seed=sd[2])
-            z4 = ops.gemm(c, W4, NT, bias=b4); s4 = ops.row_stats(z4)
-            r2 = ops.gemm(e, Wr2, NT, bias=br2)
-            d = ops.ln_act_apply(z4, s4[0], s4[1], g4, be4, ACT_RELU, addend=r2, drop_p=ps[3], seed=sd[3])
-            o = ops.gemm(d, Wf, NT, bias=bf)
+            c = ops.ln_act_apply(z3, s3[0], s3[1], P.g3, P.be3, ACT_RELU, addend=r1, drop_p=ps[2], seed=sd[2])
+            z4 = ops.gemm(c, P.W4, NT, bias=P.b4); s4 = ops.row_stats(z4)
+            r2 = ops.gemm(e, P.Wr2, NT, bias=P.br2)
+            d = ops.ln_act_apply(z4, s4[0], s4[1], P.g4, P.be4, ACT_RELU, addend=r2, drop_p=ps[3], seed=sd[3])
+            o = ops.gemm(d, P.Wf, NT, bias=P.bf)
         exist, counts = ops.vertex_finalize_fwd(o, V, vd)
         _keep_params(ctx, params)
         ctx.dims = (B, V, vd)
@@ -659,103 +639,99 @@ class VertexFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, do3, dexist, _dcounts):
         with _seeded(ctx.drop[2]):
-            return (*VertexFn._backward(ctx, do3, dexist), *[None] * ctx.n_extra)
+            de, dupooled, G = VertexFn._backward(ctx, do3, dexist)
+        if not config.RETAIN_SAVED:
+            ctx.saved = None
+        # Wpp, bpp take a slot only when they were passed
+        return (de, dupooled, None, None, *G.out()[:len(ctx.params)], *[None] * ctx.n_extra)
 
     @staticmethod
     def _backward(ctx, do3, dexist):
-        params = _params(ctx)
         ps, sd, _ = ctx.drop
         B, V, vd = ctx.dims
-        (W1, b1, g1, be1, W2, b2, g2, be2, W3, b3, g3, be3, W4, b4, g4, be4, Wf, bf, Wr1, br1, Wr2, br2) = params[:22]
+        P = VertexParams(*_params(ctx))
         pooled, e, z1, s1, z2, s2, z3, s3, c, z4, s4, d = _saved(ctx)
         (exist,) = ctx.saved_tensors
-        G = [None] * len(params)
+        G = VertexGrads()
         do = ops.vertex_finalize_bwd(exist, dexist.contiguous() if dexist is not None else None,
                                      do3.contiguous() if do3 is not None else None, B, V, vd)
         if ctx.skinny:
             r1, r2 = c, d
             R = ACT_RELU
-            ln = [None, sk.LNIn(g1, be1, R, mu=s1[0], rs=s1[1]), sk.LNIn(g2, be2, R, mu=s2[0], rs=s2[1]),
-                  sk.LNIn(g3, be3, R, mu=s3[0], rs=s3[1]), sk.LNIn(g4, be4, R, mu=s4[0], rs=s4[1])]
+            ln = [None, sk.LNIn(P.g1, P.be1, R, mu=s1[0], rs=s1[1]), sk.LNIn(P.g2, P.be2, R, mu=s2[0], rs=s2[1]),
+                  sk.LNIn(P.g3, P.be3, R, mu=s3[0], rs=s3[1]), sk.LNIn(P.g4, P.be4, R, mu=s4[0], rs=s4[1])]
             # final layer: input d = relu(LN(z4)) + r2
-            (G[16], G[17], sl), = sk.bwd(B, sk.Bwd(do, Wf, z4, x_ln=ln[4], x_add=r2))
-            dd, G4, G[14], G[15], rp4 = sk.reduce(B, Wf.shape[1], [sl], ln=(z4, s4[0], s4[1], g4, be4, R))
+            (G.Wf, G.bf, sl), = sk.bwd(B, sk.Bwd(do, P.Wf, z4, x_ln=ln[4], x_add=r2))
+            dd, G4, G.g4, G.be4, rp4 = sk.reduce(B, P.Wf.shape[1], [sl], ln=(z4, s4[0], s4[1], P.g4, P.be4, R))
             # residual_proj2 (plain dz = dd) and vertex_mlp4 (input c = relu(LN(z3)) + r1) in one launch
-            (G[20], G[21], sl_e2), (G[12], G[13], sl) = sk.bwd(
-                B, sk.Bwd(dd, Wr2, e), sk.Bwd(G4, W4, z3, ln_out=sk.LNOut(z4, s4[0], s4[1], rp4), x_ln=ln[3], x_add=r1))
-            dc, G3, G[10], G[11], rp3 = sk.reduce(B, W4.shape[1], [sl], ln=(z3, s3[0], s3[1], g3, be3, R))
-            (G[18], G[19], sl_e1), (G[8], G[9], sl) = sk.bwd(
-                B, sk.Bwd(dc, Wr1, e), sk.Bwd(G3, W3, z2, ln_out=sk.LNOut(z3, s3[0], s3[1], rp3), x_ln=ln[2]))
-            _, G2, G[6], G[7], rp2 = sk.reduce(B, W3.shape[1], [sl], want_dh=False, ln=(z2, s2[0], s2[1], g2, be2, R))
-            (G[4], G[5], sl), = sk.bwd(B, sk.Bwd(G2, W2, z1, ln_out=sk.LNOut(z2, s2[0], s2[1], rp2), x_ln=ln[1]))
-            _, G1, G[2], G[3], rp1 = sk.reduce(B, W2.shape[1], [sl], want_dh=False, ln=(z1, s1[0], s1[1], g1, be1, R))
-            (G[0], G[1], sl_e0), = sk.bwd(B, sk.Bwd(G1, W1, e, ln_out=sk.LNOut(z1, s1[0], s1[1], rp1)))
-            de, *_ = sk.reduce(B, W1.shape[1], [sl_e0, sl_e1, sl_e2])
+            (G.Wr2, G.br2, sl_e2), (G.W4, G.b4, sl) = sk.bwd(
+                B, sk.Bwd(dd, P.Wr2, e), sk.Bwd(G4, P.W4, z3, ln_out=sk.LNOut(z4, s4[0], s4[1], rp4), x_ln=ln[3], x_add=r1))
+            dc, G3, G.g3, G.be3, rp3 = sk.reduce(B, P.W4.shape[1], [sl], ln=(z3, s3[0], s3[1], P.g3, P.be3, R))
+            (G.Wr1, G.br1, sl_e1), (G.W3, G.b3, sl) = sk.bwd(
+                B, sk.Bwd(dc, P.Wr1, e), sk.Bwd(G3, P.W3, z2, ln_out=sk.LNOut(z3, s3[0], s3[1], rp3), x_ln=ln[2]))
+            _, G2, G.g2, G.be2, rp2 = sk.reduce(B, P.W3.shape[1], [sl], want_dh=False, ln=(z2, s2[0], s2[1], P.g2, P.be2, R))
+            (G.W2, G.b2, sl), = sk.bwd(B, sk.Bwd(G2, P.W2, z1, ln_out=sk.LNOut(z2, s2[0], s2[1], rp2), x_ln=ln[1]))
+            _, G1, G.g1, G.be1, rp1 = sk.reduce(B, P.W2.shape[1], [sl], want_dh=False, ln=(z1, s1[0], s1[1], P.g1, P.be1, R))
+            (G.W1, G.b1, sl_e0), = sk.bwd(B, sk.Bwd(G1, P.W1, e, ln_out=sk.LNOut(z1, s1[0], s1[1], rp1)))
+            de, *_ = sk.reduce(B, P.W1.shape[1], [sl_e0, sl_e1, sl_e2])
             dupooled = None
             if pooled is not None:
-                Wpp = params[22]
-                (G[22], G[23], sl), = sk.bwd(B, sk.Bwd(de, Wpp, pooled))
-                dupooled, *_ = sk.reduce(B, Wpp.shape[1], [sl])
-            if not config.RETAIN_SAVED:
-                ctx.saved = None
-            return (de, dupooled, None, None, *G)
-        G[17] = ops.colsum(do)
-        G[16], dd = _lin_bwd(do, d, Wf, None)
+                (G.Wpp, G.bpp, sl), = sk.bwd(B, sk.Bwd(de, P.Wpp, pooled))
+                dupooled, *_ = sk.reduce(B, P.Wpp.shape[1], [sl])
+            return de, dupooled, G
+        G.bf = ops.colsum(do)
+        G.Wf, dd = _lin_bwd(do, d, P.Wf, None)
         # d = relu(LN(z4)) + r2
-        G[21] = ops.colsum(dd)
-        G[20] = ops.gemm(dd, e, TN)
-        de = ops.gemm(dd, Wr2, NN)
-        dz4, G[14], G[15], G[13] = ops.ln_act_bwd(dd, z4, s4[0], s4[1], g4, be4, ACT_RELU, ps[3], sd[3])
-        G[12], dc = _lin_bwd(dz4, c, W4, None)
+        G.br2 = ops.colsum(dd)
+        G.Wr2 = ops.gemm(dd, e, TN)
+        de = ops.gemm(dd, P.Wr2, NN)
+        dz4, G.g4, G.be4, G.b4 = ops.ln_act_bwd(dd, z4, s4[0], s4[1], P.g4, P.be4, ACT_RELU, ps[3], sd[3])
+        G.W4, dc = _lin_bwd(dz4, c, P.W4, None)
         # c = relu(LN(z3)) + r1
-        G[19] = ops.colsum(dc)
-        G[18] = ops.gemm(dc, e, TN)
-        ops.gemm(dc, Wr1, NN, out=de, accumulate=True)
-        dz3, G[10], G[11], G[9] = ops.ln_act_bwd(dc, z3, s3[0], s3[1], g3, be3, ACT_RELU, ps[2], sd[2])
-        G[8], dh = _lin_bwd(dz3, z2, W3, Pro(ACT_RELU, s2[0], s2[1], g2, be2, ps[1], sd[1]))
-        dz2, G[6], G[7], G[5] = ops.ln_act_bwd(dh, z2, s2[0], s2[1], g2, be2, ACT_RELU, ps[1], sd[1], inplace=True)
-        G[4], dh = _lin_bwd(dz2, z1, W2, Pro(ACT_RELU, s1[0], s1[1], g1, be1, ps[0], sd[0]))
-        dz1, G[2], G[3], G[1] = ops.ln_act_bwd(dh, z1, s1[0], s1[1], g1, be1, ACT_RELU, ps[0], sd[0], inplace=True)
-        G[0] = ops.gemm(dz1, e, TN)
-        ops.gemm(dz1, W1, NN, out=de, accumulate=True)
+        G.br1 = ops.colsum(dc)
+        G.Wr1 = ops.gemm(dc, e, TN)
+        ops.gemm(dc, P.Wr1, NN, out=de, accumulate=True)
+        dz3, G.g3, G.be3, G.b3 = ops.ln_act_bwd(dc, z3, s3[0], s3[1], P.g3, P.be3, ACT_RELU, ps[2], sd[2])
+        G.W3, dh = _lin_bwd(dz3, z2, P.W3, Pro(ACT_RELU, s2[0], s2[1], P.g2, P.be2, ps[1], sd[1]))
+        dz2, G.g2, G.be2, G.b2 = ops.ln_act_bwd(dh, z2, s2[0], s2[1], P.g2, P.be2, ACT_RELU, ps[1], sd[1], inplace=True)
+        G.W2, dh = _lin_bwd(dz2, z1, P.W2, Pro(ACT_RELU, s1[0], s1[1], P.g1, P.be1, ps[0], sd[0]))
+        dz1, G.g1, G.be1, G.b1 = ops.ln_act_bwd(dh, z1, s1[0], s1[1], P.g1, P.be1, ACT_RELU, ps[0], sd[0], inplace=True)
+        G.W1 = ops.gemm(dz1, e, TN)
+        ops.gemm(dz1, P.W1, NN, out=de, accumulate=True)
         dupooled = None
         if pooled is not None:
-            Wpp = params[22]
-            G[23] = ops.colsum(de)
-            G[22] = ops.gemm(de, pooled, TN)
-            dupooled = ops.gemm(de, Wpp, NN)
-        if not config.RETAIN_SAVED:
-            ctx.saved = None
-        return (de, dupooled, None, None, *G)
+            G.bpp = ops.colsum(de)
+            G.Wpp = ops.gemm(de, pooled, TN)
+            dupooled = ops.gemm(de, P.Wpp, NN)
+        return de, dupooled, G
 
 
 # ===========================================================================
 # Edge head (all samples of the batch in one pass, ragged)
 # ===========================================================================
-def _edge_vertex_section(verts, meta, heads, x3, params, drop_ps=(0.0, 0.0), seeds=(0, 0)):
+def _edge_vertex_section(verts, meta, heads, x3, P, drop_ps=(0.0, 0.0), seeds=(0, 0)):
     """The per-vertex section of the edge head (sum-of-counts rows): vertex_proj, attention with its residual, and the
     two projections Pa / Pb of edge_mlp.0 that the pair combine adds per edge.  EdgeFn._forward and infer.edge_stream
-    both run it; drop_ps / seeds: vertex_proj.5 and attention.
+    both run it on their EdgeParams block P; drop_ps / seeds: the stage's, of which vertex_proj.5 and attention lead.
     Returns cv, za, sa, zb, sb, f, qkv, cx, lse, Fm, Pa, Pb."""
-    P0w, P0b, P1g, P1b, P3w, P3b, P4g, P4b, Aw, Ab, Ow, Ob, M0w, M0b = params[:14]
-    H = P3w.shape[0]
+    M0w, H = P.M0w, P.P3w.shape[0]
     cv = ops.edge_gather_verts(verts, meta)
-    za = ops.gemm(cv, P0w, NT, bias=P0b); sa = ops.row_stats(za)
+    za = ops.gemm(cv, P.P0w, NT, bias=P.P0b); sa = ops.row_stats(za)
     # per-vertex Linears: in bf16x3 mode the fp32 operands are split inside the GEMM's staging pass (x3), forward and
     # backward; the K = 3 coordinate products stay exact fp32
-    zb = ops.gemm(za, P3w, NT, bias=P3b, pro=Pro(ACT_GELU, sa[0], sa[1], P1g, P1b), x3=x3); sb = ops.row_stats(zb)
-    f = ops.ln_act_apply(zb, sb[0], sb[1], P4g, P4b, ACT_NONE, drop_p=drop_ps[0], seed=seeds[0])
-    qkv = ops.gemm(f, Aw, NT, bias=Ab, x3=x3)
+    zb = ops.gemm(za, P.P3w, NT, bias=P.P3b, pro=Pro(ACT_GELU, sa[0], sa[1], P.P1g, P.P1b), x3=x3); sb = ops.row_stats(zb)
+    f = ops.ln_act_apply(zb, sb[0], sb[1], P.P4g, P.P4b, ACT_NONE, drop_p=drop_ps[0], seed=seeds[0])
+    qkv = ops.gemm(f, P.Aw, NT, bias=P.Ab, x3=x3)
     cx, lse = ops.attn_fwd(qkv, meta, H, heads, drop_ps[1], seeds[1])
-    Fm = ops.gemm(cx, Ow, NT, bias=Ob, addend=f, x3=x3)              # residual (EdgePredictor.py:114)
+    Fm = ops.gemm(cx, P.Ow, NT, bias=P.Ob, addend=f, x3=x3)              # residual (EdgePredictor.py:114)
     vd = cv.shape[1]                                   # coordinates per vertex (EdgePredictor(vertex_dim=...): 3 in the model)
     Wa, Wb, Wc, Wd = M0w[:, :H], M0w[:, H:2 * H], M0w[:, 2 * H:2 * H + vd], M0w[:, 2 * H + vd:2 * H + 2 * vd]
     if vd <= 4:
         # the coordinate columns ride on the two GEMMs as a rank-vd epilogue term (exact fp32)
-        Pa = ops.gemm(Fm, Wa, NT, bias=M0b, x3=x3, lowrank=(cv, Wc))
+        Pa = ops.gemm(Fm, Wa, NT, bias=P.M0b, x3=x3, lowrank=(cv, Wc))
         Pb = ops.gemm(Fm, Wb, NT, x3=x3, lowrank=(cv, Wd))
     else:
-        Pa = ops.gemm(Fm, Wa, NT, bias=M0b, x3=x3)
+        Pa = ops.gemm(Fm, Wa, NT, bias=P.M0b, x3=x3)
         ops.gemm(cv, Wc, NT, out=Pa, accumulate=True)
         Pb = ops.gemm(Fm, Wb, NT, x3=x3)
         ops.gemm(cv, Wd, NT, out=Pb, accumulate=True)
@@ -769,37 +745,34 @@ class EdgeFn(torch.autograd.Function):
     launch covers the worst-case B*V vertex and B*V(V-1)/2 edge rows, max_E = V(V-1)/2, and the kernels keep the rows
     past the live totals finite in forward and zero in backward (include/wf3d.h, "PADDED layouts").
 
-    params = [P0w,P0b, P1g,P1b, P3w,P3b, P4g,P4b, Aw,Ab, Ow,Ob,
-              M0w,M0b, M1g,M1b, M4w,M4b, M5g,M5b, M8w,M8b, M10w,M10b]
-    (vertex_proj.{0,1,3,4}, attention.{in_proj,out_proj}, edge_mlp.{0,1,4,5,8,10})
+    params = the fields of EdgeParams (vertex_proj.{0,1,3,4}, attention.{in_proj,out_proj}, edge_mlp.{0,1,4,5,8,10})
 
-    `seed` is the host-drawn seed (an int), or the device seed words of wf3d.random (an int32 tensor, dropout_rng
-    "device"): then the four site seeds are indices 1..4 into those words, which every mask kernel of the forward and
-    of the backward loads at run time."""
+    params may end in one Drop(ps, seed): train-mode dropout at vertex_proj.5, attention, edge_mlp.3 and edge_mlp.7.  With
+    the device seed words of wf3d.random (dropout_rng "device") the four site seeds are indices 1..4 into those words,
+    which every mask kernel of the forward and of the backward loads at run time."""
 
     @staticmethod
-    def forward(ctx, verts, counts, heads, drop_ps, seed, precision, *params):
-        words = seed if torch.is_tensor(seed) else None
-        ctx.words = words
-        with seed_words(words):
-            return EdgeFn._forward(ctx, verts, counts, heads, drop_ps, seed, precision, *params)
+    def forward(ctx, verts, counts, heads, precision, *params):
+        rest, *ctx.drop = _take_drop(params, 4, "EdgeFn")
+        ctx.n_extra = len(params) - len(rest)
+        with _seeded(ctx.drop[2]):
+            return EdgeFn._forward(ctx, verts, counts, heads, precision, *rest)
 
     @staticmethod
-    def _forward(ctx, verts, counts, heads, drop_ps, seed, precision, *params):
-        (P0w, P0b, P1g, P1b, P3w, P3b, P4g, P4b, Aw, Ab, Ow, Ob,
-         M0w, M0b, M1g, M1b, M4w, M4b, M5g, M5b, M8w, M8b, M10w, M10b) = params
+    def _forward(ctx, verts, counts, heads, precision, *params):
+        P = EdgeParams(*params)
+        ps, sd, _ = ctx.drop
+        _, _, p1_, p2_ = ps                                 # vertex_proj.5, attention, edge_mlp.3, edge_mlp.7
         B, V, _ = verts.shape
-        H = P3w.shape[0]
+        H = P.P3w.shape[0]
         # counts: host ints, or an EdgeMeta already built on the device (EdgePredictor.forward_padded)
         meta = counts if isinstance(counts, ops.EdgeMeta) else ops.EdgeMeta.get(counts, verts.device)
-        sd = [1, 2, 3, 4] if ctx.words is not None else [(seed + 0x9E3779B9 * k) & 0xFFFFFFFF for k in range(1, 5)]
-        pf_, pa_, p1_, p2_ = (float(x) for x in drop_ps)   # vertex_proj.5, attention, edge_mlp.3, edge_mlp.7
         x3 = precision == "bf16x3" and config.EDGE_X3
-        cv, za, sa, zb, sb, f, qkv, cx, lse, Fm, Pa, Pb = _edge_vertex_section(verts, meta, heads, x3, params, (pf_, pa_), sd[:2])
+        cv, za, sa, zb, sb, f, qkv, cx, lse, Fm, Pa, Pb = _edge_vertex_section(verts, meta, heads, x3, P, ps, sd)
         npr = _SPLIT_PRODUCTS.get(precision, 3)
         routes = _edge_routes(meta.Re, H, precision, x3)
         # decided once, here; backward only reads it (and the logits kernel chosen below)
-        rowdot = M10w.shape[0] == 1 and M10w.is_contiguous() and ops.rowdot_act_shape_ok(H // 4)
+        rowdot = P.M10w.shape[0] == 1 and P.M10w.is_contiguous() and ops.rowdot_act_shape_ok(H // 4)
         ctx.live = live = _edge_live(meta, routes, rowdot)
         # the launches over meta.Re edge rows: pair combine, edge_mlp.4 / .8 / .10, sigmoid
         with ops.live_rows(live):
@@ -809,28 +782,28 @@ class EdgeFn(torch.autograd.Function):
                 # second edge layer on the transposing-read kernel (operand h1) and the LayerNorm backward rebuilding the
                 # row from Pa / Pb (ops.edge_pair_ln_bwd, H <= 1024), nothing does.
                 keep_pre = routes[0].wgrad not in _TN or H > 1024
-                pre, mu0, rs0, delta, h1 = ops.edge_pair_fwd(Pa, Pb, cv, M0w, meta, ln=(M1g, M1b, ACT_GELU, p1_, sd[2]), keep_pre=keep_pre)
-                (M4s, M4t), (M8s, M8t) = ops.split_weights([M4w, M8w])
-                z2 = ops.gemm_split(h1, M4s, bias=M4b, products=npr)
-                mu2, rs2, h2 = ops.ln_prep(z2, M5g, M5b, ACT_GELU, drop_p=p2_, seed=sd[3])
+                pre, mu0, rs0, delta, h1 = ops.edge_pair_fwd(Pa, Pb, cv, P.M0w, meta, ln=(P.M1g, P.M1b, ACT_GELU, p1_, sd[2]), keep_pre=keep_pre)
+                (M4s, M4t), (M8s, M8t) = ops.split_weights([P.M4w, P.M8w])
+                z2 = ops.gemm_split(h1, M4s, bias=P.M4b, products=npr)
+                mu2, rs2, h2 = ops.ln_prep(z2, P.M5g, P.M5b, ACT_GELU, drop_p=p2_, seed=sd[3])
                 s2 = (mu2, rs2)
-                z3 = ops.gemm_split(h2, M8s, bias=M8b, products=npr)
+                z3 = ops.gemm_split(h2, M8s, bias=P.M8b, products=npr)
             else:
-                pre, mu0, rs0, delta = ops.edge_pair_fwd(Pa, Pb, cv, M0w, meta)
+                pre, mu0, rs0, delta = ops.edge_pair_fwd(Pa, Pb, cv, P.M0w, meta)
                 h1 = h2 = M4t = M8t = None
-                z2 = ops.gemm(pre, M4w, NT, bias=M4b, pro=Pro(ACT_GELU, mu0, rs0, M1g, M1b, p1_, sd[2]), x3=x3); s2 = ops.row_stats(z2)
-                z3 = ops.gemm(z2, M8w, NT, bias=M8b, pro=Pro(ACT_GELU, s2[0], s2[1], M5g, M5b, p2_, sd[3]), x3=x3)
-            fused_tail = ops.rowdot_act_ok(z3, M10w)
+                z2 = ops.gemm(pre, P.M4w, NT, bias=P.M4b, pro=Pro(ACT_GELU, mu0, rs0, P.M1g, P.M1b, p1_, sd[2]), x3=x3); s2 = ops.row_stats(z2)
+                z3 = ops.gemm(z2, P.M8w, NT, bias=P.M8b, pro=Pro(ACT_GELU, s2[0], s2[1], P.M5g, P.M5b, p2_, sd[3]), x3=x3)
+            fused_tail = ops.rowdot_act_ok(z3, P.M10w)
             assert fused_tail or live is None           # the count was chosen for the row-dot kernel: no fp32 GEMM under it
             if fused_tail:
-                logit = ops.rowdot_act(z3, M10w, M10b, ACT_GELU)          # one-output Linear: a row dot product, not a GEMM
+                logit = ops.rowdot_act(z3, P.M10w, P.M10b, ACT_GELU)          # one-output Linear: a row dot product, not a GEMM
             else:
-                logit = ops.gemm(z3, M10w, NT, bias=M10b, pro=Pro(ACT_GELU))
+                logit = ops.gemm(z3, P.M10w, NT, bias=P.M10b, pro=Pro(ACT_GELU))
             probs = ops.edge_prob_fwd(logit, meta)
         if pre is not None:
             Pa = Pb = None
         _keep_params(ctx, params)
-        ctx.cfg = (B, V, H, heads, (pf_, pa_, p1_, p2_), sd, meta)
+        ctx.cfg = (B, V, H, heads, meta)
         ctx.routes, ctx.wT, ctx.x3, ctx.products, ctx.fused_tail = routes, (M4t, M8t), x3, npr, fused_tail
         ctx.saved = (cv, za, sa, zb, sb, f, qkv, cx, lse, Fm, pre, mu0, rs0, delta, z2, s2, z3, h1, h2, Pa, Pb)
         ctx.save_for_backward(probs)
@@ -839,18 +812,17 @@ class EdgeFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dprobs):
         # autograd's own thread: the seed source is set again here (the _Leaves side stream runs inside it)
-        with seed_words(ctx.words):
-            return EdgeFn._backward(ctx, dprobs)
+        with _seeded(ctx.drop[2]):
+            return (*EdgeFn._backward(ctx, dprobs), *[None] * ctx.n_extra)
 
     @staticmethod
     def _backward(ctx, dprobs):
-        params = _params(ctx)
-        (P0w, P0b, P1g, P1b, P3w, P3b, P4g, P4b, Aw, Ab, Ow, Ob,
-         M0w, M0b, M1g, M1b, M4w, M4b, M5g, M5b, M8w, M8b, M10w, M10b) = params
-        B, V, H, heads, (pf_, pa_, p1_, p2_), sd, meta = ctx.cfg
+        P = EdgeParams(*_params(ctx))
+        B, V, H, heads, meta = ctx.cfg
+        (pf_, pa_, p1_, p2_), sd, _ = ctx.drop
         cv, za, sa, zb, sb, f, qkv, cx, lse, Fm, pre, mu0, rs0, delta, z2, s2, z3, h1, h2, Pa, Pb = _saved(ctx)
         (probs,) = ctx.saved_tensors
-        G = [None] * len(params)
+        G = EdgeGrads()
         x3, npr = ctx.x3, ctx.products
         # weight / bias gradients run beside the dgrad chain while the launches are small enough to share the chip
         # (cfg2, 64.5 k edge rows: +0.7 % on the step; cfg5, 1.04 M rows: -1.3 %, every kernel fills it alone)
@@ -859,19 +831,19 @@ class EdgeFn(torch.autograd.Function):
         # set again here; the _Leaves side stream runs inside the same thread)
         with ops.live_rows(ctx.live):
             dlogit = ops.edge_prob_bwd(probs, dprobs.contiguous(), meta)                      # [Re,1]
-            G[23] = ops.colsum(dlogit)
+            G.M10b = ops.colsum(dlogit)
             fused_tail = ctx.fused_tail
             if fused_tail:
                 dh3 = z3            # shape / dtype stand-in: the fused kernel below produces dz3 directly
-            elif M10w.shape[0] == 1:
+            elif P.M10w.shape[0] == 1:
                 # one-output Linear: dW[c] = sum_r dlogit[r]*gelu(z3[r,c]) is a weighted column sum,
                 # d gelu(z3) = dlogit (outer) W — no 128x128 MFMA tile wasted on a 1-wide problem
-                G[22] = ops.colsum(z3, dlogit.view(-1), ACT_GELU).view(1, -1)
-                dh3 = ops.gemm(dlogit, M10w, NN)
+                G.M10w = ops.colsum(z3, dlogit.view(-1), ACT_GELU).view(1, -1)
+                dh3 = ops.gemm(dlogit, P.M10w, NN)
             else:
-                G[22], dh3 = _lin_bwd(dlogit, z3, M10w, Pro(ACT_GELU))
-            p2 = Pro(ACT_GELU, s2[0], s2[1], M5g, M5b, p2_, sd[3])
-            p1 = Pro(ACT_GELU, mu0, rs0, M1g, M1b, p1_, sd[2])
+                G.M10w, dh3 = _lin_bwd(dlogit, z3, P.M10w, Pro(ACT_GELU))
+            p2 = Pro(ACT_GELU, s2[0], s2[1], P.M5g, P.M5b, p2_, sd[3])
+            p1 = Pro(ACT_GELU, mu0, rs0, P.M1g, P.M1b, p1_, sd[2])
             r2, r3 = ctx.routes
 
             def wgrad(r, dz, dz_s, h, pro, h_s):
@@ -880,29 +852,29 @@ class EdgeFn(torch.autograd.Function):
             dz3_s = torch.empty_like(dh3) if r3.dgrad == "split" else None            # dz3 has dh3's shape
             if fused_tail:
                 # logits-layer backward + GELU backward + both column sums in one pass over z3
-                dz3, G[22], G[21] = ops.rowdot_act_bwd(z3, dlogit, M10w, ACT_GELU, want_dz=_dz32(r3), dz_split=dz3_s)
+                dz3, G.M10w, G.M8b = ops.rowdot_act_bwd(z3, dlogit, P.M10w, ACT_GELU, want_dz=_dz32(r3), dz_split=dz3_s)
             else:
-                dz3, _, _, G[21] = ops.ln_act_bwd(dh3, z3, None, None, None, None, ACT_GELU, inplace=True,
+                dz3, _, _, G.M8b = ops.ln_act_bwd(dh3, z3, None, None, None, None, ACT_GELU, inplace=True,
                                                   dz_split=dz3_s, want_dz=_dz32(r3))
-            G[20] = wgrad(r3, dz3, dz3_s, z2, p2, h2)
-            dh2 = _dgrad(r3, dz3, dz3_s, M8w, ctx.wT[1], npr)
+            G.M8w = wgrad(r3, dz3, dz3_s, z2, p2, h2)
+            dh2 = _dgrad(r3, dz3, dz3_s, P.M8w, ctx.wT[1], npr)
             del dz3, dz3_s
             dz2_s = torch.empty_like(dh2) if r2.dgrad == "split" else None
-            dz2, G[18], G[19], G[17] = ops.ln_act_bwd(dh2, z2, s2[0], s2[1], M5g, M5b, ACT_GELU, p2_, sd[3],
+            dz2, G.M5g, G.M5b, G.M4b = ops.ln_act_bwd(dh2, z2, s2[0], s2[1], P.M5g, P.M5b, ACT_GELU, p2_, sd[3],
                                                       inplace=True, dz_split=dz2_s, want_dz=_dz32(r2))
-            G[16] = wgrad(r2, dz2, dz2_s, pre, p1, h1)
-            dh1 = _dgrad(r2, dz2, dz2_s, M4w, ctx.wT[0], npr)
+            G.M4w = wgrad(r2, dz2, dz2_s, pre, p1, h1)
+            dh1 = _dgrad(r2, dz2, dz2_s, P.M4w, ctx.wT[0], npr)
             del dz2, dz2_s
             # LN/GELU backward of the first edge layer; the same pass yields the gradient of its distance-weight column
             if pre is None:
-                dpre, G[14], G[15], wsum = ops.edge_pair_ln_bwd(dh1, Pa, Pb, delta, M0w, meta, mu0, rs0, M1g, M1b, ACT_GELU, p1_, sd[2])
+                dpre, G.M1g, G.M1b, wsum = ops.edge_pair_ln_bwd(dh1, Pa, Pb, delta, P.M0w, meta, mu0, rs0, P.M1g, P.M1b, ACT_GELU, p1_, sd[2])
             else:
-                dpre, G[14], G[15], wsum = ops.ln_act_bwd_wsum(dh1, pre, delta, mu0, rs0, M1g, M1b, ACT_GELU, p1_, sd[2], inplace=True)
+                dpre, G.M1g, G.M1b, wsum = ops.ln_act_bwd_wsum(dh1, pre, delta, mu0, rs0, P.M1g, P.M1b, ACT_GELU, p1_, sd[2], inplace=True)
             # split first layer backward
             vd = cv.shape[1]
-            dW0 = torch.empty_like(M0w)           # every column is written below: Wa | Wb | Wc | Wd | w_delta
+            dW0 = torch.empty_like(P.M0w)           # every column is written below: Wa | Wb | Wc | Wd | w_delta
             dW0[:, 2 * H + 2 * vd].copy_(wsum)
-            dPa, dPb, dcv = ops.edge_pair_bwd(dpre, delta, cv, M0w, meta, coord=True)     # dcv includes dPa·Wc + dPb·Wd
+            dPa, dPb, dcv = ops.edge_pair_bwd(dpre, delta, cv, P.M0w, meta, coord=True)     # dcv includes dPa·Wc + dPb·Wd
 
         def first_layer_leaves():
             ops.gemm(dPa, Fm, TN, out=dW0[:, :H], x3=x3)
@@ -910,30 +882,30 @@ class EdgeFn(torch.autograd.Function):
             ops.gemm(dPa, cv, TN, out=dW0[:, 2 * H:2 * H + vd])
             ops.gemm(dPb, cv, TN, out=dW0[:, 2 * H + vd:2 * H + 2 * vd])
             return ops.colsum(dPa)
-        G[13] = lv.run(first_layer_leaves, dPa, dPb, Fm, cv, dW0)
-        G[12] = dW0
-        Wa, Wb = M0w[:, :H], M0w[:, H:2 * H]
+        G.M0b = lv.run(first_layer_leaves, dPa, dPb, Fm, cv, dW0)
+        G.M0w = dW0
+        Wa, Wb = P.M0w[:, :H], P.M0w[:, H:2 * H]
         dF = ops.gemm(dPa, Wa, NN, x3=x3)
         ops.gemm(dPb, Wb, NN, out=dF, accumulate=True, x3=x3)
         # F = f + out_proj(ctx)
-        G[11], G[10] = lv.run(lambda: (ops.colsum(dF), ops.gemm(dF, cx, TN, x3=x3)), dF, cx)
-        dcx = ops.gemm(dF, Ow, NN, x3=x3)
+        G.Ob, G.Ow = lv.run(lambda: (ops.colsum(dF), ops.gemm(dF, cx, TN, x3=x3)), dF, cx)
+        dcx = ops.gemm(dF, P.Ow, NN, x3=x3)
         dqkv = ops.attn_bwd(qkv, dcx, cx, lse, meta, H, heads, pa_, sd[1])
-        G[9], G[8] = lv.run(lambda: (ops.colsum(dqkv), ops.gemm(dqkv, f, TN, x3=x3)), dqkv, f)
-        df = ops.gemm(dqkv, Aw, NN, addend=dF, x3=x3)
+        G.Ab, G.Aw = lv.run(lambda: (ops.colsum(dqkv), ops.gemm(dqkv, f, TN, x3=x3)), dqkv, f)
+        df = ops.gemm(dqkv, P.Aw, NN, addend=dF, x3=x3)
         # f = drop(LN(zb))
-        dzb, G[6], G[7], G[5] = ops.ln_act_bwd(df, zb, sb[0], sb[1], P4g, P4b, ACT_NONE, pf_, sd[0], inplace=True)
-        pa = Pro(ACT_GELU, sa[0], sa[1], P1g, P1b)
-        G[4] = lv.run(lambda: ops.gemm(dzb, za, TN, pro=pa, x3=x3), dzb, za)
-        dha = ops.gemm(dzb, P3w, NN, x3=x3)
-        dza, G[2], G[3], G[1] = ops.ln_act_bwd(dha, za, sa[0], sa[1], P1g, P1b, ACT_GELU, inplace=True)
-        G[0] = lv.run(lambda: ops.gemm(dza, cv, TN), dza, cv)
-        ops.gemm(dza, P0w, NN, out=dcv, accumulate=True)
-        lv.join(G[20], G[16], G[13], dW0, G[11], G[10], G[9], G[8], G[4], G[0])
+        dzb, G.P4g, G.P4b, G.P3b = ops.ln_act_bwd(df, zb, sb[0], sb[1], P.P4g, P.P4b, ACT_NONE, pf_, sd[0], inplace=True)
+        pa = Pro(ACT_GELU, sa[0], sa[1], P.P1g, P.P1b)
+        G.P3w = lv.run(lambda: ops.gemm(dzb, za, TN, pro=pa, x3=x3), dzb, za)
+        dha = ops.gemm(dzb, P.P3w, NN, x3=x3)
+        dza, G.P1g, G.P1b, G.P0b = ops.ln_act_bwd(dha, za, sa[0], sa[1], P.P1g, P.P1b, ACT_GELU, inplace=True)
+        G.P0w = lv.run(lambda: ops.gemm(dza, cv, TN), dza, cv)
+        ops.gemm(dza, P.P0w, NN, out=dcv, accumulate=True)
+        lv.join(G.M8w, G.M4w, G.M0b, dW0, G.Ob, G.Ow, G.Ab, G.Aw, G.P3w, G.P0w)
         dverts = ops.edge_scatter_dverts(dcv, meta, B, V)
         if not config.RETAIN_SAVED:
             ctx.saved = None
-        return (dverts, None, None, None, None, None, *G)
+        return (dverts, None, None, None, *G.out())
 
 
 class _FrozenList(list):

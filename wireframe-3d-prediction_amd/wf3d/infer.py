@@ -19,7 +19,7 @@ WF3D_EDGE_INFERENCE=stream, and EdgePredictor.forward_stream calls it directly."
 import torch
 
 from . import config, ops
-from .functional import _SPLIT_PRODUCTS, _edge_live_fwd, _edge_routes, _edge_vertex_section, _encoder_routes
+from .functional import _SPLIT_PRODUCTS, _edge_live_fwd, _edge_routes, _edge_vertex_section, _encoder_routes, mlp_layers
 from .ops import ACT_GELU, ACT_RELU, NT, Pro
 
 
@@ -67,7 +67,8 @@ def encoder_stream(x2, pools_layout, n_hidden, precision, params, rows=None, wan
     if not 0 <= walk <= M:
         raise ValueError(f"wf3d.infer.encoder_stream: walk must be 0 .. {M} (got {walk})")
     plan = block_plan(walk, rows)
-    Ws = [params[4 * i] for i in range(n_hidden + 1)]
+    layers = mlp_layers(params, n_hidden)
+    Ws = [L.W for L in layers]
     # decided once, from the row total, as the training forward decides them: a short last block flips no layer
     routes = _encoder_routes(x2[:walk], Ws, precision in _SPLIT_PRODUCTS, want_dx=False)
     npr = _SPLIT_PRODUCTS.get(precision, 3)
@@ -97,11 +98,10 @@ def encoder_stream(x2, pools_layout, n_hidden, precision, params, rows=None, wan
             mu, rs = rowbuf[0, :n], rowbuf[1, :n]
             valid = ops.point_valid(xb, out=rowbuf[2, :n])
             a, a_s, pro = xb, None, None
-            for i, r in enumerate(routes):
-                W, b = Ws[i], params[4 * i + 1]
+            for i, (r, (W, b, g, be)) in enumerate(zip(routes, layers)):
                 D = W.shape[0]
                 if r.fwd == "first":
-                    a_s = ops.first_layer_infer(xb, W, b, params[2], params[3], ACT_RELU, out=hb[:n * D].view(n, D))
+                    a_s = ops.first_layer_infer(xb, W, b, g, be, ACT_RELU, out=hb[:n * D].view(n, D))
                     a, pro = None, None
                     continue
                 out = pf[r0:r0 + n] if (i == n_hidden and want_pf) else zb[i % 2][:n * D].view(n, D)
@@ -111,7 +111,6 @@ def encoder_stream(x2, pools_layout, n_hidden, precision, params, rows=None, wan
                     z = ops.gemm(a, W, NT, bias=b, pro=pro, out=out)
                 if i == n_hidden:
                     break
-                g, be = params[4 * i + 2], params[4 * i + 3]
                 if routes[i + 1].fwd == "split":
                     a_s = hb[:n * D].view(n, D)
                     ops.ln_prep(z, g, be, ACT_RELU, out=(mu, rs, a_s))
@@ -123,13 +122,14 @@ def encoder_stream(x2, pools_layout, n_hidden, precision, params, rows=None, wan
         return pool.finish(), pf
 
 
-def edge_stream(verts, meta, heads, precision, params, rows=None):
+def edge_stream(verts, meta, heads, precision, P, rows=None):
     """The forward-only edge head: EdgeFn's forward without dropout, with the edge rows walked in blocks of `rows`
     (default config.INFER_EDGE_ROWS) through buffers that are allocated once, sized by the block height, and reused.
     Nothing per edge row outlives its block except its logit (4 B per row).
 
-    verts [B, V, vertex_dim] float32 (a view is fine); meta: an ops.EdgeMeta, host-built or EdgeMeta.device; params as
-    EdgeFn's.  Returns edge_probs [B, meta.max_e], zero padding included, as EdgeFn returns it: bit for bit when one
+    verts [B, V, vertex_dim] float32 (a view is fine); meta: an ops.EdgeMeta, host-built or EdgeMeta.device; P: the
+    head's functional.EdgeParams block.
+    Returns edge_probs [B, meta.max_e], zero padding included, as EdgeFn returns it: bit for bit when one
     block covers all rows (rows >= meta.Re), within the forward bound at other heights (the GEMMs' split-K plans follow
     the block's row count).
 
@@ -142,18 +142,17 @@ def edge_stream(verts, meta, heads, precision, params, rows=None):
     if not verts.is_cuda:
         raise RuntimeError("wf3d: the HIP path needs CUDA (ROCm) tensors; there is no CPU fallback")
     rows = check_rows(config.INFER_EDGE_ROWS if rows is None else rows)
-    M0w, _M0b, M1g, M1b, M4w, M4b, M5g, M5b, M8w, M8b, M10w, M10b = params[12:]
-    H, dev = M0w.shape[0], verts.device
+    H, dev = P.M0w.shape[0], verts.device
     with torch.no_grad():
         # ---- per-vertex section: EdgeFn's, drop p = 0 ----
         x3 = precision == "bf16x3" and config.EDGE_X3
-        cv, *_, Pa, Pb = _edge_vertex_section(verts, meta, heads, x3, params)
+        cv, *_, Pa, Pb = _edge_vertex_section(verts, meta, heads, x3, P)
         del _
         # ---- edge-row section: decided once, from the row total; a short last block flips nothing ----
         npr = _SPLIT_PRODUCTS.get(precision, 3)
         routes = _edge_routes(meta.Re, H, precision, x3)
         split = routes[0].fwd == "split"
-        rowdot = M10w.shape[0] == 1 and M10w.is_contiguous() and ops.rowdot_act_shape_ok(H // 4)
+        rowdot = P.M10w.shape[0] == 1 and P.M10w.is_contiguous() and ops.rowdot_act_shape_ok(H // 4)
         # every launch of the loop below then honours the count; on any other route the tail is computed, as EdgeFn does
         live = _edge_live_fwd(meta, routes, rowdot)
         plan = block_plan(meta.Re, rows)
@@ -163,28 +162,28 @@ def edge_stream(verts, meta, heads, precision, params, rows=None):
         z2, z3 = torch.empty(R, H // 2, **f32), torch.empty(R, H // 4, **f32)
         if split:
             h1, h2 = torch.empty(R, H, **f32), torch.empty(R, H // 2, **f32)
-            (M4s, _), (M8s, _) = ops.split_weights([M4w, M8w])
+            (M4s, _), (M8s, _) = ops.split_weights([P.M4w, P.M8w])
         else:
             pre = torch.empty(R, H, **f32)
         rowbuf = torch.empty(2, max(R, 1), **f32)            # mu / rs of the layer at hand (launches run in stream order)
-        fused_tail = ops.rowdot_act_ok(z3, M10w)
+        fused_tail = ops.rowdot_act_ok(z3, P.M10w)
         assert fused_tail or live is None
         blive = ops.block_live(live, rows, meta.Re, len(plan)) if live is not None else None
         for k, (e0, n) in enumerate(plan):
             mu, rs = rowbuf[0, :n], rowbuf[1, :n]
             with ops.live_rows(blive[k:k + 1] if blive is not None else None):
                 if split:
-                    ops.edge_pair_infer(Pa, Pb, cv, M0w, meta, e0, n, h1[:n], ln=(M1g, M1b, ACT_GELU))
-                    ops.gemm_split(h1[:n], M4s, bias=M4b, out=z2[:n], products=npr)
-                    ops.ln_prep(z2[:n], M5g, M5b, ACT_GELU, out=(mu, rs, h2[:n]))
-                    ops.gemm_split(h2[:n], M8s, bias=M8b, out=z3[:n], products=npr)
+                    ops.edge_pair_infer(Pa, Pb, cv, P.M0w, meta, e0, n, h1[:n], ln=(P.M1g, P.M1b, ACT_GELU))
+                    ops.gemm_split(h1[:n], M4s, bias=P.M4b, out=z2[:n], products=npr)
+                    ops.ln_prep(z2[:n], P.M5g, P.M5b, ACT_GELU, out=(mu, rs, h2[:n]))
+                    ops.gemm_split(h2[:n], M8s, bias=P.M8b, out=z3[:n], products=npr)
                 else:
-                    ops.edge_pair_infer(Pa, Pb, cv, M0w, meta, e0, n, (pre[:n], mu, rs))
-                    ops.gemm(pre[:n], M4w, NT, bias=M4b, pro=Pro(ACT_GELU, mu, rs, M1g, M1b), x3=x3, out=z2[:n])
+                    ops.edge_pair_infer(Pa, Pb, cv, P.M0w, meta, e0, n, (pre[:n], mu, rs))
+                    ops.gemm(pre[:n], P.M4w, NT, bias=P.M4b, pro=Pro(ACT_GELU, mu, rs, P.M1g, P.M1b), x3=x3, out=z2[:n])
                     ops.row_stats(z2[:n], out=(mu, rs))
-                    ops.gemm(z2[:n], M8w, NT, bias=M8b, pro=Pro(ACT_GELU, mu, rs, M5g, M5b), x3=x3, out=z3[:n])
+                    ops.gemm(z2[:n], P.M8w, NT, bias=P.M8b, pro=Pro(ACT_GELU, mu, rs, P.M5g, P.M5b), x3=x3, out=z3[:n])
                 if fused_tail:
-                    ops.rowdot_act(z3[:n], M10w, M10b, ACT_GELU, out=logit[e0:e0 + n])
+                    ops.rowdot_act(z3[:n], P.M10w, P.M10b, ACT_GELU, out=logit[e0:e0 + n])
                 else:
-                    ops.gemm(z3[:n], M10w, NT, bias=M10b, pro=Pro(ACT_GELU), out=logit[e0:e0 + n])
+                    ops.gemm(z3[:n], P.M10w, NT, bias=P.M10b, pro=Pro(ACT_GELU), out=logit[e0:e0 + n])
         return ops.edge_prob_fwd(logit, meta)
