@@ -1,7 +1,7 @@
 """Per-kernel parity of the HIP ops (through the C ABI) against plain PyTorch
 references of the same op.  fp32 tolerance: 1e-4 relative to the tensor's
 scale for anything that went through a GEMM (BASELINE.json north_star), 2e-5
-for elementwise / reduction kernels."""
+for elementwise / reduction kernels.  The per-element and per-route checks of wf3d_gemm live in test_gemm_forms_gpu.py."""
 import math
 
 import pytest
