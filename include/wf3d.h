@@ -737,7 +737,8 @@ int wf3d_cloud_sample(const double* norm, const long* first, const int* cloud, c
  *     int    cloud[B]          the resident cloud of sample b, 0 .. nclouds-1                  at byte 32 * B
  *     int    out_first[B + 1]  sample b's first output row; out_first[0] = 0,                  at byte 36 * B
  *                              out_first[b+1] - out_first[b] = first[cloud[b]+1] - first[cloud[b]], out_first[B] <= capacity
- * The host fills it (numpy draws in the reference's order) and copies it up; the launches take only its address, so a
+ * The host fills it (numpy draws in the reference's order) and copies it up, or wf3d_cloud_epoch_params (below) writes it
+ * on the device; the launches take only its address, so a
  * captured graph replays them on whatever block is there.  1 <= B <= 4096.
  * wf3d_cloud_pack: points [capacity, C] fp32 — cloud[b]'s rows in file order at rows out_first[b] .. out_first[b+1]-1, each
  *   with the flips and the z-rotation of wf3d_cloud_sample (float64, one rounding), rows out_first[B] .. capacity-1 exact
@@ -767,6 +768,28 @@ int wf3d_cloud_sample_dev(const double* norm, const long* first, int nclouds, co
 int wf3d_wireframe_targets(const double* wf_vertices, const int32_t* wf_edges, const long* vfirst, const long* efirst, int nclouds,
                            const void* params, int B, int V, float* vertices, float* vertex_existence, int64_t* vertex_counts,
                            float* edge_labels, void* stream);
+/* RESIDENT EPOCHS: the parameter block above and the seed words of wf3d_cloud_sample_dev, written ON THE DEVICE from
+ * state = {uint64 key, uint64 t} (device memory, 8-byte aligned; t = the batches produced so far), so that a captured
+ * graph of this launch and the launches above walks shuffled, rank-sharded, augmented epochs with no host work between
+ * replays.  wf3d.sampling.epoch_batch is the specification, bit for bit.  With mix64(key, n) = wf3d_dropout_draw's
+ * splitmix64 step, S = D / (world * B) steps per epoch (the last partial batch is dropped), e = t / S, s = t % S and
+ * g = s * world * B + rank * B + b the global slot of sample b:
+ *     cloud[b]  = members[order_e[g]], order_e = wf3d.sampling.choice_indices(low32(mix64(key, e)), 0, D, D): a permutation
+ *                 of 0 .. D-1 per epoch; members = int32 [D] resident cloud indices (device memory)
+ *     aug[b]    = {1, 1, 1, 0} without `augment`, else with c = e * 2^32 + g: flip_x = -1 iff bit 63 of
+ *                 za = mix64(key ^ 0x6A09E667F3BCC908, c), flip_y the same on bit 62, and cos / sin of
+ *                 t_rot = u * (pi / 18) - pi / 36, u = (mix64(key ^ 0xBB67AE8584CAA73B, c) >> 11) * 2^-53, as the fixed
+ *                 polynomials of wf3d.sampling.epoch_cos_sin, every operation rounded on its own (no fma)
+ *     out_first = b * P for the fixed-size form (P >= 1); P = 0, the packed form: the exclusive prefix sum of the rows of
+ *                 cloud[0 .. B-1] (a cloud index outside 0 .. nclouds-1 counts no rows)
+ *     seed_words[k] = low32(mix64(key ^ 0x3C6EF372FE94F82B, t * world + rank)) + k * 0x9E3779B9, k = 0 .. 4
+ * then t += 1.  Slots and augmentation depend on (e, g) only: the ranks' batches of a step are disjoint and their union
+ * is the batch of one rank with batch world * B; the seed words are per (step, rank).  One workgroup: every thread
+ * reads the state, a barrier, one thread stores t + 1; every byte of the block and of the five words is written by plain
+ * stores.  1 <= D < 2^31, 1 <= B <= 4096 (WF3D_ERR_UNSUPPORTED above), 0 <= rank < world, world * B <= D, B * P < 2^31.
+ * The caller sees to it that no batch of `members` breaks the rules of the launches behind it (row capacity, V). */
+int wf3d_cloud_epoch_params(uint64_t* state, const int32_t* members, int D, const long* first, int nclouds, int B, int world,
+                            int rank, int P, int augment, void* params, uint32_t* seed_words, void* stream);
 /* HOST function: the numbers of a whitespace-separated text file (.xyz: 8 per row; np.loadtxt, :98) into out[0..max_vals);
  * returns the count in the file (call again with a larger buffer if > max_vals), -1 unreadable, -2 not a number: a token
  * is every character up to whitespace, `#` or the end, and the whole of it must be one decimal number, inf or nan, as

@@ -28,6 +28,15 @@ collate_batch (wireframe lists), which "sampled" replaces by device targets: the
 
     python scripts/bench_resident_batches.py --form fixed --batch-sizes 32 --num-points 4096 --out profiles/r10_sampled_batches.jsonl
 
+--form epoch: the same fixed-size batches with NOTHING made on the host ("One capture for a data set,
+nothing between replays").  Arm "sampled" as above (`cache.stage` + one replay of a graph around `cache.fill`); arm
+"epoch": one replay of a graph captured around `cache.fill_epoch` (epoch parameters, sampler, targets) under an
+EpochSampler over the same clouds cycled to 4 B members — no draw, no mirror, no copy.  Host wall time per batch of
+both, ended by a synchronize, in one alternation; then the device time of each replayed graph (three launches each)
+between events over --reps back-to-back replays.
+
+    python scripts/bench_resident_batches.py --form epoch --batch-sizes 32 --num-points 4096 --out profiles/r18_epoch_batches.jsonl
+
 Prints one JSON line per batch size and appends them to --out.
 """
 import argparse
@@ -214,13 +223,77 @@ def run_fixed(B, ds, cache, dev, args):
             "sampler_GB/s": round(nbytes / dev_us["sampler"]["median"] / 1e3, 1)}
 
 
+def run_epoch(B, ds, cache, dev, args):
+    """--form epoch: the stage-plus-replay arm of --form fixed beside one replay of a graph captured around
+    cache.fill_epoch with NOTHING else per batch, in one session and one alternation"""
+    P = args.num_points
+    ds.num_points = P
+    idxs = [i % len(ds) for i in range(B)]
+    members = [i % len(ds) for i in range(4 * B)]                  # four steps per epoch over the same clouds
+    sampler = cache.epoch_sampler(B, members, seed=0)
+    graphs, bufs = {}, {}
+    np.random.seed(0)
+    for name in ("sampled", "epoch"):
+        buf = bufs[name] = cache.sampled_buffers(B, V, P)
+        fill = (lambda b=buf: cache.fill(b)) if name == "sampled" else (lambda b=buf: cache.fill_epoch(b, sampler))
+        if name == "sampled":
+            cache.stage(buf, idxs)
+        fill()
+        torch.cuda.synchronize()
+        graphs[name] = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(graphs[name]):
+            fill()
+
+    def sampled():
+        t0 = time.perf_counter()
+        cache.stage(bufs["sampled"], idxs)
+        graphs["sampled"].replay()
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) * 1e3
+
+    def epoch():
+        t0 = time.perf_counter()
+        graphs["epoch"].replay()
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) * 1e3
+
+    t_before = int(sampler.get_state()[1])
+    med = blocks_of({"sampled": sampled, "epoch": epoch}, args.blocks, args.block_steps, args.warmup)
+    batches = int(sampler.get_state()[1]) - t_before
+    ev = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+
+    def timed(launch):
+        def fn():
+            ev[0].record()
+            for _ in range(args.reps):
+                launch()
+            ev[1].record()
+            torch.cuda.synchronize()
+            return ev[0].elapsed_time(ev[1]) * 1e3 / args.reps
+        return fn
+
+    dmed = blocks_of({"fill_graph": timed(graphs["sampled"].replay), "fill_epoch_graph": timed(graphs["epoch"].replay)},
+                     args.blocks, args.block_steps, args.warmup)
+    # the walk went where the specification says
+    t = int(sampler.get_state()[1])
+    cloud = cache._block_views(bufs["epoch"]["params"].cpu(), B)[1]
+    s, e = summary(med["sampled"]), summary(med["epoch"])
+    return {"bench": "epoch_batches", "B": B, "num_points": P, "columns": cache.ncol, "max_vertices": V, "members": len(members),
+            "steps_per_epoch": sampler.steps_per_epoch, "blocks": args.blocks, "steps_per_block": args.block_steps, "reps": args.reps,
+            "stage_replay_ms": s, "epoch_replay_ms": e, "stage_replay_over_epoch": round(s["median"] / e["median"], 2),
+            "h2d_bytes_stage": 40 * B + 4, "h2d_bytes_epoch": 0, "host_draws_epoch": 0,
+            "batches_walked": batches == args.blocks * args.block_steps + args.warmup,
+            "last_batch_is_specified": cloud.tolist() == sampler.batch_at(t - 1)["cloud"].tolist(),
+            "device_us": {k: summary(v, 2) for k, v in dmed.items()}}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--blocks", type=int, default=5)
     ap.add_argument("--block-steps", type=int, default=7)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--batch-sizes", default="3,32")
-    ap.add_argument("--form", choices=("packed", "fixed"), default="packed")
+    ap.add_argument("--form", choices=("packed", "fixed", "epoch"), default="packed")
     ap.add_argument("--num-points", type=int, default=4096)
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "r06_resident_batches.jsonl"))
@@ -229,7 +302,7 @@ def main():
     ds = fixture_dataset()
     cache = DeviceCloudCache(ds, dev)
     for B in (int(b) for b in args.batch_sizes.split(",")):
-        r = (run_fixed if args.form == "fixed" else run)(B, ds, cache, dev, args)
+        r = {"fixed": run_fixed, "epoch": run_epoch, "packed": run}[args.form](B, ds, cache, dev, args)
         print(json.dumps(r), flush=True)
         if args.out:
             with open(args.out, "a") as f:

@@ -20,6 +20,9 @@
 //   cloud_sample_dev kernels per fixed-size batch: cloud_sample_kernel's output with the random choice computed in the
 //                            kernel (wf3d/sampling.py) from a seed word in device memory and the same parameter block:
 //                            no per-point host data, capturable.
+//   cloud_epoch_params_kernel per batch of a resident epoch: WRITES that parameter block and the seed words — which clouds
+//                            (a keyed permutation per epoch, sharded over ranks), their augmentation, the row offsets —
+//                            from a 16-byte state in device memory, so nothing of a batch is made on the host.
 // Plus the host-side text parser for .xyz files (np.loadtxt replacement): wf3d_parse_floats.
 #include <locale.h>
 #include <stdio.h>
@@ -197,6 +200,18 @@ __device__ __forceinline__ uint32_t fmix32(uint32_t x) {
 // what is the same for every row of sample b: block-uniform, so the compiler keeps it in scalar registers
 struct SamplePlan { long r0; uint32_t n, key, key2, a, c, mask; int h; bool replace; };
 
+// the keys of sample b of a batch over n rows under one seed word (1 <= n < 2^31)
+__device__ __forceinline__ void plan_keys(SamplePlan& s, uint32_t seed_word, int b, uint32_t n, bool replace) {
+    s.n = n;
+    s.key = fmix32(fmix32(seed_word + 0x9E3779B9u) ^ ((uint32_t)(b + 1) * 0x85EBCA6Bu));
+    s.key2 = fmix32(s.key ^ 0x68E31DA4u);
+    s.a = __umulhi(fmix32(s.key ^ 0xB5297A4Du), s.n);
+    s.c = __umulhi(fmix32(s.key ^ 0x1B56C4E9u), s.n);
+    s.h = (32 - __clz((int)(s.n - 1)) + 1) >> 1;                 // n = 1: h = 0, the permutation of one value
+    s.mask = (1u << s.h) - 1u;
+    s.replace = replace;
+}
+
 // false: the sample has no source (cloud index outside the resident clouds, an empty cloud) and is written as zeros
 __device__ __forceinline__ bool sample_plan(const BatchParams& Q, const long* __restrict__ first, int nclouds,
                                             const uint32_t* __restrict__ seed_words, int b, int P, SamplePlan& s) {
@@ -205,14 +220,7 @@ __device__ __forceinline__ bool sample_plan(const BatchParams& Q, const long* __
     s.r0 = first[cl];
     const long n = first[cl + 1] - s.r0;
     if (n < 1 || n > 0x7FFFFFFFL) return false;
-    s.n = (uint32_t)n;
-    s.key = fmix32(fmix32(seed_words[0] + 0x9E3779B9u) ^ ((uint32_t)(b + 1) * 0x85EBCA6Bu));
-    s.key2 = fmix32(s.key ^ 0x68E31DA4u);
-    s.a = __umulhi(fmix32(s.key ^ 0xB5297A4Du), s.n);
-    s.c = __umulhi(fmix32(s.key ^ 0x1B56C4E9u), s.n);
-    s.h = (32 - __clz((int)(s.n - 1)) + 1) >> 1;                 // n = 1: h = 0, the permutation of one value
-    s.mask = (1u << s.h) - 1u;
-    s.replace = n < P;
+    plan_keys(s, seed_words[0], b, (uint32_t)n, n < P);
     return true;
 }
 
@@ -296,6 +304,107 @@ __global__ __launch_bounds__(256) void cloud_sample_dev_kernel(const double* __r
     o[0] = (float)(x * c - y * sn);
     o[1] = (float)(x * sn + y * c);
     for (int k = 2; k < C; ++k) o[k] = (float)row[k];
+}
+
+// ---- epochs drawn on the device ---------------------------------------------------------------------------------------
+// wf3d/sampling.py epoch_batch, the specification: the parameter block and the seed words of batch number t of a
+// shuffled, rank-sharded, augmented walk over `members`, from state = {key, t} in device memory.  One workgroup; thread
+// i owns the slots [i * K, (i + 1) * K), K = ceil(B / 256) <= 16, so the packed form's row offsets are one scan over 256
+// partial sums.
+__device__ __forceinline__ uint64_t mix64(uint64_t key, uint64_t n) {           // csrc/random.hip's splitmix64 step
+    uint64_t z = key + (n + 1) * 0x9E3779B97F4A7C15ull;
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    return z ^ (z >> 31);
+}
+
+// cos and sin of |t| <= pi / 36 as the specification's fixed polynomials: every operation rounded on its own (no fma),
+// so that numpy gives the same bits
+__device__ __forceinline__ void epoch_cos_sin(double t, double& c, double& s) {
+#pragma clang fp contract(off)
+    const double x = t * t;
+    double ps = 1.0, pc = 1.0;
+#pragma unroll
+    for (int k = 13; k >= 3; k -= 2) {
+        ps = 1.0 - x * ps / (double)(k * (k - 1));
+        pc = 1.0 - x * pc / (double)((k - 1) * (k - 2));
+    }
+    c = pc;
+    s = t * ps;
+}
+
+__device__ __forceinline__ uint32_t cloud_rows(const long* __restrict__ first, int nclouds, int cl) {
+    return cl >= 0 && cl < nclouds ? (uint32_t)(first[cl + 1] - first[cl]) : 0u;
+}
+
+__global__ __launch_bounds__(256) void cloud_epoch_params_kernel(uint64_t* state, const int32_t* __restrict__ members, int D,
+                                                                  const long* __restrict__ first, int nclouds, int B, int world,
+                                                                  int rank, int P, int augment, double span, double half_span,
+                                                                  void* params, uint32_t* __restrict__ seed_words) {
+    __shared__ uint32_t part[256];
+    const int tid = threadIdx.x;
+    const uint64_t key = state[0], t = state[1];
+    __syncthreads();                                             // every read of the counter comes before its store
+    if (tid == 0) {
+        state[1] = t + 1;
+        const uint32_t s = (uint32_t)mix64(key ^ 0x3C6EF372FE94F82Bull, t * (uint64_t)world + (uint64_t)rank);
+#pragma unroll
+        for (int k = 0; k < 5; ++k) seed_words[k] = s + 0x9E3779B9u * (uint32_t)k;       // wf3d_dropout_draw's five words
+    }
+    const uint32_t WB = (uint32_t)world * (uint32_t)B;
+    const uint64_t S = (uint64_t)((uint32_t)D / WB);             // the host refuses world * B > D: S >= 1
+    const uint64_t e = t / S;
+    const uint32_t g0 = (uint32_t)(t % S) * WB + (uint32_t)rank * (uint32_t)B;          // g0 + B <= S * WB <= D
+    SamplePlan plan;
+    plan.r0 = 0;
+    plan_keys(plan, (uint32_t)mix64(key, e), 0, (uint32_t)D, false);                   // choice_indices(word, 0, D, D)
+    double* aug = (double*)params;
+    int* cloud = (int*)((char*)params + (size_t)B * 32);
+    int* out_first = (int*)((char*)params + (size_t)B * 36);
+    const int K = (B + 255) >> 8, b0 = min(tid * K, B), b1 = min(b0 + K, B);
+    uint32_t rows = 0;
+    for (int b = b0; b < b1; ++b) {
+        const uint32_t g = g0 + (uint32_t)b;
+        const int cl = members[sample_index(plan, g)];
+        cloud[b] = cl;
+        if (P == 0) rows += cloud_rows(first, nclouds, cl);
+        double fx = 1.0, fy = 1.0, c = 1.0, s = 0.0;
+        if (augment) {
+            const uint64_t ctr = (e << 32) + (uint64_t)g;
+            const uint64_t za = mix64(key ^ 0x6A09E667F3BCC908ull, ctr), zb = mix64(key ^ 0xBB67AE8584CAA73Bull, ctr);
+            fx = (za >> 63) & 1 ? -1.0 : 1.0;
+            fy = (za >> 62) & 1 ? -1.0 : 1.0;
+            const double u = (double)(zb >> 11) * 0x1p-53;       // exact: 53 bits, a power of two
+            double rot;
+            {
+#pragma clang fp contract(off)
+                rot = u * span - half_span;
+            }
+            epoch_cos_sin(rot, c, s);
+        }
+        aug[b * 4] = fx; aug[b * 4 + 1] = fy; aug[b * 4 + 2] = c; aug[b * 4 + 3] = s;
+        if (P > 0) out_first[b] = b * P;
+    }
+    if (P > 0) {
+        if (tid == 0) out_first[B] = B * P;
+        return;
+    }
+    // the packed form: out_first = the exclusive prefix sum of the clouds' row counts (uint32 arithmetic; the host has
+    // checked that no batch of these members passes the buffers' capacity)
+    part[tid] = rows;
+    __syncthreads();
+    for (int o = 1; o < 256; o <<= 1) {
+        const uint32_t v = tid >= o ? part[tid - o] : 0u;
+        __syncthreads();
+        part[tid] += v;
+        __syncthreads();
+    }
+    uint32_t at = part[tid] - rows;
+    for (int b = b0; b < b1; ++b) {
+        out_first[b] = (int)at;
+        at += cloud_rows(first, nclouds, cloud[b]);              // this thread's own store
+    }
+    if (tid == 255) out_first[B] = (int)part[255];
 }
 
 // wf3d/targets.py train_targets(..., full_width=True) for sample b = blockIdx.x: c_s vertices augmented like the points,
@@ -397,6 +506,23 @@ extern "C" int wf3d_cloud_sample_dev(const double* norm, const long* first, int 
         hipLaunchKernelGGL(cloud_sample_dev_kernel, grid, dim3(256), 0, (hipStream_t)stream, norm, first, nclouds, params,
                            seed_words, B, P, C, points);
     }
+    WF3D_LAUNCH_CHECK();
+    return WF3D_OK;
+}
+
+extern "C" int wf3d_cloud_epoch_params(uint64_t* state, const int32_t* members, int D, const long* first, int nclouds, int B,
+                                       int world, int rank, int P, int augment, void* params, uint32_t* seed_words, void* stream) {
+    WF3D_CHECK(D >= 1 && nclouds >= 1 && B >= 1 && world >= 1 && rank >= 0 && rank < world && P >= 0 && (augment == 0 || augment == 1),
+               WF3D_ERR_ARG, "wf3d_cloud_epoch_params: bad dims");
+    WF3D_CHECK(B <= 4096, WF3D_ERR_UNSUPPORTED, "wf3d_cloud_epoch_params: B > 4096");
+    WF3D_CHECK((long)world * B <= D, WF3D_ERR_ARG, "wf3d_cloud_epoch_params: world * B must not pass D (no whole step in an epoch)");
+    WF3D_CHECK((long)B * P <= 0x7FFFFFFFL, WF3D_ERR_ARG, "wf3d_cloud_epoch_params: B * P must stay below 2^31");
+    WF3D_CHECK(state && members && first && params && seed_words, WF3D_ERR_ARG, "wf3d_cloud_epoch_params: null pointer");
+    WF3D_CHECK((((uintptr_t)state | (uintptr_t)params) & 7) == 0 && (((uintptr_t)seed_words | (uintptr_t)members) & 3) == 0, WF3D_ERR_ARG,
+               "wf3d_cloud_epoch_params: state and params must be 8-byte aligned, members and seed_words 4-byte aligned");
+    const double pi = 3.141592653589793;                         // the double numpy calls pi; both quotients rounded once
+    hipLaunchKernelGGL(cloud_epoch_params_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, state, members, D, first, nclouds, B,
+                       world, rank, P, augment, pi / 18.0, pi / 36.0, params, seed_words);
     WF3D_LAUNCH_CHECK();
     return WF3D_OK;
 }

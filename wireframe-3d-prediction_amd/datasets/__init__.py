@@ -1,5 +1,5 @@
 """Drop-in `datasets` package (reference datasets/__init__.py:12-18): build_dataset(cfg) -> {"train", "test"}."""
-from .building3d import Building3DReconstructionDataset, DeviceCloudCache  # noqa: F401
+from .building3d import Building3DReconstructionDataset, DeviceCloudCache, EpochSampler  # noqa: F401
 
 
 def build_dataset(dataset_config):

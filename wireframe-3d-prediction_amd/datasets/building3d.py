@@ -19,7 +19,11 @@ training targets) that read everything else from resident device memory.  `packe
 The fixed-size form without per-point host data: `cache.sampled_buffers` / `stage` / `fill` do the same for
 `[B, num_points, C]` batches whose rows are chosen IN the kernel (wf3d/sampling.py states the index function) under a seed
 word that `fill` draws on the device, so one captured step trains as the reference trains — random fixed-size subsets,
-flips, z-rotation; `cache.batch(indices, sampler="device")` is the same sampler for one batch."""
+flips, z-rotation; `cache.batch(indices, sampler="device")` is the same sampler for one batch.
+
+Resident epochs: `cache.epoch_sampler` / `fill_epoch` replace `stage` by a kernel — which clouds a batch holds (a keyed
+permutation per epoch, sharded over ranks), the augmentation and the seed words come from a 16-byte state in device memory
+(wf3d/sampling.py `epoch_batch` states them), so a loop of graph replays with nothing between them walks the data set."""
 import ctypes
 import glob
 import operator
@@ -537,3 +541,153 @@ class DeviceCloudCache:
             self.wf_vertices.data_ptr(), self.wf_edges.data_ptr(), self.vfirst.data_ptr(), self.efirst.data_ptr(), len(self.n),
             buffers["params"].data_ptr(), B, V, buffers["vertices"].data_ptr(), buffers["vertex_existence"].data_ptr(),
             buffers["vertex_counts"].data_ptr(), buffers["edge_labels"].data_ptr(), _stream()), "wireframe_targets")
+
+    # ---- resident epochs: the batch order, the rank shards and the augmentation drawn on the device ---------------------
+    def epoch_sampler(self, B, members=None, world=1, rank=0, seed=None):
+        """An EpochSampler over `members` (resident cloud indices; all clouds by default, so one cache can hold several
+        splits) for batches of B clouds per rank.  seed=None keys it from torch's CPU generator, at world == 1 only: the
+        ranks of a data-parallel run must share one key, so world > 1 needs an explicit integer `seed`.  Create it
+        before a capture starts."""
+        return EpochSampler(self, B, members, world, rank, seed)
+
+    def _check_epoch(self, buffers, sampler):
+        """what stage() checks per batch, once for every batch the sampler can produce"""
+        sampled = "sample_words" in buffers
+        B, V = buffers["vertices"].shape[0], buffers["vertices"].shape[1]
+        if sampler.cache is not self:
+            raise ValueError("DeviceCloudCache.fill_epoch: the sampler belongs to another cache")
+        if B != sampler.B:
+            raise ValueError(f"DeviceCloudCache.fill_epoch: a sampler of {sampler.B} clouds per batch for buffers of {B}")
+        members = sampler.members
+        if members.min() < 0 or members.max() >= len(self.n):
+            raise IndexError(f"DeviceCloudCache.fill_epoch: member out of range for {len(self.n)} clouds")
+        most = max(self.nv[i] for i in set(members.tolist()))
+        if most > V:
+            raise ValueError(f"a wireframe has {most} vertices, more than max_vertices = {V}")
+        if not sampled:
+            rows = int(np.sort(np.asarray(self.n, dtype=np.int64)[members])[-B:].sum())
+            if rows > buffers["points"].shape[0]:
+                raise ValueError(f"DeviceCloudCache.fill_epoch: the {B} largest member clouds hold {rows} points, above the "
+                                 f"capacity of {buffers['points'].shape[0]} rows")
+
+    def fill_epoch(self, buffers, sampler):
+        """fill() for the NEXT batch of `sampler`, with nothing made on the host: three launches — the parameter block
+        and the seed words of batch t from the sampler's state (wf3d_cloud_epoch_params, which advances t), the sampler
+        (`buffers` from sampled_buffers) or the pack kernel (from packed_buffers), the targets.  Capturable, and every
+        replay advances to the next batch: no np.random draw, no pinned mirror, no copy.  The first call for a (buffers,
+        sampler) pair checks, once and before any launch, what stage() checks per batch: every member is a resident cloud
+        (IndexError), max_vertices holds the largest member wireframe and, for packed buffers, the capacity holds the B
+        largest member clouds (ValueError) — so no batch can break the block's rules."""
+        from wf3d import _lib
+        from wf3d.ops import _stream
+        sampled = "sample_words" in buffers
+        B, V = buffers["vertices"].shape[0], buffers["vertices"].shape[1]
+        pair = (buffers["params"].data_ptr(), buffers["points"].data_ptr(), tuple(buffers["points"].shape), V)
+        if pair not in sampler._checked:
+            self._check_epoch(buffers, sampler)
+            sampler._checked.add(pair)
+        lib = _lib.load()
+        words = buffers["sample_words"] if sampled else sampler.seed_words
+        _lib.check(lib.wf3d_cloud_epoch_params(
+            sampler.state.data_ptr(), sampler.members_dev.data_ptr(), len(sampler.members), self.first.data_ptr(), len(self.n), B,
+            sampler.world, sampler.rank, buffers["points"].shape[1] if sampled else 0, 1 if self.ds.augment else 0,
+            buffers["params"].data_ptr(), words.data_ptr(), _stream()), "cloud_epoch_params")
+        if sampled:
+            self._sample(buffers["params"], words, buffers["points"])
+        else:
+            self._pack(buffers["params"], B, buffers["points"].shape[0], buffers["points"], buffers["point_counts"])
+        _lib.check(lib.wf3d_wireframe_targets(
+            self.wf_vertices.data_ptr(), self.wf_edges.data_ptr(), self.vfirst.data_ptr(), self.efirst.data_ptr(), len(self.n),
+            buffers["params"].data_ptr(), B, V, buffers["vertices"].data_ptr(), buffers["vertex_existence"].data_ptr(),
+            buffers["vertex_counts"].data_ptr(), buffers["edge_labels"].data_ptr(), _stream()), "wireframe_targets")
+
+
+def _as_int64(x):
+    """the 64 bits of x as a signed integer (what an int64 tensor holds)"""
+    x &= (1 << 64) - 1
+    return x - (1 << 64) if x >= 1 << 63 else x
+
+
+class EpochSampler:
+    """Shuffled, rank-sharded, augmented epochs over the member clouds of a DeviceCloudCache, from 16 bytes of device
+    memory: `state` = int64 [key, t], t the batches produced so far.  `cache.fill_epoch(buffers, sampler)` reads it in the
+    kernel and advances t, so a loop of graph.replay() calls with nothing between them walks the epochs;
+    wf3d.sampling.epoch_batch states what batch t holds.
+
+        sampler = cache.epoch_sampler(B, world=W, rank=r, seed=1234)       # before the capture
+        with torch.cuda.graph(graph):
+            cache.fill_epoch(buffers, sampler)                               # ... and the training step
+        for _ in range(epochs * sampler.steps_per_epoch):
+            graph.replay()
+
+    steps_per_epoch = len(members) // (world * B): the last partial batch of an epoch is dropped.  The ranks' batches of
+    a step are disjoint, and their union is the batch a single rank with batch world * B would get (same clouds, same
+    augmentation).  The point rows a cloud contributes are keyed per (step, rank) and by the sample's position in the
+    rank's batch: they are NOT invariant under the world size."""
+
+    def __init__(self, cache, B, members=None, world=1, rank=0, seed=None):
+        from wf3d import sampling
+        B, world, rank = operator.index(B), operator.index(world), operator.index(rank)
+        members = list(range(len(cache.n))) if members is None else [operator.index(i) for i in members]
+        self.steps_per_epoch = sampling.epoch_steps(len(members), B, world, rank)
+        if any(not -1 << 31 <= i < 1 << 31 for i in members):
+            raise ValueError("DeviceCloudCache.epoch_sampler: a member is no int32")
+        if seed is None:
+            if world > 1:
+                raise ValueError("DeviceCloudCache.epoch_sampler: world > 1 needs an explicit integer seed (the ranks share one key)")
+        elif isinstance(seed, bool):
+            raise ValueError("DeviceCloudCache.epoch_sampler: seed must be an integer or None")
+        else:
+            seed = operator.index(seed)
+        if torch.device(cache.device).type == "cuda" and torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("DeviceCloudCache.epoch_sampler: the sampler must be created before a graph capture starts")
+        if seed is None:                                                   # as wf3d.random.DropoutGenerator keys itself
+            lo, hi = (int(x) for x in torch.randint(0, 1 << 32, (2,), dtype=torch.int64))
+            seed = lo | (hi << 32)
+        self.cache, self.B, self.world, self.rank = cache, B, world, rank
+        self.key = seed & ((1 << 64) - 1)
+        self.members = np.asarray(members, dtype=np.int32)
+        self.members_dev = torch.from_numpy(self.members).to(cache.device)
+        self.state = torch.tensor([_as_int64(self.key), 0], dtype=torch.int64, device=cache.device)
+        self.seed_words = torch.zeros(5, dtype=torch.int32, device=cache.device)     # packed buffers have none of their own
+        self._checked = set()
+
+    def get_state(self):
+        """[key, t] as a CPU int64 tensor (synchronises with the device)."""
+        return self.state.detach().to("cpu", copy=True)
+
+    def set_state(self, state):
+        state = torch.as_tensor(state, dtype=torch.int64).cpu()
+        if state.shape != (2,):
+            raise ValueError(f"EpochSampler.set_state: an int64 tensor [key, t], got shape {tuple(state.shape)}")
+        self.key = int(state[0]) & ((1 << 64) - 1)
+        self.state.copy_(state)
+
+    def seek(self, epoch, step=0):
+        """The next batch is step `step` of epoch `epoch`."""
+        epoch, step = operator.index(epoch), operator.index(step)
+        if epoch < 0 or not 0 <= step < self.steps_per_epoch:
+            raise ValueError(f"EpochSampler.seek: needs epoch >= 0 and 0 <= step < {self.steps_per_epoch} (got {epoch}, {step})")
+        self.set_state(torch.tensor([_as_int64(self.key), _as_int64(epoch * self.steps_per_epoch + step)], dtype=torch.int64))
+
+    def batch_at(self, t):
+        """Batch number t as the specification gives it, on the host and without a sync: wf3d.sampling.epoch_batch's
+        dict plus `cloud` (int32 [B]: the resident clouds).  A pure function of (key, t)."""
+        from wf3d import sampling
+        out = sampling.epoch_batch(self.key, t, len(self.members), self.B, self.world, self.rank, bool(self.cache.ds.augment))
+        out["cloud"] = self.members[out["order"]]
+        return out
+
+    def block_at(self, t, num_points=0):
+        """The parameter block of batch t (uint8 [40 B + 4], include/wf3d.h) as the kernel writes it: out_first = b *
+        num_points for the fixed-size form, the clouds' row offsets for the packed form (num_points = 0)."""
+        spec, B, n = self.batch_at(t), self.B, self.cache.n
+        block = torch.zeros(PARAM_BYTES * B + 4, dtype=torch.uint8)
+        v_aug, v_cloud, v_first = DeviceCloudCache._block_views(block, B)
+        v_aug[:], v_cloud[:] = spec["aug"], spec["cloud"]
+        if num_points:
+            v_first[:] = np.arange(B + 1, dtype=np.int64) * operator.index(num_points)
+        else:
+            rows = np.array([n[i] if 0 <= i < len(n) else 0 for i in spec["cloud"]], dtype=np.int64)
+            v_first[0], v_first[1:] = 0, (np.cumsum(rows) & 0xFFFFFFFF).astype(np.uint32).view(np.int32)
+        return block

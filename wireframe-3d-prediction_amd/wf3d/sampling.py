@@ -23,6 +23,8 @@ same distribution of subsets, not the same subsets.
 
 All arithmetic is modulo 2^32 (the kernel's uint32); the only wide product is the multiply-high.  Limits: 1 <= n < 2^31,
 1 <= P.  "Uniform" is up to the 2^-32 granularity of the multiply-high (a relative bias below n / 2^32).
+
+Below it, the specification of the epoch sampler (cloud_epoch_params_kernel): `epoch_batch(key, t, D, B, world, rank)`.
 """
 import numpy as np
 
@@ -99,3 +101,107 @@ def choice_indices_many(seed_words, b, n, P, return_walks=False):
 def choice_indices(seed_word, b, n, P):
     """int64 [P]: the rows sample `b` of a batch takes from a cloud of n rows under the batch's 32-bit `seed_word`."""
     return choice_indices_many([int(seed_word) & 0xFFFFFFFF], b, n, P)[0]
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Resident epochs (csrc/cloud.hip, cloud_epoch_params_kernel): which clouds a batch holds, their augmentation and the row
+# sampler's seed words as a pure function of a 64-bit key and the batch number t.
+#
+#   mix64(key, n)   csrc/random.hip's splitmix64 step: z = key + (n + 1) * 0x9E3779B97F4A7C15;
+#                   z = (z ^ z >> 30) * 0xBF58476D1CE4E5B9; z = (z ^ z >> 27) * 0x94D049BB133111EB; z ^ z >> 31  (mod 2^64)
+#   D member clouds, B per rank, W ranks, rank r:  S = D // (W B) steps per epoch (the last partial batch is dropped)
+#   batch t:  e = t // S, s = t % S;  slot b's global slot g = s W B + r B + b
+#   order_e  = choice_indices(low32(mix64(key, e)), 0, D, D)          a permutation of [0, D) per epoch
+#   cloud[b] = members[order_e[g]]
+#   c = e 2^32 + g:  za = mix64(key ^ 0x6A09E667F3BCC908, c): flip_x = -1 iff bit 63, flip_y = -1 iff bit 62
+#                    u = (mix64(key ^ 0xBB67AE8584CAA73B, c) >> 11) 2^-53;  t_rot = u (pi / 18) - pi / 36
+#   cos, sin of t_rot: epoch_cos_sin, fixed polynomials with every operation rounded on its own
+#   seed words: s = low32(mix64(key ^ 0x3C6EF372FE94F82B, t W + r)), words[k] = s + k 0x9E3779B9 (k = 0..4)
+#
+# Slots and augmentation depend on (e, g) only: the W ranks' batches of a step are disjoint and their union is the batch
+# of ONE rank with batch W B.  The seed words are per (step, rank), and the row sampler keys sample b by its LOCAL b, so
+# the ROWS a cloud contributes are not world-size invariant.  Limits: 1 <= D < 2^31, 1 <= B <= 4096, 0 <= r < W, W B <= D.
+# ---------------------------------------------------------------------------------------------------------------------
+_M64 = (1 << 64) - 1
+KEY_FLIP, KEY_ANGLE, KEY_ROWS = 0x6A09E667F3BCC908, 0xBB67AE8584CAA73B, 0x3C6EF372FE94F82B
+MAX_EPOCH_BATCH = 4096
+
+
+def mix64(key, n):
+    """uint64 array: the splitmix64 step at position(s) n of key's stream; key and n broadcast (any integers, mod 2^64)."""
+    key = np.asarray([int(k) & _M64 for k in np.atleast_1d(key).tolist()], dtype=np.uint64)
+    n = np.asarray([int(k) & _M64 for k in np.atleast_1d(n).tolist()], dtype=np.uint64)
+    with np.errstate(over="ignore"):
+        z = key + (n + _u(1)) * _u(0x9E3779B97F4A7C15)
+        z = (z ^ (z >> _u(30))) * _u(0xBF58476D1CE4E5B9)
+        z = (z ^ (z >> _u(27))) * _u(0x94D049BB133111EB)
+    return z ^ (z >> _u(31))
+
+
+def epoch_steps(D, B, world=1, rank=0):
+    """S = D // (world * B), the steps of an epoch, behind the limits (ValueError)."""
+    D, B, world, rank = int(D), int(B), int(world), int(rank)
+    if not 1 <= D < 1 << 31:
+        raise ValueError(f"epoch sampler: needs 1 <= D < 2^31 member clouds (got {D})")
+    if not 1 <= B <= MAX_EPOCH_BATCH:
+        raise ValueError(f"epoch sampler: needs 1 <= B <= {MAX_EPOCH_BATCH} (got {B})")
+    if world < 1 or not 0 <= rank < world:
+        raise ValueError(f"epoch sampler: needs 0 <= rank < world (got rank {rank}, world {world})")
+    if world * B > D:
+        raise ValueError(f"epoch sampler: world * B = {world * B} passes the {D} member clouds: no whole step in an epoch")
+    return D // (world * B)
+
+
+def epoch_order(key, e, D):
+    """int64 [D]: the order in which epoch e visits the members, a permutation of [0, D)."""
+    return choice_indices(int(mix64(key, e)[0]) & 0xFFFFFFFF, 0, D, D)
+
+
+def epoch_cos_sin(t):
+    """(cos t, sin t) for |t| <= pi / 36 as fixed polynomials — Taylor's, by Horner's rule, to x^12 and x^13 — with every
+    operation rounded on its own, so that the kernel (no fma) gives the same bits.  Truncation < 1e-25 on that range."""
+    t = np.asarray(t, dtype=np.float64)
+    x = t * t
+    ps, pc = np.ones_like(t), np.ones_like(t)
+    for k in (13, 11, 9, 7, 5, 3):
+        ps = 1.0 - x * ps / float(k * (k - 1))
+    for k in (12, 10, 8, 6, 4, 2):
+        pc = 1.0 - x * pc / float(k * (k - 1))
+    return pc, t * ps
+
+
+def epoch_augmentation(key, e, g, augment=True):
+    """float64 [len(g), 4] {flip_x, flip_y, cos t_rot, sin t_rot} of the global slots g of epoch e, and t_rot [len(g)]."""
+    g = np.atleast_1d(np.asarray(g, dtype=np.int64))
+    aug = np.tile(np.array([1.0, 1.0, 1.0, 0.0]), (g.size, 1))
+    if not augment:
+        return aug, np.zeros(g.size)
+    c = [((int(e) << 32) + int(k)) & _M64 for k in g]
+    za, zb = mix64(int(key) ^ KEY_FLIP, c), mix64(int(key) ^ KEY_ANGLE, c)
+    aug[:, 0] = np.where((za >> _u(63)) & _u(1), -1.0, 1.0)
+    aug[:, 1] = np.where((za >> _u(62)) & _u(1), -1.0, 1.0)
+    u = (zb >> _u(11)).astype(np.float64) * 2.0 ** -53
+    t_rot = u * (np.pi / 18) - np.pi / 36
+    aug[:, 2], aug[:, 3] = epoch_cos_sin(t_rot)
+    return aug, t_rot
+
+
+def epoch_seed_words(key, t, world=1, rank=0):
+    """uint32 [5]: the seed words of batch t on `rank` (word 0 is the row sampler's)."""
+    s = int(mix64(int(key) ^ KEY_ROWS, int(t) * int(world) + int(rank))[0]) & 0xFFFFFFFF
+    return np.array([(s + k * 0x9E3779B9) & 0xFFFFFFFF for k in range(5)], dtype=np.uint32)
+
+
+def epoch_batch(key, t, D, B, world=1, rank=0, augment=True):
+    """Batch number t >= 0 of the sampler keyed `key`: a dict of `epoch`, `step`, `slots` (int64 [B]: the global slots g),
+    `order` (int64 [B]: order_e[g], positions in the member table), `aug` (float64 [B, 4]), `angle` (float64 [B]: t_rot)
+    and `seed_words` (uint32 [5])."""
+    S = epoch_steps(D, B, world, rank)
+    key, t = int(key) & _M64, int(t)
+    if not 0 <= t <= _M64:
+        raise ValueError(f"epoch sampler: the batch number is a uint64 (got {t})")
+    e, s = divmod(t, S)
+    g = s * world * B + rank * B + np.arange(B, dtype=np.int64)
+    aug, angle = epoch_augmentation(key, e, g, augment)
+    return {"epoch": e, "step": s, "slots": g, "order": epoch_order(key, e, D)[g], "aug": aug, "angle": angle,
+            "seed_words": epoch_seed_words(key, t, world, rank)}
