@@ -642,6 +642,32 @@ int wf3d_clip_adam_step_dev(float* const* params, float* const* grads, float* co
                             const float* lr_dev, double beta1, double beta2, double eps, double weight_decay, float* ws,
                             size_t ws_floats, float* total_norm, void* stream);
 
+/* Grouped form: the same step with the Adam hyper-parameters per PARAMETER GROUP; the norm and the clip coefficient
+ * stay global (one clip_grad_norm_ over every tensor of every group and every clip-only tensor).  group[i] in
+ * [0, ngroups) is tensor i's group (ignored where params[i] is NULL); lr, beta1, beta2, eps, weight_decay, decoupled
+ * and step are HOST arrays of ngroups (at most 16) entries; lr_dev (NULL, or a host array of ngroups device fp32 scalars
+ * with NULL entries) replaces lr[k] where non-NULL.  decoupled[k] != 0 selects torch.optim.AdamW's decay for group k:
+ * the gradient enters the moments without the decay term and the parameter loses lr * weight_decay * p beside the Adam
+ * step, both in one subtraction; 0 is the L2 form of wf3d_clip_adam_step, whose bits a call with equal hyper-parameters
+ * in every group reproduces.
+ * steps == NULL is the host form: step[k] is the 1-based Adam step of every tensor of group k.  steps != NULL is the
+ * capturable form: steps[i] as in wf3d_clip_adam_step_dev, but each tensor's bias corrections come from its own
+ * counter, so tensors may be at different steps; `step` is not read.
+ * flags: WF3D_ADAM_SKIP_NONFINITE (capturable form only; needs skipped and total_norm) — when the global norm is NaN or
+ * infinite, no gradient, parameter, moment or step counter is written, *skipped (device int64) grows by one and
+ * total_norm still receives the norm.  The decision is taken on the device from the fp32 sum of squares: finite
+ * gradients whose squares overflow fp32 (a norm above 1.8e19) count as non-finite.  Without the flag a NaN norm
+ * poisons every tensor, as clip_grad_norm_ does.
+ * More than 16 groups: WF3D_ERR_UNSUPPORTED; a group index out of range or the flag without steps: WF3D_ERR_ARG;
+ * both before anything is launched. */
+#define WF3D_ADAM_SKIP_NONFINITE 1
+int wf3d_clip_adam_step_groups(float* const* params, float* const* grads, float* const* exp_avg, float* const* exp_avg_sq,
+                               const long* numel, const int* group, float* const* steps, int ntensors, const double* lr,
+                               const float* const* lr_dev, const double* beta1, const double* beta2, const double* eps,
+                               const double* weight_decay, const int* decoupled, const int* step, int ngroups,
+                               double max_norm, int flags, int64_t* skipped, float* ws, size_t ws_floats,
+                               float* total_norm, void* stream);
+
 /* ------------------------------------------------------------------------
  * Device-side dropout seeds (wf3d/random.py).  state = {key, counter} (uint64, device).  wf3d_dropout_draw: one thread
  * writes words[0..4] = s + k * 0x9E3779B9 (k = 0..4; words[k] for k >= 1 are EdgeFn's per-site seeds) with

@@ -40,3 +40,35 @@ from wf3d.optim import ClipAdam
 opt = ClipAdam(params[:-2], lr=1e-3, weight_decay=1e-6, max_norm=1.0, norm_params=lambda: params)   # last two = the lazy layer: clip only
 print(f"wf3d.optim.ClipAdam (clip + Adam, 2 launches): {timeit(lambda: opt.step()):.3f} ms "
       f"(0.99 GB moved -> {0.99 / timeit(lambda: opt.step()) :.2f} TB/s)")
+# the same tensors in two parameter groups (matrices; gains and biases without decay): the grouped launches carry 48
+# tensors each instead of 80, so 78 tensors + 2 clip-only take 2 Adam launches where one group takes 1
+own = params[:-2]
+two = ClipAdam([dict(params=[p for p in own if p.dim() > 1]), dict(params=[p for p in own if p.dim() <= 1], weight_decay=0.0)],
+               lr=1e-3, weight_decay=1e-6, max_norm=1.0, norm_params=lambda: params)
+for _ in range(3):                                       # alternated, so that a drift shows in both arms
+    print(f"ClipAdam one group {timeit(lambda: opt.step()):.3f} ms   two groups {timeit(lambda: two.step()):.3f} ms")
+
+
+def host_ms(fn, n=20):
+    """The call alone, on an idle device: what the host spends before it returns."""
+    import time
+    ts = []
+    for _ in range(n):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter(); fn(); ts.append((time.perf_counter() - t0) * 1e3)
+    return statistics.median(ts)
+
+
+def back_to_back_ms(fn, n=50):
+    """n steps issued without waiting: per step, the larger of the host's and the device's time."""
+    torch.cuda.synchronize()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(n):
+        fn()
+    e1.record(); torch.cuda.synchronize()
+    return e0.elapsed_time(e1) / n
+
+
+for name, o in (("one group", opt), ("two groups", two)):
+    print(f"ClipAdam {name}: host {host_ms(o.step):.3f} ms, back to back {back_to_back_ms(o.step):.3f} ms per step")
