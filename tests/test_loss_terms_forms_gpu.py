@@ -1,4 +1,4 @@
-"""The loss-term kernels of csrc/loss.hip (loss_terms_kernel, loss_terms_dev_kernel and its device-edge-width form)
+"""The loss-term kernels of csrc/loss.hip (loss_terms_kernel over host match lists, over a device assignment, and the latter's device-edge-width form)
 fed by the test itself: the assignment is a RANDOM permutation per sample, not an optimal one, so the kernels are held
 to what they are told and not to what the solver would have said.  Reference: float64 torch on the CPU with autograd —
 SmoothL1 (beta = 1) over the pairs {(p, col4row[p]) : col4row[p] < count}, averaged over 3 x the batch's matches, and

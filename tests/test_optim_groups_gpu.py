@@ -1,4 +1,4 @@
-"""The grouped form of csrc/optim.hip (clip_adam_groups_kernel, step_advance_finite_kernel, through
+"""The grouped form of csrc/optim.hip (clip_adam_kernel over its GroupedTab, step_advance_finite_kernel, through
 wf3d_clip_adam_step_groups and wf3d.optim.ClipAdam with parameter groups) against the float64 model
 tests/optim_groups_model.py, which tests/test_optim_groups_model.py pins to torch's clip_grad_norm_ + two-group Adam /
 AdamW in float64 and shows to reject near misses (another group's lr or step, a per-group norm, L2 for decoupled).
@@ -265,6 +265,33 @@ def test_many_small_tensors_over_two_groups(count, skip):
     assert c.shape == (count,) and c.tolist() == [4.0, 2.0] * (count // 2) + [4.0] * (count % 2)
     if skip:
         assert rig.opt.skipped_steps.item() == 0
+
+
+@pytest.mark.parametrize("capturable", [False, True])
+def test_the_two_table_cuts_give_the_same_bits(capturable):
+    """82 tensors of 3 elements, one of 16385 (two chunks) among the first 48 and a clip-only one of 9, at Adam step 2
+    with a clipped norm.  One group: the single-group entry points, whose table is cut after 80 tensors; two groups with
+    equal hyper-parameters and alternating membership: the grouped one, cut after 48.  Neither the number nor the place
+    of a partial sum depends on the cut, and the update is one expression: p, g, m, v of every tensor and the reported
+    norm are bit-equal."""
+    sizes = [3] * 82
+    sizes.insert(7, 16385)
+    alternating = [i % 2 for i in range(len(sizes))]
+    row = GM.group_hp(**GM.TWO_GROUPS[0])
+    before = GM.make_group_inputs(sizes, [9], alternating, (2, 2), seed=5500 + capturable, norm=4.0 * GM.MAX_NORM)
+    out = []
+    for rows, tg in (([row], [0] * len(sizes)), ([row, row], alternating)):
+        rig = GroupRig(sizes, tg, [9], rows=rows, capturable=capturable)
+        rig.load(before, (2, 2))
+        _, after, _ = rig.step(f"table cuts: {len(rows)} group(s) capturable={capturable}", before, report=False)
+        assert rig.counters().tolist() == [2.0] * len(sizes)
+        out.append((after, rig.opt.last_grad_norm.cpu().numpy()))
+    (a, na), (b, nb) = out
+    assert na > 2.0 * GM.MAX_NORM and _bits_equal(na, nb)
+    for r in "pgmv":
+        assert len(a[r]) == len(b[r]) == len(sizes) + 1
+        for x, y in zip(a[r], b[r]):
+            assert _bits_equal(x, y), r
 
 
 # ---------------------------------------------------------------------------------------------------------------------

@@ -57,34 +57,69 @@ __device__ __forceinline__ float bce(float p, float t, float& g) {
     return -(t * fmaxf(logf(p), -100.0f) + (1.0f - t) * fmaxf(log1pf(-p), -100.0f));
 }
 
-// One workgroup per sample: partial sums of the three terms + all gradients.
+// One workgroup per sample: partial sums of the three terms + all gradients.  The forms differ in the vertex term only:
+//   ASSIGNED = false  matches from host lists (the scipy path): m_a = m_pred, with m_tgt and m_off; gv = weight / normaliser
+//   ASSIGNED = true   the device assignment m_a = col4row: prediction p of sample b is matched iff col4row[b,p] < counts[b];
+//                     gv arrives as the vertex weight and is normalised here by the matches the counts add up to
+// The edge term runs over the common width min_e with the gradient scale gd (weight / normaliser, like ge); ewidth
+// non-NULL: the prediction width comes from the device, and min_e and gd are formed here from it and the edge weight we.
+template <bool ASSIGNED>
 __global__ __launch_bounds__(256) void loss_terms_kernel(const float* __restrict__ verts, long vs_b, long vs_v,
                                                           const float* __restrict__ exist,
                                                           const float* __restrict__ edge, int Ep,
                                                           const float* __restrict__ tverts, int Vt,
                                                           const float* __restrict__ texist,
                                                           const float* __restrict__ tlabel, int Et, int min_e,
-                                                          const int32_t* __restrict__ m_pred,
+                                                          const int32_t* __restrict__ m_a,
                                                           const int32_t* __restrict__ m_tgt,
-                                                          const int32_t* __restrict__ m_off, int V, int B,
-                                                          float gv, float ge, float gd,      // weight / normaliser
+                                                          const int32_t* __restrict__ m_off,
+                                                          const int64_t* __restrict__ counts, int V, int B,
+                                                          float gv, float ge, float gd,
                                                           float* __restrict__ dverts, float* __restrict__ dexist,
-                                                          float* __restrict__ dedge, float* __restrict__ part) {
+                                                          float* __restrict__ dedge, float* __restrict__ part,
+                                                          const int64_t* __restrict__ ewidth, float we) {
     __shared__ float red[4];
     const int b = blockIdx.x, tid = threadIdx.x;
+    if (ewidth) {
+        min_e = edge_common_width(*ewidth, Ep, Et);
+        gd = min_e ? we / ((float)B * min_e) : 0.f;
+    }
     // vertex term: SmoothL1 (beta = 1) over the Hungarian-matched pairs
-    for (int i = tid; i < V * 3; i += 256) dverts[(size_t)b * V * 3 + i] = 0.f;
-    __syncthreads();
     float sv = 0.f;
-    for (int m = m_off[b] + tid; m < m_off[b + 1]; m += 256) {
-        const int p = m_pred[m], t = m_tgt[m];
-        const float* v = verts + (size_t)b * vs_b + (size_t)p * vs_v;
-        const float* w = tverts + ((size_t)b * Vt + t) * 3;
+    if (ASSIGNED) {
+        long nm = 0;
+        for (int s = 0; s < B; ++s) nm += min((long)counts[s], (long)V);        // total matches = sum of real targets
+        gv = nm > 0 ? gv / (3.0f * (float)nm) : 0.f;
+        const int cnt = (int)counts[b];
+        for (int p = tid; p < V; p += 256) {
+            const int t = m_a[(size_t)b * V + p];
+            const bool m = t < cnt;
+            const float* vp = verts + (size_t)b * vs_b + (size_t)p * vs_v;
+            const float* w = tverts + ((size_t)b * Vt + (m ? t : 0)) * 3;
 #pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            const float d = v[k] - w[k], a = fabsf(d);
-            sv += a < 1.0f ? 0.5f * d * d : a - 0.5f;
-            dverts[((size_t)b * V + p) * 3 + k] = gv * (a < 1.0f ? d : (d > 0.f ? 1.0f : -1.0f));   // p unique per match
+            for (int k = 0; k < 3; ++k) {
+                float g = 0.f;
+                if (m) {
+                    const float d = vp[k] - w[k], a = fabsf(d);
+                    sv += a < 1.0f ? 0.5f * d * d : a - 0.5f;
+                    g = gv * (a < 1.0f ? d : (d > 0.f ? 1.0f : -1.0f));
+                }
+                dverts[((size_t)b * V + p) * 3 + k] = g;
+            }
+        }
+    } else {
+        for (int i = tid; i < V * 3; i += 256) dverts[(size_t)b * V * 3 + i] = 0.f;
+        __syncthreads();
+        for (int m = m_off[b] + tid; m < m_off[b + 1]; m += 256) {
+            const int p = m_a[m], t = m_tgt[m];
+            const float* v = verts + (size_t)b * vs_b + (size_t)p * vs_v;
+            const float* w = tverts + ((size_t)b * Vt + t) * 3;
+#pragma unroll
+            for (int k = 0; k < 3; ++k) {
+                const float d = v[k] - w[k], a = fabsf(d);
+                sv += a < 1.0f ? 0.5f * d * d : a - 0.5f;
+                dverts[((size_t)b * V + p) * 3 + k] = gv * (a < 1.0f ? d : (d > 0.f ? 1.0f : -1.0f));   // p unique per match
+            }
         }
     }
     // existence term
@@ -94,7 +129,7 @@ __global__ __launch_bounds__(256) void loss_terms_kernel(const float* __restrict
         se += bce(exist[(size_t)b * V + i], texist[(size_t)b * V + i], g);
         dexist[(size_t)b * V + i] = ge * g;
     }
-    // edge term over the common width min(Ep, Et)
+    // edge term over the common width
     float sd = 0.f;
     for (int i = tid; i < Ep; i += 256) {
         float g = 0.f;
@@ -105,10 +140,21 @@ __global__ __launch_bounds__(256) void loss_terms_kernel(const float* __restrict
     if (tid == 0) { part[b * 3] = sv; part[b * 3 + 1] = se; part[b * 3 + 2] = sd; }
 }
 
-__global__ void loss_final_kernel(const float* __restrict__ part, int B, float nv, float ne, float nd, float wv, float we,
-                                  float wd, float* __restrict__ out) {
+// COUNTS (the device assignment): the match count, so the vertex normaliser nv, is formed here from counts (a template
+// argument: the one thread's loop waits for no second load where there are no counts); ewidth non-NULL: so is the edge
+// normaliser nd
+template <bool COUNTS>
+__global__ void loss_final_kernel(const float* __restrict__ part, const int64_t* __restrict__ counts, int B, int V, float nv,
+                                  float ne, float nd, float wv, float we, float wd, float* __restrict__ out,
+                                  const int64_t* __restrict__ ewidth, int Ep, int Et) {
+    if (ewidth) nd = (float)B * edge_common_width(*ewidth, Ep, Et);
     float sv = 0.f, se = 0.f, sd = 0.f;
-    for (int b = 0; b < B; ++b) { sv += part[b * 3]; se += part[b * 3 + 1]; sd += part[b * 3 + 2]; }
+    long nm = 0;
+    for (int b = 0; b < B; ++b) {
+        sv += part[b * 3]; se += part[b * 3 + 1]; sd += part[b * 3 + 2];
+        if (COUNTS) nm += min((long)counts[b], (long)V);
+    }
+    if (COUNTS) nv = 3.0f * (float)nm;
     const float lv = nv > 0.f ? sv / nv : 0.f, le = ne > 0.f ? se / ne : 0.f, ld = nd > 0.f ? sd / nd : 0.f;
     out[0] = lv; out[1] = le; out[2] = ld; out[3] = wv * lv + we * le + wd * ld;
 }
@@ -301,73 +347,6 @@ __global__ __launch_bounds__(64) void lsa64_kernel(const float* __restrict__ cos
     }
 }
 
-// loss terms from the device assignment: prediction p of sample b is matched iff col4row[b,p] < count[b]
-__global__ __launch_bounds__(256) void loss_terms_dev_kernel(const float* __restrict__ verts, long vs_b, long vs_v,
-                                                              const float* __restrict__ exist,
-                                                              const float* __restrict__ edge, int Ep,
-                                                              const float* __restrict__ tverts, int Vt,
-                                                              const float* __restrict__ texist,
-                                                              const float* __restrict__ tlabel, int Et, int min_e,
-                                                              const int32_t* __restrict__ col4row,
-                                                              const int64_t* __restrict__ counts, int V, int B,
-                                                              float wv, float ge, float gd,
-                                                              float* __restrict__ dverts, float* __restrict__ dexist,
-                                                              float* __restrict__ dedge, float* __restrict__ part,
-                                                              const int64_t* __restrict__ ewidth = nullptr, float we = 0.f) {
-    __shared__ float red[4];
-    const int b = blockIdx.x, tid = threadIdx.x;
-    if (ewidth) {               // prediction width from the device: min_e and the edge gradient scale formed here
-        min_e = edge_common_width(*ewidth, Ep, Et);
-        gd = min_e ? we / ((float)B * min_e) : 0.f;
-    }
-    long nm = 0;
-    for (int s = 0; s < B; ++s) nm += min((long)counts[s], (long)V);        // total matches = sum of real targets
-    const float gv = nm > 0 ? wv / (3.0f * (float)nm) : 0.f;
-    const int cnt = (int)counts[b];
-    float sv = 0.f;
-    for (int p = tid; p < V; p += 256) {
-        const int t = col4row[(size_t)b * V + p];
-        const bool m = t < cnt;
-        const float* vp = verts + (size_t)b * vs_b + (size_t)p * vs_v;
-        const float* w = tverts + ((size_t)b * Vt + (m ? t : 0)) * 3;
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            float g = 0.f;
-            if (m) {
-                const float d = vp[k] - w[k], a = fabsf(d);
-                sv += a < 1.0f ? 0.5f * d * d : a - 0.5f;
-                g = gv * (a < 1.0f ? d : (d > 0.f ? 1.0f : -1.0f));
-            }
-            dverts[((size_t)b * V + p) * 3 + k] = g;
-        }
-    }
-    float se = 0.f;
-    for (int i = tid; i < V; i += 256) {
-        float g;
-        se += bce(exist[(size_t)b * V + i], texist[(size_t)b * V + i], g);
-        dexist[(size_t)b * V + i] = ge * g;
-    }
-    float sd = 0.f;
-    for (int i = tid; i < Ep; i += 256) {
-        float g = 0.f;
-        if (i < min_e) sd += bce(edge[(size_t)b * Ep + i], tlabel[(size_t)b * Et + i], g);
-        dedge[(size_t)b * Ep + i] = gd * g;
-    }
-    sv = block_sum(sv, red); se = block_sum(se, red); sd = block_sum(sd, red);
-    if (tid == 0) { part[b * 3] = sv; part[b * 3 + 1] = se; part[b * 3 + 2] = sd; }
-}
-
-__global__ void loss_final_dev_kernel(const float* __restrict__ part, const int64_t* __restrict__ counts, int B, int V,
-                                      float ne, float nd, float wv, float we, float wd, float* __restrict__ out,
-                                      const int64_t* __restrict__ ewidth = nullptr, int Ep = 0, int Et = 0) {
-    if (ewidth) nd = (float)B * edge_common_width(*ewidth, Ep, Et);
-    float sv = 0.f, se = 0.f, sd = 0.f;
-    long nm = 0;
-    for (int b = 0; b < B; ++b) { sv += part[b * 3]; se += part[b * 3 + 1]; sd += part[b * 3 + 2]; nm += min((long)counts[b], (long)V); }
-    const float lv = nm > 0 ? sv / (3.0f * (float)nm) : 0.f, le = ne > 0.f ? se / ne : 0.f, ld = nd > 0.f ? sd / nd : 0.f;
-    out[0] = lv; out[1] = le; out[2] = ld; out[3] = wv * lv + we * le + wd * ld;
-}
-
 }  // namespace
 
 extern "C" int wf3d_loss_cost_matrix(const float* verts, long sample_stride, long vertex_stride, const float* exist,
@@ -383,28 +362,79 @@ extern "C" int wf3d_loss_cost_matrix(const float* verts, long sample_stride, lon
     return WF3D_OK;
 }
 
+namespace {
+// where a term launch takes its matches from: host lists (the scipy path), or a device assignment (counts non-NULL),
+// which may come with a device edge width
+struct LossMatch {
+    const int32_t *m_pred, *m_tgt, *m_off;
+    int n_match;
+    const int32_t* col4row;
+    const int64_t *counts, *ewidth;
+};
+}  // namespace
+
+// The shared checks and the two launches of the three term entry points.  own_ptrs: the entry's own pointers are there.
+static int loss_terms_run(const char* fn, const LossMatch& ms, bool own_ptrs, const float* verts, long sample_stride,
+                          long vertex_stride, const float* exist, const float* edge, int Ep, const float* tverts, int Vt,
+                          const float* texist, const float* tlabel, int Et, int B, int V, float w_vertex, float w_exist,
+                          float w_edge, float* dverts, float* dexist, float* dedge, float* losses, void* ws, size_t ws_bytes,
+                          void* stream) {
+    WF3D_CHECK(B > 0 && V > 0 && Ep >= 0 && Et >= 0, WF3D_ERR_ARG, "%s: bad dims", fn);
+    WF3D_CHECK(own_ptrs && verts && exist && tverts && texist && dverts && dexist && losses, WF3D_ERR_ARG, "%s: null pointer", fn);
+    WF3D_CHECK(Ep == 0 || (edge && dedge), WF3D_ERR_ARG, "%s: null edge tensors", fn);
+    WF3D_CHECK(ws && ws_bytes >= (size_t)B * 3 * sizeof(float), WF3D_ERR_WS, "%s: workspace too small", fn);
+    // with a device edge width the common width, its gradient scale and its normaliser are formed on the device
+    const int min_e = (!ms.ewidth && Ep > 0 && Et > 0 && tlabel) ? (Ep < Et ? Ep : Et) : 0;
+    const float nv = 3.0f * (float)ms.n_match, ne = (float)B * V, nd = (float)B * min_e;
+    // the vertex gradient scale: the lists' is formed here, the assignment's on the device from the weight
+    const float gv = ms.counts ? w_vertex : (ms.n_match ? w_vertex / nv : 0.f);
+    hipStream_t st = (hipStream_t)stream;
+    auto terms = ms.counts ? &loss_terms_kernel<true> : &loss_terms_kernel<false>;
+    hipLaunchKernelGGL(terms, dim3(B), dim3(256), 0, st, verts, sample_stride, vertex_stride, exist, edge, Ep, tverts, Vt,
+                       texist, tlabel, Et, min_e, ms.counts ? ms.col4row : ms.m_pred, ms.m_tgt, ms.m_off, ms.counts, V, B, gv,
+                       w_exist / ne, min_e ? w_edge / nd : 0.f, dverts, dexist, dedge, (float*)ws, ms.ewidth, w_edge);
+    WF3D_LAUNCH_CHECK();
+    auto fin = ms.counts ? &loss_final_kernel<true> : &loss_final_kernel<false>;
+    hipLaunchKernelGGL(fin, dim3(1), dim3(1), 0, st, (const float*)ws, ms.counts, B, V, nv, ne, nd, w_vertex,
+                       w_exist, w_edge, losses, ms.ewidth, Ep, Et);
+    WF3D_LAUNCH_CHECK();
+    return WF3D_OK;
+}
+
 extern "C" int wf3d_loss_terms(const float* verts, long sample_stride, long vertex_stride, const float* exist,
                                const float* edge, int Ep, const float* tverts, int Vt, const float* texist,
                                const float* tlabel, int Et, const int32_t* m_pred, const int32_t* m_tgt,
                                const int32_t* m_off, int n_match, int B, int V, float w_vertex, float w_exist,
                                float w_edge, float* dverts, float* dexist, float* dedge, float* losses, void* ws,
                                size_t ws_bytes, void* stream) {
-    WF3D_CHECK(B > 0 && V > 0 && Ep >= 0 && Et >= 0 && n_match >= 0, WF3D_ERR_ARG, "wf3d_loss_terms: bad dims");
-    WF3D_CHECK(verts && exist && tverts && texist && m_off && dverts && dexist && losses, WF3D_ERR_ARG, "wf3d_loss_terms: null pointer");
-    WF3D_CHECK(Ep == 0 || (edge && dedge), WF3D_ERR_ARG, "wf3d_loss_terms: null edge tensors");
-    WF3D_CHECK(ws && ws_bytes >= (size_t)B * 3 * sizeof(float), WF3D_ERR_WS, "wf3d_loss_terms: workspace too small");
-    const int min_e = (Ep > 0 && Et > 0 && tlabel) ? (Ep < Et ? Ep : Et) : 0;
-    const float nv = 3.0f * (float)n_match, ne = (float)B * V, nd = (float)B * min_e;
-    const float gv = n_match ? w_vertex / nv : 0.f, ge = w_exist / ne, gd = min_e ? w_edge / nd : 0.f;
-    hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(loss_terms_kernel, dim3(B), dim3(256), 0, st, verts, sample_stride, vertex_stride, exist, edge, Ep,
-                       tverts, Vt, texist, tlabel, Et, min_e, m_pred, m_tgt, m_off, V, B, gv, ge, gd, dverts, dexist,
-                       dedge, (float*)ws);
-    WF3D_LAUNCH_CHECK();
-    hipLaunchKernelGGL(loss_final_kernel, dim3(1), dim3(1), 0, st, (const float*)ws, B, nv, ne, nd, w_vertex, w_exist,
-                       w_edge, losses);
-    WF3D_LAUNCH_CHECK();
-    return WF3D_OK;
+    WF3D_CHECK(n_match >= 0, WF3D_ERR_ARG, "wf3d_loss_terms: bad dims");
+    return loss_terms_run("wf3d_loss_terms", LossMatch{m_pred, m_tgt, m_off, n_match, nullptr, nullptr, nullptr}, m_off != nullptr,
+                          verts, sample_stride, vertex_stride, exist, edge, Ep, tverts, Vt, texist, tlabel, Et, B, V, w_vertex,
+                          w_exist, w_edge, dverts, dexist, dedge, losses, ws, ws_bytes, stream);
+}
+
+extern "C" int wf3d_loss_terms_assigned(const float* verts, long sample_stride, long vertex_stride, const float* exist,
+                                        const float* edge, int Ep, const float* tverts, int Vt, const float* texist,
+                                        const float* tlabel, int Et, const int32_t* col4row, const int64_t* counts,
+                                        int B, int V, float w_vertex, float w_exist, float w_edge, float* dverts,
+                                        float* dexist, float* dedge, float* losses, void* ws, size_t ws_bytes,
+                                        void* stream) {
+    return loss_terms_run("wf3d_loss_terms_assigned", LossMatch{nullptr, nullptr, nullptr, 0, col4row, counts, nullptr},
+                          col4row && counts, verts, sample_stride, vertex_stride, exist, edge, Ep, tverts, Vt, texist, tlabel, Et,
+                          B, V, w_vertex, w_exist, w_edge, dverts, dexist, dedge, losses, ws, ws_bytes, stream);
+}
+
+extern "C" int wf3d_loss_terms_assigned_ew(const float* verts, long sample_stride, long vertex_stride, const float* exist,
+                                           const float* edge, int Ep, const float* tverts, int Vt, const float* texist,
+                                           const float* tlabel, int Et, const int64_t* edge_width, const int32_t* col4row,
+                                           const int64_t* counts, int B, int V, float w_vertex, float w_exist, float w_edge,
+                                           float* dverts, float* dexist, float* dedge, float* losses, void* ws,
+                                           size_t ws_bytes, void* stream) {
+    // the other entries read a null tlabel as width 0; here the width is the device's to say
+    WF3D_CHECK(Et <= 0 || tlabel, WF3D_ERR_ARG, "wf3d_loss_terms_assigned_ew: null edge labels");
+    return loss_terms_run("wf3d_loss_terms_assigned_ew", LossMatch{nullptr, nullptr, nullptr, 0, col4row, counts, edge_width},
+                          col4row && counts && edge_width, verts, sample_stride, vertex_stride, exist, edge, Ep, tverts, Vt, texist,
+                          tlabel, Et, B, V, w_vertex, w_exist, w_edge, dverts, dexist, dedge, losses, ws, ws_bytes, stream);
 }
 
 extern "C" int wf3d_loss_assign(const float* cost, int B, int V, int32_t* col4row, void* stream) {
@@ -418,55 +448,6 @@ extern "C" int wf3d_loss_assign(const float* cost, int B, int V, int32_t* col4ro
         const size_t lds = (size_t)V * (3 * sizeof(double) + 4 * sizeof(int) + 1) + 16;
         hipLaunchKernelGGL(lsa_kernel, dim3(B), dim3(64), lds, (hipStream_t)stream, cost, V, col4row);
     }
-    WF3D_LAUNCH_CHECK();
-    return WF3D_OK;
-}
-
-extern "C" int wf3d_loss_terms_assigned(const float* verts, long sample_stride, long vertex_stride, const float* exist,
-                                        const float* edge, int Ep, const float* tverts, int Vt, const float* texist,
-                                        const float* tlabel, int Et, const int32_t* col4row, const int64_t* counts,
-                                        int B, int V, float w_vertex, float w_exist, float w_edge, float* dverts,
-                                        float* dexist, float* dedge, float* losses, void* ws, size_t ws_bytes,
-                                        void* stream) {
-    WF3D_CHECK(B > 0 && V > 0 && Ep >= 0 && Et >= 0, WF3D_ERR_ARG, "wf3d_loss_terms_assigned: bad dims");
-    WF3D_CHECK(verts && exist && tverts && texist && col4row && counts && dverts && dexist && losses, WF3D_ERR_ARG,
-               "wf3d_loss_terms_assigned: null pointer");
-    WF3D_CHECK(Ep == 0 || (edge && dedge), WF3D_ERR_ARG, "wf3d_loss_terms_assigned: null edge tensors");
-    WF3D_CHECK(ws && ws_bytes >= (size_t)B * 3 * sizeof(float), WF3D_ERR_WS, "wf3d_loss_terms_assigned: workspace too small");
-    const int min_e = (Ep > 0 && Et > 0 && tlabel) ? (Ep < Et ? Ep : Et) : 0;
-    const float ne = (float)B * V, nd = (float)B * min_e;
-    const float ge = w_exist / ne, gd = min_e ? w_edge / nd : 0.f;
-    hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(loss_terms_dev_kernel, dim3(B), dim3(256), 0, st, verts, sample_stride, vertex_stride, exist, edge,
-                       Ep, tverts, Vt, texist, tlabel, Et, min_e, col4row, counts, V, B, w_vertex, ge, gd, dverts, dexist,
-                       dedge, (float*)ws);
-    WF3D_LAUNCH_CHECK();
-    hipLaunchKernelGGL(loss_final_dev_kernel, dim3(1), dim3(1), 0, st, (const float*)ws, counts, B, V, ne, nd, w_vertex,
-                       w_exist, w_edge, losses);
-    WF3D_LAUNCH_CHECK();
-    return WF3D_OK;
-}
-
-extern "C" int wf3d_loss_terms_assigned_ew(const float* verts, long sample_stride, long vertex_stride, const float* exist,
-                                           const float* edge, int Ep, const float* tverts, int Vt, const float* texist,
-                                           const float* tlabel, int Et, const int64_t* edge_width, const int32_t* col4row,
-                                           const int64_t* counts, int B, int V, float w_vertex, float w_exist, float w_edge,
-                                           float* dverts, float* dexist, float* dedge, float* losses, void* ws,
-                                           size_t ws_bytes, void* stream) {
-    WF3D_CHECK(B > 0 && V > 0 && Ep >= 0 && Et >= 0, WF3D_ERR_ARG, "wf3d_loss_terms_assigned_ew: bad dims");
-    WF3D_CHECK(verts && exist && tverts && texist && col4row && counts && edge_width && dverts && dexist && losses, WF3D_ERR_ARG,
-               "wf3d_loss_terms_assigned_ew: null pointer");
-    WF3D_CHECK(Ep == 0 || (edge && dedge), WF3D_ERR_ARG, "wf3d_loss_terms_assigned_ew: null edge tensors");
-    WF3D_CHECK(Et == 0 || tlabel, WF3D_ERR_ARG, "wf3d_loss_terms_assigned_ew: null edge labels");
-    WF3D_CHECK(ws && ws_bytes >= (size_t)B * 3 * sizeof(float), WF3D_ERR_WS, "wf3d_loss_terms_assigned_ew: workspace too small");
-    const float ne = (float)B * V, ge = w_exist / ne;
-    hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(loss_terms_dev_kernel, dim3(B), dim3(256), 0, st, verts, sample_stride, vertex_stride, exist, edge,
-                       Ep, tverts, Vt, texist, tlabel, Et, 0, col4row, counts, V, B, w_vertex, ge, 0.f, dverts, dexist,
-                       dedge, (float*)ws, edge_width, w_edge);
-    WF3D_LAUNCH_CHECK();
-    hipLaunchKernelGGL(loss_final_dev_kernel, dim3(1), dim3(1), 0, st, (const float*)ws, counts, B, V, ne, 0.f, w_vertex,
-                       w_exist, w_edge, losses, edge_width, Ep, Et);
     WF3D_LAUNCH_CHECK();
     return WF3D_OK;
 }

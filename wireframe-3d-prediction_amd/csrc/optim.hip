@@ -19,6 +19,8 @@
 // capturable form every tensor's bias corrections come from its own counter.  The norm and the coefficient stay global.
 // The group table rides in the kernel arguments, so a launch carries 48 tensors instead of 80; the partial sums are
 // the same launches and the same positions as in the single-group form, so equal hyper-parameters give equal bits.
+// All forms are ONE kernel template and one host routine over two tensor tables: WideTab (80 tensors, one group, one
+// step pointer) and GroupedTab (48 tensors, a step pointer and a group index per tensor, 16 groups).
 // With WF3D_ADAM_SKIP_NONFINITE a step whose norm is NaN or infinite writes nothing but the norm and a skipped-step
 // count.  The sum of squares is an fp32 sum: finite gradients whose squares overflow it (norm above 1.8e19) count as
 // non-finite too.
@@ -48,22 +50,67 @@ struct StepArgs {
     int n;
 };
 
-// the device-side scalars of the capturable form (unused by the host-step launch)
-struct AdamDev {
-    const float* step;    // the Adam step BEFORE this update (torch.optim.Adam(capturable=True) state["step"])
-    const float* lr;      // NULL: the lr argument
-    double beta1, beta2;
+constexpr int OPT_MAXG = 16;              // parameter groups
+constexpr int OPT_GMAXT = 48;             // tensors per grouped launch: the 16-group table takes the room of the other 32
+
+// the hyper-parameters of NG parameter groups, one column per group; every derived scalar is formed in double before its
+// one rounding to fp32, as torch does on the host: 1 - 0.999 must become 0.001f, not 1.0f - 0.999f (off by 5e-5)
+template <int NG>
+struct GroupTab {
+    const float* lr_dev[NG];              // NULL: lr[k]
+    double beta1d[NG], beta2d[NG];        // the capturable form's bias corrections are formed in double
+    float lr[NG], beta1[NG], omb1[NG], beta2[NG], omb2[NG], eps[NG], wd[NG];
+    float bc1[NG], bc2_sqrt[NG];          // the host form's, per group, from its 1-based step
+    unsigned decoupled;                   // bit k: group k decays the parameter (AdamW), not the gradient
+
+    void set(int k, double lr_, const float* lr_dev_, double b1, double b2, double eps_, double wd_, bool dec, int step) {
+        lr_dev[k] = lr_dev_;
+        beta1d[k] = b1; beta2d[k] = b2;
+        lr[k] = (float)lr_; eps[k] = (float)eps_; wd[k] = (float)wd_;
+        beta1[k] = (float)b1; omb1[k] = (float)(1.0 - b1);
+        beta2[k] = (float)b2; omb2[k] = (float)(1.0 - b2);
+        if (step) {
+            bc1[k] = (float)(1.0 - pow(b1, (double)step));
+            bc2_sqrt[k] = (float)sqrt(1.0 - pow(b2, (double)step));
+        }
+        if (dec) decoupled |= 1u << k;
+    }
 };
 
-struct AdamArgs {
-    float* p[OPT_MAXT];
-    float* g[OPT_MAXT];
-    float* m[OPT_MAXT];
-    float* v[OPT_MAXT];
-    long n[OPT_MAXT];
-    int blk_begin[OPT_MAXT + 1];
+template <int MAXT_>
+struct TensorTab {
+    static constexpr int MAXT = MAXT_;
+    float* p[MAXT];
+    float* g[MAXT];
+    float* m[MAXT];
+    float* v[MAXT];
+    long n[MAXT];
+    int blk_begin[MAXT + 1];
     int ntensors;
 };
+
+// one group, so no group index, and ONE step pointer: the first optimised tensor's (every optimised tensor is at the
+// same step, the caller's rule).  bind() keeps the first it is given, through all launches of a step.
+struct WideTab : TensorTab<OPT_MAXT> {
+    using Groups = GroupTab<1>;
+    static constexpr bool SKIPS = false;  // no entry point asks the single-group form for the non-finite skip
+    const float* step0;
+    __device__ const float* step(int) const { return step0; }
+    __device__ int group(int) const { return 0; }
+    void bind(int i, const float* s, int) { if (p[i] && !step0) step0 = s; }
+};
+
+struct GroupedTab : TensorTab<OPT_GMAXT> {
+    using Groups = GroupTab<OPT_MAXG>;
+    static constexpr bool SKIPS = true;
+    const float* steps[MAXT];             // capturable form: the tensor's own counter
+    unsigned char groups[MAXT];
+    __device__ const float* step(int t) const { return steps[t]; }
+    __device__ int group(int t) const { return groups[t]; }
+    void bind(int i, const float* s, int k) { steps[i] = s; groups[i] = p[i] ? (unsigned char)k : 0; }
+};
+static_assert(sizeof(WideTab) + sizeof(WideTab::Groups) + 64 <= 4096, "kernel-argument budget");
+static_assert(sizeof(GroupedTab) + sizeof(GroupedTab::Groups) + 64 <= 4096, "kernel-argument budget");
 
 template <typename A>
 __device__ __forceinline__ int find_tensor(const A& a, int blk) {
@@ -125,14 +172,10 @@ __device__ __forceinline__ float clip_coef(float norm, float max_norm) {
 }
 
 // one workgroup's chunk [base, end) of one tensor: upd(p, g, m, v) per element, as f32x4 where all four are 16-byte
-// aligned; p == NULL: a clip-only tensor, g *= coef
+// aligned
 template <typename F>
-__device__ __forceinline__ void walk_chunk(float* p, float* g, float* m, float* v, long base, long end, float coef, F upd) {
+__device__ __forceinline__ void walk_chunk(float* p, float* g, float* m, float* v, long base, long end, F upd) {
     const bool vec = (((uintptr_t)g | (uintptr_t)p | (uintptr_t)m | (uintptr_t)v) & 15) == 0;
-    if (p == nullptr) {                               // clip-only tensor
-        for (long i = base + threadIdx.x; i < end; i += 256) g[i] *= coef;
-        return;
-    }
     if (vec) {
         for (long i = base + threadIdx.x * 4; i < end; i += 1024) {
             if (i + 4 <= end) {
@@ -155,73 +198,15 @@ __device__ __forceinline__ void walk_chunk(float* p, float* g, float* m, float* 
     }
 }
 
-template <bool DEV>
-__global__ __launch_bounds__(256) void clip_adam_kernel(const AdamArgs a, const float* __restrict__ partials, int npart,
-                                                         float max_norm, float lr, float beta1, float omb1, float beta2,
-                                                         float omb2, float eps, float wd, float bc1, float bc2_sqrt,
-                                                         float* __restrict__ norm_out, const AdamDev dv) {
-    __shared__ float s_red[4];
-    if (DEV) {
-        // as the host forms them: in double from the 1-based step, one rounding to fp32
-        const double t = (double)*dv.step + 1.0;
-        bc1 = (float)(1.0 - pow(dv.beta1, t));
-        bc2_sqrt = (float)sqrt(1.0 - pow(dv.beta2, t));
-        if (dv.lr) lr = *dv.lr;
-    }
-    const float norm = fold_norm(partials, npart, s_red);
-    const float coef = clip_coef(norm, max_norm);
-    if (blockIdx.x == 0 && threadIdx.x == 0 && norm_out) *norm_out = norm;
-    const int t = find_tensor(a, blockIdx.x);
-    const long base = (long)(blockIdx.x - a.blk_begin[t]) * OPT_CHUNK;
-    const long n = a.n[t];
-    const long end = base + OPT_CHUNK < n ? base + OPT_CHUNK : n;
-    const float step = lr / bc1;      // omb1 = 1 - beta1, omb2 = 1 - beta2 come rounded from double (1.0f - 0.999f is off by 5e-5)
-    walk_chunk(a.p[t], a.g[t], a.m[t], a.v[t], base, end, coef, [&](float& pp, float& gg, float& mm, float& vv) {
-        gg *= coef;                                   // the clipped gradient is what stays in .grad
-        const float ge = fmaf(wd, pp, gg);            // L2 weight decay folded into the gradient (torch Adam)
-        // exp_avg.lerp_(grad, 1 - beta1), from the nearer end as torch.lerp does: at beta1 <= 0.5 (weight >= 0.5) the
-        // form m + w (ge - m) leaves a rounding of m's size in a result of ge's size, which sqrt(v) ~ |ge| then divides
-        mm = omb1 < 0.5f ? fmaf(omb1, ge - mm, mm) : fmaf(-beta1, ge - mm, ge);
-        vv = fmaf(omb2 * ge, ge, beta2 * vv);         // exp_avg_sq.mul_(beta2).addcmul_(grad, grad, value = 1 - beta2)
-        pp -= step * (mm / (sqrtf(vv) / bc2_sqrt + eps));
-    });
-}
-
-// ---------------------------------------------------------------------------------------------------------------------
-// Grouped form (wf3d_clip_adam_step_groups): one global norm and one coefficient over every tensor, the Adam
-// hyper-parameters per parameter group, the Adam step per group (host form) or per tensor (capturable form).
-// ---------------------------------------------------------------------------------------------------------------------
-constexpr int OPT_MAXG = 16;              // parameter groups
-constexpr int OPT_GMAXT = 48;             // tensors per grouped launch: the group table takes the room of the other 32
-
-struct GroupTab {
-    const float* lr_dev[OPT_MAXG];        // NULL: lr[k]
-    double beta1d[OPT_MAXG], beta2d[OPT_MAXG];                    // the capturable form's bias corrections are formed in double
-    float lr[OPT_MAXG], beta1[OPT_MAXG], omb1[OPT_MAXG], beta2[OPT_MAXG], omb2[OPT_MAXG], eps[OPT_MAXG], wd[OPT_MAXG];
-    float bc1[OPT_MAXG], bc2_sqrt[OPT_MAXG];                      // the host form's, per group
-    unsigned decoupled;                   // bit k: group k decays the parameter (AdamW), not the gradient
-};
-
-struct GroupAdamArgs {
-    float* p[OPT_GMAXT];
-    float* g[OPT_GMAXT];
-    float* m[OPT_GMAXT];
-    float* v[OPT_GMAXT];
-    const float* step[OPT_GMAXT];         // capturable form: the tensor's own counter
-    long n[OPT_GMAXT];
-    int blk_begin[OPT_GMAXT + 1];
-    int ntensors;
-    unsigned char group[OPT_GMAXT];
-};
-static_assert(sizeof(GroupAdamArgs) + sizeof(GroupTab) + 64 <= 4096, "kernel-argument budget");
-
+// The Adam launch of every form: one global norm and one coefficient over every tensor, the Adam hyper-parameters per
+// parameter group of the table A, the Adam step (DEV: read from the device) per A::step().
 // SKIP: a norm that is NaN or infinite (an fp32 overflow of the sum of squares included) ends every workgroup before
 // its first store; the norm itself is still reported.  All workgroups of all launches of a step take the same decision:
 // they fold the same partials to the same bits.
-template <bool DEV, bool SKIP>
-__global__ __launch_bounds__(256) void clip_adam_groups_kernel(const GroupAdamArgs a, const GroupTab gt,
-                                                                const float* __restrict__ partials, int npart, float max_norm,
-                                                                float* __restrict__ norm_out) {
+template <typename A, bool DEV, bool SKIP>
+__global__ __launch_bounds__(256) void clip_adam_kernel(const A a, const typename A::Groups gt,
+                                                         const float* __restrict__ partials, int npart, float max_norm,
+                                                         float* __restrict__ norm_out) {
     __shared__ float s_red[4];
     const float norm = fold_norm(partials, npart, s_red);
     const float coef = clip_coef(norm, max_norm);
@@ -237,34 +222,38 @@ __global__ __launch_bounds__(256) void clip_adam_groups_kernel(const GroupAdamAr
         for (long i = base + threadIdx.x; i < end; i += 256) g[i] *= coef;
         return;
     }
-    const int k = a.group[t];
+    const int k = a.group(t);
     float bc1 = gt.bc1[k], bc2_sqrt = gt.bc2_sqrt[k];
     if (DEV) {
-        const double ts = (double)*a.step[t] + 1.0;   // as the host forms them, from this tensor's own step
+        // as the host forms them: in double from the 1-based step (the counter holds the step BEFORE this update, as
+        // torch.optim.Adam(capturable=True)'s state["step"]), one rounding to fp32
+        const double ts = (double)*a.step(t) + 1.0;
         bc1 = (float)(1.0 - pow(gt.beta1d[k], ts));
         bc2_sqrt = (float)sqrt(1.0 - pow(gt.beta2d[k], ts));
     }
     const float lr = gt.lr_dev[k] ? *gt.lr_dev[k] : gt.lr[k];
     const float beta1 = gt.beta1[k], omb1 = gt.omb1[k], beta2 = gt.beta2[k], omb2 = gt.omb2[k], eps = gt.eps[k], wd = gt.wd[k];
     const float step = lr / bc1;
+    // both moments from the gradient ge that enters them; returns the Adam decrement
+    auto adam = [&](float ge, float& mm, float& vv) {
+        // exp_avg.lerp_(grad, 1 - beta1), from the nearer end as torch.lerp does: at beta1 <= 0.5 (weight >= 0.5) the
+        // form m + w (ge - m) leaves a rounding of m's size in a result of ge's size, which sqrt(v) ~ |ge| then divides
+        mm = omb1 < 0.5f ? fmaf(omb1, ge - mm, mm) : fmaf(-beta1, ge - mm, ge);
+        vv = fmaf(omb2 * ge, ge, beta2 * vv);             // exp_avg_sq.mul_(beta2).addcmul_(grad, grad, value = 1 - beta2)
+        return step * (mm / (sqrtf(vv) / bc2_sqrt + eps));
+    };
     if (!((gt.decoupled >> k) & 1)) {
-        // L2 decay: clip_adam_kernel's expression, unchanged
-        walk_chunk(p, a.g[t], a.m[t], a.v[t], base, end, coef, [&](float& pp, float& gg, float& mm, float& vv) {
-            gg *= coef;
-            const float ge = fmaf(wd, pp, gg);
-            mm = omb1 < 0.5f ? fmaf(omb1, ge - mm, mm) : fmaf(-beta1, ge - mm, ge);
-            vv = fmaf(omb2 * ge, ge, beta2 * vv);
-            pp -= step * (mm / (sqrtf(vv) / bc2_sqrt + eps));
+        walk_chunk(p, a.g[t], a.m[t], a.v[t], base, end, [&](float& pp, float& gg, float& mm, float& vv) {
+            gg *= coef;                                   // the clipped gradient is what stays in .grad
+            pp -= adam(fmaf(wd, pp, gg), mm, vv);         // L2 weight decay folded into the gradient (torch Adam)
         });
     } else {
         // decoupled decay (torch.optim.AdamW: p *= 1 - lr wd, then the Adam step): the gradient enters the moments
         // as it is, and the whole decrement is formed before the one subtraction, so p is rounded once
         const float lrwd = lr * wd;
-        walk_chunk(p, a.g[t], a.m[t], a.v[t], base, end, coef, [&](float& pp, float& gg, float& mm, float& vv) {
+        walk_chunk(p, a.g[t], a.m[t], a.v[t], base, end, [&](float& pp, float& gg, float& mm, float& vv) {
             gg *= coef;
-            mm = omb1 < 0.5f ? fmaf(omb1, gg - mm, mm) : fmaf(-beta1, gg - mm, gg);
-            vv = fmaf(omb2 * gg, gg, beta2 * vv);
-            const float d = fmaf(lrwd, pp, step * (mm / (sqrtf(vv) / bc2_sqrt + eps)));
+            const float d = fmaf(lrwd, pp, adam(gg, mm, vv));
             pp -= d;
         });
     }
@@ -325,53 +314,6 @@ static int gradsq_launch(const char* fn, float* const* params, float* const* gra
     return WF3D_OK;
 }
 
-// shared by the two single-group entry points: `dv` null for the host step (bc1 / bc2_sqrt given), else the capturable form
-static int clip_adam_launch(const char* fn, float* const* params, float* const* grads, float* const* exp_avg,
-                            float* const* exp_avg_sq, const long* numel, int ntensors, double max_norm, double lr, double beta1,
-                            double beta2, double eps, double weight_decay, float bc1, float bc2_sqrt, const AdamDev* dv,
-                            float* ws, size_t ws_floats, float* total_norm, hipStream_t st) {
-    int npart = 0;
-    const int rc = gradsq_launch(fn, params, grads, exp_avg, exp_avg_sq, numel, ntensors, ws, ws_floats, st, &npart);
-    if (rc) return rc;
-    for (int t0 = 0; t0 < ntensors; t0 += OPT_MAXT) {
-        const int nt = ntensors - t0 < OPT_MAXT ? ntensors - t0 : OPT_MAXT;
-        AdamArgs a;
-        a.ntensors = nt;
-        int blk = 0;
-        for (int i = 0; i < nt; ++i) {
-            a.p[i] = params[t0 + i]; a.g[i] = grads[t0 + i]; a.m[i] = exp_avg[t0 + i]; a.v[i] = exp_avg_sq[t0 + i];
-            a.n[i] = numel[t0 + i]; a.blk_begin[i] = blk;
-            blk += wf3d_cdiv(numel[t0 + i], OPT_CHUNK);
-        }
-        for (int i = nt; i <= OPT_MAXT; ++i) a.blk_begin[i] = blk;
-        if (dv)
-            hipLaunchKernelGGL(clip_adam_kernel<true>, dim3(blk), dim3(256), 0, st, a, ws, npart, (float)max_norm, (float)lr,
-                               (float)beta1, (float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2), (float)eps, (float)weight_decay, 0.f,
-                               0.f, t0 == 0 ? total_norm : nullptr, *dv);
-        else
-            hipLaunchKernelGGL(clip_adam_kernel<false>, dim3(blk), dim3(256), 0, st, a, ws, npart, (float)max_norm, (float)lr,
-                               (float)beta1, (float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2), (float)eps, (float)weight_decay, bc1,
-                               bc2_sqrt, t0 == 0 ? total_norm : nullptr, AdamDev{});
-        WF3D_LAUNCH_CHECK();
-    }
-    return WF3D_OK;
-}
-
-extern "C" int wf3d_clip_adam_step(float* const* params, float* const* grads, float* const* exp_avg, float* const* exp_avg_sq,
-                                   const long* numel, int ntensors, double max_norm, double lr, double beta1, double beta2,
-                                   double eps, double weight_decay, int step, float* ws, size_t ws_floats, float* total_norm,
-                                   void* stream) {
-    WF3D_CHECK(ntensors >= 0 && params && grads && exp_avg && exp_avg_sq && numel, WF3D_ERR_ARG, "wf3d_clip_adam_step: null table");
-    if (ntensors == 0) return WF3D_OK;
-    WF3D_CHECK(step >= 1 && lr >= 0. && beta1 >= 0. && beta1 < 1. && beta2 >= 0. && beta2 < 1., WF3D_ERR_ARG, "wf3d_clip_adam_step: bad hyper-parameters");
-    // hyper-parameters arrive as doubles (Python floats) and every derived scalar is formed in double before the one
-    // rounding to fp32, as torch does on the host: 1 - 0.999 must become 0.001f, not 1.0f - 0.999f
-    const float bc1 = (float)(1.0 - pow(beta1, (double)step));
-    const float bc2_sqrt = (float)sqrt(1.0 - pow(beta2, (double)step));
-    return clip_adam_launch("wf3d_clip_adam_step", params, grads, exp_avg, exp_avg_sq, numel, ntensors, max_norm, lr, beta1,
-                            beta2, eps, weight_decay, bc1, bc2_sqrt, nullptr, ws, ws_floats, total_norm, (hipStream_t)stream);
-}
-
 // The capturable forms' last launches, after the last Adam launch on the same stream: no workgroup of this step reads an
 // advanced counter.  norm non-NULL (the skip flag): the counters stay where a non-finite *norm stopped the step, and the
 // first launch (there is one even without counters) adds that step to *skipped.
@@ -404,6 +346,51 @@ static int advance_steps(float* const* params, float* const* steps, int ntensors
     return WF3D_OK;
 }
 
+// The whole step of every form over tensor tables of type A, cut after A::MAXT tensors: the sums of squares, the Adam
+// launches and, in the capturable form (steps non-NULL), the counter advance.  group NULL: every tensor in group 0.
+template <typename A>
+static int clip_adam_run(const char* fn, float* const* params, float* const* grads, float* const* exp_avg,
+                         float* const* exp_avg_sq, const long* numel, const int* group, float* const* steps, int ntensors,
+                         const typename A::Groups& gt, double max_norm, bool skip, int64_t* skipped, float* ws,
+                         size_t ws_floats, float* total_norm, hipStream_t st) {
+    int npart = 0;
+    const int rc = gradsq_launch(fn, params, grads, exp_avg, exp_avg_sq, numel, ntensors, ws, ws_floats, st, &npart);
+    if (rc) return rc;
+    auto kern = steps ? &clip_adam_kernel<A, true, false> : &clip_adam_kernel<A, false, false>;
+    if constexpr (A::SKIPS)
+        if (skip) kern = &clip_adam_kernel<A, true, true>;
+    A a = {};                                             // one table for all launches: WideTab keeps its step pointer
+    for (int t0 = 0; t0 < ntensors; t0 += A::MAXT) {
+        const int nt = ntensors - t0 < A::MAXT ? ntensors - t0 : A::MAXT;
+        a.ntensors = nt;
+        int blk = 0;
+        for (int i = 0; i < nt; ++i) {
+            a.p[i] = params[t0 + i]; a.g[i] = grads[t0 + i]; a.m[i] = exp_avg[t0 + i]; a.v[i] = exp_avg_sq[t0 + i];
+            a.n[i] = numel[t0 + i]; a.blk_begin[i] = blk;
+            a.bind(i, steps ? steps[t0 + i] : nullptr, group ? group[t0 + i] : 0);
+            blk += wf3d_cdiv(numel[t0 + i], OPT_CHUNK);
+        }
+        for (int i = nt; i <= A::MAXT; ++i) a.blk_begin[i] = blk;
+        hipLaunchKernelGGL(kern, dim3(blk), dim3(256), 0, st, a, gt, ws, npart, (float)max_norm, t0 == 0 ? total_norm : nullptr);
+        WF3D_LAUNCH_CHECK();
+    }
+    if (!steps) return WF3D_OK;
+    return advance_steps(params, steps, ntensors, skip ? total_norm : nullptr, skipped, st);
+}
+
+extern "C" int wf3d_clip_adam_step(float* const* params, float* const* grads, float* const* exp_avg, float* const* exp_avg_sq,
+                                   const long* numel, int ntensors, double max_norm, double lr, double beta1, double beta2,
+                                   double eps, double weight_decay, int step, float* ws, size_t ws_floats, float* total_norm,
+                                   void* stream) {
+    WF3D_CHECK(ntensors >= 0 && params && grads && exp_avg && exp_avg_sq && numel, WF3D_ERR_ARG, "wf3d_clip_adam_step: null table");
+    if (ntensors == 0) return WF3D_OK;
+    WF3D_CHECK(step >= 1 && lr >= 0. && beta1 >= 0. && beta1 < 1. && beta2 >= 0. && beta2 < 1., WF3D_ERR_ARG, "wf3d_clip_adam_step: bad hyper-parameters");
+    GroupTab<1> gt = {};
+    gt.set(0, lr, nullptr, beta1, beta2, eps, weight_decay, false, step);
+    return clip_adam_run<WideTab>("wf3d_clip_adam_step", params, grads, exp_avg, exp_avg_sq, numel, nullptr, nullptr, ntensors, gt,
+                                  max_norm, false, nullptr, ws, ws_floats, total_norm, (hipStream_t)stream);
+}
+
 extern "C" int wf3d_clip_adam_step_dev(float* const* params, float* const* grads, float* const* exp_avg,
                                        float* const* exp_avg_sq, float* const* steps, const long* numel, int ntensors,
                                        double max_norm, double lr, const float* lr_dev, double beta1, double beta2, double eps,
@@ -413,25 +400,14 @@ extern "C" int wf3d_clip_adam_step_dev(float* const* params, float* const* grads
     if (ntensors == 0) return WF3D_OK;
     WF3D_CHECK(lr >= 0. && beta1 >= 0. && beta1 < 1. && beta2 >= 0. && beta2 < 1., WF3D_ERR_ARG,
                "wf3d_clip_adam_step_dev: bad hyper-parameters");
-    const float* step0 = nullptr;
-    for (int i = 0; i < ntensors; ++i) {
+    for (int i = 0; i < ntensors; ++i)
         WF3D_CHECK(!params[i] || steps[i], WF3D_ERR_ARG, "wf3d_clip_adam_step_dev: tensor %d has no step counter", i);
-        if (params[i] && !step0) step0 = steps[i];
-    }
-    hipStream_t st = (hipStream_t)stream;
-    if (step0) {
-        // every optimised tensor is at the same step (the caller's rule): the first one's counter gives the bias corrections
-        const AdamDev dv{step0, lr_dev, beta1, beta2};
-        const int rc = clip_adam_launch("wf3d_clip_adam_step_dev", params, grads, exp_avg, exp_avg_sq, numel, ntensors, max_norm,
-                                        lr, beta1, beta2, eps, weight_decay, 0.f, 0.f, &dv, ws, ws_floats, total_norm, st);
-        if (rc) return rc;
-    } else {
-        // clip-only tensors: the step counter never enters
-        const int rc = clip_adam_launch("wf3d_clip_adam_step_dev", params, grads, exp_avg, exp_avg_sq, numel, ntensors, max_norm,
-                                        lr, beta1, beta2, eps, weight_decay, 1.f, 1.f, nullptr, ws, ws_floats, total_norm, st);
-        if (rc) return rc;
-    }
-    return advance_steps(params, steps, ntensors, nullptr, nullptr, st);
+    // every optimised tensor is at the same step (the caller's rule): the first one's counter gives the bias corrections.
+    // A table of clip-only tensors has none, and no workgroup reads one.
+    GroupTab<1> gt = {};
+    gt.set(0, lr, lr_dev, beta1, beta2, eps, weight_decay, false, 0);
+    return clip_adam_run<WideTab>("wf3d_clip_adam_step_dev", params, grads, exp_avg, exp_avg_sq, numel, nullptr, steps, ntensors,
+                                  gt, max_norm, false, nullptr, ws, ws_floats, total_norm, (hipStream_t)stream);
 }
 
 extern "C" int wf3d_clip_adam_step_groups(float* const* params, float* const* grads, float* const* exp_avg,
@@ -452,54 +428,18 @@ extern "C" int wf3d_clip_adam_step_groups(float* const* params, float* const* gr
     WF3D_CHECK(!skip || (steps && skipped && total_norm), WF3D_ERR_ARG,
                "%s: WF3D_ADAM_SKIP_NONFINITE needs device step counters, a skipped-step counter and total_norm", fn);
     if (ntensors == 0) return WF3D_OK;
-    GroupTab gt = {};
+    GroupTab<OPT_MAXG> gt = {};
     for (int k = 0; k < ngroups; ++k) {
         WF3D_CHECK(lr[k] >= 0. && beta1[k] >= 0. && beta1[k] < 1. && beta2[k] >= 0. && beta2[k] < 1. && (steps || step[k] >= 1),
                    WF3D_ERR_ARG, "%s: bad hyper-parameters in group %d", fn, k);
-        // every derived scalar in double before its one rounding to fp32, as in the single-group forms
-        gt.lr_dev[k] = lr_dev ? lr_dev[k] : nullptr;
-        gt.beta1d[k] = beta1[k]; gt.beta2d[k] = beta2[k];
-        gt.lr[k] = (float)lr[k]; gt.eps[k] = (float)eps[k]; gt.wd[k] = (float)weight_decay[k];
-        gt.beta1[k] = (float)beta1[k]; gt.omb1[k] = (float)(1.0 - beta1[k]);
-        gt.beta2[k] = (float)beta2[k]; gt.omb2[k] = (float)(1.0 - beta2[k]);
-        if (!steps) {
-            gt.bc1[k] = (float)(1.0 - pow(beta1[k], (double)step[k]));
-            gt.bc2_sqrt[k] = (float)sqrt(1.0 - pow(beta2[k], (double)step[k]));
-        }
-        if (decoupled[k]) gt.decoupled |= 1u << k;
+        gt.set(k, lr[k], lr_dev ? lr_dev[k] : nullptr, beta1[k], beta2[k], eps[k], weight_decay[k], decoupled[k], steps ? 0 : step[k]);
     }
     for (int i = 0; i < ntensors; ++i) {
         if (!params[i]) continue;
         WF3D_CHECK(group[i] >= 0 && group[i] < ngroups, WF3D_ERR_ARG, "%s: tensor %d is in group %d of %d", fn, i, group[i], ngroups);
         WF3D_CHECK(!steps || steps[i], WF3D_ERR_ARG, "%s: tensor %d has no step counter", fn, i);
     }
-    hipStream_t st = (hipStream_t)stream;
-    int npart = 0;
-    int rc = gradsq_launch(fn, params, grads, exp_avg, exp_avg_sq, numel, ntensors, ws, ws_floats, st, &npart);
-    if (rc) return rc;
-    for (int t0 = 0; t0 < ntensors; t0 += OPT_GMAXT) {
-        const int nt = ntensors - t0 < OPT_GMAXT ? ntensors - t0 : OPT_GMAXT;
-        GroupAdamArgs a = {};
-        a.ntensors = nt;
-        int blk = 0;
-        for (int i = 0; i < nt; ++i) {
-            a.p[i] = params[t0 + i]; a.g[i] = grads[t0 + i]; a.m[i] = exp_avg[t0 + i]; a.v[i] = exp_avg_sq[t0 + i];
-            a.step[i] = steps ? steps[t0 + i] : nullptr;
-            a.group[i] = params[t0 + i] ? (unsigned char)group[t0 + i] : 0;
-            a.n[i] = numel[t0 + i]; a.blk_begin[i] = blk;
-            blk += wf3d_cdiv(numel[t0 + i], OPT_CHUNK);
-        }
-        for (int i = nt; i <= OPT_GMAXT; ++i) a.blk_begin[i] = blk;
-        float* norm_out = t0 == 0 ? total_norm : nullptr;
-        const float mx = (float)max_norm;
-        if (steps && skip)
-            hipLaunchKernelGGL((clip_adam_groups_kernel<true, true>), dim3(blk), dim3(256), 0, st, a, gt, ws, npart, mx, norm_out);
-        else if (steps)
-            hipLaunchKernelGGL((clip_adam_groups_kernel<true, false>), dim3(blk), dim3(256), 0, st, a, gt, ws, npart, mx, norm_out);
-        else
-            hipLaunchKernelGGL((clip_adam_groups_kernel<false, false>), dim3(blk), dim3(256), 0, st, a, gt, ws, npart, mx, norm_out);
-        WF3D_LAUNCH_CHECK();
-    }
-    if (!steps) return WF3D_OK;
-    return advance_steps(params, steps, ntensors, skip ? total_norm : nullptr, skipped, st);
+    return clip_adam_run<GroupedTab>(fn, params, grads, exp_avg, exp_avg_sq, numel, group, steps, ntensors, gt, max_norm, skip,
+                                     skipped, ws, ws_floats, total_norm, (hipStream_t)stream);
 }
+

@@ -36,7 +36,16 @@ from scipy.optimize import linear_sum_assignment
 from wf3d import ops
 
 
-class _LossDevFn(torch.autograd.Function):
+class _TermsFn(torch.autograd.Function):
+    """The backward of both forms: forward saved the gradients of the total w.r.t. its first three inputs."""
+
+    @staticmethod
+    def backward(ctx, g_total, _g_losses):
+        dv, de, dd = ctx.saved_tensors
+        return (dv * g_total, de * g_total, dd * g_total) + (None,) * (len(ctx.needs_input_grad) - 3)
+
+
+class _LossDevFn(_TermsFn):
     """Fully asynchronous variant: cost matrices, assignment, loss terms and gradients all on the device."""
 
     @staticmethod
@@ -56,13 +65,8 @@ class _LossDevFn(torch.autograd.Function):
         ctx.mark_non_differentiable(losses)
         return losses[3].clone(), losses
 
-    @staticmethod
-    def backward(ctx, g_total, _g_losses):
-        dv, de, dd = ctx.saved_tensors
-        return (dv * g_total, de * g_total, dd * g_total, None, None, None, None, None, None, None)
 
-
-class _LossFn(torch.autograd.Function):
+class _LossFn(_TermsFn):
     @staticmethod
     def forward(ctx, verts, exist, edge, tverts, texist, tlabel, m_pred, m_tgt, m_off, n_match, weights):
         losses, dv, de, dd = ops.loss_terms(verts, exist.contiguous(), edge.contiguous(), tverts, texist, tlabel,
@@ -70,11 +74,6 @@ class _LossFn(torch.autograd.Function):
         ctx.save_for_backward(dv, de, dd)
         ctx.mark_non_differentiable(losses)
         return losses[3].clone(), losses
-
-    @staticmethod
-    def backward(ctx, g_total, _g_losses):
-        dv, de, dd = ctx.saved_tensors
-        return (dv * g_total, de * g_total, dd * g_total, None, None, None, None, None, None, None, None)
 
 
 class WireframeLoss(nn.Module):
@@ -150,14 +149,14 @@ class WireframeLoss(nn.Module):
             raise ValueError(f"targets['vertex_existence'] must be [B, V] = {(B, V)}, got {tuple(targets['vertex_existence'].shape)}")
         if targets["vertices"].dim() != 3 or targets["vertices"].shape[0] != B or targets["vertices"].shape[2] != 3:
             raise ValueError("targets['vertices'] must be [B, Vt, 3]")
+        tv, te, tl = (targets[k].to(device=dev, dtype=torch.float32).contiguous()
+                      for k in ("vertices", "vertex_existence", "edge_labels"))
+        # weights in the kernels' (vertex, existence, edge) order
+        w = (self.vertex_weight, self.existence_weight, self.edge_weight)
         if self.assignment == "device":
             counts = targets["vertex_counts"].to(device=dev, dtype=torch.int64).contiguous()
-            tv = targets["vertices"].to(device=dev, dtype=torch.float32).contiguous()
-            te = targets["vertex_existence"].to(device=dev, dtype=torch.float32).contiguous()
-            tl = targets["edge_labels"].to(device=dev, dtype=torch.float32).contiguous()
             # the kernels index targets['vertices'][b, :counts[b]] and need counts[b] <= V real columns: clamp (docstring)
             counts = counts.clamp(min=0, max=min(V, tv.shape[1]))
-            w = (self.vertex_weight, self.existence_weight, self.edge_weight)
             ew = predictions.get("edge_width")        # padded edge head: the prediction width is a device scalar
             ew = ew.to(device=dev, dtype=torch.int64) if ew is not None else None
             scales = self._dp_scales(counts, B, V, pp.shape[1] if ew is None else ew, tl.shape[1], dev)
@@ -171,13 +170,8 @@ class WireframeLoss(nn.Module):
         cat = lambda k: (np.concatenate([m[k] for m in matches]).astype(np.int32) if n_match else np.zeros(0, np.int32))   # noqa: E731
         packed = torch.from_numpy(np.concatenate([cat(0), cat(1), off])).to(dev, non_blocking=True)
         m_pred, m_tgt, m_off = packed[:n_match], packed[n_match:2 * n_match], packed[2 * n_match:]
-        tv = targets["vertices"].to(device=dev, dtype=torch.float32).contiguous()
-        te = targets["vertex_existence"].to(device=dev, dtype=torch.float32).contiguous()
-        tl = targets["edge_labels"].to(device=dev, dtype=torch.float32).contiguous()
         if predictions.get("edge_width") is not None:
             # padded edge head: this path has synced already, the width is read here and the columns past it dropped
             pp = pp[:, :int(predictions["edge_width"])]
-        # weights in the kernel's (vertex, existence, edge) order
-        w = (self.vertex_weight, self.existence_weight, self.edge_weight)
         total, parts = _LossFn.apply(pv, pe, pp, tv, te, tl, m_pred, m_tgt, m_off, n_match, w)
         return {"total_loss": total, "vertex_loss": parts[0], "existence_loss": parts[1], "edge_loss": parts[2]}
