@@ -745,6 +745,31 @@ int wf3d_meter_update(const float* total, const float* vertex_loss, const float*
                       const float* pred_vertices, long pred_stride, const float* target_vertices, long target_stride,
                       const int64_t* count0, int max_v, float* state, int capacity, void* stream);
 
+/* Training metrics (wf3d.meter.WireframeMeter): batch-wide quality counters from the assignment the loss has solved
+ * (col4row of wf3d_loss_assign, int32 [B, V]), in two launches with no atomics: the same inputs give the same bits.
+ * verts / exist / edge / tverts / texist / tlabel / counts as wf3d_loss_terms_assigned takes them.  With
+ * c_b = clamp(counts[b], 0, min(V, Vt)):
+ *   matched pair   slot p of sample b with 0 <= col4row[b, p] < c_b, its target t = col4row[b, p]; every other value
+ *                  (negative, >= c_b) leaves the slot unmatched, and the pairs are counted, not assumed to be c_b.
+ *                  d2 = ((dx dx + dy dy) + dz dz) in fp64 from the fp32 coordinates, each product and sum rounded;
+ *                  sum_sq += d2, sum_dist += sqrt(d2), n_within += (d2 <= double(distance_thresh)^2).
+ *   existence      over all B * V slots: predicted exist > 0.5f, label texist > 0.5f -> ex_tp, ex_fp, ex_fn;
+ *                  count_abs_err += |#(exist[b] > 0.5f) - c_b| per sample.
+ *   edges          over the first w = min(Ep, Et) columns, or min(*edge_width, Ep, Et) with edge_width (a padded edge
+ *                  head's device width, read when the kernels run): predicted edge > edge_threshold, label tlabel >
+ *                  0.5f -> ed_tp, ed_fp, ed_fn.  Columns at or past w are not read.
+ * Comparisons with NaN are false: the integer counters stay finite, the two sums carry the NaN.
+ * state [2][13] fp64 (8-byte aligned): row 0 is written with this batch, row 1 grows by it (the caller zeroes row 1 to
+ * reset); columns updates (1 per call), n_samples (B), n_pairs, sum_sq, sum_dist, n_within, ex_tp, ex_fp, ex_fn,
+ * count_abs_err, ed_tp, ed_fp, ed_fn.  Counts held in fp64 are exact to 2^53.
+ * ws: wf3d_train_metrics_ws_bytes(B, Ep) bytes, 16-byte aligned (one record per sample and per 2048 edge columns).
+ * V <= 1024, B <= 65535, B * Ep and B * Et below 2^31, else WF3D_ERR_UNSUPPORTED; B, V, Vt >= 1. */
+size_t wf3d_train_metrics_ws_bytes(int B, int Ep);
+int wf3d_train_metrics(const float* verts, long sample_stride, long vertex_stride, const float* exist, const float* edge,
+                       int Ep, const float* tverts, int Vt, const float* texist, const float* tlabel, int Et,
+                       const int32_t* col4row, const int64_t* counts, const int64_t* edge_width, int B, int V,
+                       float edge_threshold, float distance_thresh, double* state, void* ws, size_t ws_bytes, void* stream);
+
 /* ------------------------------------------------------------------------
  * Row f-3: the input pipeline, datasets/building3d.py:95-158.  Clouds are parsed once, normalised once on
  * the device in float64 (the raw coordinates are UTM metres: colour / 256 for columns [color_lo, color_hi), centroid and

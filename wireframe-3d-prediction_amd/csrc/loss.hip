@@ -12,14 +12,6 @@
 
 namespace {
 
-// the edge term's common width min(prediction width, Ep, Et) when the prediction width is a device scalar
-// (a padded edge head's edge_width; its predictions tensor is Ep >= width wide)
-__device__ __forceinline__ int edge_common_width(int64_t w, int Ep, int Et) {
-    int64_t m = w < (int64_t)Ep ? w : (int64_t)Ep;
-    if ((int64_t)Et < m) m = Et;
-    return m > 0 ? (int)m : 0;
-}
-
 // cost[b,p,t] = sum_k |v[b,p,k] - tv[b,t,k]| + |e[b,p] - 1|   for t < count[b]   (real targets)
 //             = e[b,p]                                         for t >= count[b]  (dummy columns)
 __global__ __launch_bounds__(256) void loss_cost_kernel(const float* __restrict__ verts, long vs_b, long vs_v,

@@ -222,6 +222,14 @@ __device__ __forceinline__ void edge_ij(int e, int v, int& i, int& j) {
 }
 __device__ __forceinline__ int edge_offset(int i, int v) { return (i * (2 * v - i - 1)) / 2; }
 
+// the common width min(prediction width, Ep, Et) of the loss's edge term and of the training metrics when the prediction
+// width is a device scalar (a padded edge head's edge_width; its predictions tensor is Ep >= width wide)
+__device__ __forceinline__ int edge_common_width(int64_t w, int Ep, int Et) {
+    int64_t m = w < (int64_t)Ep ? w : (int64_t)Ep;
+    if ((int64_t)Et < m) m = Et;
+    return m > 0 ? (int)m : 0;
+}
+
 __device__ __forceinline__ float wf3d_wave_sum(float v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);

@@ -24,6 +24,11 @@ Differences to know about:
   * a padded edge head (PointCloudToWireframe.set_edge_layout("padded")) predicts [B, V(V-1)/2] with the width
     max_s E_s in predictions["edge_width"] (a device scalar): the edge term runs over min(that width, label width),
     as the reference's over min(pred width, label width), so labels may be allocated at full width V(V-1)/2.
+  * `last_assignment`: after every forward, the matching the loss used, as an int32 [B, V] device tensor — prediction
+    slot p of sample b is matched to target last_assignment[b, p] iff that value is below the sample's (clamped) count.
+    On the device path it is the solver's output itself (no extra launch; unmatched slots hold their dummy column);
+    on the scipy path it is built from the match lists with V in the unmatched slots.  wf3d.meter.WireframeMeter
+    turns it into batch-wide metrics without a host read.
   * `set_data_parallel()`: with one process per GPU each rank sees a slice of the batch, but the reference's
     normalisers are batch-wide (matched-vertex count, :276-281; B x common edge width, :82-86).  When enabled,
     the three normalisers are exchanged (one tiny all-reduce) and each term is rescaled so that the MEAN over
@@ -37,10 +42,11 @@ from wf3d import ops
 
 
 class _TermsFn(torch.autograd.Function):
-    """The backward of both forms: forward saved the gradients of the total w.r.t. its first three inputs."""
+    """The backward of both forms: forward saved the gradients of the total w.r.t. its first three inputs; every output
+    after the total is non-differentiable."""
 
     @staticmethod
-    def backward(ctx, g_total, _g_losses):
+    def backward(ctx, g_total, *_g_rest):
         dv, de, dd = ctx.saved_tensors
         return (dv * g_total, de * g_total, dd * g_total) + (None,) * (len(ctx.needs_input_grad) - 3)
 
@@ -62,8 +68,8 @@ class _LossDevFn(_TermsFn):
             losses = torch.cat([losses[:3], (losses[:3] * w * scales).sum().reshape(1)])
             dv, de, dd = dv * scales[0], de * scales[1], dd * scales[2]
         ctx.save_for_backward(dv, de, dd)
-        ctx.mark_non_differentiable(losses)
-        return losses[3].clone(), losses
+        ctx.mark_non_differentiable(losses, col4row)
+        return losses[3].clone(), losses, col4row      # the assignment as solved: WireframeLoss.last_assignment
 
 
 class _LossFn(_TermsFn):
@@ -90,6 +96,7 @@ class WireframeLoss(nn.Module):
         self.smooth_l1_loss = nn.SmoothL1Loss()      # kept for attribute parity; not called
         self.bce_loss = nn.BCELoss()
         self._dp = (False, None)
+        self.last_assignment = None      # int32 [B, V] device tensor of the latest forward (module docstring)
 
     def set_data_parallel(self, enabled=True, group=None):
         """One process per GPU, batch sharded over ranks: rescale the three terms to the batch-wide normalisers
@@ -160,7 +167,7 @@ class WireframeLoss(nn.Module):
             ew = predictions.get("edge_width")        # padded edge head: the prediction width is a device scalar
             ew = ew.to(device=dev, dtype=torch.int64) if ew is not None else None
             scales = self._dp_scales(counts, B, V, pp.shape[1] if ew is None else ew, tl.shape[1], dev)
-            total, parts = _LossDevFn.apply(pv, pe, pp, tv, te, tl, counts, w, scales, ew)
+            total, parts, self.last_assignment = _LossDevFn.apply(pv, pe, pp, tv, te, tl, counts, w, scales, ew)
             return {"total_loss": total, "vertex_loss": parts[0], "existence_loss": parts[1], "edge_loss": parts[2]}
         matches = self._hungarian_matching(predictions, targets)
         lens = [len(m[0]) for m in matches]
@@ -168,8 +175,12 @@ class WireframeLoss(nn.Module):
         np.cumsum(lens, out=off[1:])
         n_match = int(off[-1])
         cat = lambda k: (np.concatenate([m[k] for m in matches]).astype(np.int32) if n_match else np.zeros(0, np.int32))   # noqa: E731
-        packed = torch.from_numpy(np.concatenate([cat(0), cat(1), off])).to(dev, non_blocking=True)
-        m_pred, m_tgt, m_off = packed[:n_match], packed[n_match:2 * n_match], packed[2 * n_match:]
+        col4row = np.full((B, V), V, dtype=np.int32)            # last_assignment: unmatched slots hold V
+        for b, (pi, ti) in enumerate(matches):
+            col4row[b, pi] = ti
+        packed = torch.from_numpy(np.concatenate([cat(0), cat(1), off, col4row.ravel()])).to(dev, non_blocking=True)
+        m_pred, m_tgt, m_off = packed[:n_match], packed[n_match:2 * n_match], packed[2 * n_match:2 * n_match + B + 1]
+        self.last_assignment = packed[2 * n_match + B + 1:].view(B, V)
         if predictions.get("edge_width") is not None:
             # padded edge head: this path has synced already, the width is read here and the columns past it dropped
             pp = pp[:, :int(predictions["edge_width"])]
