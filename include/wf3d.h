@@ -668,6 +668,53 @@ int wf3d_clip_adam_step_groups(float* const* params, float* const* grads, float*
                                double max_norm, int flags, int64_t* skipped, float* ws, size_t ws_floats,
                                float* total_norm, void* stream);
 
+/* The grouped step with averaged weights and the schedules' update count; every other argument is
+ * wf3d_clip_adam_step_groups' own, and with ema == NULL and schedule_step == NULL so are the launches and the bits.
+ * ema (NULL, or a host array of ntensors device pointers with NULL entries): tensor i's exponential moving average, fp32
+ * of numel[i] elements.  In the pass that stores the new parameter value p', ema' = fmaf(1 - d, p' - ema, ema) with
+ * d = ema_decay[group[i]] (host array of ngroups doubles in [0, 1); a tensor with an average needs d > 0) and 1 - d
+ * rounded once from double.  WF3D_ADAM_EMA_WARMUP: d = min(ema_decay, (1 + n) / (10 + n)), formed in double, where n is
+ * the tensor's Adam step before this update (capturable form: steps[i]; host form: step[k] - 1).  p, g, m, v and the
+ * norm are those of the step without the average, bit for bit; lr = 0 still moves the average; a skipped step leaves
+ * it alone; clip-only tensors have none.  An average costs 8 B per parameter on top of 32, and a launch with an ema
+ * table carries 40 tensors instead of 48 (the partial sums of the norm do not move).
+ * schedule_step (capturable form only, may be NULL): a device int64 that grows by one in a step that advances at least
+ * one Adam counter — not in a skipped step, not in a step of clip-only tensors alone — in the launch that advances
+ * those counters.  It is what wf3d_lr_schedule reads. */
+#define WF3D_ADAM_EMA_WARMUP 2
+int wf3d_clip_adam_step_ema(float* const* params, float* const* grads, float* const* exp_avg, float* const* exp_avg_sq,
+                            float* const* ema, const long* numel, const int* group, float* const* steps, int ntensors,
+                            const double* lr, const float* const* lr_dev, const double* beta1, const double* beta2,
+                            const double* eps, const double* weight_decay, const int* decoupled, const double* ema_decay,
+                            const int* step, int ngroups, double max_norm, int flags, int64_t* skipped,
+                            int64_t* schedule_step, float* ws, size_t ws_floats, float* total_norm, void* stream);
+
+/* Learning-rate schedules on the device: one launch, one thread per group, writes
+ * last_lr[k] = float(lr[k] * fw * fd) (formed in double, rounded once) for every group with write[k] != 0, from
+ * t = *schedule_step, the number of updates applied so far; the step entry points read it through lr_dev[k].  All
+ * tables are HOST arrays of ngroups (at most 16) entries; milestones has 8 per group, of which nmilestones[k] count.
+ *   fw = warmup_start + (1 - warmup_start) t / warmup_steps   for t < warmup_steps, else 1
+ *   u  = max(t - warmup_steps, 0),  T = decay_steps,  x = min(u, T) / T
+ *   fd = 1 (CONSTANT);  min_factor + (1 - min_factor) (1 + cos(pi x)) / 2 (COSINE);  1 + (min_factor - 1) x (LINEAR);
+ *        max(gamma^u, min_factor) (EXPONENTIAL);  gamma^(number of milestones <= u) (MULTISTEP)
+ * Past T, COSINE and LINEAR stay at min_factor.  warmup_steps 0 with CONSTANT is "no schedule": float(lr[k]).
+ * Refused with WF3D_ERR_ARG before the launch: warmup_steps < 0, decay_steps < 1 where COSINE or LINEAR read it,
+ * warmup_start or min_factor outside [0, 1], gamma outside (0, 1] where it is read, more than 8 or decreasing
+ * milestones, an unknown decay. */
+#define WF3D_LR_CONSTANT 0
+#define WF3D_LR_COSINE 1
+#define WF3D_LR_LINEAR 2
+#define WF3D_LR_EXPONENTIAL 3
+#define WF3D_LR_MULTISTEP 4
+int wf3d_lr_schedule(const double* lr, const long* warmup_steps, const double* warmup_start, const int* decay,
+                     const long* decay_steps, const double* min_factor, const double* gamma, const long* milestones,
+                     const int* nmilestones, const int* write, int ngroups, const int64_t* schedule_step, float* last_lr,
+                     void* stream);
+
+/* Parameters and averages change places, element for element: ntensors pairs of numel[i] fp32 values each (host
+ * tables of device pointers, no NULL entries).  Two calls are the identity, bit for bit.  Capturable. */
+int wf3d_ema_swap(float* const* params, float* const* ema, const long* numel, int ntensors, void* stream);
+
 /* ------------------------------------------------------------------------
  * Device-side dropout seeds (wf3d/random.py).  state = {key, counter} (uint64, device).  wf3d_dropout_draw: one thread
  * writes words[0..4] = s + k * 0x9E3779B9 (k = 0..4; words[k] for k >= 1 are EdgeFn's per-site seeds) with

@@ -72,3 +72,28 @@ def back_to_back_ms(fn, n=50):
 
 for name, o in (("one group", opt), ("two groups", two)):
     print(f"ClipAdam {name}: host {host_ms(o.step):.3f} ms, back to back {back_to_back_ms(o.step):.3f} ms per step")
+
+
+# The capturable grouped step on the same two groups, alone, with a schedule (one small launch more) and with averaged
+# weights (40 B per parameter instead of 32), alternated in one run; the plain arm's spread over the rounds is the
+# yardstick for the other two.  A report, not a gate.
+def capturable(**kw):
+    return ClipAdam([dict(params=[p for p in own if p.dim() > 1]), dict(params=[p for p in own if p.dim() <= 1], weight_decay=0.0)],
+                    lr=1e-3, weight_decay=1e-6, max_norm=1.0, norm_params=lambda: params, capturable=True, **kw)
+
+
+n_own = sum(p.numel() for p in own)
+arms = (("plain", capturable(), 32),
+        ("schedule", capturable(lr_schedule=dict(warmup_steps=500, warmup_start=0.01, decay="cosine", decay_steps=20000, min_factor=0.01)), 32),
+        ("ema", capturable(ema_decay=0.999, ema_warmup=True), 40))
+ms = {name: [] for name, _, _ in arms}
+for _ in range(5):
+    for name, o, _ in arms:
+        ms[name].append(timeit(o.step))
+for name, _, nbytes in arms:
+    best = statistics.median(ms[name])
+    print(f"capturable two groups, {name}: {best:.3f} ms (rounds {' '.join(f'{t:.3f}' for t in ms[name])}), "
+          f"{nbytes} B x {n_own} parameters -> {nbytes * n_own / best / 1e9:.2f} TB/s")
+spread = max(ms["plain"]) - min(ms["plain"])
+print(f"plain arm's spread over its rounds: {spread:.3f} ms; schedule - plain {statistics.median(ms['schedule']) - statistics.median(ms['plain']):+.3f} ms; "
+      f"ema - plain {statistics.median(ms['ema']) - statistics.median(ms['plain']):+.3f} ms")
