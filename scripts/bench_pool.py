@@ -1,5 +1,6 @@
 #!/usr/bin/env python3
-"""4-way pool forward / backward at cfg2 and cfg4 shapes: time and achieved HBM GB/s (csrc/pool.hip)."""
+"""4-way pool forward / backward at cfg2 and cfg4 shapes: time and achieved HBM GB/s (the training kernels of csrc/pool.hip; its streaming pool is
+timed inside scripts/bench_inference.py --path stream)."""
 import os, sys, statistics
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "wireframe-3d-prediction_amd"))

@@ -1,10 +1,13 @@
-"""A numpy model, in float64, of the device assignment solver of csrc/loss.hip: scipy's shortest-augmenting-path
+"""A numpy model, in float64, of the device assignment solvers (csrc/lsa_solve.h, csrc/loss.hip): scipy's shortest-augmenting-path
 algorithm with the kernels' own choices written out, so that a test can ask for the kernels' col4row element for
 element and not merely for an optimum.
 
-  square(C)        lsa_kernel (64 < V <= 1024) and lsa64_kernel<false> (V <= 64)
+  square(C)        lsa_kernel (64 < V <= 1024: lsa_rect_solve of lsa_solve.h on the square problem) and
+                   lsa64_kernel<false> (V <= 64)
   rect(C, count)   lsa64_kernel<true>: the rectangular shortcut over the real targets of a wireframe cost
   sanitise(C)      what every kernel's cost load does to a value that is not finite
+_augmenting_paths is also the model of lsa_rect_kernel (csrc/evalmetrics.hip), the same lsa_rect_solve on rectangular
+fp64 costs (tests/evalmetrics_model.py).
 
 The kernels' choices:
   * rows are added in order cur = 0 .. nrow-1;

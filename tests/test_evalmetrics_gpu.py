@@ -1,4 +1,4 @@
-"""Evaluation metrics on the device (csrc/evalmetrics.hip): wf3d_lsa_rect_batch against the numpy model
+"""Evaluation metrics on the device (csrc/evalmetrics.hip; the solver body is csrc/lsa_solve.h): wf3d_lsa_rect_batch against the numpy model
 (tests/evalmetrics_model.py) element for element and against scipy where the optimum is unique; then
 evaluate_batch(compact=True, metrics="device") against metrics="host" on the inputs of tests/test_evalmetrics_model.py —
 integer counters exact, `distance` and `wed` within rtol 1e-12 — and EvalLabels reuse."""

@@ -2,12 +2,12 @@
 
   lsa64_kernel<false>   square problem, V <= 64, state in registers
   lsa64_kernel<true>    rectangular shortcut over `counts`, V <= 64
-  lsa_kernel            64 < V <= 1024, state in LDS
+  lsa_kernel            64 < V <= 1024, state in LDS: lsa_rect_solve of csrc/lsa_solve.h on the square problem
 
 Each result must be a permutation, carry scipy's optimal total (equal where the costs are integers or dyadic, within
 1e-12 relative otherwise) and equal tests/lsa_model.py, the numpy statement of the kernels' algorithm and tie rule
 ("unassigned column first, then lowest index"), ELEMENT FOR ELEMENT — an optimum reached by another tie rule fails.
-Sizes sit on both sides of the wave width, of the 64-column trips of lsa_kernel and of the switch between kernels;
+Sizes sit on both sides of the wave width, of the 64-column trips of lsa_rect_solve and of the switch between kernels;
 inputs go beyond Gaussian costs: negative, badly scaled, tied (small integers, constant, rank one, lattice wireframes)
 and the product matrix (i+1)(j+1), whose augmenting paths run through every assigned row.
 

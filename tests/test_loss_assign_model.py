@@ -1,4 +1,4 @@
-"""tests/lsa_model.py, the numpy model of the device assignment solver (csrc/loss.hip), held to scipy on the CPU: on
+"""tests/lsa_model.py, the numpy model of the device assignment solver (csrc/lsa_solve.h, csrc/loss.hip), held to scipy on the CPU: on
 every cost generator of the device tests it returns a permutation of scipy's optimal total.  test_loss_assign_forms_gpu.py
 then asks the kernels for the model's assignment element for element, which pins their tie rule as well.
 

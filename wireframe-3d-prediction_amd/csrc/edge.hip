@@ -73,6 +73,17 @@ __global__ __launch_bounds__(256) void edge_layout_kernel(const int64_t* __restr
     for (int r = blockIdx.x * 256 + threadIdx.x; r < Re; r += stride) esample[r] = r < ne ? owner(eo, r) : -1;
 }
 
+// The forward-only edge head (wf3d.infer.edge_stream) walks the edge rows in blocks of `rows`; this cuts a layout's live
+// edge-row total into one count per block:  blive[k] = clamp(*total - k * rows, 0, min(rows, Re - k * rows)).
+__global__ __launch_bounds__(256) void block_live_kernel(const int32_t* __restrict__ total, int rows, int Re, int nblocks,
+                                                          int32_t* __restrict__ blive) {
+    const int k = blockIdx.x * 256 + threadIdx.x;
+    if (k >= nblocks) return;
+    const long r0 = (long)k * rows;
+    const long cap = max(0L, min((long)rows, (long)Re - r0));
+    blive[k] = (int32_t)min(max((long)*total - r0, 0L), cap);
+}
+
 // ---- vertex rows: gather counts[s] leading vertices of each sample ------------
 __global__ __launch_bounds__(256) void gather_verts_kernel(const float* __restrict__ verts, long s_stride, long v_stride,
                                                             const int32_t* __restrict__ voff,
@@ -428,6 +439,16 @@ extern "C" int wf3d_edge_layout(const int64_t* counts, int B, int V, int32_t* vo
     const int blocks = wf3d_cdiv(rows, 256), grid = blocks < 1 ? 1 : (blocks > 1024 ? 1024 : blocks);
     hipLaunchKernelGGL(edge_layout_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, counts, B, V, voff, eoff, vsample,
                        esample, counts_out, width);
+    WF3D_LAUNCH_CHECK();
+    return WF3D_OK;
+}
+
+extern "C" int wf3d_block_live(const int32_t* total, int rows, int Re, int nblocks, int32_t* blive, void* stream) {
+    WF3D_CHECK(rows > 0 && Re >= 0 && nblocks >= 0, WF3D_ERR_ARG, "wf3d_block_live: bad dims rows=%d Re=%d nblocks=%d", rows, Re, nblocks);
+    if (nblocks == 0) return WF3D_OK;
+    WF3D_CHECK(total && blive, WF3D_ERR_ARG, "wf3d_block_live: null pointer");
+    hipLaunchKernelGGL(block_live_kernel, dim3(wf3d_cdiv(nblocks, 256)), dim3(256), 0, (hipStream_t)stream, total, rows, Re,
+                       nblocks, blive);
     WF3D_LAUNCH_CHECK();
     return WF3D_OK;
 }

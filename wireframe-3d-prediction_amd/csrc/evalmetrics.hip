@@ -1,23 +1,17 @@
 // Evaluation metrics on the device: what eval/ap_calculator.py's compute_metrics derives from a sample's Hausdorff matrix
 // (APCalculator._with_edges / _corners_only), for a whole batch.  tests/evalmetrics_model.py states all of it in numpy.
 //
-//   lsa_rect_kernel       B rectangular assignment problems on fp64 costs, one wave per sample: lsa_kernel of loss.hip
-//                         (same algorithm, association and tie rule; tests/lsa_model.py::_augmenting_paths) with nrow <=
-//                         ncol, the matrix read through two strides so that the shorter side is the solver's rows without a
-//                         transposed copy.  State in LDS while the long side is <= 1024, else in the caller's workspace.
+//   lsa_rect_kernel       B rectangular assignment problems on fp64 costs, one wave per sample: the solver of
+//                         lsa_solve.h (shared with lsa_kernel of loss.hip; tests/lsa_model.py::_augmenting_paths) with
+//                         nrow <= ncol, the matrix read through two strides so that the shorter side is the solver's rows
+//                         without a transposed copy.  State in LDS while the long side is <= 1024, else in the caller's
+//                         workspace.  The solver terminates on any input (lsa_solve.h); a defect shows as WF3D_EVAL_STEPS.
 //   corner_sets_kernel    one workgroup per sample: the matched pairs under the threshold, the corner sets by VALUE (used
 //                         flags over the V predicted and the label vertices, O(k^2) duplicate flags and counting ranks for
 //                         np.unique / np.setdiff1d's lexicographic order), the free-corner distance matrix for the second
 //                         assignment, and e_term.
 //   finalize_kernel       one wave per sample: the second assignment's pairs in row order -> distances and the counters.
-//
-// Termination of the solver on any input: costs are read through lsa_cost64 (NaN, +-inf and anything beyond +-FLT_MAX
-// become +-FLT_MAX as doubles), so the argument in loss.hip's comment carries over: the duals stay finite, the first scan
-// of a search sets path[j] for every column, and the walk follows rows of this search's tree.  Independently of that
-// argument a search scans at most nrow rows and the walk takes at most nrow steps: a wrong kernel would give a wrong
-// answer and WF3D_EVAL_STEPS, never a hang.
-#include <float.h>
-
+#include "lsa_solve.h"
 #include "wf3d_common.h"
 
 namespace {
@@ -25,103 +19,6 @@ namespace {
 constexpr int LSA_LDS_LONG = 1024;          // long side up to which the solver state lies in LDS (41 bytes per column)
 constexpr int SETS_MAX = 1024;              // vertices per sample (predicted, label) of corner_sets_kernel
 constexpr int SETS_THREADS = 256;
-
-inline size_t lsa_state_bytes(long L) { return (size_t)((41 * L + 15) / 16 * 16); }
-
-__device__ __forceinline__ double lsa_cost64(double c, bool& bad) {
-    const double m = (double)FLT_MAX;
-    if (!(c <= m && c >= -m)) bad = true;                                // NaN fails both
-    return c < m ? (c > -m ? c : -m) : m;                                // NaN fails the first comparison
-}
-
-// cost(i, j) = C[i * rs + j * cs], nrow <= ncol.  State arrays are sized by ncol.  IN_LDS only separates the two call sites'
-// instantiations: in the one whose `base` is the LDS array the compiler keeps every state access an LDS instruction.
-template <bool IN_LDS>
-__device__ __forceinline__ int lsa_rect_solve(unsigned char* base, int* fail_s, const double* __restrict__ C, int nrow, int ncol,
-                                              long rs, long cs, int32_t* __restrict__ out) {
-    const long L = ncol;
-    double* u = reinterpret_cast<double*>(base);            // [nrow] row duals
-    double* v = u + L;                                      // [ncol] column duals
-    double* spc = v + L;                                    // [ncol] shortest path costs
-    int* path = reinterpret_cast<int*>(spc + L);            // [ncol]
-    int* row4col = path + L;                                // [ncol]
-    int* col4row = row4col + L;                             // [nrow]
-    int* srlist = col4row + L;                              // [nrow]
-    unsigned char* in_sc = reinterpret_cast<unsigned char*>(srlist + L);   // [ncol]
-    const int lane = threadIdx.x;
-    bool bad = false;
-    for (int j = lane; j < ncol; j += 64) { v[j] = 0.0; row4col[j] = -1; }
-    for (int i = lane; i < nrow; i += 64) { u[i] = 0.0; col4row[i] = -1; }
-    if (lane == 0) *fail_s = 0;
-    __syncthreads();
-    bool failed = false;
-    for (int cur = 0; cur < nrow && !failed; ++cur) {
-        for (int j = lane; j < ncol; j += 64) { spc[j] = INFINITY; in_sc[j] = 0; path[j] = -1; }
-        __syncthreads();
-        int i = cur, sink = -1, nsr = 0;
-        double min_val = 0.0;
-        while (sink < 0) {
-            if (nsr >= nrow) { failed = true; break; }                  // a search scans each row at most once
-            if (lane == 0) srlist[nsr] = i;
-            ++nsr;
-            const double ui = u[i];
-            double best = INFINITY;
-            int bestj = 0x7fffffff, best_free = 0;
-            for (int j = lane; j < ncol; j += 64) {
-                if (in_sc[j]) continue;
-                const double r = min_val + lsa_cost64(C[(long)i * rs + (long)j * cs], bad) - ui - v[j];
-                double cur_spc = spc[j];
-                if (r < cur_spc) { cur_spc = r; spc[j] = r; path[j] = i; }
-                const int fr = row4col[j] < 0;
-                if (cur_spc < best || (cur_spc == best && (fr > best_free || (fr == best_free && j < bestj)))) {
-                    best = cur_spc; bestj = j; best_free = fr;
-                }
-            }
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) {
-                const double ob = __shfl_xor(best, o, 64);
-                const int oj = __shfl_xor(bestj, o, 64), of = __shfl_xor(best_free, o, 64);
-                if (ob < best || (ob == best && (of > best_free || (of == best_free && oj < bestj)))) {
-                    best = ob; bestj = oj; best_free = of;
-                }
-            }
-            if (bestj < 0 || bestj >= ncol) { failed = true; break; }   // no unscanned column left: cannot happen before the bound
-            min_val = best;
-            if (lane == 0) in_sc[bestj] = 1;
-            __syncthreads();
-            const int r4c = row4col[bestj];
-            if (r4c < 0) sink = bestj; else i = r4c;
-        }
-        if (failed) break;
-        // dual update
-        for (int k = lane; k < nsr; k += 64) {
-            const int r = srlist[k];
-            u[r] += (r == cur) ? min_val : min_val - spc[col4row[r]];
-        }
-        for (int j = lane; j < ncol; j += 64)
-            if (in_sc[j]) v[j] -= min_val - spc[j];
-        __syncthreads();
-        // augment along the path (sequential), at most nrow steps
-        if (lane == 0) {
-            int j = sink, steps = 0;
-            while (true) {
-                const int r = (j >= 0 && j < ncol) ? path[j] : -1;
-                if (r < 0 || r >= nrow || steps >= nrow) { *fail_s = 1; break; }
-                ++steps;
-                row4col[j] = r;
-                const int prev = col4row[r];
-                col4row[r] = j;
-                j = prev;
-                if (r == cur) break;
-            }
-        }
-        __syncthreads();
-        failed = *fail_s != 0;
-    }
-    __syncthreads();
-    for (int p = lane; p < nrow; p += 64) out[p] = col4row[p];
-    return (failed ? WF3D_EVAL_STEPS : 0) | (__ballot(bad) != 0ull ? WF3D_EVAL_NONFINITE : 0);
-}
 
 __global__ __launch_bounds__(64) void lsa_rect_kernel(const double* __restrict__ cost, const int64_t* __restrict__ ooff,
                                                       const int32_t* __restrict__ noff, const int32_t* __restrict__ moff,
@@ -142,8 +39,8 @@ __global__ __launch_bounds__(64) void lsa_rect_kernel(const double* __restrict__
         const bool tr = n > m;                                           // the solver's rows are the shorter side
         const int nrow = (int)(tr ? m : n), ncol = (int)(tr ? n : m);
         const long rs = tr ? 1 : m, cs = tr ? m : 1;
-        if (ncol <= LSA_LDS_LONG) st = lsa_rect_solve<true>(lsm, &fail_s, C, nrow, ncol, rs, cs, out);
-        else st = lsa_rect_solve<false>(ws + (size_t)s * ws_stride, &fail_s, C, nrow, ncol, rs, cs, out);
+        if (ncol <= LSA_LDS_LONG) st = lsa_rect_solve<double, true, true>(lsm, &fail_s, C, nrow, ncol, rs, cs, out);
+        else st = lsa_rect_solve<double, false, true>(ws + (size_t)s * ws_stride, &fail_s, C, nrow, ncol, rs, cs, out);
     }
     if (lane == 0) status[s] = st;
 }

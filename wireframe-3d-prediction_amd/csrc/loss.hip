@@ -8,6 +8,7 @@
 // exactly the cotangents entering the hot path's backward.
 #include <cfloat>
 
+#include "lsa_solve.h"
 #include "wf3d_common.h"
 
 namespace {
@@ -163,93 +164,21 @@ __global__ void loss_final_kernel(const float* __restrict__ part, const int64_t*
 // those are unique whenever the optimum is.  tests/lsa_model.py states algorithm and tie rule in numpy; the kernels'
 // col4row equals it element for element (only additions and subtractions here: nothing contracts to an FMA).
 //
-// Non-finite costs.  All three kernels read the cost matrix through lsa_cost(): NaN and +inf become FLT_MAX, -inf
-// becomes -FLT_MAX, a finite value is unchanged.  That is what makes them terminate on any input: `r < spc` is false
-// for a NaN and for +inf against the initial +inf, so a raw row without a finite entry would leave path[j] unset for a
-// column that is still picked once only such columns remain, and the augmenting walk would then follow an unset entry
-// and never meet `r == cur`.  With finite costs every r of a row's first scan is finite (the duals are sums and
-// differences of finite costs, far below fp64's range) and less than the initial +inf, so the first scan sets path[j]
-// for every column; later scans only overwrite it with rows scanned in this same search.  Every path entry the walk
-// reads therefore names a row of this search's tree, each step moves one edge towards its root `cur`, and the walk ends
-// after at most V steps.  The result is always a permutation; a NaN in the model outputs then reaches the loss through
-// the term kernels, as it would in torch.
+// Non-finite costs.  All three kernels read the cost matrix clamped: NaN and +inf become FLT_MAX, -inf becomes
+// -FLT_MAX, a finite value is unchanged (lsa_cost here, lsa_cost64 in lsa_solve.h: the same function of a float).  That
+// is what makes them terminate on any input; lsa_solve.h gives the argument.  The result is always a permutation; a NaN
+// in the model outputs then reaches the loss through the term kernels, as it would in torch.
 // ---------------------------------------------------------------------------
 __device__ __forceinline__ float lsa_cost(float c) {
     return c < FLT_MAX ? (c > -FLT_MAX ? c : -FLT_MAX) : FLT_MAX;       // NaN fails the first comparison
 }
 
+// V > 64: the solver of lsa_solve.h on the square problem, state in LDS.  wf3d_loss_assign has no status output: the
+// solver's is dropped, and its guards are compiled out (lsa_solve.h says what they cost here).
 __global__ __launch_bounds__(64) void lsa_kernel(const float* __restrict__ cost, int V, int32_t* __restrict__ col4row_out) {
     extern __shared__ __attribute__((aligned(16))) unsigned char lsm[];
-    double* u = reinterpret_cast<double*>(lsm);            // [V] row duals
-    double* v = u + V;                                     // [V] column duals
-    double* spc = v + V;                                   // [V] shortest path costs
-    int* path = reinterpret_cast<int*>(spc + V);           // [V]
-    int* row4col = path + V;                               // [V]
-    int* col4row = row4col + V;                            // [V]
-    int* srlist = col4row + V;                             // [V]
-    unsigned char* in_sc = reinterpret_cast<unsigned char*>(srlist + V);   // [V]
-    const int lane = threadIdx.x, b = blockIdx.x;
-    const float* C = cost + (size_t)b * V * V;
-    for (int j = lane; j < V; j += 64) { u[j] = 0.0; v[j] = 0.0; row4col[j] = -1; col4row[j] = -1; }
-    __syncthreads();
-    for (int cur = 0; cur < V; ++cur) {
-        for (int j = lane; j < V; j += 64) { spc[j] = INFINITY; in_sc[j] = 0; }
-        __syncthreads();
-        int i = cur, sink = -1, nsr = 0;
-        double min_val = 0.0;
-        while (sink < 0) {
-            if (lane == 0) srlist[nsr] = i;
-            ++nsr;
-            const double ui = u[i];
-            double best = INFINITY;
-            int bestj = 0x7fffffff, best_free = 0;
-            for (int j = lane; j < V; j += 64) {
-                if (in_sc[j]) continue;
-                const double r = min_val + (double)lsa_cost(C[(size_t)i * V + j]) - ui - v[j];
-                double cur_spc = spc[j];
-                if (r < cur_spc) { cur_spc = r; spc[j] = r; path[j] = i; }
-                const int fr = row4col[j] < 0;
-                if (cur_spc < best || (cur_spc == best && (fr > best_free || (fr == best_free && j < bestj)))) {
-                    best = cur_spc; bestj = j; best_free = fr;
-                }
-            }
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) {
-                const double ob = __shfl_xor(best, o, 64);
-                const int oj = __shfl_xor(bestj, o, 64), of = __shfl_xor(best_free, o, 64);
-                if (ob < best || (ob == best && (of > best_free || (of == best_free && oj < bestj)))) {
-                    best = ob; bestj = oj; best_free = of;
-                }
-            }
-            min_val = best;
-            if (lane == 0) in_sc[bestj] = 1;
-            __syncthreads();
-            const int r4c = row4col[bestj];
-            if (r4c < 0) sink = bestj; else i = r4c;
-        }
-        // dual update
-        for (int k = lane; k < nsr; k += 64) {
-            const int r = srlist[k];
-            u[r] += (r == cur) ? min_val : min_val - spc[col4row[r]];
-        }
-        for (int j = lane; j < V; j += 64)
-            if (in_sc[j]) v[j] -= min_val - spc[j];
-        __syncthreads();
-        // augment along the path (sequential, wave-uniform)
-        if (lane == 0) {
-            int j = sink;
-            while (true) {
-                const int r = path[j];
-                row4col[j] = r;
-                const int prev = col4row[r];
-                col4row[r] = j;
-                j = prev;
-                if (r == cur) break;
-            }
-        }
-        __syncthreads();
-    }
-    for (int p = lane; p < V; p += 64) col4row_out[(size_t)b * V + p] = col4row[p];
+    const int b = blockIdx.x;
+    lsa_rect_solve<float, true, false>(lsm, nullptr, cost + (size_t)b * V * V, V, V, V, 1, col4row_out + (size_t)b * V);
 }
 
 // V <= 64: the whole solver state lives in registers — lane j owns column j (v_j, shortest-path cost, predecessor,
@@ -437,8 +366,7 @@ extern "C" int wf3d_loss_assign(const float* cost, int B, int V, int32_t* col4ro
     if (V <= 64) {
         hipLaunchKernelGGL(lsa64_kernel<false>, dim3(B), dim3(64), 0, (hipStream_t)stream, cost, (const int64_t*)nullptr, V, col4row);
     } else {
-        const size_t lds = (size_t)V * (3 * sizeof(double) + 4 * sizeof(int) + 1) + 16;
-        hipLaunchKernelGGL(lsa_kernel, dim3(B), dim3(64), lds, (hipStream_t)stream, cost, V, col4row);
+        hipLaunchKernelGGL(lsa_kernel, dim3(B), dim3(64), lsa_state_bytes(V), (hipStream_t)stream, cost, V, col4row);
     }
     WF3D_LAUNCH_CHECK();
     return WF3D_OK;

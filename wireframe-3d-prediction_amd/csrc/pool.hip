@@ -11,6 +11,10 @@
 // LDS tree; the N axis is split over blockIdx.y so that thousands of workgroups fill the chip, and a tiny second
 // kernel folds the splits.  Every fold keeps torch.max's first-max rule (equal values: the smaller n wins).
 // pool4_partial_kernel (any C): thread = channel, 4-byte loads — the fallback.
+//
+// Both row walks are templates on ARG, whether the arg-max rows are kept.  The training kernels (dense and segmented) are
+// the ARG instantiations; the forward-only streaming pool (wf3d.infer, below the packed layout) runs the same walks
+// without arg-max over the slices of a passing block of rows and folds them into a running state.
 #include "wf3d_common.h"
 
 namespace {
@@ -30,32 +34,66 @@ __global__ __launch_bounds__(256) void point_valid_kernel(const float* __restric
     valid[m] = s > 1e-9f ? 1.0f : 0.0f;
 }
 
-// The partial kernels' bodies work on one cloud: `pf` / `valid` point at its first row, n0..n1 are rows of that cloud (the
-// arg-max indices they record are local to it), `part` / `cnt_part` at the slot of this (cloud, range of rows).  The dense
-// kernels take the cloud and the range from the grid, the segmented ones (packed batches, below) from a chunk table.
+// The partial kernels' bodies work on one range of rows of one cloud: `pf` / `valid` point at a base row, n0..n1 are rows
+// from that base (the arg-max indices they record are those row numbers), `part` / `cnt_part` at the slot of this range.
+// The dense kernels take the cloud and the range from the grid (base = the cloud's first row), the segmented ones (packed
+// batches, below) from a chunk table, the streaming ones (further below) from a slice of the block that passes (base =
+// the block's first row).
+//
+// ARG: keep the arg-max rows (training: the backward scatter reads them).  The two forms also differ on a NaN, and each
+// keeps its rule as it was, since each is held to its own model by its own tests and a change is visible in the outputs:
+//   ARG    a row is taken as the maximum when `v > max || arg < 0`: the first row of a range is always taken, so a NaN
+//          there is taken and then sticks (no later `v > NaN` is true);
+//   !ARG   `v > max` from -inf: a NaN is never taken.
+// Making them one rule would change what one of the forms returns on such inputs; that is left to a change of its own.
+//
+// pool4_takes: whether a row's value v replaces the running maximum mx, whose row so far is arg (< 0: none yet; !ARG: unused).
+template <bool ARG>
+__device__ __forceinline__ bool pool4_takes(float v, float mx, int arg) {
+    return ARG ? (v > mx || arg < 0) : v > mx;
+}
+
+struct Pool1 { float msum, usum, mmax, umax, cnt; int am, au; };       // one channel over a range of rows (am, au: ARG)
+
+// the scalar walk: rows n0..n1 of channel c, in row order
+template <bool ARG>
+__device__ __forceinline__ Pool1 pool4_walk_rows(const float* __restrict__ pf, const float* __restrict__ valid, int n0, int n1,
+                                                 int C, int c) {
+    Pool1 a{0.f, 0.f, -INFINITY, -INFINITY, 0.f, -1, -1};
+    const float* p = pf + (size_t)n0 * C + c;
+    for (int n = n0; n < n1; ++n, p += C) {
+        const float v = *p;
+        const float ok = valid[n];
+        a.usum += v;
+        if (pool4_takes<ARG>(v, a.umax, a.au)) { a.umax = v; a.au = n; }
+        if (ok != 0.f) {
+            a.msum += v; a.cnt += 1.f;
+            if (pool4_takes<ARG>(v, a.mmax, a.am)) { a.mmax = v; a.am = n; }
+        }
+    }
+    return a;
+}
+
+// the partial record of one (range of rows, channel): with the arg-max rows for training, 16 bytes for the streaming pool
+__device__ __forceinline__ void pool4_store(PoolPart* p, float msum, float usum, float mmax, float umax, int am, int au) {
+    *p = PoolPart{msum, usum, mmax, umax, am, au};
+}
+__device__ __forceinline__ void pool4_store(f32x4* p, float msum, float usum, float mmax, float umax, int, int) {
+    *p = f32x4{msum, usum, mmax, umax};
+}
+
+template <bool ARG, typename Part>
 __device__ __forceinline__ void pool4_partial_rows(const float* __restrict__ pf, const float* __restrict__ valid,
                                                    int n0, int n1, int C,
-                                                   PoolPart* __restrict__ part, float* __restrict__ cnt_part) {
+                                                   Part* __restrict__ part, float* __restrict__ cnt_part) {
     const int c = blockIdx.x * 256 + threadIdx.x;
-    float msum = 0.f, usum = 0.f, mmax = -INFINITY, umax = -INFINITY, cnt = 0.f;
-    int am = -1, au = -1;
+    float cnt = 0.f;
     if (c < C) {
-        const float* p = pf + (size_t)n0 * C + c;
-        const float* vp = valid;
-        for (int n = n0; n < n1; ++n, p += C) {
-            const float v = *p;
-            const float ok = vp[n];
-            usum += v;
-            if (v > umax || au < 0) { umax = v; au = n; }
-            if (ok != 0.f) {
-                msum += v; cnt += 1.f;
-                if (v > mmax || am < 0) { mmax = v; am = n; }
-            }
-        }
-        PoolPart o{msum, usum, mmax, umax, am, au};
-        part[c] = o;
+        const Pool1 a = pool4_walk_rows<ARG>(pf, valid, n0, n1, C, c);
+        cnt = a.cnt;
+        pool4_store(part + c, a.msum, a.usum, a.mmax, a.umax, a.am, a.au);
     }
-    if (blockIdx.x == 0 && threadIdx.x == 0) *cnt_part = cnt;
+    if (blockIdx.x == 0 && threadIdx.x == 0) *cnt_part = cnt;          // channel 0 exists: every thread counts the same rows
 }
 
 __global__ __launch_bounds__(256) void pool4_partial_kernel(const float* __restrict__ pf, const float* __restrict__ valid,
@@ -64,52 +102,66 @@ __global__ __launch_bounds__(256) void pool4_partial_kernel(const float* __restr
     const int b = blockIdx.z, sp = blockIdx.y;
     const int n0 = sp * npb, n1 = min(N, n0 + npb);
     const size_t slot = (size_t)b * nsplit + sp;
-    pool4_partial_rows(pf + (size_t)b * N * C, valid + (size_t)b * N, n0, n1, C, part + slot * C, cnt_part + slot);
+    pool4_partial_rows<true>(pf + (size_t)b * N * C, valid + (size_t)b * N, n0, n1, C, part + slot * C, cnt_part + slot);
 }
 
-struct Pool4 {                 // running state of 4 channels
+template <bool ARG> struct Pool4;              // running state of 4 channels
+template <> struct Pool4<true> {
     f32x4 msum, usum, mmax, umax;
     int am[4], au[4];
 };
+template <> struct Pool4<false> { f32x4 msum, usum, mmax, umax; };
 
-// fold `o` into `a`; on equal maxima the smaller point index wins (torch.max returns the first maximum)
-__device__ __forceinline__ void pool4_merge(Pool4& a, const Pool4& o) {
+// fold `o` into `a`; ARG: on equal maxima the smaller point index wins (torch.max returns the first maximum)
+template <bool ARG>
+__device__ __forceinline__ void pool4_merge(Pool4<ARG>& a, const Pool4<ARG>& o) {
     a.msum += o.msum;
     a.usum += o.usum;
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
-        if (o.au[e] >= 0 && (a.au[e] < 0 || o.umax[e] > a.umax[e] || (o.umax[e] == a.umax[e] && o.au[e] < a.au[e]))) {
-            a.umax[e] = o.umax[e]; a.au[e] = o.au[e];
-        }
-        if (o.am[e] >= 0 && (a.am[e] < 0 || o.mmax[e] > a.mmax[e] || (o.mmax[e] == a.mmax[e] && o.am[e] < a.am[e]))) {
-            a.mmax[e] = o.mmax[e]; a.am[e] = o.am[e];
+        if constexpr (ARG) {
+            if (o.au[e] >= 0 && (a.au[e] < 0 || o.umax[e] > a.umax[e] || (o.umax[e] == a.umax[e] && o.au[e] < a.au[e]))) {
+                a.umax[e] = o.umax[e]; a.au[e] = o.au[e];
+            }
+            if (o.am[e] >= 0 && (a.am[e] < 0 || o.mmax[e] > a.mmax[e] || (o.mmax[e] == a.mmax[e] && o.am[e] < a.am[e]))) {
+                a.mmax[e] = o.mmax[e]; a.am[e] = o.am[e];
+            }
+        } else {
+            if (pool4_takes<false>(o.umax[e], a.umax[e], -1)) a.umax[e] = o.umax[e];
+            if (pool4_takes<false>(o.mmax[e], a.mmax[e], -1)) a.mmax[e] = o.mmax[e];
         }
     }
 }
 
-__device__ __forceinline__ Pool4 pool4_shfl_xor(const Pool4& a, int mask) {
-    Pool4 o;
+template <bool ARG>
+__device__ __forceinline__ Pool4<ARG> pool4_shfl_xor(const Pool4<ARG>& a, int mask) {
+    Pool4<ARG> o;
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
         o.msum[e] = __shfl_xor(a.msum[e], mask, 64); o.usum[e] = __shfl_xor(a.usum[e], mask, 64);
         o.mmax[e] = __shfl_xor(a.mmax[e], mask, 64); o.umax[e] = __shfl_xor(a.umax[e], mask, 64);
-        o.am[e] = __shfl_xor(a.am[e], mask, 64);     o.au[e] = __shfl_xor(a.au[e], mask, 64);
+        if constexpr (ARG) { o.am[e] = __shfl_xor(a.am[e], mask, 64); o.au[e] = __shfl_xor(a.au[e], mask, 64); }
     }
     return o;
 }
 
+// NT: read the rows with non-temporal loads (training: a pass over a tensor written long before); plain loads where the
+// rows were written just before (the streaming pool's block comes from the GEMM in front of it).
+template <bool ARG, bool NT, typename Part>
 __device__ __forceinline__ void pool4_partial_v4_rows(const float* __restrict__ pf, const float* __restrict__ valid,
                                                       int n0, int n1, int C,
-                                                      PoolPart* __restrict__ part, float* __restrict__ cnt_part) {
-    __shared__ Pool4 s_p[3][16];
+                                                      Part* __restrict__ part, float* __restrict__ cnt_part) {
+    __shared__ Pool4<ARG> s_p[3][16];
     __shared__ float s_cnt[4];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int rsub = lane >> 4, c = blockIdx.x * 64 + (lane & 15) * 4;
-    Pool4 a;
+    Pool4<ARG> a;
     a.msum = a.usum = f32x4{0.f, 0.f, 0.f, 0.f};
     a.mmax = a.umax = f32x4{-INFINITY, -INFINITY, -INFINITY, -INFINITY};
+    if constexpr (ARG) {
 #pragma unroll
-    for (int e = 0; e < 4; ++e) a.am[e] = a.au[e] = -1;
+        for (int e = 0; e < 4; ++e) a.am[e] = a.au[e] = -1;
+    }
     float cnt = 0.f;
     const float* base = pf + c;
     const float* vp = valid;
@@ -120,7 +172,11 @@ __device__ __forceinline__ void pool4_partial_v4_rows(const float* __restrict__ 
 #pragma unroll
         for (int u = 0; u < U; ++u) {
             const int nn = n + 16 * u;
-            if (nn < n1) { v[u] = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(base + (size_t)nn * C)); ok[u] = vp[nn]; }
+            if (nn < n1) {
+                const f32x4* q = reinterpret_cast<const f32x4*>(base + (size_t)nn * C);
+                v[u] = NT ? __builtin_nontemporal_load(q) : *q;
+                ok[u] = vp[nn];
+            }
         }
 #pragma unroll
         for (int u = 0; u < U; ++u) {
@@ -128,14 +184,20 @@ __device__ __forceinline__ void pool4_partial_v4_rows(const float* __restrict__ 
             if (nn < n1) {
                 a.usum += v[u];
 #pragma unroll
-                for (int e = 0; e < 4; ++e)
-                    if (v[u][e] > a.umax[e] || a.au[e] < 0) { a.umax[e] = v[u][e]; a.au[e] = nn; }
+                for (int e = 0; e < 4; ++e) {
+                    if constexpr (ARG) {
+                        if (pool4_takes<true>(v[u][e], a.umax[e], a.au[e])) { a.umax[e] = v[u][e]; a.au[e] = nn; }
+                    } else if (pool4_takes<false>(v[u][e], a.umax[e], -1)) a.umax[e] = v[u][e];
+                }
                 if (ok[u] != 0.f) {
                     a.msum += v[u];
                     cnt += 1.f;
 #pragma unroll
-                    for (int e = 0; e < 4; ++e)
-                        if (v[u][e] > a.mmax[e] || a.am[e] < 0) { a.mmax[e] = v[u][e]; a.am[e] = nn; }
+                    for (int e = 0; e < 4; ++e) {
+                        if constexpr (ARG) {
+                            if (pool4_takes<true>(v[u][e], a.mmax[e], a.am[e])) { a.mmax[e] = v[u][e]; a.am[e] = nn; }
+                        } else if (pool4_takes<false>(v[u][e], a.mmax[e], -1)) a.mmax[e] = v[u][e];
+                    }
                 }
             }
         }
@@ -154,8 +216,10 @@ __device__ __forceinline__ void pool4_partial_v4_rows(const float* __restrict__ 
         pool4_merge(a, s_p[1][lane]);
         pool4_merge(a, s_p[2][lane]);
 #pragma unroll
-        for (int e = 0; e < 4; ++e)
-            part[c + e] = PoolPart{a.msum[e], a.usum[e], a.mmax[e], a.umax[e], a.am[e], a.au[e]};
+        for (int e = 0; e < 4; ++e) {
+            if constexpr (ARG) pool4_store(part + c + e, a.msum[e], a.usum[e], a.mmax[e], a.umax[e], a.am[e], a.au[e]);
+            else pool4_store(part + c + e, a.msum[e], a.usum[e], a.mmax[e], a.umax[e], -1, -1);
+        }
         if (blockIdx.x == 0 && lane == 0) *cnt_part = s_cnt[0] + s_cnt[1] + s_cnt[2] + s_cnt[3];
     }
 }
@@ -166,7 +230,7 @@ __global__ __launch_bounds__(256) void pool4_partial_v4_kernel(const float* __re
     const int b = blockIdx.z, sp = blockIdx.y;
     const int n0 = sp * npb, n1 = min(N, n0 + npb);
     const size_t slot = (size_t)b * nsplit + sp;
-    pool4_partial_v4_rows(pf + (size_t)b * N * C, valid + (size_t)b * N, n0, n1, C, part + slot * C, cnt_part + slot);
+    pool4_partial_v4_rows<true, true>(pf + (size_t)b * N * C, valid + (size_t)b * N, n0, n1, C, part + slot * C, cnt_part + slot);
 }
 
 // folds the `nsplit` partial results of cloud b (N points), slots s0 .. s0 + nsplit - 1, in slot order
@@ -374,8 +438,8 @@ __global__ __launch_bounds__(256) void pool4_seg_partial_kernel(const float* __r
     const int k = blockIdx.y;
     if (chunks[4 * (size_t)k] < 0) return;                 // pad rows, or a dead entry of a capacity table: no cloud reads them
     const SegChunk s = seg_chunk(rows, chunks, k);
-    if (V4) pool4_partial_v4_rows(pf + s.row0 * C, valid + s.row0, s.n0, s.n1, C, part + (size_t)k * C, cnt_part + k);
-    else    pool4_partial_rows(pf + s.row0 * C, valid + s.row0, s.n0, s.n1, C, part + (size_t)k * C, cnt_part + k);
+    if (V4) pool4_partial_v4_rows<true, true>(pf + s.row0 * C, valid + s.row0, s.n0, s.n1, C, part + (size_t)k * C, cnt_part + k);
+    else    pool4_partial_rows<true>(pf + s.row0 * C, valid + s.row0, s.n0, s.n1, C, part + (size_t)k * C, cnt_part + k);
 }
 
 __global__ __launch_bounds__(256) void pool4_seg_final_kernel(const PoolPart* __restrict__ part,
@@ -505,6 +569,150 @@ __global__ __launch_bounds__(256) void packed_layout_kernel(const CountT* __rest
         *status = s_flags;                                 // every atomicOr precedes the second scan's barriers
     }
 }
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Streaming pool (forward only, wf3d.infer).  The per-point MLP runs over one block of rows [r0, r0 + rows) of the flat row
+// space at a time; the pools are a running state per (cloud, channel) that each block is folded into as it passes:
+//     state[b * C + c] = (masked sum, unmasked sum, masked max, unmasked max)      one 16-byte piece
+//     cnt[b]           = valid rows seen so far                                    behind the B * C pieces
+// The cloud of a row comes from the int32 device table of B + 1 row offsets (a packed layout's `rows`; b * N for a dense
+// batch), which only the kernels read.  A block may start and end anywhere.  It is cut into slices of `spr` rows:
+//   - pool4_stream_partial_kernel reduces every slice that lies inside ONE cloud to one partial per channel with the
+//     training kernels' row walks (!ARG: no arg-max is kept, nothing reads it without a backward);
+//   - pool4_stream_fold_kernel has ONE owner thread per (cloud, channel): it walks the slices that hold rows of its
+//     cloud in ascending row order and adds the slice's partial — or, for a slice that straddles a cloud boundary or the
+//     end of the live rows (at most two per cloud and block, `spr` rows each), the cloud's rows of that slice read
+//     directly — into the state.  No atomics: the summation order is a function of (offsets, r0, rows, C) alone.
+// Rows at or past offsets[B] belong to no cloud and are never read.
+// ---------------------------------------------------------------------------------------------------------------------
+// the cloud of row r < offsets[B]: the largest b with offsets[b] <= r (a cloud of no rows is never the answer)
+__device__ __forceinline__ int stream_cloud_of(const int32_t* __restrict__ offsets, int B, int r) {
+    int lo = 0, hi = B;                                    // offsets[lo] <= r < offsets[hi]
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (offsets[mid] <= r) lo = mid; else hi = mid;
+    }
+    return lo;
+}
+
+// Slice s of the block: rows [a, e) of the flat row space, cut at the end of the block and of the live rows.  `whole`:
+// the slice has rows and they are all one cloud's, so its partial exists.
+struct StreamSlice { int a, e, b; bool whole; };
+
+__device__ __forceinline__ StreamSlice stream_slice(const int32_t* __restrict__ offsets, int B, int r0, int rows, int spr, int s) {
+    StreamSlice q;
+    const long end = min((long)r0 + rows, (long)offsets[B]);
+    q.a = (int)min((long)r0 + (long)s * spr, (long)r0 + rows);
+    q.e = (int)max((long)q.a, min((long)q.a + spr, end));
+    q.b = -1;
+    q.whole = false;
+    if (q.e > q.a) {
+        q.b = stream_cloud_of(offsets, B, q.a);
+        q.whole = q.e <= offsets[q.b + 1];
+    }
+    return q;
+}
+
+// grid (C / 64 or ceil(C / 256), slices).  pf / valid point at row r0 (the block's first row).
+template <bool V4>
+__global__ __launch_bounds__(256) void pool4_stream_partial_kernel(const float* __restrict__ pf, const float* __restrict__ valid,
+                                                                    const int32_t* __restrict__ offsets, int B, int r0,
+                                                                    int rows, int spr, int C, f32x4* __restrict__ part,
+                                                                    float* __restrict__ cnt_part) {
+    const int s = blockIdx.y;
+    const StreamSlice q = stream_slice(offsets, B, r0, rows, spr, s);
+    if (!q.whole) return;                                  // the fold reads a straddling slice's rows itself
+    const int n0 = q.a - r0, n1 = q.e - r0;                // rows of the block
+    if (V4) pool4_partial_v4_rows<false, false>(pf, valid, n0, n1, C, part + (size_t)s * C, cnt_part + s);
+    else    pool4_partial_rows<false>(pf, valid, n0, n1, C, part + (size_t)s * C, cnt_part + s);
+}
+
+// grid (ceil(C / 256), B): thread = the owner of (cloud b, channel c)
+__global__ __launch_bounds__(256) void pool4_stream_fold_kernel(const float* __restrict__ pf, const float* __restrict__ valid,
+                                                                 const int32_t* __restrict__ offsets, int B, int r0, int rows,
+                                                                 int spr, int C, const f32x4* __restrict__ part,
+                                                                 const float* __restrict__ cnt_part, f32x4* __restrict__ state,
+                                                                 float* __restrict__ cnt_state) {
+    const int b = blockIdx.y;
+    const int c = blockIdx.x * 256 + threadIdx.x;
+    // the cloud's rows inside this block
+    const long lo = max((long)offsets[b], (long)r0), hi = min((long)offsets[b + 1], (long)r0 + rows);
+    if (hi <= lo) return;
+    if (c >= C) return;
+    const bool counts = c == 0;                            // channel 0's owner also owns the cloud's valid-row count
+    f32x4 st = state[(size_t)b * C + c];
+    float cnt = counts ? cnt_state[b] : 0.f;
+    const int s_first = (int)((lo - r0) / spr), s_last = (int)((hi - 1 - r0) / spr);
+    for (int s = s_first; s <= s_last; ++s) {
+        const long a = max(lo, (long)r0 + (long)s * spr), e = min(hi, (long)r0 + (long)(s + 1) * spr);
+        // the slice's partial exists when all its live rows are this cloud's (stream_slice, whole)
+        const long sa = (long)r0 + (long)s * spr, se = min(min(sa + spr, (long)r0 + rows), (long)offsets[B]);
+        if (a == sa && e == se) {
+            const f32x4 q = part[(size_t)s * C + c];
+            st[0] += q[0]; st[1] += q[1];
+            st[2] = q[2] > st[2] ? q[2] : st[2];
+            st[3] = q[3] > st[3] ? q[3] : st[3];
+            if (counts) cnt += cnt_part[s];
+        } else {
+            const Pool1 q = pool4_walk_rows<false>(pf, valid, (int)(a - r0), (int)(e - r0), C, c);
+            st[0] += q.msum; st[1] += q.usum;
+            st[2] = q.mmax > st[2] ? q.mmax : st[2];
+            st[3] = q.umax > st[3] ? q.umax : st[3];
+            cnt += q.cnt;
+        }
+    }
+    state[(size_t)b * C + c] = st;
+    if (counts) cnt_state[b] = cnt;
+}
+
+__global__ __launch_bounds__(256) void pool4_stream_init_kernel(f32x4* __restrict__ state, float* __restrict__ cnt_state,
+                                                                 long n, int B) {
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i < n) state[i] = f32x4{0.f, 0.f, -INFINITY, -INFINITY};
+    if (i < B) cnt_state[i] = 0.f;
+}
+
+// grid (ceil(C / 256), B): what pool4_final_cloud writes, without the arg-max rows
+__global__ __launch_bounds__(256) void pool4_stream_finish_kernel(const f32x4* __restrict__ state,
+                                                                   const float* __restrict__ cnt_state,
+                                                                   const int32_t* __restrict__ offsets, int C, int ldo,
+                                                                   float* __restrict__ mmax_o, float* __restrict__ mavg_o,
+                                                                   float* __restrict__ umean_o, float* __restrict__ umax_o,
+                                                                   float* __restrict__ cnt_o, float* __restrict__ nvalid_o) {
+    const int b = blockIdx.y;
+    const int c = blockIdx.x * 256 + threadIdx.x;
+    const float cnt = cnt_state[b];
+    const float cl = fmaxf(cnt, 1.0f);                      // clamp(min=1), PointNetEncoder.py:86
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        cnt_o[b] = cl;
+        if (nvalid_o) nvalid_o[b] = cnt;
+    }
+    if (c >= C) return;
+    const int N = offsets[b + 1] - offsets[b];
+    const f32x4 st = state[(size_t)b * C + c];
+    const size_t ov = (size_t)b * ldo + c;
+    // where(isfinite(max), max, 0): a cloud with no valid row pools to 0
+    mmax_o[ov] = (cnt > 0.f && isfinite(st[2])) ? st[2] : 0.f;
+    mavg_o[ov] = st[0] / cl;
+    // a cloud of no rows pools to zeros, as pool4_seg_fwd gives
+    umean_o[ov] = N > 0 ? st[1] / (float)N : 0.f;
+    umax_o[ov] = N > 0 ? st[3] : 0.f;
+}
+
+// Rows per slice of a block of `rows` rows: about 512 workgroups over column blocks x slices (two per CU at rows = 8192,
+// C = 512: 64 slices of 128 rows), a slice no shorter than 64 rows (32: thread-per-channel form) and a multiple of 16,
+// the rows of one pass of the 16-byte form.  A function of (rows, C) alone: so is the summation order.
+int stream_spr(int rows, int C) {
+    const bool v4 = C % 64 == 0;
+    const int cb = v4 ? C / 64 : wf3d_cdiv(C, 256);
+    int ns = 512 / cb;
+    const int cap = wf3d_cdiv(rows, v4 ? 64 : 32);
+    ns = ns > cap ? cap : ns;
+    ns = ns < 1 ? 1 : ns;
+    return wf3d_cdiv(wf3d_cdiv(rows, ns), 16) * 16;
+}
+
+size_t stream_part_bytes(int ns, int C) { return ((size_t)ns * C * sizeof(f32x4) + 255) & ~(size_t)255; }
 
 int packed_chunk_rows(int rows) {                          // wf3d.ops.PackedLayout: about 256 chunks, at least 256 rows each
     const int per = wf3d_cdiv(wf3d_cdiv(rows, 256), 64) * 64;
@@ -736,4 +944,69 @@ extern "C" int wf3d_packed_layout_build(const int64_t* counts, int B, int capaci
 extern "C" int wf3d_packed_layout_build_i32(const int32_t* counts, int B, int capacity, int32_t* rows, int32_t* cchunk,
                                             int32_t* chunks, int32_t* status, void* stream) {
     return packed_layout_build_impl(counts, B, capacity, rows, cchunk, chunks, status, stream);
+}
+
+// ---- streaming pool ----
+extern "C" size_t wf3d_pool4_stream_state_bytes(int B, int C) {
+    if (B <= 0 || C <= 0) return 0;
+    return (size_t)B * C * sizeof(f32x4) + (size_t)B * sizeof(float);
+}
+
+extern "C" int wf3d_pool4_stream_init(void* state, int B, int C, void* stream) {
+    WF3D_CHECK(B > 0 && C > 0 && B <= 65535, WF3D_ERR_ARG, "wf3d_pool4_stream_init: bad dims B=%d C=%d", B, C);
+    WF3D_CHECK(state && (uintptr_t)state % 16 == 0, WF3D_ERR_ARG, "wf3d_pool4_stream_init: null or misaligned state");
+    const long n = (long)B * C;
+    hipLaunchKernelGGL(pool4_stream_init_kernel, dim3(wf3d_cdiv(n, 256)), dim3(256), 0, (hipStream_t)stream, (f32x4*)state,
+                       (float*)((f32x4*)state + n), n, B);
+    WF3D_LAUNCH_CHECK();
+    return WF3D_OK;
+}
+
+extern "C" size_t wf3d_pool4_stream_ws_bytes(int rows, int C) {
+    if (rows <= 0 || C <= 0) return 0;
+    const int ns = wf3d_cdiv(rows, stream_spr(rows, C));
+    return stream_part_bytes(ns, C) + (size_t)ns * sizeof(float);
+}
+
+extern "C" int wf3d_pool4_stream(const float* pf, const float* valid, const int32_t* offsets, int B, int r0, int rows, int C,
+                                 void* state, void* ws, size_t ws_bytes, void* stream) {
+    WF3D_CHECK(B > 0 && C > 0 && B <= 65535 && r0 >= 0 && rows >= 0 && (long)r0 + rows <= 0x7FFFFFFFL, WF3D_ERR_ARG,
+               "wf3d_pool4_stream: bad dims B=%d C=%d r0=%d rows=%d", B, C, r0, rows);
+    if (rows == 0) return WF3D_OK;
+    WF3D_CHECK(pf && valid && offsets && state && (uintptr_t)state % 16 == 0, WF3D_ERR_ARG,
+               "wf3d_pool4_stream: null pointer or misaligned state");
+    WF3D_CHECK(ws && (uintptr_t)ws % 16 == 0 && ws_bytes >= wf3d_pool4_stream_ws_bytes(rows, C), WF3D_ERR_WS,
+               "wf3d_pool4_stream: workspace too small or misaligned");
+    const int spr = stream_spr(rows, C);
+    const int ns = wf3d_cdiv(rows, spr);
+    WF3D_CHECK(ns <= 65535, WF3D_ERR_UNSUPPORTED, "wf3d_pool4_stream: more than 65535 slices (rows=%d)", rows);
+    f32x4* part = (f32x4*)ws;
+    float* cnt_part = (float*)((char*)ws + stream_part_bytes(ns, C));
+    f32x4* st = (f32x4*)state;
+    float* cnt_state = (float*)(st + (size_t)B * C);
+    hipStream_t s = (hipStream_t)stream;
+    if (pool_v4(pf, C))
+        hipLaunchKernelGGL(pool4_stream_partial_kernel<true>, dim3(C / 64, ns), dim3(256), 0, s, pf, valid, offsets, B, r0, rows,
+                           spr, C, part, cnt_part);
+    else
+        hipLaunchKernelGGL(pool4_stream_partial_kernel<false>, dim3(wf3d_cdiv(C, 256), ns), dim3(256), 0, s, pf, valid, offsets,
+                           B, r0, rows, spr, C, part, cnt_part);
+    WF3D_LAUNCH_CHECK();
+    hipLaunchKernelGGL(pool4_stream_fold_kernel, dim3(wf3d_cdiv(C, 256), B), dim3(256), 0, s, pf, valid, offsets, B, r0, rows,
+                       spr, C, part, cnt_part, st, cnt_state);
+    WF3D_LAUNCH_CHECK();
+    return WF3D_OK;
+}
+
+extern "C" int wf3d_pool4_stream_finish(const void* state, const int32_t* offsets, int B, int C, float* mmax, float* mavg,
+                                        float* umean, float* umax, int ldo, float* cnt, float* nvalid, void* stream) {
+    WF3D_CHECK(ldo >= C, WF3D_ERR_ARG, "wf3d_pool4_stream_finish: ldo=%d < C=%d", ldo, C);
+    WF3D_CHECK(B > 0 && C > 0 && B <= 65535, WF3D_ERR_ARG, "wf3d_pool4_stream_finish: bad dims B=%d C=%d", B, C);
+    WF3D_CHECK(state && (uintptr_t)state % 16 == 0 && offsets && mmax && mavg && umean && umax && cnt, WF3D_ERR_ARG,
+               "wf3d_pool4_stream_finish: null pointer or misaligned state");
+    const f32x4* st = (const f32x4*)state;
+    hipLaunchKernelGGL(pool4_stream_finish_kernel, dim3(wf3d_cdiv(C, 256), B), dim3(256), 0, (hipStream_t)stream, st,
+                       (const float*)(st + (size_t)B * C), offsets, C, ldo, mmax, mavg, umean, umax, cnt, nvalid);
+    WF3D_LAUNCH_CHECK();
+    return WF3D_OK;
 }
