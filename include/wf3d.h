@@ -866,6 +866,33 @@ int wf3d_cloud_sample_dev(const double* norm, const long* first, int nclouds, co
 int wf3d_wireframe_targets(const double* wf_vertices, const int32_t* wf_edges, const long* vfirst, const long* efirst, int nclouds,
                            const void* params, int B, int V, float* vertices, float* vertex_existence, int64_t* vertex_counts,
                            float* edge_labels, void* stream);
+/* FARTHEST-POINT SAMPLING: wf3d_cloud_sample_dev's fixed-size batch — the same parameter block, word 0 of the same
+ * seed_words, both read in device memory at run time (a captured launch samples afresh on every replay), out_first
+ * ignored — with the rows chosen by distance: points[b, p, :] = fp32(augment(norm[first[cloud[b]] + idx(b, p), :])),
+ * idx(b, .) = wf3d.sampling.fps_indices(seed_words[0], b, xyz of cloud[b], P), bit for bit:
+ *     start    = mulhi(fmix32(key ^ 0xB5297A4D), n_b), the offset `a` of the random sampler: one start per (word, sample)
+ *     a round  = every row's d (+inf at first; -1 once picked) lowered to r = ((dx dx + dy dy) + dz dz) from the row just
+ *                picked where r < d, then the row of the largest d, the LOWEST index among equals; float64 on columns 0..2
+ *                of `norm` BEFORE the augmentation (flips and the z-rotation are isometries), every operation rounded on
+ *                its own, no fma.  A NaN r lowers nothing, so a row with non-finite coordinates is picked early.
+ *     idx(b, p) = order[p mod n_b] over min(n_b, P) rounds: a cloud shorter than P repeats its order cyclically.
+ * The flips and the rotation are wf3d_cloud_sample's (float64, one rounding) through wf3d_cloud_sample_dev's gather: C = 8
+ * moves 16 bytes per access (norm and points 16-byte aligned), other C take a row per lane.  idx_out: int32 [B, P] or
+ * NULL; receives idx(b, p).  Every element of points, and of idx_out when given, is written by plain stores of this one
+ * launch; a sample whose cloud index is outside 0 .. nclouds-1, whose cloud is empty or longer than max_rows is written
+ * as zeros, its idx_out row too.
+ * One workgroup per sample and no synchronisation between workgroups; P - 1 dependent rounds of one barrier each.
+ * max_rows: the rows of the longest resident cloud (the caller knows it; `first` is device memory).  It sizes the
+ * workgroup (256 threads up to 2048 rows, 512 up to 4096, else 1024); clouds of at most WF3D_FPS_REG_ROWS rows keep
+ * their coordinates and d in registers for all rounds.  max_rows above it: ws holds d and the order of the longer clouds,
+ * wf3d_cloud_sample_fps_ws_bytes(B, max_rows) bytes (0 up to WF3D_FPS_REG_ROWS), 8-byte aligned, and those clouds read
+ * their coordinates again every round — that tier is correct and NOT tuned.
+ * 1 <= B <= 4096, 1 <= P, B * P < 2^31, 1 <= max_rows < 2^31, else WF3D_ERR_ARG before any launch. */
+#define WF3D_FPS_REG_ROWS 8192
+size_t wf3d_cloud_sample_fps_ws_bytes(int B, long max_rows);
+int wf3d_cloud_sample_fps(const double* norm, const long* first, int nclouds, const void* params, const uint32_t* seed_words,
+                          int B, int P, int C, float* points, int32_t* idx_out, long max_rows, void* ws, size_t ws_bytes,
+                          void* stream);
 /* RESIDENT EPOCHS: the parameter block above and the seed words of wf3d_cloud_sample_dev, written ON THE DEVICE from
  * state = {uint64 key, uint64 t} (device memory, 8-byte aligned; t = the batches produced so far), so that a captured
  * graph of this launch and the launches above walks shuffled, rank-sharded, augmented epochs with no host work between

@@ -37,6 +37,13 @@ between events over --reps back-to-back replays.
 
     python scripts/bench_resident_batches.py --form epoch --batch-sizes 32 --num-points 4096 --out profiles/r18_epoch_batches.jsonl
 
+--sampler fps (both forms above): the sampled buffers choose their rows by farthest-point sampling
+(`sampled_buffers(..., sampler="fps")`, wf3d_cloud_sample_fps): min(n, P) - 1 dependent rounds per sample instead of one
+gather pass, so "sampler", "graph" and the replay arms then show what the fill costs; --longest makes every sample the
+longest fixture cloud (2,479 rows).  The GB/s figure of an FPS sampler says nothing: its time is rounds, not bytes.
+
+    python scripts/bench_resident_batches.py --form fixed --sampler fps --batch-sizes 32 --num-points 2560 --out profiles/r19_fps_batches.jsonl
+
 Prints one JSON line per batch size and appends them to --out.
 """
 import argparse
@@ -70,6 +77,11 @@ def fixture_dataset():
     order = np.argsort([os.path.basename(f) for f in ds.pc_files])
     ds.pc_files, ds.wireframe_files = [ds.pc_files[i] for i in order], [ds.wireframe_files[i] for i in order]
     return ds
+
+
+def batch_indices(B, ds, cache, args):
+    """the fixture clouds cycled to B samples, or (--longest) the longest of them B times"""
+    return [int(np.argmax(cache.n))] * B if args.longest else [i % len(ds) for i in range(B)]
 
 
 def rows_figure():
@@ -166,8 +178,8 @@ def run_fixed(B, ds, cache, dev, args):
     from wf3d.ops import _stream
     P = args.num_points
     ds.num_points = P
-    idxs = [i % len(ds) for i in range(B)]
-    buf = cache.sampled_buffers(B, V, P)
+    idxs = batch_indices(B, ds, cache, args)
+    buf = cache.sampled_buffers(B, V, P, sampler=args.sampler)
     np.random.seed(0)
     cache.stage(buf, idxs)
     cache.fill(buf)
@@ -210,12 +222,13 @@ def run_fixed(B, ds, cache, dev, args):
     dmed = blocks_of({"gather": timed(lambda: _lib.check(lib.wf3d_cloud_sample(
                           cache.norm.data_ptr(), cache.first.data_ptr(), ids.data_ptr(), choice.data_ptr(), aug.data_ptr(), B, P,
                           cache.ncol, out.data_ptr(), _stream()), "cloud_sample")),
-                      "sampler": timed(lambda: cache._sample(buf["params"], buf["sample_words"], out)),
+                      "sampler": timed(lambda: cache._sample(buf["params"], buf["sample_words"], out,
+                                                             buf if args.sampler == "fps" else None)),
                       "graph": timed(graph.replay)}, args.blocks, args.block_steps, args.warmup)
     nbytes = B * P * cache.ncol * 12
     b, r = summary(med["batch"]), summary(med["sampled"])
     dev_us = {k: summary(v, 2) for k, v in dmed.items()}
-    return {"bench": "sampled_batches", "B": B, "num_points": P, "columns": cache.ncol, "max_vertices": V,
+    return {"bench": "sampled_batches", "sampler": args.sampler, "B": B, "num_points": P, "columns": cache.ncol, "max_vertices": V,
             "cloud_rows": sorted(set(cache.n[i] for i in idxs)), "blocks": args.blocks, "steps_per_block": args.block_steps,
             "reps": args.reps, "batch_ms": b, "sampled_ms": r, "batch_over_sampled": round(b["median"] / r["median"], 2),
             "h2d_bytes_batch": B * P * 4 + 36 * B, "h2d_bytes_sampled": 40 * B + 4, "device_us": dev_us, "point_bytes": nbytes,
@@ -228,13 +241,13 @@ def run_epoch(B, ds, cache, dev, args):
     cache.fill_epoch with NOTHING else per batch, in one session and one alternation"""
     P = args.num_points
     ds.num_points = P
-    idxs = [i % len(ds) for i in range(B)]
-    members = [i % len(ds) for i in range(4 * B)]                  # four steps per epoch over the same clouds
+    idxs = batch_indices(B, ds, cache, args)
+    members = batch_indices(4 * B, ds, cache, args)                # four steps per epoch over the same clouds
     sampler = cache.epoch_sampler(B, members, seed=0)
     graphs, bufs = {}, {}
     np.random.seed(0)
     for name in ("sampled", "epoch"):
-        buf = bufs[name] = cache.sampled_buffers(B, V, P)
+        buf = bufs[name] = cache.sampled_buffers(B, V, P, sampler=args.sampler)
         fill = (lambda b=buf: cache.fill(b)) if name == "sampled" else (lambda b=buf: cache.fill_epoch(b, sampler))
         if name == "sampled":
             cache.stage(buf, idxs)
@@ -278,7 +291,8 @@ def run_epoch(B, ds, cache, dev, args):
     t = int(sampler.get_state()[1])
     cloud = cache._block_views(bufs["epoch"]["params"].cpu(), B)[1]
     s, e = summary(med["sampled"]), summary(med["epoch"])
-    return {"bench": "epoch_batches", "B": B, "num_points": P, "columns": cache.ncol, "max_vertices": V, "members": len(members),
+    return {"bench": "epoch_batches", "sampler": args.sampler, "B": B, "num_points": P, "columns": cache.ncol, "max_vertices": V,
+            "cloud_rows": sorted(set(cache.n[i] for i in idxs)), "members": len(members),
             "steps_per_epoch": sampler.steps_per_epoch, "blocks": args.blocks, "steps_per_block": args.block_steps, "reps": args.reps,
             "stage_replay_ms": s, "epoch_replay_ms": e, "stage_replay_over_epoch": round(s["median"] / e["median"], 2),
             "h2d_bytes_stage": 40 * B + 4, "h2d_bytes_epoch": 0, "host_draws_epoch": 0,
@@ -296,6 +310,8 @@ def main():
     ap.add_argument("--form", choices=("packed", "fixed", "epoch"), default="packed")
     ap.add_argument("--num-points", type=int, default=4096)
     ap.add_argument("--reps", type=int, default=20)
+    ap.add_argument("--sampler", choices=("device", "fps"), default="device", help="--form fixed / epoch: how the rows are chosen")
+    ap.add_argument("--longest", action="store_true", help="--form fixed / epoch: every sample is the longest fixture cloud")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "r06_resident_batches.jsonl"))
     args = ap.parse_args()
     dev = torch.device("cuda:0")

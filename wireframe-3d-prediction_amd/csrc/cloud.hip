@@ -20,6 +20,8 @@
 //   cloud_sample_dev kernels per fixed-size batch: cloud_sample_kernel's output with the random choice computed in the
 //                            kernel (wf3d/sampling.py) from a seed word in device memory and the same parameter block:
 //                            no per-point host data, capturable.
+//   cloud_fps_kernel         per fixed-size batch: the same output with the rows chosen by farthest-point sampling
+//                            (wf3d/sampling.py fps_indices), one workgroup per sample, the cloud in registers.
 //   cloud_epoch_params_kernel per batch of a resident epoch: WRITES that parameter block and the seed words — which clouds
 //                            (a keyed permutation per epoch, sharded over ranks), their augmentation, the row offsets —
 //                            from a 16-byte state in device memory, so nothing of a batch is made on the host.
@@ -244,6 +246,56 @@ __device__ __forceinline__ uint32_t sample_index(const SamplePlan& s, uint32_t p
     return x >= s.n ? x - s.n : x;
 }
 
+// The gather of the sampled forms (the random sampler below, farthest-point sampling behind it): output row `o` from
+// resident row `src` under sample b's flips and z-rotation, float64 and one rounding; zeros for a sample without a source.
+struct Augment { double fx, fy, c, sn; };
+__device__ __forceinline__ Augment sample_augment(const BatchParams& Q, int b, bool live) {
+    if (!live) return {1, 1, 1, 0};
+    return {Q.aug[b * 4], Q.aug[b * 4 + 1], Q.aug[b * 4 + 2], Q.aug[b * 4 + 3]};
+}
+
+// x c - y s and x s + y c with the operations cloud_sample_kernel's expressions compile to (the product with y rounded,
+// the one with x fused into the sum), written out: wherever the gather is inlined it gives that kernel's bits
+__device__ __forceinline__ void rotate_xy(const Augment& A, double u0, double u1, double& ox, double& oy) {
+#pragma clang fp contract(off)
+    const double x = A.fx * u0, y = A.fy * u1;
+    ox = fma(x, A.c, -(y * A.sn));
+    oy = fma(x, A.sn, y * A.c);
+}
+
+// C = 8: this lane's half of the row (cloud_pack8_kernel's layout), four fp32 as one 16-byte store
+__device__ __forceinline__ void gather_half_row8(const double* __restrict__ norm, bool live, long src, int half, const Augment& A,
+                                                 float* __restrict__ o) {
+    f32x4 v = {0.f, 0.f, 0.f, 0.f};
+    if (live) {
+        const f64x2* row = reinterpret_cast<const f64x2*>(norm + src * 8) + half * 2;
+        const f64x2 u = row[0], w = row[1];
+        if (half == 0) {
+            double x, y;
+            rotate_xy(A, u[0], u[1], x, y);
+            v = f32x4{(float)x, (float)y, (float)w[0], (float)w[1]};
+        } else {
+            v = f32x4{(float)u[0], (float)u[1], (float)w[0], (float)w[1]};
+        }
+    }
+    *reinterpret_cast<f32x4*>(o + half * 4) = v;
+}
+
+// any C: the whole row in one lane
+__device__ __forceinline__ void gather_row(const double* __restrict__ norm, bool live, long src, int C, const Augment& A,
+                                           float* __restrict__ o) {
+    if (!live) {
+        for (int k = 0; k < C; ++k) o[k] = 0.f;
+        return;
+    }
+    const double* row = norm + src * C;
+    double x, y;
+    rotate_xy(A, row[0], row[1], x, y);
+    o[0] = (float)x;
+    o[1] = (float)y;
+    for (int k = 2; k < C; ++k) o[k] = (float)row[k];
+}
+
 // C = 8, cloud_pack8_kernel's layout: two lanes per row, 16-byte accesses, consecutive lanes store consecutive 16 bytes.
 // A wave owns 64 output rows: lane l computes the index of row l ONCE, and the two passes of 32 rows fetch theirs with
 // one ds_bpermute each (from lane j * 32 + l / 2) — against computing every index in both lanes of its pair, this
@@ -261,25 +313,12 @@ __global__ __launch_bounds__(256) void cloud_sample_dev8_kernel(const double* __
     uint32_t idx = 0;
     if (live && wave_row + lane < P) idx = sample_index(s, (uint32_t)(wave_row + lane));
     const uint32_t idx0 = __shfl(idx, lane >> 1, 64), idx1 = __shfl(idx, 32 + (lane >> 1), 64);
-    const int half = lane & 1;
-    double fx = 1, fy = 1, c = 1, sn = 0;
-    if (live) { fx = Q.aug[b * 4]; fy = Q.aug[b * 4 + 1]; c = Q.aug[b * 4 + 2]; sn = Q.aug[b * 4 + 3]; }
+    const Augment A = sample_augment(Q, b, live);
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
         const long p = wave_row + j * 32 + (lane >> 1);
         if (p >= P) continue;
-        f32x4 o = {0.f, 0.f, 0.f, 0.f};
-        if (live) {
-            const f64x2* row = reinterpret_cast<const f64x2*>(norm + (s.r0 + (j ? idx1 : idx0)) * 8) + half * 2;
-            const f64x2 u = row[0], v = row[1];
-            if (half == 0) {
-                const double x = fx * u[0], y = fy * u[1];
-                o = f32x4{(float)(x * c - y * sn), (float)(x * sn + y * c), (float)v[0], (float)v[1]};
-            } else {
-                o = f32x4{(float)u[0], (float)u[1], (float)v[0], (float)v[1]};
-            }
-        }
-        *reinterpret_cast<f32x4*>(out + ((long)b * P + p) * 8 + half * 4) = o;
+        gather_half_row8(norm, live, live ? s.r0 + (j ? idx1 : idx0) : 0, lane & 1, A, out + ((long)b * P + p) * 8);
     }
 }
 
@@ -292,18 +331,185 @@ __global__ __launch_bounds__(256) void cloud_sample_dev_kernel(const double* __r
     const int b = blockIdx.y;
     const long p = (long)blockIdx.x * 256 + threadIdx.x;
     if (p >= P) return;
-    float* o = out + ((long)b * P + p) * C;
     SamplePlan s;
-    if (!sample_plan(Q, first, nclouds, seed_words, b, P, s)) {
-        for (int k = 0; k < C; ++k) o[k] = 0.f;
-        return;
+    const bool live = sample_plan(Q, first, nclouds, seed_words, b, P, s);
+    gather_row(norm, live, live ? s.r0 + sample_index(s, (uint32_t)p) : 0, C, sample_augment(Q, b, live), out + ((long)b * P + p) * C);
+}
+
+// ---- fixed-size batches by farthest-point sampling --------------------------------------------------------------------
+// wf3d/sampling.py fps_indices(seed_word, b, xyz, P), the specification: from the row fps_start (the random sampler's
+// offset a), L - 1 = min(n, P) - 1 dependent rounds of "lower every point's d to its squared distance from the row just
+// picked, take the largest d, the lowest index among equals".  One workgroup of T = 256, 512 or 1024 threads per sample,
+// nothing between workgroups.  Thread t owns the rows i = t, t + T, ...; a cloud of at most FPS_K * T rows keeps their
+// coordinates and d in registers for all rounds (the register tier), a longer one keeps d in the caller's workspace
+// and reads the coordinates again every round (correct, not tuned).  A round: the update and the thread's arg-max, a
+// butterfly over the wave, one candidate per wave — with its coordinates, so that the pick reaches every thread together
+// with the point — into one of TWO sets of LDS slots, ONE barrier, and every thread combines the T / 64 candidates.
+// Round r + 1 writes the other set, and a wave reaches round r + 2's stores only behind round r + 1's barrier, which every
+// wave passes after its reads of round r: no second barrier.  Every loop is bounded by P or n.
+constexpr int FPS_K = 8, FPS_MAX_WAVES = 16;
+static_assert(FPS_K == 8 && FPS_K * 64 * FPS_MAX_WAVES == WF3D_FPS_REG_ROWS, "the register tier's limit is the header's");
+struct FpsSlot { double d; int idx, pad; double x, y, z; };
+
+// r of the specification: every operation rounded on its own, in this association
+__device__ __forceinline__ double fps_dist(double x, double y, double z, double xs, double ys, double zs) {
+#pragma clang fp contract(off)
+    const double dx = x - xs, dy = y - ys, dz = z - zs;
+    const double xx = dx * dx, yy = dy * dy, zz = dz * dz;
+    const double xy = xx + yy;
+    return xy + zz;
+}
+
+// the arg-max of (d, i) over the wave, the lowest index among equal d, in every lane (no d is a NaN)
+__device__ __forceinline__ void fps_wave_max(double& d, int& i) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const double od = __shfl_xor(d, o, 64);
+        const int oi = __shfl_xor(i, o, 64);
+        if (od > d || (od == d && oi < i)) { d = od; i = oi; }
     }
-    const double* row = norm + (s.r0 + sample_index(s, (uint32_t)p)) * C;
-    const double fx = Q.aug[b * 4], fy = Q.aug[b * 4 + 1], c = Q.aug[b * 4 + 2], sn = Q.aug[b * 4 + 3];
-    const double x = fx * row[0], y = fy * row[1];
-    o[0] = (float)(x * c - y * sn);
-    o[1] = (float)(x * sn + y * c);
-    for (int k = 2; k < C; ++k) o[k] = (float)row[k];
+}
+
+// The register tier's round for a thread with KC live row slots (KC = ceil(n / T), block-uniform): straight-line code, so the
+// KC distance chains interleave.  A slot without a row (i >= n) holds d = -2, which no r lowers and no pick equals.
+template <int KC>
+__device__ __forceinline__ void fps_update(const double (&x)[FPS_K], const double (&y)[FPS_K], const double (&z)[FPS_K],
+                                           double (&d)[FPS_K], double xs, double ys, double zs, int pick, int tid, int T,
+                                           double& bd, int& bi) {
+#pragma unroll
+    for (int k = 0; k < KC; ++k) {
+        const int i = k * T + tid;
+        const double q = fps_dist(x[k], y[k], z[k], xs, ys, zs);
+        d[k] = i == pick ? -1.0 : (q < d[k] ? q : d[k]);
+        if (d[k] > bd) { bd = d[k]; bi = i; }                    // ascending i: the first of equals stays
+    }
+}
+
+// behind the round's barrier: the pick among the waves' candidates and its coordinates
+// (eight slots are read at once — independent LDS reads, one wait — and those of waves the workgroup does not have,
+// which nothing ever wrote, are masked out)
+__device__ __forceinline__ int fps_combine(const FpsSlot* __restrict__ slot, int W, double& xs, double& ys, double& zs) {
+    double d = -3.0;                                             // below every candidate: wave 0's is taken first
+    int i = 0x7FFFFFFF, at = 0;
+#pragma unroll
+    for (int g = 0; g < FPS_MAX_WAVES; g += 8) {                 // eight at a time: 24 registers beside the cloud's 64
+        if (g >= W) break;
+        double od[8];
+        int oi[8];
+#pragma unroll
+        for (int w = 0; w < 8; ++w) { od[w] = slot[g + w].d; oi[w] = slot[g + w].idx; }
+#pragma unroll
+        for (int w = 0; w < 8; ++w) {
+            const bool better = g + w < W && (od[w] > d || (od[w] == d && oi[w] < i));
+            d = better ? od[w] : d;
+            i = better ? oi[w] : i;
+            at = better ? g + w : at;
+        }
+    }
+    xs = slot[at].x; ys = slot[at].y; zs = slot[at].z;
+    return i;
+}
+
+__global__ __launch_bounds__(1024) void cloud_fps_kernel(const double* __restrict__ norm, const long* __restrict__ first,
+                                                          int nclouds, const void* __restrict__ params,
+                                                          const uint32_t* __restrict__ seed_words, int B, int P, int C, int shift,
+                                                          float* __restrict__ out, int* __restrict__ idx_out,
+                                                          double* __restrict__ ws_d, int* __restrict__ ws_order, long ws_rows) {
+    __shared__ FpsSlot slot[2][FPS_MAX_WAVES];
+    __shared__ int order_s[WF3D_FPS_REG_ROWS];
+    const BatchParams Q = batch_params(params, B);
+    const int b = blockIdx.x, tid = threadIdx.x, T = 1 << shift, lane = tid & 63, wave = tid >> 6, W = T >> 6;
+    SamplePlan s = {};
+    bool live = sample_plan(Q, first, nclouds, seed_words, b, P, s);
+    const bool in_regs = live && s.n <= (uint32_t)(FPS_K * T);
+    live = live && (in_regs || (long)s.n <= ws_rows);            // a cloud longer than the caller said: no room for its d
+    const int n = live ? (int)s.n : 1, L = n < P ? n : P;
+    int* order_w = ws_order + (long)b * ws_rows;                 // dereferenced by the workspace tier only
+    if (live) {
+        const double* cloud = norm + s.r0 * C;
+        int pick = (int)s.a;                                     // fps_start
+        double xs = cloud[(long)pick * C], ys = cloud[(long)pick * C + 1], zs = cloud[(long)pick * C + 2];
+        if (in_regs) {
+            double x[FPS_K], y[FPS_K], z[FPS_K], d[FPS_K];
+#pragma unroll
+            for (int k = 0; k < FPS_K; ++k) {
+                const int i = k * T + tid;
+                x[k] = y[k] = z[k] = 0.0;
+                d[k] = -2.0;                                     // no row: below every row, picked ones included
+                if (i < n) { x[k] = cloud[(long)i * C]; y[k] = cloud[(long)i * C + 1]; z[k] = cloud[(long)i * C + 2]; d[k] = HUGE_VAL; }
+            }
+            if (tid == 0) order_s[0] = pick;
+            const int kc = (n + T - 1) >> shift;
+            for (int r = 1; r < L; ++r) {
+                double bd = -2.0;
+                int bi = 0x7FFFFFFF;
+                switch (kc) {
+                    case 1: fps_update<1>(x, y, z, d, xs, ys, zs, pick, tid, T, bd, bi); break;
+                    case 2: fps_update<2>(x, y, z, d, xs, ys, zs, pick, tid, T, bd, bi); break;
+                    case 3: fps_update<3>(x, y, z, d, xs, ys, zs, pick, tid, T, bd, bi); break;
+                    case 4: fps_update<4>(x, y, z, d, xs, ys, zs, pick, tid, T, bd, bi); break;
+                    case 5: fps_update<5>(x, y, z, d, xs, ys, zs, pick, tid, T, bd, bi); break;
+                    case 6: fps_update<6>(x, y, z, d, xs, ys, zs, pick, tid, T, bd, bi); break;
+                    case 7: fps_update<7>(x, y, z, d, xs, ys, zs, pick, tid, T, bd, bi); break;
+                    default: fps_update<8>(x, y, z, d, xs, ys, zs, pick, tid, T, bd, bi); break;
+                }
+                fps_wave_max(bd, bi);
+                FpsSlot* mine = &slot[r & 1][wave];
+                if (lane == 0) { mine->d = bd; mine->idx = bi; }
+                const int ku = __builtin_amdgcn_readfirstlane(bi) >> shift;       // the wave's candidate is row ku of one lane
+                if ((bi & (T - 1)) == tid) {
+#pragma unroll
+                    for (int k = 0; k < FPS_K; ++k)
+                        if (k == ku) { mine->x = x[k]; mine->y = y[k]; mine->z = z[k]; }
+                }
+                __syncthreads();
+                pick = fps_combine(slot[r & 1], W, xs, ys, zs);
+                if (tid == 0) order_s[r] = pick;
+            }
+        } else {
+            double* dw = ws_d + (long)b * ws_rows;
+            for (long i = tid; i < n; i += T) dw[i] = HUGE_VAL;   // read back by this thread only
+            if (tid == 0) order_w[0] = pick;
+            for (int r = 1; r < L; ++r) {
+                double bd = -2.0;
+                int bi = 0x7FFFFFFF;
+                for (long i = tid; i < n; i += T) {
+                    double di = dw[i];
+                    if (i == pick) {
+                        dw[i] = di = -1.0;
+                    } else {
+                        const double q = fps_dist(cloud[i * C], cloud[i * C + 1], cloud[i * C + 2], xs, ys, zs);
+                        if (q < di) dw[i] = di = q;
+                    }
+                    if (di > bd) { bd = di; bi = (int)i; }
+                }
+                fps_wave_max(bd, bi);
+                if (lane == 0) {
+                    FpsSlot* mine = &slot[r & 1][wave];
+                    mine->d = bd; mine->idx = bi;
+                    if (bi < n) { mine->x = cloud[(long)bi * C]; mine->y = cloud[(long)bi * C + 1]; mine->z = cloud[(long)bi * C + 2]; }
+                }
+                __syncthreads();
+                pick = fps_combine(slot[r & 1], W, xs, ys, zs);
+                if (tid == 0) order_w[r] = pick;
+            }
+        }
+    }
+    __syncthreads();                                             // the order, for every thread (block-uniform: `live` is)
+    // the rows: idx(b, p) = order[p mod n], through cloud_sample_dev's gather
+    const Augment A = sample_augment(Q, b, live);
+    const long rows = (long)P << (C == 8 ? 1 : 0);               // C = 8: two lanes per row, consecutive lanes 16 bytes apart
+    for (long t = tid; t < rows; t += T) {
+        const long p = C == 8 ? t >> 1 : t;
+        int idx = 0;
+        if (live) {
+            const int q = (int)(p < n ? p : p % n);
+            idx = in_regs ? order_s[q] : order_w[q];
+        }
+        if (C == 8) gather_half_row8(norm, live, s.r0 + idx, (int)(t & 1), A, out + ((long)b * P + p) * 8);
+        else gather_row(norm, live, s.r0 + idx, C, A, out + ((long)b * P + p) * C);
+        if (idx_out && (C != 8 || (t & 1) == 0)) idx_out[(long)b * P + p] = idx;
+    }
 }
 
 // ---- epochs drawn on the device ---------------------------------------------------------------------------------------
@@ -506,6 +712,37 @@ extern "C" int wf3d_cloud_sample_dev(const double* norm, const long* first, int 
         hipLaunchKernelGGL(cloud_sample_dev_kernel, grid, dim3(256), 0, (hipStream_t)stream, norm, first, nclouds, params,
                            seed_words, B, P, C, points);
     }
+    WF3D_LAUNCH_CHECK();
+    return WF3D_OK;
+}
+
+// the workspace tier's d (float64) and order (int32) of max_rows rows per sample; nothing while every cloud fits the registers
+extern "C" size_t wf3d_cloud_sample_fps_ws_bytes(int B, long max_rows) {
+    if (B < 1 || max_rows <= WF3D_FPS_REG_ROWS) return 0;
+    return ((size_t)B * (size_t)max_rows * 12 + 15) & ~(size_t)15;
+}
+
+extern "C" int wf3d_cloud_sample_fps(const double* norm, const long* first, int nclouds, const void* params,
+                                     const uint32_t* seed_words, int B, int P, int C, float* points, int32_t* idx_out,
+                                     long max_rows, void* ws, size_t ws_bytes, void* stream) {
+    WF3D_CHECK(nclouds >= 1 && B >= 1 && B <= 4096 && P >= 1 && C >= 3 && C <= 16 && max_rows >= 1 && max_rows <= 0x7FFFFFFFL,
+               WF3D_ERR_ARG, "wf3d_cloud_sample_fps: bad dims");
+    WF3D_CHECK((long)B * P <= 0x7FFFFFFFL, WF3D_ERR_ARG, "wf3d_cloud_sample_fps: B * P must stay below 2^31");
+    WF3D_CHECK(norm && first && params && seed_words && points, WF3D_ERR_ARG, "wf3d_cloud_sample_fps: null pointer");
+    WF3D_CHECK(((uintptr_t)params & 7) == 0 && (((uintptr_t)seed_words | (uintptr_t)idx_out) & 3) == 0, WF3D_ERR_ARG,
+               "wf3d_cloud_sample_fps: params must be 8-byte aligned, seed_words and idx_out 4-byte aligned");
+    WF3D_CHECK(C != 8 || (((uintptr_t)norm | (uintptr_t)points) & 15) == 0, WF3D_ERR_ARG,
+               "wf3d_cloud_sample_fps: norm and points must be 16-byte aligned");
+    const size_t need = wf3d_cloud_sample_fps_ws_bytes(B, max_rows);
+    WF3D_CHECK(need == 0 || (ws && ws_bytes >= need && ((uintptr_t)ws & 7) == 0), WF3D_ERR_ARG,
+               "wf3d_cloud_sample_fps: workspace missing, misaligned or below wf3d_cloud_sample_fps_ws_bytes");
+    // the workgroup by the longest cloud: FPS_K rows per thread
+    const int shift = max_rows <= FPS_K * 256 ? 8 : (max_rows <= FPS_K * 512 ? 9 : 10);
+    const long ws_rows = need ? max_rows : 0;
+    double* ws_d = need ? (double*)ws : nullptr;
+    int* ws_order = need ? (int*)(ws_d + (size_t)B * (size_t)ws_rows) : nullptr;
+    hipLaunchKernelGGL(cloud_fps_kernel, dim3(B), dim3(1 << shift), 0, (hipStream_t)stream, norm, first, nclouds, params, seed_words,
+                       B, P, C, shift, points, idx_out, ws_d, ws_order, ws_rows);
     WF3D_LAUNCH_CHECK();
     return WF3D_OK;
 }

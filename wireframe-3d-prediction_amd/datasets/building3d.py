@@ -19,7 +19,8 @@ training targets) that read everything else from resident device memory.  `packe
 The fixed-size form without per-point host data: `cache.sampled_buffers` / `stage` / `fill` do the same for
 `[B, num_points, C]` batches whose rows are chosen IN the kernel (wf3d/sampling.py states the index function) under a seed
 word that `fill` draws on the device, so one captured step trains as the reference trains — random fixed-size subsets,
-flips, z-rotation; `cache.batch(indices, sampler="device")` is the same sampler for one batch.
+flips, z-rotation; `cache.batch(indices, sampler="device")` is the same sampler for one batch.  `sampler="fps"` in either
+chooses the rows by farthest-point sampling instead (wf3d/sampling.py `fps_indices`), in the same launches.
 
 Resident epochs: `cache.epoch_sampler` / `fill_epoch` replace `stage` by a kernel — which clouds a batch holds (a keyed
 permutation per epoch, sharded over ranks), the augmentation and the seed words come from a 16-byte state in device memory
@@ -33,6 +34,8 @@ from collections import defaultdict
 import numpy as np
 import torch
 from torch.utils.data import Dataset
+
+from wf3d._lib import DEFINES as _DEFINES
 
 
 def _read_xyz(path, ncols=None):
@@ -227,6 +230,8 @@ class Building3DReconstructionDataset(Dataset):
         return pc_files, wf_files
 
 
+FPS_REG_ROWS = _DEFINES["WF3D_FPS_REG_ROWS"]      # farthest-point sampling keeps clouds up to this many rows in registers
+SAMPLERS = ("numpy", "device", "fps")
 PARAM_BYTES = 40       # per sample in the parameter block of a packed batch: aug 4 doubles, cloud int32, out_first int32
 
 
@@ -287,6 +292,9 @@ class DeviceCloudCache:
 
         batch = cache.batch([3, 0, 7], sampler="device")
         buf = cache.sampled_buffers(B, max_vertices)   # points [B, num_points, C]; stage / fill as above, three launches
+
+    The same with the rows by farthest-point sampling (even coverage instead of the scanner's density; the seed word
+    picks the start row): `sampler="fps"` in both calls; `point_indices` holds the rows taken.
     """
 
     def __init__(self, dataset, device):
@@ -353,11 +361,14 @@ class DeviceCloudCache:
         reference's batches.  sampler="device": the rows are chosen in the kernel (wf3d_cloud_sample_dev,
         wf3d.sampling.choice_indices) under a seed word drawn from `sample_generator` and kept as `last_sample_words`
         (int32 [5] on the device, word 0) — the same distribution, another random stream; np.random then sees the
-        augmentation draws only (per sample flip-x, flip-y, angle), NO choice draws.  Every other key is the same."""
+        augmentation draws only (per sample flip-x, flip-y, angle), NO choice draws.  Every other key is the same.
+        sampler="fps": as "device", with the rows by farthest-point sampling (wf3d_cloud_sample_fps,
+        wf3d.sampling.fps_indices on the cloud's normalised xyz; the seed word picks the start row only), and one more
+        key, `point_indices` (int32 [B, num_points] on the device): the rows taken."""
         from wf3d import _lib
         from wf3d.ops import _stream
-        if sampler not in ("numpy", "device"):
-            raise ValueError(f"DeviceCloudCache.batch: sampler must be 'numpy' or 'device' (got {sampler!r})")
+        if sampler not in SAMPLERS:
+            raise ValueError(f"DeviceCloudCache.batch: sampler must be 'numpy' or 'device', or 'fps' (got {sampler!r})")
         if not self.ds.num_points:
             raise ValueError("DeviceCloudCache needs dataset.num_points (fixed-size batches)")
         ds, P = self.ds, self.ds.num_points
@@ -368,8 +379,8 @@ class DeviceCloudCache:
         if any(not 0 <= i < len(self.n) for i in indices):
             raise IndexError(f"DeviceCloudCache.batch: index out of range for {len(self.n)} clouds")
         B = len(indices)
-        if sampler == "device":
-            return self._batch_sampled(indices, P)
+        if sampler != "numpy":
+            return self._batch_sampled(indices, P, sampler)
         choice = np.empty((B, P), dtype=np.int32)
         aug = np.empty((B, 4), dtype=np.float64)
         items = []
@@ -390,11 +401,11 @@ class DeviceCloudCache:
         out["point_clouds"] = pcs
         return out
 
-    def _batch_sampled(self, indices, P):
-        """batch(..., sampler="device") behind its index checks"""
+    def _batch_sampled(self, indices, P, sampler):
+        """batch(..., sampler="device" or "fps") behind its index checks"""
         ds, B = self.ds, len(indices)
         if not 1 <= B <= 4096 or B * P > 0x7FFFFFFF:
-            raise ValueError(f"DeviceCloudCache.batch: sampler='device' needs 1 <= B <= 4096 and B * num_points < 2^31 (got {B} x {P})")
+            raise ValueError(f"DeviceCloudCache.batch: sampler={sampler!r} needs 1 <= B <= 4096 and B * num_points < 2^31 (got {B} x {P})")
         block = torch.empty(PARAM_BYTES * B + 4, dtype=torch.uint8)
         v_aug, v_cloud, v_first = self._block_views(block, B)
         v_cloud[:], v_first[:] = indices, np.arange(B + 1, dtype=np.int64) * P
@@ -406,14 +417,35 @@ class DeviceCloudCache:
         out = ds.collate_batch(items)
         pcs = torch.empty(B, P, self.ncol, dtype=torch.float32, device=self.device)
         self.last_sample_words = self.sample_generator.draw()
-        self._sample(block.to(self.device), self.last_sample_words, pcs)
+        fps = self._fps_tensors(B, P) if sampler == "fps" else {}
+        self._sample(block.to(self.device), self.last_sample_words, pcs, fps)
         out["point_clouds"] = pcs
+        if fps:
+            out["point_indices"] = fps["point_indices"]
         return out
 
-    def _sample(self, params, words, points):
+    def _fps_tensors(self, B, P):
+        """what farthest-point sampling writes beside the points: `point_indices` (int32 [B, P]: the rows taken), and
+        `fps_workspace` when a resident cloud is longer than FPS_REG_ROWS (the library allocates nothing)"""
+        from wf3d import _lib
+        out = {"point_indices": torch.zeros(B, P, dtype=torch.int32, device=self.device)}
+        nbytes = _lib.load().wf3d_cloud_sample_fps_ws_bytes(B, max(self.n))
+        if nbytes:
+            out["fps_workspace"] = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+        return out
+
+    def _sample(self, params, words, points, fps=None):
+        """the sampler's launch: the random sampler, or farthest-point sampling into `fps`' tensors (_fps_tensors)"""
         from wf3d import _lib
         from wf3d.ops import _stream
         B, P = points.shape[0], points.shape[1]
+        if fps:
+            ws = fps.get("fps_workspace")
+            _lib.check(_lib.load().wf3d_cloud_sample_fps(
+                self.norm.data_ptr(), self.first.data_ptr(), len(self.n), params.data_ptr(), words.data_ptr(), B, P, self.ncol,
+                points.data_ptr(), fps["point_indices"].data_ptr(), max(self.n), ws.data_ptr() if ws is not None else None,
+                ws.numel() if ws is not None else 0, _stream()), "cloud_sample_fps")
+            return
         _lib.check(_lib.load().wf3d_cloud_sample_dev(self.norm.data_ptr(), self.first.data_ptr(), len(self.n), params.data_ptr(),
                                                      words.data_ptr(), B, P, self.ncol, points.data_ptr(), _stream()), "cloud_sample_dev")
 
@@ -473,11 +505,17 @@ class DeviceCloudCache:
                 "params_host": torch.zeros(PARAM_BYTES * B + 4, dtype=torch.uint8).pin_memory(),
                 "params_copied": torch.cuda.Event()}
 
-    def sampled_buffers(self, B, max_vertices, num_points=None):
+    def sampled_buffers(self, B, max_vertices, num_points=None, sampler="device"):
         """Static device tensors of a captured step for FIXED-SIZE batches sampled on the device: `points`
         [B, P, C] (P = num_points or the data set's; the dense forward takes it as it is), train_targets' `vertices` /
         `vertex_existence` / `edge_labels` (full width) / `vertex_counts`, the parameter block `params` with its pinned
-        mirror `params_host`, and `sample_words` (int32 [5]: the seed words `fill` draws, word 0 is the batch's)."""
+        mirror `params_host`, and `sample_words` (int32 [5]: the seed words `fill` draws, word 0 is the batch's).
+        sampler="fps": the rows by farthest-point sampling (wf3d_cloud_sample_fps, wf3d.sampling.fps_indices) — the same
+        buffers plus "sampler": "fps", `point_indices` (int32 [B, P]: the rows taken) and, when a resident cloud is
+        longer than FPS_REG_ROWS, `fps_workspace`; stage / fill / fill_epoch dispatch on that key."""
+        if sampler not in SAMPLERS[1:]:
+            raise ValueError(f"DeviceCloudCache.sampled_buffers: sampler must be 'device' or 'fps' ('numpy' draws on the host: "
+                             f"batch()) (got {sampler!r})")
         B, V = operator.index(B), operator.index(max_vertices)
         P = operator.index(num_points or self.ds.num_points or 0)
         if P < 1:
@@ -487,6 +525,7 @@ class DeviceCloudCache:
                              f"(got {B}, {V}, {P})")
         dev = self.device
         f32 = dict(dtype=torch.float32, device=dev)
+        fps = dict(self._fps_tensors(B, P), sampler="fps") if sampler == "fps" else {}
         return {"points": torch.zeros(B, P, self.ncol, **f32),
                 "vertices": torch.zeros(B, V, 3, **f32),
                 "vertex_existence": torch.zeros(B, V, **f32),
@@ -495,7 +534,7 @@ class DeviceCloudCache:
                 "params": torch.zeros(PARAM_BYTES * B + 4, dtype=torch.uint8, device=dev),
                 "params_host": torch.zeros(PARAM_BYTES * B + 4, dtype=torch.uint8).pin_memory(),
                 "params_copied": torch.cuda.Event(),
-                "sample_words": torch.zeros(5, dtype=torch.int32, device=dev)}
+                "sample_words": torch.zeros(5, dtype=torch.int32, device=dev), **fps}
 
     def stage(self, buffers, indices):
         """Host only, outside any capture: check the batch against the buffers (IndexError / ValueError, nothing touched),
@@ -534,7 +573,8 @@ class DeviceCloudCache:
         from wf3d.ops import _stream
         B, V = buffers["vertices"].shape[0], buffers["vertices"].shape[1]
         if "sample_words" in buffers:
-            self._sample(buffers["params"], self.sample_generator.draw(out=buffers["sample_words"]), buffers["points"])
+            self._sample(buffers["params"], self.sample_generator.draw(out=buffers["sample_words"]), buffers["points"],
+                         buffers if buffers.get("sampler") == "fps" else None)
         else:
             self._pack(buffers["params"], B, buffers["points"].shape[0], buffers["points"], buffers["point_counts"])
         _lib.check(_lib.load().wf3d_wireframe_targets(
@@ -593,7 +633,7 @@ class DeviceCloudCache:
             sampler.world, sampler.rank, buffers["points"].shape[1] if sampled else 0, 1 if self.ds.augment else 0,
             buffers["params"].data_ptr(), words.data_ptr(), _stream()), "cloud_epoch_params")
         if sampled:
-            self._sample(buffers["params"], words, buffers["points"])
+            self._sample(buffers["params"], words, buffers["points"], buffers if buffers.get("sampler") == "fps" else None)
         else:
             self._pack(buffers["params"], B, buffers["points"].shape[0], buffers["points"], buffers["point_counts"])
         _lib.check(lib.wf3d_wireframe_targets(

@@ -24,7 +24,8 @@ same distribution of subsets, not the same subsets.
 All arithmetic is modulo 2^32 (the kernel's uint32); the only wide product is the multiply-high.  Limits: 1 <= n < 2^31,
 1 <= P.  "Uniform" is up to the 2^-32 granularity of the multiply-high (a relative bias below n / 2^32).
 
-Below it, the specification of the epoch sampler (cloud_epoch_params_kernel): `epoch_batch(key, t, D, B, world, rank)`.
+Below it, the specification of the epoch sampler (cloud_epoch_params_kernel): `epoch_batch(key, t, D, B, world, rank)`,
+and of farthest-point sampling (cloud_fps_kernel): `fps_indices(seed_word, b, xyz, P)`, the rows by distance.
 """
 import numpy as np
 
@@ -205,3 +206,66 @@ def epoch_batch(key, t, D, B, world=1, rank=0, augment=True):
     aug, angle = epoch_augmentation(key, e, g, augment)
     return {"epoch": e, "step": s, "slots": g, "order": epoch_order(key, e, D)[g], "aug": aug, "angle": angle,
             "seed_words": epoch_seed_words(key, t, world, rank)}
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Farthest-point sampling (csrc/cloud.hip, cloud_fps kernels): the rows of a fixed-size batch chosen by distance instead
+# of by chance.  One start point per (seed word, sample), then P - 1 dependent rounds of "lower every point's distance to
+# the picked set, take the farthest".  Specified bit for bit: float64, every operation rounded on its own (no fma), in
+# ONE association, and the lowest index among equal distances — so lattices and coincident points are determined too.
+# ---------------------------------------------------------------------------------------------------------------------
+def fps_start(seed_word, b, n):
+    """The first row sample `b` takes from a cloud of n rows under `seed_word`: mulhi(fmix32(key ^ 0xB5297A4D), n), the
+    offset `a` of choice_indices — uniform on [0, n)."""
+    n = int(n)
+    if not 1 <= n < 1 << 31:
+        raise ValueError(f"fps_start: needs 1 <= n < 2^31 (got n = {n})")
+    key = sample_keys([int(seed_word) & 0xFFFFFFFF], b)[0]
+    return int(mulhi(fmix32(key ^ _u(0xB5297A4D)), n)[0])
+
+
+def fps_order(xyz, start, L):
+    """int64 [L]: the first L rows of the farthest-point order of xyz (float64 [n, 3], 1 <= L <= n) from row `start`.
+
+    order[0] = start.  Every point carries d, +inf at first.  After picking s: d[s] = -1 (a picked point is never picked
+    again), and for every other i, r = ((x_i - x_s)^2 + (y_i - y_s)^2) + (z_i - z_s)^2 — each subtraction, product and
+    sum rounded to float64 on its own, in this association — and d[i] = r if r < d[i].  The next pick is the index of
+    the largest d, the LOWEST index among equals.  fps_order(xyz, start, n) is a permutation of [0, n), and a shorter
+    order is its prefix.
+
+    Non-finite coordinates: a NaN r never lowers a d (the comparison is false), so a point with a NaN or two infinities
+    of a kind keeps d = +inf until it is picked, which is early; while it is the picked point no d moves.  Every index
+    stays in range and the loop ends after L rounds whatever the input."""
+    xyz = np.ascontiguousarray(xyz, dtype=np.float64)
+    if xyz.ndim != 2 or xyz.shape[1] != 3:
+        raise ValueError(f"fps_order: xyz must be [n, 3] (got {xyz.shape})")
+    n, start, L = xyz.shape[0], int(start), int(L)
+    if not (1 <= L <= n and 0 <= start < n):
+        raise ValueError(f"fps_order: needs 1 <= L <= n and 0 <= start < n (got n = {n}, L = {L}, start = {start})")
+    x, y, z = xyz[:, 0].copy(), xyz[:, 1].copy(), xyz[:, 2].copy()
+    d = np.full(n, np.inf)
+    order = np.empty(L, dtype=np.int64)
+    s = start
+    with np.errstate(invalid="ignore", over="ignore"):
+        for k in range(L):
+            order[k] = s
+            if k + 1 == L:
+                break
+            d[s] = -1.0                    # r >= 0 or NaN: never below -1, a picked point stays picked
+            dx, dy, dz = x - x[s], y - y[s], z - z[s]
+            r = (dx * dx + dy * dy) + dz * dz
+            np.copyto(d, r, where=r < d)
+            s = int(np.argmax(d))          # the first of the largest: no d is a NaN
+    return order
+
+
+def fps_indices(seed_word, b, xyz, P):
+    """int64 [P]: the rows sample `b` of a batch takes from the cloud xyz (float64 [n, 3]) under farthest-point sampling
+    from fps_start(seed_word, b, n): idx[p] = order[p mod n], order = fps_order(xyz, start, min(n, P)) — a cloud shorter
+    than P repeats its order cyclically (this sampler's `replace = n < P`).  1 <= n < 2^31, P >= 1."""
+    xyz = np.asarray(xyz, dtype=np.float64)
+    n, P = xyz.shape[0], int(P)
+    if not (1 <= n < 1 << 31 and P >= 1):
+        raise ValueError(f"fps_indices: needs 1 <= n < 2^31 and P >= 1 (got n = {n}, P = {P})")
+    order = fps_order(xyz, fps_start(seed_word, b, n), min(n, P))
+    return order[np.arange(P) % n]
