@@ -611,6 +611,32 @@ int wf3d_loss_terms_assigned_ew(const float* verts, long sample_stride, long ver
                                 const int64_t* counts, int B, int V, float w_vertex, float w_exist, float w_edge,
                                 float* dverts, float* dexist, float* dedge, float* losses, void* ws, size_t ws_bytes,
                                 void* stream);
+/* wf3d_loss_terms_assigned (edge_width NULL) or _ew (edge_width given) with the class-balanced / focal edge element
+ *   L(p, t) = -( w t (1-p)^gamma max(log p, -100) + (1-t) p^gamma max(log1p(-p), -100) ),   w = edge_pos_weight > 0,
+ *   gamma = edge_focal_gamma >= 0 (anything else, NaN and inf included: WF3D_ERR_ARG),
+ * dedge its derivative (a clamp that binds has derivative 0), the normaliser unchanged (B x common width).  A side
+ * whose coefficient t or 1-t is exactly 0 is not evaluated, and a column with p == t == 0 or p == t == 1 (the padded
+ * columns of a ragged batch) contributes exactly 0 and gets gradient exactly 0 at every gamma.  At w = 1, gamma = 0 the
+ * call is the plain entry point itself: the same launches, the same bits. */
+int wf3d_loss_terms_assigned_bal(const float* verts, long sample_stride, long vertex_stride, const float* exist,
+                                 const float* edge, int Ep, const float* tverts, int Vt, const float* texist,
+                                 const float* tlabel, int Et, const int64_t* edge_width, const int32_t* col4row,
+                                 const int64_t* counts, int B, int V, float w_vertex, float w_exist, float w_edge,
+                                 float edge_pos_weight, float edge_focal_gamma, float* dverts, float* dexist, float* dedge,
+                                 float* losses, void* ws, size_t ws_bytes, void* stream);
+/* Edge labels that follow the matching.  Column k of a prediction row is the pair (p, q) of predicted slots, pair k of
+ * the pairs i < j < d_b in lexicographic order; tlabel [B, Et] holds sample b's labels in the pair order of its c_b
+ * ground-truth vertices (wf3d.targets.train_targets).  out [B, Ep]:
+ *   out[b, k] = tlabel[b, pair_index(min(tp, tq), max(tp, tq), c_b)]   for k < d_b(d_b-1)/2, tp = col4row[b, p] and
+ *               tq = col4row[b, q] both in [0, c_b) and different, and that index below Et;
+ *             = 0.0 in every other case, and in every column at or past d_b(d_b-1)/2.
+ * col4row int32 [B, V]: any assignment (wf3d_loss_assign's, or one with V or a negative value in unmatched slots);
+ * counts int64 [B] = c_b and pair_counts int64 [B] = d_b, each clamped to 0..V here; pair_counts NULL: d_b = c_b.
+ * One launch over (column chunks, B); every element of out is written exactly once, nothing is read on the host.
+ * wf3d.targets.matched_edge_labels states the function in numpy; the result equals it element for element.
+ * V <= 1024, B <= 65535, B * Ep and B * Et below 2^31 (else WF3D_ERR_UNSUPPORTED, nothing launched). */
+int wf3d_edge_labels_matched(const float* tlabel, int Et, const int32_t* col4row, const int64_t* counts,
+                             const int64_t* pair_counts, int B, int V, int Ep, float* out, void* stream);
 int wf3d_loss_terms(const float* verts, long sample_stride, long vertex_stride, const float* exist,
                     const float* edge, int Ep, const float* tverts, int Vt, const float* texist,
                     const float* tlabel, int Et, const int32_t* m_pred, const int32_t* m_tgt, const int32_t* m_off,

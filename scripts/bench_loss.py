@@ -35,10 +35,15 @@ print(f"cost matrix      {timeit(lambda: ops.loss_cost_matrix(pv.detach(), pec, 
 print(f"assignment (JV)  {timeit(lambda: ops.loss_assign(cost)):8.1f} us")
 c4r = ops.loss_assign(cost)
 print(f"terms + grads    {timeit(lambda: ops.loss_terms_assigned(pv.detach(), pec, pp.detach(), tgts['vertices'], tgts['vertex_existence'], tgts['edge_labels'], c4r, counts, (3.0, 1.0, 1.5))):8.1f} us")
-for mode in ("device", "scipy"):
-    crit = WireframeLoss(3.0, 1.5, 1.0, assignment=mode)
+us = timeit(lambda: ops.edge_labels_matched(tgts["edge_labels"], c4r, counts, E))
+print(f"matched labels   {us:8.1f} us  ({(2 * B * E + B * V) * 4 / us / 1e3:.0f} GB/s: labels read once, written once, assignment)")
+print(f"terms, balanced  {timeit(lambda: ops.loss_terms_assigned_bal(pv.detach(), pec, pp.detach(), tgts['vertices'], tgts['vertex_existence'], tgts['edge_labels'], c4r, counts, (3.0, 1.0, 1.5), 4.0, 2.0)):8.1f} us")
+VARIANTS = (("device", {}), ("scipy", {}), ("device", {"edge_targets": "matched"}),
+            ("device", {"edge_targets": "matched", "edge_pos_weight": 4.0, "edge_focal_gamma": 2.0}))
+for mode, kw in VARIANTS:
+    crit = WireframeLoss(3.0, 1.5, 1.0, assignment=mode, **kw)
     def full():
         for t in (pv, pe, pp):
             t.grad = None
         crit({"vertices": pv, "existence_probabilities": pe, "edge_probs": pp}, tgts)["total_loss"].backward()
-    print(f"WireframeLoss fwd+bwd, assignment={mode}: {timeit(full):8.1f} us")
+    print(f"WireframeLoss fwd+bwd, assignment={mode} {kw or ''}: {timeit(full):8.1f} us")

@@ -50,13 +50,45 @@ __device__ __forceinline__ float bce(float p, float t, float& g) {
     return -(t * fmaxf(logf(p), -100.0f) + (1.0f - t) * fmaxf(log1pf(-p), -100.0f));
 }
 
+// One side of the class-balanced edge element: v = x^gamma * max(log y, -100) with x = 1 - y (ly = log y as formed by the
+// caller), and dv/dy in dy.  x^(gamma - 1) is formed as x^gamma / x; at x = 0 that factor meets ly = log 1 = 0 and the
+// product's limit is 0, which is what is returned there instead of inf * 0.
+__device__ __forceinline__ float focal_side(float y, float x, float ly, float gamma, float& dy) {
+    const float xg = gamma > 0.f ? powf(x, gamma) : 1.0f;
+    const float l = fmaxf(ly, -100.0f);
+    dy = (ly > -100.0f ? xg / y : 0.f) - (gamma > 0.f && x > 0.f ? gamma * (xg / x) * l : 0.f);
+    return xg * l;
+}
+
+// The balanced / focal edge element (WireframeLoss(edge_pos_weight = w, edge_focal_gamma = gamma)):
+//   L = -(w t (1-p)^gamma max(log p, -100) + (1-t) p^gamma max(log1p(-p), -100)),  g = dL/dp of that expression
+// (the clamps have derivative 0 where they bind).  A side whose coefficient t or 1-t is exactly 0 is not evaluated, and a
+// probability that equals a hard label exactly (p = t = 0 or 1: the padded columns of a ragged batch) gives 0 and
+// gradient 0 at every gamma, as bce() does there.
+__device__ __forceinline__ float bce_bal(float p, float t, float w, float gamma, float& g) {
+    g = 0.f;
+    if (p == t && (t == 0.f || t == 1.f)) return 0.f;
+    float s = 0.f, d;
+    if (t != 0.f) {
+        s = w * t * focal_side(p, 1.0f - p, logf(p), gamma, d);
+        g = w * t * d;
+    }
+    if (t != 1.0f) {
+        s += (1.0f - t) * focal_side(1.0f - p, p, log1pf(-p), gamma, d);
+        g -= (1.0f - t) * d;                   // d/dp of a function of y = 1 - p
+    }
+    g = -g;
+    return -s;
+}
+
 // One workgroup per sample: partial sums of the three terms + all gradients.  The forms differ in the vertex term only:
 //   ASSIGNED = false  matches from host lists (the scipy path): m_a = m_pred, with m_tgt and m_off; gv = weight / normaliser
 //   ASSIGNED = true   the device assignment m_a = col4row: prediction p of sample b is matched iff col4row[b,p] < counts[b];
 //                     gv arrives as the vertex weight and is normalised here by the matches the counts add up to
 // The edge term runs over the common width min_e with the gradient scale gd (weight / normaliser, like ge); ewidth
 // non-NULL: the prediction width comes from the device, and min_e and gd are formed here from it and the edge weight we.
-template <bool ASSIGNED>
+// BAL: the edge element is bce_bal(pos_w, gamma) instead of bce(); the two arguments are not read otherwise.
+template <bool ASSIGNED, bool BAL = false>
 __global__ __launch_bounds__(256) void loss_terms_kernel(const float* __restrict__ verts, long vs_b, long vs_v,
                                                           const float* __restrict__ exist,
                                                           const float* __restrict__ edge, int Ep,
@@ -70,7 +102,8 @@ __global__ __launch_bounds__(256) void loss_terms_kernel(const float* __restrict
                                                           float gv, float ge, float gd,
                                                           float* __restrict__ dverts, float* __restrict__ dexist,
                                                           float* __restrict__ dedge, float* __restrict__ part,
-                                                          const int64_t* __restrict__ ewidth, float we) {
+                                                          const int64_t* __restrict__ ewidth, float we, float pos_w,
+                                                          float gamma) {
     __shared__ float red[4];
     const int b = blockIdx.x, tid = threadIdx.x;
     if (ewidth) {
@@ -126,7 +159,10 @@ __global__ __launch_bounds__(256) void loss_terms_kernel(const float* __restrict
     float sd = 0.f;
     for (int i = tid; i < Ep; i += 256) {
         float g = 0.f;
-        if (i < min_e) sd += bce(edge[(size_t)b * Ep + i], tlabel[(size_t)b * Et + i], g);
+        if (i < min_e) {
+            const float p = edge[(size_t)b * Ep + i], t = tlabel[(size_t)b * Et + i];
+            sd += BAL ? bce_bal(p, t, pos_w, gamma, g) : bce(p, t, g);
+        }
         dedge[(size_t)b * Ep + i] = gd * g;
     }
     sv = block_sum(sv, red); se = block_sum(se, red); sd = block_sum(sd, red);
@@ -291,6 +327,7 @@ struct LossMatch {
     int n_match;
     const int32_t* col4row;
     const int64_t *counts, *ewidth;
+    float pos_w = 1.0f, gamma = 0.0f;      // the edge element: (1, 0) is bce(), anything else bce_bal() (device assignment only)
 };
 }  // namespace
 
@@ -310,10 +347,12 @@ static int loss_terms_run(const char* fn, const LossMatch& ms, bool own_ptrs, co
     // the vertex gradient scale: the lists' is formed here, the assignment's on the device from the weight
     const float gv = ms.counts ? w_vertex : (ms.n_match ? w_vertex / nv : 0.f);
     hipStream_t st = (hipStream_t)stream;
-    auto terms = ms.counts ? &loss_terms_kernel<true> : &loss_terms_kernel<false>;
+    const bool bal = ms.pos_w != 1.0f || ms.gamma != 0.0f;
+    auto terms = bal ? &loss_terms_kernel<true, true> : ms.counts ? &loss_terms_kernel<true> : &loss_terms_kernel<false>;
     hipLaunchKernelGGL(terms, dim3(B), dim3(256), 0, st, verts, sample_stride, vertex_stride, exist, edge, Ep, tverts, Vt,
                        texist, tlabel, Et, min_e, ms.counts ? ms.col4row : ms.m_pred, ms.m_tgt, ms.m_off, ms.counts, V, B, gv,
-                       w_exist / ne, min_e ? w_edge / nd : 0.f, dverts, dexist, dedge, (float*)ws, ms.ewidth, w_edge);
+                       w_exist / ne, min_e ? w_edge / nd : 0.f, dverts, dexist, dedge, (float*)ws, ms.ewidth, w_edge,
+                       ms.pos_w, ms.gamma);
     WF3D_LAUNCH_CHECK();
     auto fin = ms.counts ? &loss_final_kernel<true> : &loss_final_kernel<false>;
     hipLaunchKernelGGL(fin, dim3(1), dim3(1), 0, st, (const float*)ws, ms.counts, B, V, nv, ne, nd, w_vertex,
@@ -356,6 +395,97 @@ extern "C" int wf3d_loss_terms_assigned_ew(const float* verts, long sample_strid
     return loss_terms_run("wf3d_loss_terms_assigned_ew", LossMatch{nullptr, nullptr, nullptr, 0, col4row, counts, edge_width},
                           col4row && counts && edge_width, verts, sample_stride, vertex_stride, exist, edge, Ep, tverts, Vt, texist,
                           tlabel, Et, B, V, w_vertex, w_exist, w_edge, dverts, dexist, dedge, losses, ws, ws_bytes, stream);
+}
+
+extern "C" int wf3d_loss_terms_assigned_bal(const float* verts, long sample_stride, long vertex_stride, const float* exist,
+                                            const float* edge, int Ep, const float* tverts, int Vt, const float* texist,
+                                            const float* tlabel, int Et, const int64_t* edge_width, const int32_t* col4row,
+                                            const int64_t* counts, int B, int V, float w_vertex, float w_exist, float w_edge,
+                                            float edge_pos_weight, float edge_focal_gamma, float* dverts, float* dexist,
+                                            float* dedge, float* losses, void* ws, size_t ws_bytes, void* stream) {
+    // negated comparisons: NaN is refused too
+    WF3D_CHECK(edge_pos_weight > 0.f && edge_pos_weight <= FLT_MAX && edge_focal_gamma >= 0.f && edge_focal_gamma <= FLT_MAX,
+               WF3D_ERR_ARG, "wf3d_loss_terms_assigned_bal: edge_pos_weight must be a finite number > 0 and edge_focal_gamma one >= 0");
+    WF3D_CHECK(!edge_width || Et <= 0 || tlabel, WF3D_ERR_ARG, "wf3d_loss_terms_assigned_bal: null edge labels");
+    return loss_terms_run("wf3d_loss_terms_assigned_bal",
+                          LossMatch{nullptr, nullptr, nullptr, 0, col4row, counts, edge_width, edge_pos_weight, edge_focal_gamma},
+                          col4row && counts, verts, sample_stride, vertex_stride, exist, edge, Ep, tverts, Vt, texist, tlabel, Et,
+                          B, V, w_vertex, w_exist, w_edge, dverts, dexist, dedge, losses, ws, ws_bytes, stream);
+}
+
+// ---------------------------------------------------------------------------
+// Matched edge labels (WireframeLoss(edge_targets="matched")).  Column k of a prediction row is the pair (p, q) of
+// predicted SLOTS; the labels arrive per pair (i, j) of ground-truth vertices.  out[b, k] = the label of the pair of
+// targets that slots p and q are matched to, 0 where either is unmatched; wf3d.targets.matched_edge_labels states it in
+// numpy and the kernel equals it element for element.  Grid (column chunks, B): a sample's row is cut into chunks of
+// ELM_COLS columns, each workgroup stages the sample's assignment row in LDS (<= 4 KiB) and writes its chunk once.
+// ---------------------------------------------------------------------------
+namespace {
+constexpr int ELM_COLS = 512;      // columns per workgroup, two per thread
+
+// pair k of the pairs i < j < d in lexicographic order, 0 <= k < d(d-1)/2, d <= 1024: (2d-1)^2 - 8k is an integer in
+// 1 .. 2^24, so its fp32 square root is off by less than one unit and one integer step either way mends the estimate
+__device__ __forceinline__ void pair_unrank(int k, int d, int& p, int& q) {
+    const int b = 2 * d - 1;
+    int i = (int)(((float)b - sqrtf((float)(b * b - 8 * k))) * 0.5f);
+    i = max(0, min(i, d - 2));
+    if (edge_offset(i + 1, d) <= k) ++i;
+    else if (edge_offset(i, d) > k) --i;
+    p = i;
+    q = k - edge_offset(i, d) + i + 1;
+}
+
+__global__ __launch_bounds__(256) void edge_labels_matched_kernel(const float* __restrict__ tlabel, int Et,
+                                                                   const int32_t* __restrict__ col4row,
+                                                                   const int64_t* __restrict__ counts,
+                                                                   const int64_t* __restrict__ pair_counts, int V, int Ep,
+                                                                   float* __restrict__ out) {
+    __shared__ int32_t tgt[1024];      // slot -> matched target, -1 for none
+    const int b = blockIdx.y, tid = threadIdx.x;
+    const int c = (int)min(max(counts[b], (int64_t)0), (int64_t)V);
+    const int d = pair_counts ? (int)min(max(pair_counts[b], (int64_t)0), (int64_t)V) : c;
+    for (int p = tid; p < d; p += 256) {
+        const int t = col4row[(size_t)b * V + p];
+        tgt[p] = t >= 0 && t < c ? t : -1;
+    }
+    __syncthreads();
+    const int npair = d * (d - 1) / 2;
+    const float* tl = tlabel + (size_t)b * Et;
+    const long k0 = (long)blockIdx.x * ELM_COLS;
+#pragma unroll
+    for (int it = 0; it < ELM_COLS / 256; ++it) {
+        const long k = k0 + it * 256 + tid;
+        if (k >= Ep) break;
+        float v = 0.f;
+        if (k < npair) {
+            int p, q;
+            pair_unrank((int)k, d, p, q);
+            const int tp = tgt[p], tq = tgt[q];
+            if (tp >= 0 && tq >= 0 && tp != tq) {
+                const int lo = min(tp, tq), hi = max(tp, tq);
+                const int idx = edge_offset(lo, c) + (hi - lo - 1);
+                if (idx < Et) v = tl[idx];
+            }
+        }
+        out[(size_t)b * Ep + k] = v;
+    }
+}
+}  // namespace
+
+extern "C" int wf3d_edge_labels_matched(const float* tlabel, int Et, const int32_t* col4row, const int64_t* counts,
+                                        const int64_t* pair_counts, int B, int V, int Ep, float* out, void* stream) {
+    WF3D_CHECK(B >= 0 && V > 0 && Ep >= 0 && Et >= 0, WF3D_ERR_ARG,
+               "wf3d_edge_labels_matched: bad dims (B %d, V %d, Ep %d, Et %d)", B, V, Ep, Et);
+    WF3D_CHECK(V <= 1024, WF3D_ERR_UNSUPPORTED, "wf3d_edge_labels_matched: V > 1024 (got %d)", V);
+    WF3D_CHECK(B <= 65535, WF3D_ERR_UNSUPPORTED, "wf3d_edge_labels_matched: B > 65535 (got %d)", B);
+    WF3D_CHECK((long)B * Ep < (1L << 31) && (long)B * Et < (1L << 31), WF3D_ERR_UNSUPPORTED,
+               "wf3d_edge_labels_matched: B * Ep or B * Et >= 2^31 (B %d, Ep %d, Et %d)", B, Ep, Et);
+    if (B == 0 || Ep == 0) return WF3D_OK;
+    WF3D_CHECK(col4row && counts && out && (Et == 0 || tlabel), WF3D_ERR_ARG, "wf3d_edge_labels_matched: null pointer");
+    hipLaunchKernelGGL(edge_labels_matched_kernel, dim3(wf3d_cdiv(Ep, ELM_COLS), B), dim3(256), 0, (hipStream_t)stream, tlabel,
+                       Et, col4row, counts, pair_counts, V, Ep, out);
+    WF3D_LAUNCH_CHECK();
+    return WF3D_OK;
 }
 
 extern "C" int wf3d_loss_assign(const float* cost, int B, int V, int32_t* col4row, void* stream) {

@@ -29,6 +29,20 @@ Differences to know about:
     On the device path it is the solver's output itself (no extra launch; unmatched slots hold their dummy column);
     on the scipy path it is built from the match lists with V in the unmatched slots.  wf3d.meter.WireframeMeter
     turns it into batch-wide metrics without a host read.
+  * `edge_targets="matched"` (opt-in; the default "positional" is the reference).  The reference compares column k of
+    `edge_probs[b]` — the pair (p, q) of predicted SLOTS — with column k of `edge_labels[b]`, the pair (i, j) of
+    ground-truth vertices: right only under an identity matching.  "matched" materialises, after the assignment, the
+    labels of the pairs of targets that the slots are matched to (ops.edge_labels_matched, one launch; specification
+    wf3d.targets.matched_edge_labels) and runs the edge term on them at the prediction's width.  The pair order of the
+    prediction row is that of `predictions["edge_counts"]` when the key is there (a padded edge head) and of the target
+    counts otherwise (train mode).  `last_edge_labels` keeps the tensor, [B, edge-term width], beside `last_assignment`.
+    A pair with an unmatched slot is labelled 0; edges to targets matched by slots at or past the pair count stay
+    unsupervised, and existence targets stay positional.
+  * `edge_pos_weight=w`, `edge_focal_gamma=g` (opt-in, defaults 1 and 0): the edge element becomes
+    -(w t (1-p)^g max(log p, -100) + (1-t) p^g max(log1p(-p), -100)) with its own derivative as the gradient, same
+    normaliser.  Columns with p == t in {0, 1} (a ragged batch's padding) contribute exactly 0.  Both `assignment=`
+    values take every option; under "scipy" a non-default option runs the terms from `last_assignment` on the device
+    entry points.
   * `set_data_parallel()`: with one process per GPU each rank sees a slice of the batch, but the reference's
     normalisers are batch-wide (matched-vertex count, :276-281; B x common edge width, :82-86).  When enabled,
     the three normalisers are exchanged (one tiny all-reduce) and each term is rescaled so that the MEAN over
@@ -51,25 +65,55 @@ class _TermsFn(torch.autograd.Function):
         return (dv * g_total, de * g_total, dd * g_total) + (None,) * (len(ctx.needs_input_grad) - 3)
 
 
+def _edge_terms(verts, exist, edge, tverts, texist, tlabel, col4row, counts, weights, edge_width, edge_opts):
+    """The term launch under a device assignment.  edge_opts None: today's launch.  Otherwise (matched, pair_counts,
+    pos_weight, focal_gamma): matched labels are materialised first (one launch, label width = prediction width), and a
+    non-default weight or gamma takes the balanced entry point.  Returns (losses, dverts, dexist, dedge, labels or None)."""
+    matched, pair_counts, pos_weight, gamma = edge_opts or (False, None, 1.0, 0.0)
+    labels = ops.edge_labels_matched(tlabel, col4row, counts, edge.shape[1], pair_counts) if matched else None
+    tl = labels if matched else tlabel
+    if pos_weight == 1.0 and gamma == 0.0:
+        out = ops.loss_terms_assigned(verts, exist, edge, tverts, texist, tl, col4row, counts, weights, edge_width=edge_width)
+    else:
+        out = ops.loss_terms_assigned_bal(verts, exist, edge, tverts, texist, tl, col4row, counts, weights, pos_weight,
+                                          gamma, edge_width=edge_width)
+    return (*out, labels)
+
+
 class _LossDevFn(_TermsFn):
     """Fully asynchronous variant: cost matrices, assignment, loss terms and gradients all on the device."""
 
     @staticmethod
-    def forward(ctx, verts, exist, edge, tverts, texist, tlabel, counts, weights, scales=None, edge_width=None):
+    def forward(ctx, verts, exist, edge, tverts, texist, tlabel, counts, weights, scales=None, edge_width=None,
+                edge_opts=None):
         exist_c = exist.contiguous()
         cost = ops.loss_cost_matrix(verts, exist_c, tverts, counts)
         # the square problem, rows in prediction order like scipy: L1 costs have exact ties (2 of 32 random samples
         # at V = 64) and the rectangular shortcut of ops.loss_assign(cost, counts) resolves them differently
         col4row = ops.loss_assign(cost)
-        losses, dv, de, dd = ops.loss_terms_assigned(verts, exist_c, edge.contiguous(), tverts, texist, tlabel,
-                                                     col4row, counts, weights, edge_width=edge_width)
+        losses, dv, de, dd, labels = _edge_terms(verts, exist_c, edge.contiguous(), tverts, texist, tlabel, col4row, counts,
+                                                 weights, edge_width, edge_opts)
         if scales is not None:       # data-parallel renormalisation: (vertex, existence, edge) factors, device scalars
             w = torch.tensor(weights, dtype=torch.float32, device=losses.device)
             losses = torch.cat([losses[:3], (losses[:3] * w * scales).sum().reshape(1)])
             dv, de, dd = dv * scales[0], de * scales[1], dd * scales[2]
         ctx.save_for_backward(dv, de, dd)
-        ctx.mark_non_differentiable(losses, col4row)
-        return losses[3].clone(), losses, col4row      # the assignment as solved: WireframeLoss.last_assignment
+        ctx.mark_non_differentiable(losses, col4row, *(() if labels is None else (labels,)))
+        # the assignment as solved (WireframeLoss.last_assignment) and the matched labels (last_edge_labels, or None)
+        return losses[3].clone(), losses, col4row, labels
+
+
+class _LossAssignedFn(_TermsFn):
+    """The scipy path under a non-default edge option: the terms from its col4row (V in unmatched slots) on the device
+    entry points, which hold the matched labels and the balanced element."""
+
+    @staticmethod
+    def forward(ctx, verts, exist, edge, tverts, texist, tlabel, col4row, counts, weights, edge_opts):
+        losses, dv, de, dd, labels = _edge_terms(verts, exist.contiguous(), edge.contiguous(), tverts, texist, tlabel,
+                                                 col4row, counts, weights, None, edge_opts)
+        ctx.save_for_backward(dv, de, dd)
+        ctx.mark_non_differentiable(losses, *(() if labels is None else (labels,)))
+        return losses[3].clone(), losses, labels
 
 
 class _LossFn(_TermsFn):
@@ -83,13 +127,28 @@ class _LossFn(_TermsFn):
 
 
 class WireframeLoss(nn.Module):
-    def __init__(self, vertex_weight=1.0, edge_weight=1.0, existence_weight=1.0, assignment="device"):
+    def __init__(self, vertex_weight=1.0, edge_weight=1.0, existence_weight=1.0, assignment="device",
+                 edge_targets="positional", edge_pos_weight=1.0, edge_focal_gamma=0.0):
         """assignment: "device" (default) = Hungarian matching on the GPU, no host sync at all;
-        "scipy" = the reference's scipy.optimize.linear_sum_assignment on the host (one sync)."""
+        "scipy" = the reference's scipy.optimize.linear_sum_assignment on the host (one sync).
+        edge_targets: "positional" (default, the reference) or "matched"; edge_pos_weight > 0 and edge_focal_gamma >= 0:
+        the class-balanced edge element (module docstring).  The defaults are the reference's loss."""
         super().__init__()
         if assignment not in ("device", "scipy"):
             raise ValueError("assignment must be 'device' or 'scipy'")
+        if edge_targets not in ("positional", "matched"):
+            raise ValueError("edge_targets must be 'positional' or 'matched'")
+        if isinstance(edge_pos_weight, bool) or not isinstance(edge_pos_weight, (int, float)) \
+                or not (0.0 < edge_pos_weight < float("inf")):
+            raise ValueError("edge_pos_weight must be a finite number > 0")
+        if isinstance(edge_focal_gamma, bool) or not isinstance(edge_focal_gamma, (int, float)) \
+                or not (0.0 <= edge_focal_gamma < float("inf")):
+            raise ValueError("edge_focal_gamma must be a finite number >= 0")
         self.assignment = assignment
+        self.edge_targets = edge_targets
+        self.edge_pos_weight = float(edge_pos_weight)
+        self.edge_focal_gamma = float(edge_focal_gamma)
+        self.last_edge_labels = None     # fp32 [B, Ep] device tensor of the latest forward under edge_targets="matched"
         self.vertex_weight = vertex_weight
         self.edge_weight = edge_weight
         self.existence_weight = existence_weight
@@ -160,14 +219,23 @@ class WireframeLoss(nn.Module):
                       for k in ("vertices", "vertex_existence", "edge_labels"))
         # weights in the kernels' (vertex, existence, edge) order
         w = (self.vertex_weight, self.existence_weight, self.edge_weight)
+        matched = self.edge_targets == "matched"
+        edge_opts = None          # all three edge options at their defaults: exactly the launches of the plain loss
+        if matched or self.edge_pos_weight != 1.0 or self.edge_focal_gamma != 0.0:
+            # matched labels follow the pair order of the prediction row: a padded edge head says which counts it used
+            pc = predictions.get("edge_counts") if matched else None
+            pc = pc.to(device=dev, dtype=torch.int64).contiguous() if pc is not None else None
+            edge_opts = (matched, pc, self.edge_pos_weight, self.edge_focal_gamma)
         if self.assignment == "device":
             counts = targets["vertex_counts"].to(device=dev, dtype=torch.int64).contiguous()
             # the kernels index targets['vertices'][b, :counts[b]] and need counts[b] <= V real columns: clamp (docstring)
             counts = counts.clamp(min=0, max=min(V, tv.shape[1]))
             ew = predictions.get("edge_width")        # padded edge head: the prediction width is a device scalar
             ew = ew.to(device=dev, dtype=torch.int64) if ew is not None else None
-            scales = self._dp_scales(counts, B, V, pp.shape[1] if ew is None else ew, tl.shape[1], dev)
-            total, parts, self.last_assignment = _LossDevFn.apply(pv, pe, pp, tv, te, tl, counts, w, scales, ew)
+            # matched labels are as wide as the prediction
+            scales = self._dp_scales(counts, B, V, pp.shape[1] if ew is None else ew, pp.shape[1] if matched else tl.shape[1], dev)
+            total, parts, self.last_assignment, self.last_edge_labels = _LossDevFn.apply(pv, pe, pp, tv, te, tl, counts, w,
+                                                                                         scales, ew, edge_opts)
             return {"total_loss": total, "vertex_loss": parts[0], "existence_loss": parts[1], "edge_loss": parts[2]}
         matches = self._hungarian_matching(predictions, targets)
         lens = [len(m[0]) for m in matches]
@@ -184,5 +252,11 @@ class WireframeLoss(nn.Module):
         if predictions.get("edge_width") is not None:
             # padded edge head: this path has synced already, the width is read here and the columns past it dropped
             pp = pp[:, :int(predictions["edge_width"])]
+        if edge_opts is not None:
+            counts = targets["vertex_counts"].to(device=dev, dtype=torch.int64).clamp(min=0, max=min(V, tv.shape[1])).contiguous()
+            total, parts, self.last_edge_labels = _LossAssignedFn.apply(pv, pe, pp, tv, te, tl, self.last_assignment, counts,
+                                                                        w, edge_opts)
+            return {"total_loss": total, "vertex_loss": parts[0], "existence_loss": parts[1], "edge_loss": parts[2]}
+        self.last_edge_labels = None
         total, parts = _LossFn.apply(pv, pe, pp, tv, te, tl, m_pred, m_tgt, m_off, n_match, w)
         return {"total_loss": total, "vertex_loss": parts[0], "existence_loss": parts[1], "edge_loss": parts[2]}

@@ -1187,9 +1187,10 @@ def loss_cost_matrix(verts, exist, tverts, counts):
     return cost
 
 
-def _loss_launch(name, verts, exist, edge, tverts, texist, tlabel, match, weights):
+def _loss_launch(name, verts, exist, edge, tverts, texist, tlabel, match, weights, balance=()):
     """One launch of wf3d_<name>, a wf3d_loss_terms* entry point: they differ only in `match`, the arguments between Et
-    and B that say which prediction is matched to which target.  Allocates and returns (losses, dverts, dexist, dedge)."""
+    and B that say which prediction is matched to which target, and in `balance`, the (pos_weight, focal_gamma) that the
+    _bal entry takes after the weights.  Allocates and returns (losses, dverts, dexist, dedge)."""
     B, V, _ = verts.shape
     Ep = edge.shape[1] if edge is not None else 0
     Et = tlabel.shape[1] if tlabel is not None else 0
@@ -1201,8 +1202,8 @@ def _loss_launch(name, verts, exist, edge, tverts, texist, tlabel, match, weight
     ws = scratch(B * 3 * 4, dev)
     check(getattr(_lib.load(), "wf3d_" + name)(
         _p(verts), verts.stride(0), verts.stride(1), _p(exist), _p(edge), Ep, _p(tverts), tverts.shape[1], _p(texist),
-        _p(tlabel), Et, *match, B, V, float(weights[0]), float(weights[1]), float(weights[2]), _p(dverts), _p(dexist),
-        _p(dedge), _p(losses), _p(ws), ws.numel(), _stream()), name)
+        _p(tlabel), Et, *match, B, V, float(weights[0]), float(weights[1]), float(weights[2]), *balance, _p(dverts),
+        _p(dexist), _p(dedge), _p(losses), _p(ws), ws.numel(), _stream()), name)
     return losses, dverts, dexist, dedge
 
 
@@ -1238,3 +1239,36 @@ def loss_terms_assigned(verts, exist, edge, tverts, texist, tlabel, col4row, cou
         raise RuntimeError("wf3d.loss_terms_assigned: edge_width must be a one-element int64 tensor")
     return _loss_launch("loss_terms_assigned_ew", verts, exist, edge, tverts, texist, tlabel,
                         (_p(edge_width), _p(col4row), _p(counts)), weights)
+
+
+def loss_terms_assigned_bal(verts, exist, edge, tverts, texist, tlabel, col4row, counts, weights, edge_pos_weight,
+                            edge_focal_gamma, edge_width=None):
+    """loss_terms_assigned with the class-balanced / focal edge element (include/wf3d.h, wf3d_loss_terms_assigned_bal):
+    positives weighted by edge_pos_weight > 0, each side modulated by (1 - its probability)^edge_focal_gamma, gamma >= 0.
+    edge_width as in loss_terms_assigned, or None."""
+    _need_cuda(verts, exist, edge, tverts, texist, tlabel, col4row, counts, edge_width)
+    if edge_width is not None and (edge_width.dtype != torch.int64 or edge_width.numel() != 1):
+        raise RuntimeError("wf3d.loss_terms_assigned_bal: edge_width must be a one-element int64 tensor")
+    return _loss_launch("loss_terms_assigned_bal", verts, exist, edge, tverts, texist, tlabel,
+                        (_p(edge_width), _p(col4row), _p(counts)), weights,
+                        balance=(float(edge_pos_weight), float(edge_focal_gamma)))
+
+
+def edge_labels_matched(edge_labels, assignment, counts, width, pair_counts=None):
+    """The edge labels under an assignment, on the device (wf3d.targets.matched_edge_labels is the specification; the
+    result equals it element for element).  edge_labels fp32 [B, Et], assignment int32 [B, V], counts int64 [B] (target
+    counts), pair_counts int64 [B] or None (the counts whose pair order the prediction row has) -> fp32 [B, width].
+    One launch, nothing read on the host."""
+    _need_cuda(edge_labels, assignment, counts, pair_counts)
+    if (edge_labels.dtype != torch.float32 or edge_labels.dim() != 2 or assignment.dtype != torch.int32 or assignment.dim() != 2
+            or counts.dtype != torch.int64 or (pair_counts is not None and pair_counts.dtype != torch.int64)
+            or not (edge_labels.is_contiguous() and assignment.is_contiguous() and counts.is_contiguous())
+            or (pair_counts is not None and not pair_counts.is_contiguous())):
+        raise RuntimeError("wf3d.edge_labels_matched: bad layout / dtype")
+    B, V = assignment.shape
+    if edge_labels.shape[0] != B or counts.numel() != B or (pair_counts is not None and pair_counts.numel() != B):
+        raise RuntimeError("wf3d.edge_labels_matched: batch sizes differ")
+    out = torch.empty(B, int(width), dtype=torch.float32, device=assignment.device)
+    check(_lib.load().wf3d_edge_labels_matched(_p(edge_labels), edge_labels.shape[1], _p(assignment), _p(counts),
+                                               _p(pair_counts), B, V, int(width), _p(out), _stream()), "edge_labels_matched")
+    return out
