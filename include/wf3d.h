@@ -988,6 +988,44 @@ int wf3d_hausdorff_lines_batch(const float* seg, const int32_t* koff, const floa
                                const int64_t* ooff, int B, long max_pairs, int sample_points, double* out, void* stream);
 
 /* ------------------------------------------------------------------------
+ * Wireframe decoding (csrc/evalpost.hip; the specification, stated in numpy, is wf3d/decode.py and the kernel gives its
+ * values exactly): one forward pass -> per sample a wireframe of vertices that exist, are distinct and are connected.
+ * The reference has no such step: it hands all V slots to its metrics.
+ * Inputs: verts [B, V, 3] (strides in floats, unit inner stride), exist [B, V] with element stride exist_stride and
+ * sample stride V * exist_stride (a column of a [B, V, k] tensor passes as it is), counts [B], probs [B, max_e] in the
+ * model's lexicographic pair order over the first c_s = clamp(counts[s], 0, V) slots.
+ *   1. slot i is alive iff i < c_s, its coordinates are finite, its existence is not NaN and existence > exist_threshold
+ *      (exist_threshold = -INFINITY: no existence test).  A non-finite coordinate or NaN existence below c_s sets
+ *      WF3D_DECODE_NONFINITE in status[s].
+ *   2. greedy suppression: the alive slots visited by (existence descending, slot ascending), floats as values; a slot
+ *      within the radius of an earlier representative, d2 <= merge_radius^2 with d2 = (dx dx + dy dy) + dz dz in fp64 (no
+ *      FMA), is merged into the first such one in visiting order, else it is a representative.  merge_radius < 0: no
+ *      merging; 0: coincident slots only.  A merged slot keeps its representative's coordinates, unchanged.
+ *   3. candidate e = (i < j < c_s), e < max_e, survives iff both ends are alive, probs[s, e] > edge_threshold (NaN and
+ *      equality do not pass) and the two representatives differ; a pair of representatives takes the maximum probability
+ *      of the candidates that land on it (0.0 above -0.0).
+ *   4. output vertices = the representatives in slot order (drop_isolated: only the ends of an output edge).
+ * Outputs: nverts [B]; dverts [B, V, 3], rows at and past nverts[s] zero; slots [B, V] = the source slot of each output
+ * vertex, -1 behind them; koff [B + 1], pairs / seg / kprob (B * max_e rows, the first K = koff[B] packed, the rest left
+ * untouched) in the layout of wf3d_edge_compact: pairs in the NEW vertex indices, lexicographic within a sample, end
+ * points higher z first (equal z: the second vertex first), so wf3d_hausdorff_lines_batch takes them as they are, and every
+ * end point is a row of dverts, as wf3d_eval_metrics_nv requires; status [B].
+ * Four launches: one workgroup per sample (slot state in LDS, at most V suppression rounds of one barrier, the per-pair
+ * maximum by atomic max in ws), then count / scan / place over the pairs of output vertices.  The only reduction is a
+ * maximum: the same bits on every run.  Every loop is bounded by V or max_e, whatever the data.
+ * ws: wf3d_wireframe_decode_ws_bytes(B, V, max_e) bytes (4 B V^2 + the chunk counts; 0 when V < 2 or max_e = 0), else
+ * WF3D_ERR_WS.  A NaN threshold or radius: WF3D_ERR_ARG.  V <= 1024, B <= 65535, B * max_e < 2^31, else
+ * WF3D_ERR_UNSUPPORTED.  B = 0 launches nothing; V < 2 or max_e = 0 still decodes the vertices and writes koff = 0.
+ * ------------------------------------------------------------------------ */
+#define WF3D_DECODE_NONFINITE 1
+size_t wf3d_wireframe_decode_ws_bytes(int B, int V, int max_e);
+int wf3d_wireframe_decode(const float* verts, long sample_stride, long vertex_stride, const float* exist, long exist_stride,
+                          const int32_t* counts, const float* probs, int B, int V, int max_e, float exist_threshold,
+                          float edge_threshold, double merge_radius, int drop_isolated, int32_t* nverts, float* dverts,
+                          int32_t* slots, int32_t* koff, int32_t* pairs, float* seg, float* kprob, int32_t* status,
+                          void* ws, size_t ws_bytes, void* stream);
+
+/* ------------------------------------------------------------------------
  * Evaluation metrics on the device (csrc/evalmetrics.hip): what eval/ap_calculator.py's compute_metrics derives from a
  * sample's Hausdorff matrix — two rectangular assignments, the corner sets, the counters and the corner distance sum —
  * for a whole batch in four launches.
@@ -1026,6 +1064,11 @@ int wf3d_hausdorff_lines_batch(const float* seg, const int32_t* koff, const floa
  * ws: wf3d_eval_metrics_ws_bytes(B, V, total_lverts, max_long) bytes, total_lverts = lvoff[B].
  * B <= 65535, V <= 1024, max_lverts (>= every sample's label vertex count) <= 1024, B * V and V * total_lverts below
  * 2^31, else WF3D_ERR_UNSUPPORTED; B = 0 launches nothing.
+ *
+ * wf3d_eval_metrics_nv: the same with a vertex count per sample, for decoded wireframes (wf3d_wireframe_decode's dverts /
+ * nverts): sample s's predicted vertices are the first clamp(nverts[s], 0, V) rows of verts[s], counters[s, 1] reports
+ * that number, and the rows behind them are never read.  nverts = NULL means V for every sample: wf3d_eval_metrics is
+ * that call.  Strides, workspace layout and wf3d_eval_metrics_ws_bytes are the same.
  * ------------------------------------------------------------------------ */
 #define WF3D_EVAL_NONFINITE 1
 #define WF3D_EVAL_NO_MATCH 2
@@ -1042,6 +1085,11 @@ int wf3d_eval_metrics(const float* verts, long sample_stride, long vertex_stride
                       const double* hd, const int64_t* ooff, const int32_t* aoff, int32_t* assign, double thresh,
                       int max_lverts, long total_lverts, long max_long, int32_t* counters, double* distances, void* ws,
                       size_t ws_bytes, void* stream);
+int wf3d_eval_metrics_nv(const float* verts, long sample_stride, long vertex_stride, int B, int V, const int32_t* nverts,
+                         const float* seg, const int32_t* koff, const float* lverts, const int32_t* lvoff, const float* lseg,
+                         const int32_t* loff, const double* hd, const int64_t* ooff, const int32_t* aoff, int32_t* assign,
+                         double thresh, int max_lverts, long total_lverts, long max_long, int32_t* counters,
+                         double* distances, void* ws, size_t ws_bytes, void* stream);
 
 #ifdef __cplusplus
 }

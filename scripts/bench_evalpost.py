@@ -27,6 +27,14 @@ measures evaluate_batch(compact=True) three ways in the same alternating blocks:
 "device" (metrics="device", the EvalLabels built inside the timed call) and "device_labels" (an EvalLabels built once,
 outside).  Then one worst-case row: V = 64 with every one of the 2016 candidates kept, against a label of 120 vertices
 and 300 edges (few blocks: the host arm solves 32 assignments of 2016 x 300 per batch).
+
+    python scripts/bench_evalpost.py --what decode [--out profiles/r20_decode.jsonl]
+
+measures evaluate_batch(compact=True, metrics="device", labels=...) without and with `decode` (wf3d_wireframe_decode in
+front, wf3d_eval_metrics_nv behind) on the same predictions, padded layout: "undecoded" (decode=None: the call as it was
+before decoding existed), "decoded" (every slot alive, merge_radius 0.05 merges nothing: the same wireframes, so the
+difference is the cost of the step) and "decoded_sparse" (the 12 label slots and a quarter of the others alive: what the
+step saves downstream).  Existence values come from a generator of their own, so the predictions are those of --what metrics.
 """
 import argparse
 import json
@@ -179,17 +187,49 @@ def run_metrics(V, layout, data, args, thresh, blocks, steps, warmup, tag=None):
     return lines
 
 
+def run_decode(V, data, args):
+    pred = lambda ex: dict(predictions(data, V, "padded"), existence_probabilities=ex)      # noqa: E731
+    labels = postprocess.EvalLabels(*data["labels"], data["vertices"].device)
+    gen = np.random.RandomState(1)
+    alive = gen.uniform(0.6, 0.99, (B, V)).astype(np.float32)
+    sparse = np.where(gen.uniform(0, 1, (B, V)) < 0.25, alive, np.float32(0.1))
+    sparse[:, :12] = alive[:, :12]
+    ex = {"decoded": torch.from_numpy(alive).to(data["vertices"].device), "decoded_sparse": torch.from_numpy(sparse).to(data["vertices"].device)}
+    opts = {"existence_threshold": 0.5, "merge_radius": 0.05}
+
+    def evaluate(arm):
+        calc = ap.APCalculator(distance_thresh=0.1)
+        postprocess.evaluate_batch(pred(ex.get(arm, ex["decoded"])), *data["labels"], calc, compact=True, metrics="device",
+                                   labels=labels, decode=None if arm == "undecoded" else opts)
+        return calc
+
+    arms = {name: (lambda name=name: evaluate(name)) for name in ("undecoded", "decoded", "decoded_sparse")}
+    ref = {name: fn() for name, fn in arms.items()}
+    med = blocks_of(arms, args.blocks, args.block_steps, args.warmup)
+    u = summary(med["undecoded"])
+    common = {"bench": "decode", "what": "evaluate", "B": B, "V": V, "max_e": V * (V - 1) // 2, "layout": "padded",
+              "kept_edges": data["kept"], "blocks": args.blocks, "steps_per_block": args.block_steps}
+    lines = []
+    for name in arms:
+        m = summary(med[name])
+        lines.append(dict(common, arm=name, ms=m, decoded_minus_undecoded_ms=round(m["median"] - u["median"], 3),
+                          tp_fp_corners=int(ref[name].ap_dict["tp_fp_corners"]), tp_fp_edges=int(ref[name].ap_dict["tp_fp_edges"]),
+                          tp_edges=int(ref[name].ap_dict["tp_edges"])))
+    return lines
+
+
 def main():
     p = argparse.ArgumentParser()
     p.add_argument("--blocks", type=int, default=5)
     p.add_argument("--block-steps", type=int, default=7)
     p.add_argument("--warmup", type=int, default=2)
     p.add_argument("--vertices", default="64,256")
-    p.add_argument("--what", choices=("compact", "metrics"), default="compact")
+    p.add_argument("--what", choices=("compact", "metrics", "decode"), default="compact")
     p.add_argument("--out", default=None)
     args = p.parse_args()
     if args.out is None:
-        args.out = os.path.join(ROOT, "profiles", "r13_evalpost.jsonl" if args.what == "compact" else "r15_evalmetrics.jsonl")
+        args.out = os.path.join(ROOT, "profiles", {"compact": "r13_evalpost.jsonl", "metrics": "r15_evalmetrics.jsonl",
+                                                   "decode": "r20_decode.jsonl"}[args.what])
     dev = torch.device("cuda:0")
     ap.set_device(dev)
     gen = np.random.RandomState(0)
@@ -203,6 +243,9 @@ def main():
 
     for V in (int(v) for v in args.vertices.split(",")):
         data = synthetic(V, gen, dev)
+        if args.what == "decode":
+            emit(run_decode(V, data, args))
+            continue
         for layout in ("ragged", "padded"):
             if args.what == "compact":
                 emit(run(V, layout, data, args))

@@ -11,6 +11,7 @@
 //                         np.unique / np.setdiff1d's lexicographic order), the free-corner distance matrix for the second
 //                         assignment, and e_term.
 //   finalize_kernel       one wave per sample: the second assignment's pairs in row order -> distances and the counters.
+// wf3d_eval_metrics_nv gives every sample its own predicted vertex count (decoded wireframes): the first nverts[s] rows.
 #include "lsa_solve.h"
 #include "wf3d_common.h"
 
@@ -118,8 +119,14 @@ EvalWs eval_ws(void* ws, int B, int V, long total_lverts, long max_long) {
     return w;
 }
 
+// sample s's predicted vertex count: the first clamp(nverts[s], 0, V) rows of its V (nverts null: all of them)
+__device__ __forceinline__ int sample_verts(const int32_t* __restrict__ nverts, int s, int V) {
+    return nverts ? min(max(nverts[s], 0), V) : V;
+}
+
 __global__ __launch_bounds__(SETS_THREADS) void corner_sets_kernel(
-    const float* __restrict__ verts, long sstride, long vstride, int V, const float* __restrict__ seg,
+    const float* __restrict__ verts, long sstride, long vstride, int Vmax, const int32_t* __restrict__ nverts,
+    const float* __restrict__ seg,
     const int32_t* __restrict__ koff, const float* __restrict__ lverts, const int32_t* __restrict__ lvoff,
     const float* __restrict__ lseg, const int32_t* __restrict__ loff, const double* __restrict__ hd,
     const int64_t* __restrict__ ooff, const int32_t* __restrict__ assign, const int32_t* __restrict__ aoff, double thresh,
@@ -130,6 +137,7 @@ __global__ __launch_bounds__(SETS_THREADS) void corner_sets_kernel(
     __shared__ double emin[SETS_MAX];
     __shared__ int st_s, tp_s, cnt_p[2], cnt_g[2];
     const int s = blockIdx.x, tid = threadIdx.x, B = gridDim.x;
+    const int V = sample_verts(nverts, s, Vmax);                 // the workspace layout keeps the stride Vmax
     const int k0 = koff[s], l0 = loff[s], g0 = lvoff[s];
     const long n = (long)koff[s + 1] - k0, m = (long)loff[s + 1] - l0;
     int Lv = lvoff[s + 1] - g0;
@@ -148,7 +156,7 @@ __global__ __launch_bounds__(SETS_THREADS) void corner_sets_kernel(
         used_g[i] = 0;
         if (!pt_finite(g)) st |= WF3D_EVAL_NONFINITE;
     }
-    const int64_t dmo = (int64_t)V * g0;
+    const int64_t dmo = (int64_t)Vmax * g0;
     double* dm = dm_all + dmo;
     __syncthreads();
     if (n <= 0 || (st & WF3D_EVAL_RANGE)) {
@@ -160,7 +168,7 @@ __global__ __launch_bounds__(SETS_THREADS) void corner_sets_kernel(
         if (st) atomicOr(&st_s, st);
         __syncthreads();
         if (tid == 0) {
-            ooff2[s] = dmo; aoff2[s] = s * V; eterm[s] = 0.0;
+            ooff2[s] = dmo; aoff2[s] = s * Vmax; eterm[s] = 0.0;
             dims[2 * s] = 0; dims[2 * s + 1] = V; dims[2 * B + 2 * s] = 0; dims[2 * B + 2 * s + 1] = Lv;
             part[4 * s] = 0; part[4 * s + 1] = 0; part[4 * s + 2] = st_s; part[4 * s + 3] = 0;
         }
@@ -214,13 +222,13 @@ __global__ __launch_bounds__(SETS_THREADS) void corner_sets_kernel(
         int sts = st_s;
         if (npu == 0) sts |= WF3D_EVAL_NO_MATCH;
         if (!(e == e) || isinf(e)) sts |= WF3D_EVAL_NONFINITE;
-        ooff2[s] = dmo; aoff2[s] = s * V; eterm[s] = e;
+        ooff2[s] = dmo; aoff2[s] = s * Vmax; eterm[s] = e;
         dims[2 * s] = 0; dims[2 * s + 1] = nfp; dims[2 * B + 2 * s] = 0; dims[2 * B + 2 * s + 1] = nfg;
         part[4 * s] = npu; part[4 * s + 1] = tp_s; part[4 * s + 2] = sts; part[4 * s + 3] = 0;
     }
 }
 
-__global__ __launch_bounds__(64) void finalize_kernel(int V, const int32_t* __restrict__ koff, const int32_t* __restrict__ lvoff,
+__global__ __launch_bounds__(64) void finalize_kernel(int V, const int32_t* __restrict__ nverts, const int32_t* __restrict__ koff, const int32_t* __restrict__ lvoff,
                                                       const int32_t* __restrict__ loff, double thresh,
                                                       const double* __restrict__ dm_all, const int64_t* __restrict__ ooff2,
                                                       const double* __restrict__ eterm, const int32_t* __restrict__ dims,
@@ -261,7 +269,7 @@ __global__ __launch_bounds__(64) void finalize_kernel(int V, const int32_t* __re
     }
     distances[s] = sum + eterm[s];
     int32_t* c = counters + 8 * (long)s;
-    c[0] = part[4 * s] + nok; c[1] = V; c[2] = lvoff[s + 1] - lvoff[s]; c[3] = part[4 * s + 1];
+    c[0] = part[4 * s] + nok; c[1] = sample_verts(nverts, s, V); c[2] = lvoff[s + 1] - lvoff[s]; c[3] = part[4 * s + 1];
     c[4] = koff[s + 1] - koff[s]; c[5] = loff[s + 1] - loff[s]; c[6] = st; c[7] = 0;
 }
 
@@ -301,11 +309,12 @@ extern "C" size_t wf3d_eval_metrics_ws_bytes(int B, int V, long total_lverts, lo
     return eval_ws(nullptr, B, V, total_lverts, max_long).total;
 }
 
-extern "C" int wf3d_eval_metrics(const float* verts, long sample_stride, long vertex_stride, int B, int V, const float* seg,
-                                 const int32_t* koff, const float* lverts, const int32_t* lvoff, const float* lseg,
-                                 const int32_t* loff, const double* hd, const int64_t* ooff, const int32_t* aoff,
-                                 int32_t* assign, double thresh, int max_lverts, long total_lverts, long max_long,
-                                 int32_t* counters, double* distances, void* ws, size_t ws_bytes, void* stream) {
+extern "C" int wf3d_eval_metrics_nv(const float* verts, long sample_stride, long vertex_stride, int B, int V,
+                                    const int32_t* nverts, const float* seg, const int32_t* koff, const float* lverts,
+                                    const int32_t* lvoff, const float* lseg, const int32_t* loff, const double* hd,
+                                    const int64_t* ooff, const int32_t* aoff, int32_t* assign, double thresh, int max_lverts,
+                                    long total_lverts, long max_long, int32_t* counters, double* distances, void* ws,
+                                    size_t ws_bytes, void* stream) {
     WF3D_CHECK(B >= 0 && V >= 0 && max_lverts >= 0 && total_lverts >= 0 && max_long >= 0, WF3D_ERR_ARG,
                "wf3d_eval_metrics: bad dims");
     WF3D_CHECK(B <= 65535, WF3D_ERR_UNSUPPORTED, "wf3d_eval_metrics: B > 65535 (got %d)", B);
@@ -323,14 +332,22 @@ extern "C" int wf3d_eval_metrics(const float* verts, long sample_stride, long ve
     // hd / assign / seg / lseg may be null when no sample has a pair: the kernels then read none of them
     int rc = lsa_rect_launch(hd, ooff, koff, loff, 1, aoff, B, max_long, assign, w.status1, w.lsa, st);
     if (rc != WF3D_OK) return rc;
-    hipLaunchKernelGGL(corner_sets_kernel, dim3(B), dim3(SETS_THREADS), 0, st, verts, sample_stride, vertex_stride, V, seg, koff,
+    hipLaunchKernelGGL(corner_sets_kernel, dim3(B), dim3(SETS_THREADS), 0, st, verts, sample_stride, vertex_stride, V, nverts, seg, koff,
                        lverts, lvoff, lseg, loff, hd, ooff, assign, aoff, thresh, w.dm, w.ooff2, w.eterm, w.dims, w.aoff2, w.part);
     WF3D_LAUNCH_CHECK();
     rc = lsa_rect_launch(w.dm, w.ooff2, w.dims, w.dims + 2 * B, 2, w.aoff2, B, SETS_MAX, w.assign2, w.status2, w.lsa, st);
     if (rc != WF3D_OK) return rc;
-    hipLaunchKernelGGL(finalize_kernel, dim3(B), dim3(64), 0, st, V, koff, lvoff, loff, thresh, w.dm, w.ooff2, w.eterm, w.dims,
+    hipLaunchKernelGGL(finalize_kernel, dim3(B), dim3(64), 0, st, V, nverts, koff, lvoff, loff, thresh, w.dm, w.ooff2, w.eterm, w.dims,
                        w.part, w.assign2, w.status1, w.status2, w.inv, counters, distances);
     WF3D_LAUNCH_CHECK();
     return WF3D_OK;
 }
 
+extern "C" int wf3d_eval_metrics(const float* verts, long sample_stride, long vertex_stride, int B, int V, const float* seg,
+                                 const int32_t* koff, const float* lverts, const int32_t* lvoff, const float* lseg,
+                                 const int32_t* loff, const double* hd, const int64_t* ooff, const int32_t* aoff,
+                                 int32_t* assign, double thresh, int max_lverts, long total_lverts, long max_long,
+                                 int32_t* counters, double* distances, void* ws, size_t ws_bytes, void* stream) {
+    return wf3d_eval_metrics_nv(verts, sample_stride, vertex_stride, B, V, nullptr, seg, koff, lverts, lvoff, lseg, loff, hd, ooff,
+                                aoff, assign, thresh, max_lverts, total_lverts, max_long, counters, distances, ws, ws_bytes, stream);
+}

@@ -13,11 +13,17 @@ Opt-in on top of that: the metrics themselves on the device (csrc/evalmetrics.hi
     labels = EvalLabels(wf_vertices, wf_edges, device)     # once per label set: device copy + edit-distance constants
     evaluate_batch(..., compact=True, metrics="device", labels=labels)     # both assignments, corner sets, counters: 4 launches
 
+Opt-in before any of them: decoding (csrc/evalpost.hip wf3d_wireframe_decode; the specification is wf3d/decode.py).  The
+reference hands all V slots to its metrics; this turns a forward pass into vertices that exist, are distinct and are connected.
+
+    samples = decode_wireframes(model(x), merge_radius=0.05)                # existence filter, vertex merging, edge re-indexing
+    evaluate_batch(..., decode={"merge_radius": 0.05})                      # any of the three paths above, fed from it
+
 `hausdorff_lines` is the device form of eval.ap_calculator.hausdorff_distance_line (csrc/evalpost.hip)."""
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, decode as _decode
 from ._lib import check
 from .functional import edge_index_lists
 from .ops import _stream
@@ -79,6 +85,15 @@ def _gt_edge_vertices(gt_vertices, gt_edges):
     return ev[np.arange(ev.shape[0])[:, np.newaxis], np.flip(np.argsort(ev[:, :, -1]), axis=1)]
 
 
+def _vertex_counts(predictions, dev):
+    """int32 [B] on `dev`: `edge_counts` when the dict has it (padded edge layout; nothing of it is read on the host), else
+    each count from len(edge_indices[s])."""
+    if predictions.get("edge_counts") is not None:
+        return predictions["edge_counts"].detach().to(device=dev, dtype=torch.int32)
+    lens = [len(e) for e in predictions["edge_indices"]]
+    return torch.tensor([int(round((1 + (1 + 8 * n) ** 0.5) / 2)) if n else 0 for n in lens], dtype=torch.int32).to(dev)
+
+
 def wireframes_compact(predictions, threshold=0.5, keep_device=False):
     """wireframes_from_predictions with the kept edges compacted on the device (wf3d_edge_compact): the same list of
     per-sample dicts (equal values, dtypes and shapes, the empty (0, 2) / (0, 2, 3) included) plus `pd_edge_probs`
@@ -92,11 +107,7 @@ def wireframes_compact(predictions, threshold=0.5, keep_device=False):
     B, V, _ = verts.shape
     max_e = probs.shape[1]
     dev = verts.device
-    if predictions.get("edge_counts") is not None:
-        cnt = predictions["edge_counts"].detach().to(device=dev, dtype=torch.int32)
-    else:
-        lens = [len(e) for e in predictions["edge_indices"]]
-        cnt = torch.tensor([int(round((1 + (1 + 8 * n) ** 0.5) / 2)) if n else 0 for n in lens], dtype=torch.int32).to(dev)
+    cnt = _vertex_counts(predictions, dev)
     v = verts.detach().float()
     if v.stride(2) != 1:
         v = v.contiguous()
@@ -132,6 +143,99 @@ def wireframes_compact(predictions, threshold=0.5, keep_device=False):
     return out
 
 
+DECODE_OPTIONS = ("existence_threshold", "edge_threshold", "merge_radius", "drop_isolated")
+
+
+def decode_wireframes(predictions, existence_threshold=0.5, edge_threshold=0.5, merge_radius=None, drop_isolated=False,
+                      keep_device=False):
+    """One forward pass -> per sample a wireframe of vertices that exist, are distinct and are connected (the steps and
+    every tie rule: wf3d/decode.py).  Slots whose `existence_probabilities` do not exceed `existence_threshold` (None: no
+    test) are dropped, slots within `merge_radius` of a more probable one are merged into it (None: no merging), the
+    candidate edges above `edge_threshold` are re-indexed onto the surviving vertices, and drop_isolated=True keeps only
+    vertices with an edge.  Returns the per-sample dict list of wireframes_compact plus `slots` (int64 [n_s], the source
+    slot of each vertex); `pred_vertices` is [n_s, 3] and `pd_edges` index into it.  The counts come from `edge_counts`
+    when present, else from len(edge_indices[s]), as in wireframes_compact.
+    CUDA predictions run wf3d_wireframe_decode (four launches), then one synchronisation for koff | nverts | status and
+    one packed copy; CPU predictions run the numpy specification.  Both return equal values.
+    keep_device=True (CUDA predictions only, else ValueError): returns (samples, {"koff", "seg", "dverts", "nverts", "status": tensors on the predictions' device,
+    "koff_host", "status_host": numpy}) — what wf3d_hausdorff_lines_batch and wf3d_eval_metrics_nv take."""
+    if edge_threshold is None:
+        raise ValueError("decode_wireframes: edge_threshold must be a number")
+    for name, t in (("existence_threshold", existence_threshold), ("edge_threshold", edge_threshold), ("merge_radius", merge_radius)):
+        if t is not None and np.isnan(t):
+            raise ValueError(f"decode_wireframes: {name} is NaN")
+    verts, probs = predictions["vertices"], predictions["edge_probs"]
+    B, V, _ = verts.shape
+    max_e = probs.shape[1]
+    dev = verts.device
+    if keep_device and dev.type == "cpu":
+        raise ValueError("decode_wireframes: keep_device=True needs CUDA predictions (its tensors feed the batched kernels)")
+    cnt = _vertex_counts(predictions, dev)
+    ex = predictions["existence_probabilities"].detach().float()
+    if tuple(ex.shape) != (B, V):
+        raise ValueError(f"decode_wireframes: existence_probabilities must be [B, V] = {(B, V)}, got {tuple(ex.shape)}")
+    v = verts.detach().float()
+    pr = probs.detach().float().contiguous()
+    if dev.type == "cpu":
+        d = _decode.decode_batch(v.numpy(), ex.numpy(), pr.numpy(), cnt.numpy(), existence_threshold=existence_threshold,
+                                 edge_threshold=edge_threshold, merge_radius=merge_radius, drop_isolated=drop_isolated)
+        koff_h, nv_h, st_h = d["koff"], d["nverts"], d["status"]
+        pv, sl, pe, ps, pp = d["dverts"], d["slots"], d["pairs"].astype(np.int64), d["seg"], d["kprob"]
+    else:
+        if v.stride(2) != 1:
+            v = v.contiguous()
+        # the kernel reads a [B, V] existence array of one element stride: a column of a [B, V, k] tensor passes as it is
+        se = ex.stride(1) if V > 1 else (ex.stride(0) if B > 1 else 1)
+        if B * V > 0 and not (se >= 1 and (B == 1 or ex.stride(0) == V * se)):
+            ex, se = ex.contiguous(), 1
+        lib = _lib.load()
+        cap = B * max_e
+        head = torch.empty(3 * B + 1, dtype=torch.int32, device=dev)         # koff [B + 1] | nverts [B] | status [B]
+        koff, nverts, status = head[:B + 1], head[B + 1:2 * B + 1], head[2 * B + 1:]
+        dverts = torch.empty(B, V, 3, dtype=torch.float32, device=dev)
+        slots = torch.empty(B, V, dtype=torch.int32, device=dev)
+        pairs = torch.empty(cap, 2, dtype=torch.int32, device=dev)
+        seg = torch.empty(cap, 2, 3, dtype=torch.float32, device=dev)
+        kprob = torch.empty(cap, dtype=torch.float32, device=dev)
+        ws_bytes = lib.wf3d_wireframe_decode_ws_bytes(B, V, max_e)
+        ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=dev)
+        check(lib.wf3d_wireframe_decode(v.data_ptr(), v.stride(0), v.stride(1), ex.data_ptr(), se, cnt.data_ptr(), pr.data_ptr(),
+                                        B, V, max_e, float("-inf") if existence_threshold is None else float(existence_threshold),
+                                        float(edge_threshold), -1.0 if merge_radius is None else float(merge_radius),
+                                        int(bool(drop_isolated)), nverts.data_ptr(), dverts.data_ptr(), slots.data_ptr(),
+                                        koff.data_ptr(), pairs.data_ptr(), seg.data_ptr(), kprob.data_ptr(), status.data_ptr(),
+                                        ws.data_ptr(), ws_bytes, _stream()), "wireframe_decode")
+        head_h = head.cpu().numpy()                                          # the one synchronisation
+        koff_h, nv_h, st_h = head_h[:B + 1], head_h[B + 1:2 * B + 1], head_h[2 * B + 1:]
+        K = int(koff_h[B])
+        # one packed device->host transfer: vertices | slots | pairs | segments | probabilities, as raw 32-bit words
+        words = torch.cat([dverts.reshape(-1).view(torch.int32), slots.reshape(-1), pairs[:K].reshape(-1),
+                           seg[:K].reshape(-1).view(torch.int32), kprob[:K].view(torch.int32)]).cpu().numpy()
+        nv, ns = B * V * 3, B * V
+        pv = words[:nv].view(np.float32).reshape(B, V, 3)
+        sl = words[nv:nv + ns].reshape(B, V)
+        o = nv + ns
+        pe = words[o:o + 2 * K].reshape(K, 2).astype(np.int64)
+        ps = words[o + 2 * K:o + 8 * K].view(np.float32).reshape(K, 2, 3)
+        pp = words[o + 8 * K:].view(np.float32)
+        keep = {"koff": koff, "seg": seg, "dverts": dverts, "nverts": nverts, "status": status}
+    out = []
+    for s in range(B):
+        a, b, n = int(koff_h[s]), int(koff_h[s + 1]), int(nv_h[s])
+        out.append({"pred_vertices": pv[s, :n].copy(), "pd_edges": pe[a:b].copy(), "pd_edges_vertices": ps[a:b].copy(),
+                    "pd_edge_probs": pp[a:b].copy(), "slots": sl[s, :n].astype(np.int64)})
+    if keep_device:
+        return out, dict(keep, koff_host=koff_h, status_host=st_h)
+    return out
+
+
+def _decoded(predictions, threshold, decode):
+    """(samples, device dict) of the batch: wireframes_compact, or decode_wireframes under the `decode` options."""
+    if decode is None:
+        return wireframes_compact(predictions, threshold, keep_device=True)
+    return decode_wireframes(predictions, **decode, keep_device=True)
+
+
 def _as_numpy(x):
     return x.numpy() if torch.is_tensor(x) else np.asarray(x)
 
@@ -148,10 +252,11 @@ def _compute_sample(ap_calculator, w, gt_v, gt_e, gt_ev, hd):
                                    "hausdorff": [hd]})
 
 
-def _evaluate_batch_compact(predictions, wf_vertices, wf_edges, ap_calculator, threshold, sample_points=20):
+def _evaluate_batch_compact(predictions, wf_vertices, wf_edges, ap_calculator, threshold, sample_points=20, decode=None):
     """evaluate_batch on the compacted edges: every sample's Hausdorff matrix from ONE launch over the segments that
-    wireframes_compact left on the device, the label segments uploaded once, the matrices read back in one copy."""
-    samples, d = wireframes_compact(predictions, threshold, keep_device=True)
+    wireframes_compact (or, with `decode`, decode_wireframes) left on the device, the label segments uploaded once, the
+    matrices read back in one copy."""
+    samples, d = _decoded(predictions, threshold, decode)
     B = len(samples)
     dev = d["seg"].device
     n = np.diff(d["koff_host"]).astype(np.int64)
@@ -247,20 +352,25 @@ class EvalLabels:
         return (wed_e + (distances + snap)) / total
 
 
-def _evaluate_batch_device(predictions, wf_vertices, wf_edges, ap_calculator, threshold, labels, sample_points=20):
+def _evaluate_batch_device(predictions, wf_vertices, wf_edges, ap_calculator, threshold, labels, sample_points=20, decode=None):
     """evaluate_batch(compact=True) with everything that follows the Hausdorff matrices on the device too
-    (wf3d_eval_metrics): the matrices stay there, [B] distances and [B, 8] counters come back in one copy."""
+    (wf3d_eval_metrics): the matrices stay there, [B] distances and [B, 8] counters come back in one copy.  With `decode`
+    the vertices are the decoded ones, each sample with its own count (wf3d_eval_metrics_nv), and a sample whose decode
+    status is not zero takes the per-sample host call."""
     if labels is None:
         labels = EvalLabels(wf_vertices, wf_edges, predictions["vertices"].device)
-    samples, d = wireframes_compact(predictions, threshold, keep_device=True)
+    samples, d = _decoded(predictions, threshold, decode)
     B = len(samples)
     dev = d["seg"].device
     if len(labels) != B or labels.device != dev:
         raise ValueError(f"evaluate_batch(metrics='device'): labels of {len(labels)} samples on {labels.device} for a batch "
                          f"of {B} on {dev}")
-    verts = predictions["vertices"].detach().float()
-    if verts.stride(2) != 1:
-        verts = verts.contiguous()
+    if decode is None:
+        verts = predictions["vertices"].detach().float()
+        if verts.stride(2) != 1:
+            verts = verts.contiguous()
+    else:
+        verts = d["dverts"]
     V = verts.shape[1]
     n = np.diff(d["koff_host"]).astype(np.int64)
     m = labels.nsegs
@@ -283,16 +393,21 @@ def _evaluate_batch_device(predictions, wf_vertices, wf_edges, ap_calculator, th
     max_long = int(max(n.max(), m.max())) if B else 0
     ws_bytes = lib.wf3d_eval_metrics_ws_bytes(B, V, total_lv, max_long)
     ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=dev)
-    check(lib.wf3d_eval_metrics(verts.data_ptr(), verts.stride(0), verts.stride(1), B, V, d["seg"].data_ptr(),
-                                d["koff"].data_ptr(), labels.lverts.data_ptr(), labels.lvoff.data_ptr(), labels.lseg.data_ptr(),
-                                labels.loff.data_ptr(), hd.data_ptr(), d_ooff.data_ptr(), d_aoff.data_ptr(), assign.data_ptr(),
-                                float(ap_calculator.distance_thresh), max_lv, total_lv, max_long, out[2 * B:].data_ptr(),
-                                out.data_ptr(), ws.data_ptr(), ws_bytes, _stream()), "eval_metrics")
+    tail = (d["seg"].data_ptr(), d["koff"].data_ptr(), labels.lverts.data_ptr(), labels.lvoff.data_ptr(), labels.lseg.data_ptr(),
+            labels.loff.data_ptr(), hd.data_ptr(), d_ooff.data_ptr(), d_aoff.data_ptr(), assign.data_ptr(),
+            float(ap_calculator.distance_thresh), max_lv, total_lv, max_long, out[2 * B:].data_ptr(), out.data_ptr(),
+            ws.data_ptr(), ws_bytes, _stream())
+    if decode is None:
+        check(lib.wf3d_eval_metrics(verts.data_ptr(), verts.stride(0), verts.stride(1), B, V, *tail), "eval_metrics")
+    else:
+        check(lib.wf3d_eval_metrics_nv(verts.data_ptr(), verts.stride(0), verts.stride(1), B, V, d["nverts"].data_ptr(), *tail),
+              "eval_metrics_nv")
+    flagged = np.zeros(B, dtype=bool) if decode is None else d["status_host"] != 0
     words = out.cpu().numpy()                                            # the one copy back
     dist, cnt = words[:2 * B].view(np.float64), words[2 * B:].reshape(B, 8)
     names = ("tp_corners", "tp_fp_corners", "tp_fn_corners", "tp_edges", "tp_fp_edges", "tp_fn_edges")
     for s, w in enumerate(samples):
-        if labels.host[s] or cnt[s, 6] != 0:
+        if labels.host[s] or cnt[s, 6] != 0 or flagged[s]:
             # today's per-sample call, with the sample's own matrix where the batch launch made one
             mat = hd[ooff[s]:ooff[s + 1]].cpu().numpy().reshape(n[s], m[s]) if n[s] * m[s] > 0 else None
             _compute_sample(ap_calculator, w, labels.verts[s], labels.edges[s], labels.segs[s], mat)
@@ -304,7 +419,8 @@ def _evaluate_batch_device(predictions, wf_vertices, wf_edges, ap_calculator, th
         ap_calculator.ap_dict["wed"] += labels.wed(s, dist[s]) if n[s] > 0 else 1
 
 
-def evaluate_batch(predictions, wf_vertices, wf_edges, ap_calculator, threshold=0.5, compact=False, metrics="host", labels=None):
+def evaluate_batch(predictions, wf_vertices, wf_edges, ap_calculator, threshold=None, compact=False, metrics="host", labels=None,
+                   decode=None):
     """The body of the reference's evaluation loop (evaluate.py:74-110) for one batch: `wf_vertices` / `wf_edges` are the
     collate_batch lists of tensors; accumulates into `ap_calculator`.
     compact=True: the kept edges are compacted on the device (wireframes_compact) and all Hausdorff matrices of the batch
@@ -318,15 +434,39 @@ def evaluate_batch(predictions, wf_vertices, wf_edges, ap_calculator, threshold=
     wf_vertices / wf_edges, which are otherwise unused).  A sample the device flags (a non-finite value, kept edges of
     which none matches — the reference raises there, and so does this —, a matched end point that is no vertex row), one
     whose label vertices are not float32 and one whose label has no edge take today's per-sample call.  Where a sample's
-    optimal assignment is not unique, the device's choice (the tie rule of tests/lsa_model.py) may differ from scipy's."""
+    optimal assignment is not unique, the device's choice (the tie rule of tests/lsa_model.py) may differ from scipy's.
+    threshold: the edge probability threshold, 0.5 when not given.
+    decode: None (today's paths, unchanged: every one of the V slots is a predicted corner, as in the reference) or a dict
+    of decode_wireframes' options (DECODE_OPTIONS).  The batch is then decoded once and every path is fed from the decoded
+    wireframes: the per-sample host call and compact=True from the decoded samples (the Hausdorff matrices from the
+    decoded segments), metrics="device" from the decoded vertices with each sample's own count (wf3d_eval_metrics_nv); a
+    sample the decode flags (a non-finite slot) takes the per-sample host call there.  `threshold` and
+    decode["edge_threshold"] given together and different: ValueError.  CPU predictions decode through the numpy
+    specification (compact=False only)."""
     if metrics not in ("host", "device"):
         raise ValueError(f"evaluate_batch: metrics must be 'host' or 'device' (got {metrics!r})")
+    if decode is not None:
+        unknown = sorted(set(decode) - set(DECODE_OPTIONS))
+        if unknown:
+            raise ValueError(f"evaluate_batch: unknown decode option(s) {unknown}; the options are {DECODE_OPTIONS}")
+        if threshold is not None and "edge_threshold" in decode and decode["edge_threshold"] != threshold:
+            raise ValueError(f"evaluate_batch: threshold={threshold!r} and decode['edge_threshold']={decode['edge_threshold']!r} differ")
+        decode = dict(decode)
+        if threshold is not None:
+            decode["edge_threshold"] = threshold
+    if threshold is None:
+        threshold = 0.5
     if metrics == "device":
         if not compact:
             raise ValueError("evaluate_batch: metrics='device' needs compact=True")
-        return _evaluate_batch_device(predictions, wf_vertices, wf_edges, ap_calculator, threshold, labels)
+        return _evaluate_batch_device(predictions, wf_vertices, wf_edges, ap_calculator, threshold, labels, decode=decode)
     if compact:
-        return _evaluate_batch_compact(predictions, wf_vertices, wf_edges, ap_calculator, threshold)
+        return _evaluate_batch_compact(predictions, wf_vertices, wf_edges, ap_calculator, threshold, decode=decode)
+    if decode is not None:
+        for s, w in enumerate(decode_wireframes(predictions, **decode)):
+            gt_v, gt_e = _as_numpy(wf_vertices[s]), _as_numpy(wf_edges[s]).astype(np.int64)
+            _compute_sample(ap_calculator, w, gt_v, gt_e, _gt_edge_vertices(gt_v, gt_e), None)
+        return
     for s, w in enumerate(wireframes_from_predictions(predictions, threshold)):
         gt_v = wf_vertices[s].numpy() if torch.is_tensor(wf_vertices[s]) else np.asarray(wf_vertices[s])
         gt_e = (wf_edges[s].numpy() if torch.is_tensor(wf_edges[s]) else np.asarray(wf_edges[s])).astype(np.int64)
