@@ -941,6 +941,53 @@ int wf3d_cloud_sample_fps(const double* norm, const long* first, int nclouds, co
  * The caller sees to it that no batch of `members` breaks the rules of the launches behind it (row capacity, V). */
 int wf3d_cloud_epoch_params(uint64_t* state, const int32_t* members, int D, const long* first, int nclouds, int B, int world,
                             int rank, int P, int augment, void* params, uint32_t* seed_words, void* stream);
+/* THE AUGMENTATION EXTENSION of the sampled forms: a random scale, per-point jitter and random point dropout inside the
+ * gather — still one launch, float64 and one rounding.  wf3d.sampling.augment_point / jitter_noise / dropped are the
+ * specification, bit for bit.  The EXTENSION BLOCK `ext` is float64 [B, 8] in device memory, 8-byte aligned, BESIDE the
+ * parameter block (whose layout does not change): per sample {sx, sy, sz, sigma, clip, drop, 0, 0}.  The host fills it,
+ * or wf3d_cloud_epoch_params_ext writes it.  With (key, key2) the row sampler's keys of sample b under seed_words[0]
+ * and K = key * 2^32 | key2, output row p of sample b is
+ *     dropped    iff p >= 1 and (mix64(K ^ 0x1F83D9ABFB41BD6B, p) >> 11) * 2^-53 < drop; p_eff = 0 if dropped, else p: a
+ *                dropped row is an exact copy of output row 0 (row 0 is never dropped)
+ *     its source idx(b, p_eff) of the plain entry point, and (xr, yr, z) that entry point's float64 values BEFORE its rounding
+ *     g_k      = (double)(S_k - 131070) * 0x1.bb67ae8584caap-16, S_k the sum of the four 16-bit fields of
+ *                mix64(K ^ 0x9B05688C2B3E6C1F, 3 * p_eff + k), k = 0, 1, 2: Irwin-Hall of four, mean 0, variance 1,
+ *                |g| <= 3.4641, no transcendental
+ *     j_k      = min(max(sigma * g_k, -clip), clip)
+ *     x' = xr * sx + j_0, y' = yr * sy + j_1, z' = z * sz + j_2: every operation rounded on its own (no fma), then ONE
+ *                rounding to fp32; sigma == 0 adds nothing, so a -0.0 keeps its sign.  Columns 3 and up are the plain form's.
+ * An identity row {1, 1, 1, 0, inf, 0} gives the plain entry point's bits.  No value of `ext` moves an address: it
+ * changes arithmetic and replaces p by 0, nothing else.  In a block the host did not build, a NaN scale, sigma or clip
+ * gives NaN coordinates and a NaN drop drops nothing; a dead sample is still all zeros.
+ * wf3d_cloud_sample_dev_ext / wf3d_cloud_sample_fps_ext: the plain argument lists plus `ext` (NULL: WF3D_ERR_ARG), the
+ *   same kernels with the extension compiled in.  At C = 8, x, y and z sit in the even lane of a row's pair; the odd
+ *   lane and every 16-byte access are the plain form's.  Farthest-point sampling leaves its rounds alone — distances are
+ *   measured on the resident coordinates, unscaled (an anisotropic scale is no isometry: accepted) — takes idx(b, 0)
+ *   for a dropped row and reports that index in idx_out.
+ * wf3d_wireframe_targets_ext: vertices = the plain form's float64 values times (sx, sy, sz), each product rounded on its
+ *   own, then one rounding to fp32; no jitter, no dropout.  vertex_existence, vertex_counts and edge_labels are the
+ *   plain form's bits, and so are the vertices where sx = sy = sz = 1.
+ * wf3d_cloud_epoch_params_ext: wf3d_cloud_epoch_params, which also writes every byte of `ext` — still one workgroup, one
+ *   launch, t += 1 once.  cfg: HOST memory, 8 doubles {lo, hi, anisotropic (0 or 1), sigma, clip, max_dropout, 0, 0},
+ *   held to wf3d.sampling.check_augment: finite 0 < lo <= hi, finite sigma >= 0, clip > 0 (inf: no clip), max_dropout
+ *   in [0, 1], else WF3D_ERR_ARG before any launch.  With c = e * 2^32 + g as for the flips
+ *   (wf3d.sampling.epoch_augment_ext):
+ *     s_k  = lo + u_k * (hi - lo), u_k = (mix64(key ^ (0xA54FF53A5F1D36F1 + k), c) >> 11) * 2^-53; k = 0, 1, 2 when
+ *            anisotropic, else k = 0 for the three axes
+ *     drop = u_d * max_dropout, u_d from 0x510E527FADE682D1; sigma and clip copied
+ *   so scale and dropout ratio depend on (epoch, global slot) only and are world-size invariant; jitter and the dropped
+ *   rows are keyed by seed_words[0] and the LOCAL b, per (step, rank) like the row choice, and are not. */
+int wf3d_cloud_sample_dev_ext(const double* norm, const long* first, int nclouds, const void* params, const uint32_t* seed_words,
+                              int B, int P, int C, float* points, const double* ext, void* stream);
+int wf3d_cloud_sample_fps_ext(const double* norm, const long* first, int nclouds, const void* params, const uint32_t* seed_words,
+                              int B, int P, int C, float* points, int32_t* idx_out, long max_rows, void* ws, size_t ws_bytes,
+                              const double* ext, void* stream);
+int wf3d_wireframe_targets_ext(const double* wf_vertices, const int32_t* wf_edges, const long* vfirst, const long* efirst, int nclouds,
+                               const void* params, int B, int V, float* vertices, float* vertex_existence, int64_t* vertex_counts,
+                               float* edge_labels, const double* ext, void* stream);
+int wf3d_cloud_epoch_params_ext(uint64_t* state, const int32_t* members, int D, const long* first, int nclouds, int B, int world,
+                                int rank, int P, int augment, void* params, uint32_t* seed_words, const double* cfg, double* ext,
+                                void* stream);
 /* HOST function: the numbers of a whitespace-separated text file (.xyz: 8 per row; np.loadtxt, :98) into out[0..max_vals);
  * returns the count in the file (call again with a larger buffer if > max_vals), -1 unreadable, -2 not a number: a token
  * is every character up to whitespace, `#` or the end, and the whole of it must be one decimal number, inf or nan, as

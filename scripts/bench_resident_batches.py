@@ -44,6 +44,13 @@ longest fixture cloud (2,479 rows).  The GB/s figure of an FPS sampler says noth
 
     python scripts/bench_resident_batches.py --form fixed --sampler fps --batch-sizes 32 --num-points 2560 --out profiles/r19_fps_batches.jsonl
 
+--augment (both forms above): the sampled buffers carry the augmentation extension (`sampled_buffers(..., augment=AUGMENT)`:
+anisotropic scale, clipped jitter, point dropout), so the same arms run the `_ext` entry points — per point three 64-bit
+hashes for the jitter and one for the dropout on top of the plain gather.  Without it the lines are what they were, plus
+"augment": null.
+
+    python scripts/bench_resident_batches.py --form epoch --augment --batch-sizes 32 --num-points 4096 --out profiles/r20_augment_batches.jsonl
+
 Prints one JSON line per batch size and appends them to --out.
 """
 import argparse
@@ -65,6 +72,14 @@ from wf3d.targets import train_targets  # noqa: E402
 
 KEYS = ("vertices", "vertex_existence", "edge_labels", "vertex_counts")
 V = 16
+AUGMENT = {"scale": (0.8, 1.25), "anisotropic": True, "jitter_sigma": 0.01, "jitter_clip": 0.05, "max_dropout": 0.875}
+
+
+def sampled_buffers(cache, B, P, args):
+    """--augment: with the extension; else exactly the call this script always made"""
+    if args.augment:
+        return cache.sampled_buffers(B, V, P, sampler=args.sampler, augment=AUGMENT)
+    return cache.sampled_buffers(B, V, P, sampler=args.sampler)
 
 
 def fixture_dataset():
@@ -179,7 +194,7 @@ def run_fixed(B, ds, cache, dev, args):
     P = args.num_points
     ds.num_points = P
     idxs = batch_indices(B, ds, cache, args)
-    buf = cache.sampled_buffers(B, V, P, sampler=args.sampler)
+    buf = sampled_buffers(cache, B, P, args)
     np.random.seed(0)
     cache.stage(buf, idxs)
     cache.fill(buf)
@@ -223,12 +238,13 @@ def run_fixed(B, ds, cache, dev, args):
                           cache.norm.data_ptr(), cache.first.data_ptr(), ids.data_ptr(), choice.data_ptr(), aug.data_ptr(), B, P,
                           cache.ncol, out.data_ptr(), _stream()), "cloud_sample")),
                       "sampler": timed(lambda: cache._sample(buf["params"], buf["sample_words"], out,
-                                                             buf if args.sampler == "fps" else None)),
+                                                             buf if args.sampler == "fps" else None,
+                                                             *((buf["aug_ext"],) if args.augment else ()))),
                       "graph": timed(graph.replay)}, args.blocks, args.block_steps, args.warmup)
     nbytes = B * P * cache.ncol * 12
     b, r = summary(med["batch"]), summary(med["sampled"])
     dev_us = {k: summary(v, 2) for k, v in dmed.items()}
-    return {"bench": "sampled_batches", "sampler": args.sampler, "B": B, "num_points": P, "columns": cache.ncol, "max_vertices": V,
+    return {"bench": "sampled_batches", "sampler": args.sampler, "augment": AUGMENT if args.augment else None, "B": B, "num_points": P, "columns": cache.ncol, "max_vertices": V,
             "cloud_rows": sorted(set(cache.n[i] for i in idxs)), "blocks": args.blocks, "steps_per_block": args.block_steps,
             "reps": args.reps, "batch_ms": b, "sampled_ms": r, "batch_over_sampled": round(b["median"] / r["median"], 2),
             "h2d_bytes_batch": B * P * 4 + 36 * B, "h2d_bytes_sampled": 40 * B + 4, "device_us": dev_us, "point_bytes": nbytes,
@@ -247,7 +263,7 @@ def run_epoch(B, ds, cache, dev, args):
     graphs, bufs = {}, {}
     np.random.seed(0)
     for name in ("sampled", "epoch"):
-        buf = bufs[name] = cache.sampled_buffers(B, V, P, sampler=args.sampler)
+        buf = bufs[name] = sampled_buffers(cache, B, P, args)
         fill = (lambda b=buf: cache.fill(b)) if name == "sampled" else (lambda b=buf: cache.fill_epoch(b, sampler))
         if name == "sampled":
             cache.stage(buf, idxs)
@@ -291,7 +307,7 @@ def run_epoch(B, ds, cache, dev, args):
     t = int(sampler.get_state()[1])
     cloud = cache._block_views(bufs["epoch"]["params"].cpu(), B)[1]
     s, e = summary(med["sampled"]), summary(med["epoch"])
-    return {"bench": "epoch_batches", "sampler": args.sampler, "B": B, "num_points": P, "columns": cache.ncol, "max_vertices": V,
+    return {"bench": "epoch_batches", "sampler": args.sampler, "augment": AUGMENT if args.augment else None, "B": B, "num_points": P, "columns": cache.ncol, "max_vertices": V,
             "cloud_rows": sorted(set(cache.n[i] for i in idxs)), "members": len(members),
             "steps_per_epoch": sampler.steps_per_epoch, "blocks": args.blocks, "steps_per_block": args.block_steps, "reps": args.reps,
             "stage_replay_ms": s, "epoch_replay_ms": e, "stage_replay_over_epoch": round(s["median"] / e["median"], 2),
@@ -311,6 +327,7 @@ def main():
     ap.add_argument("--num-points", type=int, default=4096)
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--sampler", choices=("device", "fps"), default="device", help="--form fixed / epoch: how the rows are chosen")
+    ap.add_argument("--augment", action="store_true", help="--form fixed / epoch: the sampled buffers carry the augmentation extension")
     ap.add_argument("--longest", action="store_true", help="--form fixed / epoch: every sample is the longest fixture cloud")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "r06_resident_batches.jsonl"))
     args = ap.parse_args()

@@ -25,10 +25,16 @@
 //   cloud_epoch_params_kernel per batch of a resident epoch: WRITES that parameter block and the seed words — which clouds
 //                            (a keyed permutation per epoch, sharded over ranks), their augmentation, the row offsets —
 //                            from a 16-byte state in device memory, so nothing of a batch is made on the host.
+//   the `_ext` forms         cloud_sample_dev, cloud_fps, cloud_epoch_params and wireframe_targets once more with the
+//                            augmentation extension (a random scale, per-point jitter, random point dropout;
+//                            wf3d/sampling.py augment_point) as a compile-time form of the same bodies.
 // Plus the host-side text parser for .xyz files (np.loadtxt replacement): wf3d_parse_floats.
 #include <locale.h>
 #include <stdio.h>
 #include <stdlib.h>
+
+#include <cmath>
+#include <type_traits>
 
 #include "wf3d_common.h"
 
@@ -263,17 +269,87 @@ __device__ __forceinline__ void rotate_xy(const Augment& A, double u0, double u1
     oy = fma(x, A.sn, y * A.c);
 }
 
-// C = 8: this lane's half of the row (cloud_pack8_kernel's layout), four fp32 as one 16-byte store
+__device__ __forceinline__ uint64_t mix64(uint64_t key, uint64_t n) {           // csrc/random.hip's splitmix64 step
+    uint64_t z = key + (n + 1) * 0x9E3779B97F4A7C15ull;
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    return z ^ (z >> 31);
+}
+
+// The augmentation extension (wf3d/sampling.py augment_point, the specification): row b of ext [B, 8] float64 beside the
+// parameter block, {sx, sy, sz, sigma, clip, drop, 0, 0}.  It changes arithmetic and replaces an output position p by 0
+// (a dropped row is a copy of row 0), nothing else: no value of it reaches an address.  NoExt is the plain form's.
+struct NoExt {};
+struct Ext { double sx, sy, sz, sigma, clip, drop; };
+// what a kernel takes by value: nothing for the plain form (its arguments are what they were), the block's address
+struct NoExtBlock { using Row = NoExt; };
+struct ExtBlock { using Row = Ext; const double* ext; };
+__device__ __forceinline__ NoExt sample_ext(const NoExtBlock&, int, bool) { return {}; }
+__device__ __forceinline__ Ext sample_ext(const ExtBlock& xb, int b, bool live) {
+    if (!live) return {1, 1, 1, 0, HUGE_VAL, 0};
+    const double* e = xb.ext + (long)b * 8;
+    return {e[0], e[1], e[2], e[3], e[4], e[5]};
+}
+
+// K of the specification for sample b (the sample's keys under the batch's seed word) under one of the two salts
+constexpr uint64_t KEY_JITTER = 0x9B05688C2B3E6C1Full, KEY_DROP = 0x1F83D9ABFB41BD6Bull;
+__device__ __forceinline__ uint64_t point_key(const SamplePlan& s, uint64_t salt) {
+    return (((uint64_t)s.key << 32) | (uint64_t)s.key2) ^ salt;
+}
+
+// p_eff: 0 for a dropped output row (p >= 1 and u < drop; a NaN drop drops nothing), else p
+__device__ __forceinline__ uint32_t effective_row(const SamplePlan& s, const NoExt&, uint32_t p) { return p; }
+__device__ __forceinline__ uint32_t effective_row(const SamplePlan& s, const Ext& X, uint32_t p) {
+    const double u = (double)(mix64(point_key(s, KEY_DROP), p) >> 11) * 0x1p-53;       // exact: 53 bits, a power of two
+    return p >= 1u && u < X.drop ? 0u : p;
+}
+
+// S_k - 131070 of row p_eff: the sum of the four 16-bit fields of a 64-bit hash, centred (Irwin-Hall of four)
+struct Noise { int s[3]; };
+__device__ __forceinline__ Noise point_noise(const SamplePlan& s, uint32_t p_eff) {
+    const uint64_t K = point_key(s, KEY_JITTER);
+    Noise g;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const uint64_t z = mix64(K, 3ull * p_eff + (uint64_t)k);
+        g.s[k] = (int)((z & 0xFFFF) + ((z >> 16) & 0xFFFF) + ((z >> 32) & 0xFFFF) + (z >> 48)) - 131070;
+    }
+    return g;
+}
+
+// v sk + min(max(sigma g, -clip), clip), every operation rounded on its own; sigma == 0 adds nothing; a NaN sigma or
+// clip gives a NaN (numpy's minimum / maximum)
+__device__ __forceinline__ double ext_axis(double v, double scale, const Ext& X, int s) {
+#pragma clang fp contract(off)
+    const double w = v * scale;
+    if (X.sigma == 0.0) return w;
+    double j = X.sigma * ((double)s * 0x1.bb67ae8584caap-16);    // the double nearest to sqrt(3) 2^-16
+    j = j < -X.clip ? -X.clip : j;
+    j = j > X.clip ? X.clip : j;
+    j = X.clip != X.clip ? X.clip : j;
+    return w + j;
+}
+__device__ __forceinline__ void ext_xyz(const NoExt&, const Noise&, double&, double&, double&) {}
+__device__ __forceinline__ void ext_xyz(const Ext& X, const Noise& g, double& x, double& y, double& z) {
+    x = ext_axis(x, X.sx, X, g.s[0]);
+    y = ext_axis(y, X.sy, X, g.s[1]);
+    z = ext_axis(z, X.sz, X, g.s[2]);
+}
+
+// C = 8: this lane's half of the row (cloud_pack8_kernel's layout), four fp32 as one 16-byte store; x, y and z all sit
+// in the even lane, so the extension touches that lane only
+template <class E>
 __device__ __forceinline__ void gather_half_row8(const double* __restrict__ norm, bool live, long src, int half, const Augment& A,
-                                                 float* __restrict__ o) {
+                                                 const E& X, const Noise& g, float* __restrict__ o) {
     f32x4 v = {0.f, 0.f, 0.f, 0.f};
     if (live) {
         const f64x2* row = reinterpret_cast<const f64x2*>(norm + src * 8) + half * 2;
         const f64x2 u = row[0], w = row[1];
         if (half == 0) {
-            double x, y;
+            double x, y, z = w[0];
             rotate_xy(A, u[0], u[1], x, y);
-            v = f32x4{(float)x, (float)y, (float)w[0], (float)w[1]};
+            ext_xyz(X, g, x, y, z);
+            v = f32x4{(float)x, (float)y, (float)z, (float)w[1]};
         } else {
             v = f32x4{(float)u[0], (float)u[1], (float)w[0], (float)w[1]};
         }
@@ -282,18 +358,22 @@ __device__ __forceinline__ void gather_half_row8(const double* __restrict__ norm
 }
 
 // any C: the whole row in one lane
+template <class E>
 __device__ __forceinline__ void gather_row(const double* __restrict__ norm, bool live, long src, int C, const Augment& A,
-                                           float* __restrict__ o) {
+                                           const E& X, const Noise& g, float* __restrict__ o) {
     if (!live) {
         for (int k = 0; k < C; ++k) o[k] = 0.f;
         return;
     }
     const double* row = norm + src * C;
-    double x, y;
+    double x, y, z = row[2];
     rotate_xy(A, row[0], row[1], x, y);
+    ext_xyz(X, g, x, y, z);
     o[0] = (float)x;
     o[1] = (float)y;
-    for (int k = 2; k < C; ++k) o[k] = (float)row[k];
+    constexpr int K0 = std::is_same<E, NoExt>::value ? 2 : 3;   // z is the extension's too
+    if (K0 == 3) o[2] = (float)z;
+    for (int k = K0; k < C; ++k) o[k] = (float)row[k];
 }
 
 // C = 8, cloud_pack8_kernel's layout: two lanes per row, 16-byte accesses, consecutive lanes store consecutive 16 bytes.
@@ -301,39 +381,60 @@ __device__ __forceinline__ void gather_row(const double* __restrict__ norm, bool
 // one ds_bpermute each (from lane j * 32 + l / 2) — against computing every index in both lanes of its pair, this
 // halves the Feistel rounds per row (6 x 11 VALU operations per application, times the longest walk of the wave) for
 // two cross-lane reads per 64 rows.  The shuffles come before any store guard, with the whole wave active.
+// The extension (E = Ext) rides the same scheme: lane l also decides whether row l is dropped (its index is then row 0's)
+// and hashes its three noise sums once, and the passes fetch them with three more shuffles each.
+template <class XB>
 __global__ __launch_bounds__(256) void cloud_sample_dev8_kernel(const double* __restrict__ norm, const long* __restrict__ first,
                                                                  int nclouds, const void* __restrict__ params,
                                                                  const uint32_t* __restrict__ seed_words, int B, int P,
-                                                                 float* __restrict__ out) {
+                                                                 float* __restrict__ out, const XB xb) {
+    constexpr bool EXT = std::is_same<XB, ExtBlock>::value;
     const BatchParams Q = batch_params(params, B);
     const int b = blockIdx.y, lane = threadIdx.x & 63;
     const long wave_row = (long)blockIdx.x * 256 + (threadIdx.x & ~63);
     SamplePlan s;
     const bool live = sample_plan(Q, first, nclouds, seed_words, b, P, s);
+    const typename XB::Row X = sample_ext(xb, b, live);
     uint32_t idx = 0;
-    if (live && wave_row + lane < P) idx = sample_index(s, (uint32_t)(wave_row + lane));
+    Noise g = {};
+    if (live && wave_row + lane < P) {
+        const uint32_t p_eff = effective_row(s, X, (uint32_t)(wave_row + lane));
+        idx = sample_index(s, p_eff);
+        if constexpr (EXT) g = point_noise(s, p_eff);
+    }
     const uint32_t idx0 = __shfl(idx, lane >> 1, 64), idx1 = __shfl(idx, 32 + (lane >> 1), 64);
+    Noise g0 = {}, g1 = {};
+    if constexpr (EXT) {
+#pragma unroll
+        for (int k = 0; k < 3; ++k) { g0.s[k] = __shfl(g.s[k], lane >> 1, 64); g1.s[k] = __shfl(g.s[k], 32 + (lane >> 1), 64); }
+    }
     const Augment A = sample_augment(Q, b, live);
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
         const long p = wave_row + j * 32 + (lane >> 1);
         if (p >= P) continue;
-        gather_half_row8(norm, live, live ? s.r0 + (j ? idx1 : idx0) : 0, lane & 1, A, out + ((long)b * P + p) * 8);
+        gather_half_row8(norm, live, live ? s.r0 + (j ? idx1 : idx0) : 0, lane & 1, A, X, j ? g1 : g0, out + ((long)b * P + p) * 8);
     }
 }
 
 // any C (3 and 7 in this project): one lane per row
+template <class XB>
 __global__ __launch_bounds__(256) void cloud_sample_dev_kernel(const double* __restrict__ norm, const long* __restrict__ first,
                                                                 int nclouds, const void* __restrict__ params,
                                                                 const uint32_t* __restrict__ seed_words, int B, int P, int C,
-                                                                float* __restrict__ out) {
+                                                                float* __restrict__ out, const XB xb) {
+    constexpr bool EXT = std::is_same<XB, ExtBlock>::value;
     const BatchParams Q = batch_params(params, B);
     const int b = blockIdx.y;
     const long p = (long)blockIdx.x * 256 + threadIdx.x;
     if (p >= P) return;
     SamplePlan s;
     const bool live = sample_plan(Q, first, nclouds, seed_words, b, P, s);
-    gather_row(norm, live, live ? s.r0 + sample_index(s, (uint32_t)p) : 0, C, sample_augment(Q, b, live), out + ((long)b * P + p) * C);
+    const typename XB::Row X = sample_ext(xb, b, live);
+    const uint32_t p_eff = live ? effective_row(s, X, (uint32_t)p) : 0u;
+    Noise g = {};
+    if constexpr (EXT) { if (live) g = point_noise(s, p_eff); }
+    gather_row(norm, live, live ? s.r0 + sample_index(s, p_eff) : 0, C, sample_augment(Q, b, live), X, g, out + ((long)b * P + p) * C);
 }
 
 // ---- fixed-size batches by farthest-point sampling --------------------------------------------------------------------
@@ -410,11 +511,14 @@ __device__ __forceinline__ int fps_combine(const FpsSlot* __restrict__ slot, int
     return i;
 }
 
+template <class XB>
 __global__ __launch_bounds__(1024) void cloud_fps_kernel(const double* __restrict__ norm, const long* __restrict__ first,
                                                           int nclouds, const void* __restrict__ params,
                                                           const uint32_t* __restrict__ seed_words, int B, int P, int C, int shift,
                                                           float* __restrict__ out, int* __restrict__ idx_out,
-                                                          double* __restrict__ ws_d, int* __restrict__ ws_order, long ws_rows) {
+                                                          double* __restrict__ ws_d, int* __restrict__ ws_order, long ws_rows,
+                                                          const XB xb) {
+    constexpr bool EXT = std::is_same<XB, ExtBlock>::value;
     __shared__ FpsSlot slot[2][FPS_MAX_WAVES];
     __shared__ int order_s[WF3D_FPS_REG_ROWS];
     const BatchParams Q = batch_params(params, B);
@@ -496,18 +600,24 @@ __global__ __launch_bounds__(1024) void cloud_fps_kernel(const double* __restric
         }
     }
     __syncthreads();                                             // the order, for every thread (block-uniform: `live` is)
-    // the rows: idx(b, p) = order[p mod n], through cloud_sample_dev's gather
+    // the rows: idx(b, p) = order[p mod n], through cloud_sample_dev's gather; the rounds above know nothing of the
+    // extension, a dropped row takes idx(b, 0)
     const Augment A = sample_augment(Q, b, live);
+    const typename XB::Row X = sample_ext(xb, b, live);
     const long rows = (long)P << (C == 8 ? 1 : 0);               // C = 8: two lanes per row, consecutive lanes 16 bytes apart
     for (long t = tid; t < rows; t += T) {
         const long p = C == 8 ? t >> 1 : t;
         int idx = 0;
+        Noise g = {};
         if (live) {
-            const int q = (int)(p < n ? p : p % n);
+            long pe = p;
+            if constexpr (EXT) pe = effective_row(s, X, (uint32_t)p);
+            const int q = (int)(pe < n ? pe : pe % n);
             idx = in_regs ? order_s[q] : order_w[q];
+            if constexpr (EXT) { if (C != 8 || (t & 1) == 0) g = point_noise(s, (uint32_t)pe); }
         }
-        if (C == 8) gather_half_row8(norm, live, s.r0 + idx, (int)(t & 1), A, out + ((long)b * P + p) * 8);
-        else gather_row(norm, live, s.r0 + idx, C, A, out + ((long)b * P + p) * C);
+        if (C == 8) gather_half_row8(norm, live, s.r0 + idx, (int)(t & 1), A, X, g, out + ((long)b * P + p) * 8);
+        else gather_row(norm, live, s.r0 + idx, C, A, X, g, out + ((long)b * P + p) * C);
         if (idx_out && (C != 8 || (t & 1) == 0)) idx_out[(long)b * P + p] = idx;
     }
 }
@@ -517,13 +627,6 @@ __global__ __launch_bounds__(1024) void cloud_fps_kernel(const double* __restric
 // shuffled, rank-sharded, augmented walk over `members`, from state = {key, t} in device memory.  One workgroup; thread
 // i owns the slots [i * K, (i + 1) * K), K = ceil(B / 256) <= 16, so the packed form's row offsets are one scan over 256
 // partial sums.
-__device__ __forceinline__ uint64_t mix64(uint64_t key, uint64_t n) {           // csrc/random.hip's splitmix64 step
-    uint64_t z = key + (n + 1) * 0x9E3779B97F4A7C15ull;
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-}
-
 // cos and sin of |t| <= pi / 36 as the specification's fixed polynomials: every operation rounded on its own (no fma),
 // so that numpy gives the same bits
 __device__ __forceinline__ void epoch_cos_sin(double t, double& c, double& s) {
@@ -543,10 +646,33 @@ __device__ __forceinline__ uint32_t cloud_rows(const long* __restrict__ first, i
     return cl >= 0 && cl < nclouds ? (uint32_t)(first[cl + 1] - first[cl]) : 0u;
 }
 
+// the extension's configuration, by value: {lo, hi - lo, sigma, clip, max_dropout}, one scale per axis or one for all,
+// and where the rows go (ext [B, 8] float64).  NoEpochExt is the plain form's.
+struct NoEpochExt {};
+struct EpochExt { double lo, width, sigma, clip, max_dropout; int anisotropic; double* ext; };
+constexpr uint64_t KEY_SCALE = 0xA54FF53A5F1D36F1ull, KEY_DROPOUT = 0x510E527FADE682D1ull;
+
+__device__ __forceinline__ void epoch_ext_row(const NoEpochExt&, uint64_t, uint64_t, int) {}
+// wf3d/sampling.py epoch_augment_ext: all eight doubles of row b, keyed by ctr = e 2^32 + g alone
+__device__ __forceinline__ void epoch_ext_row(const EpochExt& X, uint64_t key, uint64_t ctr, int b) {
+#pragma clang fp contract(off)
+    double* e = X.ext + (long)b * 8;
+    double sc[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const double u = (double)(mix64(key ^ (KEY_SCALE + (uint64_t)(X.anisotropic ? k : 0)), ctr) >> 11) * 0x1p-53;
+        const double w = u * X.width;
+        sc[k] = X.lo + w;
+    }
+    const double ud = (double)(mix64(key ^ KEY_DROPOUT, ctr) >> 11) * 0x1p-53;
+    e[0] = sc[0]; e[1] = sc[1]; e[2] = sc[2]; e[3] = X.sigma; e[4] = X.clip; e[5] = ud * X.max_dropout; e[6] = 0.0; e[7] = 0.0;
+}
+
+template <class E>
 __global__ __launch_bounds__(256) void cloud_epoch_params_kernel(uint64_t* state, const int32_t* __restrict__ members, int D,
                                                                   const long* __restrict__ first, int nclouds, int B, int world,
                                                                   int rank, int P, int augment, double span, double half_span,
-                                                                  void* params, uint32_t* __restrict__ seed_words) {
+                                                                  void* params, uint32_t* __restrict__ seed_words, const E X) {
     __shared__ uint32_t part[256];
     const int tid = threadIdx.x;
     const uint64_t key = state[0], t = state[1];
@@ -575,8 +701,9 @@ __global__ __launch_bounds__(256) void cloud_epoch_params_kernel(uint64_t* state
         cloud[b] = cl;
         if (P == 0) rows += cloud_rows(first, nclouds, cl);
         double fx = 1.0, fy = 1.0, c = 1.0, s = 0.0;
+        const uint64_t ctr = (e << 32) + (uint64_t)g;
+        epoch_ext_row(X, key, ctr, b);
         if (augment) {
-            const uint64_t ctr = (e << 32) + (uint64_t)g;
             const uint64_t za = mix64(key ^ 0x6A09E667F3BCC908ull, ctr), zb = mix64(key ^ 0xBB67AE8584CAA73Bull, ctr);
             fx = (za >> 63) & 1 ? -1.0 : 1.0;
             fy = (za >> 62) & 1 ? -1.0 : 1.0;
@@ -616,11 +743,15 @@ __global__ __launch_bounds__(256) void cloud_epoch_params_kernel(uint64_t* state
 // wf3d/targets.py train_targets(..., full_width=True) for sample b = blockIdx.x: c_s vertices augmented like the points,
 // zeros after; existence; the count; labels of all pairs of V vertices: the row is zeroed, then (after a barrier) every
 // edge min < max < c_s stores 1.0 at its pair's position among the pairs of c_s vertices.
+// EXT: the vertices follow the points' scale — (sx, sy, sz) of the sample's extension row, each product rounded on its
+// own behind the rotation's float64 values, one rounding to fp32; no jitter, and nothing else changes.
+template <bool EXT>
 __global__ __launch_bounds__(256) void wireframe_targets_kernel(const double* __restrict__ wfv, const int32_t* __restrict__ wfe,
                                                                  const long* __restrict__ vfirst, const long* __restrict__ efirst,
                                                                  int nclouds, const void* __restrict__ params, int B, int V,
                                                                  float* __restrict__ vertices, float* __restrict__ existence,
-                                                                 int64_t* __restrict__ counts, float* __restrict__ labels) {
+                                                                 int64_t* __restrict__ counts, float* __restrict__ labels,
+                                                                 const double* __restrict__ ext) {
     const BatchParams P = batch_params(params, B);
     const int b = blockIdx.x, tid = threadIdx.x;
     const int cl = P.cloud[b];
@@ -635,9 +766,16 @@ __global__ __launch_bounds__(256) void wireframe_targets_kernel(const double* __
         if (i < c) {
             const double* v = wfv + (v0 + i) * 3;
             const double x = fx * v[0], y = fy * v[1];
-            o[0] = (float)(x * co - y * si);
-            o[1] = (float)(x * si + y * co);
-            o[2] = (float)v[2];
+            double xr = x * co - y * si, yr = x * si + y * co, z = v[2];
+            if constexpr (EXT) {
+#pragma clang fp contract(off)
+                xr = xr * ext[(long)b * 8];
+                yr = yr * ext[(long)b * 8 + 1];
+                z = z * ext[(long)b * 8 + 2];
+            }
+            o[0] = (float)xr;
+            o[1] = (float)yr;
+            o[2] = (float)z;
         } else {
             o[0] = o[1] = o[2] = 0.f;
         }
@@ -696,8 +834,10 @@ extern "C" int wf3d_cloud_pack(const double* norm, const long* first, int ncloud
     return WF3D_OK;
 }
 
-extern "C" int wf3d_cloud_sample_dev(const double* norm, const long* first, int nclouds, const void* params,
-                                     const uint32_t* seed_words, int B, int P, int C, float* points, void* stream) {
+// the plain entry point and its `_ext` form (E = Ext, `ext` required): one argument list, one launch
+template <class XB>
+static int cloud_sample_dev_launch(const double* norm, const long* first, int nclouds, const void* params,
+                                   const uint32_t* seed_words, int B, int P, int C, float* points, const XB& xb, void* stream) {
     WF3D_CHECK(nclouds >= 1 && B >= 1 && B <= 4096 && P >= 1 && C >= 3 && C <= 16, WF3D_ERR_ARG, "wf3d_cloud_sample_dev: bad dims");
     WF3D_CHECK((long)B * P <= 0x7FFFFFFFL, WF3D_ERR_ARG, "wf3d_cloud_sample_dev: B * P must stay below 2^31");
     WF3D_CHECK(norm && first && params && seed_words && points, WF3D_ERR_ARG, "wf3d_cloud_sample_dev: null pointer");
@@ -706,14 +846,26 @@ extern "C" int wf3d_cloud_sample_dev(const double* norm, const long* first, int 
     const dim3 grid(wf3d_cdiv(P, 256), B);
     if (C == 8) {
         WF3D_CHECK((((uintptr_t)norm | (uintptr_t)points) & 15) == 0, WF3D_ERR_ARG, "wf3d_cloud_sample_dev: norm and points must be 16-byte aligned");
-        hipLaunchKernelGGL(cloud_sample_dev8_kernel, grid, dim3(256), 0, (hipStream_t)stream, norm, first, nclouds, params,
-                           seed_words, B, P, points);
+        hipLaunchKernelGGL(cloud_sample_dev8_kernel<XB>, grid, dim3(256), 0, (hipStream_t)stream, norm, first, nclouds, params,
+                           seed_words, B, P, points, xb);
     } else {
-        hipLaunchKernelGGL(cloud_sample_dev_kernel, grid, dim3(256), 0, (hipStream_t)stream, norm, first, nclouds, params,
-                           seed_words, B, P, C, points);
+        hipLaunchKernelGGL(cloud_sample_dev_kernel<XB>, grid, dim3(256), 0, (hipStream_t)stream, norm, first, nclouds, params,
+                           seed_words, B, P, C, points, xb);
     }
     WF3D_LAUNCH_CHECK();
     return WF3D_OK;
+}
+
+extern "C" int wf3d_cloud_sample_dev(const double* norm, const long* first, int nclouds, const void* params,
+                                     const uint32_t* seed_words, int B, int P, int C, float* points, void* stream) {
+    return cloud_sample_dev_launch(norm, first, nclouds, params, seed_words, B, P, C, points, NoExtBlock{}, stream);
+}
+
+extern "C" int wf3d_cloud_sample_dev_ext(const double* norm, const long* first, int nclouds, const void* params,
+                                         const uint32_t* seed_words, int B, int P, int C, float* points, const double* ext,
+                                         void* stream) {
+    WF3D_CHECK(ext && ((uintptr_t)ext & 7) == 0, WF3D_ERR_ARG, "wf3d_cloud_sample_dev_ext: ext must be given, 8-byte aligned");
+    return cloud_sample_dev_launch(norm, first, nclouds, params, seed_words, B, P, C, points, ExtBlock{ext}, stream);
 }
 
 // the workspace tier's d (float64) and order (int32) of max_rows rows per sample; nothing while every cloud fits the registers
@@ -722,9 +874,10 @@ extern "C" size_t wf3d_cloud_sample_fps_ws_bytes(int B, long max_rows) {
     return ((size_t)B * (size_t)max_rows * 12 + 15) & ~(size_t)15;
 }
 
-extern "C" int wf3d_cloud_sample_fps(const double* norm, const long* first, int nclouds, const void* params,
-                                     const uint32_t* seed_words, int B, int P, int C, float* points, int32_t* idx_out,
-                                     long max_rows, void* ws, size_t ws_bytes, void* stream) {
+template <class XB>
+static int cloud_sample_fps_launch(const double* norm, const long* first, int nclouds, const void* params,
+                                   const uint32_t* seed_words, int B, int P, int C, float* points, int32_t* idx_out,
+                                   long max_rows, void* ws, size_t ws_bytes, const XB& xb, void* stream) {
     WF3D_CHECK(nclouds >= 1 && B >= 1 && B <= 4096 && P >= 1 && C >= 3 && C <= 16 && max_rows >= 1 && max_rows <= 0x7FFFFFFFL,
                WF3D_ERR_ARG, "wf3d_cloud_sample_fps: bad dims");
     WF3D_CHECK((long)B * P <= 0x7FFFFFFFL, WF3D_ERR_ARG, "wf3d_cloud_sample_fps: B * P must stay below 2^31");
@@ -741,14 +894,31 @@ extern "C" int wf3d_cloud_sample_fps(const double* norm, const long* first, int 
     const long ws_rows = need ? max_rows : 0;
     double* ws_d = need ? (double*)ws : nullptr;
     int* ws_order = need ? (int*)(ws_d + (size_t)B * (size_t)ws_rows) : nullptr;
-    hipLaunchKernelGGL(cloud_fps_kernel, dim3(B), dim3(1 << shift), 0, (hipStream_t)stream, norm, first, nclouds, params, seed_words,
-                       B, P, C, shift, points, idx_out, ws_d, ws_order, ws_rows);
+    hipLaunchKernelGGL(cloud_fps_kernel<XB>, dim3(B), dim3(1 << shift), 0, (hipStream_t)stream, norm, first, nclouds, params, seed_words,
+                       B, P, C, shift, points, idx_out, ws_d, ws_order, ws_rows, xb);
     WF3D_LAUNCH_CHECK();
     return WF3D_OK;
 }
 
-extern "C" int wf3d_cloud_epoch_params(uint64_t* state, const int32_t* members, int D, const long* first, int nclouds, int B,
-                                       int world, int rank, int P, int augment, void* params, uint32_t* seed_words, void* stream) {
+extern "C" int wf3d_cloud_sample_fps(const double* norm, const long* first, int nclouds, const void* params,
+                                     const uint32_t* seed_words, int B, int P, int C, float* points, int32_t* idx_out,
+                                     long max_rows, void* ws, size_t ws_bytes, void* stream) {
+    return cloud_sample_fps_launch(norm, first, nclouds, params, seed_words, B, P, C, points, idx_out, max_rows, ws, ws_bytes,
+                                   NoExtBlock{}, stream);
+}
+
+extern "C" int wf3d_cloud_sample_fps_ext(const double* norm, const long* first, int nclouds, const void* params,
+                                         const uint32_t* seed_words, int B, int P, int C, float* points, int32_t* idx_out,
+                                         long max_rows, void* ws, size_t ws_bytes, const double* ext, void* stream) {
+    WF3D_CHECK(ext && ((uintptr_t)ext & 7) == 0, WF3D_ERR_ARG, "wf3d_cloud_sample_fps_ext: ext must be given, 8-byte aligned");
+    return cloud_sample_fps_launch(norm, first, nclouds, params, seed_words, B, P, C, points, idx_out, max_rows, ws, ws_bytes,
+                                   ExtBlock{ext}, stream);
+}
+
+template <class E>
+static int cloud_epoch_params_launch(uint64_t* state, const int32_t* members, int D, const long* first, int nclouds, int B,
+                                     int world, int rank, int P, int augment, void* params, uint32_t* seed_words, const E& X,
+                                     void* stream) {
     WF3D_CHECK(D >= 1 && nclouds >= 1 && B >= 1 && world >= 1 && rank >= 0 && rank < world && P >= 0 && (augment == 0 || augment == 1),
                WF3D_ERR_ARG, "wf3d_cloud_epoch_params: bad dims");
     WF3D_CHECK(B <= 4096, WF3D_ERR_UNSUPPORTED, "wf3d_cloud_epoch_params: B > 4096");
@@ -758,8 +928,47 @@ extern "C" int wf3d_cloud_epoch_params(uint64_t* state, const int32_t* members, 
     WF3D_CHECK((((uintptr_t)state | (uintptr_t)params) & 7) == 0 && (((uintptr_t)seed_words | (uintptr_t)members) & 3) == 0, WF3D_ERR_ARG,
                "wf3d_cloud_epoch_params: state and params must be 8-byte aligned, members and seed_words 4-byte aligned");
     const double pi = 3.141592653589793;                         // the double numpy calls pi; both quotients rounded once
-    hipLaunchKernelGGL(cloud_epoch_params_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, state, members, D, first, nclouds, B,
-                       world, rank, P, augment, pi / 18.0, pi / 36.0, params, seed_words);
+    hipLaunchKernelGGL(cloud_epoch_params_kernel<E>, dim3(1), dim3(256), 0, (hipStream_t)stream, state, members, D, first, nclouds, B,
+                       world, rank, P, augment, pi / 18.0, pi / 36.0, params, seed_words, X);
+    WF3D_LAUNCH_CHECK();
+    return WF3D_OK;
+}
+
+extern "C" int wf3d_cloud_epoch_params(uint64_t* state, const int32_t* members, int D, const long* first, int nclouds, int B,
+                                       int world, int rank, int P, int augment, void* params, uint32_t* seed_words, void* stream) {
+    return cloud_epoch_params_launch(state, members, D, first, nclouds, B, world, rank, P, augment, params, seed_words, NoEpochExt{},
+                                     stream);
+}
+
+// cfg (HOST memory): {lo, hi, anisotropic, sigma, clip, max_dropout, 0, 0}, held to wf3d.sampling.check_augment's rules
+extern "C" int wf3d_cloud_epoch_params_ext(uint64_t* state, const int32_t* members, int D, const long* first, int nclouds, int B,
+                                           int world, int rank, int P, int augment, void* params, uint32_t* seed_words,
+                                           const double* cfg, double* ext, void* stream) {
+    WF3D_CHECK(cfg && ext && ((uintptr_t)ext & 7) == 0, WF3D_ERR_ARG, "wf3d_cloud_epoch_params_ext: cfg and ext must be given, ext 8-byte aligned");
+    const double lo = cfg[0], hi = cfg[1], sigma = cfg[3], clip = cfg[4], max_dropout = cfg[5];
+    WF3D_CHECK(std::isfinite(lo) && std::isfinite(hi) && 0.0 < lo && lo <= hi, WF3D_ERR_ARG,
+               "wf3d_cloud_epoch_params_ext: scale needs finite 0 < lo <= hi");
+    WF3D_CHECK(cfg[2] == 0.0 || cfg[2] == 1.0, WF3D_ERR_ARG, "wf3d_cloud_epoch_params_ext: anisotropic must be 0 or 1");
+    WF3D_CHECK(std::isfinite(sigma) && sigma >= 0.0, WF3D_ERR_ARG, "wf3d_cloud_epoch_params_ext: sigma must be finite and >= 0");
+    WF3D_CHECK(clip > 0.0, WF3D_ERR_ARG, "wf3d_cloud_epoch_params_ext: clip must be > 0 (inf: no clip)");
+    WF3D_CHECK(max_dropout >= 0.0 && max_dropout <= 1.0, WF3D_ERR_ARG, "wf3d_cloud_epoch_params_ext: max_dropout must be in [0, 1]");
+    WF3D_CHECK(cfg[6] == 0.0 && cfg[7] == 0.0, WF3D_ERR_ARG, "wf3d_cloud_epoch_params_ext: cfg[6] and cfg[7] must be 0");
+    const EpochExt X = {lo, hi - lo, sigma, clip, max_dropout, cfg[2] == 1.0 ? 1 : 0, ext};
+    return cloud_epoch_params_launch(state, members, D, first, nclouds, B, world, rank, P, augment, params, seed_words, X, stream);
+}
+
+template <bool EXT>
+static int wireframe_targets_launch(const double* wf_vertices, const int32_t* wf_edges, const long* vfirst, const long* efirst,
+                                    int nclouds, const void* params, int B, int V, float* vertices, float* vertex_existence,
+                                    int64_t* vertex_counts, float* edge_labels, const double* ext, void* stream) {
+    WF3D_CHECK(nclouds >= 1 && B >= 1 && B <= 4096 && V >= 1 && V <= 32768, WF3D_ERR_ARG, "wf3d_wireframe_targets: bad dims");
+    // wf_vertices / wf_edges / edge_labels may be NULL where they hold nothing (no vertices, no edges, V = 1)
+    WF3D_CHECK(vfirst && efirst && params && vertices && vertex_existence && vertex_counts && (edge_labels || V < 2), WF3D_ERR_ARG,
+               "wf3d_wireframe_targets: null pointer");
+    WF3D_CHECK(((uintptr_t)params & 7) == 0, WF3D_ERR_ARG, "wf3d_wireframe_targets: params must be 8-byte aligned");
+    WF3D_CHECK(!EXT || (ext && ((uintptr_t)ext & 7) == 0), WF3D_ERR_ARG, "wf3d_wireframe_targets_ext: ext must be given, 8-byte aligned");
+    hipLaunchKernelGGL(wireframe_targets_kernel<EXT>, dim3(B), dim3(256), 0, (hipStream_t)stream, wf_vertices, wf_edges, vfirst, efirst,
+                       nclouds, params, B, V, vertices, vertex_existence, vertex_counts, edge_labels, ext);
     WF3D_LAUNCH_CHECK();
     return WF3D_OK;
 }
@@ -767,15 +976,15 @@ extern "C" int wf3d_cloud_epoch_params(uint64_t* state, const int32_t* members, 
 extern "C" int wf3d_wireframe_targets(const double* wf_vertices, const int32_t* wf_edges, const long* vfirst, const long* efirst,
                                       int nclouds, const void* params, int B, int V, float* vertices, float* vertex_existence,
                                       int64_t* vertex_counts, float* edge_labels, void* stream) {
-    WF3D_CHECK(nclouds >= 1 && B >= 1 && B <= 4096 && V >= 1 && V <= 32768, WF3D_ERR_ARG, "wf3d_wireframe_targets: bad dims");
-    // wf_vertices / wf_edges / edge_labels may be NULL where they hold nothing (no vertices, no edges, V = 1)
-    WF3D_CHECK(vfirst && efirst && params && vertices && vertex_existence && vertex_counts && (edge_labels || V < 2), WF3D_ERR_ARG,
-               "wf3d_wireframe_targets: null pointer");
-    WF3D_CHECK(((uintptr_t)params & 7) == 0, WF3D_ERR_ARG, "wf3d_wireframe_targets: params must be 8-byte aligned");
-    hipLaunchKernelGGL(wireframe_targets_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, wf_vertices, wf_edges, vfirst, efirst,
-                       nclouds, params, B, V, vertices, vertex_existence, vertex_counts, edge_labels);
-    WF3D_LAUNCH_CHECK();
-    return WF3D_OK;
+    return wireframe_targets_launch<false>(wf_vertices, wf_edges, vfirst, efirst, nclouds, params, B, V, vertices, vertex_existence,
+                                           vertex_counts, edge_labels, nullptr, stream);
+}
+
+extern "C" int wf3d_wireframe_targets_ext(const double* wf_vertices, const int32_t* wf_edges, const long* vfirst, const long* efirst,
+                                          int nclouds, const void* params, int B, int V, float* vertices, float* vertex_existence,
+                                          int64_t* vertex_counts, float* edge_labels, const double* ext, void* stream) {
+    return wireframe_targets_launch<true>(wf_vertices, wf_edges, vfirst, efirst, nclouds, params, B, V, vertices, vertex_existence,
+                                          vertex_counts, edge_labels, ext, stream);
 }
 
 // Host: the numbers of a whitespace-separated text table.  `#` starts a comment (to the end of the line: \n, \r\n or \r); numbers are

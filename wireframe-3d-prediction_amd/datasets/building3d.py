@@ -24,7 +24,13 @@ chooses the rows by farthest-point sampling instead (wf3d/sampling.py `fps_indic
 
 Resident epochs: `cache.epoch_sampler` / `fill_epoch` replace `stage` by a kernel — which clouds a batch holds (a keyed
 permutation per epoch, sharded over ranks), the augmentation and the seed words come from a 16-byte state in device memory
-(wf3d/sampling.py `epoch_batch` states them), so a loop of graph replays with nothing between them walks the data set."""
+(wf3d/sampling.py `epoch_batch` states them), so a loop of graph replays with nothing between them walks the data set.
+
+The augmentation extension: `augment=cfg` (wf3d.sampling.check_augment: scale, anisotropic, jitter_sigma, jitter_clip,
+max_dropout) on `sampled_buffers` or on `batch(..., sampler="device" | "fps")` adds a random scale, per-point jitter and
+random point dropout INSIDE the same gather launch (wf3d/sampling.py `augment_point`), independent of the data set's
+`augment` (flips and rotation).  The per-sample values live in an extension block of 64 B bytes beside the parameter
+block; `stage` draws them from np.random, `fill_epoch` on the device."""
 import ctypes
 import glob
 import operator
@@ -343,19 +349,22 @@ class DeviceCloudCache:
             wf_vertices /= md
         return wf_vertices, cen, md
 
-    def _item(self, idx, fx, fy, rot):
-        """__getitem__'s dict for cloud idx under one augmentation draw (flips, rot = rotz(angle)), without its point cloud."""
+    def _item(self, idx, fx, fy, rot, scale=None):
+        """__getitem__'s dict for cloud idx under one augmentation draw (flips, rot = rotz(angle)), without its point cloud.
+        scale: (sx, sy, sz) of the sample's extension row — the vertices follow the points."""
         ds = self.ds
         wf_vertices, cen, md = self._normalised_vertices(idx)
         if ds.augment:
             wf_vertices[:, 0] *= fx
             wf_vertices[:, 1] *= fy
             wf_vertices[:, 0:3] = np.dot(wf_vertices[:, 0:3], np.transpose(rot))
+        if scale is not None:
+            wf_vertices[:, 0:3] *= np.asarray(scale, dtype=np.float64)
         it = ds._finish(np.empty((0, self.ncol)), wf_vertices, self.wireframes[idx][1], cen, md, ds.pc_files[idx])
         del it["point_clouds"]
         return it
 
-    def batch(self, indices, sampler="numpy"):
+    def batch(self, indices, sampler="numpy", augment=None):
         """collate_batch([dataset[i] for i in indices]) with `point_clouds` [B, num_points, C] on the device.
         sampler="numpy": the rows are np.random.choice draws in the reference's order, so a seeded run reproduces the
         reference's batches.  sampler="device": the rows are chosen in the kernel (wf3d_cloud_sample_dev,
@@ -364,11 +373,18 @@ class DeviceCloudCache:
         augmentation draws only (per sample flip-x, flip-y, angle), NO choice draws.  Every other key is the same.
         sampler="fps": as "device", with the rows by farthest-point sampling (wf3d_cloud_sample_fps,
         wf3d.sampling.fps_indices on the cloud's normalised xyz; the seed word picks the start row only), and one more
-        key, `point_indices` (int32 [B, num_points] on the device): the rows taken."""
-        from wf3d import _lib
+        key, `point_indices` (int32 [B, num_points] on the device): the rows taken.
+        augment=cfg (sampler "device" or "fps" only): the extension of sampled_buffers for one batch — np.random sees, after
+        the batch's draws above, per sample the scale value(s) and the dropout ratio (wf3d.sampling.ext_draws); the
+        host-side wireframe fields are scaled like the points, and one more key, `aug_ext` (float64 [B, 8] on the device)."""
+        from wf3d import _lib, sampling
         from wf3d.ops import _stream
         if sampler not in SAMPLERS:
             raise ValueError(f"DeviceCloudCache.batch: sampler must be 'numpy' or 'device', or 'fps' (got {sampler!r})")
+        cfg = sampling.check_augment(augment)
+        if cfg is not None and sampler == "numpy":
+            raise ValueError("DeviceCloudCache.batch: augment= needs sampler='device' or 'fps' (jitter and dropout are keyed by "
+                             "the device sampler's seed words, which sampler='numpy' does not have)")
         if not self.ds.num_points:
             raise ValueError("DeviceCloudCache needs dataset.num_points (fixed-size batches)")
         ds, P = self.ds, self.ds.num_points
@@ -380,7 +396,7 @@ class DeviceCloudCache:
             raise IndexError(f"DeviceCloudCache.batch: index out of range for {len(self.n)} clouds")
         B = len(indices)
         if sampler != "numpy":
-            return self._batch_sampled(indices, P, sampler)
+            return self._batch_sampled(indices, P, sampler, cfg)
         choice = np.empty((B, P), dtype=np.int32)
         aug = np.empty((B, 4), dtype=np.float64)
         items = []
@@ -401,7 +417,17 @@ class DeviceCloudCache:
         out["point_clouds"] = pcs
         return out
 
-    def _batch_sampled(self, indices, P, sampler):
+    @staticmethod
+    def _draw_ext(cfg, B):
+        """float64 [B, 8]: the extension rows of a host-staged batch from np.random — per sample, in order, the scale
+        value(s) (1, or 3 when anisotropic) and the dropout ratio, each drawn only where that part is configured
+        (wf3d.sampling.ext_draws), the values one np.random.random() each would give, into wf3d.sampling.ext_rows"""
+        from wf3d import sampling
+        n_scale, n_drop = sampling.ext_draws(cfg)
+        u = np.random.random((B, n_scale + n_drop))                # row-major: sample by sample, in the order above
+        return sampling.ext_rows(cfg, u[:, :n_scale], u[:, n_scale] if n_drop else None)
+
+    def _batch_sampled(self, indices, P, sampler, cfg=None):
         """batch(..., sampler="device" or "fps") behind its index checks"""
         ds, B = self.ds, len(indices)
         if not 1 <= B <= 4096 or B * P > 0x7FFFFFFF:
@@ -409,17 +435,22 @@ class DeviceCloudCache:
         block = torch.empty(PARAM_BYTES * B + 4, dtype=torch.uint8)
         v_aug, v_cloud, v_first = self._block_views(block, B)
         v_cloud[:], v_first[:] = indices, np.arange(B + 1, dtype=np.int64) * P
-        items = []
+        draws = []
         for b, idx in enumerate(indices):
             fx, fy, angle = ds._draw_augmentation() if ds.augment else (1.0, 1.0, 0.0)
             v_aug[b] = (fx, fy, np.cos(angle), np.sin(angle))
-            items.append(self._item(idx, fx, fy, rotz(angle)))
-        out = ds.collate_batch(items)
+            draws.append((fx, fy, angle))
+        ext = self._draw_ext(cfg, B) if cfg is not None else None           # behind every draw the batch made before
+        out = ds.collate_batch([self._item(idx, fx, fy, rotz(angle), None if ext is None else ext[b, :3])
+                                for b, (idx, (fx, fy, angle)) in enumerate(zip(indices, draws))])
         pcs = torch.empty(B, P, self.ncol, dtype=torch.float32, device=self.device)
         self.last_sample_words = self.sample_generator.draw()
         fps = self._fps_tensors(B, P) if sampler == "fps" else {}
-        self._sample(block.to(self.device), self.last_sample_words, pcs, fps)
+        ext_dev = torch.from_numpy(ext).to(self.device) if ext is not None else None
+        self._sample(block.to(self.device), self.last_sample_words, pcs, fps, ext_dev)
         out["point_clouds"] = pcs
+        if ext_dev is not None:
+            out["aug_ext"] = ext_dev
         if fps:
             out["point_indices"] = fps["point_indices"]
         return out
@@ -434,20 +465,37 @@ class DeviceCloudCache:
             out["fps_workspace"] = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
         return out
 
-    def _sample(self, params, words, points, fps=None):
-        """the sampler's launch: the random sampler, or farthest-point sampling into `fps`' tensors (_fps_tensors)"""
+    def _sample(self, params, words, points, fps=None, ext=None):
+        """the sampler's launch: the random sampler, or farthest-point sampling into `fps`' tensors (_fps_tensors); with
+        an extension block `ext` (float64 [B, 8] on the device) the `_ext` entry point of either"""
         from wf3d import _lib
         from wf3d.ops import _stream
+        lib = _lib.load()
         B, P = points.shape[0], points.shape[1]
+        more = () if ext is None else (ext.data_ptr(),)
         if fps:
             ws = fps.get("fps_workspace")
-            _lib.check(_lib.load().wf3d_cloud_sample_fps(
+            _lib.check((lib.wf3d_cloud_sample_fps if ext is None else lib.wf3d_cloud_sample_fps_ext)(
                 self.norm.data_ptr(), self.first.data_ptr(), len(self.n), params.data_ptr(), words.data_ptr(), B, P, self.ncol,
                 points.data_ptr(), fps["point_indices"].data_ptr(), max(self.n), ws.data_ptr() if ws is not None else None,
-                ws.numel() if ws is not None else 0, _stream()), "cloud_sample_fps")
+                ws.numel() if ws is not None else 0, *more, _stream()), "cloud_sample_fps")
             return
-        _lib.check(_lib.load().wf3d_cloud_sample_dev(self.norm.data_ptr(), self.first.data_ptr(), len(self.n), params.data_ptr(),
-                                                     words.data_ptr(), B, P, self.ncol, points.data_ptr(), _stream()), "cloud_sample_dev")
+        _lib.check((lib.wf3d_cloud_sample_dev if ext is None else lib.wf3d_cloud_sample_dev_ext)(
+            self.norm.data_ptr(), self.first.data_ptr(), len(self.n), params.data_ptr(), words.data_ptr(), B, P, self.ncol,
+            points.data_ptr(), *more, _stream()), "cloud_sample_dev")
+
+    def _targets(self, buffers):
+        """the targets' launch from the buffers' parameter block; the vertices follow the extension block's scale"""
+        from wf3d import _lib
+        from wf3d.ops import _stream
+        lib = _lib.load()
+        ext = buffers.get("aug_ext")
+        B, V = buffers["vertices"].shape[0], buffers["vertices"].shape[1]
+        _lib.check((lib.wf3d_wireframe_targets if ext is None else lib.wf3d_wireframe_targets_ext)(
+            self.wf_vertices.data_ptr(), self.wf_edges.data_ptr(), self.vfirst.data_ptr(), self.efirst.data_ptr(), len(self.n),
+            buffers["params"].data_ptr(), B, V, buffers["vertices"].data_ptr(), buffers["vertex_existence"].data_ptr(),
+            buffers["vertex_counts"].data_ptr(), buffers["edge_labels"].data_ptr(), *(() if ext is None else (ext.data_ptr(),)),
+            _stream()), "wireframe_targets")
 
     # ---- packed batches: whole clouds, one after the other ----------------------------------------------------------
     def _plan(self, indices, who, capacity=None, max_vertices=None, num_points=None):
@@ -467,9 +515,18 @@ class DeviceCloudCache:
         _lib.check(_lib.load().wf3d_cloud_pack(self.norm.data_ptr(), self.first.data_ptr(), len(self.n), params.data_ptr(), B,
                                                rows, self.ncol, points.data_ptr(), point_counts.data_ptr(), _stream()), "cloud_pack")
 
-    def packed_batch(self, indices):
+    @staticmethod
+    def _refuse_packed_augment(who, augment):
+        from wf3d import sampling
+        if sampling.check_augment(augment) is not None:
+            raise ValueError(f"DeviceCloudCache.{who}: augment= is for fixed-size sampled batches only (sampled_buffers, "
+                             "batch(sampler='device' | 'fps')): whole-cloud batches have no seed words under stage / fill")
+
+    def packed_batch(self, indices, augment=None):
         """collate_packed([ds0[i] for i in indices]), ds0 = the data set with num_points = 0, with `point_clouds`
-        [sum n_b, C] on the device; np.random is consumed as those __getitem__ calls consume it."""
+        [sum n_b, C] on the device; np.random is consumed as those __getitem__ calls consume it.  augment=: refused
+        (ValueError), the extension is the sampled forms'."""
+        self._refuse_packed_augment("packed_batch", augment)
         indices, out_first, aug = self._plan(indices, "packed_batch")
         B, rows = len(indices), int(out_first[-1])
         items = [self._item(idx, fx, fy, np.array([[c, -s, 0], [s, c, 0], [0, 0, 1]])) for idx, (fx, fy, c, s) in zip(indices, aug)]
@@ -484,10 +541,12 @@ class DeviceCloudCache:
         out["point_counts"] = torch.tensor([self.n[i] for i in indices], dtype=torch.int64)
         return out
 
-    def packed_buffers(self, B, capacity, max_vertices):
+    def packed_buffers(self, B, capacity, max_vertices, augment=None):
         """Static device tensors of a captured step for batches of B whole clouds: `points` [capacity, C],
         `point_counts` int64 [B], train_targets' `vertices` / `vertex_existence` / `edge_labels` (full width) /
-        `vertex_counts`, the parameter block `params` (uint8 [40 B + 4]) and its pinned host mirror `params_host`."""
+        `vertex_counts`, the parameter block `params` (uint8 [40 B + 4]) and its pinned host mirror `params_host`.
+        augment=: refused (ValueError), the extension is the sampled forms'."""
+        self._refuse_packed_augment("packed_buffers", augment)
         from wf3d.ops import check_capacity
         capacity = check_capacity(capacity)
         B, V = operator.index(B), operator.index(max_vertices)
@@ -505,17 +564,24 @@ class DeviceCloudCache:
                 "params_host": torch.zeros(PARAM_BYTES * B + 4, dtype=torch.uint8).pin_memory(),
                 "params_copied": torch.cuda.Event()}
 
-    def sampled_buffers(self, B, max_vertices, num_points=None, sampler="device"):
+    def sampled_buffers(self, B, max_vertices, num_points=None, sampler="device", augment=None):
         """Static device tensors of a captured step for FIXED-SIZE batches sampled on the device: `points`
         [B, P, C] (P = num_points or the data set's; the dense forward takes it as it is), train_targets' `vertices` /
         `vertex_existence` / `edge_labels` (full width) / `vertex_counts`, the parameter block `params` with its pinned
         mirror `params_host`, and `sample_words` (int32 [5]: the seed words `fill` draws, word 0 is the batch's).
         sampler="fps": the rows by farthest-point sampling (wf3d_cloud_sample_fps, wf3d.sampling.fps_indices) — the same
         buffers plus "sampler": "fps", `point_indices` (int32 [B, P]: the rows taken) and, when a resident cloud is
-        longer than FPS_REG_ROWS, `fps_workspace`; stage / fill / fill_epoch dispatch on that key."""
+        longer than FPS_REG_ROWS, `fps_workspace`; stage / fill / fill_epoch dispatch on that key.
+        augment=cfg (wf3d.sampling.check_augment; None or {}: nothing): a random scale, per-point jitter and random point
+        dropout inside the sampler's launch, the vertices scaled with the points — three more entries, `augment` (the
+        checked dict), `aug_ext` (float64 [B, 8] on the device: the extension block, identity rows at first) and
+        `aug_ext_host` (its pinned mirror); stage / fill / fill_epoch dispatch on `aug_ext`.  Independent of the data
+        set's `augment` (flips and rotation)."""
+        from wf3d import sampling
         if sampler not in SAMPLERS[1:]:
             raise ValueError(f"DeviceCloudCache.sampled_buffers: sampler must be 'device' or 'fps' ('numpy' draws on the host: "
                              f"batch()) (got {sampler!r})")
+        cfg = sampling.check_augment(augment)
         B, V = operator.index(B), operator.index(max_vertices)
         P = operator.index(num_points or self.ds.num_points or 0)
         if P < 1:
@@ -526,6 +592,9 @@ class DeviceCloudCache:
         dev = self.device
         f32 = dict(dtype=torch.float32, device=dev)
         fps = dict(self._fps_tensors(B, P), sampler="fps") if sampler == "fps" else {}
+        if cfg is not None:
+            identity = torch.tensor(sampling.EXT_IDENTITY, dtype=torch.float64).repeat(B, 1)
+            fps.update(augment=cfg, aug_ext=identity.to(dev), aug_ext_host=identity.clone().pin_memory())
         return {"points": torch.zeros(B, P, self.ncol, **f32),
                 "vertices": torch.zeros(B, V, 3, **f32),
                 "vertex_existence": torch.zeros(B, V, **f32),
@@ -542,7 +611,11 @@ class DeviceCloudCache:
         block.  Returns the batch's host-side fields `scan_idx`, `centroid`, `max_distance` as collate_batch builds them.
         `buffers` from packed_buffers or from sampled_buffers: the same checks (without the row capacity, which a
         fixed-size batch does not have) and the same draws in the same order — per sample flip-x, flip-y, angle.  The
-        sampled form draws NO np.random.choice: it leaves np.random elsewhere than batch() does."""
+        sampled form draws NO np.random.choice: it leaves np.random elsewhere than batch() does.
+        Buffers with an extension (`aug_ext`): behind the batch's draws above, per sample and in order, the scale
+        value(s) (1, or 3 when anisotropic; none when scale is (1, 1)) and the dropout ratio (none when max_dropout is 0),
+        each one np.random.random() (wf3d.sampling.ext_row); the mirror `aug_ext_host` goes up by a second non-blocking
+        copy in front of the same event.  Without one np.random is consumed exactly as before."""
         sampled = "sample_words" in buffers
         B = buffers["vertices"].shape[0]
         if len(indices) != B:
@@ -555,6 +628,9 @@ class DeviceCloudCache:
         v_aug, v_cloud, v_first = self._block_views(buffers["params_host"], B)
         v_aug[:], v_cloud[:], v_first[:] = aug, indices, out_first
         buffers["params"].copy_(buffers["params_host"], non_blocking=True)
+        if "aug_ext" in buffers:
+            buffers["aug_ext_host"].numpy()[:] = self._draw_ext(buffers["augment"], B)
+            buffers["aug_ext"].copy_(buffers["aug_ext_host"], non_blocking=True)
         buffers["params_copied"].record()
         ds = self.ds
         info = {"scan_idx": torch.tensor(np.array([np.array(os.path.splitext(os.path.basename(ds.pc_files[i]))[0]).astype(np.int64)
@@ -568,19 +644,15 @@ class DeviceCloudCache:
         """The two launches that fill `buffers` from the staged parameter block: every element of `points`, `point_counts`
         and the four target tensors is written.  Capturable: everything the kernels read is in device memory.
         Sampled buffers take three: a draw of `sample_generator` into `sample_words`, the sampler (every element of
-        `points`), the targets — so every replay of a capture samples afresh."""
-        from wf3d import _lib
-        from wf3d.ops import _stream
-        B, V = buffers["vertices"].shape[0], buffers["vertices"].shape[1]
+        `points`), the targets — so every replay of a capture samples afresh.  Buffers with an extension (`aug_ext`): the
+        same launches through the `_ext` entry points, which read the staged extension block."""
+        B = buffers["vertices"].shape[0]
         if "sample_words" in buffers:
             self._sample(buffers["params"], self.sample_generator.draw(out=buffers["sample_words"]), buffers["points"],
-                         buffers if buffers.get("sampler") == "fps" else None)
+                         buffers if buffers.get("sampler") == "fps" else None, buffers.get("aug_ext"))
         else:
             self._pack(buffers["params"], B, buffers["points"].shape[0], buffers["points"], buffers["point_counts"])
-        _lib.check(_lib.load().wf3d_wireframe_targets(
-            self.wf_vertices.data_ptr(), self.wf_edges.data_ptr(), self.vfirst.data_ptr(), self.efirst.data_ptr(), len(self.n),
-            buffers["params"].data_ptr(), B, V, buffers["vertices"].data_ptr(), buffers["vertex_existence"].data_ptr(),
-            buffers["vertex_counts"].data_ptr(), buffers["edge_labels"].data_ptr(), _stream()), "wireframe_targets")
+        self._targets(buffers)
 
     # ---- resident epochs: the batch order, the rank shards and the augmentation drawn on the device ---------------------
     def epoch_sampler(self, B, members=None, world=1, rank=0, seed=None):
@@ -617,8 +689,11 @@ class DeviceCloudCache:
         replay advances to the next batch: no np.random draw, no pinned mirror, no copy.  The first call for a (buffers,
         sampler) pair checks, once and before any launch, what stage() checks per batch: every member is a resident cloud
         (IndexError), max_vertices holds the largest member wireframe and, for packed buffers, the capacity holds the B
-        largest member clouds (ValueError) — so no batch can break the block's rules."""
-        from wf3d import _lib
+        largest member clouds (ValueError) — so no batch can break the block's rules.
+        Buffers with an extension (`aug_ext`): the same three launches through the `_ext` entry points — the first also
+        writes the extension block from the buffers' `augment` (wf3d.sampling.epoch_augment_ext: scale and dropout ratio
+        per (epoch, global slot), world-size invariant; jitter and the dropped rows per (step, rank))."""
+        from wf3d import _lib, sampling
         from wf3d.ops import _stream
         sampled = "sample_words" in buffers
         B, V = buffers["vertices"].shape[0], buffers["vertices"].shape[1]
@@ -628,18 +703,18 @@ class DeviceCloudCache:
             sampler._checked.add(pair)
         lib = _lib.load()
         words = buffers["sample_words"] if sampled else sampler.seed_words
-        _lib.check(lib.wf3d_cloud_epoch_params(
+        ext = buffers.get("aug_ext")
+        cfg8 = None if ext is None else sampling.augment_cfg8(buffers["augment"])      # host memory, read during the call
+        _lib.check((lib.wf3d_cloud_epoch_params if ext is None else lib.wf3d_cloud_epoch_params_ext)(
             sampler.state.data_ptr(), sampler.members_dev.data_ptr(), len(sampler.members), self.first.data_ptr(), len(self.n), B,
             sampler.world, sampler.rank, buffers["points"].shape[1] if sampled else 0, 1 if self.ds.augment else 0,
-            buffers["params"].data_ptr(), words.data_ptr(), _stream()), "cloud_epoch_params")
+            buffers["params"].data_ptr(), words.data_ptr(), *(() if ext is None else (cfg8.ctypes.data, ext.data_ptr())),
+            _stream()), "cloud_epoch_params")
         if sampled:
-            self._sample(buffers["params"], words, buffers["points"], buffers if buffers.get("sampler") == "fps" else None)
+            self._sample(buffers["params"], words, buffers["points"], buffers if buffers.get("sampler") == "fps" else None, ext)
         else:
             self._pack(buffers["params"], B, buffers["points"].shape[0], buffers["points"], buffers["point_counts"])
-        _lib.check(lib.wf3d_wireframe_targets(
-            self.wf_vertices.data_ptr(), self.wf_edges.data_ptr(), self.vfirst.data_ptr(), self.efirst.data_ptr(), len(self.n),
-            buffers["params"].data_ptr(), B, V, buffers["vertices"].data_ptr(), buffers["vertex_existence"].data_ptr(),
-            buffers["vertex_counts"].data_ptr(), buffers["edge_labels"].data_ptr(), _stream()), "wireframe_targets")
+        self._targets(buffers)
 
 
 def _as_int64(x):
@@ -710,18 +785,21 @@ class EpochSampler:
             raise ValueError(f"EpochSampler.seek: needs epoch >= 0 and 0 <= step < {self.steps_per_epoch} (got {epoch}, {step})")
         self.set_state(torch.tensor([_as_int64(self.key), _as_int64(epoch * self.steps_per_epoch + step)], dtype=torch.int64))
 
-    def batch_at(self, t):
+    def batch_at(self, t, augment_ext=None):
         """Batch number t as the specification gives it, on the host and without a sync: wf3d.sampling.epoch_batch's
-        dict plus `cloud` (int32 [B]: the resident clouds).  A pure function of (key, t)."""
+        dict plus `cloud` (int32 [B]: the resident clouds).  A pure function of (key, t).  augment_ext=cfg (the
+        `augment` of the buffers): also `ext` (float64 [B, 8]), the extension block fill_epoch writes."""
         from wf3d import sampling
-        out = sampling.epoch_batch(self.key, t, len(self.members), self.B, self.world, self.rank, bool(self.cache.ds.augment))
+        out = sampling.epoch_batch(self.key, t, len(self.members), self.B, self.world, self.rank, bool(self.cache.ds.augment),
+                                   augment_ext)
         out["cloud"] = self.members[out["order"]]
         return out
 
-    def block_at(self, t, num_points=0):
+    def block_at(self, t, num_points=0, augment_ext=None):
         """The parameter block of batch t (uint8 [40 B + 4], include/wf3d.h) as the kernel writes it: out_first = b *
-        num_points for the fixed-size form, the clouds' row offsets for the packed form (num_points = 0)."""
-        spec, B, n = self.batch_at(t), self.B, self.cache.n
+        num_points for the fixed-size form, the clouds' row offsets for the packed form (num_points = 0).
+        augment_ext=cfg: the pair (parameter block, extension block float64 [B, 8])."""
+        spec, B, n = self.batch_at(t, augment_ext), self.B, self.cache.n
         block = torch.zeros(PARAM_BYTES * B + 4, dtype=torch.uint8)
         v_aug, v_cloud, v_first = DeviceCloudCache._block_views(block, B)
         v_aug[:], v_cloud[:] = spec["aug"], spec["cloud"]
@@ -730,4 +808,6 @@ class EpochSampler:
         else:
             rows = np.array([n[i] if 0 <= i < len(n) else 0 for i in spec["cloud"]], dtype=np.int64)
             v_first[0], v_first[1:] = 0, (np.cumsum(rows) & 0xFFFFFFFF).astype(np.uint32).view(np.int32)
+        if "ext" in spec:
+            return block, torch.from_numpy(spec["ext"].copy())
         return block

@@ -25,7 +25,8 @@ All arithmetic is modulo 2^32 (the kernel's uint32); the only wide product is th
 1 <= P.  "Uniform" is up to the 2^-32 granularity of the multiply-high (a relative bias below n / 2^32).
 
 Below it, the specification of the epoch sampler (cloud_epoch_params_kernel): `epoch_batch(key, t, D, B, world, rank)`,
-and of farthest-point sampling (cloud_fps_kernel): `fps_indices(seed_word, b, xyz, P)`, the rows by distance.
+and of farthest-point sampling (cloud_fps_kernel): `fps_indices(seed_word, b, xyz, P)`, the rows by distance.  At the
+end, the augmentation extension of the sampled forms (the `_ext` entry points): scale, jitter and point dropout.
 """
 import numpy as np
 
@@ -130,8 +131,11 @@ MAX_EPOCH_BATCH = 4096
 
 def mix64(key, n):
     """uint64 array: the splitmix64 step at position(s) n of key's stream; key and n broadcast (any integers, mod 2^64)."""
-    key = np.asarray([int(k) & _M64 for k in np.atleast_1d(key).tolist()], dtype=np.uint64)
-    n = np.asarray([int(k) & _M64 for k in np.atleast_1d(n).tolist()], dtype=np.uint64)
+    def words(v):
+        if isinstance(v, np.ndarray) and v.dtype.kind in "iu":          # two's complement: the same as & (2^64 - 1)
+            return np.atleast_1d(v).astype(np.uint64)
+        return np.asarray([int(k) & _M64 for k in np.atleast_1d(v).tolist()], dtype=np.uint64)
+    key, n = words(key), words(n)
     with np.errstate(over="ignore"):
         z = key + (n + _u(1)) * _u(0x9E3779B97F4A7C15)
         z = (z ^ (z >> _u(30))) * _u(0xBF58476D1CE4E5B9)
@@ -193,10 +197,11 @@ def epoch_seed_words(key, t, world=1, rank=0):
     return np.array([(s + k * 0x9E3779B9) & 0xFFFFFFFF for k in range(5)], dtype=np.uint32)
 
 
-def epoch_batch(key, t, D, B, world=1, rank=0, augment=True):
+def epoch_batch(key, t, D, B, world=1, rank=0, augment=True, augment_ext=None):
     """Batch number t >= 0 of the sampler keyed `key`: a dict of `epoch`, `step`, `slots` (int64 [B]: the global slots g),
     `order` (int64 [B]: order_e[g], positions in the member table), `aug` (float64 [B, 4]), `angle` (float64 [B]: t_rot)
-    and `seed_words` (uint32 [5])."""
+    and `seed_words` (uint32 [5]); with a configuration `augment_ext` (check_augment) also `ext` (float64 [B, 8]:
+    epoch_augment_ext of the slots)."""
     S = epoch_steps(D, B, world, rank)
     key, t = int(key) & _M64, int(t)
     if not 0 <= t <= _M64:
@@ -204,8 +209,11 @@ def epoch_batch(key, t, D, B, world=1, rank=0, augment=True):
     e, s = divmod(t, S)
     g = s * world * B + rank * B + np.arange(B, dtype=np.int64)
     aug, angle = epoch_augmentation(key, e, g, augment)
-    return {"epoch": e, "step": s, "slots": g, "order": epoch_order(key, e, D)[g], "aug": aug, "angle": angle,
-            "seed_words": epoch_seed_words(key, t, world, rank)}
+    out = {"epoch": e, "step": s, "slots": g, "order": epoch_order(key, e, D)[g], "aug": aug, "angle": angle,
+           "seed_words": epoch_seed_words(key, t, world, rank)}
+    if check_augment(augment_ext) is not None:
+        out["ext"] = epoch_augment_ext(key, e, g, augment_ext)
+    return out
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -269,3 +277,178 @@ def fps_indices(seed_word, b, xyz, P):
         raise ValueError(f"fps_indices: needs 1 <= n < 2^31 and P >= 1 (got n = {n}, P = {P})")
     order = fps_order(xyz, fps_start(seed_word, b, n), min(n, P))
     return order[np.arange(P) % n]
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# The augmentation extension of the sampled forms (csrc/cloud.hip, the `_ext` entry points): a random scale, per-point
+# jitter and random point dropout inside the gather — one launch, float64, one rounding — keyed like everything above.
+# All float64, every operation rounded on its own (no fma).
+#
+#   ext [B, 8] float64 per sample {sx, sy, sz, sigma, clip, drop, 0, 0}: device memory BESIDE the parameter block
+#   K = key 2^32 | key2, (key, key2) = sample_keys(seed_word, b)                       one per (seed word, sample)
+#   dropped(p)   p >= 1 and (mix64(K ^ KEY_DROP, p) >> 11) 2^-53 < drop;  p_eff = 0 if dropped else p
+#   row p        = the row p_eff of the plain form: source index idx(b, p_eff), then (xr, yr, z) by today's flips and
+#                  z-rotation (today's bits), then
+#   g_k          = float64(S_k - 131070) JITTER_C, S_k the sum of the four 16-bit fields of mix64(K ^ KEY_JITTER, 3 p_eff + k)
+#   j_k          = min(max(sigma g_k, -clip), clip)                                    (a NaN sigma or clip gives NaN)
+#   x' = xr sx + j_0, y' = yr sy + j_1, z' = z sz + j_2, rounded to fp32 once; sigma == 0 adds NOTHING (-0.0 keeps its sign)
+#
+# Jitter and dropout are keyed by word 0 of the seed words and the sample's LOCAL position b: like the row choice they
+# are per (step, rank) and NOT world-size invariant.  The scales and the dropout ratio of a resident epoch
+# (epoch_augment_ext) are keyed like the flips by (epoch, global slot) alone and ARE world-size invariant.
+# Farthest-point sampling keeps measuring distance on the unscaled resident coordinates: an anisotropic scale is not an
+# isometry, so the rows it takes are the farthest points of the cloud as it is stored, not as it is emitted.  Accepted.
+# ---------------------------------------------------------------------------------------------------------------------
+KEY_SCALE, KEY_DROPOUT = 0xA54FF53A5F1D36F1, 0x510E527FADE682D1          # per (epoch, global slot): + k for the axes
+KEY_JITTER, KEY_DROP = 0x9B05688C2B3E6C1F, 0x1F83D9ABFB41BD6B            # per (seed word, sample, point)
+JITTER_C = float.fromhex("0x1.bb67ae8584caap-16")                        # the double nearest to sqrt(3) 2^-16
+JITTER_MAX = 131070 * JITTER_C                                           # 3.46405...: every |g| is at most this
+EXT_IDENTITY = (1.0, 1.0, 1.0, 0.0, np.inf, 0.0, 0.0, 0.0)
+_NO_AUGMENT = {"scale": (1.0, 1.0), "anisotropic": False, "jitter_sigma": 0.0, "jitter_clip": np.inf, "max_dropout": 0.0}
+
+
+def check_augment(cfg):
+    """The extension's configuration with every key present (a copy), or ValueError.  Keys, all optional, an absent one
+    the identity: scale (lo, hi) finite with 0 < lo <= hi ((1, 1)); anisotropic (False: one scale for the three axes);
+    jitter_sigma >= 0, finite (0); jitter_clip > 0, finite or inf (inf: no clip); max_dropout in [0, 1] (0).  None and {}
+    mean no extension at all and return None."""
+    if cfg is None or (isinstance(cfg, dict) and not cfg):
+        return None
+    if not isinstance(cfg, dict):
+        raise ValueError(f"augment: must be a dict or None, got {type(cfg).__name__}")
+    unknown = set(cfg) - set(_NO_AUGMENT)
+    if unknown:
+        raise ValueError(f"augment: unknown keys {sorted(unknown)} (known: {sorted(_NO_AUGMENT)})")
+    c = dict(_NO_AUGMENT, **cfg)
+    try:
+        lo, hi = (float(v) for v in c["scale"])
+    except (TypeError, ValueError):
+        raise ValueError(f"augment: scale must be a pair (lo, hi), got {c['scale']!r}") from None
+    if not (np.isfinite(lo) and np.isfinite(hi) and 0.0 < lo <= hi):
+        raise ValueError(f"augment: scale needs finite 0 < lo <= hi, got ({lo}, {hi})")
+    c["scale"] = (lo, hi)
+    if not isinstance(c["anisotropic"], (bool, np.bool_)):
+        raise ValueError(f"augment: anisotropic must be a bool, got {c['anisotropic']!r}")
+    c["anisotropic"] = bool(c["anisotropic"])
+    for key in ("jitter_sigma", "jitter_clip", "max_dropout"):
+        if isinstance(c[key], (bool, np.bool_)):
+            raise ValueError(f"augment: {key} must be a number, got {c[key]!r}")
+        try:
+            c[key] = float(c[key])
+        except (TypeError, ValueError):
+            raise ValueError(f"augment: {key} must be a number, got {c[key]!r}") from None
+    if not (np.isfinite(c["jitter_sigma"]) and c["jitter_sigma"] >= 0.0):
+        raise ValueError(f"augment: jitter_sigma must be finite and >= 0, got {c['jitter_sigma']}")
+    if not c["jitter_clip"] > 0.0:
+        raise ValueError(f"augment: jitter_clip must be > 0 (inf: no clip), got {c['jitter_clip']}")
+    if not 0.0 <= c["max_dropout"] <= 1.0:
+        raise ValueError(f"augment: max_dropout must be in [0, 1], got {c['max_dropout']}")
+    return c
+
+
+def augment_cfg8(cfg):
+    """float64 [8] {lo, hi, anisotropic, sigma, clip, max_dropout, 0, 0}: what wf3d_cloud_epoch_params_ext takes (host
+    memory) for a configuration (checked here)."""
+    c = check_augment(cfg) or dict(_NO_AUGMENT)
+    return np.array([c["scale"][0], c["scale"][1], 1.0 if c["anisotropic"] else 0.0, c["jitter_sigma"], c["jitter_clip"],
+                     c["max_dropout"], 0.0, 0.0], dtype=np.float64)
+
+
+def ext_draws(cfg):
+    """(scale values, dropout ratios) one sample of a HOST-staged batch draws from np.random, in this order: 1 scale
+    value (3 when anisotropic) when scale is not (1, 1), then 1 dropout ratio when max_dropout > 0."""
+    c = check_augment(cfg) or dict(_NO_AUGMENT)
+    return (0 if c["scale"] == (1.0, 1.0) else (3 if c["anisotropic"] else 1)), (1 if c["max_dropout"] > 0.0 else 0)
+
+
+def ext_rows(cfg, u_scale, u_drop):
+    """float64 [B, 8]: the extension rows of B samples from uniform draws in [0, 1) — u_scale [B, k], k = 0 (scale (1, 1)
+    stays 1), 1 (one value for the three axes) or 3; u_drop [B] or None (drop = 0): s_k = lo + u_k (hi - lo),
+    drop = u_drop max_dropout, sigma and clip copied."""
+    c = check_augment(cfg) or dict(_NO_AUGMENT)
+    lo, hi = (np.float64(v) for v in c["scale"])
+    u = np.asarray(u_scale, dtype=np.float64)
+    B = u.shape[0]
+    ext = np.zeros((B, 8), dtype=np.float64)
+    ext[:, :3] = lo + u.reshape(B, -1) * (hi - lo) if u.size else 1.0
+    ext[:, 3], ext[:, 4] = c["jitter_sigma"], c["jitter_clip"]
+    if u_drop is not None:
+        ext[:, 5] = np.asarray(u_drop, dtype=np.float64) * np.float64(c["max_dropout"])
+    return ext
+
+
+def ext_row(cfg, u_scale=(), u_drop=None):
+    """float64 [8]: ext_rows for one sample (u_scale of 0, 1 or 3 values, u_drop a value or None)."""
+    return ext_rows(cfg, np.asarray(u_scale, dtype=np.float64).reshape(1, -1), None if u_drop is None else [u_drop])[0]
+
+
+def _point_key(seed_word, b, salt):
+    key, key2 = sample_keys([int(seed_word) & 0xFFFFFFFF], b)
+    return ((int(key[0]) << 32) | int(key2[0])) ^ salt
+
+
+def jitter_noise(seed_word, b, p):
+    """float64 [len(p), 3] (or [3] for a scalar p): g of output row(s) p of sample b under `seed_word` — Irwin-Hall of four
+    16-bit fields, centred and scaled: mean 0, variance 1 - 2^-32, |g| <= JITTER_MAX = 3.46405, excess kurtosis -0.3; no
+    transcendental.  Per (seed word, LOCAL sample position, point): not world-size invariant."""
+    pp = np.atleast_1d(np.asarray(p, dtype=np.int64))
+    K = _point_key(seed_word, b, KEY_JITTER)
+    ctr = (3 * pp[:, None] + np.arange(3, dtype=np.int64)[None, :]).reshape(-1)
+    z = mix64(K, ctr)
+    f = _u(0xFFFF)
+    S = ((z & f) + ((z >> _u(16)) & f) + ((z >> _u(32)) & f) + (z >> _u(48))).astype(np.int64) - 131070
+    g = (S.astype(np.float64) * JITTER_C).reshape(-1, 3)
+    return g[0] if np.ndim(p) == 0 else g
+
+
+def dropped(seed_word, b, p, drop):
+    """bool [len(p)] (or a bool for a scalar p): output row p of sample b is dropped — it becomes an exact copy of output
+    row 0 (PointNet++'s random_point_dropout): p >= 1 and (mix64(K ^ KEY_DROP, p) >> 11) 2^-53 < drop.  Row 0 never is;
+    drop = 0 (or a NaN) drops nothing, drop = 1 every row p >= 1."""
+    pp = np.atleast_1d(np.asarray(p, dtype=np.int64))
+    u = (mix64(_point_key(seed_word, b, KEY_DROP), pp) >> _u(11)).astype(np.float64) * 2.0 ** -53
+    with np.errstate(invalid="ignore"):
+        d = (pp >= 1) & (u < np.float64(drop))
+    return bool(d[0]) if np.ndim(p) == 0 else d
+
+
+def effective_rows(seed_word, b, P, drop):
+    """int64 [P]: p_eff of the P output rows of sample b — 0 for a dropped row, else p.  Everything behind (the source
+    index idx(b, p_eff), the noise jitter_noise(., b, p_eff)) uses p_eff."""
+    p = np.arange(int(P), dtype=np.int64)
+    return np.where(dropped(seed_word, b, p, drop), 0, p)
+
+
+def augment_point(xyz_rot, ext_row, noise):
+    """float32 [..., 3]: (xr, yr, z) float64 — a row's first three columns behind today's flips and z-rotation, with
+    today's bits — under ext_row = {sx, sy, sz, sigma, clip, drop, ..} and noise g [..., 3]:
+    x' = xr sx + j_0, y' = yr sy + j_1, z' = z sz + j_2, j_k = min(max(sigma g_k, -clip), clip), every operation rounded
+    on its own, the result rounded to fp32 once.  sigma == 0 adds nothing (-0.0 keeps its sign).  Columns 3 and up of a
+    row are not the extension's."""
+    e = np.asarray(ext_row, dtype=np.float64)
+    v = np.asarray(xyz_rot, dtype=np.float64)
+    with np.errstate(invalid="ignore", over="ignore"):
+        out = v * e[:3]
+        if e[3] != 0.0:
+            j = e[3] * np.asarray(noise, dtype=np.float64)
+            out = out + np.minimum(np.maximum(j, -e[4]), e[4])
+        return out.astype(np.float32)
+
+
+def epoch_augment_ext(key, e, g, cfg):
+    """float64 [len(g), 8]: the extension rows of the global slots g of epoch e, keyed like the flips by c = e 2^32 + g
+    alone — world-size invariant: u_k = (mix64(key ^ (KEY_SCALE + k), c) >> 11) 2^-53, s_k = lo + u_k (hi - lo), k = 0, 1,
+    2 when anisotropic, else k = 0 for the three axes; drop = u_d max_dropout from KEY_DROPOUT; sigma and clip copied."""
+    cfg8 = augment_cfg8(cfg)
+    lo, hi, aniso, sigma, clip, maxdrop = cfg8[:6]
+    g = np.atleast_1d(np.asarray(g, dtype=np.int64))
+    c = [((int(e) << 32) + int(k)) & _M64 for k in g]
+    ext = np.zeros((g.size, 8), dtype=np.float64)
+
+    def unit(salt):
+        return (mix64(int(key) ^ (salt & _M64), c) >> _u(11)).astype(np.float64) * 2.0 ** -53
+    for k in range(3):
+        ext[:, k] = lo + unit(KEY_SCALE + (k if aniso else 0)) * (hi - lo)
+    ext[:, 3], ext[:, 4] = sigma, clip
+    ext[:, 5] = unit(KEY_DROPOUT) * maxdrop
+    return ext
