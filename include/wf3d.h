@@ -154,6 +154,27 @@ int wf3d_gemm_bf16(const void* A_sx8, const void* B_sx8, float* C, const float* 
                    int lda, int ldb, int ldc, int accumulate, void* ws, size_t ws_bytes, void* stream);
 int wf3d_gemm_bf16_tn(const void* A_sx8, const void* B_sx8, float* C, int Mo, int No, int K, int lda, int ldb,
                       int ldc, int accumulate, void* ws, size_t ws_bytes, void* stream);
+/* Which kernel a wf3d_gemm_split / wf3d_gemm_bf16 call (wf3d_gemm_split_tn / wf3d_gemm_bf16_tn: the _tn query) with
+ * these arguments takes, under the options in force: the launch path decides through the same host function.  Nothing is
+ * launched and nothing is written but route[0..7]: kernel form (WF3D_SPLIT_FORM_*), K ranges after the workspace fit, K
+ * slices per range, 1 if the wgrad grid is the XCD-mapped 1-D one, combine kind (WF3D_SPLIT_COMBINE_*), tile rows,
+ * tile columns, workgroups of the persistent kernel (0 for every other form).  C, bias and ws are looked at as
+ * addresses only (alignment, NULL).  cus: the device's compute-unit count; 0 asks the current device, any other value
+ * needs no device.  Returns WF3D_OK, or what the call itself returns for dimensions it refuses (and WF3D_ERR_ARG for an
+ * empty output, which a call accepts and no kernel serves). */
+#define WF3D_SPLIT_FORM_REGS 0    /* register-staged 128x128 (K % 32 != 0, or split_kernel 1) */
+#define WF3D_SPLIT_FORM_DMA3 1    /* 256x128, three LDS stages */
+#define WF3D_SPLIT_FORM_X16 2     /* 256x256 on the 16x16x32 MFMA, one workgroup per tile */
+#define WF3D_SPLIT_FORM_X16P 3    /* its persistent, tile-claiming form */
+#define WF3D_SPLIT_FORM_DMA3_TN 4 /* wgrad, 256x128 */
+#define WF3D_SPLIT_FORM_X16_TN 5  /* wgrad, 256x256 */
+#define WF3D_SPLIT_COMBINE_NONE 0
+#define WF3D_SPLIT_COMBINE_NARROW 1 /* slab after slab */
+#define WF3D_SPLIT_COMBINE_WIDE 2   /* 16 strided partial sums per output (more than 16 slabs, N % 4 == 0) */
+int wf3d_gemm_split_route(int M, int N, int K, int lda, int ldb, int ldc, const void* C, const void* bias, int accumulate,
+                          const void* ws, size_t ws_bytes, int cus, int* route);
+int wf3d_gemm_split_tn_route(int Mo, int No, int K, int lda, int ldb, int ldc, int accumulate, const void* ws,
+                             size_t ws_bytes, int* route);
 /* out_sx8[r, c] = split(in[r*row_stride + c*col_stride])  (col_stride 1: convert;
  * row_stride 1: transpose-convert, used for W^T) */
 int wf3d_split_rows(const float* in, long row_stride, long col_stride, int R, int C, void* out_sx8, void* stream);

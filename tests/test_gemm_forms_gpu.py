@@ -15,8 +15,6 @@ and on both: the poisoned gap columns N..ldc-1 and rows past M keep their bits, 
 split-K case submitted without a workspace (ws = NULL, or one byte short) runs as one K range — bit-equal on exact data,
 inside the bound on general data.  Outputs start as NaN poison, so a tile the XCD remap never visits shows.
 """
-import contextlib
-
 import numpy as np
 import pytest
 import torch
@@ -25,8 +23,9 @@ pytestmark = pytest.mark.gpu
 
 import helpers as H  # noqa: E402,F401  (sets sys.path)
 import gemm_cases as G  # noqa: E402
+import gemm_gpu_util as U  # noqa: E402
 
-POISON = 0x7FC0BEEF          # a quiet NaN with a payload: an untouched word is recognisable bit for bit
+POISON, dev, _poisoned, _place, _place1, workspace = U.POISON, U.dev, U.poisoned, U.place, U.place1, U.workspace
 NAMES = [c.name for c in G.CASES]
 
 
@@ -35,31 +34,6 @@ def ops():
     from wf3d import ops as o
     o._lib.load()
     return o
-
-
-def dev():
-    return torch.device("cuda:0")
-
-
-def _poisoned(n):
-    return torch.full((n,), POISON, dtype=torch.int32, device=dev()).view(torch.float32)
-
-
-def _place(arr, pad=0, off=0):
-    """A 2-D array as a device view with `pad` extra (poisoned) columns per row, `off` floats past an aligned base."""
-    rows, cols = arr.shape
-    ld = cols + pad
-    buf = _poisoned(off + rows * ld + 4)
-    v = buf[off:off + rows * ld].view(rows, ld)[:, :cols]
-    v.copy_(torch.from_numpy(arr))
-    return v
-
-
-def _place1(arr, off=0):
-    buf = _poisoned(off + arr.shape[0] + 4)
-    v = buf[off:off + arr.shape[0]]
-    v.copy_(torch.from_numpy(arr))
-    return v
 
 
 class Staged:
@@ -79,25 +53,6 @@ class Staged:
                  for k in ("mu", "rs", "gamma", "beta")}
             p, seed = inp.get("drop", (0.0, 0))
             self.pro = (c.pro.act, t["mu"], t["rs"], t["gamma"], t["beta"], p, seed)
-
-
-@contextlib.contextmanager
-def workspace(ops, mode):
-    """mode None: the wrapper's own workspace; "null": none at all; "short": one byte less than wf3d_gemm_ws_bytes asks for."""
-    if mode is None:
-        yield
-        return
-    real = ops.scratch
-
-    def scratch(nbytes, device, slot=0):
-        if mode == "null" or nbytes <= 0:
-            return None
-        return real(nbytes, device, slot)[:nbytes - 1]
-    ops.scratch = scratch
-    try:
-        yield
-    finally:
-        ops.scratch = real
 
 
 def run(ops, st, ws=None, accumulate=None):
@@ -126,26 +81,11 @@ def where(case, r, i, j):
 
 
 def assert_equal(case, r, got, want, what):
-    if torch.equal(got, want):
-        return
-    bad = ~((got == want) | (got.isnan() & want.isnan()))
-    idx = bad.nonzero()
-    i, j = (int(v) for v in idx[0])
-    tiles = sorted({(int(a) // r.bm, int(b) // r.bn) for a, b in idx[:4096].tolist()})
-    raise AssertionError(f"{case.name} [{what}]: {idx.shape[0]} of {got.numel()} elements differ; first at {where(case, r, i, j)}: "
-                         f"got {float(got[i, j])!r}, want {float(want[i, j])!r}; tiles touched: {tiles[:12]}")
+    U.assert_equal(case.name, (r.bm, r.bn), lambda i, j: where(case, r, i, j), got, want, what)
 
 
 def assert_bound(case, r, got, ref, S, extra, what):
-    g = got.double().cpu().numpy()
-    lim = G.unit_roundoff_bound(case) * S + extra
-    err = np.abs(g - ref)
-    err = np.where(np.isfinite(err), err, np.inf)
-    ratio = err / np.maximum(lim, 1e-300)
-    i, j = np.unravel_index(int(np.argmax(ratio)), ratio.shape)
-    print(f"{case.name} [{what}]: worst |err| / bound = {ratio[i, j]:.3g}")
-    assert ratio[i, j] <= 1.0, (f"{case.name} [{what}]: |got - ref| = {err[i, j]:.4g} > bound {lim[i, j]:.4g} (S = {S[i, j]:.4g}) at "
-                                f"{where(case, r, i, j)}; {int((ratio > 1).sum())} elements over")
+    U.assert_bound(case.name, lambda i, j: where(case, r, i, j), got, ref, G.unit_roundoff_bound(case) * S + extra, S, what)
 
 
 @pytest.mark.parametrize("name", NAMES)

@@ -947,13 +947,16 @@ SplitK plan_tn(int Mo, int No, int K) {
 
 // The kernel forms and their grids.  DMA3 / X16: one workgroup per tile and K range; X16P: `cus` persistent workgroups;
 // X16_TN under zmap: a 1-D grid of tiles x K ranges (SplitParams::zmap).
-enum class Form { DMA3, X16, X16P, DMA3_TN, X16_TN };
+// REGS is gemm.hip's register-staged kernel (wf3d_gemm_split_regs).  The values are include/wf3d.h's WF3D_SPLIT_FORM_*.
+enum class Form { REGS = WF3D_SPLIT_FORM_REGS, DMA3 = WF3D_SPLIT_FORM_DMA3, X16 = WF3D_SPLIT_FORM_X16, X16P = WF3D_SPLIT_FORM_X16P,
+                  DMA3_TN = WF3D_SPLIT_FORM_DMA3_TN, X16_TN = WF3D_SPLIT_FORM_X16_TN };
 
 template <int NP>
 void launch_form(Form form, const SplitParams& p, int cus, hipStream_t st) {
     const dim3 tiles(p.nbm * p.nbn, 1, p.ksplit), block(512);
     switch (form) {
-    case Form::DMA3:    hipLaunchKernelGGL((gemm_split_dma3_kernel<false, NP>), tiles, block, 0, st, p); break;
+    case Form::REGS:    break;                      // launched by wf3d_gemm_split_regs
+    case Form::DMA3:   hipLaunchKernelGGL((gemm_split_dma3_kernel<false, NP>), tiles, block, 0, st, p); break;
     case Form::X16:     hipLaunchKernelGGL((gemm_split_x16_kernel<false, NP>), tiles, block, 0, st, p); break;
     case Form::X16P:
         if (p.bias) hipLaunchKernelGGL((gemm_split_x16p_kernel<true, NP>), dim3(cus, 1, 1), block, 0, st, p);
@@ -993,6 +996,63 @@ int combine(const SplitParams& p, const int32_t* rows_live, hipStream_t st) {
                                 rows_live}, false, st);
 }
 
+// The host decisions of one call: the kernel form and its parameter block (tile grid, split-K plan fitted to the
+// workspace, zmap), the persistent kernel's workgroup count and the combine that follows.  The launch paths below and the
+// route queries (wf3d_gemm_split_route / wf3d_gemm_split_tn_route) both get them here, so a query cannot say anything but
+// what a launch does.
+struct Route { Form form; SplitParams p; int cus; int combine; };
+
+// wf3d_splitk_combine's choice (gemm.hip); the register-staged kernel asks for the narrow one
+int combine_kind(Form form, const SplitParams& p, const void* ws) {
+    if (p.ksplit == 1) return WF3D_SPLIT_COMBINE_NONE;
+    return form != Form::REGS && p.ksplit > 16 && p.N % 4 == 0 && (uintptr_t)ws % 16 == 0 ? WF3D_SPLIT_COMBINE_WIDE : WF3D_SPLIT_COMBINE_NARROW;
+}
+
+// cus_hint: the compute-unit count to decide with; 0 = the current device's
+Route route_nt(const void* A_sx8, const void* B_sx8, float* C, const float* bias, int M, int N, int K, int lda, int ldb, int ldc,
+               int accumulate, void* ws, size_t ws_bytes, int cus_hint) {
+    Route r{};
+    const int kernel = g_split_kernel.load(std::memory_order_relaxed);
+    // the LDS-DMA kernels take every K that is a multiple of their 32-wide slice, the register-staged one the rest
+    if (kernel == 1 || K % SBK != 0) {
+        const int ktotal = wf3d_cdiv(K, SBK);
+        const SplitK s = wf3d_splitk_fit(plan_regs(M, N, K), ktotal, M, N, ws, ws_bytes);
+        r.form = Form::REGS;
+        r.p.M = M; r.p.N = N; r.p.K = K;
+        r.p.nbm = wf3d_cdiv(M, 128); r.p.nbn = wf3d_cdiv(N, 128);
+        r.p.ksplit = s.ksplit; r.p.kt_per_split = s.kt_per;
+        r.p.live = wf3d_live_rows();
+    } else {
+        const int variant = split_variant(M, N, kernel);
+        r.p = split_params(A_sx8, B_sx8, C, bias, M, N, K, lda, ldb, ldc, accumulate, variant == 6 ? 256 : 128,
+                           plan_dma(M, N, K, variant), ws, ws_bytes);
+        r.form = variant == 6 ? Form::X16 : Form::DMA3;
+        if (variant == 6) {
+            int cus = cus_hint > 0 ? cus_hint : cu_count();
+            { const int lim = g_gemm_cus.load(std::memory_order_relaxed); if (lim >= 8 && lim < cus) cus = lim / 8 * 8; }
+            if (persistent_ok(r.p, cus, ws, ws_bytes)) { r.form = Form::X16P; r.cus = cus; }
+        }
+    }
+    r.combine = combine_kind(r.form, r.p, ws);
+    return r;
+}
+
+Route route_tn(const void* A_sx8, const void* B_sx8, float* C, int Mo, int No, int K, int lda, int ldb, int ldc, int accumulate,
+               void* ws, size_t ws_bytes) {
+    Route r{};
+    const bool big = tn16(Mo, No);
+    r.form = big ? Form::X16_TN : Form::DMA3_TN;
+    r.p = split_params(A_sx8, B_sx8, C, nullptr, Mo, No, K, lda, ldb, ldc, accumulate, big ? 256 : 128, plan_tn(Mo, No, K), ws, ws_bytes);
+    r.p.zmap = big && r.p.ksplit >= 8 && r.p.ksplit % 8 == 0;
+    r.combine = combine_kind(r.form, r.p, ws);
+    return r;
+}
+
+void report(const Route& r, int* route) {
+    const int v[8] = {(int)r.form, r.p.ksplit, r.p.kt_per_split, r.p.zmap, r.combine, r.p.nbm, r.p.nbn, r.cus};
+    memcpy(route, v, sizeof(v));
+}
+
 // products: 3 = bf16x3 (wf3d_gemm_split), 1 = plain bf16 on the hi planes (wf3d_gemm_bf16).  Same checks, same kernel
 // choice, same split-K plan and workspace either way.
 int gemm_split_impl(const char* fn, int products, const void* A_sx8, const void* B_sx8, float* C, const float* bias, int M,
@@ -1004,30 +1064,17 @@ int gemm_split_impl(const char* fn, int products, const void* A_sx8, const void*
                "%s: K, lda, ldb must be multiples of 8 (sx8 groups)", fn);
     WF3D_CHECK(lda >= K && ldb >= K && ldc >= N, WF3D_ERR_ARG, "%s: leading dimension too small", fn);
     WF3D_CHECK(((uintptr_t)A_sx8 % 16 == 0) && ((uintptr_t)B_sx8 % 16 == 0), WF3D_ERR_ARG, "%s: operands must be 16-byte aligned", fn);
+    const Route r = route_nt(A_sx8, B_sx8, C, bias, M, N, K, lda, ldb, ldc, accumulate, ws, ws_bytes, 0);
     hipStream_t st = (hipStream_t)stream;
-    const int kernel = g_split_kernel.load(std::memory_order_relaxed);
-    // the LDS-DMA kernels take every K that is a multiple of their 32-wide slice, the register-staged one the rest
-    if (kernel == 1 || K % SBK != 0) {
-        const int ktotal = wf3d_cdiv(K, SBK);
-        const SplitK s = wf3d_splitk_fit(plan_regs(M, N, K), ktotal, M, N, ws, ws_bytes);
-        return wf3d_gemm_split_regs(products, A_sx8, B_sx8, C, bias, M, N, K, lda, ldb, ldc, accumulate, s, (float*)ws,
-                                    wf3d_live_rows(), st);
+    if (r.form == Form::REGS)
+        return wf3d_gemm_split_regs(products, A_sx8, B_sx8, C, bias, M, N, K, lda, ldb, ldc, accumulate,
+                                    SplitK{r.p.ksplit, r.p.kt_per_split}, (float*)ws, r.p.live, st);
+    SplitParams p = r.p;
+    if (r.form == Form::X16P) {
+        p.ctl = (unsigned*)ws;
+        if (hipMemsetAsync(ws, 0, 512, st) != hipSuccess) { wf3d_set_error("%s: hipMemsetAsync failed", fn); return WF3D_ERR_LAUNCH; }
     }
-    const int variant = split_variant(M, N, kernel);
-    SplitParams p = split_params(A_sx8, B_sx8, C, bias, M, N, K, lda, ldb, ldc, accumulate, variant == 6 ? 256 : 128,
-                                 plan_dma(M, N, K, variant), ws, ws_bytes);
-    Form form = variant == 6 ? Form::X16 : Form::DMA3;
-    int cus = 0;
-    if (variant == 6) {
-        cus = cu_count();
-        { const int lim = g_gemm_cus.load(std::memory_order_relaxed); if (lim >= 8 && lim < cus) cus = lim / 8 * 8; }
-        if (persistent_ok(p, cus, ws, ws_bytes)) {
-            form = Form::X16P;
-            p.ctl = (unsigned*)ws;
-            if (hipMemsetAsync(ws, 0, 512, st) != hipSuccess) { wf3d_set_error("%s: hipMemsetAsync failed", fn); return WF3D_ERR_LAUNCH; }
-        }
-    }
-    launch(products, form, p, cus, st);
+    launch(products, r.form, p, r.cus, st);
     WF3D_LAUNCH_CHECK();
     return combine(p, p.live, st);
 }
@@ -1039,14 +1086,11 @@ int gemm_split_tn_impl(const char* fn, int products, const void* A_sx8, const vo
     WF3D_CHECK(A_sx8 && B_sx8 && C, WF3D_ERR_ARG, "%s: null operand", fn);
     WF3D_CHECK(lda >= Mo && ldb >= No && ldc >= No, WF3D_ERR_ARG, "%s: leading dimension too small", fn);
     WF3D_CHECK(((uintptr_t)A_sx8 % 16 == 0) && ((uintptr_t)B_sx8 % 16 == 0), WF3D_ERR_ARG, "%s: misaligned operand", fn);
-    const bool big = tn16(Mo, No);
-    SplitParams p = split_params(A_sx8, B_sx8, C, nullptr, Mo, No, K, lda, ldb, ldc, accumulate, big ? 256 : 128,
-                                 plan_tn(Mo, No, K), ws, ws_bytes);
-    p.zmap = big && p.ksplit >= 8 && p.ksplit % 8 == 0;
+    const Route r = route_tn(A_sx8, B_sx8, C, Mo, No, K, lda, ldb, ldc, accumulate, ws, ws_bytes);
     hipStream_t st = (hipStream_t)stream;
-    launch(products, big ? Form::X16_TN : Form::DMA3_TN, p, 0, st);
+    launch(products, r.form, r.p, 0, st);
     WF3D_LAUNCH_CHECK();
-    return combine(p, nullptr, st);
+    return combine(r.p, nullptr, st);
 }
 
 }  // namespace
@@ -1099,6 +1143,29 @@ extern "C" int wf3d_gemm_split(const void* A_sx8, const void* B_sx8, float* C, c
 extern "C" int wf3d_gemm_bf16(const void* A_sx8, const void* B_sx8, float* C, const float* bias, int M, int N, int K,
                               int lda, int ldb, int ldc, int accumulate, void* ws, size_t ws_bytes, void* stream) {
     return gemm_split_impl("wf3d_gemm_bf16", 1, A_sx8, B_sx8, C, bias, M, N, K, lda, ldb, ldc, accumulate, ws, ws_bytes, stream);
+}
+
+extern "C" int wf3d_gemm_split_route(int M, int N, int K, int lda, int ldb, int ldc, const void* C, const void* bias, int accumulate,
+                                     const void* ws, size_t ws_bytes, int cus, int* route) {
+    const char* fn = "wf3d_gemm_split_route";
+    WF3D_CHECK(route != nullptr && cus >= 0, WF3D_ERR_ARG, "%s: null route or negative cus", fn);
+    WF3D_CHECK(M > 0 && N > 0 && K > 0, WF3D_ERR_ARG, "%s: bad dims", fn);
+    WF3D_CHECK(K % 8 == 0 && lda % 8 == 0 && ldb % 8 == 0, WF3D_ERR_UNSUPPORTED,
+               "%s: K, lda, ldb must be multiples of 8 (sx8 groups)", fn);
+    WF3D_CHECK(lda >= K && ldb >= K && ldc >= N, WF3D_ERR_ARG, "%s: leading dimension too small", fn);
+    report(route_nt(nullptr, nullptr, (float*)C, (const float*)bias, M, N, K, lda, ldb, ldc, accumulate, (void*)ws, ws_bytes, cus), route);
+    return WF3D_OK;
+}
+
+extern "C" int wf3d_gemm_split_tn_route(int Mo, int No, int K, int lda, int ldb, int ldc, int accumulate, const void* ws,
+                                        size_t ws_bytes, int* route) {
+    const char* fn = "wf3d_gemm_split_tn_route";
+    WF3D_CHECK(route != nullptr, WF3D_ERR_ARG, "%s: null route", fn);
+    WF3D_CHECK(wf3d_gemm_split_tn_ok(Mo, No, K, lda, ldb), WF3D_ERR_UNSUPPORTED,
+               "%s: needs Mo %% 256 == 0, No %% 128 == 0, K %% 32 == 0 (Mo=%d No=%d K=%d)", fn, Mo, No, K);
+    WF3D_CHECK(lda >= Mo && ldb >= No && ldc >= No, WF3D_ERR_ARG, "%s: leading dimension too small", fn);
+    report(route_tn(nullptr, nullptr, nullptr, Mo, No, K, lda, ldb, ldc, accumulate, (void*)ws, ws_bytes), route);
+    return WF3D_OK;
 }
 
 // C[Mo,No] (+)= A^T·B, A = sx8[K,Mo], B = sx8[K,No]  (Linear wgrad: A = dY, B = X, both as stored)
